@@ -2,6 +2,7 @@
 """bench.py -- RRI sweeps/sec and achieved HBM GB/s of the MI355X path (BASELINE.json's metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5|c5s] [--schedule gram|residual]
+                    [--dump-outputs DIR] [--full]
 
 A step is one RRI sweep (k topic steps = k T-row + k W-column updates, nmf.py:415-476) over a
 synthetic dense fp32 X that is already resident in HBM when the timed region starts.
@@ -22,9 +23,18 @@ Workloads (BASELINE.json configs):
 Prints ONE JSON line on rank 0 (contract in the task description) including
     roofline      the dominant kernel -- algorithmic bytes per launch over its average duration, measured with HIP
                   events on the kernel's stream inside the timed region, against 8 TB/s
+
+A plain run does only what that line needs: set-up, `--warmup` sweeps, the `--steps` timed sweeps, the outputs if
+`--dump-outputs DIR` is given, the line.  `--full` adds everything that takes work of its own after the timed region:
     cpu_baseline  the float64 numpy restatement (oracle/) timed on this box's host cores: c3 at FULL size (every
                   row, `--cpu-sweeps` timed sweeps), the other workloads on the stated sample
-    parity_sample the device path against that CPU run after equal sweeps (same X, same start).
+    parity_sample the device path against that CPU run after equal sweeps (same X, same start)
+    rank1_update, launch_per_phase_schedule, pcie_inclusive   the other kernels / schedules on the same X (plain flavour).
+
+--dump-outputs DIR writes what the timed path computed, W and T after the last timed sweep (rank 0's row block of W when
+row-sharded), as DIR/W.npy and DIR/T.npy in float64.  When they would exceed DUMP_BYTES, W is replaced by a fixed
+seeded sample of its rows: DIR/W_sample.npy and the row indices as DIR/W_sample_rows.npy.  Every input is generated
+from fixed seeds, so two runs with the same arguments see the same X, W0 and T0.
 """
 import argparse
 import hashlib
@@ -56,6 +66,7 @@ PROFILE_ROUND = 'r04'
 # rows of the weighted workloads the CPU oracle runs (one sweep: about a CPU-minute on 16 threads; a full-size sweep of the
 # reference's two n*d*k GEMMs per topic takes five) -- the same slice tests/test_full_size_gpu.py::test_c5_slice_against_the_cpu_oracle asserts
 WEIGHTED_CPU_ROWS = 20000
+DUMP_BYTES = 60 * 1000 * 1000   # --dump-outputs: payload of all files together (below 64 MB with the .npy headers)
 
 
 def parse():
@@ -78,8 +89,17 @@ def parse():
     ap.add_argument('--collective', default='library', choices=['library', 'torch'],
                     help='row-sharded runs: library = RCCL inside librri_hip.so, the all-reduce enqueued by rri_sweep itself '
                          '(default); torch = the caller-owned protocol, torch.distributed per topic step from Python')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write W and T after the last timed sweep to DIR/<name>.npy (float64, a seeded row sample of W '
+                         'beyond DUMP_BYTES)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the measurements beside the headline: CPU baseline, parity against it, the rank-one update '
+                         'kernel, the other schedules, PCIe upload (off: set-up, warm-up, timed steps and the line only)')
     ap.add_argument('--comm-probe', default='', help=argparse.SUPPRESS)    # child mode of probe_library_collective()
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def free_port():
@@ -194,6 +214,23 @@ def device_planted_shard(n_rows, d, k, seed, device):
 def relfro(a, b):
     import numpy as np
     return float(np.linalg.norm(a - b) / np.linalg.norm(b))
+
+
+def dump_outputs(out_dir, W, T):
+    """W (rows x k) and T (k x d) as float64 .npy files; W as a fixed seeded sample of its rows when the two together
+    would exceed DUMP_BYTES"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    W = np.ascontiguousarray(W, dtype=np.float64)
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    np.save(os.path.join(out_dir, 'T.npy'), T)
+    if W.nbytes + T.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, 'W.npy'), W)
+        return
+    rows = (DUMP_BYTES - T.nbytes) // (W.shape[1] * 8 + 8)      # a row of W and its index, both float64
+    idx = np.sort(np.random.RandomState(0).choice(W.shape[0], rows, replace=False))
+    np.save(os.path.join(out_dir, 'W_sample.npy'), W[idx])
+    np.save(os.path.join(out_dir, 'W_sample_rows.npy'), idx.astype(np.float64))
 
 
 def cpu_plain(X_dev, W0, T0, rows, sweeps, threads, n_full, want_factors=True):
@@ -347,7 +384,8 @@ def main():
         t_up = time.perf_counter()
         eng.upload_observed_csr(A)
         t_up = time.perf_counter() - t_up
-        Xs_keep, Ms_keep = X[:WEIGHTED_CPU_ROWS].cpu().numpy().astype(np.float64), Mask[:WEIGHTED_CPU_ROWS].cpu().numpy().astype(np.float64)
+        if args.full:      # the CPU baseline's rows: X and the mask are freed below
+            Xs_keep, Ms_keep = X[:WEIGHTED_CPU_ROWS].cpu().numpy().astype(np.float64), Mask[:WEIGHTED_CPU_ROWS].cpu().numpy().astype(np.float64)
         del X, Mask, A
         torch.cuda.empty_cache()
     else:
@@ -399,6 +437,8 @@ def main():
     launches, pass_ms = eng.timing_read(3 if (weighted or resid_sched) else 0)
     n1, wcol_ms = eng.timing_read(1)
     n2, trow_ms = eng.timing_read(2)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng.get_W(), eng.get_T())
     pass_avg_ms = pass_ms / max(launches, 1)
     # plain: one fused pass reads X once.  weighted: two passes per topic step over (E, M): B reads E and M, C reads
     # E and M and writes E = 5 fp32 arrays with a dense fp32 mask (SURVEY 8d's figure); the 0/1 mask of this workload
@@ -543,7 +583,7 @@ def main():
             pass
 
     thr = int(min(16, os.cpu_count() or 16))       # the box's CPU share for one GPU
-    if rank == 0 and world == 1 and weighted and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and weighted and not args.no_cpu_baseline:
         rows = min(WEIGHTED_CPU_ROWS, n_local)
         if sparse:
             Xs, Ms = Xs_keep[:rows], Ms_keep[:rows]
@@ -583,7 +623,7 @@ def main():
                                              'of 6e-8 to percents in W, T while objective and masked reconstruction M.(WT) agree '
                                              '(tests/test_full_size_gpu.py, DESIGN.md 7)' % (rows, args.storage)}
         out['gpu_over_cpu'] = value / out['cpu_baseline']['value']
-    if rank == 0 and world == 1 and not weighted:
+    if args.full and rank == 0 and world == 1 and not weighted:
         # the explicit rank-one residual update R <- R - a b^T (read + write, fused residual products), with the handle's
         # own factors W[:,0], T[0,:] as a, b (tests/test_residual_gpu.py checks the same kernel against numpy / torch)
         try:
@@ -716,7 +756,7 @@ def main():
                                          'note': 'rri_upload_X of a 10000-row sample from pageable host memory; uploading the whole X once '
                                                  'costs x_upload_ms = %.1f sweeps; never part of `value`' % (bytes_per_launch / (h2d * 1e9) * sweeps_per_s)}
             out['gpu_over_cpu'] = value / out['cpu_baseline']['value'] if out['cpu_baseline']['value'] else None
-    if sharded and world > 1 and not weighted and not args.no_cpu_baseline:
+    if args.full and sharded and world > 1 and not weighted and not args.no_cpu_baseline:
         # N > 1: parity THROUGH the N-rank path and the CPU baseline from ONE host run.  A problem of the workload's own
         # shape (min(n, 100000) x d, same k, same generator) is row-sharded over the same ranks and communicator, two sweeps;
         # rank 0 runs the CPU oracle on ALL its rows (timed: that is the baseline) and compares its block of W and the

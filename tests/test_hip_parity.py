@@ -565,14 +565,14 @@ def test_the_abi_from_plain_c(tmp_path):
 
 
 def test_bench_line_keeps_its_contract():
-    """`python bench.py` prints ONE JSON line with the keys the driver reads, the roofline and cpu_baseline objects
+    """`python bench.py --full` prints ONE JSON line with the keys the driver reads, the roofline and cpu_baseline objects
     included (smallest BASELINE configuration, a few steps)"""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--config', 'c2', '--steps', '3', '--warmup', '1'],
+    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--config', 'c2', '--steps', '3', '--warmup', '1', '--full'],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
@@ -602,6 +602,40 @@ def test_bench_line_keeps_its_contract():
     sc = j['rank1_update']['schedule']
     assert sc['sweeps_per_s'] > 0 and max(sc['vs_default_schedule_after_4_sweeps'].values()) < 1e-4, sc
     assert j['rank1_update']['achieved'] > 0
+
+
+def test_plain_bench_run_is_lean_and_dumps_what_it_computed(tmp_path):
+    """A plain `python bench.py` line carries the headline and nothing that takes work of its own; --dump-outputs writes
+    W and T after the last timed sweep, the same with and without --full (the timed path does not depend on it)"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = {}, {}
+    for mode in ('plain', 'full'):
+        out = tmp_path / mode
+        res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--config', 'c2', '--steps', '3', '--warmup', '1',
+                              '--dump-outputs', str(out)] + (['--full'] if mode == 'full' else []),
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert res.returncode == 0, res.stderr[-2000:]
+        got = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
+        assert len(got) == 1
+        lines[mode] = json.loads(got[0])
+        assert sorted(os.listdir(str(out))) == ['T.npy', 'W.npy']
+        assert sum(os.path.getsize(str(out / f)) for f in os.listdir(str(out))) < 64 * 1000 * 1000
+        dumps[mode] = {f: np.load(str(out / (f + '.npy'))) for f in ('W', 'T')}
+    j = lines['plain']
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'roofline'):
+        assert key in j, key
+    assert j['steps'] == 3 and j['warmup'] == 1 and abs(j['ms_per_step'] * j['value'] - 1e3) < 1e-6 * 1e3
+    for key in ('cpu_baseline', 'parity_sample', 'rank1_update', 'launch_per_phase_schedule', 'pcie_inclusive', 'gpu_over_cpu'):
+        assert key not in j, key
+        assert key not in ('cpu_baseline', 'parity_sample', 'rank1_update') or key in lines['full'], key
+    W, T = dumps['plain']['W'], dumps['plain']['T']
+    assert W.shape == (10000, 20) and T.shape == (20, 1000) and W.dtype == T.dtype == np.float64
+    assert np.isfinite(W).all() and np.isfinite(T).all() and W.min() >= 0 and T.min() >= 0 and (W @ T).max() > 0
+    assert relfro(W, dumps['full']['W']) < TOL[np.float32] and relfro(T, dumps['full']['T']) < TOL[np.float32]
 
 
 @pytest.mark.parametrize('shape', [(700, 333, 6), (257, 1030, 5), (1501, 100, 3), (5003, 1000, 22), (64, 4100, 2), (9, 7, 2), (300, 500, 1)])

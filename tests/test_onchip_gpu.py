@@ -611,7 +611,7 @@ def test_the_objective_the_persistent_sweep_leaves_behind(monkeypatch, flags):
 
 @pytest.mark.parametrize('case', ['plain, the rule ends the run', 'plain, never stops', 'topic-model flags', 'regularised',
                                   'reset events inside a chunk', 'max_iter = 3'])
-def test_nmf_runs_the_sweep_objective_stop_loop_on_the_device_in_chunks(monkeypatch, case):
+def test_nmf_runs_the_sweep_objective_stop_loop_on_the_device_in_chunks(monkeypatch, tmp_path, case):
     """nmf()'s loop -- sweep, objective, stop rule (nmf.py:377-516) -- as rri_sweep_until: the persistent kernel keeps every
     sweep's objective and ends the launch after the first sweep that satisfies optimization.py:284-291.  Against the same call
     sweep by sweep (RRI_NMF_CHUNK=0): the same number of sweeps, the same objectives, the same bits in W and T."""
@@ -639,7 +639,7 @@ def test_nmf_runs_the_sweep_objective_stop_loop_on_the_device_in_chunks(monkeypa
     out = {}
     for chunk in ('1', '0'):
         monkeypatch.setenv('RRI_NMF_CHUNK', chunk)
-        log = '/tmp/onchip_chunk_%s.log' % chunk
+        log = str(tmp_path / ('onchip_chunk_%s.log' % chunk))
         if os.path.exists(log):
             os.remove(log)
         monkeypatch.setenv('RRI_ONCHIP_LOG', log)

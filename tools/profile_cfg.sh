@@ -29,7 +29,7 @@ PY
 python3 tools/pmc_summary.py $out/r04_pmc_hbm_traffic_$tag.json $(dirname $(find /tmp/pf_$tag/FETCH_SIZE -name '*counter_collection.csv' | head -1)) $(dirname $(find /tmp/pf_$tag/WRITE_SIZE -name '*counter_collection.csv' | head -1)) > $out/r04_pmc_hbm_traffic_$tag.txt 2>&1
 cp $out/r04_pmc_hbm_traffic_$tag.json profiles/ 2>/dev/null   # so that the bench line below finds it
 echo "[$tag] bench $(date +%T)" >> $repo/gpurun_out/profile_progress.log
-timeout -k 10 400 python3 bench.py "$@" > /tmp/pf_$tag.json 2>/tmp/pf_$tag.err && tail -1 /tmp/pf_$tag.json > $out/r04_bench_$tag.json
+timeout -k 10 400 python3 bench.py "$@" --full > /tmp/pf_$tag.json 2>/tmp/pf_$tag.err && tail -1 /tmp/pf_$tag.json > $out/r04_bench_$tag.json
 tail -3 /tmp/pf_$tag.FETCH_SIZE.log > $out/r04_${tag}_pmc_fetch_tail.log; tail -3 /tmp/pf_$tag.err >> $out/r04_${tag}_pmc_fetch_tail.log
 echo "[$tag] done $(date +%T)" >> $repo/gpurun_out/profile_progress.log
 head -4 $out/r04_${tag}_rocprofv3_kernel_stats.csv | cut -c1-160

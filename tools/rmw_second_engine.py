@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Does something ELSE alive in the process set the mode of the read-modify-write pass?  bench.py's default run times the
+"""Does something ELSE alive in the process set the mode of the read-modify-write pass?  bench.py --full times the
 explicit-residual schedule while the default schedule's handle is still alive (slow mode there in every line on file), its
 --schedule residual run has one handle (fast in most).  One residual handle, measured: alone | with a second (idle) handle
 alive | with only a second HIP stream alive | with only a 4 GB torch tensor alive | alone again.

@@ -15,4 +15,4 @@ with open(sys.argv[2], 'w', newline='') as out:
     for r in rows[:15]:
         w.writerow([r[0][:110]] + r[1:])
 PY
-python3 bench.py --config $cfg > /tmp/st_$cfg.json 2>/dev/null && tail -1 /tmp/st_$cfg.json > $js
+python3 bench.py --config $cfg --full > /tmp/st_$cfg.json 2>/dev/null && tail -1 /tmp/st_$cfg.json > $js
