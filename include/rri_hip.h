@@ -60,7 +60,8 @@ enum {
 
 enum { RRI_F32 = 0, RRI_F64 = 1 };   /* storage type of X, mask, residual in HBM (arithmetic is float64) */
 /* rri_create's `weighted`: the flavour of the handle */
-enum { RRI_UNWEIGHTED = 0, RRI_WEIGHTED_DENSE = 1, RRI_WEIGHTED_SPARSE = 2, RRI_UNWEIGHTED_RESIDUAL = 3 };
+enum { RRI_UNWEIGHTED = 0, RRI_WEIGHTED_DENSE = 1, RRI_WEIGHTED_SPARSE = 2, RRI_UNWEIGHTED_RESIDUAL = 3,
+       RRI_UNWEIGHTED_SPARSE = 4 };
 enum { RRI_RESET_NONE = 0, RRI_RESET_MAX_RESID_DOCUMENT = 1, RRI_RESET_RANDOM = 2 };
 enum { RRI_EVENT_NONE = 0, RRI_EVENT_RESET_T = 1, RRI_EVENT_RESET_W = 2 };
 
@@ -98,6 +99,13 @@ uint32_t   rri_abi_version(void);
  * topic step is one rank-one residual update pass R <- R -+ v u^T fused with the residual products R t / R^T w of
  * nmf.py:670-676,728-734 (SURVEY 8a "explicit-residual variant"; k >= 2, both halves free), 2 n d bytes per step
  * where the default Gram-form schedule (RRI_UNWEIGHTED) reads X once.  Same results to rounding.
+ * RRI_UNWEIGHTED_SPARSE is the unweighted flavour (the Gram form of RRI_UNWEIGHTED) with X kept as CSR: the topic-model case of
+ * term counts at a few per cent density or less (nmf.py:670-676, 728-734 on a sparse X).  rri_upload_X_csr then keeps the
+ * canonical CSR (8 B of index and value per stored fp32 entry, 12 B fp64) and two blocked copies of it, rows and columns as
+ * segments (6 B per entry each fp32, 10 B fp64, plus a 4-byte position), and no dense n x d array at all; every topic step reads
+ * both copies once (12 nnz bytes fp32) in one launch.  It refuses (RRI_ERR_UNSUPPORTED) rri_upload_X, rri_bind_X_device, every
+ * mask, rri_attach_comm, rri_range_finder and the device preprocessing (rri_column_positive_counts, rri_scale_X; tf-idf /
+ * normalisation of a CSR X belong on the host), never takes the persistent on-chip path, and takes at most 2^31 - 2 entries.
  * device: HIP device ordinal.  stream: hipStream_t to run on, or NULL for an own stream. */
 rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dtype,
                       int32_t weighted, int32_t device, void* stream);
@@ -117,6 +125,8 @@ rri_status rri_bind_mask_device(rri_ctx* ctx, const void* dev, int64_t ld);
 /* Ingestion without host densification (the reference densifies with .toarray(), sklearn_interface.py:78-102):
  * X from host CSR arrays (indptr n+1 int64, indices int32 column ids, data of data_dtype) scattered into the
  * zero-filled dense device X; and the observation mask W_mat = [X != 0] of such a matrix, built bit-packed. */
+/* On an RRI_UNWEIGHTED_SPARSE handle rri_upload_X_csr keeps X as CSR instead (column indices are sorted per row on the host,
+ * duplicates refused, explicit zeros kept): see rri_create. */
 rri_status rri_upload_X_csr(rri_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data,
                             int64_t nnz, int32_t data_dtype);
 rri_status rri_upload_mask_csr_pattern(rri_ctx* ctx, const int64_t* indptr, const int32_t* indices,

@@ -16,6 +16,8 @@ RRI_ERR_INVALID, RRI_ERR_HIP, RRI_ERR_UNSUPPORTED = -1, -2, -3
 RRI_ERR_UNBOUNDED, RRI_ERR_W_COL_ZERO, RRI_ERR_NOT_IMPLEMENTED, RRI_ERR_COMM = -4, -5, -6, -7
 RRI_COMM_ID_BYTES = 128
 RRI_F32, RRI_F64 = 0, 1
+# rri_create's `weighted`: the flavour of the handle
+RRI_UNWEIGHTED, RRI_WEIGHTED_DENSE, RRI_WEIGHTED_SPARSE, RRI_UNWEIGHTED_RESIDUAL, RRI_UNWEIGHTED_SPARSE = 0, 1, 2, 3, 4
 RESET_NONE, RESET_MAX_RESID_DOCUMENT, RESET_RANDOM = 0, 1, 2
 EVENT_NONE, EVENT_RESET_T, EVENT_RESET_W = 0, 1, 2
 ABI_VERSION = 1

@@ -170,6 +170,11 @@ struct rri_ctx {
         int* perm = nullptr;            // position in the canonical CSR
         SpWork* work = nullptr;
     } sp[2];
+    // unweighted flavour with X kept as CSR (RRI_UNWEIGHTED_SPARSE; `sparse` is set too, `weighted` is not): the copies hold X
+    // itself, read by k_spx_pass; spx_work = the items of copy 0 followed by those of copy 1 (SpWork.pad = copy)
+    bool sparse_x = false;
+    SpWork* spx_work = nullptr;
+    double* rowhat = nullptr;   // per-row sum of (W T)_ij^2 over the pattern (the objective's fallback)
     // dense weighted, one read-modify-write pass per topic step: the column sums a pass leaves for the next T row lack the
     // rank-one term of the W update that follows it; k_wmcorr takes that term from the mask alone (Cpart: its partials)
     double* Cpart = nullptr;
@@ -586,6 +591,10 @@ struct LaunchX {
     template <bool DO_Y, bool DO_Z>
     static void pass(rri_ctx* c, int t, int tz, const TgramJob& job = TgramJob{}) {
         TimedScope ts(c, 0);
+        if (c->sparse_x) {    // X on CSR: the read-only pass over its two blocked copies (no side job: the caller runs k_tgram)
+            spx_pass<DO_Y, DO_Z>(c, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw);
+            return;
+        }
         pass_cfg<DO_Y, DO_Z, 0>(c, c->X, c->ldx, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw, Upd{}, job);
     }
     // explicit-residual schedule: the same products over the stored residual R (c->E, stride LD)
@@ -764,6 +773,34 @@ struct LaunchX {
             sp_blk<DO_Z, UPD2, WRITE>(c, 1, a1, a2, wc, b1, b2, c->Zpart, c->Z2part, c->LD);
     }
     // out (nseg x m, row-major, device) = the X on the pattern (which = 0) or its transpose (1) times B (gdim x m)
+    // RRI_UNWEIGHTED_SPARSE: row dots against trow (DO_Y, the row copy, into Ypart) and column sums against wc (DO_Z, the
+    // column copy, into Zpart) in ONE launch over the items of both copies (k_spx_pass)
+    template <bool DO_Y, bool DO_Z>
+    static void spx_pass(rri_ctx* c, const double* trow, const double* wc) {
+        SpxArgs<SX> a{};
+        a.work = c->spx_work;
+        a.first = DO_Y ? 0 : c->sp[0].nwork;
+        for (int w = 0; w < 2; ++w) {
+            const rri_ctx::SpCopy& cp = c->sp[w];
+            a.segptr[w] = cp.segptr; a.idx[w] = cp.idx; a.val[w] = (const SX*)cp.val;
+            a.nseg[w] = cp.nseg; a.gdim[w] = cp.gdim; a.bw[w] = cp.bw; a.lps[w] = cp.lps;
+        }
+        a.F[0] = trow; a.S[0] = c->Ypart; a.lds[0] = c->n;
+        a.F[1] = wc; a.S[1] = c->Zpart; a.lds[1] = c->LD;
+        const int items = (DO_Y ? c->sp[0].nwork : 0) + (DO_Z ? c->sp[1].nwork : 0);
+        if (items < 1) return;
+        const int bwmax = std::max(DO_Y ? c->sp[0].bw : 0, DO_Z ? c->sp[1].bw : 0);
+        hipLaunchKernelGGL((k_spx_pass<SX>), dim3(items), dim3(1024), spx_lds_bytes(bwmax), c->stream, a,
+                           (const DevState*)c->st);
+    }
+    static void spx_xtt(rri_ctx* c, const double* Tm, int m, double* out) {   // out (m x n) = (X Tm^T)^T on the CSR
+        const i64 total = (i64)m * c->d;
+        hipLaunchKernelGGL((k_convert2d<double, double, true>), dim3((unsigned)std::min<i64>(4096, (total + 255) / 256)),
+                           dim3(256), 0, c->stream, Tm, c->LD, c->sp_Tt, (i64)c->kp, (i64)m, c->d);
+        hipLaunchKernelGGL((k_spx_xtt<SX>), dim3((unsigned)((c->n + 3) / 4)), dim3(256), 0, c->stream,
+                           (const i64*)c->sp_rowptr, (const int*)c->sp_col, (const SX*)c->sp_x, c->n,
+                           (const double*)c->sp_Tt, m, c->kp, out, c->ldw);
+    }
     static void sp_spmm(rri_ctx* c, int which, const double* B, int m, double* part, double* out) {
         const rri_ctx::SpCopy& cp = c->sp[which];
         const i64 waves = (i64)cp.nblk * cp.nseg;
@@ -774,14 +811,14 @@ struct LaunchX {
         hipLaunchKernelGGL(k_sp_sum_blocks, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream,
                            (const double*)part, count, cp.nblk, out);
     }
-    static void sp_resid(rri_ctx* c, bool write_e, double* rowobj, double* rowpos) {
+    static void sp_resid(rri_ctx* c, bool write_e, double* rowobj, double* rowpos, double* rowhat = nullptr) {
         const i64 total = (i64)c->k * c->d;
         hipLaunchKernelGGL((k_convert2d<double, double, true>), dim3((unsigned)std::min<i64>(4096, (total + 255) / 256)),
                            dim3(256), 0, c->stream, (const double*)c->T, c->LD, c->sp_Tt, (i64)c->kp, (i64)c->k, c->d);
         hipLaunchKernelGGL((k_sp_resid<SX>), dim3((unsigned)((c->n + 3) / 4)), dim3(256), 4 * (size_t)c->kp * sizeof(double),
                            c->stream, (const i64*)c->sp_rowptr, (const int*)c->sp_col, (const SX*)c->sp_x, c->n,
                            (const double*)c->W, c->ldw, (const double*)c->sp_Tt, c->k, c->kp,
-                           write_e ? (SX*)c->sp_e : (SX*)nullptr, rowobj, rowpos);
+                           write_e ? (SX*)c->sp_e : (SX*)nullptr, rowobj, rowpos, rowhat);
         if (write_e && c->nnz > 0)
             for (int w = 0; w < 2; ++w)
                 hipLaunchKernelGGL((k_sp_permute<SX>), dim3(2048), dim3(256), 0, c->stream, (const SX*)c->sp_e,
@@ -838,7 +875,10 @@ struct LaunchX {
         hipLaunchKernelGGL((k_xtt<SX>), dim3((unsigned)((c->n + 63) / 64)), dim3(256), 0, c->stream, (const SX*)c->X,
                            c->ldx, Tm, c->LD, (int)c->n, (int)c->d, m, out, c->ldw);
     }
-    static void xtt(rri_ctx* c) { xtt_any(c, c->T, c->k, c->Qt); }
+    static void xtt(rri_ctx* c) {
+        if (c->sparse_x) spx_xtt(c, c->T, c->k, c->Qt);
+        else xtt_any(c, c->T, c->k, c->Qt);
+    }
     // column sums against NV = 8 row-vectors at once (Qt: 8 x n, stride ldw): out rows <- X^T q_v
     static void colsums8(rri_ctx* c, const double* Qt, int nv, double* zmulti, double* out_rows) {
         constexpr int NV = 8;
@@ -934,7 +974,7 @@ struct LaunchX {
             e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return e;
         }
-        return e;
+        return hipFuncSetAttribute((const void*)k_spx_pass<SX>, hipFuncAttributeMaxDynamicSharedMemorySize, SP_BLOCK_BYTES + 64);
     }
 };
 
@@ -1219,7 +1259,7 @@ void enqueue_W_half(rri_ctx* c, int sweep, int t) {
     const int finish = (LK::light(c) && !c->prm.fix_T && !c->skip_row_finish) ? 1 : 0;
     c->skip_row_finish = false;
     TgramJob job{};
-    if (c->prm.fix_T || g_side_jobs == 0) {
+    if (c->prm.fix_T || g_side_jobs == 0 || c->sparse_x) {
         TimedScope ts(c, 2);
         LK::tgram(c, t, finish, sweep);
     } else {
@@ -1654,7 +1694,7 @@ void calibrate_rot(rri_ctx* c) {
 
 // ---- T fixed: the W half of all topics of a sweep as one launch (k_wsweep_rows) ---------------------------------------
 bool wsweep_ok(const rri_ctx* c) {
-    return g_wsweep && c->prm.fix_T && !c->prm.fix_W && !c->weighted && !c->sparse && c->k >= 1 &&
+    return g_wsweep && c->prm.fix_T && !c->prm.fix_W && !c->weighted && (!c->sparse || c->sparse_x) && c->k >= 1 &&
            wsweep_lds_bytes(c->k) <= 150 * 1024;
 }
 // topics [t0, k) of sweep `sweep`; false: a buffer could not be had (the caller takes the launch-per-topic schedule)
@@ -2058,6 +2098,13 @@ hipError_t big_malloc(void** p, size_t bytes) {
     return hipMalloc(p, bytes);
 }
 
+// what the data entry points of a dense handle say on a handle that keeps X on a pattern
+const char* sparse_data_refusal(const rri_ctx* c) {
+    return c->sparse_x ? "an RRI_UNWEIGHTED_SPARSE handle keeps X as CSR: it takes its data through rri_upload_X_csr only "
+                         "(no dense X, no device binding, no mask)"
+                       : "a sparse-pattern handle takes its data through rri_upload_observed_csr";
+}
+
 rri_status ready(rri_ctx* c) {
     if (!c->have_X || !c->have_W || !c->have_T || !c->have_params)
         return fail(c, RRI_ERR_INVALID, "X, W, T and params must be set before stepping");
@@ -2086,14 +2133,17 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
         return fail(nullptr, RRI_ERR_HIP, "no HIP device available (librri_hip needs an MI355X)");
     if (device < 0 || device >= ndev) return fail(nullptr, RRI_ERR_INVALID, "device %d out of range [0,%d)", device, ndev);
-    if (weighted < 0 || weighted > 3)
-        return fail(nullptr, RRI_ERR_INVALID, "weighted must be RRI_UNWEIGHTED, RRI_WEIGHTED_DENSE, RRI_WEIGHTED_SPARSE or RRI_UNWEIGHTED_RESIDUAL");
+    if (weighted < 0 || weighted > 4)
+        return fail(nullptr, RRI_ERR_INVALID, "weighted must be RRI_UNWEIGHTED, RRI_WEIGHTED_DENSE, RRI_WEIGHTED_SPARSE, "
+                                              "RRI_UNWEIGHTED_RESIDUAL or RRI_UNWEIGHTED_SPARSE");
     rri_ctx* c = new rri_ctx();
     const bool explicit_resid = weighted == RRI_UNWEIGHTED_RESIDUAL;
-    if (explicit_resid) weighted = RRI_UNWEIGHTED;   // the same flavour of the algorithm, another schedule of its passes
+    const bool sparse_x = weighted == RRI_UNWEIGHTED_SPARSE;
+    if (explicit_resid || sparse_x) weighted = RRI_UNWEIGHTED;   // the same flavour of the algorithm: another schedule / storage
     c->explicit_resid = explicit_resid;
+    c->sparse_x = sparse_x;
     c->n = n; c->d = d; c->k = k; c->dtype = dtype; c->weighted = weighted; c->device = device;
-    c->sparse = weighted == RRI_WEIGHTED_SPARSE;
+    c->sparse = weighted == RRI_WEIGHTED_SPARSE || sparse_x;
     c->kp = (int)round_up(k, 8);
     c->es = dtype == RRI_F32 ? 4 : 8;
     c->VN = (int)(16 / c->es);
@@ -2205,7 +2255,9 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
         // (= Zpart rows); block widths so that three factor tables of a block fit SP_BLOCK_BYTES of LDS
         i64 block_bytes = SP_BLOCK_BYTES;
         if (const char* e = getenv("RRI_SP_BLOCK_KB")) block_bytes = std::min<i64>(SP_BLOCK_BYTES, std::max(8, atoi(e)) * 1024LL);
-        const i64 cap = block_bytes / (3 * (dtype == RRI_F32 ? 4 : 8));
+        // (X on CSR: ONE table of float64 factors per block, spx_block_cap -- k_spx_pass)
+        const i64 cap = sparse_x ? std::min<i64>(spx_block_cap(), std::max<i64>(64, (block_bytes / 8 - 64) / 64 * 64))
+                                 : block_bytes / (3 * (dtype == RRI_F32 ? 4 : 8));
         for (int w = 0; w < 2; ++w) {
             rri_ctx::SpCopy& cp = c->sp[w];
             cp.gdim = w == 0 ? d : n;
@@ -2289,6 +2341,10 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
             CR(hipMemsetAsync(c->sp_Tt, 0, (size_t)d * c->kp * f8, c->stream));
         }
     }
+    if (sparse_x) {
+        CR(hipMalloc((void**)&c->sp_Tt, (size_t)d * c->kp * f8));
+        CR(hipMemsetAsync(c->sp_Tt, 0, (size_t)d * c->kp * f8, c->stream));
+    }
     if (explicit_resid) {
         const i64 zn = std::max<i64>(c->LD, n);
         CR(big_malloc(&c->E, (size_t)n * c->LD * es_x));
@@ -2321,7 +2377,7 @@ rri_status rri_destroy(rri_ctx* c) {
                     (void*)c->tpart, (void*)c->tpart_idx, (void*)c->rowobj, (void*)c->rowpos, (void*)c->normpart,
                     (void*)c->dtmp, (void*)c->itmp, (void*)c->resetT, (void*)c->resetW, (void*)c->st, (void*)c->Y2part,
                     (void*)c->Z2part, (void*)c->Mbits, (void*)c->Qt, (void*)c->dtv, (void*)c->dwv, (void*)c->wold, (void*)c->zeros,
-                    (void*)c->XYpart, (void*)c->objbuf, (void*)c->told, (void*)c->Cpart, (void*)c->N2part, (void*)c->Mcols, (void*)c->Gfull, (void*)c->Wsweep0, (void*)c->wsum_part, (void*)c->wsums, (void*)c->ctail, (void*)c->cand, (void*)c->mkZ, (void*)c->mkG, (void*)c->mkP, (void*)c->mkX, (void*)c->mkT, (void*)c->objE, (void*)c->objhist, (void*)c->objdec, (void*)c->mkbar, (void*)c->Wsafe, (void*)c->Tsafe, (void*)c->sp_rowptr, (void*)c->sp_col, c->sp_x, c->sp_e, (void*)c->sp_Tt,
+                    (void*)c->XYpart, (void*)c->objbuf, (void*)c->told, (void*)c->Cpart, (void*)c->N2part, (void*)c->Mcols, (void*)c->Gfull, (void*)c->Wsweep0, (void*)c->wsum_part, (void*)c->wsums, (void*)c->ctail, (void*)c->cand, (void*)c->mkZ, (void*)c->mkG, (void*)c->mkP, (void*)c->mkX, (void*)c->mkT, (void*)c->objE, (void*)c->objhist, (void*)c->objdec, (void*)c->mkbar, (void*)c->Wsafe, (void*)c->Tsafe, (void*)c->sp_rowptr, (void*)c->sp_col, c->sp_x, c->sp_e, (void*)c->sp_Tt, (void*)c->spx_work, (void*)c->rowhat,
                     (void*)c->sp[0].segptr, (void*)c->sp[0].idx, c->sp[0].val, (void*)c->sp[0].perm, (void*)c->sp[0].work,
                     (void*)c->sp[1].segptr, (void*)c->sp[1].idx, c->sp[1].val, (void*)c->sp[1].perm, (void*)c->sp[1].work};
     for (void* b : bufs)
@@ -2338,7 +2394,7 @@ rri_status rri_destroy(rri_ctx* c) {
 // ---- data ------------------------------------------------------------------------------------------
 rri_status rri_upload_X(rri_ctx* c, const void* host, int64_t ld, int32_t host_dtype) {
     CHECK_CTX(c);
-    if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "a sparse-pattern handle takes its data through rri_upload_observed_csr");
+    if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     HIPCHK(c, hipSetDevice(c->device));
     if (c->X && !c->own_X) c->X = nullptr;
     if (!c->X) {
@@ -2354,7 +2410,7 @@ rri_status rri_upload_X(rri_ctx* c, const void* host, int64_t ld, int32_t host_d
 
 rri_status rri_upload_mask(rri_ctx* c, const void* host, int64_t ld, int32_t host_dtype) {
     CHECK_CTX(c);
-    if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "a sparse-pattern handle takes its data through rri_upload_observed_csr");
+    if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     if (!c->weighted) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=1");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->M && !c->own_M) c->M = nullptr;
@@ -2404,10 +2460,14 @@ rri_status csr_to_device(rri_ctx* c, const int64_t* indptr, const int32_t* indic
 }
 }  // namespace
 
+static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data,
+                                    int64_t nnz, int32_t data_dtype);
+
 rri_status rri_upload_X_csr(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data,
                             int64_t nnz, int32_t data_dtype) {
     CHECK_CTX(c);
-    if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "a sparse-pattern handle takes its data through rri_upload_observed_csr");
+    if (c->sparse_x) return upload_X_csr_kept(c, indptr, indices, data, nnz, data_dtype);
+    if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     HIPCHK(c, hipSetDevice(c->device));
     CsrDev dv;
     rri_status s = csr_to_device(c, indptr, indices, data, nnz, data_dtype, dv);
@@ -2435,10 +2495,75 @@ rri_status rri_upload_X_csr(rri_ctx* c, const int64_t* indptr, const int32_t* in
     return RRI_OK;
 }
 
+namespace {
+rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indices, int64_t nnz, int32_t data_dtype,
+                          CsrDev& dv, int target_items);
+}
+// RRI_UNWEIGHTED_SPARSE: X stays CSR -- the canonical copy and the two blocked copies with X's values (k_spx_pass)
+static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data,
+                                    int64_t nnz, int32_t data_dtype) {
+    if (nnz >= 2147483647LL) return fail(c, RRI_ERR_UNSUPPORTED, "more than 2^31-1 stored entries");
+    if (!indptr || (nnz > 0 && (!indices || !data)) || nnz < 0) return fail(c, RRI_ERR_INVALID, "bad CSR arrays");
+    if (data_dtype != RRI_F32 && data_dtype != RRI_F64) return fail(c, RRI_ERR_INVALID, "bad CSR data dtype");
+    if (indptr[0] != 0 || indptr[c->n] != nnz) return fail(c, RRI_ERR_INVALID, "indptr does not span nnz");
+    for (i64 r = 0; r < c->n; ++r)
+        if (indptr[r + 1] < indptr[r]) return fail(c, RRI_ERR_INVALID, "indptr not monotone at row %lld", r);
+    HIPCHK(c, hipSetDevice(c->device));
+    // column indices sorted inside every row (a sorted host copy where the caller's are not); duplicates are refused
+    const size_t ds = data_dtype == RRI_F32 ? 4 : 8;
+    std::vector<int32_t> sidx;
+    std::vector<unsigned char> sval;
+    for (i64 r = 0; r < c->n; ++r) {
+        bool sorted = true;
+        for (i64 p = indptr[r] + 1; p < indptr[r + 1] && sorted; ++p) sorted = indices[p] > indices[p - 1];
+        if (sorted) continue;
+        if (sidx.empty()) {
+            sidx.assign(indices, indices + nnz);
+            sval.assign((const unsigned char*)data, (const unsigned char*)data + (size_t)nnz * ds);
+        }
+        std::vector<i64> ord((size_t)(indptr[r + 1] - indptr[r]));
+        for (size_t q = 0; q < ord.size(); ++q) ord[q] = indptr[r] + (i64)q;
+        std::stable_sort(ord.begin(), ord.end(), [&](i64 a, i64 b) { return indices[a] < indices[b]; });
+        for (size_t q = 0; q < ord.size(); ++q) {
+            sidx[(size_t)indptr[r] + q] = indices[ord[q]];
+            std::memcpy(sval.data() + ((size_t)indptr[r] + q) * ds, (const unsigned char*)data + (size_t)ord[q] * ds, ds);
+        }
+    }
+    if (!sidx.empty()) { indices = sidx.data(); data = sval.data(); }
+    for (i64 r = 0; r < c->n; ++r)
+        for (i64 p = indptr[r] + 1; p < indptr[r + 1]; ++p)
+            if (indices[p] == indices[p - 1])
+                return fail(c, RRI_ERR_INVALID, "row %lld stores column %d twice (sum the duplicates first)", r, indices[p]);
+    CsrDev dv;
+    rri_status s = csr_to_device(c, indptr, indices, data, nnz, data_dtype, dv);
+    if (s != RRI_OK) return s;
+    // one launch runs the items of both copies: half of the chip's CUs each, so that all of them are ONE round of workgroups
+    int target_items = std::max(1, c->n_cu / 2);
+    if (const char* e = getenv("RRI_SPX_ITEMS")) target_items = std::max(1, atoi(e));
+    s = build_sp_store(c, indptr, indices, nnz, data_dtype, dv, target_items);
+    if (s != RRI_OK) return s;
+    if (nnz > 0)
+        DISPATCH(c, for (int w = 0; w < 2; ++w)
+                        hipLaunchKernelGGL((k_sp_permute<typename L::Elem>), dim3(2048), dim3(256), 0, c->stream,
+                                           (const typename L::Elem*)c->sp_x, (const int*)c->sp[w].perm, c->sp[w].count,
+                                           (typename L::Elem*)c->sp[w].val));
+    if (c->spx_work) { (void)hipFree(c->spx_work); c->spx_work = nullptr; }
+    const int nw0 = c->sp[0].nwork, nw1 = c->sp[1].nwork;
+    HIPCHK(c, hipMalloc((void**)&c->spx_work, (size_t)std::max(1, nw0 + nw1) * sizeof(SpWork)));
+    if (nw0 > 0) HIPCHK(c, hipMemcpyAsync(c->spx_work, c->sp[0].work, (size_t)nw0 * sizeof(SpWork), hipMemcpyDeviceToDevice, c->stream));
+    if (nw1 > 0) HIPCHK(c, hipMemcpyAsync(c->spx_work + nw0, c->sp[1].work, (size_t)nw1 * sizeof(SpWork), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->have_X = true;
+    invalidate(c);
+    c->q_valid = false; c->gfull_valid = false;
+    c->x_sq_valid = false;
+    return RRI_OK;
+}
+
 rri_status rri_upload_mask_csr_pattern(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data,
                                        int64_t nnz, int32_t data_dtype) {
     CHECK_CTX(c);
-    if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "a sparse-pattern handle takes its data through rri_upload_observed_csr");
+    if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     if (!c->weighted) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=1");
     HIPCHK(c, hipSetDevice(c->device));
     CsrDev dv;
@@ -2464,19 +2589,13 @@ rri_status rri_upload_mask_csr_pattern(rri_ctx* c, const int64_t* indptr, const 
     return RRI_OK;
 }
 
-rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* values,
-                                   int64_t nnz, int32_t data_dtype) {
-    CHECK_CTX(c);
-    if (!c->sparse) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=RRI_WEIGHTED_SPARSE");
-    if (nnz >= 2147483647LL) return fail(c, RRI_ERR_UNSUPPORTED, "more than 2^31-1 observed entries");
-    HIPCHK(c, hipSetDevice(c->device));
-    CsrDev dv;   // validates the arrays; its device copies of indptr / indices become the CSR copy
-    rri_status s = csr_to_device(c, indptr, indices, values, nnz, data_dtype, dv);
-    if (s != RRI_OK) return s;
-    for (i64 r = 0; r < c->n; ++r)
-        for (i64 p = indptr[r] + 1; p < indptr[r + 1]; ++p)
-            if (indices[p] <= indices[p - 1])
-                return fail(c, RRI_ERR_INVALID, "column indices of row %lld are not strictly increasing", r);
+namespace {
+// The canonical CSR (rowptr, col, values in the storage type) and the two blocked copies of a pattern, shared by the
+// pattern-only weighted handle and the unweighted handle with X on CSR.  indptr / indices: the validated host arrays (column
+// indices strictly increasing in every row); dv: their device copies (csr_to_device), taken over as the canonical CSR.
+// `target_items`: work items per copy (SpWork.pad = the copy).  The blocked copies' values are left zero.
+rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indices, int64_t nnz, int32_t data_dtype,
+                          CsrDev& dv, int target_items) {
     i64 longest_row = 0;
     for (i64 r = 0; r < c->n; ++r) longest_row = std::max<i64>(longest_row, (i64)(indptr[r + 1] - indptr[r]));
     void* old[] = {(void*)c->sp_rowptr, (void*)c->sp_col, c->sp_x, c->sp_e};
@@ -2487,7 +2606,6 @@ rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int3
     c->sp_x = nullptr; c->sp_e = nullptr;
     const size_t cnt = (size_t)std::max<i64>(nnz, 1);
     HIPCHK(c, hipMalloc(&c->sp_x, cnt * c->es));
-    HIPCHK(c, hipMalloc(&c->sp_e, cnt * c->es));
     if (nnz > 0) {   // values -> storage type (dv.data holds them in the caller's type)
         const bool hf = data_dtype == RRI_F32, df = c->dtype == RRI_F32;
         if (hf && df) launch_convert<float, float, false>(c, dv.data, nnz, c->sp_x, nnz, 1, nnz);
@@ -2496,8 +2614,6 @@ rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int3
         else launch_convert<double, double, false>(c, dv.data, nnz, c->sp_x, nnz, 1, nnz);
     }
     // the two blocked copies: counting sort on the host, stable, so offsets ascend inside a segment
-    int target_items = std::max(1, c->n_cu);
-    if (const char* e = getenv("RRI_SP_ITEMS")) target_items = std::max(1, atoi(e));
     for (int w = 0; w < 2; ++w) {
         rri_ctx::SpCopy& cp = c->sp[w];
         void* oldc[] = {(void*)cp.segptr, (void*)cp.idx, cp.val, (void*)cp.perm, (void*)cp.work};
@@ -2568,10 +2684,10 @@ rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int3
                         s1 = std::lower_bound(row + s0 + 1, row + nseg, want) - row;
                         s1 = std::min<i64>(std::max<i64>(s1, s0 + 1), nseg);
                     }
-                    work.push_back(SpWork{b, (int)s0, (int)s1, 0});
+                    work.push_back(SpWork{b, (int)s0, (int)s1, w});
                     s0 = s1;
                 }
-                if (s0 < nseg) work.push_back(SpWork{b, (int)s0, (int)nseg, 0});
+                if (s0 < nseg) work.push_back(SpWork{b, (int)s0, (int)nseg, w});
             }
         }
         cp.nwork = (int)work.size();
@@ -2598,6 +2714,28 @@ rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int3
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->nnz = nnz;
     c->sp_max_row = (int)longest_row;
+    return RRI_OK;
+}
+}  // namespace
+
+rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* values,
+                                   int64_t nnz, int32_t data_dtype) {
+    CHECK_CTX(c);
+    if (!c->sparse || c->sparse_x) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=RRI_WEIGHTED_SPARSE");
+    if (nnz >= 2147483647LL) return fail(c, RRI_ERR_UNSUPPORTED, "more than 2^31-1 observed entries");
+    HIPCHK(c, hipSetDevice(c->device));
+    CsrDev dv;   // validates the arrays; its device copies of indptr / indices become the CSR copy
+    rri_status s = csr_to_device(c, indptr, indices, values, nnz, data_dtype, dv);
+    if (s != RRI_OK) return s;
+    for (i64 r = 0; r < c->n; ++r)
+        for (i64 p = indptr[r] + 1; p < indptr[r + 1]; ++p)
+            if (indices[p] <= indices[p - 1])
+                return fail(c, RRI_ERR_INVALID, "column indices of row %lld are not strictly increasing", r);
+    int target_items = std::max(1, c->n_cu);
+    if (const char* e = getenv("RRI_SP_ITEMS")) target_items = std::max(1, atoi(e));
+    s = build_sp_store(c, indptr, indices, nnz, data_dtype, dv, target_items);
+    if (s != RRI_OK) return s;
+    HIPCHK(c, hipMalloc(&c->sp_e, (size_t)std::max<i64>(nnz, 1) * c->es));
     c->have_X = true;
     c->have_M = true;
     invalidate(c);
@@ -2606,7 +2744,7 @@ rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int3
 
 rri_status rri_bind_X_device(rri_ctx* c, const void* dev, int64_t ld) {
     CHECK_CTX(c);
-    if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "a sparse-pattern handle takes its data through rri_upload_observed_csr");
+    if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     if (!dev || ld < c->d || (ld * (i64)c->es) % 16 || ((uintptr_t)dev) % 16)
         return fail(c, RRI_ERR_INVALID, "device X must be 16-byte aligned with a 16-byte-multiple row stride >= d");
     if (c->d % c->VN) return fail(c, RRI_ERR_INVALID, "binding device X needs d %% %d == 0 (no pad columns)", c->VN);
@@ -2625,7 +2763,7 @@ rri_status rri_bind_X_device(rri_ctx* c, const void* dev, int64_t ld) {
 
 rri_status rri_bind_mask_device(rri_ctx* c, const void* dev, int64_t ld) {
     CHECK_CTX(c);
-    if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "a sparse-pattern handle takes its data through rri_upload_observed_csr");
+    if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     if (!c->weighted) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=1");
     if (!dev || ld < c->d || (ld * (i64)c->es) % 16 || ((uintptr_t)dev) % 16)
         return fail(c, RRI_ERR_INVALID, "device mask must be 16-byte aligned with a 16-byte-multiple row stride >= d");
@@ -2979,8 +3117,12 @@ static rri_status norms_of(rri_ctx* c, const double* A, i64 rows, i64 cols, i64 
 // ||X||^2, once per X (the constant of the objective's Gram form)
 static rri_status ensure_x_sq(rri_ctx* c) {
     if (c->x_sq_valid) return RRI_OK;
-    DISPATCH(c, hipLaunchKernelGGL((k_sqsum<typename L::Elem>), dim3(256), dim3(256), 0, c->stream,
-                                   (const typename L::Elem*)c->X, c->ldx, c->n, c->d, c->normpart));
+    if (c->sparse_x)    // the stored entries as one row
+        DISPATCH(c, hipLaunchKernelGGL((k_sqsum<typename L::Elem>), dim3(256), dim3(256), 0, c->stream,
+                                       (const typename L::Elem*)c->sp_x, std::max<i64>(c->nnz, 1), (i64)1, c->nnz, c->normpart));
+    else
+        DISPATCH(c, hipLaunchKernelGGL((k_sqsum<typename L::Elem>), dim3(256), dim3(256), 0, c->stream,
+                                       (const typename L::Elem*)c->X, c->ldx, c->n, c->d, c->normpart));
     double h[256];
     HIPCHK(c, hipMemcpyAsync(h, c->normpart, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3056,6 +3198,36 @@ static rri_status objective_terms(rri_ctx* c, double out[3], double* tn) {
         c->resid_fresh = true;
         c->dw_pending = false;
         c->dt_pending = false;
+    } else if (c->sparse_x) {
+        // X on CSR, without the cross terms of a complete sweep: ||X - W T||^2 = sum_pattern r^2 + (<W^T W, T T^T> -
+        // sum_pattern (W T)_ij^2) -- outside the pattern the residual is -(W T)_ij, whose squares are the Gram term less the
+        // pattern's share
+        if (!c->rowhat) HIPCHK(c, hipMalloc((void**)&c->rowhat, (size_t)c->n * sizeof(double)));
+        DISPATCH(c, L::sp_resid(c, false, c->rowobj, nullptr, c->rowhat));
+        const int k = c->k;
+        double* gw = c->objbuf;
+        double* gt = gw + k * k;
+        hipLaunchKernelGGL(k_gram, dim3(k, k), dim3(256), 0, c->stream, (const double*)c->W, c->ldw, c->n, k, gw);
+        hipLaunchKernelGGL(k_gram, dim3(k, k), dim3(256), 0, c->stream, (const double*)c->T, c->LD, c->d, k, gt);
+        hipLaunchKernelGGL(k_vec_sum_argmax, dim3(1), dim3(1024), 0, c->stream, (const double*)c->rowobj, c->n,
+                           c->dtmp, (i64*)nullptr);
+        hipLaunchKernelGGL(k_vec_sum_argmax, dim3(1), dim3(1024), 0, c->stream, (const double*)c->rowhat, c->n,
+                           c->dtmp + 1, (i64*)nullptr);
+        std::vector<double> h((size_t)2 * k * k);
+        double sums[2] = {0.0, 0.0};
+        HIPCHK(c, hipMemcpyAsync(h.data(), gw, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(sums, c->dtmp, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        double quad = 0.0;
+        for (int q = 0; q < k * k; ++q) quad += h[(size_t)q] * h[(size_t)k * k + q];
+        double nw[3];
+        rri_status r = norms_of(c, c->W, c->k, c->n, c->ldw, nw);
+        if (r != RRI_OK) return r;
+        out[0] = 0.5 * (sums[0] + (quad - sums[1]));
+        out[1] = nw[1];
+        out[2] = nw[2];
+        if (tn) return norms_of(c, c->T, c->k, c->d, c->LD, tn);
+        return RRI_OK;
     } else {
         DISPATCH(c, L::resid(c, false, false, c->rowobj, nullptr));
     }
@@ -3437,7 +3609,7 @@ rri_status rri_range_finder(rri_ctx* c, const double* Q0, int32_t m, int32_t n_i
 rri_status rri_column_positive_counts(rri_ctx* c, double* df_out) {
     CHECK_CTX(c);
     if (!df_out) return fail(c, RRI_ERR_INVALID, "df_out is NULL");
-    if (c->weighted || !c->have_X) return fail(c, RRI_ERR_INVALID, "needs an unweighted handle with a dense X");
+    if (c->weighted || !c->have_X || c->sparse_x) return fail(c, RRI_ERR_INVALID, "needs an unweighted handle with a dense X");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
     const int ncols = (int)std::min<i64>(c->ldx, c->LD);
@@ -3454,7 +3626,7 @@ rri_status rri_column_positive_counts(rri_ctx* c, double* df_out) {
 
 rri_status rri_scale_X(rri_ctx* c, const double* col_scale, int32_t normalize_rows) {
     CHECK_CTX(c);
-    if (c->weighted || !c->have_X) return fail(c, RRI_ERR_INVALID, "needs an unweighted handle with a dense X");
+    if (c->weighted || !c->have_X || c->sparse_x) return fail(c, RRI_ERR_INVALID, "needs an unweighted handle with a dense X");
     if (!c->own_X) return fail(c, RRI_ERR_INVALID, "X is bound caller memory: it is not rewritten in place");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
@@ -3716,6 +3888,7 @@ rri_status rri_comm_destroy(rri_comm* m) {
 
 rri_status rri_attach_comm(rri_ctx* c, rri_comm* comm, int64_t row_offset, int64_t n_global) {
     CHECK_CTX(c);
+    if (comm && c->sparse_x) return fail(c, RRI_ERR_UNSUPPORTED, "an RRI_UNWEIGHTED_SPARSE handle is not row-sharded");
     if (!comm) {              // detach
         c->comm = nullptr;
         c->row_offset = 0;
@@ -3839,7 +4012,7 @@ rri_status rri_synchronize(rri_ctx* c) {
 
 rri_status rri_bench_stream_copy(rri_ctx* c, int32_t reps, double* avg_ms) {
     CHECK_CTX(c);
-    if (!c->have_X || reps < 1) return fail(c, RRI_ERR_INVALID, "X must be set and reps >= 1");
+    if (!c->have_X || reps < 1 || c->sparse) return fail(c, RRI_ERR_INVALID, "a dense X must be set and reps >= 1");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->n * c->ldx * c->es;
     void* dst = nullptr;
@@ -3866,8 +4039,8 @@ rri_status rri_bench_stream_copy(rri_ctx* c, int32_t reps, double* avg_ms) {
 
 rri_status rri_bench_rank1_update(rri_ctx* c, int32_t reps, double* avg_ms) {
     CHECK_CTX(c);
-    if (!c->have_X || !c->have_W || !c->have_T || reps < 1 || c->weighted)
-        return fail(c, RRI_ERR_INVALID, "an unweighted handle with X, W, T set and reps >= 1");
+    if (!c->have_X || !c->have_W || !c->have_T || reps < 1 || c->weighted || c->sparse_x)
+        return fail(c, RRI_ERR_INVALID, "an unweighted handle with a dense X, W, T set and reps >= 1");
     HIPCHK(c, hipSetDevice(c->device));
     // scratch residual R = copy of X; every repetition folds the rank-one term w_0 t_0^T of the handle's own factors
     // into it (non-trivial row and column factors; R stays finite: it moves by reps * w_0 t_0^T) and takes the row

@@ -181,6 +181,120 @@ __global__ __launch_bounds__(1024) void k_sp_blk(const SpWork* __restrict__ work
     }
 }
 
+// ---- the unweighted flavour with X kept as CSR (RRI_UNWEIGHTED_SPARSE) ------------------------------------------------
+// A Gram-form topic step needs two products of X: the row dots X t_t (for the W column of topic t) and the column sums
+// w_{t+1}^T X (for the next T row).  Both inputs are ready at the same moment, so ONE read-only launch serves both: its work
+// list holds the items of the row copy (segments = rows, gathered from a table of t_t over the item's column block) followed
+// by those of the column copy (segments = columns, gathered from a table of w_{t+1} over the item's row block); item i takes
+// the copy work[i].pad.  S[copy][blk * lds + seg] are the per-block partial sums in the layout k_wcol (Ypart: column blocks x
+// n) and k_reduce / k_trow_small (Zpart: row blocks x LD) already add in a fixed order.  No corrections, no write-back: 6 B
+// per stored entry and copy for fp32 X (2 of offset, 4 of value), 12 B per entry and topic step for both.
+//
+// The tables hold the factors as DOUBLES (the dense pass multiplies by the float64 factors; rounding them to the storage type
+// would move the sums by 1e-7 of their size against the dense handle): one vector per block instead of k_sp_blk's three, so a
+// block is SP_BLOCK_BYTES / 8 ~ 15296 wide -- 1.5x k_sp_blk's fp32 width, 3x its fp64 width -- and the uint16 offsets still fit.
+// What k_sp_blk learnt is kept: quads of entries per load, 8 in flight per lane, plain loads, pads into the zero slot of the
+// table (offset bw) rather than a branch per entry, and at most n_cu items in all, cut by entry count (the host's work lists).
+constexpr int SPX_UNR = 8;
+__host__ __device__ constexpr i64 spx_block_cap() { return (i64)(SP_BLOCK_BYTES / 8 - 64) / 64 * 64; }
+__host__ __device__ constexpr size_t spx_lds_bytes(int bw) { return (size_t)(bw + 1) * sizeof(double); }
+
+template <typename SX>
+struct SpxArgs {
+    const SpWork* work;                 // items of copy 0, then of copy 1
+    int first;                          // first item of this launch (a launch may run one copy's items only)
+    const i64* segptr[2];
+    const unsigned short* idx[2];
+    const SX* val[2];
+    const double* F[2];                 // per-entry factor: T[t, :] (copy 0, d entries) / W[:, tz] (copy 1, n entries)
+    double* S[2];                       // S[blk * lds + seg]
+    i64 nseg[2], gdim[2], lds[2];
+    int bw[2], lps[2];
+};
+
+template <typename SX, int LPS>
+__device__ __forceinline__ void spx_segments(const SpWork& w, const i64* __restrict__ segptr, i64 nseg,
+                                             const unsigned short* __restrict__ idx, const SX* __restrict__ val, int bw,
+                                             const double* __restrict__ tab, double* __restrict__ S, i64 lds) {
+    typedef typename SpQuad<SX>::type V4;
+    constexpr int GROUPS = 1024 / LPS;
+    const int sub = threadIdx.x % LPS, grp = threadIdx.x / LPS;
+    const i64* sp = segptr + (i64)w.blk * (nseg + 1);
+    const sp_us4* idx4 = reinterpret_cast<const sp_us4*>(idx);
+    const V4* val4 = reinterpret_cast<const V4*>(val);
+    for (int s = w.s0 + grp; s < w.s1; s += GROUPS) {
+        const i64 q0 = sp[s] >> 2, q1 = sp[s + 1] >> 2;     // segment bounds are multiples of 4 entries
+        double acc = 0.0;
+        for (i64 q = q0 + sub; q < q1; q += (i64)LPS * SPX_UNR) {
+            sp_us4 g[SPX_UNR];
+            V4 e[SPX_UNR];
+#pragma unroll
+            for (int u = 0; u < SPX_UNR; ++u) {
+                const i64 qq = q + (i64)u * LPS;
+                if (qq < q1) {
+                    g[u] = idx4[qq];
+                    e[u] = val4[qq];
+                } else {                                     // the zero slot: no branch per entry below
+                    const unsigned short z = (unsigned short)bw;
+                    g[u] = sp_us4{z, z, z, z};
+                    e[u] = V4{SX(0), SX(0), SX(0), SX(0)};
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < SPX_UNR; ++u) {
+                double f[4];
+#pragma unroll
+                for (int m = 0; m < 4; ++m) f[m] = tab[g[u][m]];     // the gathers of a quad first, then its arithmetic
+#pragma unroll
+                for (int m = 0; m < 4; ++m) acc = fma((double)e[u][m], f[m], acc);
+            }
+        }
+        acc = group_sum<LPS>(acc);
+        if (sub == 0) S[(i64)w.blk * lds + s] = acc;
+    }
+}
+
+template <typename SX>
+__global__ __launch_bounds__(1024) void k_spx_pass(SpxArgs<SX> a, const DevState* __restrict__ st) {
+    if (st->halt) return;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double* tab = reinterpret_cast<double*>(smem);   // [bw + 1]; slot bw: the zero entry the pads point at
+    const SpWork w = a.work[a.first + blockIdx.x];
+    const int cp = w.pad;
+    const int bw = a.bw[cp];
+    const i64 g0 = (i64)w.blk * bw, gdim = a.gdim[cp];
+    const double* F = a.F[cp];
+    for (int g = threadIdx.x; g <= bw; g += 1024) tab[g] = (g < bw && g0 + g < gdim) ? F[g0 + g] : 0.0;
+    __syncthreads();
+    switch (a.lps[cp]) {
+        case 8: spx_segments<SX, 8>(w, a.segptr[cp], a.nseg[cp], a.idx[cp], a.val[cp], bw, tab, a.S[cp], a.lds[cp]); break;
+        case 16: spx_segments<SX, 16>(w, a.segptr[cp], a.nseg[cp], a.idx[cp], a.val[cp], bw, tab, a.S[cp], a.lds[cp]); break;
+        case 32: spx_segments<SX, 32>(w, a.segptr[cp], a.nseg[cp], a.idx[cp], a.val[cp], bw, tab, a.S[cp], a.lds[cp]); break;
+        default: spx_segments<SX, 64>(w, a.segptr[cp], a.nseg[cp], a.idx[cp], a.val[cp], bw, tab, a.S[cp], a.lds[cp]); break;
+    }
+}
+
+// X T^T on the canonical CSR for the W half with T fixed (k_wsweep_rows, the fold-in): Qt[l][i] = sum_p x_p Tt[col_p][l],
+// one wave per row, lane = topic (64 topics per round), entries of the row in order.  Tt: d x kp (T transposed, pad 0).
+template <typename SX>
+__global__ __launch_bounds__(256) void k_spx_xtt(const i64* __restrict__ rowptr, const int* __restrict__ col,
+                                                 const SX* __restrict__ xval, i64 n, const double* __restrict__ Tt, int k,
+                                                 int kp, double* __restrict__ Qt, i64 ldq) {
+    const int lane = threadIdx.x & 63;
+    const i64 i = (i64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const i64 p0 = rowptr[i], p1 = rowptr[i + 1];
+    for (int l0 = 0; l0 < k; l0 += 64) {
+        const int l = l0 + lane;
+        double acc = 0.0;
+        for (i64 p = p0; p < p1; ++p) {
+            const double x = (double)xval[p];
+            if (l < k) acc = fma(x, Tt[(i64)col[p] * kp + l], acc);
+        }
+        if (l < k) Qt[(i64)l * ldq + i] = acc;
+    }
+}
+
 // Residual on the pattern (the sparse counterpart of k_resid): r_ij = x_ij - W[i,:] . T[:,j] for the entries of
 // row i.  One wave per row, 8 lanes per entry (lane q of a group takes the topics q, q+8, ...: one 64-byte
 // read of the TRANSPOSED T per step), 8 entries per wave in flight.  Tt: d x kp (kp = k rounded up to 8, pad 0).
@@ -188,12 +302,14 @@ __global__ __launch_bounds__(1024) void k_sp_blk(const SpWork* __restrict__ work
 //   rowobj != NULL: rowobj[i] = sum_j r^2                      (true_objective, nmf.py:71-94, on the mask)
 //   rowpos != NULL: rowpos[i] = sum_j max(r, 0)^2              (reset search, nmf.py:770-773: outside the
 //                                                               pattern x = 0 and max(0 - WT, 0) = 0)
+//   rowhat != NULL: rowhat[i] = sum_j (W T)_ij^2               (unweighted X on CSR: ||X - W T||^2 = sum r^2 +
+//                                                               <W^T W, T T^T> - sum of these over the pattern)
 template <typename SX>
 __global__ __launch_bounds__(256) void k_sp_resid(const i64* __restrict__ rowptr, const int* __restrict__ col,
                                                   const SX* __restrict__ xval, i64 n, const double* __restrict__ Wt,
                                                   i64 ldw, const double* __restrict__ Tt, int k, int kp,
                                                   SX* __restrict__ E, double* __restrict__ rowobj,
-                                                  double* __restrict__ rowpos) {
+                                                  double* __restrict__ rowpos, double* __restrict__ rowhat) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* wsh = reinterpret_cast<double*>(smem);   // [4][kp]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -203,7 +319,7 @@ __global__ __launch_bounds__(256) void k_sp_resid(const i64* __restrict__ rowptr
     __syncthreads();
     const int q = lane & 7, slot = lane >> 3;
     const double* wrow = wsh + wave * kp;
-    double obj = 0.0, pos = 0.0;
+    double obj = 0.0, pos = 0.0, hat = 0.0;
     const i64 p0 = live ? rowptr[i] : 0, p1 = live ? rowptr[i + 1] : 0;
     for (i64 pb = p0; pb < p1; pb += 8) {
         const i64 p = pb + slot;
@@ -227,14 +343,17 @@ __global__ __launch_bounds__(256) void k_sp_resid(const i64* __restrict__ rowptr
             obj = fma(r, r, obj);
             const double rp = fmax(r, 0.0);
             pos = fma(rp, rp, pos);
+            hat = fma(acc, acc, hat);
         }
     }
-    if (rowobj || rowpos) {
+    if (rowobj || rowpos || rowhat) {
         obj = wave_sum<double>(obj);
         pos = wave_sum<double>(pos);
+        hat = wave_sum<double>(hat);
         if (lane == 0 && live) {
             if (rowobj) rowobj[i] = obj;
             if (rowpos) rowpos[i] = pos;
+            if (rowhat) rowhat[i] = hat;
         }
     }
 }

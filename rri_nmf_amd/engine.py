@@ -28,10 +28,12 @@ def _as_host(a, what):
 
 
 class RRIEngine(object):
-    def __init__(self, n, d, k, dtype=np.float32, weighted=False, device=0, stream=None, schedule='gram'):
+    def __init__(self, n, d, k, dtype=np.float32, weighted=False, device=0, stream=None, schedule='gram', sparse_x=False):
         """schedule (unweighted handles): 'gram' -- the residual is never formed, one read of X per topic step
         (the reference's form, nmf.py:670-676, 728-734) -- or 'residual' -- R = X - W T is kept in HBM and every topic
-        step is one rank-one residual update pass fused with the residual products (RRI_UNWEIGHTED_RESIDUAL)"""
+        step is one rank-one residual update pass fused with the residual products (RRI_UNWEIGHTED_RESIDUAL).
+        sparse_x (unweighted, 'gram'): X stays CSR on the device (RRI_UNWEIGHTED_SPARSE) -- upload_X_csr keeps it so, and
+        there is no dense n x d array at all"""
         self._lib = _capi.load_library()
         self.n, self.d, self.k = int(n), int(d), int(k)
         self.dtype = np.dtype(dtype)
@@ -39,7 +41,11 @@ class RRIEngine(object):
         if self.dtype not in _NP2RRI:
             raise ValueError('dtype must be float32 or float64')
         # weighted: False | True (dense W_mat) | 'sparse' (0/1 W_mat given as a CSR pattern, upload_observed_csr)
-        self.sparse = weighted == 'sparse'
+        self.sparse_x = bool(sparse_x)
+        if self.sparse_x and (weighted or schedule != 'gram'):
+            raise ValueError("sparse_x=True is the unweighted flavour in the Gram form: no weights, schedule='gram'")
+        # pattern-only handles (weighted 'sparse') and X kept as CSR both take their products with X 64 columns at a time
+        self.sparse = weighted == 'sparse' or self.sparse_x
         self.weighted = bool(weighted)
         if schedule not in ('gram', 'residual'):
             raise ValueError("schedule must be 'gram' or 'residual'")
@@ -53,7 +59,8 @@ class RRIEngine(object):
         self._reset_method = None
         self.group = None
         st = self._lib.rri_create(C.byref(self._h), self.n, self.d, self.k, _NP2RRI[self.dtype],
-                                  3 if schedule == 'residual' else 2 if self.sparse else int(self.weighted), int(device),
+                                  _capi.RRI_UNWEIGHTED_SPARSE if self.sparse_x else 3 if schedule == 'residual'
+                                  else 2 if self.sparse else int(self.weighted), int(device),
                                   C.c_void_p(stream or 0))
         if st != _capi.RRI_OK:
             msg = self._lib.rri_last_error(None)
@@ -172,7 +179,7 @@ class RRIEngine(object):
                       data.ctypes.data, int(A.nnz), _NP2RRI[data.dtype])
 
     def upload_X_csr(self, A):
-        """X from a scipy sparse matrix, densified on the device (no host .toarray())"""
+        """X from a scipy sparse matrix, densified on the device (no host .toarray()); kept as CSR on a sparse_x handle"""
         keep, args = self._csr_args(A)
         self._check(self._lib.rri_upload_X_csr(self._h, *args))
 

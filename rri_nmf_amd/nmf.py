@@ -23,6 +23,10 @@ additions select the device side:
             both halves free, k >= 2).  Same results to rounding.
     sparse_pattern  weighted flavour with scipy sparse X and 0/1 sparse W_mat: keep the residual on the observed
             entries only (True), densify on the device (False); None = pattern-only below 35 % observed.
+    sparse_X  unweighted flavour: keep X as CSR on the device (True; a dense X is converted with scipy.sparse.csr_matrix),
+            densify a scipy sparse X on the device (False); None = densify, unless the dense array would not fit the
+            device's free memory (sparse_x_route).  With True: no W_mat, schedule='residual', group=, w_row,
+            store_gradients or Gaussian mechanism.
 
 What runs where
     host (numpy, once):   argument checks, warnings and sentinel returns (nmf.py:280-315), the
@@ -57,7 +61,7 @@ class TrueObjComputer(object):
     objective value; true_objective() re-evaluates it on the device."""
 
     def __init__(self, X, W, T, reg_w_l2, reg_t_l2, reg_w_l1, reg_t_l1, Wm, wr, dtype=None, device=0,
-                 sparse_pattern=None, preprocess=None, group=None):
+                 sparse_pattern=None, preprocess=None, group=None, sparse_X=None):
         self.X, self.W, self.T = X, W, T
         self.reg_w_l2, self.reg_t_l2 = reg_w_l2, reg_t_l2
         self.reg_w_l1, self.reg_t_l1 = reg_w_l1, reg_t_l1
@@ -66,13 +70,15 @@ class TrueObjComputer(object):
         self._dtype, self._device, self._sparse_pattern = dtype, device, sparse_pattern
         self._preprocess = preprocess      # device-side tf-idf / normalisation that nmf() applied to X (idf resolved)
         self._group = group                # row-sharded: true_objective() is then a collective call
+        self._sparse_X = sparse_X          # X kept as CSR on the device (nmf's sparse_X)
 
     def true_objective(self):
         X = self.X   # row weights, when used, are already folded into X by nmf() (nmf.py:335-338)
         n, d = X.shape
         k = self.W.shape[1]
         sdt = _storage_dtype(X, self._dtype) if self._preprocess is None else np.dtype(self._dtype or np.float64)
-        with _engine_with_problem(X, self.Wm, k, sdt, self._device, self._sparse_pattern) as eng:
+        with _engine_with_problem(X, self.Wm, k, sdt, self._device, self._sparse_pattern,
+                                  sparse_X=self._sparse_X) as eng:
             if self._preprocess is not None:
                 eng.preprocess(**self._preprocess)
             if self._group is not None:
@@ -120,12 +126,42 @@ def _observed_csr(X, W_mat):
     return scipy.sparse.csr_matrix((vals, M.indices, M.indptr), shape=M.shape)
 
 
-def _engine_with_problem(X, W_mat, k, sdt, device, sparse_pattern=None, schedule='gram'):
+def sparse_x_route(sparse_X, x_is_sparse, n, d, itemsize, free_bytes):
+    """Does an unweighted X go onto a handle that keeps it as CSR (RRI_UNWEIGHTED_SPARSE)?  sparse_X True: yes (a dense X is
+    converted); False: no, a scipy sparse X is densified on the device; None: no -- unless X is scipy sparse and its dense
+    device copy (n rows of d entries rounded up to 16 bytes) needs more than `free_bytes`, where densifying cannot work."""
+    if sparse_X is not None and not isinstance(sparse_X, (bool, np.bool_)):
+        raise ValueError('sparse_X must be True, False or None')
+    if sparse_X is not None:
+        return bool(sparse_X)
+    if not x_is_sparse:
+        return False
+    ld = -(-int(d) * int(itemsize) // 16) * 16 // int(itemsize)
+    return float(n) * ld * int(itemsize) > float(free_bytes)
+
+
+def _device_free_bytes(device):
+    import torch
+    return torch.cuda.mem_get_info(int(device))[0]
+
+
+def _engine_with_problem(X, W_mat, k, sdt, device, sparse_pattern=None, schedule='gram', sparse_X=None):
     """Engine with X and the weights on the device.  scipy sparse X / 0-1 sparse W_mat go up as CSR: onto a
     pattern-only handle (no dense n x d array at all) when X lives on the pattern and the pattern is sparse enough
     -- `sparse_pattern` True / False forces the choice --, else densified / bit-packed on the device (SURVEY.md 8f
-    rank 3); dense inputs as they are."""
+    rank 3); dense inputs as they are.  Without weights, sparse_x_route decides whether X stays CSR on the device."""
     n, d = X.shape
+    if W_mat is None and schedule == 'gram':
+        xs = scipy.sparse.issparse(X)
+        free = _device_free_bytes(device) if (sparse_X is None and xs) else 0
+        if sparse_x_route(sparse_X, xs, n, d, np.dtype(sdt).itemsize, free):
+            eng = RRIEngine(n, d, k, dtype=sdt, device=device, sparse_x=True)
+            try:
+                eng.upload_X_csr(X if xs else scipy.sparse.csr_matrix(X))
+            except Exception:
+                eng.close()
+                raise
+            return eng
     A = None
     if W_mat is not None and sparse_pattern is not False:
         A = _observed_csr(X, W_mat)
@@ -406,7 +442,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         diagnostics=[], store_gradients=False,
         ind_rows_to_store=None, eps_gauss_t=None, delta_gauss_t=None,
         *, dtype=None, device=0, device_init=None, sparse_pattern=None, preprocess=None, schedule='gram', group=None,
-        resident=None):
+        resident=None, sparse_X=None):
     """Non-negative factorisation X ~ W T by rank-one residue iteration; see the module docstring and
     the reference's docstring (nmf.py:109-269) for the parameters.  Returns a dict with 'W', 'T',
     'iter_cputime' (wall seconds since the start, per sweep), 'random_state' and, when the objective
@@ -418,6 +454,18 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     device; every other case preprocesses on the host.  The idf used comes back as rtv['idf'].
     resident (keyword only): a ResidentProblem that keeps the device handle -- X uploaded and preprocessed -- from one call to
     the next on the same problem (see there)."""
+    if sparse_X is not None and not isinstance(sparse_X, (bool, np.bool_)):
+        raise ValueError('sparse_X must be True, False or None')
+    if sparse_X:
+        # the handle that keeps X as CSR is the unweighted flavour in the Gram form on one device, stepped by rri_sweep
+        refused = [name for name, on in (('W_mat', W_mat is not None), ("schedule='residual'", schedule == 'residual'),
+                                         ('group=', group is not None), ('w_row', w_row is not None),
+                                         ('store_gradients', bool(store_gradients)),
+                                         ('the Gaussian mechanism', bool(eps_gauss_t and delta_gauss_t)))
+                   if on]
+        if refused:
+            raise ValueError('sparse_X=True keeps an unweighted X as CSR on one device; it does not combine with %s'
+                             % ', '.join(refused))
     if group is not None:
         # host work that would need the other ranks' rows (the SVD behind the NNDSVD start, document frequencies,
         # per-row weights with their refit) or that decides per rank (callbacks) is not part of the sharded call
@@ -448,6 +496,8 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     # scipy sparse X / 0-1 sparse W_mat are ingested as CSR (no host densification); row weights need a dense X
     if scipy.sparse.issparse(X):
         X = X.tocsr() if w_row is None else X.toarray()
+    elif sparse_X:
+        X = scipy.sparse.csr_matrix(np.asarray(X))    # kept as CSR on the device (preprocessing then takes the host route)
     else:
         X = np.asarray(X)
     W_mat = _sparse_mask_or_dense(W_mat)
@@ -526,7 +576,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             raise ValueError('resident= keeps a handle for plain calls: no group, no w_row, no host-side preprocessing')
         tf_opt = None if device_spec is None else (device_spec['tfidf'] if isinstance(device_spec['tfidf'], bool) else 'given')
         res_key = (id(X_given), tuple(X.shape), str(getattr(X, 'dtype', None)), None if W_mat_given is None else id(W_mat_given),
-                   int(k), str(sdt), device, sparse_pattern, schedule,
+                   int(k), str(sdt), device, sparse_pattern, schedule, sparse_X,
                    None if device_spec is None else (tf_opt, bool(device_spec['normalize'])))
         if tf_opt == 'given':
             res_key = None               # an idf vector from outside: not worth telling apart -- a fresh handle
@@ -538,7 +588,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     else:
         if resident is not None:
             resident.close()
-        eng = _engine_with_problem(X, W_mat, k, sdt, device, sparse_pattern, schedule)
+        eng = _engine_with_problem(X, W_mat, k, sdt, device, sparse_pattern, schedule, sparse_X)
     keep_handle = False
     try:
         if group is not None:
@@ -723,7 +773,8 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     if compute_obj_each_iter:
         rtv['obj_history'] = obj_history
         calc = TrueObjComputer(X, W, T, reg_w_l2, reg_t_l2, reg_w_l1, reg_t_l1, W_mat, w_row,
-                               dtype=dtype, device=device, sparse_pattern=sparse_pattern, preprocess=device_spec, group=group)
+                               dtype=dtype, device=device, sparse_pattern=sparse_pattern, preprocess=device_spec, group=group,
+                               sparse_X=sparse_X)
         calc.obj = obj_history[-1] if obj_history else np.inf
         rtv['obj_calculator'] = calc
     rtv['iter_cputime'] = iter_cputime
