@@ -1693,10 +1693,15 @@ void calibrate_rot(rri_ctx* c) {
 }
 
 // ---- T fixed: the W half of all topics of a sweep as one launch (k_wsweep_rows) ---------------------------------------
+// k <= 256: k_wsweep_verdict keeps one column sum per topic in ssum[256].  The LDS bound is the tighter one today (k <= 109);
+// the explicit term keeps the verdict's array safe if that bound ever moves.
 bool wsweep_ok(const rri_ctx* c) {
     return g_wsweep && c->prm.fix_T && !c->prm.fix_W && !c->weighted && (!c->sparse || c->sparse_x) && c->k >= 1 &&
-           wsweep_lds_bytes(c->k) <= 150 * 1024;
+           c->k <= 256 && wsweep_lds_bytes(c->k) <= 150 * 1024;
 }
+// k_wsweep_rows leaves one column-sum partial and one cross-term partial per 64 rows (c->nwb of them), the count that
+// note_xy(c, t, nwb * WCOL_TILES) and k_wsweep_verdict read back: that holds only with one 64-row tile per k_wcol block
+static_assert(WCOL_TILES == 1, "enqueue_wsweep assumes one 64-row tile per k_wcol block");
 // topics [t0, k) of sweep `sweep`; false: a buffer could not be had (the caller takes the launch-per-topic schedule)
 bool enqueue_wsweep(rri_ctx* c, int sweep, int t0) {
     const int k = c->k;
@@ -2128,7 +2133,7 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     if (n < 1 || d < 1 || k < 1) return fail(nullptr, RRI_ERR_INVALID, "need n,d,k >= 1 (got %lld,%lld,%d)", n, d, k);
     if (dtype != RRI_F32 && dtype != RRI_F64) return fail(nullptr, RRI_ERR_INVALID, "dtype must be RRI_F32/RRI_F64");
     if (n > 2000000000LL || d > 2000000000LL) return fail(nullptr, RRI_ERR_INVALID, "n, d must fit int32");
-    if (k > RRI_MAX_K) return fail(nullptr, RRI_ERR_UNSUPPORTED, "k=%d > %d not supported on the device path", k, RRI_MAX_K);
+    if (k > RRI_MAX_K) return fail(nullptr, RRI_ERR_UNSUPPORTED, "k=%d is above the rank limit RRI_MAX_K = %d of the device path", k, RRI_MAX_K);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
         return fail(nullptr, RRI_ERR_HIP, "no HIP device available (librri_hip needs an MI355X)");

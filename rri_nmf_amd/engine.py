@@ -65,8 +65,14 @@ class RRIEngine(object):
         if st != _capi.RRI_OK:
             msg = self._lib.rri_last_error(None)
             self._h = C.c_void_p()
-            raise _capi.RRIHipUnavailable('rri_create failed (%d): %s'
-                                          % (st, msg.decode() if msg else '?'))
+            text = 'rri_create failed (%d): %s' % (st, msg.decode() if msg else '?')
+            # a refused option or argument is the caller's to fix (the statuses _check maps); anything else is the HIP
+            # runtime or the device
+            if st == _capi.RRI_ERR_UNSUPPORTED:
+                raise NotImplementedError(text)
+            if st == _capi.RRI_ERR_INVALID:
+                raise ValueError(text)
+            raise _capi.RRIHipUnavailable(text)
 
     def begin_run(self):
         """a handle kept from an earlier nmf() call starts another one: the per-run counters of the host side"""

@@ -80,6 +80,31 @@ def test_no_cpu_fallback():
         _capi.load_library('/nonexistent/librri_hip.so')
 
 
+def test_rank_above_the_ceiling_is_refused_as_not_implemented():
+    """k = RRI_MAX_K + 1 is refused by rri_create before any HIP call (RRI_ERR_UNSUPPORTED), so with or without a device:
+    RRIEngine and nmf() raise NotImplementedError naming the limit -- not RRIHipUnavailable, which means no library or no
+    device.  A bad argument of rri_create is a ValueError."""
+    from rri_nmf_amd.nmf import nmf
+    from rri_nmf_amd.engine import RRIEngine
+    hdr = open(os.path.join(ROOT, 'include', 'rri_hip.h')).read()
+    assert int(re.search(r'#define RRI_MAX_K (\d+)', hdr).group(1)) == _capi.RRI_MAX_K
+    k = _capi.RRI_MAX_K + 1
+    lib = _capi.load_library()
+    h = ctypes.c_void_p()
+    assert lib.rri_create(ctypes.byref(h), 30, 20, k, 0, 0, 0, None) == _capi.RRI_ERR_UNSUPPORTED
+    for schedule in ('gram', 'residual'):
+        with pytest.raises(NotImplementedError, match='RRI_MAX_K = %d' % _capi.RRI_MAX_K):
+            RRIEngine(30, 20, k, schedule=schedule)
+    with pytest.raises(NotImplementedError, match='RRI_MAX_K = %d' % _capi.RRI_MAX_K):
+        RRIEngine(30, 20, k, weighted=True, dtype=np.float64)
+    X = planted_X(30, 20, 3, dtype=np.float64)
+    rs = np.random.RandomState(0)
+    with pytest.raises(NotImplementedError, match='RRI_MAX_K = %d' % _capi.RRI_MAX_K):
+        nmf(X, k, W_in=rs.rand(30, k), T_in=rs.rand(k, 20), max_iter=1)
+    with pytest.raises(ValueError, match='n,d,k'):
+        RRIEngine(30, 20, 0)
+
+
 def test_nmf_host_checks_before_device_work():
     """argument handling that the reference performs before its loop (nmf.py:280-315, 853-860)"""
     from rri_nmf_amd.nmf import nmf
