@@ -123,6 +123,22 @@ struct rri_comm {
     bool aborted = false;                      // a rank left a collective sequence half way: the communicator is unusable
 };
 
+// The environment switches a handle keeps: read once, by rri_create (read_switches), so that a handle created later under
+// another environment cannot change the schedule of one that is already running (INTEGRATION.md lists them)
+struct rri_switches {
+    bool onchip = true;        // RRI_ONCHIP=0: never the register-resident persistent sweep (rri_onchip_kernels.hpp)
+    bool onchip_obj = true;    // RRI_ONCHIP_OBJ=0: the persistent sweep does not leave the objective of its last sweep (rri_objective takes the Gram kernels)
+    bool wsweep = true;        // RRI_WSWEEP=0: runs with T fixed take the launch-per-topic W half (k_tgram, k_wcol, k_check_wcol per topic)
+    bool obj_direct = false;   // RRI_OBJ_DIRECT=1: the objective always through the residual (k_resid)
+    bool wmcorr_cols = true;   // RRI_WMCORR_COLS=0: the mask-only correction always walks every bit (k_wmcorr), also on a sparse mask
+    bool wnw_mask = true;      // RRI_WNW_MASK=0: the one-pass step keeps taking nw = (w^2)^T M in the read-modify-write pass on a sparse 0/1 mask too
+    int pass_rot = -1;         // RRI_PASS_ROT=0..7: rotate the tiles of the passes inside every group of 8 workgroups (another XCD per tile) by this
+                               // much; unset: the handle's own calibrated 0 or 1 (calibrate_rot)
+    int rot_cal = 1;           // RRI_ROT_CAL=0: no calibration, rotation 0; 1: rotations {0, 1}; n > 1: rotations 0 .. n-1
+    bool rot_debug = false;    // RRI_ROT_DEBUG (set): calibrate_rot prints its timings
+    bool mask_bits = true;     // RRI_MASK_BITS=0: a 0/1 mask stays an fp array (no bit-packed copy)
+};
+
 struct rri_ctx {
     i64 n = 0, d = 0, LD = 0;
     int k = 0, dtype = RRI_F32, weighted = 0, device = 0;
@@ -130,6 +146,7 @@ struct rri_ctx {
     int VN = 4, PW = 1024;
     hipStream_t stream = nullptr;
     bool own_stream = false;
+    rri_switches sw;
 
     void *X = nullptr, *M = nullptr, *E = nullptr;
     i64 ldx = 0, ldm = 0;
@@ -450,39 +467,6 @@ struct TimedScope {
 };
 
 // ---- typed launch helpers ------------------------------------------------------------------
-// geometry of k_pass, fixed per process (env RRI_PASS_UNROLL / RRI_PASS_NT)
-int g_pass_unroll = 8, g_pass_nt = -1, g_pass_rs = 1;   // RS: LDS row sums (needs unroll 8).  nt: -1 = per handle (non-temporal
-                                                        // loads where X cannot stay in the caches, plain loads where it can)
-int g_pass_dma_sub = 0;       // RRI_PASS_DMA_SUB: row blocks per workgroup of the ring kernel (0: ~1024 workgroups)
-int g_pass_dma = 0;           // RRI_PASS_DMA=1: the read-only pass through the LDS-DMA ring (k_pass_dma).  OFF by default: the same bits as
-                              // k_pass, but between +3 % and -9 % in time by box, process and geometry (profiles/r04_pass_dma_ab.log)
-int g_pass_unroll_upd = 16;   // rows in flight of the read-modify-write passes (RRI_PASS_UNROLL set: follows it)
-int g_wpass_uc = 8;      // RRI_WPASS_UC: rows in flight of the writing weighted pass with a bit-packed mask: 8 (one mask word per
-                         // chunk; +1.3 % at C5 over 4, 16 falls to one wave per SIMD: profiles/r02_weighted_pass_variants.log) or 4
-int g_wpass_ud = 4;      // RRI_WPASS_UD: rows in flight of the one-pass weighted step.  4 (DPP row sums, 138 VGPRs, 3 waves per SIMD): 1.458 ms at
-                         // BASELINE config 5 against 1.553 ms for 8 (LDS row sums, 240 VGPRs, 2 waves per SIMD) and 1.618 ms for 8 with
-                         // DPP row sums, engines made alternately in one process (profiles/r04_wpass_one_variants.log)
-int g_wpass_occ4 = 1;    // RRI_WPASS_OCC4=0: the one-pass step at the compiler's own register count (130: 3 waves per SIMD)
-int g_wnw_mask = 1;      // RRI_WNW_MASK=0: the one-pass step keeps taking nw = (w^2)^T M in the read-modify-write pass on a sparse 0/1 mask too
-int g_wmcorr_wgs = 16;   // RRI_WMCORR_WGS: workgroups per CU of k_wmcorr_cols (4: 60 us, 8: 48, 16: 46, 32: 44 at BASELINE config 5)
-int g_wmcorr_cols = 1;   // RRI_WMCORR_COLS=0: the mask-only correction always walks every bit (k_wmcorr), also on a sparse mask
-int g_wmcorr_skip = 1;   // RRI_WMCORR_SKIP=0: k_wmcorr does not test the row factors for zero
-int g_wpass_one = 1;     // RRI_WPASS_ONE=0: the dense weighted flavour in two passes per topic step (read; read-modify-write), as rounds 1-3
-int g_wpass_il = -1;     // RRI_WPASS_IL: 1 / 0 = interleaved / contiguous row chunks in every weighted pass; default: the writing ones
-int g_side_jobs = 1;    // RRI_SIDE_JOBS=0: every small job as a launch of its own
-int g_onchip = 1;       // RRI_ONCHIP=0: never the register-resident persistent sweep (rri_onchip_kernels.hpp)
-int g_onchip_obj = 1;   // RRI_ONCHIP_OBJ=0: the persistent sweep does not leave the objective of its last sweep (rri_objective takes the Gram kernels)
-int g_resid_mfma = 1;   // RRI_RESID_MFMA=0: the residual on the vector ALU for every k
-int g_resid_split = 0;   // RRI_RESID_SPLIT=n: column ranges per row block of the residual rebuild (0: chosen from the grid)
-int g_wsweep = 1;        // RRI_WSWEEP=0: runs with T fixed take the launch-per-topic W half (k_tgram, k_wcol, k_check_wcol per topic)
-int g_trow_small = 1;    // RRI_TROW_SMALL=0: k_reduce + k_trow_numer as two launches at every size
-int g_pass_interleave = -1;  // RRI_PASS_IL: 1 / 0 = interleaved / contiguous row chunks per workgroup of k_pass; default:
-                             // interleaved up to 1024 workgroups (+2 % at 20000 x 5000; -1 % at C3, where it stays off)
-int g_pass_rot = -1;     // RRI_PASS_ROT=0..7: rotate the tiles of the passes inside every group of 8 workgroups (another XCD per tile) by this much
-                         // for every handle; unset: each handle's own calibrated 0 or 1 (calibrate_rot)
-int g_rot_cal = 1;       // RRI_ROT_CAL=0: no calibration, rotation 0
-int g_rmw_shop = 1;      // RRI_RMW_SHOP=n (diagnostics): places a large residual buffer is tried in (calibrate_rot); 1: the first allocation is kept
-int g_obj_direct = 0;   // RRI_OBJ_DIRECT=1: the objective always through the residual (k_resid)
 // kernels that touch X / mask / residual depend on the storage type SX; the rest is float64
 template <typename SX>
 struct LaunchX {
@@ -500,7 +484,6 @@ struct LaunchX {
     // stay there anyway.  A matrix that fits the 256 MB Infinity Cache is re-read from it by every pass: plain loads are
     // 4 % faster at 10000 x 1000 (2020 against 1937 sweeps/s, profiles/r02_c2_variants.log).
     static bool pass_nt(const rri_ctx* c) {
-        if (g_pass_nt >= 0) return g_pass_nt != 0;
         return (double)c->n * (double)c->LD * (double)c->es > 192.0e6;
     }
     template <bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS>
@@ -511,81 +494,23 @@ struct LaunchX {
                            pass_shmem(c, UPD), c->stream, (XT*)Xp, ldp, (int)c->n, ncols, trow, wc, c->Ypart,
                            c->Zpart, c->LD, c->rpb, c->npanels, u.a, u.b, u.a2, u.b2, u.b2sub, (const DevState*)c->st, job,
                            // interleaved row chunks: the workgroups running at one time walk ONE window of the matrix, as a
-                           // linear stream does.  Read-only pass: +2 % up to 1024 workgroups, nothing at C3.  Read-modify-write
-                           // (UPD): +4-9 % at C3 (profiles/r02_residual_schedule_geometry.log) -- reads and writes of a window
-                           // stay in the DRAM pages that are open
-                           ((g_pass_interleave == 1 || (g_pass_interleave < 0 && (c->npanels * c->nrb <= 1024 || UPD > 0))) ? c->nrb : 0) |
-                               ((g_pass_rot >= 0 ? g_pass_rot : (UPD > 0 ? c->rot_r : c->rot_x)) << 27));
+                           // linear stream does.  Read-only pass: +2 % up to 1024 workgroups (20000 x 5000), -1 % at C3, where
+                           // it stays off.  Read-modify-write (UPD): +4-9 % at C3 (profiles/r02_residual_schedule_geometry.log)
+                           // -- reads and writes of a window stay in the DRAM pages that are open
+                           ((c->npanels * c->nrb <= 1024 || UPD > 0) ? c->nrb : 0) |
+                               ((c->sw.pass_rot >= 0 ? c->sw.pass_rot : (UPD > 0 ? c->rot_r : c->rot_x)) << 27));
     }
-    // the read-only pass through the LDS-DMA ring (k_pass_dma), opt-in (RRI_PASS_DMA=1): where the ring and the row-dot slots fit
-    // the LDS and X's rows are 16-byte aligned
-    // A workgroup of the ring kernel walks `sub` consecutive row blocks of the handle's geometry as ONE stream (the ring stays full
-    // across them) and still leaves one row of column sums per row block: Ypart / Zpart -- and every sum in them -- are exactly
-    // what k_pass leaves.  (The hope was ~1024 long workgroups: measured 0.663 against 0.661 ms for the register kernel with two
-    // blocks per workgroup, 0.72 with three, 0.671 with four -- profiles/r04_pass_dma_ab.log.)  The row-dot slots of the sub blocks
-    // must fit the LDS next to the 64 KiB ring.
-    static int pass_dma_sub(const rri_ctx* c, bool interleaved) {
-        if (interleaved) return 1;
-        if (g_pass_dma_sub > 0) return std::max(1, std::min(g_pass_dma_sub, (int)(2200 / std::max(c->rpb, 1))));
-        const int want = (int)std::max<i64>(1, ((i64)c->npanels * c->nrb + 512) / 1024);
-        return std::max(1, std::min(want, 2200 / std::max(c->rpb, 1)));
-    }
-    static size_t pass_dma_shmem(const rri_ctx* c, int sub) { return (size_t)4 * PASS_DMA_SLOTS * 1024 + 5 * (size_t)sub * c->rpb * sizeof(double); }
-    static bool pass_dma(const rri_ctx* c, i64 ldp) {
-        if (g_pass_dma == 0 || g_pass_unroll != 8 || !g_pass_rs) return false;
-        if (pass_dma_shmem(c, 1) > 150 * 1024 || ldp % c->VN != 0 || c->rpb % PASS_DMA_CHUNK != 0) return false;
-        return g_pass_dma == 1;
-    }
-    template <bool DO_Y, bool DO_Z, bool NT>
-    static void pass_dma_k(rri_ctx* c, const void* Xp, i64 ldp, const double* trow, const double* wc, const TgramJob& job) {
-        static bool attr_set[64] = {};   // per instantiation and device
-        const int dv = c->device & 63;
-        if (!attr_set[dv]) {
-            // (the kernel also has 320 bytes of static LDS for its side job: dynamic + static must stay within the CU's 160 KiB)
-            (void)hipFuncSetAttribute((const void*)k_pass_dma<SX, DO_Y, DO_Z, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-            attr_set[dv] = true;
-        }
-        const int ncols = (int)std::min<i64>(ldp, c->LD);
-        const bool il = g_pass_interleave == 1 || (g_pass_interleave < 0 && c->npanels * c->nrb <= 1024);
-        const int sub = pass_dma_sub(c, il);
-        const int ngroups = (c->nrb + sub - 1) / sub;
-        hipLaunchKernelGGL((k_pass_dma<SX, DO_Y, DO_Z, NT>), dim3(c->npanels * ngroups + job.nblocks), dim3(256), pass_dma_shmem(c, sub),
-                           c->stream, (const SX*)Xp, ldp, (int)c->n, ncols, trow, wc, c->Ypart, c->Zpart, c->LD, c->rpb,
-                           c->npanels, (const DevState*)c->st, job, il ? c->nrb : 0, sub, c->nrb);
-    }
+    // The read-only pass: 8 rows in flight per wave, the row dots (DO_Y) through LDS row sums.  The read-modify-write variants:
+    // 16 rows in flight per wave, row dots by DPP wave sums -- 0.665 against 0.639 of 8 TB/s for the 8-row LDS row-sum variant
+    // at C3 (profiles/r02_residual_schedule_geometry.log).  (The LDS-DMA ring k_pass_dma measured between +3 % and -9 % against
+    // this pass, profiles/r04_pass_dma_ab.log, and was removed.)
     template <bool DO_Y, bool DO_Z, int UPD>
     static void pass_cfg(rri_ctx* c, void* Xp, i64 ldp, const double* trow, const double* wc, const Upd& u = Upd{},
                          const TgramJob& job = TgramJob{}) {
-        if constexpr (UPD == 0) {
-            if (pass_dma(c, ldp) && ((uintptr_t)Xp) % 16 == 0) {
-                if (pass_nt(c)) pass_dma_k<DO_Y, DO_Z, true>(c, Xp, ldp, trow, wc, job);
-                else pass_dma_k<DO_Y, DO_Z, false>(c, Xp, ldp, trow, wc, job);
-                return;
-            }
-        }
-        if (UPD > 0 && g_pass_unroll_upd == 16) {
-            // the read-modify-write variants: 16 rows in flight per wave, row dots by DPP wave sums -- 0.665 against 0.639
-            // of 8 TB/s for the 8-row LDS row-sum variant at C3 (profiles/r02_residual_schedule_geometry.log)
-            if (pass_nt(c)) pass_k<DO_Y, DO_Z, UPD, 16, true, false>(c, Xp, ldp, trow, wc, u, job);
-            else pass_k<DO_Y, DO_Z, UPD, 16, false, false>(c, Xp, ldp, trow, wc, u, job);
-            return;
-        }
-        if (g_pass_unroll == 8 && g_pass_rs && DO_Y) {
-            if (pass_nt(c)) pass_k<DO_Y, DO_Z, UPD, 8, true, true>(c, Xp, ldp, trow, wc, u, job);
-            else pass_k<DO_Y, DO_Z, UPD, 8, false, true>(c, Xp, ldp, trow, wc, u, job);
-            return;
-        }
-        const int key = g_pass_unroll * 2 + (pass_nt(c) ? 1 : 0);
-        switch (key) {
-#define RRI_CASE(U_)                                                                              \
-    case U_ * 2 + 0: pass_k<DO_Y, DO_Z, UPD, U_, false, false>(c, Xp, ldp, trow, wc, u, job); break;   \
-    case U_ * 2 + 1: pass_k<DO_Y, DO_Z, UPD, U_, true, false>(c, Xp, ldp, trow, wc, u, job); break;
-            RRI_CASE(4)
-            RRI_CASE(8)
-            RRI_CASE(16)
-#undef RRI_CASE
-            default: pass_k<DO_Y, DO_Z, UPD, 8, true, false>(c, Xp, ldp, trow, wc, u, job);
-        }
+        constexpr int U = UPD > 0 ? 16 : 8;
+        constexpr bool RS = UPD == 0 && DO_Y;
+        if (pass_nt(c)) pass_k<DO_Y, DO_Z, UPD, U, true, RS>(c, Xp, ldp, trow, wc, u, job);
+        else pass_k<DO_Y, DO_Z, UPD, U, false, RS>(c, Xp, ldp, trow, wc, u, job);
     }
     // row dots against T[t,:] (DO_Y) and column sums against W[:,tz] (DO_Z); `job`: the Gram row of T[t,:] rides along
     template <bool DO_Y, bool DO_Z>
@@ -622,55 +547,48 @@ struct LaunchX {
     static void wpass_k2(rri_ctx* c, const double* trow, const double* wc, const double* a1, const double* b1,
                          const double* a2, const double* b2) {
         const int ncols = (int)std::min<i64>(c->ldx, c->LD);
-        if constexpr (DO_Y && WRITE && U == 4) {
-            if (g_wpass_occ4 && (DO_Z2 || !DO_Z)) {     // the one-pass step, 4 rows in flight: the build for four waves per SIMD
-                hipLaunchKernelGGL((k_wpass_occ4<SX, DO_Y, DO_Z, UPD2, WRITE, U, true, MBITS, RS, DO_Z2>), dim3(c->npanels * c->nrb),
-                                   dim3(256), (11 * (size_t)c->rpb + 4 * 8 * 72) * sizeof(double), c->stream, (SX*)c->E,
-                                   (const SX*)c->M, c->LD, c->ldm, (const unsigned*)c->Mbits, c->ldb, (int)c->n, ncols, trow,
-                                   wc, a1, b1, a2, b2, c->Ypart, c->Y2part, c->Zpart, c->Z2part, c->LD, c->rpb, c->npanels,
-                                   (const DevState*)c->st, ((g_wpass_il == 1 || g_wpass_il < 0) ? c->nrb : 0) | ((g_pass_rot >= 0 ? g_pass_rot : c->rot_r) << 27));
-                return;
-            }
+        const int rot = (c->sw.pass_rot >= 0 ? c->sw.pass_rot : c->rot_r) << 27;
+        if constexpr (DO_Y && WRITE && U == 4 && (DO_Z2 || !DO_Z)) {
+            // the one-pass step, 4 rows in flight: the build for four waves per SIMD (the compiler's own register count, 130,
+            // gives 3); the step whose nw comes from the mask (DO_Z && !DO_Z2) takes k_wpass below
+            hipLaunchKernelGGL((k_wpass_occ4<SX, DO_Y, DO_Z, UPD2, WRITE, U, true, MBITS, RS, DO_Z2>), dim3(c->npanels * c->nrb),
+                               dim3(256), (11 * (size_t)c->rpb + 4 * 8 * 72) * sizeof(double), c->stream, (SX*)c->E,
+                               (const SX*)c->M, c->LD, c->ldm, (const unsigned*)c->Mbits, c->ldb, (int)c->n, ncols, trow,
+                               wc, a1, b1, a2, b2, c->Ypart, c->Y2part, c->Zpart, c->Z2part, c->LD, c->rpb, c->npanels,
+                               (const DevState*)c->st, c->nrb | rot);
+        } else {
+            hipLaunchKernelGGL((k_wpass<SX, DO_Y, DO_Z, UPD2, WRITE, U, true, MBITS, RS, DO_Z2>), dim3(c->npanels * c->nrb),
+                               dim3(256), (11 * (size_t)c->rpb + 4 * 8 * 72) * sizeof(double), c->stream, (SX*)c->E,
+                               (const SX*)c->M, c->LD, c->ldm, (const unsigned*)c->Mbits, c->ldb, (int)c->n, ncols, trow,
+                               wc, a1, b1, a2, b2, c->Ypart, c->Y2part, c->Zpart, c->Z2part, c->LD, c->rpb, c->npanels,
+                               (const DevState*)c->st,
+                               // interleaved row chunks for the passes that write E back (read-modify-write), as for k_pass<UPD>
+                               ((WRITE || c->npanels * c->nrb <= 1024) ? c->nrb : 0) | rot);
         }
-        hipLaunchKernelGGL((k_wpass<SX, DO_Y, DO_Z, UPD2, WRITE, U, true, MBITS, RS, DO_Z2>), dim3(c->npanels * c->nrb),
-                           dim3(256), (11 * (size_t)c->rpb + 4 * 8 * 72) * sizeof(double), c->stream, (SX*)c->E,
-                           (const SX*)c->M, c->LD, c->ldm, (const unsigned*)c->Mbits, c->ldb, (int)c->n, ncols, trow,
-                           wc, a1, b1, a2, b2, c->Ypart, c->Y2part, c->Zpart, c->Z2part, c->LD, c->rpb, c->npanels,
-                           (const DevState*)c->st,
-                           // interleaved row chunks for the passes that write E back (read-modify-write), as for k_pass<UPD>
-                           ((g_wpass_il == 1 || (g_wpass_il < 0 && (WRITE || c->npanels * c->nrb <= 1024))) ? c->nrb : 0) |
-                               ((g_pass_rot >= 0 ? g_pass_rot : c->rot_r) << 27));
     }
+    // Rows in flight.  The one-pass step (row products and a write): 4, DPP row sums -- 1.458 ms at BASELINE config 5 against
+    // 1.553 ms for 8 with LDS row sums (240 VGPRs, 2 waves per SIMD) and 1.618 ms for 8 with DPP row sums, engines made
+    // alternately in one process (profiles/r04_wpass_one_variants.log).  The other passes that take row products: 8, LDS row
+    // sums.  Column sums alone: 8 with a bit-packed mask (one mask word per chunk; +1.3 % at C5 over 4, 16 falls to one wave
+    // per SIMD: profiles/r02_weighted_pass_variants.log), 4 with an fp mask array.
     template <bool DO_Y, bool DO_Z, bool UPD2, bool WRITE>
     static void wpass(rri_ctx* c, const double* trow, const double* wc, const double* a1, const double* b1,
                       const double* a2, const double* b2) {
         TimedScope ts(c, 3);
         if (c->sparse) { sp_wpass<DO_Y, DO_Z, UPD2, WRITE>(c, trow, wc, a1, b1, a2, b2); return; }
-        // rows in flight: 8 for the passes that take row products (they use the LDS row sums); the writing pass (two
-        // rank-one corrections, two sets of accumulators): 4 with an fp mask array, 8 with a bit-packed mask
-        constexpr int U = DO_Y ? 8 : 4;
-        const bool rs = DO_Y && g_pass_rs;
-        if constexpr (DO_Y && WRITE) {      // the one-pass step: RRI_WPASS_UD=4 -> 4 rows in flight, DPP row sums (fewer registers)
-            if (g_wpass_ud == 4) {
-                if (c->Mbits) wpass_k<DO_Y, DO_Z, UPD2, WRITE, true, 4, false>(c, trow, wc, a1, b1, a2, b2);
-                else wpass_k<DO_Y, DO_Z, UPD2, WRITE, false, 4, false>(c, trow, wc, a1, b1, a2, b2);
-                return;
-            }
-        }
-        if (c->Mbits) {
-            if (rs) wpass_k<DO_Y, DO_Z, UPD2, WRITE, true, 8, DO_Y>(c, trow, wc, a1, b1, a2, b2);
-            else if (!DO_Y && g_wpass_uc == 8) wpass_k<DO_Y, DO_Z, UPD2, WRITE, true, 8, false>(c, trow, wc, a1, b1, a2, b2);
-            else wpass_k<DO_Y, DO_Z, UPD2, WRITE, true, U, false>(c, trow, wc, a1, b1, a2, b2);
+        if constexpr (DO_Y && WRITE) {
+            if (c->Mbits) wpass_k<DO_Y, DO_Z, UPD2, WRITE, true, 4, false>(c, trow, wc, a1, b1, a2, b2);
+            else wpass_k<DO_Y, DO_Z, UPD2, WRITE, false, 4, false>(c, trow, wc, a1, b1, a2, b2);
         } else {
-            if (rs) wpass_k<DO_Y, DO_Z, UPD2, WRITE, false, 8, DO_Y>(c, trow, wc, a1, b1, a2, b2);
-            else wpass_k<DO_Y, DO_Z, UPD2, WRITE, false, U, false>(c, trow, wc, a1, b1, a2, b2);
+            if (c->Mbits) wpass_k<DO_Y, DO_Z, UPD2, WRITE, true, 8, DO_Y>(c, trow, wc, a1, b1, a2, b2);
+            else wpass_k<DO_Y, DO_Z, UPD2, WRITE, false, (DO_Y ? 8 : 4), DO_Y>(c, trow, wc, a1, b1, a2, b2);
         }
     }
     // c = M^T (wn .* dw) as row-block partials in Cpart (k_wmcorr): the correction of the column sums a one-pass topic step
     // leaves behind.  Geometry: ~4 workgroups per CU, row blocks of a multiple of 64 rows, at most 4096 (32 KiB of LDS).
     // the column-major copy of the packed mask, on first use (one-off: a kernel, a count, one synchronisation)
     static bool mask_cols(rri_ctx* c) {
-        if (!c->Mbits || !g_wmcorr_cols) return false;
+        if (!c->Mbits || !c->sw.wmcorr_cols) return false;
         if (!c->mcols_tried) {
             c->mcols_tried = true;
             const i64 ng = (c->n + 31) / 32;
@@ -692,14 +610,15 @@ struct LaunchX {
     }
     // the second column sum of a T-row step, nw = (w^2)^T M, from the mask-only kernel instead of the pass: dense handles on the
     // one-pass schedule whose mask is 0/1 and sparse enough for the column-major copy
-    static bool nw_from_mask(rri_ctx* c) { return !c->sparse && g_wpass_one && g_wnw_mask && mask_cols(c); }
+    static bool nw_from_mask(rri_ctx* c) { return !c->sparse && c->sw.wnw_mask && mask_cols(c); }
     // dw == NULL: nothing pending, nw alone (nw_from_mask handles)
     static void wmcorr(rri_ctx* c, const double* wn, const double* dw) {
         TimedScope ts(c, 2);
         if (mask_cols(c)) {     // a sparse 0/1 mask: the set bits only
             const bool nw = nw_from_mask(c);
             const int npg = (int)((c->LD + 255) / 256);
-            i64 nrb = std::min<i64>(256, std::max<i64>(1, (g_wmcorr_wgs * (i64)std::max(c->n_cu, 1) + npg - 1) / npg));
+            // 16 workgroups per CU (4: 60 us, 8: 48, 16: 46, 32: 44 at BASELINE config 5)
+            i64 nrb = std::min<i64>(256, std::max<i64>(1, (16 * (i64)std::max(c->n_cu, 1) + npg - 1) / npg));
             i64 rpb = std::min<i64>(2048, round_up((c->n + nrb - 1) / nrb, 32));
             nrb = (c->n + rpb - 1) / rpb;            // <= cpart_rows (256, or n / 2048 where that is more: rri_create)
             c->wcorr_nrb = (int)nrb;
@@ -721,12 +640,8 @@ struct LaunchX {
         nrb = (c->n + rpb - 1) / rpb;
         c->wcorr_nrb = (int)std::min<i64>(nrb, c->cpart_rows);     // (cpart_rows covers every n: see rri_create)
         const int ncols = (int)std::min<i64>(bits ? c->ldb * 4 : c->ldm, c->LD);
-        if (bits && g_wmcorr_skip)
+        if (bits)      // (a packed mask: rows whose factor is zero are skipped)
             hipLaunchKernelGGL((k_wmcorr<SX, true, true>), dim3((unsigned)(npg * nrb)), dim3(256), (size_t)rpb * sizeof(double), c->stream,
-                               (const SX*)nullptr, (i64)0, (const unsigned*)c->Mbits, c->ldb, (int)c->n, (int)(c->ldb * 4), wn, dw,
-                               c->Cpart, c->LD, (int)rpb, npg, (const DevState*)c->st);
-        else if (bits)
-            hipLaunchKernelGGL((k_wmcorr<SX, true, false>), dim3((unsigned)(npg * nrb)), dim3(256), (size_t)rpb * sizeof(double), c->stream,
                                (const SX*)nullptr, (i64)0, (const unsigned*)c->Mbits, c->ldb, (int)c->n, (int)(c->ldb * 4), wn, dw,
                                c->Cpart, c->LD, (int)rpb, npg, (const DevState*)c->st);
         else
@@ -829,7 +744,7 @@ struct LaunchX {
         if (c->Mbits) { (void)hipFree(c->Mbits); c->Mbits = nullptr; }
         if (c->Mcols) { (void)hipFree(c->Mcols); c->Mcols = nullptr; }
         c->mcols_tried = false;
-        if (const char* e = getenv("RRI_MASK_BITS")) if (atoi(e) == 0) return RRI_OK;
+        if (!c->sw.mask_bits) return RRI_OK;
         hipError_t err = hipMemsetAsync(c->itmp, 0, sizeof(i64), c->stream);
         if (err != hipSuccess) return RRI_ERR_HIP;
         hipLaunchKernelGGL((k_mask_nonbinary<SX>), dim3(2048), dim3(256), 0, c->stream, (const SX*)c->M, c->ldm,
@@ -860,20 +775,15 @@ struct LaunchX {
                            (const SX*)c->X, c->ldx, Tm, c->LD, (int)c->n, (int)c->d, m, out, c->ldw);
     }
     static void xtt_any(rri_ctx* c, const double* Tm, int m, double* out) {   // out (m x n) = (X Tm^T)^T
-        if (g_resid_mfma) {   // the product on the matrix cores, up to 64 rows of Tm per launch
-            for (int l0 = 0; l0 < m; l0 += 64) {
-                const int mm = std::min(64, m - l0);
-                const double* Tp = Tm + (i64)l0 * c->LD;
-                double* op = out + (i64)l0 * c->ldw;
-                if (mm <= 16) xtt_mfma_k<1>(c, Tp, mm, op);
-                else if (mm <= 32) xtt_mfma_k<2>(c, Tp, mm, op);
-                else if (mm <= 48) xtt_mfma_k<3>(c, Tp, mm, op);
-                else xtt_mfma_k<4>(c, Tp, mm, op);
-            }
-            return;
+        for (int l0 = 0; l0 < m; l0 += 64) {     // the product on the matrix cores, up to 64 rows of Tm per launch
+            const int mm = std::min(64, m - l0);
+            const double* Tp = Tm + (i64)l0 * c->LD;
+            double* op = out + (i64)l0 * c->ldw;
+            if (mm <= 16) xtt_mfma_k<1>(c, Tp, mm, op);
+            else if (mm <= 32) xtt_mfma_k<2>(c, Tp, mm, op);
+            else if (mm <= 48) xtt_mfma_k<3>(c, Tp, mm, op);
+            else xtt_mfma_k<4>(c, Tp, mm, op);
         }
-        hipLaunchKernelGGL((k_xtt<SX>), dim3((unsigned)((c->n + 63) / 64)), dim3(256), 0, c->stream, (const SX*)c->X,
-                           c->ldx, Tm, c->LD, (int)c->n, (int)c->d, m, out, c->ldw);
     }
     static void xtt(rri_ctx* c) {
         if (c->sparse_x) spx_xtt(c, c->T, c->k, c->Qt);
@@ -899,17 +809,16 @@ struct LaunchX {
     static void resid(rri_ctx* c, bool masked, bool write_e, double* rowobj, double* rowpos) {
         if (c->sparse) { sp_resid(c, write_e, rowobj, rowpos); return; }   // outside the pattern nothing contributes
         const unsigned nb = (unsigned)((c->n + 63) / 64);
-        if (c->k <= 64 && g_resid_mfma) {   // the k-panel product on the matrix cores
+        if (c->k <= 64) {   // the k-panel product on the matrix cores
             const int ks = c->k <= 16 ? 4 : c->k <= 32 ? 8 : c->k <= 48 ? 12 : c->k <= 52 ? 13 : 16;
             const size_t shm = 2 * (size_t)(4 * ks) * RESID_TS * sizeof(double);
             const bool sums = rowobj || rowpos;      // a plain rebuild wants neither: its epilogue is convert, subtract, store
             // column ranges per row block (the rebuild without row sums): ~12 rounds of the chip's 2 workgroups per CU or more, so
-            // that the last, partly filled round costs a twelfth and not a quarter (RRI_RESID_SPLIT=1: one range)
+            // that the last, partly filled round costs a twelfth and not a quarter
             int nsplit = 1;
             if (!sums && write_e) {
                 const i64 per_round = 2 * (i64)std::max(c->n_cu, 1);
                 nsplit = (int)std::min<i64>((c->d + 63) / 64, std::max<i64>(1, (12 * per_round + nb - 1) / nb));
-                if (g_resid_split > 0) nsplit = (int)std::min<i64>((c->d + 63) / 64, g_resid_split);
             }
             const int dchunk = (int)round_up((c->d + nsplit - 1) / nsplit, 64);
             const unsigned ny = (unsigned)((c->d + dchunk - 1) / dchunk);
@@ -1038,7 +947,7 @@ struct LK {  // float64-only kernels
     }
     // launch-bound sizes: k_reduce and k_trow_numer as one launch (every workgroup reduces the Gram partials itself)
     static bool small(const rri_ctx* c) {
-        return g_trow_small && (double)gpart_rows(c) * (c->k + 2) * c->ntb32 <= 4.0e6;
+        return (double)gpart_rows(c) * (c->k + 2) * c->ntb32 <= 4.0e6;
     }
     static void trow_small(rri_ctx* c, int t, int check_prev, int tprev, int sweep, bool force_final) {
         hipLaunchKernelGGL(k_trow_small, dim3(c->ntb32), dim3(1024), 0, c->stream, c->T, c->LD, (int)c->d, c->k, t,
@@ -1259,7 +1168,7 @@ void enqueue_W_half(rri_ctx* c, int sweep, int t) {
     const int finish = (LK::light(c) && !c->prm.fix_T && !c->skip_row_finish) ? 1 : 0;
     c->skip_row_finish = false;
     TgramJob job{};
-    if (c->prm.fix_T || g_side_jobs == 0 || c->sparse_x) {
+    if (c->prm.fix_T || c->sparse_x) {
         TimedScope ts(c, 2);
         LK::tgram(c, t, finish, sweep);
     } else {
@@ -1353,15 +1262,9 @@ void enqueue_rW_half(rri_ctx* c, int sweep, int t) {
     if (!c->resid_valid) r_refresh(c);
     const int finish = (LK::light(c) && !c->skip_row_finish) ? 1 : 0;
     c->skip_row_finish = false;
-    TgramJob job{};
-    if (g_side_jobs == 0) {
-        TimedScope ts(c, 2);
-        LK::tgram(c, t, finish, sweep);
-    } else {
-        job = TgramJob{(const double*)c->T, c->LD, (int)c->d, c->k, t, c->Ttpart, (const double*)c->tpart, c->tpart_n,
+    const TgramJob job{(const double*)c->T, c->LD, (int)c->d, c->k, t, c->Ttpart, (const double*)c->tpart, c->tpart_n,
                        c->nsplit, finish, sweep, kparams(c), c->st, c->k * c->nsplit};
-        c->ttpart_n = c->nsplit;
-    }
+    c->ttpart_n = c->nsplit;
     const double* trow = c->T + (i64)t * c->LD;
     DISPATCH(c, {
         typename L::Upd u;
@@ -1510,7 +1413,7 @@ void enqueue_wW_half(rri_ctx* c, int sweep, int t, bool defer_check = false) {
         const double* b2 = c->T + (i64)(c->dw_pending ? c->dw_topic : t) * c->LD;
         TimedScope ts(c, 3);
         DISPATCH(c, (L::template sp_blk<true, true, true>(c, 0, b1, b2, trow, c->W + (i64)t * c->ldw, a2, c->Ypart, c->Y2part, c->n)));
-    } else if (g_wpass_one) {
+    } else {
         // Dense handles: ONE read-modify-write pass per topic step (rri_wrri_kernels.hpp, "one read-modify-write pass").  It folds
         // the W-column change of the step before (still pending) and this step's T-row change into E, writes E, and takes the
         // row products of this W update AND the column sums of the next T row; what those lack -- the term the update below
@@ -1527,8 +1430,6 @@ void enqueue_wW_half(rri_ctx* c, int sweep, int t, bool defer_check = false) {
             else DISPATCH(c, (L::template wpass<true, false, false, false>(c, trow, nullptr, c->zeros, c->zeros, nullptr, nullptr)));
         } else if (cn) DISPATCH(c, (L::template wpass<true, true, true, true>(c, trow, wnx, wt_t, b1, a2, b2)));
         else DISPATCH(c, (L::template wpass<true, false, true, true>(c, trow, nullptr, wt_t, b1, a2, b2)));
-    } else {
-        DISPATCH(c, (L::template wpass<true, false, false, false>(c, trow, nullptr, c->W + (i64)t * c->ldw, b1, nullptr, nullptr)));
     }
     {
         TimedScope ts(c, 1);
@@ -1542,13 +1443,9 @@ void enqueue_wW_half(rri_ctx* c, int sweep, int t, bool defer_check = false) {
         TimedScope ts(c, 3);          // the column copy: both terms of this step, the column sums of the next topic
         if (carry_next) DISPATCH(c, (L::template sp_blk<true, true, true>(c, 1, c->wold, c->dwv, wn, b1, trow, c->Zpart, c->Z2part, c->LD)));
         else DISPATCH(c, (L::template sp_blk<false, true, true>(c, 1, c->wold, c->dwv, wn, b1, trow, c->Zpart, c->Z2part, c->LD)));
-        c->dw_pending = true;
-        c->dw_topic = t;
-    } else if (g_wpass_one) {
-        c->dw_pending = true;     // dwv x T[t,:] under the mask: folded into E by the pass of the next step
-        c->dw_topic = t;
-    } else if (carry_next) DISPATCH(c, (L::template wpass<false, true, true, true>(c, nullptr, wn, c->wold, b1, c->dwv, trow)));
-    else DISPATCH(c, (L::template wpass<false, false, true, true>(c, nullptr, nullptr, c->wold, b1, c->dwv, trow)));
+    }
+    c->dw_pending = true;     // dwv x T[t,:]: folded in by the pass of the next step (dense: into E, under the mask; pattern-only: the row copy)
+    c->dw_topic = t;
     int ns = sweep, np = t + 1;
     if (np == k) { np = 0; ns = sweep + 1; }
     if (defer_check) {   // row-sharded: the verdict needs the global column sum; it rides on the next topic's all-reduce
@@ -1572,11 +1469,10 @@ void enqueue_wW_half(rri_ctx* c, int sweep, int t, bool defer_check = false) {
 // its own values, bit for bit), the last two timed -- ~10 ms once per handle -- and keeps the faster.  The rotation changes
 // which workgroup computes a tile and nothing in any sum: the results are the same bits whichever wins.
 // (The read-only pass over X differs by ~1 % between the two: calibrated the same way, on X, for handles of the Gram form.)
-hipError_t big_malloc(void** p, size_t bytes);
 void calibrate_rot(rri_ctx* c) {
     if (c->rot_done) return;
     c->rot_done = true;
-    if (g_pass_rot >= 0 || !g_rot_cal) return;
+    if (c->sw.pass_rot >= 0 || !c->sw.rot_cal) return;
     const bool resid = resid_sched(c);
     const bool wdense = c->weighted && !c->sparse;
     const bool plain = !c->weighted && !resid && !c->sparse && !c->prm.fix_T;      // the Gram form: the read-only pass over X
@@ -1599,7 +1495,7 @@ void calibrate_rot(rri_ctx* c) {
             (void)hipEventRecord(e1, c->stream);
             float ms = 0.0f;
             if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { best = -1.0f; break; }
-            if (getenv("RRI_ROT_DEBUG")) fprintf(stderr, "rri: tile rotation %d: %.4f ms per read-only pass\n", rot, ms / 2.0f);
+            if (c->sw.rot_debug) fprintf(stderr, "rri: tile rotation %d: %.4f ms per read-only pass\n", rot, ms / 2.0f);
             if (best < 0.0f || ms < best) { best = ms; best_rot = rot; }
         }
         c->rot_x = best > 0.0f ? best_rot : 0;
@@ -1609,50 +1505,11 @@ void calibrate_rot(rri_ctx* c) {
         c->carry_topic = -1;
         return;
     }
-    auto refresh = [&]() {
+    if (!c->resid_valid) {
         if (resid) r_refresh(c);
         else w_refresh(c);
-    };
-    if (!c->resid_valid) refresh();
-    // one buffer: the better of the rotations 0 and 1 (or 0 .. RRI_ROT_CAL-1), by null updates; < 0: a launch or a wait failed
-    auto time_buffer = [&](int* rot_out) -> float {
-        float best = -1.0f;
-        const int nrot = g_rot_cal > 1 ? std::min(g_rot_cal, 8) : 2;
-        for (int rot = 0; rot < nrot; ++rot) {
-            c->rot_r = rot;
-            for (int rep = 0; rep < 3; ++rep) {
-                if (rep == 1) (void)hipEventRecord(e0, c->stream);
-                if (resid) {
-                    DISPATCH(c, {
-                        typename L::Upd u;
-                        u.a = c->zeros; u.b = c->zeros; u.a2 = c->zeros; u.b2 = c->zeros; u.b2sub = c->zeros;
-                        L::rank_update(c, c->E, c->LD, u, c->T, c->W);
-                    });
-                } else {
-                    DISPATCH(c, (L::template wpass<true, true, true, true>(c, c->T, c->W, c->zeros, c->zeros, c->zeros, c->zeros)));
-                }
-            }
-            (void)hipEventRecord(e1, c->stream);
-            float ms = 0.0f;
-            if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) return -1.0f;
-            if (getenv("RRI_ROT_DEBUG")) fprintf(stderr, "rri: tile rotation %d: %.4f ms per null update\n", rot, ms / 2.0f);
-            if (best < 0.0f || ms < best) { best = ms; *rot_out = rot; }
-        }
-        return best;
-    };
-    // The level under the parity belongs to the BUFFER, not to the process (six residuals alive in one process: one at 1.34 ms,
-    // one at 1.42, four at 1.50-1.53 whatever the rotation; physically contiguous memory: always 1.54 --
-    // profiles/r04_rmw_buffer_probe.log).  RRI_RMW_SHOP=n (diagnostics, default 1 = off) tries a large residual in up to n
-    // places -- a new allocation while the ones before it are still held, the residual rebuilt into it, timed -- until one runs
-    // 7 % faster than the slowest seen, keeps the best and frees the others: on a box whose buffers are slow it found none in
-    // 40 places (10 processes), which is why it is not the default.
-    const size_t ebytes = (size_t)c->n * (size_t)c->LD * (c->dtype == RRI_F32 ? 4 : 8);
-    const int places = ebytes >= ((size_t)1 << 30) ? std::max(1, g_rmw_shop) : 1;
-    std::vector<void*> held;
-    void* best_e = c->E;
-    int best_rot = 0, rot = 0;
-    c->rot_r = 0;
-    for (int rep = 0; rep < 2; ++rep) {        // (the first passes of a process run ~5 % slow: not the rotation's doing)
+    }
+    auto null_update = [&]() {
         if (resid) {
             DISPATCH(c, {
                 typename L::Upd u;
@@ -1662,30 +1519,30 @@ void calibrate_rot(rri_ctx* c) {
         } else {
             DISPATCH(c, (L::template wpass<true, true, true, true>(c, c->T, c->W, c->zeros, c->zeros, c->zeros, c->zeros)));
         }
+    };
+    // The level under the parity belongs to the BUFFER, not to the process (six residuals alive in one process: one at 1.34 ms,
+    // one at 1.42, four at 1.50-1.53 whatever the rotation; physically contiguous memory: always 1.54 --
+    // profiles/r04_rmw_buffer_probe.log).  Trying a large residual in several places until one ran fast found none in 40 places
+    // (10 processes) on a box whose buffers were slow: the first allocation is kept.
+    c->rot_r = 0;
+    for (int rep = 0; rep < 2; ++rep) null_update();   // (the first passes of a process run ~5 % slow: not the rotation's doing)
+    // the better of the rotations 0 and 1 (or 0 .. RRI_ROT_CAL-1), by null updates; a launch or a wait that fails: rotation 0
+    float best = -1.0f;
+    int best_rot = 0;
+    const int nrot = c->sw.rot_cal > 1 ? std::min(c->sw.rot_cal, 8) : 2;
+    for (int rot = 0; rot < nrot; ++rot) {
+        c->rot_r = rot;
+        for (int rep = 0; rep < 3; ++rep) {
+            if (rep == 1) (void)hipEventRecord(e0, c->stream);
+            null_update();
+        }
+        (void)hipEventRecord(e1, c->stream);
+        float ms = 0.0f;
+        if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { best = -1.0f; break; }
+        if (c->sw.rot_debug) fprintf(stderr, "rri: tile rotation %d: %.4f ms per null update\n", rot, ms / 2.0f);
+        if (best < 0.0f || ms < best) { best = ms; best_rot = rot; }
     }
-    float best_ms = time_buffer(&rot), worst_ms = best_ms;
-    best_rot = rot;
-    for (int a = 1; a < places && best_ms > 0.0f; ++a) {
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < 2 * ebytes + ((size_t)4 << 30)) break;
-        void* p = nullptr;
-        if (big_malloc(&p, ebytes) != hipSuccess) { (void)hipGetLastError(); break; }
-        if (c->LD != c->d) (void)hipMemsetAsync(p, 0, ebytes, c->stream);      // pad columns stay zero
-        held.push_back(c->E);
-        c->E = p;
-        refresh();
-        const float ms = time_buffer(&rot);
-        if (getenv("RRI_ROT_DEBUG")) fprintf(stderr, "rri: residual buffer %d: %.4f ms (the first %.4f)\n", a, ms / 2.0f, worst_ms / 2.0f);
-        if (ms < 0.0f) break;
-        worst_ms = std::max(worst_ms, ms);
-        if (ms < best_ms) { best_ms = ms; best_rot = rot; best_e = c->E; }
-        if (best_ms < 0.93f * worst_ms) break;
-    }
-    held.push_back(c->E);
-    for (void* p : held)
-        if (p != best_e) (void)hipFree(p);
-    c->E = best_e;                 // (its content: the residual of the current W, T -- the null updates rewrote it with itself)
-    c->rot_r = best_ms > 0.0f ? best_rot : 0;
+    c->rot_r = best > 0.0f ? best_rot : 0;
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     c->carry_valid = false;          // the null updates left their own row products and column sums in the scratch arrays
@@ -1696,7 +1553,7 @@ void calibrate_rot(rri_ctx* c) {
 // k <= 256: k_wsweep_verdict keeps one column sum per topic in ssum[256].  The LDS bound is the tighter one today (k <= 109);
 // the explicit term keeps the verdict's array safe if that bound ever moves.
 bool wsweep_ok(const rri_ctx* c) {
-    return g_wsweep && c->prm.fix_T && !c->prm.fix_W && !c->weighted && (!c->sparse || c->sparse_x) && c->k >= 1 &&
+    return c->sw.wsweep && c->prm.fix_T && !c->prm.fix_W && !c->weighted && (!c->sparse || c->sparse_x) && c->k >= 1 &&
            c->k <= 256 && wsweep_lds_bytes(c->k) <= 150 * 1024;
 }
 // k_wsweep_rows leaves one column-sum partial and one cross-term partial per 64 rows (c->nwb of them), the count that
@@ -1842,7 +1699,7 @@ bool onchip_ok(const rri_ctx* c) {
     // a handle that fell back tries the persistent path again once its own back-off has run out (a burst on another stream or
     // process must not cost a long-lived handle the launch-bound speed-up for good); eligibility therefore depends on the clock
     if (c->onchip_off && steady_now_ns() < c->onchip_off_until) return false;
-    return g_onchip && steady_now_ns() >= g_onchip_backoff_until.load() && !c->weighted && !c->explicit_resid && !c->comm && !c->sparse && c->k >= 2 &&
+    return c->sw.onchip && steady_now_ns() >= g_onchip_backoff_until.load() && !c->weighted && !c->explicit_resid && !c->comm && !c->sparse && c->k >= 2 &&
            c->k <= ONCHIP_MAX_K && !c->prm.fix_W && !c->prm.fix_T && c->ldx % c->VN == 0 && ((uintptr_t)c->X) % 16 == 0 &&
            onchip_geometry(c, &g);
 }
@@ -1853,11 +1710,9 @@ bool onchip_ok(const rri_ctx* c) {
 // two grids; there the bounded polls end the wait and the call falls back (run_and_collect).
 // hipLaunchCooperativeKernel is NOT used: it gives no stronger residency than a plain launch of a grid checked against the
 // occupancy query (same admission, same queue), costs 15-19 us per launch, and a process that has used it dies in the HIP
-// runtime's own exit handler under rocprofv3 ("the exit-time fault"; RRI_ONCHIP_COOP=1 keeps it reachable for
-// tools/exit_probe).
+// runtime's own exit handler under rocprofv3 ("the exit-time fault").
 std::mutex g_onchip_mu;
 hipEvent_t g_onchip_last[64] = {};
-int g_onchip_coop = 0;   // RRI_ONCHIP_COOP=1 (diagnostics): hipLaunchCooperativeKernel instead of the plain launch
 hipError_t onchip_ordered_launch(rri_ctx* c, const void* fn, int grid, size_t shmem, const OnchipArgs& a) {
     std::lock_guard<std::mutex> lock(g_onchip_mu);
     const int dv = c->device & 63;
@@ -1865,9 +1720,7 @@ hipError_t onchip_ordered_launch(rri_ctx* c, const void* fn, int grid, size_t sh
     if (g_onchip_last[dv]) (void)hipStreamWaitEvent(c->stream, g_onchip_last[dv], 0);
     OnchipArgs copy = a;
     void* args[] = {(void*)&copy};
-    hipError_t le;
-    if (g_onchip_coop) le = hipLaunchCooperativeKernel(fn, dim3(grid), dim3(ONCHIP_THREADS), args, (unsigned)shmem, c->stream);
-    else le = hipLaunchKernel(fn, dim3(grid), dim3(ONCHIP_THREADS), args, shmem, c->stream);
+    hipError_t le = hipLaunchKernel(fn, dim3(grid), dim3(ONCHIP_THREADS), args, shmem, c->stream);
     if (le == hipSuccess) le = hipGetLastError();
     if (le == hipSuccess && g_onchip_last[dv]) (void)hipEventRecord(g_onchip_last[dv], c->stream);
     return le;
@@ -1928,7 +1781,7 @@ bool enqueue_onchip(rri_ctx* c, Cursor cur) {
     a.fail_step = -1;
     if (const char* e = getenv("RRI_ONCHIP_FAIL_STEP")) a.fail_step = atoi(e);       // tests: give up inside the run, at this topic step of the launch
     // the last sweep of the launch runs from its topic 0: its objective can be left behind (see eacc in the kernel)
-    a.track = (g_onchip_obj && (c->run_total - 1 > cur.sweep || (cur.topic == 0 && cur.phase == 0))) ? 1 : 0;
+    a.track = (c->sw.onchip_obj && (c->run_total - 1 > cur.sweep || (cur.topic == 0 && cur.phase == 0))) ? 1 : 0;
     if (c->until.active && cur.topic == 0 && cur.phase == 0 && c->run_total - cur.sweep <= ONCHIP_UNTIL_CAP && c->x_sq_valid) {
         a.track = 2;
         a.objhist = c->objhist; a.dec = c->objdec;
@@ -2090,17 +1943,21 @@ rri_status clear_halt(rri_ctx* c) {
     return RRI_OK;
 }
 
-// The big read-modify-write buffers (the residual R / E).  RRI_MALLOC_CONTIGUOUS=1 (diagnostics, tools/rmw_place.py) asks the
-// runtime for physically contiguous memory (hipExtMallocWithFlags, hipDeviceMallocContiguous).
-int g_malloc_contig = 0;
-hipError_t big_malloc(void** p, size_t bytes) {
-    if (g_malloc_contig) {
-        hipError_t e = hipExtMallocWithFlags(p, bytes, hipDeviceMallocContiguous);
-        if (e == hipSuccess) return e;
-        (void)hipGetLastError();
-        if (getenv("RRI_ONCHIP_DEBUG")) fprintf(stderr, "rri: contiguous allocation of %zu bytes refused (%s); plain hipMalloc\n", bytes, hipGetErrorString(e));
-    }
-    return hipMalloc(p, bytes);
+// The only place that reads the switches a handle keeps: an unset variable means the default, whatever the handles
+// created before this one were created under
+rri_switches read_switches() {
+    rri_switches sw;
+    if (const char* e = getenv("RRI_ONCHIP")) sw.onchip = atoi(e) != 0;
+    if (const char* e = getenv("RRI_ONCHIP_OBJ")) sw.onchip_obj = atoi(e) != 0;
+    if (const char* e = getenv("RRI_WSWEEP")) sw.wsweep = atoi(e) != 0;
+    if (const char* e = getenv("RRI_OBJ_DIRECT")) sw.obj_direct = atoi(e) != 0;
+    if (const char* e = getenv("RRI_WMCORR_COLS")) sw.wmcorr_cols = atoi(e) != 0;
+    if (const char* e = getenv("RRI_WNW_MASK")) sw.wnw_mask = atoi(e) != 0;
+    if (const char* e = getenv("RRI_PASS_ROT")) sw.pass_rot = atoi(e) & 7;
+    if (const char* e = getenv("RRI_ROT_CAL")) sw.rot_cal = std::max(0, atoi(e));
+    sw.rot_debug = getenv("RRI_ROT_DEBUG") != nullptr;
+    if (const char* e = getenv("RRI_MASK_BITS")) sw.mask_bits = atoi(e) != 0;
+    return sw;
 }
 
 // what the data entry points of a dense handle say on a handle that keeps X on a pattern
@@ -2152,55 +2009,7 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     c->kp = (int)round_up(k, 8);
     c->es = dtype == RRI_F32 ? 4 : 8;
     c->VN = (int)(16 / c->es);
-    // the switches are per process and read again by every rri_create: an unset variable means the default, not "what
-    // the last handle was created with"
-    g_pass_unroll = 8; g_pass_unroll_upd = 16; g_pass_nt = -1; g_pass_rs = 1; g_obj_direct = 0; g_pass_interleave = -1;
-    g_wsweep = 1;
-    g_resid_split = 0;
-    if (const char* e = getenv("RRI_RESID_SPLIT")) g_resid_split = std::max(0, atoi(e));
-    if (const char* e = getenv("RRI_WSWEEP")) g_wsweep = atoi(e) != 0;
-    g_trow_small = 1; g_resid_mfma = 1; g_side_jobs = 1; g_onchip = 1; g_onchip_obj = 1; g_wpass_il = -1;
-    g_wpass_uc = 8;
-    g_wpass_one = 1;
-    g_wpass_occ4 = 1;
-    if (const char* e = getenv("RRI_WPASS_OCC4")) g_wpass_occ4 = atoi(e) != 0;
-    g_wmcorr_cols = 1;
-    g_wmcorr_wgs = 16;
-    g_wnw_mask = 1;
-    if (const char* e = getenv("RRI_WNW_MASK")) g_wnw_mask = atoi(e) != 0;
-    if (const char* e = getenv("RRI_WMCORR_WGS")) g_wmcorr_wgs = std::min(64, std::max(1, atoi(e)));
-    if (const char* e = getenv("RRI_WMCORR_COLS")) g_wmcorr_cols = atoi(e) != 0;
-    g_wmcorr_skip = 1;
-    if (const char* e = getenv("RRI_WMCORR_SKIP")) g_wmcorr_skip = atoi(e) != 0;
-    g_wpass_ud = 4;
-    if (const char* e = getenv("RRI_WPASS_UD")) g_wpass_ud = atoi(e) == 8 ? 8 : 4;
-    if (const char* e = getenv("RRI_WPASS_ONE")) g_wpass_one = atoi(e) != 0;
-    if (const char* e = getenv("RRI_PASS_UNROLL")) { int v = atoi(e); if (v == 4 || v == 8 || v == 16) { g_pass_unroll = v; g_pass_unroll_upd = v; } }
-    if (const char* e = getenv("RRI_PASS_NT")) g_pass_nt = atoi(e) != 0 ? 1 : 0;
-    g_pass_dma = 0;
-    if (const char* e = getenv("RRI_PASS_DMA")) g_pass_dma = atoi(e) != 0 ? 1 : 0;
-    g_pass_dma_sub = 0;
-    if (const char* e = getenv("RRI_PASS_DMA_SUB")) g_pass_dma_sub = std::max(0, atoi(e));
-    if (const char* e = getenv("RRI_PASS_RS")) g_pass_rs = atoi(e) != 0;
-    if (const char* e = getenv("RRI_OBJ_DIRECT")) g_obj_direct = atoi(e) != 0;
-    if (const char* e = getenv("RRI_PASS_IL")) g_pass_interleave = atoi(e) != 0 ? 1 : 0;
-    if (const char* e = getenv("RRI_TROW_SMALL")) g_trow_small = atoi(e) != 0;
-    if (const char* e = getenv("RRI_RESID_MFMA")) g_resid_mfma = atoi(e) != 0;
-    if (const char* e = getenv("RRI_SIDE_JOBS")) g_side_jobs = atoi(e) != 0;
-    if (const char* e = getenv("RRI_ONCHIP")) g_onchip = atoi(e) != 0;
-    if (const char* e = getenv("RRI_ONCHIP_OBJ")) g_onchip_obj = atoi(e) != 0;
-    g_onchip_coop = 0;
-    g_pass_rot = -1;
-    if (const char* e = getenv("RRI_PASS_ROT")) g_pass_rot = atoi(e) & 7;
-    g_rot_cal = 1;
-    g_rmw_shop = 1;
-    if (const char* e = getenv("RRI_RMW_SHOP")) g_rmw_shop = std::min(12, std::max(1, atoi(e)));
-    if (const char* e = getenv("RRI_ROT_CAL")) g_rot_cal = std::max(0, atoi(e));      // 0 off, 1 rotations {0, 1}, n > 1: rotations 0 .. n-1
-    g_malloc_contig = 0;
-    if (const char* e = getenv("RRI_MALLOC_CONTIGUOUS")) g_malloc_contig = atoi(e) != 0;
-    if (const char* e = getenv("RRI_ONCHIP_COOP")) g_onchip_coop = atoi(e) != 0;
-    if (const char* e = getenv("RRI_WPASS_IL")) g_wpass_il = atoi(e) != 0 ? 1 : 0;
-    if (const char* e = getenv("RRI_WPASS_UC")) g_wpass_uc = atoi(e) == 4 ? 4 : 8;
+    c->sw = read_switches();
     c->PW = 64 * c->VN * 4;   // columns per workgroup: 4 waves x (64 lanes x 16 B)
     c->LD = round_up(d, c->VN);
 #define CR(call)                                                                                   \
@@ -2226,13 +2035,8 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     // that 4 workgroups (16 waves) fit a CU's 160 KiB -- with 62 KiB the weighted passes ran at 2 workgroups per CU
     // and 20 % slower.  (The explicit update kernel takes a sixth array and may run at 3 per CU.)
     const i64 rpb_cap = ((40 * 1024 - 4 * 8 * 72 * 8) / ((weighted ? 11 : explicit_resid ? 7 : 5) * 8)) / 16 * 16;
-    int rpb_min = 32;
-    if (const char* e = getenv("RRI_PASS_MIN_ROWS")) rpb_min = std::max(4, atoi(e));
     i64 rpb = 0;
-    if (const char* e = getenv("RRI_PASS_WGS")) {
-        const int nrb_t = std::max(1, std::max(1, atoi(e)) / c->npanels);
-        rpb = (n + nrb_t - 1) / nrb_t;
-    } else {
+    {
         // handles whose passes write a residual back (explicit-residual, dense weighted): the read-modify-write pass
         // likes ~8192 workgroups of >= 96 rows (+3 % at C3 for the residual schedule, +6 % for the weighted one)
         // (round 4) the one-pass weighted step: ~16384 workgroups of >= 48 rows -- 1.40 against 1.50 - 1.55 ms per pass at BASELINE
@@ -2251,15 +2055,14 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
             if (r >= rows_min || total == 512) rpb = r;
         }
     }
-    rpb = std::max<i64>(rpb, rpb_min);
+    rpb = std::max<i64>(rpb, 32);
     rpb = std::min<i64>(round_up(rpb, 16), rpb_cap);
     c->rpb = (int)rpb;
     c->nrb = (int)((n + rpb - 1) / rpb);
     if (c->sparse) {
         // no dense pass: the row copy is cut into column blocks (= Ypart panels), the column copy into row blocks
         // (= Zpart rows); block widths so that three factor tables of a block fit SP_BLOCK_BYTES of LDS
-        i64 block_bytes = SP_BLOCK_BYTES;
-        if (const char* e = getenv("RRI_SP_BLOCK_KB")) block_bytes = std::min<i64>(SP_BLOCK_BYTES, std::max(8, atoi(e)) * 1024LL);
+        const i64 block_bytes = SP_BLOCK_BYTES;
         // (X on CSR: ONE table of float64 factors per block, spx_block_cap -- k_spx_pass)
         const i64 cap = sparse_x ? std::min<i64>(spx_block_cap(), std::max<i64>(64, (block_bytes / 8 - 64) / 64 * 64))
                                  : block_bytes / (3 * (dtype == RRI_F32 ? 4 : 8));
@@ -2319,7 +2122,7 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     if (weighted) {
         const i64 zn = std::max<i64>(c->LD, n);
         if (!c->sparse) {
-            CR(big_malloc(&c->E, (size_t)n * c->LD * es_x));
+            CR(hipMalloc(&c->E, (size_t)n * c->LD * es_x));
             // k_resid writes the d real columns only; the passes stream all LD: the pad columns must hold zeros
             // (recycled memory there once held NaN patterns, which fmax(numer, 0) turned into zero rows of W)
             if (c->LD != d) CR(hipMemsetAsync(c->E, 0, (size_t)n * c->LD * es_x, c->stream));
@@ -2352,7 +2155,7 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     }
     if (explicit_resid) {
         const i64 zn = std::max<i64>(c->LD, n);
-        CR(big_malloc(&c->E, (size_t)n * c->LD * es_x));
+        CR(hipMalloc(&c->E, (size_t)n * c->LD * es_x));
         if (c->LD != d) CR(hipMemsetAsync(c->E, 0, (size_t)n * c->LD * es_x, c->stream));   // pad columns stay zero
         CR(hipMalloc((void**)&c->dwv, (size_t)n * f8));
         CR(hipMemsetAsync(c->dwv, 0, (size_t)n * f8, c->stream));
@@ -2543,8 +2346,7 @@ static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int
     rri_status s = csr_to_device(c, indptr, indices, data, nnz, data_dtype, dv);
     if (s != RRI_OK) return s;
     // one launch runs the items of both copies: half of the chip's CUs each, so that all of them are ONE round of workgroups
-    int target_items = std::max(1, c->n_cu / 2);
-    if (const char* e = getenv("RRI_SPX_ITEMS")) target_items = std::max(1, atoi(e));
+    const int target_items = std::max(1, c->n_cu / 2);
     s = build_sp_store(c, indptr, indices, nnz, data_dtype, dv, target_items);
     if (s != RRI_OK) return s;
     if (nnz > 0)
@@ -2699,10 +2501,6 @@ rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indi
         // lanes per segment: 4 quads of 4 entries per lane and iteration
         const i64 avg = nnz / std::max<i64>(1, (i64)cp.nblk * nseg);
         cp.lps = avg >= 768 ? 64 : avg >= 384 ? 32 : avg >= 192 ? 16 : 8;
-        if (const char* e = getenv(w == 0 ? "RRI_SP_LANES_ROW" : "RRI_SP_LANES_COL")) {
-            const int v = atoi(e);
-            if (v == 8 || v == 16 || v == 32 || v == 64) cp.lps = v;
-        }
         HIPCHK(c, hipMalloc((void**)&cp.segptr, sp.size() * sizeof(i64)));
         HIPCHK(c, hipMalloc((void**)&cp.idx, cntp * sizeof(unsigned short)));
         HIPCHK(c, hipMalloc(&cp.val, cntp * c->es));
@@ -2736,8 +2534,7 @@ rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int3
         for (i64 p = indptr[r] + 1; p < indptr[r + 1]; ++p)
             if (indices[p] <= indices[p - 1])
                 return fail(c, RRI_ERR_INVALID, "column indices of row %lld are not strictly increasing", r);
-    int target_items = std::max(1, c->n_cu);
-    if (const char* e = getenv("RRI_SP_ITEMS")) target_items = std::max(1, atoi(e));
+    const int target_items = std::max(1, c->n_cu);
     s = build_sp_store(c, indptr, indices, nnz, data_dtype, dv, target_items);
     if (s != RRI_OK) return s;
     HIPCHK(c, hipMalloc(&c->sp_e, (size_t)std::max<i64>(nnz, 1) * c->es));
@@ -2927,7 +2724,7 @@ rri_status rri_sweep_until(rri_ctx* c, int32_t n_sweeps, double obj_prev, double
     if (c->paused) return fail(c, RRI_ERR_INVALID, "a paused run is pending: resolve the event and call rri_resume");
     if (n_sweeps < 1 || !obj_hist || !sweeps_done) return fail(c, RRI_ERR_INVALID, "n_sweeps < 1, or no place for the history / the count");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!onchip_ok(c) || n_sweeps > ONCHIP_UNTIL_CAP || !g_onchip_obj)
+    if (!onchip_ok(c) || n_sweeps > ONCHIP_UNTIL_CAP || !c->sw.onchip_obj)
         return fail(c, RRI_ERR_UNSUPPORTED, "rri_sweep_until needs the register-resident sweep (rri_onchip_info) and at most %d sweeps", ONCHIP_UNTIL_CAP);
     r = ensure_x_sq(c);
     if (r != RRI_OK) return r;
@@ -3153,7 +2950,7 @@ static rri_status objective_terms(rri_ctx* c, double out[3], double* tn) {
         c->dt_pending = false;
         c->dw_pending = false;
         c->carry_valid = false;
-    } else if (c->xy_valid && !g_obj_direct) {
+    } else if (c->xy_valid && !c->sw.obj_direct) {
         // 1/2 ||X - W T||^2 = 1/2 ||X||^2 - sum_t <w_t, X t_t> + 1/2 <W^T W, T T^T>: the cross terms were left by
         // the W halves of the sweep that has just ended (k_wcol), ||X||^2 is taken once per X -- no pass over X.
         // The terms are of the size of ||X||^2: the result carries an absolute error of a few ulp of that
@@ -3256,7 +3053,7 @@ rri_status rri_objective_parts(rri_ctx* c, double out[3]) { return objective_ter
 rri_status rri_objective(rri_ctx* c, double* out) {
     CHECK_CTX(c);
     if (!out) return fail(c, RRI_ERR_INVALID, "out is NULL");
-    if (c->obj_track_valid && c->xy_valid && !c->weighted && !c->comm && !g_obj_direct) {
+    if (c->obj_track_valid && c->xy_valid && !c->weighted && !c->comm && !c->sw.obj_direct) {
         // the persistent sweep that has just ended left its objective (all terms but the constant): nothing to launch
         if (!c->have_X || !c->have_W || !c->have_T) return fail(c, RRI_ERR_INVALID, "X, W, T must be set");
         HIPCHK(c, hipSetDevice(c->device));

@@ -10,9 +10,9 @@
 // W-column term of the step before and this step's T-row term into E, writes E, and takes the row products b, nt AND the
 // column sums of the next topic; the term the W update then leaves pending reaches those sums through a pass over the mask
 // alone (k_wmcorr; see "one read-modify-write pass" below).  (2 + 2/32) n d s bytes per topic step with a bit-packed mask.
-// Rounds 1-3 (RRI_WPASS_ONE=0): pass B reads E, M and takes the row products, pass C applies both corrections, writes E and
-// takes the next column sums: (3 + 2/32) n d s.  E is refreshed from X, W, T (k_resid) once per sweep either way, so the
-// storage rounding of E never accumulates over more than k updates.
+// Rounds 1-3 took two passes (measured and removed, profiles/r04_wpass_one_variants.log): pass B read E, M and took the row
+// products, pass C applied both corrections, wrote E and took the next column sums: (3 + 2/32) n d s.  E is refreshed from
+// X, W, T (k_resid) once per sweep, so the storage rounding of E never accumulates over more than k updates.
 #pragma once
 #include "rri_kernels.hpp"
 

@@ -638,36 +638,68 @@ def test_plain_bench_run_is_lean_and_dumps_what_it_computed(tmp_path):
     assert relfro(W, dumps['full']['W']) < TOL[np.float32] and relfro(T, dumps['full']['T']) < TOL[np.float32]
 
 
-@pytest.mark.parametrize('shape', [(700, 333, 6), (257, 1030, 5), (1501, 100, 3), (5003, 1000, 22), (64, 4100, 2), (9, 7, 2), (300, 500, 1)])
-@pytest.mark.parametrize('store', [np.float32, np.float64])
-def test_the_lds_dma_pass_gives_the_register_pass_its_bits(monkeypatch, shape, store):
-    """k_pass_dma (round 4): the read-only pass with its rows staged through an LDS ring that LDS-DMA fills.  Same arithmetic in
-    the same order as k_pass, so the SAME BITS -- on ragged shapes (rows not a multiple of the chunk, columns not a multiple of
-    a lane's vector or of a panel, fewer columns than one wave covers, more panels than one workgroup), both storage types,
-    plain and topic-model flags, fixed halves, with and without interleaved row chunks.  The library takes the ring by itself only
-    where X streams from HBM; RRI_PASS_DMA=1 forces it here."""
-    from rri_nmf_amd.engine import RRIEngine
-    n, d, k = shape
-    X = planted_X(n, d, k, seed=n + d, dtype=store)
-    W0, T0 = scaled_init(X, k, seed=3)
-    T0s = T0 / T0.sum(1, keepdims=True)
-    monkeypatch.setenv('RRI_ONCHIP', '0')          # the launch-per-phase schedule: that is where the pass runs
+@pytest.mark.parametrize('case', ['onchip', 'wsweep', 'wmcorr'])
+def test_a_handle_keeps_the_switches_it_was_created_under(monkeypatch, case):
+    """rri_create reads the switches a handle keeps once, into the handle: a handle B created later, without
+    the switch, and kept alive does not change the schedule or the bits of a handle A created under it.  onchip: A stays on the
+    launch-per-phase schedule at a launch-bound shape that B takes on chip.  wsweep: A, with T fixed, keeps one W-half launch
+    per topic.  wmcorr: a dense weighted A with a sparse 0/1 mask keeps the correction that walks every bit and takes nw in
+    the pass, with B created between two of A's sweeps."""
+    monkeypatch.setenv('RRI_ONCHIP', '0')
+    if case == 'onchip':
+        n, d, k = 1500, 700, 8                        # launch-bound: one persistent launch per call where it is allowed
+        X = planted_X(n, d, k, seed=0, dtype=np.float32)
+        W0, T0 = scaled_init(X.astype(np.float64), k, seed=1)
+        kw, flags, sweeps = dict(dtype=np.float32), {}, (3,)
 
-    def run(dma, il, flags, T, sub='0'):
-        monkeypatch.setenv('RRI_PASS_DMA', dma)
-        monkeypatch.setenv('RRI_PASS_IL', il)
-        monkeypatch.setenv('RRI_PASS_DMA_SUB', sub)       # row blocks a workgroup of the ring kernel walks as one stream
-        monkeypatch.setenv('RRI_PASS_WGS', '64' if sub != '0' else '2048')   # several row blocks even at these sizes
-        with RRIEngine(n, d, k, dtype=store) as e:
-            e.upload_X(X), e.set_W(W0), e.set_T(T), e.set_params(**flags)
-            e.sweep(3)
-            return e.get_W(), e.get_T(), e.objective()
+        def start(e):
+            e.upload_X(X); e.set_W(W0); e.set_T(T0); e.set_params(**flags)
+    elif case == 'wsweep':
+        n, d, k = 203, 141, 6
+        X = planted_X(n, d, k, seed=k, dtype=np.float64)
+        W0, T0 = scaled_init(X, k, seed=1)
+        kw, flags, sweeps = dict(dtype=np.float64), dict(fix_T=True, reset_topic_method=None), (3,)
+        monkeypatch.setenv('RRI_WSWEEP', '0')
 
-    for flags, T in ((dict(), T0), (dict(project_T_each_iter=True, t_row_sum=1.0, w_row_sum=1.0), T0s), (dict(fix_W=True), T0),
-                     (dict(reg_w_l1=0.01, reg_t_l2=0.02), T0)):
-        for il in ('0', '1'):
-            a, b = run('1', il, flags, T), run('0', il, flags, T)
-            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2], (flags, il, relfro(a[0], b[0]), relfro(a[1], b[1]))
-        # three row blocks per workgroup (contiguous rows), the last group ragged: still one row of column sums per row block
-        a, b = run('1', '0', flags, T, sub='3'), run('0', '0', flags, T, sub='3')
-        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2], (flags, 'sub 3', relfro(a[0], b[0]), relfro(a[1], b[1]))
+        def start(e):
+            e.upload_X(X); e.set_W(W0); e.set_T(T0); e.set_params(**flags)
+            e.timing_enable(True)
+    else:
+        n, d, k = 700, 333, 6
+        X = planted_X(n, d, k, seed=n, dtype=np.float64)
+        W0, T0 = scaled_init(X, k, seed=1)
+        M = (np.random.RandomState(2).rand(n, d) < 0.06).astype(np.float64)    # below 12 %: the set-bits kernel by default
+        M[0, :] = 1.0
+        Xm = M * X
+        kw, flags, sweeps = dict(dtype=np.float64, weighted=True), dict(t_row_sum=1.0, reset_topic_method=None), (2, 2)
+        monkeypatch.setenv('RRI_WMCORR_COLS', '0')
+        monkeypatch.setenv('RRI_WNW_MASK', '0')
+
+        def start(e):
+            e.upload_X(Xm); e.upload_mask(M); e.set_W(W0); e.set_T(T0); e.set_params(**flags)
+    switches = ('RRI_WSWEEP', 'RRI_WMCORR_COLS', 'RRI_WNW_MASK') + (('RRI_ONCHIP',) if case == 'onchip' else ())
+
+    with engine(n, d, k, **kw) as alone:
+        start(alone)
+        for s in sweeps:
+            alone.sweep(s)
+        want = alone.get_W(), alone.get_T(), alone.objective()
+    with engine(n, d, k, **kw) as a:
+        start(a)
+        for s in sweeps[:-1]:
+            a.sweep(s)
+        for key in switches:
+            monkeypatch.delenv(key, raising=False)
+        with engine(n, d, k, **kw) as b:
+            start(b)
+            a.sweep(sweeps[-1])
+            got = a.get_W(), a.get_T(), a.objective()
+            b.sweep(sweeps[-1])
+            if case == 'onchip':
+                assert a.onchip_info()[1] == 0, a.onchip_info()
+                assert b.onchip_info()[1] >= 1, ('the shape takes the persistent launch', b.onchip_info())
+            elif case == 'wsweep':
+                assert a.timing_read(1)[0] >= sweeps[-1] * k, ('a launch per topic expected', a.timing_read(1))
+                assert b.timing_read(1)[0] == sweeps[-1], ('one launch per sweep expected', b.timing_read(1))
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and got[2] == want[2], \
+        (case, relfro(got[0], want[0]), relfro(got[1], want[1]))
