@@ -321,6 +321,21 @@ rri_status rri_synchronize(rri_ctx* ctx);
  * rri_sweep take that path; *launches: how many it has taken on this handle.  RRI_ONCHIP=0 (environment, read by
  * rri_create) switches it off.  Either pointer may be NULL. */
 rri_status rri_onchip_info(rri_ctx* ctx, int32_t* eligible, int64_t* launches);
+/* What the handle decided about its layout and routes, for tests and diagnostics; changes nothing.  Fills out[0 .. min(n,
+ * RRI_LAYOUT_FIELDS)):
+ *   0..3   the row copy of a blocked CSR store (pattern-only weighted and CSR-X handles, after the upload; 0 on dense handles):
+ *          column blocks, block width (factors per LDS table), lanes per segment, work items;   4..7  the same of the column copy
+ *   8..10  rows per row block, row blocks and column panels of the streaming pass (blocked store: 10 = column blocks of the row
+ *          copy, 9 = row blocks of the column copy)
+ *   11     a bit-packed 0/1 mask exists;   12  its column-major copy exists;   13  the measured mask density in 1e-9, -1 before
+ *          it has been measured (the column-major copy is made, or given up, by the first topic step that wants it)
+ *   14     dense weighted: rri_sweep takes the fused T-row launch (few row blocks, one device)
+ *   15     dense weighted: the last T-row step took nw = (w^2)^T M from the mask-only kernel, not from the pass
+ *   16     dense handles: read-only passes deal their row blocks interleaved (few workgroups)
+ *   17     row blocks of the last mask-only correction launch (0 before the first);   18  compute units of the device (the cap
+ *          of a blocked copy's work items) */
+#define RRI_LAYOUT_FIELDS 19
+rri_status rri_layout_info(rri_ctx* ctx, int64_t* out, int32_t n);
 /* The exchanges of that launch poll a bounded number of times.  When its workgroups cannot all run at once (a device shared
  * with another process, CUs masked away) the launch gives up, and the call does what the reference's sweep does under any
  * scheduling (nmf.py:415-476): it completes -- W and T are put back to what they were before the launch and the same steps

@@ -11,6 +11,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RRI_HIP_LIB', os.path.join(_PKG, 'lib', 'librri_hip.so'))
 
 RRI_GRAM_SLICES = 8     # include/rri_hip.h
+RRI_LAYOUT_FIELDS = 19  # include/rri_hip.h
 RRI_MAX_K = 1024        # include/rri_hip.h: rri_create refuses a larger k (RRI_ERR_UNSUPPORTED)
 RRI_OK, RRI_PAUSED = 0, 1
 RRI_ERR_INVALID, RRI_ERR_HIP, RRI_ERR_UNSUPPORTED = -1, -2, -3
@@ -108,6 +109,7 @@ PROTOTYPES = {
     'rri_timing_read': (_I32, [_P, _I32, C.POINTER(_I64), C.POINTER(_D)]),
     'rri_onchip_info': (_I32, [_P, C.POINTER(_I32), C.POINTER(_I64)]),
     'rri_onchip_fallbacks': (_I32, [_P, C.POINTER(_I64)]),
+    'rri_layout_info': (_I32, [_P, C.POINTER(_I64), _I32]),
     'rri_debug_xcc': (_I32, [_P, C.POINTER(_I32), _I32]),
     'rri_sweep_until': (_I32, [_P, _I32, _D, _D, C.POINTER(_D), C.POINTER(_I32)]),
     'rri_synchronize': (_I32, [_P]),

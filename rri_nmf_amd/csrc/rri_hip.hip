@@ -291,6 +291,10 @@ struct rri_ctx {
 
     std::string err;
 };
+// read-only passes deal their row blocks as interleaved chunks only while the launch has few workgroups (the passes that write
+// the matrix back always do): ONE predicate for the launch sites and for rri_layout_info
+static inline bool ro_pass_interleaved(const rri_ctx* c) { return c->npanels * c->nrb <= 1024; }
+
 
 namespace {
 
@@ -497,7 +501,7 @@ struct LaunchX {
                            // linear stream does.  Read-only pass: +2 % up to 1024 workgroups (20000 x 5000), -1 % at C3, where
                            // it stays off.  Read-modify-write (UPD): +4-9 % at C3 (profiles/r02_residual_schedule_geometry.log)
                            // -- reads and writes of a window stay in the DRAM pages that are open
-                           ((c->npanels * c->nrb <= 1024 || UPD > 0) ? c->nrb : 0) |
+                           ((ro_pass_interleaved(c) || UPD > 0) ? c->nrb : 0) |
                                ((c->sw.pass_rot >= 0 ? c->sw.pass_rot : (UPD > 0 ? c->rot_r : c->rot_x)) << 27));
     }
     // The read-only pass: 8 rows in flight per wave, the row dots (DO_Y) through LDS row sums.  The read-modify-write variants:
@@ -563,7 +567,7 @@ struct LaunchX {
                                wc, a1, b1, a2, b2, c->Ypart, c->Y2part, c->Zpart, c->Z2part, c->LD, c->rpb, c->npanels,
                                (const DevState*)c->st,
                                // interleaved row chunks for the passes that write E back (read-modify-write), as for k_pass<UPD>
-                               ((WRITE || c->npanels * c->nrb <= 1024) ? c->nrb : 0) | rot);
+                               ((WRITE || ro_pass_interleaved(c)) ? c->nrb : 0) | rot);
         }
     }
     // Rows in flight.  The one-pass step (row products and a write): 4, DPP row sums -- 1.458 ms at BASELINE config 5 against
@@ -3758,6 +3762,25 @@ rri_status rri_onchip_info(rri_ctx* c, int32_t* eligible, int64_t* launches) {
     CHECK_CTX(c);
     if (eligible) *eligible = (c->have_X && c->have_params && onchip_ok(c)) ? 1 : 0;
     if (launches) *launches = c->onchip_launches;
+    return RRI_OK;
+}
+
+// what the handle decided about its layout and routes (read-only; the order is the header's)
+rri_status rri_layout_info(rri_ctx* c, int64_t* out, int32_t n) {
+    CHECK_CTX(c);
+    if (!out || n < 1) return fail(c, RRI_ERR_INVALID, "rri_layout_info needs room for at least one value");
+    const bool dense_w = c->weighted == RRI_WEIGHTED_DENSE;
+    const int64_t v[RRI_LAYOUT_FIELDS] = {
+        c->sparse ? c->sp[0].nblk : 0, c->sparse ? c->sp[0].bw : 0, c->sparse ? c->sp[0].lps : 0, c->sparse ? c->sp[0].nwork : 0,
+        c->sparse ? c->sp[1].nblk : 0, c->sparse ? c->sp[1].bw : 0, c->sparse ? c->sp[1].lps : 0, c->sparse ? c->sp[1].nwork : 0,
+        c->rpb, c->nrb, c->npanels,
+        c->Mbits ? 1 : 0, c->Mcols ? 1 : 0,
+        c->mcols_tried && c->Mbits ? (int64_t)(c->mask_density * 1.0e9 + 0.5) : -1,
+        dense_w && wtrow_small(c) ? 1 : 0,
+        dense_w && c->nw_mask ? 1 : 0,
+        !c->sparse && ro_pass_interleaved(c) ? 1 : 0,
+        c->wcorr_nrb, c->n_cu};
+    for (int i = 0; i < n && i < RRI_LAYOUT_FIELDS; ++i) out[i] = v[i];
     return RRI_OK;
 }
 

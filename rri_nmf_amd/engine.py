@@ -619,6 +619,27 @@ class RRIEngine(object):
         self._check(self._lib.rri_onchip_info(self._h, C.byref(el), C.byref(n)))
         return bool(el.value), int(n.value)
 
+    # rri_layout_info: four values per copy of a blocked store (row copy, then column copy), then one value per name
+    LAYOUT_COPY_FIELDS = ('nblk', 'bw', 'lps', 'nwork')
+    LAYOUT_FIELDS = ('rpb', 'nrb', 'npanels', 'mask_bits', 'mask_cols', 'mask_density', 'wtrow_small', 'nw_from_mask',
+                     'interleaved', 'wcorr_nrb', 'n_cu')
+    assert 2 * len(LAYOUT_COPY_FIELDS) + len(LAYOUT_FIELDS) == _capi.RRI_LAYOUT_FIELDS
+
+    def layout_info(self):
+        """what the handle decided (rri_layout_info): per-copy values of a blocked CSR store as (row copy, column copy) pairs --
+        nblk, bw, lps, nwork -- the pass geometry rpb / nrb / npanels, and which routes of the dense weighted step are taken
+        (mask_density is None until the first topic step has measured it; nw_from_mask is what the last T-row step did)"""
+        nc = len(self.LAYOUT_COPY_FIELDS)
+        out = (C.c_int64 * _capi.RRI_LAYOUT_FIELDS)()
+        self._check(self._lib.rri_layout_info(self._h, out, _capi.RRI_LAYOUT_FIELDS))
+        v = [int(x) for x in out]
+        info = {name: (v[i], v[nc + i]) for i, name in enumerate(self.LAYOUT_COPY_FIELDS)}
+        info.update(zip(self.LAYOUT_FIELDS, v[2 * nc:]))
+        for name in ('mask_bits', 'mask_cols', 'wtrow_small', 'nw_from_mask', 'interleaved'):
+            info[name] = bool(info[name])
+        info['mask_density'] = None if info['mask_density'] < 0 else info['mask_density'] * 1e-9
+        return info
+
     def debug_xcc(self, count=32):
         """diagnostics: the XCD each of `count` workgroups of a launch on this handle's stream lands on"""
         out = (C.c_int32 * count)()

@@ -240,16 +240,20 @@ class ResidentProblem(object):
     of X and W_mat (the very objects), their shapes and types, k, the storage type, the device, the schedule and the
     preprocessing asked for are those of the call that made it, and makes (and keeps) a new one otherwise.  What the estimators'
     `one_iter` loop saves at 100000 x 10000 is the upload and the handle per call (sklearn_interface.py:316-318 re-runs nmf() on
-    the same X every time).  The caller promises not to modify X or W_mat in place between the calls -- nothing here can notice --
-    and closes the holder (`close()`, or its end of life) when done.  Not for row-sharded calls or per-row weights."""
+    the same X every time).  The holder keeps a reference to X and W_mat while it keeps the handle, and reuse compares with `is`:
+    an id() alone is handed to the next array of the same size once the first one is freed, and the handle would answer for a
+    matrix that no longer exists.  The caller promises not to modify X or W_mat in place between the calls -- nothing here can
+    notice -- and closes the holder (`close()`, or its end of life) when done.  Not for row-sharded calls or per-row weights."""
 
     def __init__(self):
         self.engine = None
         self.key = None
+        self.given = (None, None)   # the X and W_mat objects of the call that made the handle
         self.idf = None
         self.reuses = 0
 
     def close(self):
+        self.given = (None, None)
         if self.engine is not None:
             try:
                 self.engine.close()
@@ -575,12 +579,13 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         if group is not None or w_row is not None or (spec is not None and device_spec is None):
             raise ValueError('resident= keeps a handle for plain calls: no group, no w_row, no host-side preprocessing')
         tf_opt = None if device_spec is None else (device_spec['tfidf'] if isinstance(device_spec['tfidf'], bool) else 'given')
-        res_key = (id(X_given), tuple(X.shape), str(getattr(X, 'dtype', None)), None if W_mat_given is None else id(W_mat_given),
-                   int(k), str(sdt), device, sparse_pattern, schedule, sparse_X,
+        res_key = (tuple(X.shape), str(getattr(X, 'dtype', None)), W_mat_given is None, int(k), str(sdt), device,
+                   sparse_pattern, schedule, sparse_X,
                    None if device_spec is None else (tf_opt, bool(device_spec['normalize'])))
         if tf_opt == 'given':
             res_key = None               # an idf vector from outside: not worth telling apart -- a fresh handle
-    reused = resident is not None and resident.engine is not None and res_key is not None and resident.key == res_key
+    reused = (resident is not None and resident.engine is not None and res_key is not None and resident.key == res_key
+              and resident.given[0] is X_given and resident.given[1] is W_mat_given)
     if reused:
         eng = resident.engine
         eng.begin_run()
@@ -603,6 +608,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             X_init = _ResidentX(eng)
         if resident is not None and res_key is not None and not reused:
             resident.engine, resident.key, resident.idf = eng, res_key, rtv.get('idf')
+            resident.given = (X_given, W_mat_given)
         W, T = _initialize_and_validate(W_in=W_in, T_in=T_in, W_mat=W_mat, X=X_init, k=k, init=init,
                                         random_state=random_state, project_T_each_iter=project_T_each_iter,
                                         project_W_each_iter=project_W_each_iter, w_row_sum=w_row_sum,

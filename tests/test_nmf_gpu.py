@@ -127,6 +127,81 @@ def test_resident_handle_between_fit_and_one_iter(monkeypatch, prep):
     assert holder.engine is None and kept._resident.engine is None
 
 
+def _freed_and_reallocated(make_first, make_second, use_first):
+    """use_first(A) with A = make_first(); A is freed; then B = make_second() -- up to 20 of them, all kept alive so that each gets
+    another address -- until one has A's id(), which CPython hands to a next array of the same size as a rule.  Returns
+    (B, whether the id collided)."""
+    A = make_first()
+    old = id(A)
+    use_first(A)
+    del A
+    tried = []
+    for _ in range(20):
+        tried.append(make_second())
+        if id(tried[-1]) == old:
+            return tried[-1], True
+    return tried[0], False
+
+
+@pytest.mark.parametrize('what', ['X', 'W_mat', 'estimator-tfidf'])
+def test_resident_handle_does_not_answer_for_a_freed_array(monkeypatch, what):
+    """The holder's handle belongs to the very objects it was made from.  Once X (or W_mat) is freed, the next array of that shape
+    and type usually gets the same id(): a call with it must upload again, count no reuse, and give what a call without holder
+    gives -- not factorise the matrix (with the idf) still on the device.  The outcome is asserted whether or not the id
+    collided this time."""
+    nmf_mod, si = api()
+    from rri_nmf_amd.engine import RRIEngine
+    g = load_golden('g1_tm_estimator')
+    X0 = np.ascontiguousarray(g['X'], dtype=np.float64)
+    n, d = X0.shape
+    rs = np.random.RandomState(3)
+    Xb = np.ascontiguousarray(X0[rs.permutation(n)][:, rs.permutation(d)] * (0.5 + rs.rand(n, d)))   # other values and other df
+    uploads = []
+    for name in ('upload_X', 'upload_mask'):
+        real = getattr(RRIEngine, name)
+        monkeypatch.setattr(RRIEngine, name, lambda self, A, real=real, name=name: (uploads.append(name), real(self, A))[1])
+    kw = dict(max_iter=3, random_state=0, eps_stop=-1)
+    if what == 'X':
+        holder = nmf_mod.ResidentProblem()
+        X2, collided = _freed_and_reallocated(X0.copy, Xb.copy, lambda A: nmf_mod.nmf(A, 5, resident=holder, **kw))
+        assert uploads == ['upload_X'] and holder.reuses == 0
+        got = nmf_mod.nmf(X2, 5, resident=holder, **kw)
+        assert uploads == ['upload_X'] * 2 and holder.reuses == 0, (uploads, holder.reuses, collided)
+        holder.close()
+        want = nmf_mod.nmf(X2, 5, **kw)
+    elif what == 'W_mat':
+        M1 = (rs.rand(n, d) < 0.6).astype(np.float64)
+        Mb = (rs.rand(n, d) < 0.6).astype(np.float64)
+        kw.update(t_row_sum=1.0, reset_topic_method=None)
+        holder = nmf_mod.ResidentProblem()
+        M2, collided = _freed_and_reallocated(M1.copy, Mb.copy, lambda A: nmf_mod.nmf(X0, 5, W_mat=A, resident=holder, **kw))
+        assert uploads == ['upload_X', 'upload_mask'] and holder.reuses == 0
+        got = nmf_mod.nmf(X0, 5, W_mat=M2, resident=holder, **kw)
+        assert uploads == ['upload_X', 'upload_mask'] * 2 and holder.reuses == 0, (uploads, holder.reuses, collided)
+        # the same objects again: this is the call the holder is for
+        again = nmf_mod.nmf(X0, 5, W_mat=M2, resident=holder, **kw)
+        assert len(uploads) == 4 and holder.reuses == 1 and np.array_equal(again['W'], got['W'])
+        holder.close()
+        want = nmf_mod.nmf(X0, 5, W_mat=M2, **kw)
+    else:
+        ekw = dict(random_state=0, max_iter=3, do_final_project_W=False, handle_tfidf=True, handle_normalization=True,
+                   nmf_kwargs={'eps_stop': -1})
+        kept = si.NMF_TM_Estimator(n, d, 5, keep_resident=True, **ekw)
+        # (the outputs of a fit keep X alive through their objective calculator: dropped here, as a caller short of memory would)
+        X2, collided = _freed_and_reallocated(X0.copy, Xb.copy, lambda A: (kept.fit(A), setattr(kept, 'nmf_outputs', None)))
+        assert uploads == ['upload_X'] and kept._resident.reuses == 0
+        idf1, W1, T1 = np.array(kept.idf), kept.W.copy(), kept.T.copy()
+        kept = kept.fit(X2)                  # continues from the first fit's factors (the estimator's warm start)
+        assert uploads == ['upload_X'] * 2 and kept._resident.reuses == 0, (uploads, kept._resident.reuses, collided)
+        kept.release()
+        fresh = si.NMF_TM_Estimator(n, d, 5, W=W1, T=T1, **ekw).fit(X2)
+        assert not np.array_equal(fresh.idf, idf1), 'the second matrix must have another idf for this test to see a stale one'
+        assert np.array_equal(kept.idf, fresh.idf)
+        got, want = dict(W=kept.W, T=kept.T), dict(W=fresh.W, T=fresh.T)
+    assert np.array_equal(got['W'], want['W']) and np.array_equal(got['T'], want['T']), (
+        'id collided: %s' % collided, relfro(got['W'], want['W']), relfro(got['T'], want['T']))
+
+
 def test_logger_level_switches_objective_tracking():
     nmf_mod, _ = api()
     X = planted_X(200, 120, 4, dtype=np.float64)

@@ -66,7 +66,9 @@ def test_sparse_pattern_matches_dense_weighted_engine(name, store):
 
 @pytest.mark.parametrize('frac,n,d', [(0.02, 900, 300), (0.6, 120, 90), (0.08, 64, 2100)])
 def test_sparse_pattern_matches_oracle(frac, n, d):
-    """short and long segments (8 ... 64 lanes per row / column), against the numpy restatement of nmf.py:687-746"""
+    """a sparse, a dense and a wide pattern against the numpy restatement of nmf.py:687-746, float64.  All three average fewer
+    than 192 entries per (block, segment), so every one runs 8 lanes per segment; 16 / 32 / 64 lanes and the thresholds between
+    them are reached in tests/test_weighted_sparse_buckets_gpu.py"""
     from oracle import rri_oracle as orc
     k = 4
     X, M, W0, T0 = _problem(n, d, k, frac, seed=3)
