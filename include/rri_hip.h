@@ -58,7 +58,17 @@ enum {
     RRI_ERR_COMM = -7            /* a collective (RCCL, or the caller's transport) failed                   */
 };
 
-enum { RRI_F32 = 0, RRI_F64 = 1 };   /* storage type of X, mask, residual in HBM (arithmetic is float64) */
+enum { RRI_F32 = 0, RRI_F64 = 1,     /* storage type of X, mask, residual in HBM (arithmetic is float64) */
+       /* float16 (IEEE binary16): for the dense X of an RRI_UNWEIGHTED handle only -- the one flavour in which the stored matrix is
+        * never rewritten, so the storage type costs exactly one rounding, at upload (to nearest even, one step from the host
+        * type), and a float16 value converts to float64 exactly: the handle solves the float64 problem on the ROUNDED X.  Half the
+        * bytes of fp32 per pass and per matrix.  Suits magnitudes below 65520 and data of 11 significant bits: integers up to 2048
+        * (term counts, ratings, pixels, 0/1) are stored exactly; otherwise the relative rounding is 2^-11 above 6.1e-5 and the
+        * absolute one 3e-8 below it (rri_storage_error reports what it came to).  rri_create refuses it (RRI_ERR_UNSUPPORTED) for
+        * the four other flavours; the handle refuses everything that would rewrite X or needs a mask, a residual or a CSR store
+        * (rri_scale_X, rri_column_positive_counts, rri_upload_mask*, rri_bind_mask_device, rri_upload_X_csr, rri_upload_observed_csr,
+        * rri_residual_*, rri_get_residual, rri_bench_*) and rri_attach_comm, and never takes the persistent on-chip path. */
+       RRI_F16 = 2 };
 /* rri_create's `weighted`: the flavour of the handle */
 enum { RRI_UNWEIGHTED = 0, RRI_WEIGHTED_DENSE = 1, RRI_WEIGHTED_SPARSE = 2, RRI_UNWEIGHTED_RESIDUAL = 3,
        RRI_UNWEIGHTED_SPARSE = 4 };
@@ -92,7 +102,7 @@ typedef struct rri_event {
 
 /* ---- lifetime ------------------------------------------------------------------ */
 uint32_t   rri_abi_version(void);
-/* dtype: RRI_F32 / RRI_F64.  weighted: RRI_UNWEIGHTED; RRI_WEIGHTED_DENSE reserves the mask and masked-residual
+/* dtype: RRI_F32 / RRI_F64, or RRI_F16 with RRI_UNWEIGHTED (see the enum).  weighted: RRI_UNWEIGHTED; RRI_WEIGHTED_DENSE reserves the mask and masked-residual
  * buffers of the elementwise-weighted flavour (WRRI, nmf.py:687-701,735-746) as dense n x d arrays;
  * RRI_WEIGHTED_SPARSE keeps that flavour on a 0/1 observation pattern only (rri_upload_observed_csr).
  * RRI_UNWEIGHTED_RESIDUAL is the unweighted flavour on the EXPLICIT residual R = X - W T (kept in HBM beside X): every
@@ -113,14 +123,22 @@ rri_status rri_destroy(rri_ctx* ctx);
 const char* rri_last_error(const rri_ctx* ctx);   /* NULL ctx: error of the last failed rri_create */
 
 /* ---- data: replaces the numpy arrays nmf() holds (nmf.py:272,351,867-868) --------- */
-/* host_dtype: RRI_F32 / RRI_F64 of the HOST buffer; converted to the handle's dtype. */
+/* host_dtype: RRI_F32 / RRI_F64 of the HOST buffer; converted to the handle's dtype.  rri_upload_X on an RRI_F16 handle also
+ * takes a host buffer of halves (RRI_F16); whatever the host type, a value that is not finite as a float16 (|x| >= 65520, inf,
+ * NaN) fails the call with RRI_ERR_INVALID and leaves the handle without an X. */
 rri_status rri_upload_X(rri_ctx* ctx, const void* host, int64_t ld, int32_t host_dtype);
 rri_status rri_upload_mask(rri_ctx* ctx, const void* host, int64_t ld, int32_t host_dtype); /* W_mat */
 /* Zero-copy alternative: X (and mask) already in device memory in the handle's dtype,
  * row-major with row stride ld (a multiple of 16 bytes, base 16-byte aligned).  The calls synchronise the device
  * once, so memory just produced on another stream is complete (rri_bind_mask_device reads the mask at once to
  * bit-pack it); later changes to the memory are the caller's to order against the handle's stream. */
+/* (an RRI_F16 handle binds an array of halves, e.g. a torch.float16 tensor: ld a multiple of 8 elements) */
 rri_status rri_bind_X_device(rri_ctx* ctx, const void* dev, int64_t ld);
+/* What storing X cost: out[0] = sum (x - stored(x))^2, out[1] = sum x^2 over the matrix given to the last rri_upload_X of an
+ * RRI_F16 handle (float64 sums in a fixed order; sqrt(out[0] / out[1]) is the relative Frobenius distance between the caller's
+ * X and the X the handle factorises -- the rounding nmf() adds to a float64 run, nmf.py:272).  Zeros on float32 / float64 handles
+ * and for bound arrays, which are taken as they are. */
+rri_status rri_storage_error(rri_ctx* ctx, double out[2]);
 rri_status rri_bind_mask_device(rri_ctx* ctx, const void* dev, int64_t ld);
 /* Ingestion without host densification (the reference densifies with .toarray(), sklearn_interface.py:78-102):
  * X from host CSR arrays (indptr n+1 int64, indices int32 column ids, data of data_dtype) scattered into the

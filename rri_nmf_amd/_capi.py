@@ -17,7 +17,7 @@ RRI_OK, RRI_PAUSED = 0, 1
 RRI_ERR_INVALID, RRI_ERR_HIP, RRI_ERR_UNSUPPORTED = -1, -2, -3
 RRI_ERR_UNBOUNDED, RRI_ERR_W_COL_ZERO, RRI_ERR_NOT_IMPLEMENTED, RRI_ERR_COMM = -4, -5, -6, -7
 RRI_COMM_ID_BYTES = 128
-RRI_F32, RRI_F64 = 0, 1
+RRI_F32, RRI_F64, RRI_F16 = 0, 1, 2   # RRI_F16: the dense X of an RRI_UNWEIGHTED handle only (include/rri_hip.h)
 # rri_create's `weighted`: the flavour of the handle
 RRI_UNWEIGHTED, RRI_WEIGHTED_DENSE, RRI_WEIGHTED_SPARSE, RRI_UNWEIGHTED_RESIDUAL, RRI_UNWEIGHTED_SPARSE = 0, 1, 2, 3, 4
 RESET_NONE, RESET_MAX_RESID_DOCUMENT, RESET_RANDOM = 0, 1, 2
@@ -55,6 +55,7 @@ PROTOTYPES = {
     'rri_upload_X': (_I32, [_P, _P, _I64, _I32]),
     'rri_upload_mask': (_I32, [_P, _P, _I64, _I32]),
     'rri_bind_X_device': (_I32, [_P, _P, _I64]),
+    'rri_storage_error': (_I32, [_P, C.POINTER(_D)]),
     'rri_bind_mask_device': (_I32, [_P, _P, _I64]),
     'rri_upload_X_csr': (_I32, [_P, C.POINTER(_I64), C.POINTER(_I32), _P, _I64, _I32]),
     'rri_upload_mask_csr_pattern': (_I32, [_P, C.POINTER(_I64), C.POINTER(_I32), _P, _I64, _I32]),

@@ -64,7 +64,9 @@ def print_report(text):
             kk, vv = body.split(':', 1)
             cur[kk.strip()] = vv.strip()
     for r in rows:
-        name = subprocess.run(['c++filt', r['name']], stdout=subprocess.PIPE, text=True).stdout.strip()
+        # (binutils' c++filt does not know DF16_, the mangling of _Float16: Dh, __fp16's, demangles the same way otherwise)
+        name = subprocess.run(['c++filt', r['name'].replace('DF16_', 'Dh')], stdout=subprocess.PIPE, text=True).stdout.strip()
+        name = re.sub(r'\bhalf\b', '_Float16', name)
         name = re.sub(r'\(.*', '', name)
         name = name.replace('void ', '').replace('rri::', '')
         print('%-64s vgpr %-4s agpr %-3s sgpr %-4s spill %s/%s  lds %-6s occ %s' % (

@@ -4,7 +4,8 @@
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -shared -fPIC -Iinclude rri_nmf_amd/csrc/rri_hip.hip
 //
 // Data layout in HBM (one handle = one nmf() call = one row shard of one GPU).  X (and the mask /
-// masked residual) are stored in the handle's dtype (fp32 or fp64); everything else is float64:
+// masked residual) are stored in the handle's dtype (fp32 or fp64; float16 for the read-only dense X of an RRI_UNWEIGHTED
+// handle, DISPATCH_RO); everything else is float64:
 //   X     n x LD   row-major, LD = d rounded up to a 16-byte multiple of X's type, pad columns zero
 //   Wt    k x n    k-major (W transposed): column t of W is the contiguous row Wt[t,:], so the
 //                  streaming pass stages the active column into LDS with coalesced loads
@@ -143,6 +144,7 @@ struct rri_ctx {
     i64 n = 0, d = 0, LD = 0;
     int k = 0, dtype = RRI_F32, weighted = 0, device = 0;
     size_t es = 4;  // element size of X / mask / residual; all other buffers are float64
+    double store_err[2] = {0.0, 0.0};   // rri_storage_error: sum (x - stored(x))^2 and sum x^2 of the last rri_upload_X
     int VN = 4, PW = 1024;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -267,7 +269,7 @@ struct rri_ctx {
     i64 row_offset = 0, n_global = 0;
     double* ctail = nullptr;   // 8 doubles (device): small collectives (column verdicts, objective parts)
     double* cand = nullptr;    // 2 * world doubles (device): candidates of the max-residual reset
-    rri_status comm_status = RRI_OK;   // first failure of a collective inside an enqueued sequence
+    rri_status comm_status = RRI_OK;   // first failure of a collective inside an enqueued sequence (or of a dispatch: f16_unreachable)
 
     // register-resident sweeps (rri_onchip_kernels.hpp): per-workgroup partial arrays and the grid barrier's counter
     int n_cu = 0;
@@ -470,11 +472,25 @@ struct TimedScope {
     }
 };
 
+// element sizes of the storage types (0: not a storage type)
+size_t dtype_size(int dt) { return dt == RRI_F32 ? 4 : dt == RRI_F64 ? 8 : dt == RRI_F16 ? 2 : 0; }
+
+// a float16 handle reached a kernel family that does not exist for it: reported like a failed step of an enqueued sequence
+void f16_unreachable(rri_ctx* c) {
+    if (c->comm_status == RRI_OK) {
+        c->comm_status = RRI_ERR_UNSUPPORTED;
+        c->err = "this operation rewrites X or needs a mask, a residual or a CSR store: not available on an RRI_F16 handle";
+    }
+}
+
 // ---- typed launch helpers ------------------------------------------------------------------
 // kernels that touch X / mask / residual depend on the storage type SX; the rest is float64
 template <typename SX>
 struct LaunchX {
     typedef SX Elem;
+    // float16 storage is read-only (RRI_F16: dense X, Gram form): only the members DISPATCH_RO reaches are ever instantiated for
+    // it, and inside those the branches to the CSR, masked and residual-writing kernels are compiled out
+    static constexpr bool RO = std::is_same<SX, _Float16>::value;
     // row-dot slots of the 4 waves, the active W column, (UPD: one or two arrays of rank-one row factors,) the row-sum tiles
     static size_t pass_shmem(const rri_ctx* c, int upd) {
         return ((5 + upd) * (size_t)c->rpb + 4 * 8 * 72) * sizeof(double);
@@ -520,9 +536,11 @@ struct LaunchX {
     template <bool DO_Y, bool DO_Z>
     static void pass(rri_ctx* c, int t, int tz, const TgramJob& job = TgramJob{}) {
         TimedScope ts(c, 0);
-        if (c->sparse_x) {    // X on CSR: the read-only pass over its two blocked copies (no side job: the caller runs k_tgram)
-            spx_pass<DO_Y, DO_Z>(c, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw);
-            return;
+        if constexpr (!RO) {
+            if (c->sparse_x) {    // X on CSR: the read-only pass over its two blocked copies (no side job: the caller runs k_tgram)
+                spx_pass<DO_Y, DO_Z>(c, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw);
+                return;
+            }
         }
         pass_cfg<DO_Y, DO_Z, 0>(c, c->X, c->ldx, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw, Upd{}, job);
     }
@@ -790,8 +808,10 @@ struct LaunchX {
         }
     }
     static void xtt(rri_ctx* c) {
-        if (c->sparse_x) spx_xtt(c, c->T, c->k, c->Qt);
-        else xtt_any(c, c->T, c->k, c->Qt);
+        if constexpr (!RO) {
+            if (c->sparse_x) { spx_xtt(c, c->T, c->k, c->Qt); return; }
+        }
+        xtt_any(c, c->T, c->k, c->Qt);
     }
     // column sums against NV = 8 row-vectors at once (Qt: 8 x n, stride ldw): out rows <- X^T q_v
     static void colsums8(rri_ctx* c, const double* Qt, int nv, double* zmulti, double* out_rows) {
@@ -811,6 +831,40 @@ struct LaunchX {
         return ((size_t)(resid_w_resident(c) ? c->k : 32) * 64 + 32 * 64) * sizeof(double) + 64 * 17 * sizeof(double);
     }
     static void resid(rri_ctx* c, bool masked, bool write_e, double* rowobj, double* rowpos) {
+        if constexpr (RO) {
+            resid_ro(c, rowobj, rowpos);       // no mask, nothing written: the two things a read-only handle asks of the residual
+            return;
+        } else {
+            resid_rw(c, masked, write_e, rowobj, rowpos);
+        }
+    }
+    // the row sums of the residual alone (objective, max-residual reset): MASKED = false, WRITE_E = false
+    static void resid_ro(rri_ctx* c, double* rowobj, double* rowpos) {
+        const unsigned nb = (unsigned)((c->n + 63) / 64);
+        if (c->k <= 64) {
+            const int ks = c->k <= 16 ? 4 : c->k <= 32 ? 8 : c->k <= 48 ? 12 : c->k <= 52 ? 13 : 16;
+            const size_t shm = 2 * (size_t)(4 * ks) * RESID_TS * sizeof(double);
+#define RRI_RESID_RO(KS_)                                                                                                    \
+    hipLaunchKernelGGL((k_resid_mfma<SX, false, false, KS_, 4, true>), dim3(nb, 1u), dim3(256), shm, c->stream, (const SX*)c->X, \
+                       c->ldx, (const SX*)nullptr, (i64)0, (const unsigned*)nullptr, (i64)0, (const double*)c->W, c->ldw,        \
+                       (const double*)c->T, c->LD, (int)c->n, (int)c->d, c->k, rowobj, rowpos, (SX*)nullptr, c->LD,              \
+                       (int)round_up(c->d, 64))
+            switch (ks) {
+                case 4: RRI_RESID_RO(4); break;
+                case 8: RRI_RESID_RO(8); break;
+                case 12: RRI_RESID_RO(12); break;
+                case 13: RRI_RESID_RO(13); break;
+                default: RRI_RESID_RO(16); break;
+            }
+#undef RRI_RESID_RO
+            return;
+        }
+        hipLaunchKernelGGL((k_resid<SX, false, false>), dim3(nb), dim3(256), resid_shmem(c), c->stream, (const SX*)c->X, c->ldx,
+                           (const SX*)nullptr, (i64)0, (const unsigned*)nullptr, (i64)0, (const double*)c->W, c->ldw,
+                           (const double*)c->T, c->LD, (int)c->n, (int)c->d, c->k, rowobj, rowpos, (SX*)nullptr, c->LD,
+                           resid_w_resident(c) ? 1 : 0);
+    }
+    static void resid_rw(rri_ctx* c, bool masked, bool write_e, double* rowobj, double* rowpos) {
         if (c->sparse) { sp_resid(c, write_e, rowobj, rowpos); return; }   // outside the pattern nothing contributes
         const unsigned nb = (unsigned)((c->n + 63) / 64);
         if (c->k <= 64) {   // the k-panel product on the matrix cores
@@ -867,19 +921,28 @@ struct LaunchX {
 #undef RRI_RESID
     }
     static void reset_row(rri_ctx* c) {
-        if (c->sparse) {
-            (void)hipMemsetAsync(c->xraw, 0, (size_t)c->LD * sizeof(double), c->stream);
-            hipLaunchKernelGGL((k_sp_reset_row<SX>), dim3((unsigned)std::max(1, (c->sp_max_row + 255) / 256)), dim3(256), 0,
-                               c->stream, (const i64*)c->sp_rowptr, (const int*)c->sp_col, (const SX*)c->sp_x,
-                               (const double*)c->W, c->ldw, (const double*)c->T, c->LD, c->k, (const i64*)c->itmp,
-                               c->xraw);
-            return;
+        if constexpr (!RO) {
+            if (c->sparse) {
+                (void)hipMemsetAsync(c->xraw, 0, (size_t)c->LD * sizeof(double), c->stream);
+                hipLaunchKernelGGL((k_sp_reset_row<SX>), dim3((unsigned)std::max(1, (c->sp_max_row + 255) / 256)), dim3(256), 0,
+                                   c->stream, (const i64*)c->sp_rowptr, (const int*)c->sp_col, (const SX*)c->sp_x,
+                                   (const double*)c->W, c->ldw, (const double*)c->T, c->LD, c->k, (const i64*)c->itmp,
+                                   c->xraw);
+                return;
+            }
         }
         hipLaunchKernelGGL((k_reset_row<SX>), dim3((unsigned)((c->d + 255) / 256)), dim3(256), 0, c->stream,
                            (const SX*)c->X, c->ldx, (const double*)c->W, c->ldw, (const double*)c->T, c->LD,
                            (int)c->d, c->k, (const i64*)c->itmp, c->xraw);
     }
     static hipError_t set_attrs() {
+        if constexpr (RO) {
+            return hipFuncSetAttribute((const void*)k_resid<SX, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        } else {
+            return set_attrs_rw();
+        }
+    }
+    static hipError_t set_attrs_rw() {
         hipError_t e = hipSuccess;
         const void* fns[] = {(const void*)k_resid<SX, true, true>, (const void*)k_resid<SX, true, false>,
                              (const void*)k_resid<SX, false, true>, (const void*)k_resid<SX, false, false>};
@@ -891,13 +954,33 @@ struct LaunchX {
     }
 };
 
+// Everything that writes X, the mask or a residual, or reads a CSR store: float32 and float64 only.  A float16 handle
+// (RRI_F16) is refused at the entry points that lead here; should one arrive all the same, nothing is launched and the call
+// that enqueued the sequence ends with RRI_ERR_UNSUPPORTED (f16_unreachable) -- never the double branch on 2-byte data.
 #define DISPATCH(c, expr)                       \
     do {                                        \
         if ((c)->dtype == RRI_F32) {            \
             typedef LaunchX<float> L;           \
             expr;                               \
-        } else {                                \
+        } else if ((c)->dtype == RRI_F64) {     \
             typedef LaunchX<double> L;          \
+            expr;                               \
+        } else {                                \
+            f16_unreachable(c);                 \
+        }                                       \
+    } while (0)
+// The kernels that only READ a dense X (the pass with UPD = 0, X T^T, X^T Q, the residual's row sums, the reset row, ||X||^2):
+// the three storage types.
+#define DISPATCH_RO(c, expr)                    \
+    do {                                        \
+        if ((c)->dtype == RRI_F32) {            \
+            typedef LaunchX<float> L;           \
+            expr;                               \
+        } else if ((c)->dtype == RRI_F64) {     \
+            typedef LaunchX<double> L;          \
+            expr;                               \
+        } else {                                \
+            typedef LaunchX<_Float16> L;        \
             expr;                               \
         }                                       \
     } while (0)
@@ -1020,14 +1103,50 @@ void launch_convert(rri_ctx* c, const void* src, i64 lds_, void* dst, i64 ldd, i
                        lds_, (Dst*)dst, ldd, rows, cols);
 }
 
+// host (rows x cols, stride ld; float32, float64 or float16) -> device float16 (the X of an RRI_F16 handle): one rounding to
+// nearest even from the host type (k_store_half), with the cost of that rounding left in c->store_err.  A float16 host
+// buffer takes the same route -- the conversion is then the identity -- so that inf / NaN in it are seen too.  A value that is
+// not finite as a half fails the call with RRI_ERR_INVALID (the caller drops the X).
+rri_status to_device_half(rri_ctx* c, const void* host, i64 ld, int host_dtype, void* dev, i64 ldd, i64 rows, i64 cols,
+                          bool transpose) {
+    if (transpose) return fail(c, RRI_ERR_INVALID, "float16 storage is for X only");
+    const size_t hs = dtype_size(host_dtype);
+    const i64 total = rows * cols;
+    const unsigned nb = (unsigned)std::max<i64>(1, std::min<i64>(4096, (total + 255) / 256));
+    DevTmp tmp, part;
+    HIPCHK(c, tmp.alloc((size_t)rows * cols * hs));
+    HIPCHK(c, part.alloc((size_t)nb * 3 * sizeof(double)));
+    HIPCHK(c, hipMemcpy2DAsync(tmp.p, cols * hs, host, ld * hs, cols * hs, rows, hipMemcpyHostToDevice, c->stream));
+#define RRI_HALF(SRC)                                                                                                  \
+    hipLaunchKernelGGL((k_store_half<SRC>), dim3(nb), dim3(256), 0, c->stream, (const SRC*)tmp.p, cols, (_Float16*)dev, ldd, \
+                       rows, cols, (double*)part.p)
+    if (host_dtype == RRI_F32) RRI_HALF(float);
+    else if (host_dtype == RRI_F64) RRI_HALF(double);
+    else RRI_HALF(_Float16);
+#undef RRI_HALF
+    std::vector<double> h((size_t)nb * 3);
+    HIPCHK(c, hipMemcpyAsync(h.data(), part.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double se = 0.0, sx = 0.0, bad = 0.0;
+    for (unsigned b = 0; b < nb; ++b) { se += h[3 * b]; sx += h[3 * b + 1]; bad += h[3 * b + 2]; }
+    c->store_err[0] = se;
+    c->store_err[1] = sx;
+    if (bad > 0.0)
+        return fail(c, RRI_ERR_INVALID, "value outside the float16 range at upload (%.0f of them: |x| >= 65520, inf or NaN)", bad);
+    return RRI_OK;
+}
+
 // host (rows x cols, stride ld, host_dtype) -> device (stride ldd, dev_dtype).
 // transpose: the device image is cols x rows (dst[c][r] = host[r][c]).
 rri_status to_device(rri_ctx* c, const void* host, i64 ld, int host_dtype, void* dev, i64 ldd, i64 rows,
                      i64 cols, int dev_dtype, bool transpose = false) {
     if (!host || ld < cols) return fail(c, RRI_ERR_INVALID, "bad host matrix (ld=%lld < cols=%lld)", ld, cols);
-    if (host_dtype != RRI_F32 && host_dtype != RRI_F64) return fail(c, RRI_ERR_INVALID, "bad host dtype");
-    const size_t hs = host_dtype == RRI_F32 ? 4 : 8;
-    const size_t ds = dev_dtype == RRI_F32 ? 4 : 8;
+    // a float16 host buffer goes onto a float16 handle only (nothing else is ever given as halves)
+    if (host_dtype != RRI_F32 && host_dtype != RRI_F64 && !(host_dtype == RRI_F16 && dev_dtype == RRI_F16))
+        return fail(c, RRI_ERR_INVALID, "bad host dtype");
+    const size_t hs = dtype_size(host_dtype);
+    const size_t ds = dtype_size(dev_dtype);
+    if (dev_dtype == RRI_F16) return to_device_half(c, host, ld, host_dtype, dev, ldd, rows, cols, transpose);
     if (host_dtype == dev_dtype && !transpose) {
         HIPCHK(c, hipMemcpy2DAsync(dev, ldd * ds, host, ld * hs, cols * hs, rows, hipMemcpyHostToDevice,
                                    c->stream));
@@ -1062,8 +1181,9 @@ rri_status to_host(rri_ctx* c, const void* dev, i64 ldd, void* host, i64 ld, int
                    int dev_dtype, bool transpose = false) {
     if (!host || ld < cols) return fail(c, RRI_ERR_INVALID, "bad host matrix (ld=%lld < cols=%lld)", ld, cols);
     if (host_dtype != RRI_F32 && host_dtype != RRI_F64) return fail(c, RRI_ERR_INVALID, "bad host dtype");
-    const size_t hs = host_dtype == RRI_F32 ? 4 : 8;
-    const size_t ds = dev_dtype == RRI_F32 ? 4 : 8;
+    if (dev_dtype != RRI_F32 && dev_dtype != RRI_F64) return fail(c, RRI_ERR_UNSUPPORTED, "nothing stored as float16 is read back");
+    const size_t hs = dtype_size(host_dtype);
+    const size_t ds = dtype_size(dev_dtype);
     if (host_dtype == dev_dtype && !transpose) {
         HIPCHK(c, hipMemcpy2DAsync(host, ld * hs, dev, ldd * ds, cols * hs, rows, hipMemcpyDeviceToHost,
                                    c->stream));
@@ -1134,7 +1254,7 @@ void enqueue_prologue(rri_ctx* c, int t, int sweep) {
         c->pending_wcheck = false;
     }
     LK::wcol<false, true>(c, t, t, sweep);                             // Gram row of w_t
-    DISPATCH(c, (L::template pass<false, true>(c, t, t)));            // w_t^T X
+    DISPATCH_RO(c, (L::template pass<false, true>(c, t, t)));         // w_t^T X
     c->carry_valid = true;
     c->carry_topic = t;
 }
@@ -1181,7 +1301,7 @@ void enqueue_W_half(rri_ctx* c, int sweep, int t) {
         c->ttpart_n = c->nsplit;
     }
     if (carry_next) {
-        DISPATCH(c, (L::template pass<true, true>(c, t, tn, job)));
+        DISPATCH_RO(c, (L::template pass<true, true>(c, t, tn, job)));
         LK::wcol<true, true>(c, t, tn, sweep);
         c->carry_valid = true;
         c->carry_topic = tn;
@@ -1191,12 +1311,12 @@ void enqueue_W_half(rri_ctx* c, int sweep, int t) {
         if (c->prm.fix_T) {
             // T is fixed: X T^T is computed once (k_xtt) and reused by every topic and every sweep
             if (!c->q_valid) {
-                DISPATCH(c, L::xtt(c));
+                DISPATCH_RO(c, L::xtt(c));
                 c->q_valid = true;
             }
             LK::wcol_src<true, false>(c, t, tn, sweep, c->Qt + (i64)t * c->ldw, 1);
         } else {
-            DISPATCH(c, (L::template pass<true, false>(c, t, tn, job)));
+            DISPATCH_RO(c, (L::template pass<true, false>(c, t, tn, job)));
             LK::wcol<true, false>(c, t, tn, sweep);
         }
         // position of the NEXT step, where a resumed run continues
@@ -1493,7 +1613,7 @@ void calibrate_rot(rri_ctx* c) {
             c->rot_x = std::max(rot, 0);
             for (int rep = 0; rep < (rot < 0 ? 2 : 3); ++rep) {
                 if (rot >= 0 && rep == 1) (void)hipEventRecord(e0, c->stream);
-                DISPATCH(c, (L::template pass<true, true>(c, 0, 0)));
+                DISPATCH_RO(c, (L::template pass<true, true>(c, 0, 0)));
             }
             if (rot < 0) continue;
             (void)hipEventRecord(e1, c->stream);
@@ -1582,7 +1702,7 @@ bool enqueue_wsweep(rri_ctx* c, int sweep, int t0) {
         c->pending_wcheck = false;
     }
     if (!c->q_valid) {           // X T^T: once per T, reused by every topic and every sweep
-        DISPATCH(c, L::xtt(c));
+        DISPATCH_RO(c, L::xtt(c));
         c->q_valid = true;
     }
     if (!c->gfull_valid) {
@@ -1703,6 +1823,7 @@ bool onchip_ok(const rri_ctx* c) {
     // a handle that fell back tries the persistent path again once its own back-off has run out (a burst on another stream or
     // process must not cost a long-lived handle the launch-bound speed-up for good); eligibility therefore depends on the clock
     if (c->onchip_off && steady_now_ns() < c->onchip_off_until) return false;
+    if (c->dtype == RRI_F16) return false;      // the persistent kernel has register layouts for 4- and 8-byte X only
     return c->sw.onchip && steady_now_ns() >= g_onchip_backoff_until.load() && !c->weighted && !c->explicit_resid && !c->comm && !c->sparse && c->k >= 2 &&
            c->k <= ONCHIP_MAX_K && !c->prm.fix_W && !c->prm.fix_T && c->ldx % c->VN == 0 && ((uintptr_t)c->X) % 16 == 0 &&
            onchip_geometry(c, &g);
@@ -1971,6 +2092,11 @@ const char* sparse_data_refusal(const rri_ctx* c) {
                        : "a sparse-pattern handle takes its data through rri_upload_observed_csr";
 }
 
+// the entry points that rewrite X in place, or need a mask, a residual, a CSR store or a scratch residual, on a float16 handle
+#define REFUSE_F16(c, what)                                                                                             \
+    if ((c)->dtype == RRI_F16)                                                                                          \
+        return fail((c), RRI_ERR_UNSUPPORTED, "%s is not available on an RRI_F16 handle (float16 stores a dense X that is only read)", what)
+
 rri_status ready(rri_ctx* c) {
     if (!c->have_X || !c->have_W || !c->have_T || !c->have_params)
         return fail(c, RRI_ERR_INVALID, "X, W, T and params must be set before stepping");
@@ -1992,7 +2118,7 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     if (!out) return RRI_ERR_INVALID;
     *out = nullptr;
     if (n < 1 || d < 1 || k < 1) return fail(nullptr, RRI_ERR_INVALID, "need n,d,k >= 1 (got %lld,%lld,%d)", n, d, k);
-    if (dtype != RRI_F32 && dtype != RRI_F64) return fail(nullptr, RRI_ERR_INVALID, "dtype must be RRI_F32/RRI_F64");
+    if (dtype != RRI_F32 && dtype != RRI_F64 && dtype != RRI_F16) return fail(nullptr, RRI_ERR_INVALID, "dtype must be RRI_F32, RRI_F64 or RRI_F16");
     if (n > 2000000000LL || d > 2000000000LL) return fail(nullptr, RRI_ERR_INVALID, "n, d must fit int32");
     if (k > RRI_MAX_K) return fail(nullptr, RRI_ERR_UNSUPPORTED, "k=%d is above the rank limit RRI_MAX_K = %d of the device path", k, RRI_MAX_K);
     int ndev = 0;
@@ -2002,6 +2128,15 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     if (weighted < 0 || weighted > 4)
         return fail(nullptr, RRI_ERR_INVALID, "weighted must be RRI_UNWEIGHTED, RRI_WEIGHTED_DENSE, RRI_WEIGHTED_SPARSE, "
                                               "RRI_UNWEIGHTED_RESIDUAL or RRI_UNWEIGHTED_SPARSE");
+    if (dtype == RRI_F16 && weighted != RRI_UNWEIGHTED) {
+        // float16 is a store for an X that is only ever read.  The explicit residual and the dense weighted residual are rewritten
+        // at every topic step (k S roundings to 11 bits over S sweeps); CSR values are a store of their own with its own layout
+        static const char* const flavour[] = {"", "RRI_WEIGHTED_DENSE", "RRI_WEIGHTED_SPARSE", "RRI_UNWEIGHTED_RESIDUAL", "RRI_UNWEIGHTED_SPARSE"};
+        const bool rewritten = weighted == RRI_WEIGHTED_DENSE || weighted == RRI_UNWEIGHTED_RESIDUAL;
+        return fail(nullptr, RRI_ERR_UNSUPPORTED, "RRI_F16 stores a read-only dense X (RRI_UNWEIGHTED); %s %s", flavour[weighted],
+                    rewritten ? "rewrites its stored residual at every topic step, which float16 would round every time"
+                              : "keeps its values in a CSR store, which has no float16 layout");
+    }
     rri_ctx* c = new rri_ctx();
     const bool explicit_resid = weighted == RRI_UNWEIGHTED_RESIDUAL;
     const bool sparse_x = weighted == RRI_UNWEIGHTED_SPARSE;
@@ -2011,8 +2146,8 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     c->n = n; c->d = d; c->k = k; c->dtype = dtype; c->weighted = weighted; c->device = device;
     c->sparse = weighted == RRI_WEIGHTED_SPARSE || sparse_x;
     c->kp = (int)round_up(k, 8);
-    c->es = dtype == RRI_F32 ? 4 : 8;
-    c->VN = (int)(16 / c->es);
+    c->es = dtype_size(dtype);
+    c->VN = (int)(16 / c->es);          // elements per 16-byte load: 4, 2, or 8 (float16)
     c->sw = read_switches();
     c->PW = 64 * c->VN * 4;   // columns per workgroup: 4 waves x (64 lanes x 16 B)
     c->LD = round_up(d, c->VN);
@@ -2069,7 +2204,7 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
         const i64 block_bytes = SP_BLOCK_BYTES;
         // (X on CSR: ONE table of float64 factors per block, spx_block_cap -- k_spx_pass)
         const i64 cap = sparse_x ? std::min<i64>(spx_block_cap(), std::max<i64>(64, (block_bytes / 8 - 64) / 64 * 64))
-                                 : block_bytes / (3 * (dtype == RRI_F32 ? 4 : 8));
+                                 : block_bytes / (3 * (i64)c->es);
         for (int w = 0; w < 2; ++w) {
             rri_ctx::SpCopy& cp = c->sp[w];
             cp.gdim = w == 0 ? d : n;
@@ -2172,7 +2307,8 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     CR(hipMemsetAsync(c->st, 0, sizeof(DevState), c->stream));
     // opt in to large dynamic LDS where a kernel needs it
     if (dtype == RRI_F32) CR(LaunchX<float>::set_attrs());
-    else CR(LaunchX<double>::set_attrs());
+    else if (dtype == RRI_F64) CR(LaunchX<double>::set_attrs());
+    else CR(LaunchX<_Float16>::set_attrs());
     CR(hipStreamSynchronize(c->stream));
 #undef CR
     *out = c;
@@ -2215,13 +2351,16 @@ rri_status rri_upload_X(rri_ctx* c, const void* host, int64_t ld, int32_t host_d
         if (c->LD != c->d) HIPCHK(c, hipMemsetAsync(c->X, 0, (size_t)c->n * c->LD * c->es, c->stream));
     }
     c->ldx = c->LD;
+    c->store_err[0] = c->store_err[1] = 0.0;
     rri_status s = to_device(c, host, ld, host_dtype, c->X, c->ldx, c->n, c->d, c->dtype);
-    if (s == RRI_OK) { c->have_X = true; invalidate(c); c->q_valid = false; c->gfull_valid = false; c->x_sq_valid = false; }
+    // (a float16 upload that fails -- the range check -- has already overwritten the store: the handle then has no X)
+    if (s == RRI_OK || c->dtype == RRI_F16) { c->have_X = s == RRI_OK; invalidate(c); c->q_valid = false; c->gfull_valid = false; c->x_sq_valid = false; }
     return s;
 }
 
 rri_status rri_upload_mask(rri_ctx* c, const void* host, int64_t ld, int32_t host_dtype) {
     CHECK_CTX(c);
+    REFUSE_F16(c, "a mask");
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     if (!c->weighted) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=1");
     HIPCHK(c, hipSetDevice(c->device));
@@ -2259,7 +2398,7 @@ rri_status csr_to_device(rri_ctx* c, const int64_t* indptr, const int32_t* indic
         if (indptr[r + 1] < indptr[r]) return fail(c, RRI_ERR_INVALID, "indptr not monotone at row %lld", r);
     for (i64 p = 0; p < nnz; ++p)
         if (indices[p] < 0 || indices[p] >= c->d) return fail(c, RRI_ERR_INVALID, "column index out of range at %lld", p);
-    const size_t ds = data_dtype == RRI_F32 ? 4 : 8;
+    const size_t ds = dtype_size(data_dtype);
     HIPCHK(c, hipMalloc((void**)&out.indptr, (size_t)(c->n + 1) * sizeof(i64)));
     HIPCHK(c, hipMalloc((void**)&out.indices, (size_t)std::max<i64>(nnz, 1) * sizeof(int)));
     HIPCHK(c, hipMalloc(&out.data, (size_t)std::max<i64>(nnz, 1) * ds));
@@ -2278,6 +2417,7 @@ static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int
 rri_status rri_upload_X_csr(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data,
                             int64_t nnz, int32_t data_dtype) {
     CHECK_CTX(c);
+    REFUSE_F16(c, "X from CSR arrays");
     if (c->sparse_x) return upload_X_csr_kept(c, indptr, indices, data, nnz, data_dtype);
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     HIPCHK(c, hipSetDevice(c->device));
@@ -2322,7 +2462,7 @@ static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int
         if (indptr[r + 1] < indptr[r]) return fail(c, RRI_ERR_INVALID, "indptr not monotone at row %lld", r);
     HIPCHK(c, hipSetDevice(c->device));
     // column indices sorted inside every row (a sorted host copy where the caller's are not); duplicates are refused
-    const size_t ds = data_dtype == RRI_F32 ? 4 : 8;
+    const size_t ds = dtype_size(data_dtype);
     std::vector<int32_t> sidx;
     std::vector<unsigned char> sval;
     for (i64 r = 0; r < c->n; ++r) {
@@ -2374,6 +2514,7 @@ static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int
 rri_status rri_upload_mask_csr_pattern(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data,
                                        int64_t nnz, int32_t data_dtype) {
     CHECK_CTX(c);
+    REFUSE_F16(c, "a mask");
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     if (!c->weighted) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=1");
     HIPCHK(c, hipSetDevice(c->device));
@@ -2528,6 +2669,7 @@ rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indi
 rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* values,
                                    int64_t nnz, int32_t data_dtype) {
     CHECK_CTX(c);
+    REFUSE_F16(c, "an observation pattern");
     if (!c->sparse || c->sparse_x) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=RRI_WEIGHTED_SPARSE");
     if (nnz >= 2147483647LL) return fail(c, RRI_ERR_UNSUPPORTED, "more than 2^31-1 observed entries");
     HIPCHK(c, hipSetDevice(c->device));
@@ -2548,6 +2690,14 @@ rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int3
     return RRI_OK;
 }
 
+rri_status rri_storage_error(rri_ctx* c, double out[2]) {
+    CHECK_CTX(c);
+    if (!out) return fail(c, RRI_ERR_INVALID, "out is NULL");
+    out[0] = c->store_err[0];
+    out[1] = c->store_err[1];
+    return RRI_OK;
+}
+
 rri_status rri_bind_X_device(rri_ctx* c, const void* dev, int64_t ld) {
     CHECK_CTX(c);
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
@@ -2560,6 +2710,7 @@ rri_status rri_bind_X_device(rri_ctx* c, const void* dev, int64_t ld) {
     c->X = const_cast<void*>(dev);
     c->own_X = false;
     c->ldx = ld;
+    c->store_err[0] = c->store_err[1] = 0.0;   // bound memory is taken as it is: nothing was rounded here
     c->have_X = true;
     invalidate(c);
     c->q_valid = false; c->gfull_valid = false;
@@ -2569,6 +2720,7 @@ rri_status rri_bind_X_device(rri_ctx* c, const void* dev, int64_t ld) {
 
 rri_status rri_bind_mask_device(rri_ctx* c, const void* dev, int64_t ld) {
     CHECK_CTX(c);
+    REFUSE_F16(c, "a mask");
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     if (!c->weighted) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=1");
     if (!dev || ld < c->d || (ld * (i64)c->es) % 16 || ((uintptr_t)dev) % 16)
@@ -2777,7 +2929,7 @@ rri_status rri_apply_reset_max_resid(rri_ctx* c, int32_t t, int64_t* row_chosen)
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->rowpos) HIPCHK(c, hipMalloc((void**)&c->rowpos, (size_t)c->n * sizeof(double)));
     HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
-    DISPATCH(c, L::resid(c, false, false, nullptr, c->rowpos));
+    DISPATCH_RO(c, L::resid(c, false, false, nullptr, c->rowpos));
     hipLaunchKernelGGL(k_vec_sum_argmax, dim3(1), dim3(1024), 0, c->stream, (const double*)c->rowpos, c->n,
                        (double*)nullptr, c->itmp);
     if (c->comm) {
@@ -2796,7 +2948,7 @@ rri_status rri_apply_reset_max_resid(rri_ctx* c, int32_t t, int64_t* row_chosen)
         int win = 0;
         for (int r = 1; r < m->world; ++r)
             if (cand[2 * r] > cand[2 * win] || (cand[2 * r] == cand[2 * win] && cand[2 * r + 1] < cand[2 * win + 1])) win = r;
-        if (m->rank == win) DISPATCH(c, L::reset_row(c));          // xraw = the reset row (d doubles)
+        if (m->rank == win) DISPATCH_RO(c, L::reset_row(c));          // xraw = the reset row (d doubles)
         comm_broadcast(c, c->xraw, c->LD, win);
         if (m->rank != win) {
             const i64 none = -1;
@@ -2810,7 +2962,7 @@ rri_status rri_apply_reset_max_resid(rri_ctx* c, int32_t t, int64_t* row_chosen)
         else invalidate(c);
         return RRI_OK;
     }
-    DISPATCH(c, L::reset_row(c));
+    DISPATCH_RO(c, L::reset_row(c));
     LK::reset_commit(c, t);
     i64 mi = -1;
     HIPCHK(c, hipMemcpyAsync(&mi, c->itmp, sizeof(i64), hipMemcpyDeviceToHost, c->stream));
@@ -2927,7 +3079,7 @@ static rri_status ensure_x_sq(rri_ctx* c) {
         DISPATCH(c, hipLaunchKernelGGL((k_sqsum<typename L::Elem>), dim3(256), dim3(256), 0, c->stream,
                                        (const typename L::Elem*)c->sp_x, std::max<i64>(c->nnz, 1), (i64)1, c->nnz, c->normpart));
     else
-        DISPATCH(c, hipLaunchKernelGGL((k_sqsum<typename L::Elem>), dim3(256), dim3(256), 0, c->stream,
+        DISPATCH_RO(c, hipLaunchKernelGGL((k_sqsum<typename L::Elem>), dim3(256), dim3(256), 0, c->stream,
                                        (const typename L::Elem*)c->X, c->ldx, c->n, c->d, c->normpart));
     double h[256];
     HIPCHK(c, hipMemcpyAsync(h, c->normpart, sizeof h, hipMemcpyDeviceToHost, c->stream));
@@ -3035,7 +3187,7 @@ static rri_status objective_terms(rri_ctx* c, double out[3], double* tn) {
         if (tn) return norms_of(c, c->T, c->k, c->d, c->LD, tn);
         return RRI_OK;
     } else {
-        DISPATCH(c, L::resid(c, false, false, c->rowobj, nullptr));
+        DISPATCH_RO(c, L::resid(c, false, false, c->rowobj, nullptr));
     }
     hipLaunchKernelGGL(k_vec_sum_argmax, dim3(1), dim3(1024), 0, c->stream, (const double*)c->rowobj, c->n,
                        c->dtmp, (i64*)nullptr);
@@ -3172,6 +3324,7 @@ rri_status rri_rollback(rri_ctx* c) {
 // ---- the explicit residual (RRI_UNWEIGHTED_RESIDUAL handles) --------------------------------------------------
 rri_status rri_residual_rebuild(rri_ctx* c) {
     CHECK_CTX(c);
+    REFUSE_F16(c, "the explicit residual");
     if (!c->explicit_resid) return fail(c, RRI_ERR_INVALID, "handle was not created with RRI_UNWEIGHTED_RESIDUAL");
     if (!c->have_X || !c->have_W || !c->have_T) return fail(c, RRI_ERR_INVALID, "X, W, T must be set");
     HIPCHK(c, hipSetDevice(c->device));
@@ -3182,6 +3335,7 @@ rri_status rri_residual_rebuild(rri_ctx* c) {
 
 rri_status rri_get_residual(rri_ctx* c, void* host, int64_t ld, int32_t host_dtype) {
     CHECK_CTX(c);
+    REFUSE_F16(c, "the explicit residual");
     if (!c->explicit_resid) return fail(c, RRI_ERR_INVALID, "handle was not created with RRI_UNWEIGHTED_RESIDUAL");
     HIPCHK(c, hipSetDevice(c->device));
     return to_host(c, c->E, c->LD, host, ld, host_dtype, c->n, c->d, c->dtype);
@@ -3190,6 +3344,7 @@ rri_status rri_get_residual(rri_ctx* c, void* host, int64_t ld, int32_t host_dty
 rri_status rri_residual_update(rri_ctx* c, const double* a, const double* b, const double* a2, const double* b2,
                                const double* trow, const double* wcol, double* y_out, double* z_out) {
     CHECK_CTX(c);
+    REFUSE_F16(c, "the explicit residual");
     if (!c->explicit_resid) return fail(c, RRI_ERR_INVALID, "handle was not created with RRI_UNWEIGHTED_RESIDUAL");
     if (!a || !b || !trow || !wcol || ((a2 == nullptr) != (b2 == nullptr)))
         return fail(c, RRI_ERR_INVALID, "a, b, trow, wcol are required; a2 and b2 come together");
@@ -3271,7 +3426,7 @@ rri_status rri_X_times(rri_ctx* c, const double* B, int32_t m, double* out) {
     rri_status s = to_device(c, B, m, RRI_F64, tm.p, c->LD, c->d, m, RRI_F64, true);
     if (s != RRI_OK) return s;
     HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
-    DISPATCH(c, L::xtt_any(c, (const double*)tm.p, m, (double*)outm.p));
+    DISPATCH_RO(c, L::xtt_any(c, (const double*)tm.p, m, (double*)outm.p));
     return to_host(c, outm.p, c->ldw, out, m, RRI_F64, c->n, m, RRI_F64, true);
 }
 
@@ -3293,7 +3448,7 @@ rri_status rri_Xt_times(rri_ctx* c, const double* Q, int32_t m, double* out) {
     DevTmp zm;      // partial column sums of 8 vectors at a time: X is read once per 8 vectors
     HIPCHK(c, zm.alloc((size_t)8 * c->nrb * c->LD * sizeof(double)));
     for (int l = 0; l < m; l += 8)
-        DISPATCH(c, L::colsums8(c, (const double*)qm.p + (i64)l * c->ldw, std::min(8, m - l), (double*)zm.p,
+        DISPATCH_RO(c, L::colsums8(c, (const double*)qm.p + (i64)l * c->ldw, std::min(8, m - l), (double*)zm.p,
                                 (double*)outm.p + (i64)l * c->LD));
     c->timing = tsave;
     (void)tm_on;
@@ -3371,10 +3526,10 @@ rri_status rri_range_finder(rri_ctx* c, const double* Q0, int32_t m, int32_t n_i
     HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
     const int tsave = c->timing;
     c->timing = 0;
-    auto X_times_dev = [&]() { DISPATCH(c, L::xtt_any(c, (const double*)Pd, m, Pn)); };                 // Pn = (X Pd^T)^T
+    auto X_times_dev = [&]() { DISPATCH_RO(c, L::xtt_any(c, (const double*)Pd, m, Pn)); };                 // Pn = (X Pd^T)^T
     auto Xt_times_dev = [&]() {                                                                          // Pd = (X^T Pn^T)^T
         for (int l = 0; l < m; l += 8)
-            DISPATCH(c, L::colsums8(c, (const double*)Pn + (i64)l * c->ldw, std::min(8, m - l), (double*)zm.p, Pd + (i64)l * c->LD));
+            DISPATCH_RO(c, L::colsums8(c, (const double*)Pn + (i64)l * c->ldw, std::min(8, m - l), (double*)zm.p, Pd + (i64)l * c->LD));
     };
     rri_status s;
     // A = X (transpose == 0: Q0 is d x m) or A = X^T (Q0 is n x m), as scikit-learn transposes when n < d
@@ -3414,6 +3569,7 @@ rri_status rri_range_finder(rri_ctx* c, const double* Q0, int32_t m, int32_t n_i
 // ---- preprocessing of the resident X ---------------------------------------------------------------------------
 rri_status rri_column_positive_counts(rri_ctx* c, double* df_out) {
     CHECK_CTX(c);
+    REFUSE_F16(c, "preprocessing of the resident X (it ends in a rewrite of X, a second rounding: preprocess on the host)");
     if (!df_out) return fail(c, RRI_ERR_INVALID, "df_out is NULL");
     if (c->weighted || !c->have_X || c->sparse_x) return fail(c, RRI_ERR_INVALID, "needs an unweighted handle with a dense X");
     HIPCHK(c, hipSetDevice(c->device));
@@ -3432,6 +3588,7 @@ rri_status rri_column_positive_counts(rri_ctx* c, double* df_out) {
 
 rri_status rri_scale_X(rri_ctx* c, const double* col_scale, int32_t normalize_rows) {
     CHECK_CTX(c);
+    REFUSE_F16(c, "rewriting X in place (a second rounding: preprocess on the host, X is then rounded once at upload)");
     if (c->weighted || !c->have_X || c->sparse_x) return fail(c, RRI_ERR_INVALID, "needs an unweighted handle with a dense X");
     if (!c->own_X) return fail(c, RRI_ERR_INVALID, "X is bound caller memory: it is not rewritten in place");
     HIPCHK(c, hipSetDevice(c->device));
@@ -3601,7 +3758,7 @@ rri_status rri_resid_row_argmax(rri_ctx* c, double* value, int64_t* local_row) {
     if (!value || !local_row) return fail(c, RRI_ERR_INVALID, "NULL output");
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->rowpos) HIPCHK(c, hipMalloc((void**)&c->rowpos, (size_t)c->n * sizeof(double)));
-    DISPATCH(c, L::resid(c, false, false, nullptr, c->rowpos));
+    DISPATCH_RO(c, L::resid(c, false, false, nullptr, c->rowpos));
     hipLaunchKernelGGL(k_vec_sum_argmax, dim3(1), dim3(1024), 0, c->stream, (const double*)c->rowpos, c->n,
                        (double*)nullptr, c->itmp);
     i64 mi = -1;
@@ -3620,7 +3777,7 @@ rri_status rri_reset_row(rri_ctx* c, int64_t local_row, double* row_out_host) {
     HIPCHK(c, hipSetDevice(c->device));
     const i64 mi = local_row;
     HIPCHK(c, hipMemcpyAsync(c->itmp, &mi, sizeof(i64), hipMemcpyHostToDevice, c->stream));
-    DISPATCH(c, L::reset_row(c));
+    DISPATCH_RO(c, L::reset_row(c));
     HIPCHK(c, hipMemcpyAsync(row_out_host, c->xraw, (size_t)c->d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RRI_OK;
@@ -3695,6 +3852,7 @@ rri_status rri_comm_destroy(rri_comm* m) {
 rri_status rri_attach_comm(rri_ctx* c, rri_comm* comm, int64_t row_offset, int64_t n_global) {
     CHECK_CTX(c);
     if (comm && c->sparse_x) return fail(c, RRI_ERR_UNSUPPORTED, "an RRI_UNWEIGHTED_SPARSE handle is not row-sharded");
+    if (comm && c->dtype == RRI_F16) return fail(c, RRI_ERR_UNSUPPORTED, "an RRI_F16 handle is not row-sharded (the combination has no test yet)");
     if (!comm) {              // detach
         c->comm = nullptr;
         c->row_offset = 0;
@@ -3837,6 +3995,7 @@ rri_status rri_synchronize(rri_ctx* c) {
 
 rri_status rri_bench_stream_copy(rri_ctx* c, int32_t reps, double* avg_ms) {
     CHECK_CTX(c);
+    REFUSE_F16(c, "the stream-copy yardstick");
     if (!c->have_X || reps < 1 || c->sparse) return fail(c, RRI_ERR_INVALID, "a dense X must be set and reps >= 1");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->n * c->ldx * c->es;
@@ -3864,6 +4023,7 @@ rri_status rri_bench_stream_copy(rri_ctx* c, int32_t reps, double* avg_ms) {
 
 rri_status rri_bench_rank1_update(rri_ctx* c, int32_t reps, double* avg_ms) {
     CHECK_CTX(c);
+    REFUSE_F16(c, "the rank-one residual update");
     if (!c->have_X || !c->have_W || !c->have_T || reps < 1 || c->weighted || c->sparse_x)
         return fail(c, RRI_ERR_INVALID, "an unweighted handle with a dense X, W, T set and reps >= 1");
     HIPCHK(c, hipSetDevice(c->device));

@@ -16,7 +16,8 @@
 //   k_wcol        numer_W = X t - W (T t)_{-t} - reg ; qf_min ; writes W[:,t];
 //                 Gram row / norm partials of the NEXT topic                             (nmf.py:464-469,673-676)
 // Precision: X (and the mask / masked residual) live in HBM in the handle's storage type SX
-// (fp32 or fp64).  EVERYTHING else -- W, T, partial sums, the closed-form updates -- is float64:
+// (fp32 or fp64; a dense X that is only read -- the Gram form without weights -- also as float16, see
+// XVec<_Float16>).  EVERYTHING else -- W, T, partial sums, the closed-form updates -- is float64:
 // the streaming pass converts each loaded X element and accumulates with v_fma_f64.  The pass is
 // HBM-bound with the vector ALU ~85 % idle, so float64 arithmetic costs no time, X traffic is
 // unchanged, and the result follows the reference's float64 numpy to summation-order rounding
@@ -90,6 +91,31 @@ template <> struct XVec<double> {
     static __device__ __forceinline__ void unpack(const f64x2& v, double (&o)[2]) { o[0] = v[0]; o[1] = v[1]; }
     static __device__ __forceinline__ f64x2 pack(const double (&o)[2]) { return f64x2{o[0], o[1]}; }
     static __device__ __forceinline__ f64x2 zero() { return f64x2{0.0, 0.0}; }
+};
+// float16 storage (RRI_F16): read-only handles of the Gram form.  8 elements per 16-byte load; half -> float -> double is
+// exact for every finite half, subnormals included, so the arithmetic sees the stored values.  pack() only ever re-packs
+// values that were read as halves (the ragged edge of k_xtt_mfma): no kernel rounds anything to float16 but k_store_half.
+// With 8 elements per lane a workgroup of k_pass / k_colsums covers 2048 columns; k_pass<_Float16, true, true, ...> holds tv[8],
+// zacc[8] and 8 rows of 4 VGPRs per lane: 202 VGPRs, 2 waves per SIMD -- and 0.337 ms per pass at 100000 x 10000 against 0.397 for
+// the same halves read 8 bytes per lane in the fp32 geometry (122 VGPRs, 4 waves), which was measured and removed.
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+template <> struct XVec<_Float16> {
+    typedef f16x8 type;
+    static constexpr int N = 8;
+    static __device__ __forceinline__ void unpack(const f16x8& v, double (&o)[8]) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (double)(float)v[e];
+    }
+    static __device__ __forceinline__ f16x8 pack(const double (&o)[8]) {
+        f16x8 r;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) r[e] = (_Float16)(float)o[e];
+        return r;
+    }
+    static __device__ __forceinline__ f16x8 zero() {
+        return f16x8{(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+    }
 };
 
 // streaming load of one 16-byte vector; NT = non-temporal (X is read once per pass, never reused)
@@ -1373,7 +1399,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2)))
     const int slot = 16 * (tc & 3) + (tc >> 2);
     constexpr int NST = (kp + WAVES - 1) / WAVES;
     double stage[NST];
-    typedef typename std::conditional<sizeof(SX) == 4, float, double>::type XR;
+    typedef typename std::conditional<sizeof(SX) <= 4, float, double>::type XR;   // (a float16 X is staged as float: exact)
     XR xq[4][4];                                     // the lane's 4 rows x 4 consecutive columns of X, as stored
     XR xn[4][4];                                     // ... of the NEXT step: requested at the start of a step, so that
                                                      // nothing issued late in a step is waited for before its barrier
@@ -1401,6 +1427,13 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2)))
                 if (i < n && j + 3 < d) {
                     const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(X + i * ldx + j));
                     dst[r][0] = v[0]; dst[r][1] = v[1]; dst[r][2] = v[2]; dst[r][3] = v[3];
+                    done = true;
+                }
+            }
+            if constexpr (sizeof(SX) == 2) {         // float16: the 4 columns are one 8-byte vector (row stride a multiple of 8)
+                if (i < n && j + 3 < d) {
+                    const f16x4 v = __builtin_nontemporal_load(reinterpret_cast<const f16x4*>(X + i * ldx + j));
+                    dst[r][0] = (float)v[0]; dst[r][1] = (float)v[1]; dst[r][2] = (float)v[2]; dst[r][3] = (float)v[3];
                     done = true;
                 }
             }
@@ -1837,6 +1870,34 @@ __global__ __launch_bounds__(256) void k_convert2d(const Src* __restrict__ src, 
             dst[r * ldd + c] = (Dst)src[r * lds_ + c];
         }
     }
+}
+
+// Upload of a float16 X: dst = half(src), rounded to nearest even in ONE step from the host type (the double -> _Float16 cast is
+// a single rounding: double -> float -> half would double-round, 1 + 2^-11 + 2^-30 -> 1.0 where numpy's astype gives 1 + 2^-10),
+// and what the rounding cost: part[3 b ..] = {sum (x - half(x))^2, sum x^2, values not finite once rounded (|x| >= 65520, inf,
+// NaN)} of block b, float64, every thread's terms in index order and the block's sum in a fixed order.
+template <typename Src>
+__global__ __launch_bounds__(256) void k_store_half(const Src* __restrict__ src, i64 lds_, _Float16* __restrict__ dst, i64 ldd,
+                                                    i64 rows, i64 cols, double* __restrict__ part) {
+    __shared__ double scratch[40];
+    const i64 total = rows * cols;
+    double se = 0.0, sx = 0.0, bad = 0.0;
+    for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
+        const i64 r = idx / cols, c = idx - r * cols;
+        const Src x = src[r * lds_ + c];
+        const _Float16 h = (_Float16)x;
+        dst[r * ldd + c] = h;
+        const double xd = (double)x, hd = (double)(float)h;
+        if (fabs(hd) <= 65504.0) {            // finite (false for inf and NaN)
+            const double e = xd - hd;
+            se = fma(e, e, se);
+            sx = fma(xd, xd, sx);
+        } else bad += 1.0;
+    }
+    se = block_sum(se, scratch);
+    sx = block_sum(sx, scratch);
+    bad = block_sum(bad, scratch);
+    if (threadIdx.x == 0) { part[3 * blockIdx.x] = se; part[3 * blockIdx.x + 1] = sx; part[3 * blockIdx.x + 2] = bad; }
 }
 
 // plain 16-byte streaming copy: the achievable-HBM yardstick measured beside the pass kernel

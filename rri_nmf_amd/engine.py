@@ -2,6 +2,13 @@
 small Python object.  All arithmetic happens in librri_hip.so; this class only moves
 arguments, resolves the rare reset events and maps status codes to the exceptions
 the reference raises (error conventions).
+
+Storage types of X in HBM: float32, float64, and -- for the unweighted flavour in the Gram form on a dense X, where the stored
+matrix is only ever read -- float16 (half the bytes of float32 per pass, twice the matrix per card).  The arithmetic is float64
+whatever the store, and a float16 value converts to float64 exactly, so a float16 handle solves the float64 problem on
+X.astype(float16): one rounding, at upload, none afterwards.  float16 suits magnitudes below 65520 (upload_X raises ValueError
+beyond) and data of 11 significant bits: integers up to 2048 are exact; otherwise the relative rounding is 2^-11 above 6.1e-5
+and the absolute one 3e-8 below it.  `storage_relerr` says what it came to.
 """
 import ctypes as C
 
@@ -12,19 +19,38 @@ from ._capi import Params, Event
 
 EPS_DIV = float(np.spacing(10))  # nmf.py:52
 
-_NP2RRI = {np.dtype(np.float32): _capi.RRI_F32, np.dtype(np.float64): _capi.RRI_F64}
+_NP2RRI = {np.dtype(np.float32): _capi.RRI_F32, np.dtype(np.float64): _capi.RRI_F64, np.dtype(np.float16): _capi.RRI_F16}
+_HOST_TYPES = (np.dtype(np.float32), np.dtype(np.float64))     # what W, T, masks and CSR values travel as
 _RESET_CODES = {None: _capi.RESET_NONE, 'max_resid_document': _capi.RESET_MAX_RESID_DOCUMENT,
                 'random': _capi.RESET_RANDOM}
 
 
-def _as_host(a, what):
-    """C-contiguous float32/float64 view or copy of a matrix (never mutates the caller's)."""
+def _as_host(a, what, half=False):
+    """C-contiguous float32/float64 view or copy of a matrix (never mutates the caller's); half: a float16 array stays one
+    (the X of a float16 handle)"""
     a = np.asarray(a)
-    if a.dtype not in _NP2RRI:
+    if a.dtype not in _HOST_TYPES and not (half and a.dtype == np.float16):
         a = a.astype(np.float64)
     if a.ndim != 2:
         raise ValueError('%s must be a 2-d array' % what)
     return np.ascontiguousarray(a)
+
+
+def check_storage_options(dtype, weighted=False, schedule='gram', sparse_x=False):
+    """The storage type of a handle against its flavour, before anything touches the library: float32 / float64 for all,
+    float16 for the unweighted flavour in the Gram form on a dense X only (the one handle whose stored matrix is never
+    rewritten).  Returns the numpy dtype; ValueError names what does not combine."""
+    dt = np.dtype(dtype)
+    if dt not in _NP2RRI:
+        raise ValueError('dtype must be float32, float64 or float16')
+    if dt == np.float16:
+        refused = [name for name, on in (('weighted=%r' % (weighted,), bool(weighted)),
+                                         ("schedule='residual'", schedule == 'residual'),
+                                         ('sparse_x=True', bool(sparse_x))) if on]
+        if refused:
+            raise ValueError('dtype=float16 stores a dense X that is only read (unweighted, schedule=\'gram\'); it does not '
+                             'combine with %s' % ', '.join(refused))
+    return dt
 
 
 class RRIEngine(object):
@@ -34,12 +60,10 @@ class RRIEngine(object):
         step is one rank-one residual update pass fused with the residual products (RRI_UNWEIGHTED_RESIDUAL).
         sparse_x (unweighted, 'gram'): X stays CSR on the device (RRI_UNWEIGHTED_SPARSE) -- upload_X_csr keeps it so, and
         there is no dense n x d array at all"""
+        self.dtype = check_storage_options(dtype, weighted, schedule, sparse_x)
         self._lib = _capi.load_library()
         self.n, self.d, self.k = int(n), int(d), int(k)
-        self.dtype = np.dtype(dtype)
         self.device = int(device)
-        if self.dtype not in _NP2RRI:
-            raise ValueError('dtype must be float32 or float64')
         # weighted: False | True (dense W_mat) | 'sparse' (0/1 W_mat given as a CSR pattern, upload_observed_csr)
         self.sparse_x = bool(sparse_x)
         if self.sparse_x and (weighted or schedule != 'gram'):
@@ -153,10 +177,20 @@ class RRIEngine(object):
 
     # ---- data ---------------------------------------------------------------------------
     def upload_X(self, X):
-        X = _as_host(X, 'X')
+        """a float16 handle takes float16 / float32 / float64 arrays as they are and rounds once, from that type; a value
+        outside the float16 range raises ValueError and leaves the handle without an X"""
+        X = _as_host(X, 'X', half=self.dtype == np.float16)
         if X.shape != (self.n, self.d):
             raise ValueError('X has wrong dimensions')
         self._check(self._lib.rri_upload_X(self._h, X.ctypes.data, X.strides[0] // X.itemsize, _NP2RRI[X.dtype]))
+
+    @property
+    def storage_relerr(self):
+        """||X - stored(X)||_F / ||X||_F of the last upload_X on a float16 handle (rri_storage_error); 0.0 on float32 / float64
+        handles, for bound arrays and for an all-zero X"""
+        out = (C.c_double * 2)()
+        self._check(self._lib.rri_storage_error(self._h, out))
+        return float(np.sqrt(out[0] / out[1])) if out[1] > 0.0 else 0.0
 
     def upload_mask(self, M):
         M = _as_host(M, 'W_mat')
@@ -176,7 +210,7 @@ class RRIEngine(object):
 
     @staticmethod
     def _csr_args_raw(A):
-        data = A.data if A.data.dtype in _NP2RRI else A.data.astype(np.float64)
+        data = A.data if A.data.dtype in _HOST_TYPES else A.data.astype(np.float64)
         indptr = np.ascontiguousarray(A.indptr, dtype=np.int64)
         indices = np.ascontiguousarray(A.indices, dtype=np.int32)
         data = np.ascontiguousarray(data)

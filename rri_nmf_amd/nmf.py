@@ -5,6 +5,13 @@ Same signature, defaults, return keys and error behaviour as the reference; keyw
 additions select the device side:
     dtype   storage type of X (and the mask) in HBM: float32 or float64.  None = float32 when X is
             float32, else float64.  The arithmetic is float64 either way (see csrc/rri_kernels.hpp).
+            float16 (never chosen by itself, not even for a float16 input): a dense X without weights in the Gram form is only
+            ever read, so it may be stored in half the bytes of float32 -- X is rounded ONCE, at upload (preprocessing and w_row
+            are applied in float64 on the host first), and since a float16 value is exact in float64 the call returns what
+            dtype=float64 returns for X.astype(float16): rtv['x_storage_relerr'] is the relative Frobenius distance of that matrix
+            from X.  For magnitudes below 65520 (ValueError beyond) and data of 11 significant bits: integers up to 2048 -- term
+            counts, ratings, pixels, 0/1 -- are stored exactly; otherwise the relative rounding is 2^-11 above 6.1e-5 and the
+            absolute one 3e-8 below it.  No W_mat, schedule='residual', sparse_X=True, group= or scipy sparse X.
     device  HIP device ordinal.
     device_init  True / False: run the products of the randomized SVD behind the NNDSVD initialisations on the
             device (initialization.randomized_svd_device) or in scikit-learn on the host; None = on the device from
@@ -470,6 +477,18 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         if refused:
             raise ValueError('sparse_X=True keeps an unweighted X as CSR on one device; it does not combine with %s'
                              % ', '.join(refused))
+    half = dtype is not None and np.dtype(dtype) == np.float16
+    if half:
+        # float16 stores an X that is only read: the unweighted flavour in the Gram form, dense, on one handle
+        refused = [name for name, on in (('W_mat', W_mat is not None), ("schedule='residual'", schedule == 'residual'),
+                                         ('sparse_X=True', bool(sparse_X)), ('group=', group is not None))
+                   if on]
+        if refused:
+            raise ValueError('dtype=float16 stores a dense, unweighted X that the Gram form only reads; it does not combine '
+                             'with %s' % ', '.join(refused))
+        if scipy.sparse.issparse(X):
+            raise ValueError('dtype=float16 stores a dense X; a scipy sparse X stays sparse on the device with sparse_X=True '
+                             '(float32 / float64 values), or pass X.toarray()')
     if group is not None:
         # host work that would need the other ranks' rows (the SVD behind the NNDSVD start, document frequencies,
         # per-row weights with their refit) or that decides per rank (callbacks) is not part of the sharded call
@@ -511,7 +530,9 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     if spec is not None:
         host_callbacks = bool(diagnostics) or bool(store_gradients) or \
             (callable(early_stop) and getattr(early_stop, 'device_entries', None) is None)
-        if scipy.sparse.issparse(X) or W_mat is not None or w_row is not None or host_callbacks:
+        # (float16 storage: tf-idf and normalisation in float64 on the host, so that X is rounded once, at upload -- the device
+        # route would round the raw X and then rewrite it)
+        if scipy.sparse.issparse(X) or W_mat is not None or w_row is not None or host_callbacks or half:
             X, rtv['idf'] = _preprocess_on_host(X, *spec)
         else:
             device_spec = {'tfidf': spec[0], 'normalize': spec[1]}
@@ -749,6 +770,8 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
 
         W, T = current()
         n_resets_used = eng.n_resets_used
+        if half:
+            rtv['x_storage_relerr'] = eng.storage_relerr
         keep_handle = resident is not None and resident.engine is eng
     finally:
         if keep_handle:

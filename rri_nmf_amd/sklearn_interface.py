@@ -263,9 +263,15 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
                     reg_w_l1=self.wr1, reg_w_l2=self.wr2, reg_t_l1=self.tr1, reg_t_l2=self.tr2,
                     random_state=self.random_state,
                     **self._preprocess_kwargs(idf=self.idf if self.handle_tfidf else None),
-                    # the one storage option of nmf_kwargs the fold-in follows: X kept as CSR on the device
-                    **({'sparse_X': self.nmf_kwargs['sparse_X']} if 'sparse_X' in self.nmf_kwargs else {}))
+                    # the storage options of nmf_kwargs the fold-in follows: X kept as CSR on the device, and a float16 store
+                    # (without it the fold-in would upload the new rows at 8 bytes per entry)
+                    **({'sparse_X': self.nmf_kwargs['sparse_X']} if 'sparse_X' in self.nmf_kwargs else {}),
+                    **({'dtype': np.float16} if self._half_storage() else {}))
         return soln['W']
+
+    def _half_storage(self):
+        dt = self.nmf_kwargs.get('dtype')
+        return dt is not None and np.dtype(dt) == np.float16
 
     def constrained_transform(self, X):
         return self.transform(X)
