@@ -114,8 +114,9 @@ uint32_t   rri_abi_version(void);
  * canonical CSR (8 B of index and value per stored fp32 entry, 12 B fp64) and two blocked copies of it, rows and columns as
  * segments (6 B per entry each fp32, 10 B fp64, plus a 4-byte position), and no dense n x d array at all; every topic step reads
  * both copies once (12 nnz bytes fp32) in one launch.  It refuses (RRI_ERR_UNSUPPORTED) rri_upload_X, rri_bind_X_device, every
- * mask, rri_attach_comm, rri_range_finder and the device preprocessing (rri_column_positive_counts, rri_scale_X; tf-idf /
- * normalisation of a CSR X belong on the host), never takes the persistent on-chip path, and takes at most 2^31 - 2 entries.
+ * mask, rri_attach_comm and rri_range_finder, and answers RRI_ERR_INVALID to the dense preprocessing calls
+ * (rri_column_positive_counts, rri_scale_X): tf-idf / normalisation of a CSR X have their own pair,
+ * rri_csr_column_positive_counts and rri_csr_scale_X.  Never takes the persistent on-chip path; at most 2^31 - 2 entries.
  * device: HIP device ordinal.  stream: hipStream_t to run on, or NULL for an own stream. */
 rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dtype,
                       int32_t weighted, int32_t device, void* stream);
@@ -252,6 +253,20 @@ rri_status rri_range_finder(rri_ctx* ctx, const double* Q0, int32_t m, int32_t n
  * float64 arithmetic, rounded to the handle's storage type when stored. */
 rri_status rri_column_positive_counts(rri_ctx* ctx, double* df_out);
 rri_status rri_scale_X(rri_ctx* ctx, const double* col_scale, int32_t normalize_rows);
+/* The same two steps (matrixops.py:124-179) on the X of an RRI_UNWEIGHTED_SPARSE handle; RRI_ERR_INVALID on every other handle
+ * and before rri_upload_X_csr.  The stored values are rewritten and both blocked copies gathered from them again.
+ *   rri_csr_column_positive_counts  df[j] = number of STORED entries of column j that are > 0 (explicit zeros do not count):
+ *                               exact integers, the same bits on every run.
+ *   rri_csr_scale_X             x <- (1 / tot[i]) * (x * col_scale[j]) with tot[i] = sum_j x * col_scale[j] + spacing(1) when
+ *                               normalize_rows != 0 (matrixops.py:139-142), else x * col_scale[j] (:172); col_scale == NULL: ones.
+ *                               float64 arithmetic, one rounding to the storage type.  A row with tot[i] < 1e-10 -- an empty one,
+ *                               or a document made only of terms whose idf is 0 -- would become the DENSE row 1/d (:143-147),
+ *                               which the pattern cannot take: the totals are therefore taken before anything is written, and
+ *                               when there are such rows X is left bit for bit as it was, *zero_rows_out is their number (> 0)
+ *                               and the call returns RRI_OK; the caller preprocesses that matrix on the host.  Otherwise
+ *                               *zero_rows_out = 0.  zero_rows_out may be NULL only when normalize_rows == 0. */
+rri_status rri_csr_column_positive_counts(rri_ctx* ctx, double* df_out);
+rri_status rri_csr_scale_X(rri_ctx* ctx, const double* col_scale, int32_t normalize_rows, int64_t* zero_rows_out);
 
 /* ---- row-sharded multi-GPU inside the library (one process per GPU; SURVEY 8b "sharded by row block internally",
  *      8e).  The reference has one call for the whole X (nmf.py:98-108); here every rank creates a handle for its row

@@ -3628,6 +3628,80 @@ rri_status rri_scale_X(rri_ctx* c, const double* col_scale, int32_t normalize_ro
     return RRI_OK;
 }
 
+// ... and of an X kept as CSR (rri_sparse_kernels.hpp: k_spx_poscount, k_spx_rowtot, k_spx_scale)
+rri_status rri_csr_column_positive_counts(rri_ctx* c, double* df_out) {
+    CHECK_CTX(c);
+    if (!df_out) return fail(c, RRI_ERR_INVALID, "df_out is NULL");
+    if (!c->sparse_x || !c->have_X) return fail(c, RRI_ERR_INVALID, "needs an RRI_UNWEIGHTED_SPARSE handle with an X");
+    HIPCHK(c, hipSetDevice(c->device));
+    DevTmp out;
+    HIPCHK(c, out.alloc((size_t)c->d * sizeof(double)));
+    const rri_ctx::SpCopy& cc = c->sp[1];      // columns as segments; its values are X's (k_sp_permute after every rewrite)
+    DISPATCH(c, hipLaunchKernelGGL((k_spx_poscount<typename L::Elem>), dim3((unsigned)((c->d + 3) / 4)), dim3(256), 0, c->stream,
+                                   (const i64*)cc.segptr, cc.nseg, cc.nblk, (const typename L::Elem*)cc.val, (double*)out.p));
+    HIPCHK(c, hipMemcpyAsync(df_out, out.p, (size_t)c->d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RRI_OK;
+}
+
+extern "C++" {
+// one group of 8 lanes per row, a whole wave from 64 entries per row on: the summation order of a row is fixed by the shape
+template <typename SX, int LPS>
+static void launch_spx_scale_lps(rri_ctx* c, const double* sdev, double* tot, unsigned long long* nzero, bool totals) {
+    const unsigned nb = (unsigned)((c->n + 256 / LPS - 1) / (256 / LPS));
+    if (totals)
+        hipLaunchKernelGGL((k_spx_rowtot<SX, LPS>), dim3(nb), dim3(256), 0, c->stream, (const i64*)c->sp_rowptr,
+                           (const int*)c->sp_col, (const SX*)c->sp_x, c->n, sdev, tot, nzero);
+    else
+        hipLaunchKernelGGL((k_spx_scale<SX, LPS>), dim3(nb), dim3(256), 0, c->stream, (const i64*)c->sp_rowptr,
+                           (const int*)c->sp_col, (SX*)c->sp_x, c->n, sdev, (const double*)tot);
+}
+template <typename SX>
+static void launch_spx_scale(rri_ctx* c, const double* sdev, double* tot, unsigned long long* nzero, bool totals) {
+    if (c->nnz / std::max<i64>(c->n, 1) >= 64) launch_spx_scale_lps<SX, 64>(c, sdev, tot, nzero, totals);
+    else launch_spx_scale_lps<SX, 8>(c, sdev, tot, nzero, totals);
+}
+}
+
+rri_status rri_csr_scale_X(rri_ctx* c, const double* col_scale, int32_t normalize_rows, int64_t* zero_rows_out) {
+    CHECK_CTX(c);
+    if (!c->sparse_x || !c->have_X) return fail(c, RRI_ERR_INVALID, "needs an RRI_UNWEIGHTED_SPARSE handle with an X");
+    if (zero_rows_out) *zero_rows_out = 0;
+    if (!col_scale && !normalize_rows) return RRI_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
+    DevTmp sd, tt, nz;
+    if (col_scale) {
+        HIPCHK(c, sd.alloc((size_t)c->d * sizeof(double)));
+        HIPCHK(c, hipMemcpyAsync(sd.p, col_scale, (size_t)c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    if (normalize_rows) {
+        HIPCHK(c, tt.alloc((size_t)c->n * sizeof(double)));
+        HIPCHK(c, nz.alloc(sizeof(unsigned long long)));
+        HIPCHK(c, hipMemsetAsync(nz.p, 0, sizeof(unsigned long long), c->stream));
+        DISPATCH(c, launch_spx_scale<typename L::Elem>(c, (const double*)sd.p, (double*)tt.p, (unsigned long long*)nz.p, true));
+        unsigned long long zero_rows = 0;
+        HIPCHK(c, hipMemcpyAsync(&zero_rows, nz.p, sizeof(zero_rows), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (zero_rows > 0) {      // normalize would make these rows dense (1/d): nothing has been written, X is what it was
+            if (!zero_rows_out) return fail(c, RRI_ERR_INVALID, "%llu rows sum to less than 1e-10 and zero_rows_out is NULL", zero_rows);
+            *zero_rows_out = (int64_t)zero_rows;
+            return RRI_OK;
+        }
+    }
+    DISPATCH(c, launch_spx_scale<typename L::Elem>(c, (const double*)sd.p, (double*)tt.p, nullptr, false));
+    if (c->nnz > 0)
+        DISPATCH(c, for (int w = 0; w < 2; ++w)
+                        hipLaunchKernelGGL((k_sp_permute<typename L::Elem>), dim3(2048), dim3(256), 0, c->stream,
+                                           (const typename L::Elem*)c->sp_x, (const int*)c->sp[w].perm, c->sp[w].count,
+                                           (typename L::Elem*)c->sp[w].val));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    invalidate(c);
+    c->q_valid = false; c->gfull_valid = false;
+    c->x_sq_valid = false;
+    return RRI_OK;
+}
+
 // ---- row-sharded multi-GPU ---------------------------------------------------------------------------------
 rri_status rri_reduce_buffer(rri_ctx* c, void** dev_ptr, int64_t* n_elems) {
     CHECK_CTX(c);

@@ -359,6 +359,71 @@ __global__ __launch_bounds__(256) void k_sp_permute(const SX* __restrict__ e, co
     }
 }
 
+// ---- tf-idf and row normalisation of an X kept as CSR (matrixops.py:124-179; rri_csr_column_positive_counts, rri_csr_scale_X) ----
+// Preprocessing rewrites the canonical values sp_x; the two blocked copies are then gathered from them again by k_sp_permute.
+//   k_spx_poscount  df_j = number of stored x_ij > 0 (explicit zeros and the pads of a segment do not count): a wave walks the
+//                   segments of column j in the column copy, row block after row block, and adds integers -- exact, no atomics
+//                   (atomic increments of a d-long counter from the canonical CSR took 2.0 ms at 6.3 M Zipf entries, nearly all
+//                   of it the 10^5 increments of the one counter of the most frequent term; this walk takes 0.23 ms there, the
+//                   time of the one wave that walks that term's 10^5 entries)
+//   k_spx_rowtot    tot_i = sum_j (double(x_ij) * s_j) + spacing(1), one group of LPS lanes per row, lane-strided, the products
+//                   rounded before they are added (the host adds the stored products of X.multiply(idf)); *nzero counts the rows
+//                   with tot_i < 1e-10 -- normalize's zero_sum_fix makes those DENSE rows 1/d, which a CSR pattern cannot take, so
+//                   the host launches nothing further when there is one and X stays as it was
+//   k_spx_scale     x_ij <- (1 / tot_i) * (double(x_ij) * s_j), or double(x_ij) * s_j without tot; rounded once, when stored
+template <typename SX>
+__global__ __launch_bounds__(256) void k_spx_poscount(const i64* __restrict__ segptr, i64 nseg, int nblk,
+                                                      const SX* __restrict__ val, double* __restrict__ df) {
+    const int lane = threadIdx.x & 63;
+    const i64 j = (i64)blockIdx.x * 4 + (threadIdx.x >> 6);      // one wave per column: it leaves or stays as a whole
+    if (j >= nseg) return;
+    unsigned cnt = 0;
+    for (int b = 0; b < nblk; ++b) {
+        const i64 p0 = segptr[(i64)b * (nseg + 1) + j], p1 = segptr[(i64)b * (nseg + 1) + j + 1];
+        for (i64 p = p0 + lane; p < p1; p += 64) cnt += val[p] > SX(0) ? 1u : 0u;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    if (lane == 0) df[j] = (double)cnt;
+}
+
+template <typename SX, int LPS>
+__global__ __launch_bounds__(256) void k_spx_rowtot(const i64* __restrict__ rowptr, const int* __restrict__ col,
+                                                    const SX* __restrict__ xval, i64 n, const double* __restrict__ s,
+                                                    double* __restrict__ tot, unsigned long long* __restrict__ nzero) {
+    const int sub = threadIdx.x % LPS;
+    const i64 i = (i64)blockIdx.x * (256 / LPS) + threadIdx.x / LPS;
+    const bool live = i < n;                                 // the lanes of a dead group still take part in the shuffles
+    const i64 p0 = live ? rowptr[i] : 0, p1 = live ? rowptr[i + 1] : 0;
+    double acc = 0.0;
+    for (i64 p = p0 + sub; p < p1; p += LPS) {
+        const double x = (double)xval[p];
+        acc += s ? __dmul_rn(x, s[col[p]]) : x;
+    }
+    acc = group_sum<LPS>(acc);
+    if (live && sub == 0) {
+        const double t = acc + 2.220446049250313e-16;        // np.spacing(1), matrixops.py:140
+        tot[i] = t;
+        if (t < 1e-10) atomicAdd(nzero, 1ull);
+    }
+}
+
+template <typename SX, int LPS>
+__global__ __launch_bounds__(256) void k_spx_scale(const i64* __restrict__ rowptr, const int* __restrict__ col,
+                                                   SX* __restrict__ xval, i64 n, const double* __restrict__ s,
+                                                   const double* __restrict__ tot) {
+    const int sub = threadIdx.x % LPS;
+    const i64 i = (i64)blockIdx.x * (256 / LPS) + threadIdx.x / LPS;
+    if (i >= n) return;
+    const i64 p0 = rowptr[i], p1 = rowptr[i + 1];
+    const double r = tot ? 1.0 / tot[i] : 1.0;
+    for (i64 p = p0 + sub; p < p1; p += LPS) {
+        const double x = (double)xval[p];
+        const double t = s ? x * s[col[p]] : x;              // X * idf               (matrixops.py:172)
+        xval[p] = (SX)(tot ? r * t : t);                     // diag(1 / tot) X       (:141-142)
+    }
+}
+
 // Sparse-times-dense products with the X on the pattern, for the randomized SVD behind the NNDSVD start of the
 // recommender flavour (initialization.py:104-105 on W_mat .* X; 16 such products, 0.5 s each in scipy at 5e7 entries):
 //   out[blk][seg][v] = sum over the entries p of segment (blk, seg) of x_p * B[blk * bw + idx[p]][v]      v < m <= 64

@@ -25,6 +25,17 @@ _RESET_CODES = {None: _capi.RESET_NONE, 'max_resid_document': _capi.RESET_MAX_RE
                 'random': _capi.RESET_RANDOM}
 
 
+class ZeroTotalRows(ValueError):
+    """Row normalisation of an X kept as CSR met `count` rows whose total is below 1e-10 -- empty documents, or documents made
+    only of terms that occur in every document (idf 0).  matrixops.normalize makes such a row the dense row 1/d, which a CSR
+    pattern cannot take: nothing was rewritten, the handle's X is unchanged."""
+
+    def __init__(self, count):
+        ValueError.__init__(self, '%d row(s) of X sum to less than 1e-10: normalisation would make them dense (1/d), which an X '
+                                  'kept as CSR cannot hold; X was left unchanged' % count)
+        self.count = int(count)
+
+
 def _as_host(a, what, half=False):
     """C-contiguous float32/float64 view or copy of a matrix (never mutates the caller's); half: a float16 array stays one
     (the X of a float16 handle)"""
@@ -489,6 +500,8 @@ class RRIEngine(object):
     def preprocess(self, tfidf=False, normalize=False):
         """tf-idf and/or row normalisation of the resident X, as matrixops.tfidf / normalize produce them.
         tfidf: True (idf from this X), an idf vector (transform of new documents), or False.  Returns the idf used."""
+        if self.sparse_x:
+            return self._preprocess_csr(tfidf, normalize)
         idf = None
         if tfidf is True:
             df = self.column_positive_counts()
@@ -502,6 +515,28 @@ class RRIEngine(object):
             idf = np.asarray(tfidf, dtype=np.float64).ravel()
         if idf is not None or normalize:
             self.scale_X(idf, normalize)
+        return idf
+
+    def _preprocess_csr(self, tfidf, normalize):
+        """preprocess() on a handle that keeps X as CSR (rri_csr_column_positive_counts, rri_csr_scale_X): the stored values are
+        rewritten.  Row normalisation turns a row whose total is below 1e-10 into the dense row 1/d (matrixops.py:143-147),
+        which the pattern cannot hold: ZeroTotalRows is raised then and X is what it was before the call."""
+        as_ptr = lambda v: v.ctypes.data_as(C.POINTER(C.c_double))
+        idf = None
+        if tfidf is True:
+            df = np.empty(self.d, dtype=np.float64)
+            self._check(self._lib.rri_csr_column_positive_counts(self._h, as_ptr(df)))
+            idf = np.log(self.n / (df + np.spacing(1)))       # matrixops.py:169-170
+        elif tfidf is not False and tfidf is not None:
+            idf = np.ascontiguousarray(tfidf, dtype=np.float64).ravel()
+            if idf.size != self.d:
+                raise ValueError('col_scale must have d entries')
+        if idf is not None or normalize:
+            zero_rows = C.c_int64(0)
+            self._check(self._lib.rri_csr_scale_X(self._h, None if idf is None else as_ptr(idf), int(bool(normalize)),
+                                                  C.byref(zero_rows)))
+            if zero_rows.value:
+                raise ZeroTotalRows(int(zero_rows.value))
         return idf
 
     # ---- row-sharded stepping -----------------------------------------------------------

@@ -48,7 +48,7 @@ import time
 import numpy as np
 import scipy.sparse
 
-from .engine import RRIEngine
+from .engine import RRIEngine, ZeroTotalRows
 from .initialization import initialize_nmf
 from .matrixops import normalize, proj_mat_to_simplex
 from .optimization import universal_stopping_condition
@@ -150,6 +150,45 @@ def sparse_x_route(sparse_X, x_is_sparse, n, d, itemsize, free_bytes):
 def _device_free_bytes(device):
     import torch
     return torch.cuda.mem_get_info(int(device))[0]
+
+
+def preprocess_route(csr_handle, x_is_sparse, normalize=False, has_empty_row=False, W_mat=False, w_row=False,
+                     host_callbacks=False, half=False, group=False):
+    """Where the `preprocess` option of nmf() runs: 'device' (X goes up raw and is rewritten there) or 'host' (matrixops on the
+    host before the upload).  csr_handle: the answer of sparse_x_route -- X is kept as CSR on the device; x_is_sparse: X is a
+    scipy sparse matrix; the other arguments say what the call asks for.
+      weights, per-row weights, callbacks that see X on the host (diagnostics, store_gradients, a plain early_stop function) and
+      float16 storage need the preprocessed X in host memory: 'host';
+      a CSR handle: 'device' -- unless rows are to be normalised and one of them stores nothing: normalize makes it the dense row
+      1/d, which the pattern cannot take, and np.diff(indptr) shows it before anything is uploaded: 'host';
+      every other X, a scipy sparse one that is densified on the device included: 'device' (the dense kernel writes such rows);
+      row-sharded (group): a dense X without weights or callbacks runs on the device, everything else is not built."""
+    if group and (x_is_sparse or csr_handle or W_mat or w_row or host_callbacks):
+        raise NotImplementedError('row-sharded preprocessing runs on the device: a dense X without weights or callbacks')
+    if W_mat or w_row or host_callbacks or half:
+        return 'host'
+    if csr_handle and normalize and has_empty_row:
+        return 'host'
+    return 'device'
+
+
+def _route_of_call(X, spec, sparse_X=None, dtype=None, device=0, W_mat=None, w_row=None, host_callbacks=False,
+                   schedule='gram', group=None):
+    """(preprocess_route's answer, sparse_x_route's answer or None where that one is not asked) for the arguments of an nmf() call
+    with preprocessing `spec` = (tfidf, normalize); X is the caller's or nmf()'s converted one"""
+    half = dtype is not None and np.dtype(dtype) == np.float16
+    xs = scipy.sparse.issparse(X)
+    csr = None
+    if W_mat is None and w_row is None and schedule == 'gram' and not half and group is None:
+        n, d = X.shape
+        free = _device_free_bytes(device) if (sparse_X is None and xs) else 0
+        csr = sparse_x_route(sparse_X, xs, n, d, np.dtype(dtype or np.float64).itemsize, free)
+    empty = False
+    if csr and spec[1]:
+        empty = bool(np.any(np.diff(X.tocsr().indptr) == 0)) if xs else not bool(np.all(np.any(np.asarray(X) != 0, axis=1)))
+    route = preprocess_route(bool(csr), xs, normalize=spec[1], has_empty_row=empty, W_mat=W_mat is not None,
+                             w_row=w_row is not None, host_callbacks=host_callbacks, half=half, group=group is not None)
+    return route, csr
 
 
 def _engine_with_problem(X, W_mat, k, sdt, device, sparse_pattern=None, schedule='gram', sparse_X=None):
@@ -461,8 +500,10 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
 
     preprocess (keyword only, not in the reference's signature): tf-idf and / or row normalisation of X
     (matrixops.py:124-179) before the factorisation -- {'tfidf': True | idf vector | False, 'normalize': bool} or
-    the step names.  A dense X without weights or host callbacks is uploaded raw and rewritten in place on the
-    device; every other case preprocesses on the host.  The idf used comes back as rtv['idf'].
+    the step names.  Without weights, host callbacks or float16 storage X is uploaded raw and rewritten on the device
+    (preprocess_route): a dense X and a scipy sparse X that is densified there in place, an X kept as CSR (sparse_X) in its
+    stored values -- except that normalising a CSR X with an empty row, or one whose tf-idf total is 0, would make that row
+    dense: such a matrix, like every other case, is preprocessed on the host.  The idf used comes back as rtv['idf'].
     resident (keyword only): a ResidentProblem that keeps the device handle -- X uploaded and preprocessed -- from one call to
     the next on the same problem (see there)."""
     if sparse_X is not None and not isinstance(sparse_X, (bool, np.bool_)):
@@ -520,19 +561,20 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     if scipy.sparse.issparse(X):
         X = X.tocsr() if w_row is None else X.toarray()
     elif sparse_X:
-        X = scipy.sparse.csr_matrix(np.asarray(X))    # kept as CSR on the device (preprocessing then takes the host route)
+        X = scipy.sparse.csr_matrix(np.asarray(X))    # kept as CSR on the device
     else:
         X = np.asarray(X)
     W_mat = _sparse_mask_or_dense(W_mat)
     rtv = {}
     spec = _preprocess_spec(preprocess)
-    device_spec = None
+    device_spec, csr_route = None, None
     if spec is not None:
         host_callbacks = bool(diagnostics) or bool(store_gradients) or \
             (callable(early_stop) and getattr(early_stop, 'device_entries', None) is None)
         # (float16 storage: tf-idf and normalisation in float64 on the host, so that X is rounded once, at upload -- the device
         # route would round the raw X and then rewrite it)
-        if scipy.sparse.issparse(X) or W_mat is not None or w_row is not None or host_callbacks or half:
+        route, csr_route = _route_of_call(X, spec, sparse_X, dtype, device, W_mat, w_row, host_callbacks, schedule, group)
+        if route == 'host':
             X, rtv['idf'] = _preprocess_on_host(X, *spec)
         else:
             device_spec = {'tfidf': spec[0], 'normalize': spec[1]}
@@ -614,15 +656,32 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     else:
         if resident is not None:
             resident.close()
-        eng = _engine_with_problem(X, W_mat, k, sdt, device, sparse_pattern, schedule, sparse_X)
+        # (with device preprocessing the question whether X stays CSR was answered for the route: the same answer here)
+        eng = _engine_with_problem(X, W_mat, k, sdt, device, sparse_pattern, schedule,
+                                   sparse_X if device_spec is None or csr_route is None else csr_route)
     keep_handle = False
     try:
         if group is not None:
             eng.attach_group(group)
         on_device = device_init if device_init is not None else (float(n) * d >= DEVICE_INIT_MIN_ELEMS)
+        if device_spec is not None and not reused:
+            try:
+                idf = eng.preprocess(**device_spec)
+            except ZeroTotalRows as exc:
+                # a CSR handle met a row that normalisation makes dense (a document of terms that occur everywhere: idf 0) and
+                # left X as it was: this matrix is preprocessed on the host after all, and no handle is kept for it
+                logger.info('%s -- preprocessing on the host instead' % exc)
+                eng.close()
+                if resident is not None:
+                    resident.close()
+                X, rtv['idf'] = _preprocess_on_host(X, *spec)
+                device_spec, resident, res_key = None, None, None
+                sdt = _storage_dtype(X, dtype)
+                eng = _engine_with_problem(X, W_mat, k, sdt, device, sparse_pattern, schedule, True)    # CSR again
         X_init = X
         if device_spec is not None:
-            idf = resident.idf if reused else eng.preprocess(**device_spec)
+            if reused:
+                idf = resident.idf
             rtv['idf'] = idf
             device_spec = {'tfidf': idf if idf is not None else False, 'normalize': device_spec['normalize']}
             on_device = True                 # the preprocessed X exists only on the device

@@ -200,7 +200,7 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
                  do_final_project_W=True, keep_resident=False):
         # keep_resident (not in the reference): fit / one_iter on the SAME array X keep its device handle -- X uploaded and
         # preprocessed -- between the calls (nmf.ResidentProblem; the caller must not modify X in place meanwhile); release()
-        # frees it
+        # frees it.  A scipy sparse X keeps its handle when its preprocessing runs on the device (_takes_holder)
         self.keep_resident = keep_resident
         self._resident = None
         self.n, self.d, self.k = n, d, k
@@ -224,7 +224,7 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
     def _solve(self, X, max_iter, max_time):
         W_in, T_in = self._warm_start()
         kw = dict(self._preprocess_kwargs(), **self.nmf_kwargs)
-        if self.keep_resident and not sp.issparse(X):
+        if self.keep_resident and self._takes_holder(X, kw):
             if self._resident is None:
                 self._resident = _nmf_module.ResidentProblem()
             kw['resident'] = self._resident
@@ -236,6 +236,21 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
         if self.handle_tfidf:
             self.idf = soln['idf']
         self._keep(soln)
+
+    @staticmethod
+    def _takes_holder(X, kw):
+        """keep_resident on a scipy sparse X: nmf() keeps a handle when the preprocessing asked for runs on the device
+        (nmf.preprocess_route); where it runs on the host -- a CSR handle and an empty row to normalise -- there is no holder, as
+        for every sparse X before the CSR handle preprocessed on the device"""
+        if not sp.issparse(X):
+            return True
+        spec = _nmf_module._preprocess_spec(kw.get('preprocess'))
+        if spec is None:
+            return False
+        route, _ = _nmf_module._route_of_call(X, spec, kw.get('sparse_X'), kw.get('dtype'), kw.get('device', 0), kw.get('W_mat'),
+                                              kw.get('w_row'), bool(kw.get('diagnostics')) or bool(kw.get('store_gradients')),
+                                              kw.get('schedule', 'gram'), kw.get('group'))
+        return route == 'device'
 
     def release(self):
         """free the device handle kept by keep_resident"""

@@ -1,0 +1,132 @@
+"""End-to-end wall time of the topic-model estimator on raw CSR term counts kept sparse on the device: where the time of
+NMF_TM_Estimator(handle_tfidf=True, handle_normalization=True, nmf_kwargs={'sparse_X': True}).fit(X_csr) goes, and what
+keep_resident=True saves per one_iter(X_csr) call.
+
+    python tools/e2e_sparse_tfidf_probe.py [--density 0.002 0.01 0.05] [--reps 5] [--calls 20] [--label NAME] [--out FILE.jsonl]
+                                           [--tree DIR]
+
+100000 x 10000 Zipf counts (tools/sparse_x_probe.zipf_counts), k = 50, fp32 storage, 30 sweeps per fit.  One JSON line per
+density: medians over --reps fits of the wall time and of its parts --
+    host_prep   matrixops on the host (nmf._preprocess_on_host)          upload    rri_upload_X_csr incl. the store build
+    device_prep RRIEngine.preprocess                                     start     the starting W, T (NNDSVD)
+    sweeps      rri_sweep / rri_sweep_until / rri_objective              other     the rest of the call
+-- and the median of --calls one_iter calls with and without keep_resident, in the same process (--calls 0: fits only).
+--tree DIR imports rri_nmf_amd from another checkout (built there), to put two commits side by side on one device; --label
+names the line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+from sparse_x_probe import zipf_counts  # noqa: E402  (imports the package of THIS checkout for its own measurements only)
+
+PARTS = ('host_prep', 'upload', 'device_prep', 'start', 'sweeps')
+
+
+def load_package(tree):
+    for name in [m for m in sys.modules if m == 'rri_nmf_amd' or m.startswith('rri_nmf_amd.')]:
+        del sys.modules[name]
+    sys.path.insert(0, os.path.abspath(tree))
+    from rri_nmf_amd import engine, nmf, sklearn_interface
+    assert os.path.abspath(os.path.dirname(os.path.dirname(nmf.__file__))) == os.path.abspath(tree)
+    return engine, nmf, sklearn_interface
+
+
+class Clock(object):
+    """sums the wall time spent inside the wrapped functions, per part; nested parts count for the outer one only"""
+
+    def __init__(self):
+        self.t = dict.fromkeys(PARTS, 0.0)
+        self.depth = 0
+
+    def reset(self):
+        self.t = dict.fromkeys(PARTS, 0.0)
+
+    def wrap(self, fn, part):
+        def timed(*a, **kw):
+            if self.depth:
+                return fn(*a, **kw)
+            self.depth += 1
+            t0 = time.perf_counter()
+            try:
+                return fn(*a, **kw)
+            finally:
+                self.t[part] += time.perf_counter() - t0
+                self.depth -= 1
+        return timed
+
+
+def instrument(engine, nmf, clock):
+    E = engine.RRIEngine
+    nmf._preprocess_on_host = clock.wrap(nmf._preprocess_on_host, 'host_prep')
+    nmf._initialize_and_validate = clock.wrap(nmf._initialize_and_validate, 'start')
+    E.upload_X_csr = clock.wrap(E.upload_X_csr, 'upload')
+    E.preprocess = clock.wrap(E.preprocess, 'device_prep')
+    for name in ('sweep', 'sweep_until', 'objective'):
+        setattr(E, name, clock.wrap(getattr(E, name), 'sweeps'))
+
+
+def median(v):
+    return float(np.median(np.asarray(v, dtype=np.float64)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--density', type=float, nargs='+', default=[0.002, 0.01, 0.05])
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--calls', type=int, default=20)
+    ap.add_argument('--label', default='this checkout')
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--tree', default=os.path.dirname(HERE))
+    args = ap.parse_args()
+    engine, nmf, si = load_package(args.tree)
+    clock = Clock()
+    instrument(engine, nmf, clock)
+    n, d, k = 100000, 10000, 50
+    kw = dict(handle_tfidf=True, handle_normalization=True, random_state=0,
+              nmf_kwargs={'sparse_X': True, 'dtype': np.float32, 'eps_stop': -1})
+    for dens in args.density:
+        X = zipf_counts(n, d, dens, seed=int(dens * 1e4))
+        rec = {'tool': 'e2e_sparse_tfidf_probe', 'label': args.label, 'shape': [n, d], 'k': k, 'density_asked': dens,
+               'nnz': int(X.nnz), 'density': X.nnz / float(n * d), 'empty_rows': int(np.sum(np.diff(X.indptr) == 0))}
+        si.NMF_TM_Estimator(n, d, k, max_iter=2, **kw).fit(X)                       # warm-up: library, allocator, sklearn
+        walls, parts, sweeps = [], [], []
+        for _ in range(args.reps):
+            est = si.NMF_TM_Estimator(n, d, k, max_iter=30, **kw)
+            clock.reset()
+            t0 = time.perf_counter()
+            est.fit(X)
+            walls.append(time.perf_counter() - t0)
+            parts.append(dict(clock.t))
+            sweeps.append(len(est.nmf_outputs['iter_cputime']))
+        split = {p: median([q[p] for q in parts]) for p in PARTS}
+        split['other'] = median([w - sum(q.values()) for w, q in zip(walls, parts)])
+        rec['fit'] = {'wall_s_median': median(walls), 'wall_s': walls, 'split_s_median': split, 'sweeps': sweeps,
+                      'route': 'host' if split['host_prep'] > 0 else 'device'}
+        for keep in ((True, False) if args.calls > 0 else ()):
+            est = si.NMF_TM_Estimator(n, d, k, max_iter=2, keep_resident=keep, **kw).fit(X)
+            calls = []
+            for _ in range(args.calls):
+                t0 = time.perf_counter()
+                est.one_iter(X)
+                calls.append(time.perf_counter() - t0)
+            holder = getattr(est, '_resident', None)
+            rec['one_iter_keep_resident' if keep else 'one_iter'] = {
+                'ms_median': 1e3 * median(calls), 'ms_min': 1e3 * min(calls), 'ms_max': 1e3 * max(calls),
+                'handle_reuses': int(holder.reuses) if holder is not None else 0}
+            if keep:
+                est.release()
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, 'a') as f:
+                f.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()
