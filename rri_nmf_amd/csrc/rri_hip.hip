@@ -124,6 +124,10 @@ struct rri_comm {
     bool aborted = false;                      // a rank left a collective sequence half way: the communicator is unusable
 };
 
+// What of the 256 MiB Infinity Cache the default-policy traffic of one topic step may fill, in MB (1e6 bytes): the chain's own
+// working set and, in what is left, a fixed part of X (pass_keep).  Chosen on sweeps/s by tools/pass_keep_probe.py.
+constexpr double PASS_CACHE_MB = 256.0;
+
 // The environment switches a handle keeps: read once, by rri_create (read_switches), so that a handle created later under
 // another environment cannot change the schedule of one that is already running (INTEGRATION.md lists them)
 struct rri_switches {
@@ -138,6 +142,7 @@ struct rri_switches {
     int rot_cal = 1;           // RRI_ROT_CAL=0: no calibration, rotation 0; 1: rotations {0, 1}; n > 1: rotations 0 .. n-1
     bool rot_debug = false;    // RRI_ROT_DEBUG (set): calibrate_rot prints its timings
     bool mask_bits = true;     // RRI_MASK_BITS=0: a 0/1 mask stays an fp array (no bit-packed copy)
+    double pass_cache_mb = PASS_CACHE_MB;   // RRI_PASS_CACHE_MB: what of the Infinity Cache a topic step may fill (pass_keep); 0: all of X streams
 };
 
 struct rri_ctx {
@@ -163,6 +168,7 @@ struct rri_ctx {
     // of the two for THIS handle's buffers (calibrate_rot); RRI_PASS_ROT forces one for all
     int rot_x = 0, rot_r = 0;
     bool rot_done = false;
+    int keep_q = -1;   // read-only pass over X: row blocks loaded with default policy, the others non-temporally; -1: all of X plain (pass_keep)
     bool gfull_valid = false;   // Gfull = T T^T of the current T (k_wsweep_rows)
     double *Gfull = nullptr, *Wsweep0 = nullptr, *wsum_part = nullptr, *wsums = nullptr;   // whole-sweep W half with T fixed: lazily allocated
     double *Y2part = nullptr, *Z2part = nullptr, *dtv = nullptr, *dwv = nullptr, *wold = nullptr, *zeros = nullptr;  // weighted
@@ -500,14 +506,17 @@ struct LaunchX {
     struct Upd {
         const double *a = nullptr, *b = nullptr, *a2 = nullptr, *b2 = nullptr, *b2sub = nullptr;
     };
-    // Non-temporal loads keep a streamed X from washing W, T and the partial sums out of the caches -- where X cannot
+    // Non-temporal loads keep a streamed matrix from washing W, T and the partial sums out of the caches -- where it cannot
     // stay there anyway.  A matrix that fits the 256 MB Infinity Cache is re-read from it by every pass: plain loads are
     // 4 % faster at 10000 x 1000 (2020 against 1937 sweeps/s, profiles/r02_c2_variants.log).
-    static bool pass_nt(const rri_ctx* c) {
-        return (double)c->n * (double)c->LD * (double)c->es > 192.0e6;
+    // The passes over a stored residual and the one pass of the preprocessing: all or nothing (their stores leave L2 on every
+    // pass; the read-only pass of the sweeps keeps a part of X instead, pass_keep).  The `keep` of pass_cfg: -1 plain, 0 streamed.
+    static int stream_whole(const rri_ctx* c) {
+        return (double)c->n * (double)c->LD * (double)c->es > 192.0e6 ? 0 : -1;
     }
     template <bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS>
-    static void pass_k(rri_ctx* c, void* Xp, i64 ldp, const double* trow, const double* wc, const Upd& u, const TgramJob& job) {
+    static void pass_k(rri_ctx* c, void* Xp, i64 ldp, const double* trow, const double* wc, const Upd& u, const TgramJob& job,
+                       int keep) {
         const int ncols = (int)std::min<i64>(ldp, c->LD);
         typedef typename std::conditional<(UPD > 0), SX, const SX>::type XT;
         hipLaunchKernelGGL((k_pass<SX, DO_Y, DO_Z, UPD, U, NT, RS>), dim3(c->npanels * c->nrb + job.nblocks), dim3(256),
@@ -518,19 +527,21 @@ struct LaunchX {
                            // it stays off.  Read-modify-write (UPD): +4-9 % at C3 (profiles/r02_residual_schedule_geometry.log)
                            // -- reads and writes of a window stay in the DRAM pages that are open
                            ((ro_pass_interleaved(c) || UPD > 0) ? c->nrb : 0) |
-                               ((c->sw.pass_rot >= 0 ? c->sw.pass_rot : (UPD > 0 ? c->rot_r : c->rot_x)) << 27));
+                               ((c->sw.pass_rot >= 0 ? c->sw.pass_rot : (UPD > 0 ? c->rot_r : c->rot_x)) << 27),
+                           keep);
     }
     // The read-only pass: 8 rows in flight per wave, the row dots (DO_Y) through LDS row sums.  The read-modify-write variants:
     // 16 rows in flight per wave, row dots by DPP wave sums -- 0.665 against 0.639 of 8 TB/s for the 8-row LDS row-sum variant
     // at C3 (profiles/r02_residual_schedule_geometry.log).  (The LDS-DMA ring k_pass_dma measured between +3 % and -9 % against
     // this pass, profiles/r04_pass_dma_ab.log, and was removed.)
+    // keep: -1 = default-policy loads (and stores) throughout; >= 0: non-temporal, but for `keep` row blocks of a read-only pass
     template <bool DO_Y, bool DO_Z, int UPD>
-    static void pass_cfg(rri_ctx* c, void* Xp, i64 ldp, const double* trow, const double* wc, const Upd& u = Upd{},
+    static void pass_cfg(rri_ctx* c, void* Xp, i64 ldp, const double* trow, const double* wc, int keep, const Upd& u = Upd{},
                          const TgramJob& job = TgramJob{}) {
         constexpr int U = UPD > 0 ? 16 : 8;
         constexpr bool RS = UPD == 0 && DO_Y;
-        if (pass_nt(c)) pass_k<DO_Y, DO_Z, UPD, U, true, RS>(c, Xp, ldp, trow, wc, u, job);
-        else pass_k<DO_Y, DO_Z, UPD, U, false, RS>(c, Xp, ldp, trow, wc, u, job);
+        if (keep >= 0) pass_k<DO_Y, DO_Z, UPD, U, true, RS>(c, Xp, ldp, trow, wc, u, job, keep);
+        else pass_k<DO_Y, DO_Z, UPD, U, false, RS>(c, Xp, ldp, trow, wc, u, job, 0);
     }
     // row dots against T[t,:] (DO_Y) and column sums against W[:,tz] (DO_Z); `job`: the Gram row of T[t,:] rides along
     template <bool DO_Y, bool DO_Z>
@@ -542,20 +553,20 @@ struct LaunchX {
                 return;
             }
         }
-        pass_cfg<DO_Y, DO_Z, 0>(c, c->X, c->ldx, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw, Upd{}, job);
+        pass_cfg<DO_Y, DO_Z, 0>(c, c->X, c->ldx, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw, c->keep_q, Upd{}, job);
     }
     // explicit-residual schedule: the same products over the stored residual R (c->E, stride LD)
     static void rpass_colsums(rri_ctx* c, int tz) {
         TimedScope ts(c, 0);
-        pass_cfg<false, true, 0>(c, c->E, c->LD, nullptr, c->W + (i64)tz * c->ldw);
+        pass_cfg<false, true, 0>(c, c->E, c->LD, nullptr, c->W + (i64)tz * c->ldw, stream_whole(c));
     }
     // R <- R - a b^T [- a2 (b2 - b2sub)^T] fused with the row dots (against trow) and column sums (against wc) of
     // the new R: the rank-one residual update north_star names
     static void rank_update(rri_ctx* c, void* R, i64 ldr, const Upd& u, const double* trow, const double* wc,
                             const TgramJob& job = TgramJob{}) {
         TimedScope ts(c, 3);
-        if (u.a2) pass_cfg<true, true, 2>(c, R, ldr, trow, wc, u, job);
-        else pass_cfg<true, true, 1>(c, R, ldr, trow, wc, u, job);
+        if (u.a2) pass_cfg<true, true, 2>(c, R, ldr, trow, wc, stream_whole(c), u, job);
+        else pass_cfg<true, true, 1>(c, R, ldr, trow, wc, stream_whole(c), u, job);
     }
     template <bool DO_Y, bool DO_Z, bool UPD2, bool WRITE, bool MBITS, int U, bool RS>
     static void wpass_k(rri_ctx* c, const double* trow, const double* wc, const double* a1, const double* b1,
@@ -2068,6 +2079,22 @@ rri_status clear_halt(rri_ctx* c) {
     return RRI_OK;
 }
 
+// How the read-only pass over a dense X loads it (rri_ctx::keep_q).  Between two passes the other kernels of a topic step load
+// and store, with default policy, W (read by k_wcol), the column-sum and row-dot partials (written by the pass, read by
+// k_reduce / k_wcol), T (read and written) and the Gram partials: a line of X survives in the Infinity Cache from one pass to
+// the next only while it and all of that fit (MI355X: about 256 MiB).  What the chain leaves of the capacity C is the budget of
+// X: an X inside it is read with default-policy loads throughout (-1); of a larger one, as many whole row blocks as fit, the
+// same ones in every pass, and the rest non-temporally, which neither allocates there nor evicts (k_pass).  C = 0 streams all.
+int pass_keep(const rri_ctx* c) {
+    const double chain = 8.0 * ((double)c->k * (double)c->ldw + 2.0 * (double)c->nrb * (double)c->LD +
+                                2.0 * (double)c->npanels * (double)c->n + 2.0 * (double)c->k * (double)c->LD +
+                                2.0 * (double)c->nwb * (double)(c->k + 2));
+    const double budget = c->sw.pass_cache_mb * 1.0e6 - chain;
+    const double block = (double)c->rpb * (double)c->LD * (double)c->es;
+    if ((double)c->n * (double)c->LD * (double)c->es <= budget) return -1;
+    return budget > 0.0 ? (int)std::min((double)c->nrb, std::floor(budget / block)) : 0;
+}
+
 // The only place that reads the switches a handle keeps: an unset variable means the default, whatever the handles
 // created before this one were created under
 rri_switches read_switches() {
@@ -2082,6 +2109,7 @@ rri_switches read_switches() {
     if (const char* e = getenv("RRI_ROT_CAL")) sw.rot_cal = std::max(0, atoi(e));
     sw.rot_debug = getenv("RRI_ROT_DEBUG") != nullptr;
     if (const char* e = getenv("RRI_MASK_BITS")) sw.mask_bits = atoi(e) != 0;
+    if (const char* e = getenv("RRI_PASS_CACHE_MB")) sw.pass_cache_mb = std::max(0.0, atof(e));
     return sw;
 }
 
@@ -2217,10 +2245,11 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     }
     c->nwb = (int)((n + 64 * WCOL_TILES - 1) / (64 * WCOL_TILES));   // k_wcol blocks = rows of Gpart
     c->nwb256 = (int)((n + 255) / 256);
+    c->ldw = n;
+    c->keep_q = pass_keep(c);
     c->ntb = (int)((d + 127) / 128);
     c->ntb32 = (int)((c->LD + 31) / 32);
     c->tpart_n = c->ntb;
-    c->ldw = n;
     c->nsplit = (int)std::max<i64>(1, std::min<i64>(8, d / 2048));
     c->red_elems = round_up(std::max<i64>(c->LD + (i64)GRAM_SLICES * (k + 2), weighted ? 2 * c->LD + 2 : 0), 4);
 
@@ -3613,7 +3642,7 @@ rri_status rri_scale_X(rri_ctx* c, const double* col_scale, int32_t normalize_ro
         // row sums of X * col_scale = the row dots of the streaming pass against col_scale
         const int tsave = c->timing;
         c->timing = 0;
-        DISPATCH(c, (L::template pass_cfg<true, false, 0>(c, c->X, c->ldx, sdev, c->W)));
+        DISPATCH(c, (L::template pass_cfg<true, false, 0>(c, c->X, c->ldx, sdev, c->W, L::stream_whole(c))));
         c->timing = tsave;
         hipLaunchKernelGGL(k_row_inverse, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream,
                            (const double*)c->Ypart, c->npanels, (int)c->n, invdev);

@@ -166,6 +166,61 @@ __device__ __forceinline__ void tgram_block(const double* __restrict__ T, i64 ld
     }
 }
 
+// The row loop of k_pass with the load policy LNT.  A macro, because the kernel needs the loop twice (a workgroup of a
+// non-temporal read-only pass takes default-policy loads in its kept row blocks) and every function form costs registers: as
+// a lambda -- even one called once -- the float64 read-only pass takes 82 VGPRs instead of 74, 5 waves per SIMD instead of 6.
+// One policy per WORKGROUP: a uniform branch around the 8 loads of a chunk is merged by the compiler into one plain load
+// (no nt left in the kernel), and two row loops one after the other cost the fp32 pass a wave per SIMD.
+#define RRI_PASS_ROWS(LNT) \
+    for (int l0 = 0; l0 < rpb; l0 += U) {                                                                         \
+        const int r = grow(l0);  /* the U rows of a chunk are consecutive */                                      \
+        if (r >= n) break;  /* later chunks lie further down still */                                             \
+        V x[U];                                                                                                   \
+        _Pragma("unroll")                                                                                         \
+        for (int u = 0; u < U; ++u) {                                                                             \
+            const int rr = r + u;                                                                                 \
+            x[u] = XV::zero();                                                                                    \
+            if (rr < n && ok) x[u] = stream_load<LNT>(reinterpret_cast<const V*>(X + (i64)rr * ldx + col));       \
+        }                                                                                                         \
+        _Pragma("unroll")                                                                                         \
+        for (int u = 0; u < U; ++u) {                                                                             \
+            const int rr = r + u;                                                                                 \
+            double wv = 0.0, na = 0.0, na2 = 0.0;                                                                 \
+            if (DO_Z && rr < n) wv = wsh[l0 + u];                                                                 \
+            if (UPD > 0 && rr < n) na = -ash[l0 + u];                                                             \
+            if (UPD > 1 && rr < n) na2 = -ash2[l0 + u];                                                           \
+            double xe[VN];                                                                                        \
+            XV::unpack(x[u], xe);                                                                                 \
+            if constexpr (UPD > 0) {                                                                              \
+        _Pragma("unroll")                                                                                         \
+                for (int e = 0; e < VN; ++e) {                                                                    \
+                    xe[e] = fma(na, bv[e], xe[e]);                                                                \
+                    if (UPD > 1) xe[e] = fma(na2, bv2[e], xe[e]);                                                 \
+                }                                                                                                 \
+                const V rounded = XV::pack(xe);                                                                   \
+                if (rr < n && ok) stream_store<NT>(reinterpret_cast<V*>(X + (i64)rr * ldx + col), rounded);       \
+                /* the stored residual is what later passes read: continue with the ROUNDED values */             \
+                if constexpr (sizeof(SX) == 4) XV::unpack(rounded, xe);                                           \
+            }                                                                                                     \
+            double yp = 0.0;                                                                                      \
+        _Pragma("unroll")                                                                                         \
+            for (int e = 0; e < VN; ++e) {                                                                        \
+                if (DO_Y) yp = fma(xe[e], tv[e], yp);                                                             \
+                if (DO_Z) zacc[e] = fma(wv, xe[e], zacc[e]);                                                      \
+            }                                                                                                     \
+            if constexpr (DO_Y && RS) wave_rowsum8_park(tile, u, lane, yp);                                       \
+            else if (DO_Y) {                                                                                      \
+                /* the same six DPP steps as wave_sum: the total where they leave it (lane 63), stored from there */ \
+                const double tot = wave_sum_lane63<double>(yp);                                                   \
+                if (lane == 63) ysh[wave * rpb + l0 + u] = tot;                                                   \
+            }                                                                                                     \
+        }                                                                                                         \
+        if constexpr (DO_Y && RS) {                                                                               \
+            const double tot = wave_rowsum8_finish(tile, lane);                                                   \
+            if ((lane & 7) == 0) ysh[wave * rpb + l0 + (lane >> 3)] = tot;                                        \
+        }                                                                                                         \
+    }
+
 // Block = 4 waves = 4 ADJACENT column panels (one per wave, 64 lanes * 16 B each) x one row block.
 // Every wave walks all rows of the block, U rows in flight; the 4 row-dot partials of a row meet in
 // LDS slots [wave][row] and are added in a fixed order at the end (Ypart has one slice per 4 panels);
@@ -181,7 +236,8 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
                                               int rpb, int npg, const double* __restrict__ avec,
                                               const double* __restrict__ bvec, const double* __restrict__ avec2,
                                               const double* __restrict__ bvec2, const double* __restrict__ bsub2,
-                                              const DevState* __restrict__ st, const TgramJob job, int nrb_il_rot) {
+                                              const DevState* __restrict__ st, const TgramJob job, int nrb_il_rot,
+                                              int keep_q) {
     typedef XVec<SX> XV;
     typedef typename XV::type V;
     constexpr int VN = XV::N;
@@ -239,53 +295,15 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
         bv2[e] = (UPD > 1 && ok) ? bvec2[col + e] - bsub2[col + e] : 0.0;
     }
     if (wave_has_cols) {
-        for (int l0 = 0; l0 < rpb; l0 += U) {
-            const int r = grow(l0);                  // the U rows of a chunk are consecutive
-            if (r >= n) break;                       // later chunks lie further down still
-            V x[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int rr = r + u;
-                x[u] = XV::zero();
-                if (rr < n && ok) x[u] = stream_load<NT>(reinterpret_cast<const V*>(X + (i64)rr * ldx + col));
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int rr = r + u;
-                double wv = 0.0, na = 0.0, na2 = 0.0;
-                if (DO_Z && rr < n) wv = wsh[l0 + u];
-                if (UPD > 0 && rr < n) na = -ash[l0 + u];
-                if (UPD > 1 && rr < n) na2 = -ash2[l0 + u];
-                double xe[VN];
-                XV::unpack(x[u], xe);
-                if constexpr (UPD > 0) {
-#pragma unroll
-                    for (int e = 0; e < VN; ++e) {
-                        xe[e] = fma(na, bv[e], xe[e]);
-                        if (UPD > 1) xe[e] = fma(na2, bv2[e], xe[e]);
-                    }
-                    const V rounded = XV::pack(xe);
-                    if (rr < n && ok) stream_store<NT>(reinterpret_cast<V*>(X + (i64)rr * ldx + col), rounded);
-                    // the stored residual is what later passes read: continue with the ROUNDED values
-                    if constexpr (sizeof(SX) == 4) XV::unpack(rounded, xe);
-                }
-                double yp = 0.0;
-#pragma unroll
-                for (int e = 0; e < VN; ++e) {
-                    if (DO_Y) yp = fma(xe[e], tv[e], yp);
-                    if (DO_Z) zacc[e] = fma(wv, xe[e], zacc[e]);
-                }
-                if constexpr (DO_Y && RS) wave_rowsum8_park(tile, u, lane, yp);
-                else if (DO_Y) {
-                    // the same six DPP steps as wave_sum, the total taken where they leave it (lane 63) and stored from there
-                    const double tot = wave_sum_lane63<double>(yp);
-                    if (lane == 63) ysh[wave * rpb + l0 + u] = tot;
-                }
-            }
-            if constexpr (DO_Y && RS) {
-                const double tot = wave_rowsum8_finish(tile, lane);
-                if ((lane & 7) == 0) ysh[wave * rpb + l0 + (lane >> 3)] = tot;
-            }
+        // keep_q of the nrb row blocks, spread evenly over the launch order, are read with default-policy loads and stay in
+        // the Infinity Cache from pass to pass; the others stream past it (host: pass_keep in rri_hip.hip)
+        if constexpr (NT && UPD == 0) {
+            const unsigned nrb = ((unsigned)gridDim.x - (unsigned)job.nblocks) / (unsigned)npg;
+            const bool kept = ((unsigned)(rb + 1) * (unsigned)keep_q) / nrb != ((unsigned)rb * (unsigned)keep_q) / nrb;
+            if (kept) { RRI_PASS_ROWS(false) }
+            else { RRI_PASS_ROWS(true) }
+        } else {
+            RRI_PASS_ROWS(NT)
         }
         if (DO_Z && ok) {
 #pragma unroll
@@ -302,6 +320,8 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
         }
     }
 }
+
+#undef RRI_PASS_ROWS
 
 // =========================================================================================
 // k_colsums: column sums of X against NV row-vectors at once (X^T Q for the randomized SVD behind NNDSVD,

@@ -196,8 +196,8 @@ int main(int argc, char** argv) {
             {
                 const size_t sh = ((5 + upd) * (size_t)rpb + 4 * 8 * 72) * sizeof(double);
                 double ms;
-                if (upd) ms = timeit([&] { hipLaunchKernelGGL((k_pass<float, true, true, 2, 16, true, false>), dim3(npg * nrb), dim3(256), sh, 0, X, ld, n, (int)ld, trow, wcol, Yr, Zr, ld, rpb, npg, avec, bvec, avec2, bvec2, (const double*)bvec /* b2 - b2sub */, (const DevState*)st, TgramJob{}, il); }, reps);
-                else ms = timeit([&] { hipLaunchKernelGGL((k_pass<float, true, true, 0, 8, true, true>), dim3(npg * nrb), dim3(256), sh, 0, (const float*)X, ld, n, (int)ld, trow, wcol, Yr, Zr, ld, rpb, npg, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (const DevState*)st, TgramJob{}, il); }, reps);
+                if (upd) ms = timeit([&] { hipLaunchKernelGGL((k_pass<float, true, true, 2, 16, true, false>), dim3(npg * nrb), dim3(256), sh, 0, X, ld, n, (int)ld, trow, wcol, Yr, Zr, ld, rpb, npg, avec, bvec, avec2, bvec2, (const double*)bvec /* b2 - b2sub */, (const DevState*)st, TgramJob{}, il, 0); }, reps);
+                else ms = timeit([&] { hipLaunchKernelGGL((k_pass<float, true, true, 0, 8, true, true>), dim3(npg * nrb), dim3(256), sh, 0, (const float*)X, ld, n, (int)ld, trow, wcol, Yr, Zr, ld, rpb, npg, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (const DevState*)st, TgramJob{}, il, 0); }, reps);
                 snprintf(nm, 160, "UPD %d  library k_pass (registers)      wgs %5d rpb %4d", upd, npg * nrb, rpb);
                 printf("%-64s %8.4f ms  %7.1f GB/s\n", nm, ms, bytes / ms / 1e6);
             }
