@@ -114,7 +114,7 @@ uint32_t   rri_abi_version(void);
  * canonical CSR (8 B of index and value per stored fp32 entry, 12 B fp64) and two blocked copies of it, rows and columns as
  * segments (6 B per entry each fp32, 10 B fp64, plus a 4-byte position), and no dense n x d array at all; every topic step reads
  * both copies once (12 nnz bytes fp32) in one launch.  It refuses (RRI_ERR_UNSUPPORTED) rri_upload_X, rri_bind_X_device, every
- * mask, rri_attach_comm and rri_range_finder, and answers RRI_ERR_INVALID to the dense preprocessing calls
+ * mask, rri_attach_comm and rri_range_finder (its range finder is rri_sparse_range_finder), and answers RRI_ERR_INVALID to the dense preprocessing calls
  * (rri_column_positive_counts, rri_scale_X): tf-idf / normalisation of a CSR X have their own pair,
  * rri_csr_column_positive_counts and rri_csr_scale_X.  Never takes the persistent on-chip path; at most 2^31 - 2 entries.
  * device: HIP device ordinal.  stream: hipStream_t to run on, or NULL for an own stream. */
@@ -244,6 +244,15 @@ rri_status rri_Xt_times(rri_ctx* ctx, const double* Q, int32_t m, double* out);
  * B_out (m x columns of A) are host arrays, row-major; 1 <= m <= 64.  Dense handles only. */
 rri_status rri_range_finder(rri_ctx* ctx, const double* Q0, int32_t m, int32_t n_iter, int32_t transpose, double* Q_out,
                             double* B_out);
+/* The same call for the handles that keep X sparse -- RRI_UNWEIGHTED_SPARSE (the CSR X) and RRI_WEIGHTED_SPARSE (X = the matrix
+ * of the observed values, as rri_X_times takes it) --, which rri_range_finder refuses: same contract, same arguments, same
+ * shifted Cholesky-QR in three passes (1e-9 trace shift in the first, pivots held at 1e-14 of their diagonal entry), float64
+ * arithmetic on the stored values.  Both panels stay on the device as tall row-major matrices, the layout the sparse products
+ * read and write; all sums are taken in a fixed order, so a rerun gives the same bits.  RRI_ERR_INVALID on a dense handle, before
+ * an upload, for m outside 1..64, n_iter < 0 and NULL arrays.  Rank-local (a handle with a communicator works on its own rows);
+ * borrows no buffer of the handle: a factorisation in progress goes on as if the call had not been made. */
+rri_status rri_sparse_range_finder(rri_ctx* ctx, const double* Q0, int32_t m, int32_t n_iter, int32_t transpose, double* Q_out,
+                                   double* B_out);
 
 /* Preprocessing of the resident dense X in place (unweighted handles):
  *   rri_column_positive_counts  df[j] = #{i : X[i,j] > 0}, the document frequencies of tfidf (matrixops.py:169)

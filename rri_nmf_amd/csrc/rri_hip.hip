@@ -759,6 +759,15 @@ struct LaunchX {
         hipLaunchKernelGGL(k_sp_sum_blocks, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream,
                            (const double*)part, count, cp.nblk, out);
     }
+    // the same product between two device panels of the range finder (rri_sparse_range_finder): with one block the sum over the
+    // blocks is a copy, and the product is written where it is wanted
+    static void sp_spmm_panel(rri_ctx* c, int which, const double* B, int m, double* part, double* out) {
+        const rri_ctx::SpCopy& cp = c->sp[which];
+        if (cp.nblk > 1) { sp_spmm(c, which, B, m, part, out); return; }
+        hipLaunchKernelGGL((k_sp_spmm<SX>), dim3((unsigned)((cp.nseg + 3) / 4)), dim3(256), 0, c->stream,
+                           (const i64*)cp.segptr, cp.nseg, 1, (const unsigned short*)cp.idx, (const int*)cp.perm,
+                           (const SX*)c->sp_x, cp.bw, B, m, out);
+    }
     static void sp_resid(rri_ctx* c, bool write_e, double* rowobj, double* rowpos, double* rowhat = nullptr) {
         const i64 total = (i64)c->k * c->d;
         hipLaunchKernelGGL((k_convert2d<double, double, true>), dim3((unsigned)std::min<i64>(4096, (total + 255) / 256)),
@@ -3593,6 +3602,102 @@ rri_status rri_range_finder(rri_ctx* c, const double* Q0, int32_t m, int32_t n_i
         if (s == RRI_OK) s = to_host(c, Pn, c->ldw, B_out, c->n, RRI_F64, m, c->n, RRI_F64, false);
     }
     return s;
+}
+
+// ---- the same range finder on a handle that keeps X sparse (RRI_UNWEIGHTED_SPARSE: the CSR X; RRI_WEIGHTED_SPARSE: the observed
+// values on the pattern) ----------------------------------------------------------------------------------------------------
+// There the 16 products went through rri_X_times / rri_Xt_times one by one, every (n or d) x m panel travelling to the host for
+// LU / QR and back.  Here both panels live on the device as TALL row-major matrices (rows x m), the layout k_sp_spmm reads and
+// writes, so a product's result is the next product's operand as it stands; they are allocated once, with the zero rows up to
+// nblk * bw that a copy's operand needs, as are the block partials.  The normalisation is the shifted Cholesky-QR of
+// cholqr2_rows (same host_cholesky, same three passes) on that layout: k_tall_gram_part / k_tall_gram_sum, k_tall_lsolve.
+// Nothing of the handle is borrowed -- no Ypart / Zpart / red, no state of a sweep --, so a factorisation in progress is left
+// as it is and nothing is invalidated.
+namespace {
+struct TallQR {
+    double *part = nullptr, *Gdev = nullptr, *Lp = nullptr;   // gram partials [npart_max][64][64], G (m x m), packed L (64 x 64 + 64)
+    std::vector<double> G, L = std::vector<double>((size_t)64 * 64 + 64, 0.0);   // L: the same entries are written for a given m
+};
+int tall_gram_parts(i64 rows) { return (int)std::max<i64>(1, std::min<i64>(512, (rows + TG_ROWS - 1) / TG_ROWS)); }
+
+rri_status cholqr_tall(rri_ctx* c, double* Y, i64 rows, int m, TallQR& q) {
+    const int npart = tall_gram_parts(rows);
+    q.G.resize((size_t)m * m);
+    for (int round = 0; round < 3; ++round) {
+        hipLaunchKernelGGL(k_tall_gram_part, dim3(npart), dim3(256), 0, c->stream, (const double*)Y, rows, m, q.part);
+        hipLaunchKernelGGL(k_tall_gram_sum, dim3((unsigned)((m * m + 255) / 256)), dim3(256), 0, c->stream, (const double*)q.part,
+                           npart, m, q.Gdev);
+        HIPCHK(c, hipMemcpyAsync(q.G.data(), q.Gdev, q.G.size() * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (!host_cholesky(q.G, m, round == 0 ? 1e-9 : 0.0)) return fail(c, RRI_ERR_INVALID, "range finder: the panel holds a non-finite value");
+        for (int i = 0; i < m; ++i) {       // as k_tall_lsolve reads it: column j of the strictly lower part contiguous, then 1 / L_ii
+            for (int j = 0; j < i; ++j) q.L[(size_t)j * 64 + i] = q.G[(size_t)i * m + j];
+            q.L[(size_t)4096 + i] = 1.0 / q.G[(size_t)i * m + i];
+        }
+        HIPCHK(c, hipMemcpyAsync(q.Lp, q.L.data(), q.L.size() * 8, hipMemcpyHostToDevice, c->stream));
+        const i64 groups = (rows + 4 * TS_ROWS - 1) / (4 * TS_ROWS);
+        hipLaunchKernelGGL(k_tall_lsolve, dim3((unsigned)std::max<i64>(1, std::min<i64>(1024, groups))), dim3(256), 0, c->stream, Y,
+                           rows, m, (const double*)q.Lp);      // (q.L is next written after the synchronise that follows this copy)
+    }
+    return RRI_OK;
+}
+}  // namespace
+
+rri_status rri_sparse_range_finder(rri_ctx* c, const double* Q0, int32_t m, int32_t n_iter, int32_t transpose, double* Q_out,
+                                   double* B_out) {
+    CHECK_CTX(c);
+    if (!c->sparse) return fail(c, RRI_ERR_INVALID, "a dense handle has rri_range_finder");
+    if (!c->have_X) return fail(c, RRI_ERR_INVALID, "X not set");
+    if (!Q0 || !Q_out || !B_out || m < 1 || m > 64 || n_iter < 0) return fail(c, RRI_ERR_INVALID, "bad operand (1 <= m <= 64)");
+    HIPCHK(c, hipSetDevice(c->device));
+    // Pd (d rows) is the operand of the row copy (X Pd), Pn (n rows) that of the column copy (X^T Pn)
+    const rri_ctx::SpCopy &cr = c->sp[0], &cc = c->sp[1];
+    const i64 rows_d = std::max<i64>(c->d, (i64)cr.nblk * cr.bw), rows_n = std::max<i64>(c->n, (i64)cc.nblk * cc.bw);
+    const i64 part_elems = std::max<i64>(cr.nblk > 1 ? (i64)cr.nblk * cr.nseg : 1, cc.nblk > 1 ? (i64)cc.nblk * cc.nseg : 1) * m;
+    DevTmp pd, pn, part, gpart, gd, lp;
+    HIPCHK(c, pd.alloc((size_t)rows_d * m * sizeof(double)));
+    HIPCHK(c, pn.alloc((size_t)rows_n * m * sizeof(double)));
+    HIPCHK(c, part.alloc((size_t)part_elems * sizeof(double)));
+    HIPCHK(c, gpart.alloc((size_t)tall_gram_parts(std::max(c->n, c->d)) * 4096 * sizeof(double)));
+    HIPCHK(c, gd.alloc((size_t)64 * 64 * sizeof(double)));
+    HIPCHK(c, lp.alloc((size_t)(64 * 64 + 64) * sizeof(double)));
+    double *Pd = (double*)pd.p, *Pn = (double*)pn.p;
+    HIPCHK(c, hipMemsetAsync(Pd, 0, (size_t)rows_d * m * sizeof(double), c->stream));
+    HIPCHK(c, hipMemsetAsync(Pn, 0, (size_t)rows_n * m * sizeof(double), c->stream));
+    TallQR q;
+    q.part = (double*)gpart.p; q.Gdev = (double*)gd.p; q.Lp = (double*)lp.p;
+    auto X_times_dev = [&]() { DISPATCH(c, L::sp_spmm_panel(c, 0, (const double*)Pd, m, (double*)part.p, Pn)); };    // Pn = X Pd
+    auto Xt_times_dev = [&]() { DISPATCH(c, L::sp_spmm_panel(c, 1, (const double*)Pn, m, (double*)part.p, Pd)); };   // Pd = X^T Pn
+    auto orth_n = [&]() { return cholqr_tall(c, Pn, c->n, m, q); };
+    auto orth_d = [&]() { return cholqr_tall(c, Pd, c->d, m, q); };
+    // A = X (transpose == 0: Q0 is d x m) or A = X^T (Q0 is n x m), as scikit-learn transposes when n < d
+    HIPCHK(c, hipMemcpyAsync(transpose ? Pn : Pd, Q0, (size_t)(transpose ? c->n : c->d) * m * sizeof(double), hipMemcpyHostToDevice,
+                             c->stream));
+    rri_status s = RRI_OK;
+    for (int it = 0; it < n_iter && s == RRI_OK; ++it) {
+        if (!transpose) {
+            X_times_dev();  s = orth_n();
+            if (s == RRI_OK) { Xt_times_dev(); s = orth_d(); }
+        } else {
+            Xt_times_dev(); s = orth_d();
+            if (s == RRI_OK) { X_times_dev(); s = orth_n(); }
+        }
+    }
+    if (s == RRI_OK) {
+        if (!transpose) {       // Q = orth(X Q) (n x m), B = Q^T X: Pd = X^T Q is its transpose (d x m)
+            X_times_dev();  s = orth_n();
+            if (s == RRI_OK) Xt_times_dev();
+        } else {                // Q = orth(X^T Q) (d x m), B = Q^T X^T: Pn = X Q is its transpose (n x m)
+            Xt_times_dev(); s = orth_d();
+            if (s == RRI_OK) X_times_dev();
+        }
+    }
+    if (s != RRI_OK) { (void)hipStreamSynchronize(c->stream); return s; }
+    const double* Qd = transpose ? Pd : Pn;
+    const double* Bt = transpose ? Pn : Pd;
+    const i64 rows_q = transpose ? c->d : c->n, cols_a = transpose ? c->n : c->d;
+    HIPCHK(c, hipMemcpyAsync(Q_out, Qd, (size_t)rows_q * m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return to_host(c, Bt, m, B_out, cols_a, RRI_F64, m, cols_a, RRI_F64, true);   // synchronises
 }
 
 // ---- preprocessing of the resident X ---------------------------------------------------------------------------

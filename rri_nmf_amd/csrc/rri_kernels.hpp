@@ -1780,6 +1780,101 @@ __global__ __launch_bounds__(256) void k_lsolve_rows(double* __restrict__ A, i64
         if (i < m) A[(i64)i * ld + r] = v[i];
 }
 
+// ---- the same two steps of Cholesky-QR on a TALL panel: Y is rows x m, row-major with no padding (m <= 64), the layout in which
+// k_sp_spmm reads its operand and writes its result (rri_sparse_range_finder) ----
+//
+// Partial Gram matrices of Y: the panel is read ONCE (k_gram reads an m x len panel once per entry of G).  A workgroup stages
+// TG_ROWS rows at a time in LDS (rows padded to 64 doubles, columns m..63 zero) and keeps a 64 x 64 accumulator in registers,
+// thread (ta, tb) the entries (tb + 16 i, ta + 16 j): in a step all lanes read one row -- 16 consecutive doubles per j across ta
+// (one 128-byte run per half wave, no bank shared) and 4 broadcast addresses per i.  Workgroup w takes the tiles w, w + grid, ...
+// in that order and leaves its sum at part[w][64][64] (entries a <= b < m only; the lower half is never read): no atomics,
+// the same bits on every run for a given grid.
+constexpr int TG_ROWS = 32;
+__global__ __launch_bounds__(256) void k_tall_gram_part(const double* __restrict__ Y, i64 rows, int m, double* __restrict__ part) {
+    __shared__ double tile[TG_ROWS * 64];
+    const int ta = threadIdx.x & 15, tb = threadIdx.x >> 4;
+    for (int e = threadIdx.x; e < TG_ROWS * 64; e += 256) tile[e] = 0.0;
+    double s[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[i][j] = 0.0;
+    const i64 ntile = (rows + TG_ROWS - 1) / TG_ROWS;
+    for (i64 t = blockIdx.x; t < ntile; t += gridDim.x) {
+        const i64 r0 = t * TG_ROWS;
+        const int nr = (int)((rows - r0) < (i64)TG_ROWS ? (rows - r0) : (i64)TG_ROWS);
+        const double* src = Y + r0 * m;               // nr * m consecutive doubles
+        __syncthreads();                              // the previous tile has been read (first round: the zero fill is done)
+        for (int e = threadIdx.x; e < TG_ROWS * m; e += 256) {
+            const int r = e / m, cc = e - r * m;
+            tile[r * 64 + cc] = r < nr ? src[e] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int r = 0; r < TG_ROWS; ++r) {
+            double a[4], b[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { a[i] = tile[r * 64 + tb + 16 * i]; b[i] = tile[r * 64 + ta + 16 * i]; }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s[i][j] = fma(a[i], b[j], s[i][j]);
+        }
+    }
+    double* P = part + (i64)blockIdx.x * 4096;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int a = tb + 16 * i, b = ta + 16 * j;
+            if (a <= b && b < m) P[a * 64 + b] = s[i][j];
+        }
+}
+
+// G (m x m, row-major) = the partial Gram matrices added in workgroup order; both halves written from the one sum (as k_gram does)
+__global__ __launch_bounds__(256) void k_tall_gram_sum(const double* __restrict__ part, int npart, int m, double* __restrict__ G) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= m * m) return;
+    const int a = e / m, b = e - a * m;
+    if (a > b) return;
+    const double s = ordered_sum<8>(part + a * 64 + b, 4096, 0, npart, 1);
+    G[a * m + b] = s;
+    G[b * m + a] = s;
+}
+
+// Y (rows x m, row-major) <- Y L^-T for a lower-triangular L, row by row: z L^T = y by forward substitution.  A wave holds
+// TS_ROWS rows, lane = column: a row is m consecutive doubles, so its load and its store are one contiguous run per wave
+// instruction, and TS_ROWS consecutive rows one run of TS_ROWS * m doubles.  Step j broadcasts z_j = v_j / L_jj from lane j
+// (readlane) and every lane i > j subtracts L_ij z_j.  Lp is L as the host packed it for this access: Lp[j * 64 + i] = L_ij for
+// j < i < m and 0 elsewhere (column j of the strictly lower part is one contiguous LDS read, and the lanes i <= j, whose entry is
+// final or not begun, need no predicate), then Lp[4096 + i] = 1 / L_ii (0 for i >= m).  The quotient is a product with that
+// reciprocal: an f64 division per step and row would be most of the kernel, and the Cholesky-QR passes that follow repair more
+// than the one rounding it adds.
+constexpr int TS_ROWS = 4;
+__global__ __launch_bounds__(256) void k_tall_lsolve(double* __restrict__ Y, i64 rows, int m, const double* __restrict__ Lp) {
+    __shared__ double Lsh[64 * 64 + 64];
+    for (int e = threadIdx.x; e < 64 * 64 + 64; e += 256) Lsh[e] = Lp[e];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double* invd = Lsh + 4096;
+    const double inv_i = invd[lane];
+    const i64 ngroup = (rows + TS_ROWS - 1) / TS_ROWS;
+    for (i64 g = (i64)blockIdx.x * 4 + wave; g < ngroup; g += (i64)gridDim.x * 4) {
+        const i64 r0 = g * TS_ROWS;
+        double v[TS_ROWS];
+#pragma unroll
+        for (int u = 0; u < TS_ROWS; ++u) v[u] = (lane < m && r0 + u < rows) ? Y[(r0 + u) * m + lane] : 0.0;
+        for (int j = 0; j < m; ++j) {
+            const double l = Lsh[j * 64 + lane], dj = invd[j];
+#pragma unroll
+            for (int u = 0; u < TS_ROWS; ++u) v[u] = fma(-l, lane_get(v[u], j) * dj, v[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < TS_ROWS; ++u)
+            if (lane < m && r0 + u < rows) Y[(r0 + u) * m + lane] = v[u] * inv_i;
+    }
+}
+
 // out[t] = sum_{b < nb} part[t * stride + b], fixed order, one workgroup per t
 __global__ __launch_bounds__(256) void k_rows_sum(const double* __restrict__ part, int nb, int stride, double* __restrict__ out) {
     __shared__ double scratch[40];

@@ -480,6 +480,21 @@ class RRIEngine(object):
                                                Q.ctypes.data_as(C.POINTER(C.c_double)), B.ctypes.data_as(C.POINTER(C.c_double))))
         return Q, B
 
+    def sparse_range_finder(self, Q0, n_iter, transpose=False):
+        """range_finder on a handle that keeps X sparse (rri_sparse_range_finder): the CSR X of sparse_x=True, the observed values
+        of weighted='sparse'.  Same arguments, same shapes, same Cholesky-QR; the panels stay on the device as tall row-major
+        matrices, the layout of the sparse products.  m <= 64; ValueError on a dense handle and before an upload."""
+        Q0 = np.ascontiguousarray(Q0, dtype=np.float64)
+        rows, cols = (self.d, self.n) if transpose else (self.n, self.d)
+        if Q0.ndim != 2 or Q0.shape[0] != cols:
+            raise ValueError('test matrix must be (%d, m)' % cols)
+        m = Q0.shape[1]
+        Q, B = np.empty((rows, m)), np.empty((m, cols))
+        self._check(self._lib.rri_sparse_range_finder(self._h, Q0.ctypes.data_as(C.POINTER(C.c_double)), m, int(n_iter),
+                                                      int(bool(transpose)), Q.ctypes.data_as(C.POINTER(C.c_double)),
+                                                      B.ctypes.data_as(C.POINTER(C.c_double))))
+        return Q, B
+
     # ---- preprocessing of the resident X (matrixops.py:124-179) ---------------------------
     def column_positive_counts(self):
         """df[j] = #{i: X[i, j] > 0}"""

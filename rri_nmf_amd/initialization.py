@@ -22,9 +22,9 @@ def randomized_svd_device(engine, n_components, random_state=None, n_oversamples
 
     Follows sklearn step by step so that it returns the same U, S, V up to rounding: the random test matrix is
     drawn from the same numpy RandomState, the matrix is transposed when n < d, signs are fixed as svd_flip does.
-    resident (round 4, the default on dense handles): the panels of the power iteration stay on the device and are
-    normalised there (Cholesky-QR, rri_range_finder); False: every product returns to the host and scipy normalises
-    (LU, then QR) exactly as scikit-learn does.
+    resident (round 4, the default): the panels of the power iteration stay on the device and are normalised there
+    (Cholesky-QR; rri_range_finder on dense handles, rri_sparse_range_finder on those that keep X sparse; k + 10 <= 64);
+    False: every product returns to the host and scipy normalises (LU, then QR) exactly as scikit-learn does.
     """
     from scipy import linalg
     n, d = engine.n, engine.d
@@ -41,6 +41,10 @@ def randomized_svd_device(engine, n_components, random_state=None, n_oversamples
         # host for LU / QR after every product: another basis of the same range, the same U, S, V up to rounding -- and
         # 0.7 s less at 100000 x 10000 (profiles/r04_e2e_*)
         Q, B = engine.range_finder(Q, n_iter, transpose=transpose)
+    elif resident and m <= 64 and getattr(engine, 'sparse', False) and hasattr(engine, 'sparse_range_finder'):
+        # an X kept sparse (the CSR X, the observed values of a pattern-only handle): the same range finder on the layout of the
+        # sparse products (rri_sparse_range_finder).  Its 16 products used to take the branch below, every panel through the host
+        Q, B = engine.sparse_range_finder(Q, n_iter, transpose=transpose)
     else:
         lu = lambda Y: linalg.lu(Y, permute_l=True, check_finite=False)[0]
         normalize_q = lu if n_iter > 2 else (lambda Y: Y)

@@ -3,7 +3,7 @@ NMF_TM_Estimator(handle_tfidf=True, handle_normalization=True, nmf_kwargs={'spar
 keep_resident=True saves per one_iter(X_csr) call.
 
     python tools/e2e_sparse_tfidf_probe.py [--density 0.002 0.01 0.05] [--reps 5] [--calls 20] [--label NAME] [--out FILE.jsonl]
-                                           [--tree DIR]
+                                           [--tree DIR] [--routes default products]
 
 100000 x 10000 Zipf counts (tools/sparse_x_probe.zipf_counts), k = 50, fp32 storage, 30 sweeps per fit.  One JSON line per
 density: medians over --reps fits of the wall time and of its parts --
@@ -11,6 +11,11 @@ density: medians over --reps fits of the wall time and of its parts --
     device_prep RRIEngine.preprocess                                     start     the starting W, T (NNDSVD)
     sweeps      rri_sweep / rri_sweep_until / rri_objective              other     the rest of the call
 -- and the median of --calls one_iter calls with and without keep_resident, in the same process (--calls 0: fits only).
+The start is also given alone (`start_s`: every fit's value, median, min, max) with the range finder of its randomized SVD as a
+line of its own (`range_finder_s`: RRIEngine.sparse_range_finder, or the 16 products X_times / Xt_times where the start takes
+them one by one; host LU / QR between them is not in it).  --routes default products fits each density under both starts in
+turn, rep by rep (one line per route): `products` hides sparse_range_finder from the engine, which is the start as it was before
+that call existed -- the two sides of the comparison on one device in one process.
 --tree DIR imports rri_nmf_amd from another checkout (built there), to put two commits side by side on one device; --label
 names the line."""
 import argparse
@@ -71,8 +76,61 @@ def instrument(engine, nmf, clock):
         setattr(E, name, clock.wrap(getattr(E, name), 'sweeps'))
 
 
+class Inner(object):
+    """wall time inside the range finder of the start (counted within 'start', not beside it)"""
+
+    def __init__(self, E):
+        self.t, self.depth = 0.0, 0
+        for name in ('sparse_range_finder', 'X_times', 'Xt_times'):
+            if hasattr(E, name):
+                setattr(E, name, self.wrap(getattr(E, name)))
+        self.E, self.method = E, getattr(E, 'sparse_range_finder', None)
+
+    def wrap(self, fn):
+        def timed(*a, **kw):
+            if self.depth:                      # X_times calls itself chunk by chunk beyond 64 columns
+                return fn(*a, **kw)
+            self.depth += 1
+            t0 = time.perf_counter()
+            try:
+                return fn(*a, **kw)
+            finally:
+                self.t += time.perf_counter() - t0
+                self.depth -= 1
+        return timed
+
+    def route(self, name):
+        if self.method is None:
+            return
+        if name == 'products' and hasattr(self.E, 'sparse_range_finder'):
+            del self.E.sparse_range_finder
+        elif name == 'default':
+            self.E.sparse_range_finder = self.method
+
+
+def spread(v):
+    return {'median': median(v), 'min': float(min(v)), 'max': float(max(v)), 'all': [float(x) for x in v]}
+
+
 def median(v):
     return float(np.median(np.asarray(v, dtype=np.float64)))
+
+
+def fit_record(r):
+    walls, parts = r['walls'], r['parts']
+    split = {p: median([q[p] for q in parts]) for p in PARTS}
+    split['other'] = median([w - sum(q.values()) for w, q in zip(walls, parts)])
+    return {'wall_s_median': median(walls), 'wall_s': walls, 'split_s_median': split, 'sweeps': r['sweeps'],
+            'start_s': spread([q['start'] for q in parts]), 'range_finder_s': spread(r['rf']),
+            'route': 'host' if split['host_prep'] > 0 else 'device'}
+
+
+def emit(args, rec):
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, 'a') as f:
+            f.write(line + '\n')
 
 
 def main():
@@ -83,10 +141,12 @@ def main():
     ap.add_argument('--label', default='this checkout')
     ap.add_argument('--out', default=None)
     ap.add_argument('--tree', default=os.path.dirname(HERE))
+    ap.add_argument('--routes', nargs='+', default=['default'], choices=['default', 'products'])
     args = ap.parse_args()
     engine, nmf, si = load_package(args.tree)
     clock = Clock()
     instrument(engine, nmf, clock)
+    inner = Inner(engine.RRIEngine)
     n, d, k = 100000, 10000, 50
     kw = dict(handle_tfidf=True, handle_normalization=True, random_state=0,
               nmf_kwargs={'sparse_X': True, 'dtype': np.float32, 'eps_stop': -1})
@@ -94,20 +154,29 @@ def main():
         X = zipf_counts(n, d, dens, seed=int(dens * 1e4))
         rec = {'tool': 'e2e_sparse_tfidf_probe', 'label': args.label, 'shape': [n, d], 'k': k, 'density_asked': dens,
                'nnz': int(X.nnz), 'density': X.nnz / float(n * d), 'empty_rows': int(np.sum(np.diff(X.indptr) == 0))}
-        si.NMF_TM_Estimator(n, d, k, max_iter=2, **kw).fit(X)                       # warm-up: library, allocator, sklearn
-        walls, parts, sweeps = [], [], []
+        for route in args.routes:                                                    # warm-up: library, allocator, sklearn
+            inner.route(route)
+            si.NMF_TM_Estimator(n, d, k, max_iter=2, **kw).fit(X)
+        runs = {route: {'walls': [], 'parts': [], 'sweeps': [], 'rf': []} for route in args.routes}
         for _ in range(args.reps):
-            est = si.NMF_TM_Estimator(n, d, k, max_iter=30, **kw)
-            clock.reset()
-            t0 = time.perf_counter()
-            est.fit(X)
-            walls.append(time.perf_counter() - t0)
-            parts.append(dict(clock.t))
-            sweeps.append(len(est.nmf_outputs['iter_cputime']))
-        split = {p: median([q[p] for q in parts]) for p in PARTS}
-        split['other'] = median([w - sum(q.values()) for w, q in zip(walls, parts)])
-        rec['fit'] = {'wall_s_median': median(walls), 'wall_s': walls, 'split_s_median': split, 'sweeps': sweeps,
-                      'route': 'host' if split['host_prep'] > 0 else 'device'}
+            for route in args.routes:                                                # the routes in turn, rep by rep
+                inner.route(route)
+                est = si.NMF_TM_Estimator(n, d, k, max_iter=30, **kw)
+                clock.reset()
+                inner.t = 0.0
+                t0 = time.perf_counter()
+                est.fit(X)
+                r = runs[route]
+                r['walls'].append(time.perf_counter() - t0)
+                r['parts'].append(dict(clock.t))
+                r['rf'].append(inner.t)
+                r['sweeps'].append(len(est.nmf_outputs['iter_cputime']))
+        base = dict(rec)
+        for route in args.routes[1:]:
+            emit(args, dict(base, route_of_start=route, fit=fit_record(runs[route])))
+        inner.route(args.routes[0])
+        rec['route_of_start'] = args.routes[0]
+        rec['fit'] = fit_record(runs[args.routes[0]])
         for keep in ((True, False) if args.calls > 0 else ()):
             est = si.NMF_TM_Estimator(n, d, k, max_iter=2, keep_resident=keep, **kw).fit(X)
             calls = []
@@ -121,11 +190,7 @@ def main():
                 'handle_reuses': int(holder.reuses) if holder is not None else 0}
             if keep:
                 est.release()
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if args.out:
-            with open(args.out, 'a') as f:
-                f.write(line + '\n')
+        emit(args, rec)
 
 
 if __name__ == '__main__':
