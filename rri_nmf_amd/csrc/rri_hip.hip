@@ -303,6 +303,59 @@ struct rri_ctx {
 // the matrix back always do): ONE predicate for the launch sites and for rri_layout_info
 static inline bool ro_pass_interleaved(const rri_ctx* c) { return c->npanels * c->nrb <= 1024; }
 
+// ---- what a handle keeps between steps and calls, and what each piece was computed from ------------------------------------
+//                                              X   M   W   T   scratch  penalties
+//   carry_valid / carry_topic                  x   x   x   x      x                 one topic's partial sums in Zpart / Gpart (Z2part)
+//   resid_valid                                x   x   x   x                        E (pattern-only: sp_e and its copies) = [M .*] (X - W T)
+//   xy_run / xy_valid                          x       x   x                        XYpart: <w_t, X t_t> of the topics of one sweep, in order
+//   obj_track_valid                            x       x   x                x       DevState.obj_track of the last persistent launch
+//   q_valid                                    x           x                        Qt = X T^T
+//   gfull_valid                                            x                        Gfull = T T^T
+//   x_sq_valid                                 x                                    x_sq = ||X||^2
+// (scratch: Zpart / Gpart / red, which other entry points borrow.)  resid_fresh, dt_pending and dw_pending qualify E and are
+// read only while resid_valid holds; every rebuild resets them (resid_rebuilt).  pending_wcheck is no cache but a verdict still
+// owed on the column sums in Gpart: it is taken before Gpart is overwritten (flush_wcheck) and dropped only with the run it
+// belongs to (CH_ENDED).  A step that PRODUCES one of these sets it itself, next to its launch; what makes one stale is said
+// here, by what changed, and nowhere else.
+// Coarser than the table on purpose: any change from outside the schedule drops the first four rows together, and a new X drops
+// Gfull as well.  A narrower rule would move where an fp32 residual is rebuilt, and with it the low bits of a run.
+enum : unsigned {
+    CH_X = 1u << 0,         // X replaced or rewritten in place
+    CH_M = 1u << 1,         // the mask or the observed pattern replaced
+    CH_W = 1u << 2,         // W written from outside the schedule
+    CH_T = 1u << 3,         // T written from outside the schedule (the row of a reset included)
+    CH_SCRATCH = 1u << 4,   // the scratch arrays were borrowed or rebound, or their sums belong to another form or communicator
+    CH_PENALTY = 1u << 5,   // reg_w_* / reg_t_* changed
+    CH_ENDED = 1u << 6,     // the run in progress is over (halt, failed collective, factors replaced, last check taken on the device):
+                            // its sums are those of an unknown step and no column verdict is owed
+    CH_T_ROW = 1u << 7,     // a step of the schedule rewrote one T row (xy_run stays: the W half of the same topic continues it)
+    CH_W_COL = 1u << 8,     // ... one or all W columns (the step leaves its own carry, cross terms and column verdict)
+    CH_E_FOLLOWS = 1u << 9  // with the two above: the step keeps E in step through dt_pending / dw_pending
+};
+static void changed(rri_ctx* c, unsigned what) {
+    if (what & (CH_X | CH_M | CH_W | CH_T | CH_SCRATCH | CH_ENDED)) {
+        c->carry_valid = false;
+        c->carry_topic = -1;
+        c->resid_valid = false;
+        c->xy_run = -1;
+        c->xy_valid = false;
+        c->obj_track_valid = false;
+    }
+    if (what & CH_T_ROW) { c->carry_valid = false; c->xy_valid = false; }
+    if ((what & (CH_T_ROW | CH_W_COL)) && !(what & CH_E_FOLLOWS)) c->resid_valid = false;
+    if (what & (CH_T_ROW | CH_W_COL | CH_PENALTY)) c->obj_track_valid = false;
+    if (what & (CH_X | CH_T | CH_T_ROW)) { c->q_valid = false; c->gfull_valid = false; }
+    if (what & CH_X) c->x_sq_valid = false;
+    if (what & CH_ENDED) c->pending_wcheck = false;
+}
+// E has just been rebuilt from the current W and T: nothing is pending on it
+static void resid_rebuilt(rri_ctx* c) {
+    c->resid_valid = true;
+    c->resid_fresh = true;
+    c->dt_pending = false;
+    c->dw_pending = false;
+}
+
 
 namespace {
 
@@ -1032,7 +1085,6 @@ struct LK {  // float64-only kernels
         if (t == 0) { c->xy_run = 1; c->xy_rows = rows; }
         else c->xy_run = (c->xy_run == t && c->xy_rows == rows) ? t + 1 : -1;
         c->xy_valid = c->xy_run == c->k;
-        c->obj_track_valid = false;
     }
     template <bool UPDATE, bool CARRY>
     static void wcol(rri_ctx* c, int t, int tn, int sweep) {
@@ -1234,15 +1286,6 @@ rri_status to_host(rri_ctx* c, const void* dev, i64 ldd, void* host, i64 ld, int
     return RRI_OK;
 }
 
-void invalidate(rri_ctx* c) {
-    c->carry_valid = false;
-    c->carry_topic = -1;
-    c->resid_valid = false;
-    c->xy_run = -1;
-    c->xy_valid = false;
-    c->obj_track_valid = false;
-}
-
 // ---- the topic-step scheduler ------------------------------------------------------------------
 // The column verdict of _check_reset_W / the assert of nmf.py:471-476 from the partial sums in Gpart, taken NOW
 // (where no T-row step follows that would carry it).  Row-sharded: the column sum is global, so the local share is
@@ -1265,14 +1308,15 @@ void wcheck_now(rri_ctx* c, int tprev, int sweep, int pos) {
     hipLaunchKernelGGL(k_wcheck_tail, dim3(1), dim3(64), 0, c->stream, (const double*)c->ctail, tprev, sweep, pos,
                        kparams(c), c->st);
 }
+// the pending column check reads Gpart: resolve it before a step that overwrites Gpart, or where no T-row step follows to carry it
+void flush_wcheck(rri_ctx* c, int sweep, int pos) {
+    if (c->pending_wcheck) wcheck_now(c, c->pending_wcheck_topic, sweep, pos);
+    c->pending_wcheck = false;
+}
 
 // carry := Zpart/Gpart hold the partial sums of topic `carry_topic`.
 void enqueue_prologue(rri_ctx* c, int t, int sweep) {
-    // the pending W-column check reads Gpart, which the prologue overwrites: resolve it first
-    if (c->pending_wcheck) {
-        wcheck_now(c, c->pending_wcheck_topic, sweep, t);
-        c->pending_wcheck = false;
-    }
+    flush_wcheck(c, sweep, t);
     LK::wcol<false, true>(c, t, t, sweep);                             // Gram row of w_t
     DISPATCH_RO(c, (L::template pass<false, true>(c, t, t)));         // w_t^T X
     c->carry_valid = true;
@@ -1296,11 +1340,7 @@ void enqueue_T_half(rri_ctx* c, int sweep, int t, bool standalone) {
         c->pending_wcheck = false;
         if (c->prm.fix_W && no_regs(c)) LK::scale_wcol(c, t);
     }
-    c->carry_valid = false;
-    c->resid_valid = false;
-    c->q_valid = false; c->gfull_valid = false;   // T changed
-    c->xy_valid = false;  // a T row changed: complete again after the W half of topic k-1
-    c->obj_track_valid = false;
+    changed(c, CH_T_ROW);
 }
 
 void enqueue_W_half(rri_ctx* c, int sweep, int t) {
@@ -1345,7 +1385,7 @@ void enqueue_W_half(rri_ctx* c, int sweep, int t) {
         wcheck_now(c, t, ns, np);
         c->carry_valid = false;
     }
-    c->resid_valid = false;
+    changed(c, CH_W_COL);
 }
 
 // ---- explicit-residual schedule (RRI_UNWEIGHTED_RESIDUAL; SURVEY 8a "explicit-residual variant") --------------
@@ -1360,19 +1400,13 @@ void enqueue_W_half(rri_ctx* c, int sweep, int t) {
 // the correction coefficients for topic `carry_topic`.
 void r_refresh(rri_ctx* c) {
     DISPATCH(c, L::resid(c, false, true, nullptr, nullptr));   // R = X - W T
-    c->resid_valid = true;
-    c->resid_fresh = true;
-    c->dw_pending = false;     // the rebuilt R contains the current W and T
-    c->dt_pending = false;
+    resid_rebuilt(c);
 }
 
 void enqueue_rT_half(rri_ctx* c, int sweep, int t, bool standalone) {
     if (!c->resid_valid) r_refresh(c);
     if (!c->carry_valid || c->carry_topic != t) {
-        if (c->pending_wcheck) {            // reads Gpart, which the prologue overwrites
-            wcheck_now(c, c->pending_wcheck_topic, sweep, t);
-            c->pending_wcheck = false;
-        }
+        flush_wcheck(c, sweep, t);
         if (c->dw_pending) r_refresh(c);    // no pass to fold the pending column change into: rebuild instead
         LK::wcol_resid<false>(c, t, t, sweep);             // ||w_t||^2
         DISPATCH(c, L::rpass_colsums(c, t));               // R^T w_t
@@ -1393,11 +1427,9 @@ void enqueue_rT_half(rri_ctx* c, int sweep, int t, bool standalone) {
         }
         c->pending_wcheck = false;
     }
-    c->carry_valid = false;
+    changed(c, CH_T_ROW | CH_E_FOLLOWS);
     c->resid_fresh = false;
     c->dt_pending = true;     // told holds the previous row: R lacks w_t (T[t,:] - told)^T
-    c->xy_valid = false;
-    c->obj_track_valid = false;
 }
 
 void enqueue_rW_half(rri_ctx* c, int sweep, int t) {
@@ -1420,6 +1452,7 @@ void enqueue_rW_half(rri_ctx* c, int sweep, int t) {
         L::rank_update(c, c->E, c->LD, u, trow, c->W + (i64)tn * c->ldw, job);
     });
     LK::wcol_resid<true>(c, t, tn, sweep);
+    changed(c, CH_W_COL | CH_E_FOLLOWS);
     c->dw_pending = true;
     c->dw_topic = t;
     c->dt_pending = false;
@@ -1434,10 +1467,7 @@ void enqueue_rW_half(rri_ctx* c, int sweep, int t) {
 // carry := Zpart / Z2part hold the column sums (a, nw) of topic `carry_topic` over the CURRENT E.
 void w_refresh(rri_ctx* c) {
     DISPATCH(c, L::resid(c, true, true, nullptr, nullptr));   // E = M .* (X - W T)
-    c->resid_valid = true;
-    c->resid_fresh = true;
-    c->dt_pending = false;     // the rebuilt E contains the current T
-    c->dw_pending = false;     // ... and W (pattern-only handles: the row copy's pending column change)
+    resid_rebuilt(c);          // (pattern-only handles: the row copy's pending column change is in it too)
     c->carry_valid = false;
 }
 
@@ -1502,12 +1532,12 @@ void enqueue_wT_solve(rri_ctx* c, int sweep, int t, bool fused = false) {
                            (const double*)c->tpart, (const i64*)c->tpart_idx, fused ? nb_small : c->ntb, c->dtv, scale_w, sweep,
                            kparams(c), c->st);
     }
-    c->carry_valid = false;
+    // a column change still pending on the row copy and no W half to fold it: rebuild
+    const bool rebuild = c->prm.fix_W && c->dw_pending;
+    changed(c, rebuild ? CH_T_ROW : CH_T_ROW | CH_E_FOLLOWS);
     c->resid_fresh = false;
-    c->dt_pending = true;
-    if (c->prm.fix_W && c->dw_pending) {   // a column change still pending on the row copy and no W half to fold it: rebuild
-        c->resid_valid = false;
-        c->dt_pending = false;
+    c->dt_pending = !rebuild;
+    if (rebuild) {
         if (no_regs(c)) LK::scale_wcol(c, t);
     } else if (c->prm.fix_W) {   // no W half follows: fold dt into E now, then rescale the kept column (nmf.py:450-452)
         DISPATCH(c, (L::template wpass<false, false, false, true>(c, nullptr, nullptr, wt_t, c->dtv, nullptr, nullptr)));
@@ -1588,6 +1618,7 @@ void enqueue_wW_half(rri_ctx* c, int sweep, int t, bool defer_check = false) {
         if (carry_next) DISPATCH(c, (L::template sp_blk<true, true, true>(c, 1, c->wold, c->dwv, wn, b1, trow, c->Zpart, c->Z2part, c->LD)));
         else DISPATCH(c, (L::template sp_blk<false, true, true>(c, 1, c->wold, c->dwv, wn, b1, trow, c->Zpart, c->Z2part, c->LD)));
     }
+    changed(c, CH_W_COL | CH_E_FOLLOWS);
     c->dw_pending = true;     // dwv x T[t,:]: folded in by the pass of the next step (dense: into E, under the mask; pattern-only: the row copy)
     c->dw_topic = t;
     int ns = sweep, np = t + 1;
@@ -1717,10 +1748,7 @@ bool enqueue_wsweep(rri_ctx* c, int sweep, int t0) {
         if (hipFuncSetAttribute((const void*)k_wsweep_rows, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess) { (void)hipGetLastError(); return false; }
         attr_set[dv] = true;
     }
-    if (c->pending_wcheck) {     // (a column check left by steps before T was fixed)
-        wcheck_now(c, c->pending_wcheck_topic, sweep, t0);
-        c->pending_wcheck = false;
-    }
+    flush_wcheck(c, sweep, t0);     // (a column check left by steps before T was fixed)
     if (!c->q_valid) {           // X T^T: once per T, reused by every topic and every sweep
         DISPATCH_RO(c, L::xtt(c));
         c->q_valid = true;
@@ -1750,7 +1778,7 @@ bool enqueue_wsweep(rri_ctx* c, int sweep, int t0) {
     for (int t = t0; t < k; ++t) LK::note_xy(c, t, c->nwb * WCOL_TILES);
     c->skip_row_finish = false;
     c->carry_valid = false;
-    c->resid_valid = false;
+    changed(c, CH_W_COL);
     return true;
 }
 
@@ -1999,23 +2027,13 @@ bool enqueue_onchip(rri_ctx* c, Cursor cur) {
     // what the launch-per-phase schedule would find after these sweeps: no carried sums, nothing pending (the kernel
     // ran the last column check itself); the objective's cross terms are complete when the last sweep ran from topic 0
     const bool whole_last = c->run_total - 1 > cur.sweep || (cur.topic == 0 && cur.phase == 0);
-    c->carry_valid = false; c->carry_topic = -1;
-    c->pending_wcheck = false;
-    c->resid_valid = false; c->q_valid = false; c->gfull_valid = false;
+    changed(c, CH_W | CH_T | CH_ENDED);
     c->skip_row_finish = false;
     c->xy_run = whole_last ? k : -1;
     c->xy_rows = g.G;
     c->xy_valid = whole_last;
-    c->obj_track_valid = false;
     c->obj_track_pending = a.track != 0;
     return true;
-}
-
-void enqueue_final_check(rri_ctx* c, int sweep_arg) {
-    if (c->pending_wcheck) {  // last column of the call: report it in this call
-        wcheck_now(c, c->pending_wcheck_topic, sweep_arg, 0);
-        c->pending_wcheck = false;
-    }
 }
 
 void enqueue_from(rri_ctx* c, Cursor cur) {
@@ -2024,7 +2042,7 @@ void enqueue_from(rri_ctx* c, Cursor cur) {
     // the sweep it is in and the caller decides
     if (c->until.active && cur.sweep < c->run_total) c->run_total = cur.sweep + 1;
     enqueue_range(c, cur, c->run_total);
-    enqueue_final_check(c, c->run_total);
+    flush_wcheck(c, c->run_total, 0);      // last column of the call: report it in this call
 }
 
 rri_status read_state(rri_ctx* c, DevState* out) {
@@ -2033,8 +2051,7 @@ rri_status read_state(rri_ctx* c, DevState* out) {
     if (c->comm_status != RRI_OK) {   // a collective of the sequence just run failed: its text is in c->err
         const rri_status r = c->comm_status;
         c->comm_status = RRI_OK;
-        invalidate(c);
-        c->pending_wcheck = false;
+        changed(c, CH_ENDED);
         return r;
     }
     return RRI_OK;
@@ -2046,8 +2063,7 @@ rri_status status_from_halt(rri_ctx* c, const DevState& s, int32_t* sweeps_done)
         if (sweeps_done) *sweeps_done = c->run_total;
         return RRI_OK;
     }
-    invalidate(c);
-    c->pending_wcheck = false;
+    changed(c, CH_ENDED);
     if (s.halt == HALT_EVENT_STOP) {      // rri_sweep_until: the stop rule held after sweep halt_sweep - 1; nothing of the next one is stored
         c->paused = false;
         if (sweeps_done) *sweeps_done = s.halt_sweep;
@@ -2392,7 +2408,7 @@ rri_status rri_upload_X(rri_ctx* c, const void* host, int64_t ld, int32_t host_d
     c->store_err[0] = c->store_err[1] = 0.0;
     rri_status s = to_device(c, host, ld, host_dtype, c->X, c->ldx, c->n, c->d, c->dtype);
     // (a float16 upload that fails -- the range check -- has already overwritten the store: the handle then has no X)
-    if (s == RRI_OK || c->dtype == RRI_F16) { c->have_X = s == RRI_OK; invalidate(c); c->q_valid = false; c->gfull_valid = false; c->x_sq_valid = false; }
+    if (s == RRI_OK || c->dtype == RRI_F16) { c->have_X = s == RRI_OK; changed(c, CH_X); }
     return s;
 }
 
@@ -2412,7 +2428,7 @@ rri_status rri_upload_mask(rri_ctx* c, const void* host, int64_t ld, int32_t hos
     rri_status s = to_device(c, host, ld, host_dtype, c->M, c->ldm, c->n, c->d, c->dtype);
     if (s == RRI_OK) {
         c->have_M = true;
-        invalidate(c);
+        changed(c, CH_M);
         DISPATCH(c, s = L::pack_mask_if_binary(c));
         if (s != RRI_OK) return fail(c, s, "packing the mask failed");
         if (c->Mbits && c->own_M) { (void)hipFree(c->M); c->M = nullptr; c->own_M = false; }   // bits replace it
@@ -2479,9 +2495,7 @@ rri_status rri_upload_X_csr(rri_ctx* c, const int64_t* indptr, const int32_t* in
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_X = true;
-    invalidate(c);
-    c->q_valid = false; c->gfull_valid = false;
-    c->x_sq_valid = false;
+    changed(c, CH_X);
     return RRI_OK;
 }
 
@@ -2543,9 +2557,7 @@ static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int
     if (nw1 > 0) HIPCHK(c, hipMemcpyAsync(c->spx_work + nw0, c->sp[1].work, (size_t)nw1 * sizeof(SpWork), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_X = true;
-    invalidate(c);
-    c->q_valid = false; c->gfull_valid = false;
-    c->x_sq_valid = false;
+    changed(c, CH_X);
     return RRI_OK;
 }
 
@@ -2575,7 +2587,7 @@ rri_status rri_upload_mask_csr_pattern(rri_ctx* c, const int64_t* indptr, const 
     else hipLaunchKernelGGL((k_csr_pattern_bits<double>), dim3(nb), dim3(256), 0, c->stream, dv.indptr, dv.indices, (const double*)dv.data, c->n, c->Mbits, c->ldb);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_M = true;
-    invalidate(c);
+    changed(c, CH_M);
     return RRI_OK;
 }
 
@@ -2724,7 +2736,7 @@ rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int3
     HIPCHK(c, hipMalloc(&c->sp_e, (size_t)std::max<i64>(nnz, 1) * c->es));
     c->have_X = true;
     c->have_M = true;
-    invalidate(c);
+    changed(c, CH_X | CH_M);
     return RRI_OK;
 }
 
@@ -2750,9 +2762,7 @@ rri_status rri_bind_X_device(rri_ctx* c, const void* dev, int64_t ld) {
     c->ldx = ld;
     c->store_err[0] = c->store_err[1] = 0.0;   // bound memory is taken as it is: nothing was rounded here
     c->have_X = true;
-    invalidate(c);
-    c->q_valid = false; c->gfull_valid = false;
-    c->x_sq_valid = false;
+    changed(c, CH_X);
     return RRI_OK;
 }
 
@@ -2771,7 +2781,7 @@ rri_status rri_bind_mask_device(rri_ctx* c, const void* dev, int64_t ld) {
     c->own_M = false;
     c->ldm = ld;
     c->have_M = true;
-    invalidate(c);
+    changed(c, CH_M);
     rri_status ps = RRI_OK;
     DISPATCH(c, ps = L::pack_mask_if_binary(c));
     if (ps != RRI_OK) return fail(c, ps, "packing the mask failed");
@@ -2782,14 +2792,14 @@ rri_status rri_set_W(rri_ctx* c, const void* host, int64_t ld, int32_t host_dtyp
     CHECK_CTX(c);
     HIPCHK(c, hipSetDevice(c->device));
     rri_status s = to_device(c, host, ld, host_dtype, c->W, c->ldw, c->n, c->k, RRI_F64, true);
-    if (s == RRI_OK) { c->have_W = true; invalidate(c); c->pending_wcheck = false; }
+    if (s == RRI_OK) { c->have_W = true; changed(c, CH_W | CH_ENDED); }
     return s;
 }
 rri_status rri_set_T(rri_ctx* c, const void* host, int64_t ld, int32_t host_dtype) {
     CHECK_CTX(c);
     HIPCHK(c, hipSetDevice(c->device));
     rri_status s = to_device(c, host, ld, host_dtype, c->T, c->LD, c->k, c->d, RRI_F64);
-    if (s == RRI_OK) { c->have_T = true; invalidate(c); c->q_valid = false; c->gfull_valid = false; }
+    if (s == RRI_OK) { c->have_T = true; changed(c, CH_T); }
     return s;
 }
 rri_status rri_get_W(rri_ctx* c, void* host, int64_t ld, int32_t host_dtype) {
@@ -2814,15 +2824,13 @@ rri_status rri_set_params(rri_ctx* c, const rri_params* p) {
     // the objective a persistent sweep left behind has the penalties of THAT launch folded in
     if (c->have_params && (c->prm.reg_w_l1 != p->reg_w_l1 || c->prm.reg_w_l2 != p->reg_w_l2 || c->prm.reg_t_l1 != p->reg_t_l1 ||
                            c->prm.reg_t_l2 != p->reg_t_l2))
-        c->obj_track_valid = false;
+        changed(c, CH_PENALTY);
     c->prm = *p;
     c->have_params = true;
     if (c->explicit_resid && form_before != resid_sched(c)) {
         // the call that follows steps in the other form: the sums carried between calls belong to the form that left them,
         // and a residual the Gram form does not maintain is stale
-        invalidate(c);
-        c->dw_pending = false;
-        c->dt_pending = false;
+        changed(c, CH_SCRATCH);
     }
     return RRI_OK;
 }
@@ -2856,18 +2864,17 @@ static rri_status run_and_collect(rri_ctx* c, Cursor from, int32_t* sweeps_done)
         // A launch that gave up IN the run (not at its entry) has left more than W and T behind: objective slots of the sweeps it
         // finished (rri_sweep_until's history: "NaN = no value from the kernel" must hold for the sweeps rerun below) and
         // DevState.obj_track.  The history goes back to "not written"; obj_track is never read for this call (onchip_in_flight is
-        // off, invalidate() drops obj_track_valid), XYpart is rewritten by the rerun's own W halves.
+        // off, CH_ENDED drops obj_track_valid), XYpart is rewritten by the rerun's own W halves.
         if (c->objhist && c->until.active)
             HIPCHK(c, hipMemsetAsync(c->objhist, 0xFF, (size_t)std::min(std::max(c->until.n, 0), ONCHIP_UNTIL_CAP) * 8, c->stream));
         c->obj_track_pending = false;
-        invalidate(c);
-        c->pending_wcheck = false;
+        changed(c, CH_ENDED);
         c->skip_row_finish = c->onchip_saved_skip;
         r = clear_halt(c);
         if (r != RRI_OK) return r;
         if (c->until.active) c->run_total = std::min(c->run_total, from.sweep + 1);     // no stop rule on this schedule: one sweep, then the caller
         enqueue_range(c, from, c->run_total);
-        enqueue_final_check(c, c->run_total);
+        flush_wcheck(c, c->run_total, 0);
         le = hipGetLastError();
         if (le != hipSuccess) return fail(c, RRI_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(le));
         r = read_state(c, &s);
@@ -2953,12 +2960,14 @@ rri_status rri_pending_event(rri_ctx* c, rri_event* ev) {
     return RRI_OK;
 }
 
-static void event_resolved(rri_ctx* c) {
-    c->q_valid = false; c->gfull_valid = false;   // a reset rewrites T[t,:] even when T is otherwise fixed (nmf.py:808,814)
-    if (c->pending.kind == RRI_EVENT_RESET_T) c->skip_row_finish = true;
-    c->pending.kind = RRI_EVENT_NONE;
-    if (c->prm.resets_left > 0) c->prm.resets_left -= 1;
-    invalidate(c);
+// a reset rewrote T[t,:] and W[:,t] (T[t,:] even when T is otherwise fixed, nmf.py:808,814); in a paused run it resolves the event
+static void reset_applied(rri_ctx* c) {
+    if (c->paused && c->pending.kind != RRI_EVENT_NONE) {
+        if (c->pending.kind == RRI_EVENT_RESET_T) c->skip_row_finish = true;
+        c->pending.kind = RRI_EVENT_NONE;
+        if (c->prm.resets_left > 0) c->prm.resets_left -= 1;
+    }
+    changed(c, CH_W | CH_T);
 }
 
 rri_status rri_apply_reset_max_resid(rri_ctx* c, int32_t t, int64_t* row_chosen) {
@@ -2996,8 +3005,7 @@ rri_status rri_apply_reset_max_resid(rri_ctx* c, int32_t t, int64_t* row_chosen)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->comm_status != RRI_OK) { const rri_status r = c->comm_status; c->comm_status = RRI_OK; return r; }
         if (row_chosen) *row_chosen = (int64_t)cand[2 * win + 1];
-        if (c->paused && c->pending.kind != RRI_EVENT_NONE) event_resolved(c);
-        else invalidate(c);
+        reset_applied(c);
         return RRI_OK;
     }
     DISPATCH_RO(c, L::reset_row(c));
@@ -3006,8 +3014,7 @@ rri_status rri_apply_reset_max_resid(rri_ctx* c, int32_t t, int64_t* row_chosen)
     HIPCHK(c, hipMemcpyAsync(&mi, c->itmp, sizeof(i64), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (row_chosen) *row_chosen = mi;
-    if (c->paused && c->pending.kind != RRI_EVENT_NONE) event_resolved(c);
-    else invalidate(c);
+    reset_applied(c);
     return RRI_OK;
 }
 
@@ -3021,8 +3028,7 @@ rri_status rri_apply_reset_vectors(rri_ctx* c, int32_t t, const double* T_row, c
     if (W_col) HIPCHK(c, hipMemcpyAsync(c->resetW, W_col, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     LK::set_row_col(c, t, T_row ? c->resetT : nullptr, W_col ? c->resetW : nullptr);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->paused && c->pending.kind != RRI_EVENT_NONE) event_resolved(c);
-    else invalidate(c);
+    reset_applied(c);
     HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
     return RRI_OK;
 }
@@ -3068,10 +3074,7 @@ rri_status rri_update_W_col(rri_ctx* c, int32_t t) {
     c->skip_row_finish = true;   // a lone W half: the T-row checks belong to rri_update_T_row
     if (resid_sched(c)) enqueue_rW_half(c, 0, t);
     else enqueue_W_half(c, 0, t);
-    if (c->pending_wcheck) {
-        wcheck_now(c, c->pending_wcheck_topic, 1, 0);
-        c->pending_wcheck = false;
-    }
+    flush_wcheck(c, 1, 0);
     DevState s;
     r = read_state(c, &s);
     if (r != RRI_OK) return r;
@@ -3093,7 +3096,7 @@ rri_status rri_project_W_rows(rri_ctx* c, double s, const double* s_vec) {
     }
     LK::proj_rows(c, s, dvec);
     hipError_t e = hipStreamSynchronize(c->stream);
-    invalidate(c);
+    changed(c, CH_W);
     if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "projection failed: %s", hipGetErrorString(e));
     return RRI_OK;
 }
@@ -3139,10 +3142,7 @@ static rri_status objective_terms(rri_ctx* c, double out[3], double* tn) {
         // computed, and the sweep that follows skips its own rebuild (nmf() asks for the objective after
         // every sweep, nmf.py:488-490)
         DISPATCH(c, L::resid(c, true, true, c->rowobj, nullptr));
-        c->resid_valid = true;
-        c->resid_fresh = true;
-        c->dt_pending = false;
-        c->dw_pending = false;
+        resid_rebuilt(c);
         c->carry_valid = false;
     } else if (c->xy_valid && !c->sw.obj_direct) {
         // 1/2 ||X - W T||^2 = 1/2 ||X||^2 - sum_t <w_t, X t_t> + 1/2 <W^T W, T T^T>: the cross terms were left by
@@ -3190,10 +3190,7 @@ static rri_status objective_terms(rri_ctx* c, double out[3], double* tn) {
         // the objective is 1/2 ||R||^2 of the residual this schedule keeps: store it while it is computed, and the
         // sweep that follows skips its own rebuild
         DISPATCH(c, L::resid(c, false, true, c->rowobj, nullptr));
-        c->resid_valid = true;
-        c->resid_fresh = true;
-        c->dw_pending = false;
-        c->dt_pending = false;
+        resid_rebuilt(c);
     } else if (c->sparse_x) {
         // X on CSR, without the cross terms of a complete sweep: ||X - W T||^2 = sum_pattern r^2 + (<W^T W, T T^T> -
         // sum_pattern (W T)_ij^2) -- outside the pattern the residual is -(W T)_ij, whose squares are the Gram term less the
@@ -3353,9 +3350,7 @@ rri_status rri_rollback(rri_ctx* c) {
     HIPCHK(c, hipMemcpyAsync(c->W, c->Wprev, (size_t)c->k * c->ldw * 8, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->T, c->Tprev, (size_t)c->k * c->LD * 8, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    invalidate(c);
-    c->q_valid = false; c->gfull_valid = false;
-    c->pending_wcheck = false;
+    changed(c, CH_W | CH_T | CH_ENDED);
     return RRI_OK;
 }
 
@@ -3425,8 +3420,7 @@ rri_status rri_residual_update(rri_ctx* c, const double* a, const double* b, con
             for (int pgi = 0; pgi < c->npanels; ++pgi) sacc += yp[(size_t)pgi * c->n + i];
             y_out[i] = sacc;
         }
-    invalidate(c);            // Zpart / red were used, and R no longer equals X - W T for the handle's factors
-    c->pending_wcheck = false;
+    changed(c, CH_SCRATCH | CH_ENDED);    // Zpart / red were used, and R no longer equals X - W T for the handle's factors
     return RRI_OK;
 }
 
@@ -3490,7 +3484,7 @@ rri_status rri_Xt_times(rri_ctx* c, const double* Q, int32_t m, double* out) {
                                 (double*)outm.p + (i64)l * c->LD));
     c->timing = tsave;
     (void)tm_on;
-    invalidate(c);   // Zpart / red were used as scratch
+    changed(c, CH_SCRATCH);
     return to_host(c, outm.p, c->LD, out, m, RRI_F64, c->d, m, RRI_F64, true);
 }
 
@@ -3592,7 +3586,7 @@ rri_status rri_range_finder(rri_ctx* c, const double* Q0, int32_t m, int32_t n_i
         }
     }
     c->timing = tsave;
-    invalidate(c);   // Zpart / red were used as scratch
+    changed(c, CH_SCRATCH);
     if (s != RRI_OK) return s;
     if (!transpose) {
         s = to_host(c, Pn, c->ldw, Q_out, m, RRI_F64, c->n, m, RRI_F64, true);
@@ -3716,7 +3710,7 @@ rri_status rri_column_positive_counts(rri_ctx* c, double* df_out) {
     LK::reduce(c);
     HIPCHK(c, hipMemcpyAsync(df_out, c->red, (size_t)c->d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    invalidate(c);   // Zpart / red were used as scratch
+    changed(c, CH_SCRATCH);
     return RRI_OK;
 }
 
@@ -3756,9 +3750,7 @@ rri_status rri_scale_X(rri_ctx* c, const double* col_scale, int32_t normalize_ro
                                    (typename L::Elem*)c->X, c->ldx, c->n, (int)c->d, col_scale ? (const double*)sdev : nullptr,
                                    (const double*)invdev));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    invalidate(c);
-    c->q_valid = false; c->gfull_valid = false;
-    c->x_sq_valid = false;
+    changed(c, CH_X);
     return RRI_OK;
 }
 
@@ -3830,9 +3822,7 @@ rri_status rri_csr_scale_X(rri_ctx* c, const double* col_scale, int32_t normaliz
                                            (const typename L::Elem*)c->sp_x, (const int*)c->sp[w].perm, c->sp[w].count,
                                            (typename L::Elem*)c->sp[w].val));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    invalidate(c);
-    c->q_valid = false; c->gfull_valid = false;
-    c->x_sq_valid = false;
+    changed(c, CH_X);
     return RRI_OK;
 }
 
@@ -3851,7 +3841,7 @@ rri_status rri_bind_reduce_buffer(rri_ctx* c, void* dev_ptr, int64_t n_elems) {
     if (c->own_red && c->red) (void)hipFree(c->red);
     c->red = (double*)dev_ptr;
     c->own_red = false;
-    invalidate(c);
+    changed(c, CH_SCRATCH);
     return RRI_OK;
 }
 
@@ -3934,10 +3924,7 @@ rri_status rri_topic_finish(rri_ctx* c, int32_t t) {
     // column takes the row's scale (nmf.py:450-452) -- as enqueue_T_half does
     LK::trow(c, t, chk, c->pending_wcheck_topic, 0, c->prm.fix_W != 0);
     c->pending_wcheck = false;
-    c->carry_valid = false;
-    c->q_valid = false; c->gfull_valid = false;
-    c->xy_valid = false;
-    c->obj_track_valid = false;
+    changed(c, CH_T_ROW);
     if (c->prm.fix_W) {
         if (no_regs(c)) LK::scale_wcol(c, t);
         return RRI_OK;
@@ -4065,7 +4052,7 @@ rri_status rri_attach_comm(rri_ctx* c, rri_comm* comm, int64_t row_offset, int64
         c->comm = nullptr;
         c->row_offset = 0;
         c->n_global = 0;
-        invalidate(c);
+        changed(c, CH_SCRATCH);
         return RRI_OK;
     }
     if (row_offset < 0 || n_global < row_offset + c->n) return fail(c, RRI_ERR_INVALID, "row block [%lld, %lld) outside 0..%lld", (long long)row_offset, (long long)(row_offset + c->n), (long long)n_global);
@@ -4081,7 +4068,7 @@ rri_status rri_attach_comm(rri_ctx* c, rri_comm* comm, int64_t row_offset, int64
     c->row_offset = row_offset;
     c->n_global = n_global;
     c->comm_status = RRI_OK;
-    invalidate(c);
+    changed(c, CH_SCRATCH);
     return RRI_OK;
 }
 
@@ -4267,7 +4254,7 @@ rri_status rri_bench_rank1_update(rri_ctx* c, int32_t reps, double* avg_ms) {
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     (void)hipFree(R);
-    invalidate(c);
+    changed(c, CH_SCRATCH);
     if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "rank-one bench failed: %s", hipGetErrorString(e));
     if (avg_ms) *avg_ms = ms / reps;
     return RRI_OK;
