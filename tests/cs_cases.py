@@ -1,0 +1,902 @@
+"""A float64 model of what one RRIEngine handle holds between calls, and the sequences of calls that tests/test_cached_state_gpu.py
+runs against it (tests/test_cached_state_cases_cpu.py checks the cases themselves, without a GPU).
+
+The handle caches (the table above changed() in rri_hip.hip): carry_valid / carry_topic, resid_valid, xy_run / xy_valid,
+obj_track_valid, q_valid, gfull_valid, x_sq_valid.  The model caches nothing: it holds X, M (or None), W, T, the current
+parameters and a snapshot, and every operation recomputes what it needs from those with numpy and the CPU oracle.  A sequence is
+checked PER OPERATION (run_sequence): W and T are read from the handle before the operation (rri_get_W / rri_get_T touch no
+flag), the model computes the state the operation must leave from those, the operation runs on the handle, and the handle's new
+state is compared.  Rounding cannot accumulate over a sequence, and a failure names the operation.  The handle carries its
+caches through the sequence and the model has none: that difference is the test.
+
+Shape: n, d, k = 700, 333, 6, planted_X(seed=5) and scaled_init(seed=6) as the two sequences that test_cached_state_gpu.py had
+before.  Two exceptions, both forced by rri_bind_X_device, which refuses a d that is no multiple of 16 bytes / itemsize:
+the float32 flavour runs at d = 336 and the directed bind_X_device and bind_mask_device cases (float64) at d = 334.
+
+What the operations deviate from a plain nmf() call in, and why:
+  * 'simplex' (t_row_sum=1 with project_T_each_iter): rri_oracle.nmf projects the T it is given before its first sweep, as the
+    reference does, and rri_sweep does not (the driver nmf.py projects and sets T).  So set_params('simplex') is the driver's
+    pair -- set_params, then set_T of the projected T -- every T written from outside while they hold has rows that sum to 1, and rollback is
+    drawn only onto a T that is feasible: the oracle's projection is then the identity (Model.sweep_from asserts 1e-12).
+  * update_T_row leaves the rescaling of W[:, t] (nmf.py:474) to the W half that follows it (enqueue_T_half), so after it
+    column t of W is not compared, as check_steps of test_kernel_buckets_gpu.py does not.
+  * residual_update's return values depend on the stored residual, which is no part of the model (it is rebuilt from W and T
+    before it is next used): they are not compared here; test_residual_gpu.py owns them.
+  * preprocess(tfidf=True, normalize=True) is drawn only while the handle's X has zeros: planted_X is positive everywhere, its
+    idf is log(1) = 0 and the X it would leave is the constant 1 / d.  It leaves an X some fifty times smaller, and factors of
+    the old size overshoot it so far that the next sweep kills topics; so the operation is preprocess followed by set_W of
+    W * mean(X after) / mean(X before), as a driver that preprocesses starts its factors at the new scale.  That set_W drops
+    the first four rows of the table; ||X||^2, Qt and Gfull are left to preprocess's own CH_X, and scale_X is the pure case.
+
+Tolerances (all the project's own): W and T after one operation relfro < 1e-9 on a float64 handle (the two earlier sequences
+of test_cached_state_gpu.py, test_residual_gpu.py), 1e-7 on the float32 one (test_fuzz_gpu.py); the objective of a weighted
+handle, which always takes the residual path, 1e-12 relative (test_kernel_buckets_gpu.py), and so the objective of an unweighted
+handle wherever the cross terms of a whole sweep cannot be valid -- after any write from outside, lone half step or new X
+(LegalState.xy_possible); right after a whole sweep with W free, where the handle answers from the cross terms or from the
+residual as its flags allow, 1e-11 * max(want, 1e-3 ||X||^2) (test_hip_parity.py).
+"""
+import os
+
+import numpy as np
+import scipy.sparse as sp
+
+from rri_nmf_amd.synthetic import planted_X, scaled_init
+
+N, D, K = 700, 333, 6
+D_F32, D_BIND = 336, 334
+
+# ---- parameters ------------------------------------------------------------------------------------------------------------
+PARAMS = {
+    'free': dict(),
+    'fix_T': dict(fix_T=True),
+    'fix_W': dict(fix_W=True),
+    'clip': dict(t_row_sum=1.0),
+    'simplex': dict(t_row_sum=1.0, project_T_each_iter=True),
+    'pen_a': dict(reg_w_l2=0.3, reg_t_l2=0.2, reg_w_l1=0.05, reg_t_l1=0.02),
+    'pen_b': dict(reg_w_l2=0.7, reg_t_l2=0.1),
+}
+REGS = ('reg_w_l2', 'reg_t_l2', 'reg_w_l1', 'reg_t_l1')
+
+
+def oracle():
+    from oracle import rri_oracle
+    return rri_oracle
+
+
+# ---- flavours --------------------------------------------------------------------------------------------------------------
+# kind: plain | residual | weighted | pattern | csr;  env: read at rri_create
+FLAVOURS = {
+    'gram-onchip': dict(kind='plain', dtype=np.float64, d=D, env={'RRI_ONCHIP': '1'}),
+    'gram-phases': dict(kind='plain', dtype=np.float64, d=D, env={'RRI_ONCHIP': '0'}),
+    'residual': dict(kind='residual', dtype=np.float64, d=D, env={}),
+    'weighted': dict(kind='weighted', dtype=np.float64, d=D, env={}),
+    'pattern': dict(kind='pattern', dtype=np.float64, d=D, env={}),
+    'csr': dict(kind='csr', dtype=np.float64, d=D, env={}),
+    'gram-fp32': dict(kind='plain', dtype=np.float32, d=D_F32, env={}),
+    # the directed bind_X_device / bind_mask_device cases only (no random sequences): float64 at an even d
+    'gram-bind': dict(kind='plain', dtype=np.float64, d=D_BIND, env={'RRI_ONCHIP': '0'}),
+    'weighted-bind': dict(kind='weighted', dtype=np.float64, d=D_BIND, env={}),
+}
+RANDOM_FLAVOURS = [f for f in FLAVOURS if not f.endswith('-bind')]
+DIRECTED_ONLY = ['bind_mask']        # operations that no random alphabet has: bind_mask_device refuses the odd d of the weighted flavours
+WEIGHTED_KINDS = ('weighted', 'pattern')
+
+STATE, LOOK = 'state', 'look'       # an operation changes the handle's state, or borrows / observes
+_COMMON = ['sweep', 'set_params', 'set_W', 'set_T', 'reset', 'project_W', 'snapshot', 'rollback']
+_HALVES = ['update_T_row', 'update_W_col']
+ALPHABET = {
+    'plain': _COMMON + _HALVES + ['upload_X', 'scale_X', 'preprocess',
+                                  'X_times', 'Xt_times', 'range_finder', 'colcounts', 'bench_rank1', 'bench_copy',
+                                  'objective', 'objective_parts'],
+    'residual': _COMMON + _HALVES + ['upload_X', 'scale_X', 'preprocess', 'residual_update',
+                                     'X_times', 'Xt_times', 'range_finder', 'colcounts', 'bench_rank1', 'bench_copy',
+                                     'objective', 'objective_parts', 'residual_check'],
+    'weighted': _COMMON + ['upload_X', 'upload_mask', 'upload_mask_pattern',
+                           'X_times', 'Xt_times', 'range_finder', 'bench_copy', 'objective', 'objective_parts'],
+    'pattern': _COMMON + ['upload_observed', 'X_times', 'Xt_times', 'sparse_range_finder', 'objective', 'objective_parts'],
+    'csr': _COMMON + _HALVES + ['upload_X_csr', 'preprocess_csr',
+                                'X_times', 'Xt_times', 'sparse_range_finder', 'objective', 'objective_parts'],
+}
+LOOKS = {'X_times', 'Xt_times', 'range_finder', 'sparse_range_finder', 'colcounts', 'bench_rank1', 'bench_copy',
+         'residual_update', 'objective', 'objective_parts', 'residual_check'}
+
+
+def alphabet(flavour):
+    f = FLAVOURS[flavour]
+    ops = list(ALPHABET[f['kind']])
+    if f['dtype'] == np.float32:
+        # scale_X rewrites a float32 X in place: a second rounding whose order the model would have to mirror; the float64
+        # flavours own it.  In exchange this flavour's d lets it bind
+        ops = [o for o in ops if o not in ('scale_X', 'preprocess')] + ['bind_X']
+    return ops
+
+
+def category(name):
+    return LOOK if name in LOOKS else STATE
+
+
+# ---- coverage: every function of rri_hip.hip that calls changed(), and who reaches it here ---------------------------------
+# value: the operations of ALPHABET (or 'bind_X') that reach it, or ('excluded', reason)
+COVERAGE = {
+    # the steps of the schedule and the end of a run: every sweep and half step
+    'enqueue_T_half': ['sweep', 'update_T_row'],
+    'enqueue_W_half': ['sweep', 'update_W_col'],
+    'enqueue_rT_half': ['sweep', 'update_T_row'],
+    'enqueue_rW_half': ['sweep', 'update_W_col'],
+    'enqueue_wT_solve': ['sweep'],
+    'enqueue_wW_half': ['sweep'],
+    'enqueue_wsweep': ['sweep'],
+    'enqueue_onchip': ['sweep'],
+    'read_state': ['sweep'],
+    'status_from_halt': ['sweep'],
+    'run_and_collect': ['sweep'],
+    'reset_applied': ['reset'],
+    # entry points
+    'rri_upload_X': ['upload_X'],
+    'rri_upload_mask': ['upload_mask'],
+    'rri_upload_X_csr': ['upload_X_csr'],
+    'upload_X_csr_kept': ['upload_X_csr'],
+    'rri_upload_mask_csr_pattern': ['upload_mask_pattern'],
+    'rri_upload_observed_csr': ['upload_observed'],
+    'rri_bind_X_device': ['bind_X'],
+    'rri_set_W': ['set_W'],
+    'rri_set_T': ['set_T'],
+    'rri_set_params': ['set_params'],
+    'rri_project_W_rows': ['project_W'],
+    'rri_rollback': ['rollback'],
+    'rri_residual_update': ['residual_update'],
+    'rri_Xt_times': ['Xt_times'],
+    'rri_range_finder': ['range_finder'],
+    'rri_column_positive_counts': ['colcounts'],
+    'rri_scale_X': ['scale_X', 'preprocess'],
+    'rri_csr_scale_X': ['preprocess_csr'],
+    'rri_bench_rank1_update': ['bench_rank1'],
+    'rri_bind_mask_device': ['bind_mask'],
+    'rri_bind_reduce_buffer': ('excluded', 'the sharded and group tests own it'),
+    'rri_topic_finish': ('excluded', 'topic_* and reduce_*: the sharded and group tests own them'),
+    'rri_attach_comm': ('excluded', 'attach_group: the sharded and group tests own it'),
+}
+# entry points that call no changed() themselves and are in the alphabet all the same (they borrow, observe or copy)
+NO_CHANGED = {'rri_X_times': 'X_times', 'rri_sparse_range_finder': 'sparse_range_finder', 'rri_bench_stream_copy': 'bench_copy',
+              'rri_snapshot': 'snapshot', 'rri_objective': 'objective', 'rri_objective_parts': 'objective_parts',
+              'rri_residual_rebuild': 'residual_check', 'rri_update_T_row': 'update_T_row', 'rri_update_W_col': 'update_W_col',
+              'rri_apply_reset_vectors': 'reset', 'rri_sweep': 'sweep', 'rri_csr_column_positive_counts': 'preprocess_csr'}
+EXCLUDED_METHODS = {'attach_group': 'the sharded and group tests own it', 'bind_reduce_buffer': 'the sharded and group tests own it',
+                    'topic_reduce_local': 'sharded', 'topic_finish': 'sharded', 'topic_finish_w': 'sharded',
+                    'reduce_read': 'sharded', 'reduce_write': 'sharded', 'reduce_buffer': 'sharded',
+                    'apply_reset_max_resid': 'no wrapper outside a paused run (rri_apply_reset_max_resid)'}
+# operation -> the RRIEngine methods it calls (checked against engine.py)
+OP_METHODS = {
+    'sweep': ['sweep'], 'set_params': ['set_params', 'set_T'], 'set_W': ['set_W'], 'set_T': ['set_T'], 'reset': ['apply_reset_vectors'],
+    'project_W': ['project_W_rows'], 'snapshot': ['snapshot'], 'rollback': ['rollback'], 'update_T_row': ['update_T_row'],
+    'update_W_col': ['update_W_col'], 'upload_X': ['upload_X'], 'scale_X': ['scale_X'], 'preprocess': ['preprocess', 'set_W'],
+    'bind_X': ['bind_X_device'], 'bind_mask': ['bind_mask_device'], 'upload_X_csr': ['upload_X_csr'], 'preprocess_csr': ['_preprocess_csr', 'set_W'],
+    'upload_mask': ['upload_mask'], 'upload_mask_pattern': ['upload_mask_csr_pattern'], 'upload_observed': ['upload_observed_csr'],
+    'X_times': ['X_times'], 'Xt_times': ['Xt_times'], 'range_finder': ['range_finder'], 'sparse_range_finder': ['sparse_range_finder'],
+    'colcounts': ['column_positive_counts'], 'bench_rank1': ['bench_rank1_update'], 'bench_copy': ['bench_stream_copy'],
+    'residual_update': ['residual_update'], 'objective': ['objective'], 'objective_parts': ['objective_parts'],
+    'residual_check': ['residual_rebuild', 'get_residual'],
+}
+
+
+# ---- inputs ----------------------------------------------------------------------------------------------------------------
+def stored(X, dtype):
+    return np.ascontiguousarray(np.asarray(X, dtype=dtype).astype(np.float64))
+
+
+def _sparse_ish(X, salt):
+    """an X with zeros (a document-term matrix has them): 35 % of the entries kept"""
+    return X * (np.random.RandomState(1000 + salt).rand(*X.shape) < 0.35)
+
+
+def other_X(d, salt, dtype, sparse):
+    """another X of the same family; three salts in four give one with zeros, as do the kinds whose X is sparse"""
+    X = planted_X(N, d, K, seed=15 + salt, dtype=np.float64)
+    if sparse or salt % 4:
+        X = _sparse_ish(X, salt)
+    return stored(X, dtype)
+
+
+def weights(d, salt):
+    """a dense mask: half the entries observed, with weights in [0.5, 1.5)"""
+    rs = np.random.RandomState(2000 + salt)
+    return (rs.rand(N, d) < 0.5) * (0.5 + rs.rand(N, d))
+
+
+def pattern(d, salt):
+    return (np.random.RandomState(3000 + salt).rand(N, d) < 0.4).astype(np.float64)
+
+
+def observed_csr(X, Mp):
+    """the CSR matrix whose stored entries are the pattern Mp (explicit zeros kept) with X's values"""
+    I, J = np.nonzero(Mp)
+    return sp.csr_matrix((X[I, J], (I, J)), shape=X.shape)
+
+
+def start(flavour):
+    """(X as the handle stores it, M or None, W0, T0) of a flavour"""
+    f = FLAVOURS[flavour]
+    d, kind = f['d'], f['kind']
+    X = planted_X(N, d, K, seed=5, dtype=np.float64)
+    W0, T0 = scaled_init(X, K, seed=6)
+    M = None
+    if kind == 'csr':
+        X = _sparse_ish(X, 0)
+    elif kind == 'weighted':
+        M = weights(d, 0)
+    elif kind == 'pattern':
+        M = pattern(d, 0)
+        X = X * M
+    return stored(X, f['dtype']), M, W0, T0
+
+
+def new_W(W0, salt):
+    return W0 * (0.5 + np.random.RandomState(4000 + salt).rand(*W0.shape))
+
+
+def t_row_total(T0, pname):
+    """what the rows of a T written from outside sum to: 1 under 'simplex' (see the docstring), else what T0's rows do"""
+    return 1.0 if pname == 'simplex' else float(T0.sum(1).mean())
+
+
+def new_T(T0, salt, pname):
+    T = T0 * (0.5 + np.random.RandomState(5000 + salt).rand(*T0.shape))
+    return T / T.sum(1, keepdims=True) * t_row_total(T0, pname)
+
+
+def reset_vectors(W0, T0, salt, pname):
+    rs = np.random.RandomState(6000 + salt)
+    row = rs.rand(T0.shape[1])
+    return int(rs.randint(K)), row / row.sum() * t_row_total(T0, pname), 2.0 * W0.mean() * rs.rand(N)
+
+
+# ---- the model -------------------------------------------------------------------------------------------------------------
+class Op(object):
+    def __init__(self, name, arg=None):
+        self.name, self.arg = name, arg
+
+    def __repr__(self):
+        return self.name if self.arg is None else '%s(%s)' % (self.name, self.arg)
+
+
+class LegalState(object):
+    """What the next draw and the bounds may depend on, cheap to follow without running the oracle: the generator follows it
+    alone, the model follows it next to its arrays (Model.apply), so there is one copy of these rules."""
+
+    def __init__(self, kind):
+        self.pname = 'free'
+        self.has_snap = False
+        self.x_bound = False                # X is bound caller memory: rri_scale_X refuses it
+        self.x_has_zeros = kind == 'csr'    # preprocess needs an X with zeros (see the module docstring)
+        self.t_feasible = False             # the rows of T sum to 1
+        self.snap_feasible = False
+        # could the cross terms of a whole sweep be valid (xy_valid)?  Only if the last operation that changed the state was a
+        # sweep with W free: note_xy wants the W halves of topics 0 .. k-1 in order, and every write from outside, every lone
+        # half step and every new X drops them.  Where this is False the objective comes from the residual
+        self.xy_possible = False
+
+    def legal(self, op):
+        n, p = op.name, PARAMS[self.pname]
+        if n == 'rollback':
+            return self.has_snap and (self.pname != 'simplex' or self.snap_feasible)
+        if n == 'update_T_row':
+            return not p.get('fix_T')
+        if n == 'update_W_col':
+            return not p.get('fix_W')
+        if n in ('scale_X', 'preprocess') and self.x_bound:
+            return False
+        if n == 'preprocess':
+            return self.x_has_zeros
+        if n == 'set_params':
+            return op.arg != self.pname
+        return True
+
+    def follow(self, op):
+        n, a, p = op.name, op.arg, PARAMS[self.pname]
+        if category(n) == STATE and n not in ('snapshot', 'set_params'):
+            self.xy_possible = n == 'sweep' and not p.get('fix_W')
+        if n == 'sweep' and not p.get('fix_T'):
+            self.t_feasible = self.pname == 'simplex'
+        elif n == 'set_params':
+            self.pname = a
+            if a == 'simplex':
+                self.t_feasible = True
+        elif n == 'set_T':
+            self.t_feasible = self.pname == 'simplex'
+        elif n == 'snapshot':
+            self.has_snap, self.snap_feasible = True, self.t_feasible
+        elif n == 'rollback':
+            self.t_feasible = self.snap_feasible
+        elif n == 'update_T_row' and self.pname != 'simplex':
+            self.t_feasible = False
+        elif n in ('upload_X', 'bind_X'):
+            self.x_bound = n == 'bind_X'
+            self.x_has_zeros = bool(a % 4)          # other_X
+
+
+class Model(object):
+    """X, M, W, T, params, snapshot: nothing cached.  apply(op) returns what the handle must answer (or None) and moves the
+    model's W and T to what the handle must hold afterwards."""
+
+    def __init__(self, flavour):
+        self.flavour = flavour
+        self.f = FLAVOURS[flavour]
+        self.kind, self.d, self.dtype = self.f['kind'], self.f['d'], self.f['dtype']
+        self.X, self.M, self.W0, self.T0 = start(flavour)
+        self.W, self.T = self.W0.copy(), self.T0.copy()
+        self.ls = LegalState(self.kind)
+        self.snap = None
+        self.skip_col = None        # column of W the last operation leaves to the next W half (update_T_row)
+
+    @property
+    def pname(self):
+        return self.ls.pname
+
+    @property
+    def params(self):
+        return PARAMS[self.pname]
+
+    @property
+    def regs(self):
+        return {r: self.params.get(r, 0.0) for r in REGS}
+
+    def weighted(self):
+        return self.kind in WEIGHTED_KINDS
+
+    def legal(self, op):
+        return self.ls.legal(op)
+
+    # -- the operations --
+    def sweep_from(self, X, M, W, T, sweeps, pname=None):
+        p = dict(PARAMS[self.pname if pname is None else pname])
+        if p.get('project_T_each_iter'):
+            P = oracle().proj_rows_simplex(T.copy(), p['t_row_sum'])
+            assert np.abs(P - T).max() <= 1e-12, 'the model was given a T off the simplex under project_T_each_iter'
+        out = oracle().nmf(X, K, W_mat=M, W_in=W.copy(), T_in=T.copy(), max_iter=sweeps, eps_stop=-1, do_final_project_W=False,
+                           reset_topic_method=None, **p)
+        assert out['n_resets_used'] == 0
+        return out['W'], out['T']
+
+    def objective_at(self, X, M, W, T, regs=None):
+        return float(oracle().true_objective(X, W, T, Wm=M, **(self.regs if regs is None else regs)))
+
+    def half_T(self, t):
+        o, p = oracle(), self.params
+        wR, nw = o.residual_products_T(self.X, self.W, self.T, t)
+        s = p.get('t_row_sum') if p.get('project_T_each_iter') else None
+        row = o.qf_min(-(wR - self.regs['reg_t_l1']), nw + self.regs['reg_t_l2'], s=s, ub=p.get('t_row_sum'))[0]
+        if s and abs(row.sum() - s) > 1e-15:
+            row = o.proj_simplex(row, s=s)                 # nmf.py:757-761
+        return row
+
+    def half_W(self, t):
+        o = oracle()
+        Rt, nt = o.residual_products_W(self.X, self.W, self.T, t)
+        return o.qf_min(-(Rt - self.regs['reg_w_l1']), nt + self.regs['reg_w_l2'], s=None, ub=None)[0]
+
+    def apply(self, op):
+        want = self._apply(op)
+        self.ls.follow(op)
+        if op.name in ('upload_X', 'bind_X'):
+            assert self.ls.x_has_zeros == bool((self.X == 0).any())
+        return want
+
+    def _apply(self, op):
+        n, a = op.name, op.arg
+        self.skip_col = None
+        self.X_before = self.X
+        if n == 'sweep':
+            self.W, self.T = self.sweep_from(self.X, self.M, self.W, self.T, a)
+        elif n == 'set_params':
+            if a == 'simplex':
+                self.T = oracle().proj_rows_simplex(self.T.copy(), 1.0)
+        elif n == 'set_W':
+            self.W = new_W(self.W0, a)
+        elif n == 'zero_W_column':
+            self.W = zero_column_W(self.W0, a)
+        elif n == 'set_T':
+            self.T = new_T(self.T0, a, self.pname)
+        elif n == 'reset':
+            t, row, col = reset_vectors(self.W0, self.T0, a, self.pname)
+            self.T = self.T.copy()
+            self.W = self.W.copy()
+            self.T[t, :] = row
+            self.W[:, t] = col
+        elif n == 'project_W':
+            self.W = oracle().proj_rows_simplex(self.W.copy(), float(a))
+        elif n == 'snapshot':
+            self.snap = (self.W.copy(), self.T.copy())
+        elif n == 'rollback':
+            self.W, self.T = self.snap[0].copy(), self.snap[1].copy()
+        elif n == 'update_T_row':
+            row = self.half_T(a)
+            self.T = self.T.copy()
+            self.T[a, :] = row
+            self.skip_col = a
+        elif n == 'update_W_col':
+            col = self.half_W(a)
+            self.W = self.W.copy()
+            self.W[:, a] = col
+        elif n in ('upload_X', 'bind_X', 'upload_X_csr'):
+            self.X = other_X(self.d, a, self.dtype, sparse=self.kind == 'csr')
+        elif n == 'scale_X':
+            self.X = self.X * col_scale(self.d, a)
+        elif n in ('preprocess', 'preprocess_csr'):
+            before = float(self.X.mean())
+            self.X = oracle().normalize(oracle().tfidf(self.X))
+            self.W = self.W * (float(self.X.mean()) / before)
+        elif n in ('upload_mask', 'bind_mask'):
+            self.M = weights(self.d, a)
+        elif n == 'upload_mask_pattern':
+            self.M = pattern(self.d, a)
+        elif n == 'upload_observed':
+            self.M = pattern(self.d, a)
+            self.X = planted_X(N, self.d, K, seed=15 + a, dtype=np.float64) * self.M
+        elif n == 'X_times':
+            return self.X.dot(operand(self.d, a))
+        elif n == 'Xt_times':
+            return self.X.T.dot(operand(N, a))
+        elif n in ('range_finder', 'sparse_range_finder', 'bench_rank1', 'bench_copy', 'residual_update'):
+            return None
+        elif n == 'colcounts':
+            return (self.X > 0).sum(0).astype(np.float64)
+        elif n == 'objective':
+            return self.objective_at(self.X, self.M, self.W, self.T)
+        elif n == 'objective_parts':
+            return [self.objective_at(self.X, self.M, self.W, self.T, regs={}), float((self.W ** 2).sum()), float(np.abs(self.W).sum())]
+        elif n == 'residual_check':
+            return self.X - self.W.dot(self.T)
+        else:
+            raise KeyError(n)
+        return None
+
+    def state(self):
+        return dict(X=self.X, M=self.M, W=self.W.copy(), T=self.T.copy(), pname=self.pname)
+
+
+def rescale_after_preprocess(X):
+    """mean(preprocessed X) / mean(X): rows that sum to 1 are some fifty times smaller than planted_X's"""
+    return float(oracle().normalize(oracle().tfidf(X)).mean()) / float(X.mean())
+
+
+def col_scale(d, salt):
+    return 0.5 + np.random.RandomState(7000 + salt).rand(d)
+
+
+def operand(rows, salt, m=3):
+    return np.random.RandomState(8000 + salt).randn(rows, m)
+
+
+def update_vectors(d, salt):
+    rs = np.random.RandomState(9000 + salt)
+    return rs.rand(N), rs.rand(d), rs.rand(d), rs.rand(N)
+
+
+# ---- the handle ------------------------------------------------------------------------------------------------------------
+def make_engine(flavour):
+    """a handle of the flavour with its X (and mask), W0, T0 and the free parameters; the caller has set FLAVOURS[..]['env']"""
+    from rri_nmf_amd.engine import RRIEngine
+    f = FLAVOURS[flavour]
+    for key, val in f['env'].items():
+        assert os.environ.get(key) == val, 'set %s=%s before the handle is created (rri_create reads it)' % (key, val)
+    X, M, W0, T0 = start(flavour)
+    kind = f['kind']
+    kw = dict(dtype=f['dtype'])
+    if kind == 'residual':
+        kw['schedule'] = 'residual'
+    elif kind == 'weighted':
+        kw['weighted'] = True
+    elif kind == 'pattern':
+        kw['weighted'] = 'sparse'
+    elif kind == 'csr':
+        kw['sparse_x'] = True
+    e = RRIEngine(N, f['d'], K, **kw)
+    try:
+        if kind == 'pattern':
+            e.upload_observed_csr(observed_csr(X, M))
+        elif kind == 'csr':
+            e.upload_X_csr(sp.csr_matrix(X))
+        else:
+            e.upload_X(X.astype(f['dtype']))
+            if kind == 'weighted':
+                e.upload_mask(M)
+        e.set_W(W0), e.set_T(T0)
+        e.set_params(reset_topic_method=None)
+    except Exception:
+        e.close()
+        raise
+    e._cs_keep = []         # device memory bound to the handle stays alive with it
+    return e
+
+
+def apply_engine(e, m, op):
+    """the operation on the handle; m is the model, which has the operation behind it (m.X_before: the X it had before)"""
+    n, a = op.name, op.arg
+    d, dt = m.d, m.dtype
+    if n == 'sweep':
+        return e.sweep(a)
+    if n == 'set_params':
+        e.set_params(reset_topic_method=None, **PARAMS[a])
+        if a == 'simplex':      # as the driver enters a run (nmf.py:414-417)
+            e.set_T(oracle().proj_rows_simplex(e.get_T(), 1.0))
+        return None
+    if n == 'set_W':
+        return e.set_W(new_W(m.W0, a))
+    if n == 'zero_W_column':
+        return e.set_W(zero_column_W(m.W0, a))
+    if n == 'set_T':
+        return e.set_T(new_T(m.T0, a, m.pname))
+    if n == 'reset':
+        return e.apply_reset_vectors(*reset_vectors(m.W0, m.T0, a, m.pname))
+    if n == 'project_W':
+        return e.project_W_rows(float(a))
+    if n in ('snapshot', 'rollback', 'update_T_row', 'update_W_col'):
+        return getattr(e, n)(*(() if a is None else (a,)))
+    if n == 'upload_X':
+        return e.upload_X(other_X(d, a, dt, False).astype(dt))
+    if n == 'bind_X':
+        import torch
+        t = torch.from_numpy(other_X(d, a, dt, False).astype(dt)).to('cuda:%d' % e.device).contiguous()
+        torch.cuda.synchronize()
+        e._cs_keep.append(t)
+        return e.bind_X_device(t.data_ptr(), d)
+    if n == 'upload_X_csr':
+        return e.upload_X_csr(sp.csr_matrix(other_X(d, a, dt, True)))
+    if n == 'scale_X':
+        return e.scale_X(col_scale(d, a))
+    if n in ('preprocess', 'preprocess_csr'):
+        W = e.get_W()
+        idf = e.preprocess(tfidf=True, normalize=True) if n == 'preprocess' else e._preprocess_csr(True, True)
+        e.set_W(W * rescale_after_preprocess(m.X_before))
+        return idf
+    if n == 'upload_mask':
+        return e.upload_mask(weights(d, a))
+    if n == 'bind_mask':
+        import torch
+        t = torch.from_numpy(np.ascontiguousarray(weights(d, a).astype(dt))).to('cuda:%d' % e.device).contiguous()
+        torch.cuda.synchronize()
+        e._cs_keep.append(t)
+        return e.bind_mask_device(t.data_ptr(), d)
+    if n == 'upload_mask_pattern':
+        return e.upload_mask_csr_pattern(sp.csr_matrix(pattern(d, a)))
+    if n == 'upload_observed':
+        Mp = pattern(d, a)
+        return e.upload_observed_csr(observed_csr(planted_X(N, d, K, seed=15 + a, dtype=np.float64) * Mp, Mp))
+    if n == 'X_times':
+        return e.X_times(operand(d, a))
+    if n == 'Xt_times':
+        return e.Xt_times(operand(N, a))
+    if n == 'range_finder':
+        Q, B = e.range_finder(operand(d, a, 4), 1)
+        return Q, B
+    if n == 'sparse_range_finder':
+        Q, B = e.sparse_range_finder(operand(d, a, 4), 1)
+        return Q, B
+    if n == 'colcounts':
+        return e.column_positive_counts()
+    if n == 'bench_rank1':
+        return e.bench_rank1_update(1)
+    if n == 'bench_copy':
+        return e.bench_stream_copy(1)
+    if n == 'residual_update':
+        return e.residual_update(*update_vectors(d, a))
+    if n == 'objective':
+        return e.objective()
+    if n == 'objective_parts':
+        return e.objective_parts()
+    if n == 'residual_check':
+        e.residual_rebuild()
+        return e.get_residual(np.float64)
+    raise KeyError(n)
+
+
+def relfro(a, b):
+    den = np.linalg.norm(b)
+    return float(np.linalg.norm(np.asarray(a, dtype=np.float64) - b) / (den if den > 0 else 1.0))
+
+
+def factor_tol(flavour):
+    return 1e-9 if FLAVOURS[flavour]['dtype'] == np.float64 else 1e-7
+
+
+def objective_tol(m, want):
+    """1e-12 relative where the objective comes from a residual (weighted handles always; unweighted ones whenever the cross
+    terms cannot be valid: LegalState.xy_possible); the bound of the cross-term path only right after a whole sweep, where the
+    handle may answer either way"""
+    if m.weighted() or not m.ls.xy_possible:
+        return 1e-12 * abs(want)
+    return 1e-11 * max(abs(want), 1e-3 * float((m.X ** 2).sum()))
+
+
+def check_value(m, op, got, want, log=None):
+    """the answer of a borrower or an observer against numpy, at the bound its own tests use; m is the model (unchanged)"""
+    n = op.name
+    where = '%r' % (op,)
+    if n in ('X_times', 'Xt_times'):
+        err = relfro(got, want)                                  # test_nmf_gpu.py: 1e-13
+        assert err < 1e-13, (where, err)
+    elif n in ('range_finder', 'sparse_range_finder'):           # test_nmf_gpu.py / test_sparse_range_finder_gpu.py: 1e-12
+        Q, B = got
+        orth = float(np.abs(Q.T.dot(Q) - np.eye(Q.shape[1])).max())
+        eb = relfro(B, Q.T.dot(m.X))
+        assert orth < 1e-12 and eb < 1e-12, (where, orth, eb)
+    elif n == 'colcounts':
+        assert np.array_equal(got, want), where                  # test_preprocess_gpu.py
+    elif n in ('bench_rank1', 'bench_copy'):
+        assert got >= 0.0, where
+    elif n == 'objective':
+        if log:
+            log('      objective: off by %.2e relative, bound %.0e (%s)' % (abs(got - want) / abs(want), objective_tol(m, want) / abs(want),
+                                                                          'either path' if m.ls.xy_possible else 'residual path'))
+        assert abs(got - want) <= objective_tol(m, want), (where, got, want, abs(got - want) / abs(want))
+    elif n == 'objective_parts':
+        assert abs(got[0] - want[0]) <= objective_tol(m, want[0]), (where, got[0], want[0])
+        assert abs(got[1] - want[1]) <= 1e-12 * want[1] and abs(got[2] - want[2]) <= 1e-12 * want[2], (where, got, want)
+    elif n == 'residual_check':
+        # every entry is x - sum of k products, in float64: (k + 2) roundings of at most |x| + |w|^T |t| each, four times over
+        bound = 4.0 * (K + 2) * 2.0 ** -53 * (np.abs(m.X) + np.abs(m.W).dot(np.abs(m.T)))
+        assert np.all(np.abs(got - want) <= bound), (where, float(np.abs(got - want).max()))
+
+
+def run_sequence(e, flavour, ops, log=None, raises=None):
+    """ops on the handle e, each checked against a model that restarts from the handle's own W and T; returns the answers.
+    raises: the index of the one operation that the oracle refuses, and the handle must refuse with the same exception type
+    (as test_fuzz_gpu.py compares outcomes); an exception anywhere else is a failure of the test"""
+    m = Model(flavour)
+    tol = factor_tol(flavour)
+    answers = []
+    for i, op in enumerate(ops):
+        m.W, m.T = e.get_W(), e.get_T()
+        if i == raises:
+            try:
+                m.apply(op)
+                refused = None
+            except (ValueError, NotImplementedError) as exc:
+                refused = type(exc)
+            except AssertionError as exc:
+                assert 'sums to 0' in str(exc) or 'negative entries' in str(exc), exc     # the oracle's own, not the model's
+                refused = AssertionError
+            assert refused is not None, 'the oracle accepts op %d %r of %r' % (i, op, ops)
+            try:
+                apply_engine(e, m, op)
+                raised = None
+            except (ValueError, AssertionError, NotImplementedError) as exc:
+                raised = type(exc)
+            assert raised is refused, 'op %d %r of %r: the handle raised %r, the oracle %r' % (i, op, ops, raised, refused)
+            m.ls.follow(op)
+            answers.append(None)
+            if log:
+                log('op %2d %-24r both raise %s' % (i, op, refused.__name__))
+            continue        # what a failed call leaves in W and T is read before the next operation, like any other state
+        want = m.apply(op)
+        got = apply_engine(e, m, op)
+        answers.append(got)
+        W, T = e.get_W(), e.get_T()
+        cols = [c for c in range(K) if c != m.skip_col]
+        ew, et = relfro(W[:, cols], m.W[:, cols]), relfro(T, m.T)
+        if log:
+            log('op %2d %-24r W %.2e  T %.2e' % (i, op, ew, et))
+        assert ew < tol and et < tol, 'after op %d %r of %r: W %.3e T %.3e (tolerance %.0e)' % (i, op, ops, ew, et, tol)
+        if category(op.name) == LOOK:
+            check_value(m, op, got, want, log)
+        assert e.n_resets_used == (sum(1 for o in ops[:i + 1] if o.name == 'reset'))
+    return answers
+
+
+def run_model(flavour, ops):
+    """the sequence on the model alone, chained: (model after the last operation, the answers, the state before each operation)"""
+    m = Model(flavour)
+    answers, states = [], []
+    for op in ops:
+        assert m.legal(op), (op, ops)
+        states.append(m.state())
+        answers.append(m.apply(op))
+    return m, answers, states
+
+
+# ---- seeded random sequences -----------------------------------------------------------------------------------------------
+SEQ_LEN = 12
+_PARAM_NAMES = sorted(PARAMS)
+
+
+def draw_op(rs, name):
+    salt = int(rs.randint(1, 50))
+    if name == 'sweep':
+        return Op(name, int(rs.randint(1, 3)))
+    if name == 'set_params':
+        return Op(name, _PARAM_NAMES[int(rs.randint(len(_PARAM_NAMES)))])
+    if name in ('update_T_row', 'update_W_col'):
+        return Op(name, int(rs.randint(K)))
+    if name == 'project_W':
+        return Op(name, 1.0)
+    if name in ('snapshot', 'rollback', 'preprocess', 'preprocess_csr', 'colcounts', 'bench_rank1', 'bench_copy', 'objective',
+                'objective_parts', 'residual_check'):
+        return Op(name)
+    return Op(name, salt)
+
+
+def healthy(flavour, ops):
+    """on the model alone: no exception, no reset, and no column of W or row of T anywhere near dead after any operation"""
+    m = Model(flavour)
+    try:
+        for op in ops:
+            if not m.legal(op):
+                return False
+            m.apply(op)
+            if not (np.isfinite(m.W).all() and np.isfinite(m.T).all() and (m.W.sum(0) > 1e-6).all() and (m.T.sum(1) > 1e-6).all()):
+                return False
+    except (ValueError, AssertionError, NotImplementedError):
+        return False
+    return True
+
+
+# A drawn sequence in which a topic dies on the model (a sweep right after X shrank fifty-fold under preprocess, say) is no case
+# for this test: resets are off, and a column that is dead or alive by rounding compares nothing.  It is drawn again.  For the
+# default seeds the redraws that this took are written down (test_cached_state_cases_cpu.py checks all of them on the model);
+# above them random_sequence looks for the first healthy draw itself.
+DEFAULT_SEEDS = 24
+REDRAWS = {('gram-onchip', 2): 1, ('gram-onchip', 3): 1, ('gram-onchip', 7): 1, ('gram-onchip', 9): 1, ('gram-onchip', 13): 1,
+           ('gram-onchip', 19): 1, ('gram-phases', 14): 1, ('residual', 10): 1, ('residual', 13): 1, ('csr', 3): 1, ('csr', 6): 1,
+           ('csr', 10): 1, ('csr', 12): 1, ('csr', 22): 1, ('gram-fp32', 9): 1}
+
+
+def random_sequence(flavour, seed):
+    """SEQ_LEN operations of the flavour's alphabet: at least half change the state, at least three borrow or observe, and the
+    last two are sweep(1) and objective()"""
+    if seed < DEFAULT_SEEDS:
+        return draw_sequence(flavour, seed, REDRAWS.get((flavour, seed), 0))
+    for attempt in range(64):
+        ops = draw_sequence(flavour, seed, attempt)
+        if healthy(flavour, ops):
+            return ops
+    raise AssertionError('no healthy sequence for %s, seed %d' % (flavour, seed))
+
+
+def draw_sequence(flavour, seed, attempt):
+    rs = np.random.RandomState((97 * RANDOM_FLAVOURS.index(flavour) + attempt) * 100003 + seed)
+    names = alphabet(flavour)
+    by = {STATE: [x for x in names if category(x) == STATE], LOOK: [x for x in names if category(x) == LOOK]}
+    slots = [STATE] * 6 + [LOOK] * 3 + ['any']
+    rs.shuffle(slots)
+    m = LegalState(FLAVOURS[flavour]['kind'])
+    ops = []
+    for slot in slots:
+        pool = names if slot == 'any' else by[slot]
+        for _ in range(100):
+            op = draw_op(rs, pool[int(rs.randint(len(pool)))])
+            # preprocess is legal only after an X with zeros went up: taken every other time it could be, or it is hardly seen
+            if 'preprocess' in pool and m.legal(Op('preprocess')) and not any(o.name == 'preprocess' for o in ops) and rs.rand() < 0.5:
+                op = Op('preprocess')
+            if m.legal(op):
+                break
+        else:
+            raise AssertionError('no legal operation found')
+        m.follow(op)
+        ops.append(op)
+    return ops + [Op('sweep', 1), Op('objective')]
+
+
+def persistent_sweeps(ops):
+    """how many sweep() calls of ops an RRI_ONCHIP=1 handle must run as persistent launches: those with both factors free
+    (onchip_ok refuses fix_W and fix_T; penalties, the clip and the projection of T ride in the kernel)"""
+    ls, count = LegalState('plain'), 0
+    for op in ops:
+        p = PARAMS[ls.pname]
+        if op.name == 'sweep' and not p.get('fix_W') and not p.get('fix_T'):
+            count += 1
+        ls.follow(op)
+    return count
+
+
+def n_seeds():
+    return int(os.environ.get('RRI_CACHED_STATE_CASES', '24'))
+
+
+# ---- directed sequences ----------------------------------------------------------------------------------------------------
+class Case(object):
+    """row: the row of the table above changed() the case aims at.  stale: how a handle that kept the named value would answer
+    the LAST operation, in oracle terms (stale_reference), or None with `waived` saying why that cannot be written.
+      ('x_sq', j)        the objective with ||X||^2 of the X before operation j
+      ('xy', j)          the objective with the cross terms <w_t, X t_t> of the W, T (and X) before operation j
+      ('penalty', j)     the objective with the penalties before operation j
+      ('objective', j)   the objective of the W and T before operation j (what the persistent launch left)
+      ('factors', j, fields)  the last operation (a sweep) run from the current state with `fields` as they were before operation j
+    """
+
+    def __init__(self, name, row, flavour, ops, stale=None, waived=None, raises=None):
+        self.name, self.row, self.flavour, self.ops, self.stale, self.waived, self.raises = name, row, flavour, ops, stale, waived, raises
+        assert (stale is None) != (waived is None)
+
+
+S1, S2, OBJ = ('sweep', 1), ('sweep', 2), ('objective',)
+
+
+def _case(name, row, flavour, steps, **kw):
+    return Case(name, row, flavour, [Op(*s) for s in steps], **kw)
+
+
+CASES = []
+# x_sq_valid: sweep, objective (takes ||X||^2), another X, sweep, objective
+for _name, _fl, _chg in (('upload_X', 'gram-phases', ('upload_X', 2)), ('scale_X', 'gram-phases', ('scale_X', 3)),
+                         ('bind_X_device', 'gram-bind', ('bind_X', 2))):
+    CASES.append(_case('x_sq-%s' % _name, 'x_sq_valid', _fl, [S1, OBJ, _chg, S1, OBJ], stale=('x_sq', 2)))
+# xy_run / xy_valid: sweep, objective, W or T written from outside, objective
+for _name, _chg in (('project_W_rows', ('project_W', 1.0)), ('rollback', ('rollback',)), ('apply_reset_vectors', ('reset', 4)),
+                    ('set_T', ('set_T', 5))):
+    _steps = [('snapshot',)] if _name == 'rollback' else []
+    _steps += [S1, OBJ, _chg, OBJ]
+    CASES.append(_case('xy-%s' % _name, 'xy_run / xy_valid', 'gram-phases', _steps, stale=('xy', len(_steps) - 2)))
+# obj_track_valid: the objective a persistent launch left
+CASES.append(_case('obj_track-set_params', 'obj_track_valid', 'gram-onchip', [S2, OBJ, ('set_params', 'pen_a'), OBJ], stale=('penalty', 2)))
+CASES.append(_case('obj_track-update_W_col', 'obj_track_valid', 'gram-onchip', [S2, ('update_W_col', 1), OBJ], stale=('objective', 1)))
+# q_valid / gfull_valid: two sweeps with T fixed, T or X changed between them
+for _name, _chg, _fields in (('set_T', ('set_T', 6), ('T',)), ('rollback', ('rollback',), ('T',)), ('scale_X', ('scale_X', 7), ('X',)),
+                             ('upload_X', ('upload_X', 4), ('X',))):
+    _steps = [('snapshot',), S1] if _name == 'rollback' else []
+    _steps += [('set_params', 'fix_T'), S1, _chg, S1]
+    CASES.append(_case('q-%s' % _name, 'q_valid / gfull_valid', 'gram-phases', _steps, stale=('factors', len(_steps) - 2, _fields)))
+# resid_valid: the maintained residual E of the three weighted layouts (dense weights, dense 0/1 bit-packed, pattern only)
+_LAYOUTS = (('weights', 'weighted', []), ('bits', 'weighted', [('upload_mask_pattern', 1)]), ('pattern', 'pattern', []))
+for _lname, _fl, _pre in _LAYOUTS:
+    _newmask = ('upload_observed', 8) if _fl == 'pattern' else ('upload_mask_pattern', 9) if _lname == 'bits' else ('upload_mask', 9)
+    for _name, _chg, _fields in (('set_W', ('set_W', 8), ('W',)), ('set_T', ('set_T', 9), ('T',)), ('rollback', ('rollback',), ('W', 'T')),
+                                 ('project_W_rows', ('project_W', 1.0), ('W',)), ('new_mask', _newmask, ('M', 'X'))):
+        # a sweep rebuilds E once, at its start, unless the objective has just stored it: only after objective() does the
+        # second sweep depend on resid_valid having been dropped
+        for _suffix, _between in (('', []), ('-after_objective', [OBJ])):
+            _steps = list(_pre) + ([('snapshot',)] if _name == 'rollback' else []) + [S1] + _between + [_chg, S1]
+            CASES.append(_case('resid-%s-%s%s' % (_lname, _name, _suffix), 'resid_valid', _fl, _steps,
+                               stale=('factors', len(_steps) - 2, _fields)))
+    if _lname == 'weights':     # the caller-owned counterpart of upload_mask, at the even d that rri_bind_mask_device accepts
+        for _suffix, _between in (('', []), ('-after_objective', [OBJ])):
+            _steps = [S1] + _between + [('bind_mask', 9), S1]
+            CASES.append(_case('resid-bound_mask%s' % _suffix, 'resid_valid', 'weighted-bind', _steps,
+                               stale=('factors', len(_steps) - 2, ('M',))))
+    CASES.append(_case('resid-%s-objective_between_sweeps' % _lname, 'resid_valid', _fl, list(_pre) + [S1, OBJ, S1],
+                       waived='the legitimate path: the objective stored E and the sweep skips its rebuild; nothing is stale'))
+CASES.append(_case('resid-residual_update', 'resid_valid', 'residual', [S1, ('residual_update', 3), S1],
+                   waived='the stored R after a foreign rank-one update is no function of W, T and X that the oracle has'))
+CASES.append(_case('resid-form_switch', 'resid_valid', 'residual', [S1, ('set_params', 'fix_T'), S1, ('set_params', 'free'), S1],
+                   stale=('factors', 2, ('W',))))
+# carry_valid: after a free sweep Zpart / Gpart hold topic 0's partial sums; a borrower overwrites them
+for _name, _b in (('Xt_times', ('Xt_times', 1)), ('column_positive_counts', ('colcounts',)), ('range_finder', ('range_finder', 2)),
+                  ('X_times', ('X_times', 3))):
+    for _nname, _next in (('sweep', S1), ('update_T_row', ('update_T_row', 0))):
+        CASES.append(_case('carry-%s-%s' % (_name, _nname), 'carry_valid / carry_topic', 'gram-phases', [S1, _b, _next],
+                           waived='an overwritten scratch buffer is no value the oracle can state'))
+# after a call that ended in an error: CH_ENDED and the column verdict that was pending
+CASES.append(_case('ended-zero_column', 'carry_valid / pending_wcheck (CH_ENDED)', 'gram-phases',
+                   [('zero_W_column', 2), S1, ('set_W', 3), S1], raises=1,
+                   waived='an error is a verdict, not a value'))
+CASES = {c.name: c for c in CASES}
+
+
+def zero_column_W(W0, t):
+    W = W0.copy()
+    W[:, t] = 0.0
+    return W
+
+
+def stale_reference(case):
+    """(what the last operation answers by the model, what a handle that kept the case's value would answer)"""
+    m, answers, states = run_model(case.flavour, case.ops)
+    kind, j = case.stale[0], case.stale[1]
+    old, cur = states[j], states[-1]
+    o = oracle()
+    if kind == 'x_sq':
+        return answers[-1], answers[-1] + 0.5 * (float((old['X'] ** 2).sum()) - float((m.X ** 2).sum()))
+    if kind == 'xy':
+        cross = sum(float(old['W'][:, t].dot(old['X'].dot(old['T'][t, :]))) for t in range(K))
+        quad = float((m.W.T.dot(m.W) * m.T.dot(m.T.T)).sum())
+        return answers[-1], 0.5 * float((m.X ** 2).sum()) - cross + 0.5 * quad
+    if kind == 'penalty':
+        return answers[-1], m.objective_at(m.X, m.M, m.W, m.T, regs={r: PARAMS[old['pname']].get(r, 0.0) for r in REGS})
+    if kind == 'objective':
+        return answers[-1], m.objective_at(m.X, m.M, old['W'], old['T'])
+    if kind == 'factors':
+        src = dict(cur)
+        for f in case.stale[2]:
+            src[f] = old[f]
+        W, T = m.sweep_from(src['X'], src['M'], src['W'], src['T'], case.ops[-1].arg, pname=cur['pname'])
+        return (m.W, m.T), (W, T)
+    raise KeyError(kind)

@@ -7,7 +7,15 @@ Two sequences on ONE handle in which T changes between two fixed-T sweeps by a r
 rri_apply_reset_max_resid has no engine wrapper outside a paused run (RRIEngine reaches it only through a pending event), so it
 has no case here.
 
-Reference: the CPU oracle, chained call by call with W_in / T_in, eps_stop=-1, in float64.  Tolerance: relfro < 1e-9 on W and
+Those two came first and stay as they were.  Everything below them runs sequences of calls on ONE handle against the float64
+model of tests/cs_cases.py, which caches nothing, operation by operation (cs_cases.run_sequence: the model restarts from the
+handle's own W and T before every operation, so a failure names the operation and no rounding accumulates):
+  * directed sequences, one test per row of the table above changed() in rri_hip.hip and per route that makes the row stale;
+  * test_random_sequence: 12 operations drawn from the flavour's alphabet, 24 seeds per flavour (RRI_CACHED_STATE_CASES raises it).
+Tolerances and what the operations are: the docstring of tests/cs_cases.py.  That a stale value cannot hide under them is
+tests/test_cached_state_cases_cpu.py's to show.
+
+Reference of the two earlier sequences: the CPU oracle, chained call by call with W_in / T_in, eps_stop=-1, in float64.  Tolerance: relfro < 1e-9 on W and
 on T of a float64 handle (summation order only, as tests/test_residual_gpu.py between two float64 runs).  A stale Qt cannot
 hide under it: given the T of the first fixed call in place of the current one, the oracle's last call ends with a W that is
 off by relfro 1.2e-1 in the first sequence and by 8.2e-1 in the second.
@@ -15,6 +23,7 @@ off by relfro 1.2e-1 in the first sequence and by 8.2e-1 in the second.
 import numpy as np
 import pytest
 
+import cs_cases as cs
 from conftest import relfro
 from rri_nmf_amd.synthetic import planted_X, scaled_init
 
@@ -90,3 +99,122 @@ def test_reset_outside_a_paused_run_between_two_fixed_T_sweeps(monkeypatch):
     ew, et = relfro(W, Wr), relfro(T, Tr)
     print('reset between fixed-T sweeps vs oracle: W %.3e  T %.3e' % (ew, et))
     assert ew < TOL and et < TOL, (ew, et)
+
+
+# ---- sequences against the model of cs_cases.py --------------------------------------------------------------------------
+def run_case(monkeypatch, flavour, ops, raises=None):
+    """the handle of the flavour through ops, every operation checked; on the RRI_ONCHIP=1 flavour every sweep with both factors
+    free must have been a persistent launch (a launch that gave up for want of co-resident workgroups, onchip_fallbacks, keeps
+    the handle off that path for seconds: then one launch is all that is asked)"""
+    for key, val in cs.FLAVOURS[flavour]['env'].items():
+        monkeypatch.setenv(key, val)                       # read at rri_create
+    lines = []
+    e = cs.make_engine(flavour)
+    try:
+        if flavour == 'gram-onchip':
+            assert e.onchip_info()[0], '700 x 333 float64 is not eligible for the register-resident sweep'
+        try:
+            answers = cs.run_sequence(e, flavour, ops, log=lines.append, raises=raises)
+        finally:
+            print('\n'.join(lines))
+        if flavour == 'gram-onchip':
+            launches, want = e.onchip_info()[1], cs.persistent_sweeps(ops)
+            print('persistent launches: %d of %d free sweeps' % (launches, want))
+            assert launches >= (want if e.onchip_fallbacks() == 0 else min(want, 1)), (launches, want, e.onchip_fallbacks())
+        return answers
+    finally:
+        e.close()
+
+
+def directed(monkeypatch, name):
+    case = cs.CASES[name]
+    return run_case(monkeypatch, case.flavour, case.ops, raises=case.raises)
+
+
+@pytest.mark.parametrize('route', ['upload_X', 'scale_X', 'bind_X_device'])
+def test_x_sq_after_another_X(monkeypatch, route):
+    """x_sq_valid: sweep(1), objective() takes ||X||^2, X changes, sweep(1), objective().  bind_X_device binds a torch tensor, at
+    d = 334 (cs_cases); where this is the first use of torch.cuda in the process, the seconds it takes are torch's start"""
+    directed(monkeypatch, 'x_sq-' + route)
+
+
+@pytest.mark.parametrize('route', ['project_W_rows', 'rollback', 'apply_reset_vectors', 'set_T'])
+def test_cross_terms_after_an_outside_write(monkeypatch, route):
+    """xy_run / xy_valid: sweep(1), objective() from the cross terms, W or T written from outside, objective()"""
+    directed(monkeypatch, 'xy-' + route)
+
+
+def test_tracked_objective_after_other_penalties(monkeypatch):
+    """obj_track_valid (RRI_ONCHIP=1): sweep(2), objective(), set_params with other penalties, objective() carries the new ones"""
+    directed(monkeypatch, 'obj_track-set_params')
+
+
+def test_tracked_objective_after_a_W_half(monkeypatch):
+    """obj_track_valid (RRI_ONCHIP=1): sweep(2), update_W_col(1), objective()"""
+    directed(monkeypatch, 'obj_track-update_W_col')
+
+
+@pytest.mark.parametrize('route', ['set_T', 'rollback', 'scale_X', 'upload_X'])
+def test_fixed_T_products_after_a_change(monkeypatch, route):
+    """q_valid / gfull_valid: a fixed-T sweep(1), T or X changed, a fixed-T sweep(1)"""
+    directed(monkeypatch, 'q-' + route)
+
+
+@pytest.mark.parametrize('stored_by', ['sweep', 'objective'])
+@pytest.mark.parametrize('route', ['set_W', 'set_T', 'rollback', 'project_W_rows', 'new_mask'])
+@pytest.mark.parametrize('layout', ['weights', 'bits', 'pattern'])
+def test_maintained_residual_after_an_outside_change(monkeypatch, layout, route, stored_by):
+    """resid_valid: sweep(1), an outside change, sweep(1) on the three weighted layouts (dense weights, a dense 0/1 mask packed
+    to bits, the observed pattern only).  A sweep rebuilds E at its start unless the objective has just stored it, so each route
+    runs a second time with objective() before the change: with CH_M taken out of changed() only those cases fail"""
+    directed(monkeypatch, 'resid-%s-%s%s' % (layout, route, '-after_objective' if stored_by == 'objective' else ''))
+
+
+@pytest.mark.parametrize('layout', ['weights', 'bits', 'pattern'])
+def test_maintained_residual_stored_by_the_objective(monkeypatch, layout):
+    """resid_valid, the legitimate path: sweep(1), objective() stores E, and the sweep(1) that follows skips its rebuild"""
+    directed(monkeypatch, 'resid-%s-objective_between_sweeps' % layout)
+
+
+@pytest.mark.parametrize('stored_by', ['sweep', 'objective'])
+def test_maintained_residual_after_a_bound_mask(monkeypatch, stored_by):
+    """resid_valid, rri_bind_mask_device: sweep(1) [, objective()], a mask in caller-owned device memory (a torch tensor; a weighted
+    float64 handle at d = 334, which the call accepts), sweep(1)"""
+    directed(monkeypatch, 'resid-bound_mask' + ('-after_objective' if stored_by == 'objective' else ''))
+
+
+def test_explicit_residual_after_a_foreign_rank_one_update(monkeypatch):
+    """resid_valid, explicit-residual handle: sweep(1), residual_update(a, b, trow, wcol), sweep(1)"""
+    directed(monkeypatch, 'resid-residual_update')
+
+
+def test_explicit_residual_across_the_form_switch(monkeypatch):
+    """resid_valid, explicit-residual handle: free sweep(1), fixed-T sweep(1) (stepped in the Gram form), free sweep(1): the form
+    switch of rri_set_params"""
+    directed(monkeypatch, 'resid-form_switch')
+
+
+@pytest.mark.parametrize('then', ['sweep', 'update_T_row'])
+@pytest.mark.parametrize('borrower', ['Xt_times', 'column_positive_counts', 'range_finder', 'X_times'])
+def test_carry_after_a_borrower(monkeypatch, borrower, then):
+    """carry_valid / carry_topic: after a free sweep Zpart / Gpart hold topic 0's partial sums; a borrower runs, then sweep(1) or
+    update_T_row(0).  Only column_positive_counts tells: it sums into Zpart and reduces into red, and with CH_SCRATCH taken out
+    of changed() its two cases fail (T off by 4e+1).  rri_Xt_times and rri_range_finder say CH_SCRATCH but keep their partial
+    sums in a buffer of their own (DevTmp zm), and rri_X_times on a dense handle calls no changed() at all: their cases show
+    that the carry survives them, which is all they can show"""
+    directed(monkeypatch, 'carry-%s-%s' % (borrower, then))
+
+
+def test_sweep_after_a_call_that_ended_in_an_error(monkeypatch):
+    """CH_ENDED and the pending column verdict: W with a zero column and no resets, sweep(1) raises as the oracle does, then
+    set_W(good), sweep(1)"""
+    case = cs.CASES['ended-zero_column']
+    run_case(monkeypatch, case.flavour, case.ops, raises=case.raises)
+
+
+@pytest.mark.parametrize('seed', range(cs.n_seeds()))
+@pytest.mark.parametrize('flavour', cs.RANDOM_FLAVOURS)
+def test_random_sequence(monkeypatch, flavour, seed):
+    ops = cs.random_sequence(flavour, seed)
+    print(ops)
+    run_case(monkeypatch, flavour, ops)
