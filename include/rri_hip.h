@@ -386,6 +386,11 @@ rri_status rri_layout_info(rri_ctx* ctx, int64_t* out, int32_t n);
  * *eligible of rri_onchip_info and RRI_ERR_UNSUPPORTED of rri_sweep_until therefore depend on the clock after a fallback.
  * *fallbacks: how often that happened on this handle. */
 rri_status rri_onchip_fallbacks(rri_ctx* ctx, int64_t* fallbacks);
+/* The device buffers that handles of this process own at this moment, and their bytes: what rri_create, the uploads and the
+ * buffers made on first use allocated and rri_destroy (or a replacement) has not yet freed.  Bound caller memory (rri_bind_*)
+ * and the temporaries of a call are not counted.  Takes no handle, so it can be read after rri_destroy: both values are then
+ * back where they were before rri_create.  Either pointer may be NULL. */
+rri_status rri_device_memory(int64_t* buffers, int64_t* bytes);
 /* diagnostics: the XCD (XCC_ID) each of `count` workgroups of a launch on the handle's stream lands on */
 rri_status rri_debug_xcc(rri_ctx* ctx, int32_t* out, int32_t count);
 /* The sweep / objective / stop-rule loop of nmf.py:377-516 for launch-bound sizes, in one call: up to n_sweeps sweeps of the

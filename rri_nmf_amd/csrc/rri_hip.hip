@@ -43,13 +43,6 @@ namespace {
 
 thread_local std::string g_create_error;   // text of the last failed rri_create of this thread
 
-// temporary device buffer that is released on every return path
-struct DevTmp {
-    void* p = nullptr;
-    ~DevTmp() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
-};
-
 struct Cursor {
     int sweep, topic, phase;  // phase 0 = T-row half, 1 = W-column half
 };
@@ -157,7 +150,10 @@ struct rri_ctx {
 
     void *X = nullptr, *M = nullptr, *E = nullptr;
     i64 ldx = 0, ldm = 0;
-    bool own_X = false, own_M = false;
+    // what the handle allocated (dev_alloc, dev_adopt) and rri_destroy frees: the field that holds it, the pointer, its size.  X, M
+    // and red may hold bound caller memory instead, which is not listed here and therefore never freed
+    struct Owned { const void* field; void* p; size_t bytes; };
+    std::vector<Owned> owned;
     double *W = nullptr, *T = nullptr, *Wprev = nullptr, *Tprev = nullptr;
     double *Ypart = nullptr, *Zpart = nullptr, *red = nullptr, *xraw = nullptr, *Ttpart = nullptr;
     unsigned* Mbits = nullptr;   // bit-packed 0/1 mask (weighted flavour), ldb words per row; NULL = fp mask in M
@@ -174,7 +170,6 @@ struct rri_ctx {
     double *Y2part = nullptr, *Z2part = nullptr, *dtv = nullptr, *dwv = nullptr, *wold = nullptr, *zeros = nullptr;  // weighted
     i64 ldw = 0;     // row stride of the k-major W (>= n)
     int nsplit = 4;  // column slices of k_tgram
-    bool own_red = false;
     i64 red_elems = 0;
     // weighted flavour on a CSR observation pattern (rri_upload_observed_csr): no dense n x d array at all
     bool sparse = false;
@@ -382,6 +377,75 @@ rri_status fail(rri_ctx* c, rri_status code, const char* fmt, ...) {
     if (!(c)) return RRI_ERR_INVALID
 
 i64 round_up(i64 a, i64 b) { return (a + b - 1) / b * b; }
+
+// ---- who owns device memory ("Who owns device memory") ------------------------------------------------------------
+// temporary device buffer that is released on every return path
+struct DevTmp {
+    void* p = nullptr;
+    size_t bytes = 0;
+    ~DevTmp() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t b) { bytes = b; return hipMalloc(&p, b); }
+};
+// the two events of one measurement, destroyed on every return path
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    hipError_t create() { const hipError_t e = hipEventCreate(&a); return e == hipSuccess ? hipEventCreate(&b) : e; }
+};
+// handle-owned allocations alive in the process (rri_device_memory)
+std::atomic<long long> g_dev_buffers{0}, g_dev_bytes{0};
+void dev_count(long long buffers, size_t bytes) { g_dev_buffers += buffers; g_dev_bytes += buffers * (long long)bytes; }
+rri_ctx::Owned* dev_owned(rri_ctx* c, const void* field) {
+    for (auto& o : c->owned)
+        if (o.field == field) return &o;
+    return nullptr;
+}
+// frees what the field holds if the handle allocated it; a bound (borrowed) pointer is only forgotten
+template <typename P>
+void dev_release(rri_ctx* c, P*& p) {
+    if (rri_ctx::Owned* o = dev_owned(c, &p)) {
+        (void)hipFree(o->p);
+        dev_count(-1, o->bytes);
+        c->owned.erase(c->owned.begin() + (o - c->owned.data()));
+    }
+    p = nullptr;
+}
+// a temporary becomes the handle's buffer p; what the field held before goes first, so a field never has two entries
+template <typename P>
+void dev_adopt(rri_ctx* c, P*& p, DevTmp& t) {
+    dev_release(c, p);
+    p = (P*)t.p;
+    c->owned.push_back({&p, t.p, t.bytes});
+    dev_count(1, t.bytes);
+    t.p = nullptr;
+}
+// the one way a handle gets device memory; zero: cleared on the handle's stream.  A failure leaves p NULL and no sticky error
+template <typename P>
+hipError_t dev_alloc(rri_ctx* c, P*& p, size_t bytes, bool zero = false) {
+    DevTmp t;
+    hipError_t e = t.alloc(bytes);
+    if (e == hipSuccess && zero) e = hipMemsetAsync(t.p, 0, bytes, c->stream);
+    if (e == hipSuccess) dev_adopt(c, p, t);
+    else { p = nullptr; (void)hipGetLastError(); }
+    return e;
+}
+// ... and the one idiom of a buffer that is allocated on first use
+template <typename P>
+hipError_t dev_ensure(rri_ctx* c, P*& p, size_t bytes, bool zero = false) {
+    return p ? hipSuccess : dev_alloc(c, p, bytes, zero);
+}
+// opts kernel K in to more than 64 KiB of dynamic LDS, once per instantiation and device (the attribute belongs to the device's
+// code object)
+template <auto K>
+hipError_t allow_lds(const rri_ctx* c, int bytes) {
+    static bool done[64] = {};
+    bool& d = done[c->device & 63];
+    if (d) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) d = true;
+    else (void)hipGetLastError();
+    return e;
+}
 
 // ---- collectives of a row-sharded handle: all on the handle's stream --------------------------------------------
 // RCCL: enqueued like a kernel (no host synchronisation).  Host-callback transport: the stream is drained, the
@@ -678,19 +742,18 @@ struct LaunchX {
         if (!c->mcols_tried) {
             c->mcols_tried = true;
             const i64 ng = (c->n + 31) / 32;
-            unsigned long long* cnt = nullptr;
-            if (hipMalloc((void**)&c->Mcols, (size_t)ng * c->LD * sizeof(unsigned)) != hipSuccess) { c->Mcols = nullptr; (void)hipGetLastError(); return false; }
-            if (hipMalloc((void**)&cnt, sizeof(unsigned long long)) != hipSuccess) { (void)hipFree(c->Mcols); c->Mcols = nullptr; (void)hipGetLastError(); return false; }
-            (void)hipMemsetAsync(cnt, 0, sizeof(unsigned long long), c->stream);
+            DevTmp cnt;
+            if (dev_alloc(c, c->Mcols, (size_t)ng * c->LD * sizeof(unsigned)) != hipSuccess) return false;
+            if (cnt.alloc(sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); dev_release(c, c->Mcols); return false; }
+            (void)hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), c->stream);
             hipLaunchKernelGGL(k_mask_cols_from_bits, dim3(4096), dim3(256), 0, c->stream, (const unsigned*)c->Mbits, c->ldb, c->n, c->Mcols,
-                               c->LD, cnt);
+                               c->LD, (unsigned long long*)cnt.p);
             unsigned long long h = 0;
-            hipError_t e = hipMemcpyAsync(&h, cnt, sizeof h, hipMemcpyDeviceToHost, c->stream);
+            hipError_t e = hipMemcpyAsync(&h, cnt.p, sizeof h, hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            (void)hipFree(cnt);
-            if (e != hipSuccess) { (void)hipFree(c->Mcols); c->Mcols = nullptr; return false; }
+            if (e != hipSuccess) { dev_release(c, c->Mcols); return false; }
             c->mask_density = (double)h / ((double)c->n * (double)c->d);
-            if (c->mask_density > 0.12) { (void)hipFree(c->Mcols); c->Mcols = nullptr; }     // the dense-bit kernel is the cheaper one there
+            if (c->mask_density > 0.12) dev_release(c, c->Mcols);     // the dense-bit kernel is the cheaper one there
         }
         return c->Mcols != nullptr;
     }
@@ -740,13 +803,7 @@ struct LaunchX {
     static void sp_blk_k(rri_ctx* c, const rri_ctx::SpCopy& cp, const double* B1, const double* B2, const double* V,
                          const double* A1, const double* A2, double* S1, double* S2, i64 lds) {
         const size_t sh = sp_lds_bytes<SX>(cp.bw);
-        static bool attr_set[64] = {};   // per instantiation and device (the attribute belongs to the device's code object)
-        const int dv = c->device & 63;
-        if (!attr_set[dv]) {
-            (void)hipFuncSetAttribute((const void*)k_sp_blk<SX, DO_S, UPD2, WRITE, LPS>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, SP_BLOCK_BYTES + 64);
-            attr_set[dv] = true;
-        }
+        (void)allow_lds<k_sp_blk<SX, DO_S, UPD2, WRITE, LPS>>(c, SP_BLOCK_BYTES + 64);
         if (cp.nwork < 1) return;
         hipLaunchKernelGGL((k_sp_blk<SX, DO_S, UPD2, WRITE, LPS>), dim3(cp.nwork), dim3(1024), sh, c->stream,
                            (const SpWork*)cp.work, (const i64*)cp.segptr, cp.nseg, (const unsigned short*)cp.idx,
@@ -836,8 +893,8 @@ struct LaunchX {
     }
     // 0/1 masks are bit-packed (32 columns per word): the mask then costs 1/32 of its fp32 bytes per pass
     static rri_status pack_mask_if_binary(rri_ctx* c) {
-        if (c->Mbits) { (void)hipFree(c->Mbits); c->Mbits = nullptr; }
-        if (c->Mcols) { (void)hipFree(c->Mcols); c->Mcols = nullptr; }
+        dev_release(c, c->Mbits);
+        dev_release(c, c->Mcols);
         c->mcols_tried = false;
         if (!c->sw.mask_bits) return RRI_OK;
         hipError_t err = hipMemsetAsync(c->itmp, 0, sizeof(i64), c->stream);
@@ -850,8 +907,7 @@ struct LaunchX {
         if (err != hipSuccess) return RRI_ERR_HIP;
         if (bad) return RRI_OK;
         c->ldb = (c->LD + 3) / 4;   // one word per 8 rows x 4 columns
-        err = hipMalloc((void**)&c->Mbits, (size_t)((c->n + 7) / 8) * c->ldb * sizeof(unsigned));
-        if (err != hipSuccess) { c->Mbits = nullptr; return RRI_ERR_HIP; }
+        if (dev_alloc(c, c->Mbits, (size_t)((c->n + 7) / 8) * c->ldb * sizeof(unsigned)) != hipSuccess) return RRI_ERR_HIP;
         hipLaunchKernelGGL((k_mask_pack<SX>), dim3(4096), dim3(256), 0, c->stream, (const SX*)c->M, c->ldm, c->n,
                            c->d, c->Mbits, c->ldb);
         err = hipStreamSynchronize(c->stream);
@@ -861,11 +917,7 @@ struct LaunchX {
     static void xtt_mfma_k(rri_ctx* c, const double* Tm, int m, double* out) {
         constexpr int VN = XVec<SX>::N;
         const size_t sh = 2 * 64 * (size_t)(16 * NT + 1) * sizeof(double) + 4 * 16 * (size_t)(64 + VN) * sizeof(SX);
-        static bool attr_set[64] = {};
-        if (!attr_set[c->device & 63]) {
-            (void)hipFuncSetAttribute((const void*)k_xtt_mfma<SX, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_set[c->device & 63] = true;
-        }
+        (void)allow_lds<k_xtt_mfma<SX, NT>>(c, 160 * 1024);
         hipLaunchKernelGGL((k_xtt_mfma<SX, NT>), dim3((unsigned)((c->n + 63) / 64)), dim3(256), sh, c->stream,
                            (const SX*)c->X, c->ldx, Tm, c->LD, (int)c->n, (int)c->d, m, out, c->ldw);
     }
@@ -1008,22 +1060,15 @@ struct LaunchX {
                            (const SX*)c->X, c->ldx, (const double*)c->W, c->ldw, (const double*)c->T, c->LD,
                            (int)c->d, c->k, (const i64*)c->itmp, c->xraw);
     }
-    static hipError_t set_attrs() {
-        if constexpr (RO) {
-            return hipFuncSetAttribute((const void*)k_resid<SX, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        } else {
-            return set_attrs_rw();
+    static hipError_t set_attrs(const rri_ctx* c) {
+        hipError_t e = allow_lds<k_resid<SX, false, false>>(c, 160 * 1024);
+        if constexpr (!RO) {
+            if (e == hipSuccess) e = allow_lds<k_resid<SX, true, true>>(c, 160 * 1024);
+            if (e == hipSuccess) e = allow_lds<k_resid<SX, true, false>>(c, 160 * 1024);
+            if (e == hipSuccess) e = allow_lds<k_resid<SX, false, true>>(c, 160 * 1024);
+            if (e == hipSuccess) e = allow_lds<k_spx_pass<SX>>(c, SP_BLOCK_BYTES + 64);
         }
-    }
-    static hipError_t set_attrs_rw() {
-        hipError_t e = hipSuccess;
-        const void* fns[] = {(const void*)k_resid<SX, true, true>, (const void*)k_resid<SX, true, false>,
-                             (const void*)k_resid<SX, false, true>, (const void*)k_resid<SX, false, false>};
-        for (const void* f : fns) {
-            e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-        return hipFuncSetAttribute((const void*)k_spx_pass<SX>, hipFuncAttributeMaxDynamicSharedMemorySize, SP_BLOCK_BYTES + 64);
+        return e;
     }
 };
 
@@ -1225,16 +1270,16 @@ rri_status to_device(rri_ctx* c, const void* host, i64 ld, int host_dtype, void*
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return RRI_OK;
     }
-    void* tmp = nullptr;
-    HIPCHK(c, hipMalloc(&tmp, (size_t)rows * cols * hs));
-    hipError_t e = hipMemcpy2DAsync(tmp, cols * hs, host, ld * hs, cols * hs, rows, hipMemcpyHostToDevice,
+    DevTmp tmp;
+    HIPCHK(c, tmp.alloc((size_t)rows * cols * hs));
+    hipError_t e = hipMemcpy2DAsync(tmp.p, cols * hs, host, ld * hs, cols * hs, rows, hipMemcpyHostToDevice,
                                     c->stream);
     if (e == hipSuccess) {
         const bool hf = host_dtype == RRI_F32, df = dev_dtype == RRI_F32;
 #define RRI_CONV(SRC, DST)                                                                  \
     do {                                                                                    \
-        if (transpose) launch_convert<SRC, DST, true>(c, tmp, cols, dev, ldd, rows, cols);  \
-        else launch_convert<SRC, DST, false>(c, tmp, cols, dev, ldd, rows, cols);           \
+        if (transpose) launch_convert<SRC, DST, true>(c, tmp.p, cols, dev, ldd, rows, cols);  \
+        else launch_convert<SRC, DST, false>(c, tmp.p, cols, dev, ldd, rows, cols);           \
     } while (0)
         if (hf && df) RRI_CONV(float, float);
         else if (hf) RRI_CONV(float, double);
@@ -1243,7 +1288,6 @@ rri_status to_device(rri_ctx* c, const void* host, i64 ld, int host_dtype, void*
 #undef RRI_CONV
         e = hipStreamSynchronize(c->stream);
     }
-    (void)hipFree(tmp);
     if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
     return RRI_OK;
 }
@@ -1262,15 +1306,15 @@ rri_status to_host(rri_ctx* c, const void* dev, i64 ldd, void* host, i64 ld, int
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return RRI_OK;
     }
-    void* tmp = nullptr;
-    HIPCHK(c, hipMalloc(&tmp, (size_t)rows * cols * hs));
+    DevTmp tmp;
+    HIPCHK(c, tmp.alloc((size_t)rows * cols * hs));
     {
         const bool hf = host_dtype == RRI_F32, df = dev_dtype == RRI_F32;
         // source is the device image; for a transposed image its shape is cols x rows
 #define RRI_CONV(SRC, DST)                                                                     \
     do {                                                                                       \
-        if (transpose) launch_convert<SRC, DST, true>(c, dev, ldd, tmp, cols, cols, rows);     \
-        else launch_convert<SRC, DST, false>(c, dev, ldd, tmp, cols, rows, cols);              \
+        if (transpose) launch_convert<SRC, DST, true>(c, dev, ldd, tmp.p, cols, cols, rows);   \
+        else launch_convert<SRC, DST, false>(c, dev, ldd, tmp.p, cols, rows, cols);            \
     } while (0)
         if (df && hf) RRI_CONV(float, float);
         else if (df) RRI_CONV(float, double);
@@ -1278,10 +1322,9 @@ rri_status to_host(rri_ctx* c, const void* dev, i64 ldd, void* host, i64 ld, int
         else RRI_CONV(double, double);
 #undef RRI_CONV
     }
-    hipError_t e = hipMemcpy2DAsync(host, ld * hs, tmp, cols * hs, cols * hs, rows, hipMemcpyDeviceToHost,
+    hipError_t e = hipMemcpy2DAsync(host, ld * hs, tmp.p, cols * hs, cols * hs, rows, hipMemcpyDeviceToHost,
                                     c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(tmp);
     if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "download failed: %s", hipGetErrorString(e));
     return RRI_OK;
 }
@@ -1652,32 +1695,35 @@ void calibrate_rot(rri_ctx* c) {
     const bool wdense = c->weighted && !c->sparse;
     const bool plain = !c->weighted && !resid && !c->sparse && !c->prm.fix_T;      // the Gram form: the read-only pass over X
     if (!(resid || wdense || plain) || (double)c->n * (double)c->d < 1.0e8 || c->npanels * c->nrb < 64) return;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess) { (void)hipGetLastError(); return; }
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipGetLastError(); (void)hipEventDestroy(e0); return; }
+    EventPair ev;
+    if (ev.create() != hipSuccess) { (void)hipGetLastError(); return; }
+    // the better of the rotations 0 .. nrot-1 of `rot` by what `pass` takes: two warm passes at rotation 0 (the first passes of a
+    // process run ~5 % slow: not the rotation's doing), then three per rotation, the last two timed; the first of equal times wins;
+    // a launch or a wait that fails: rotation 0.  The passes leave their own row products and column sums in the scratch arrays
+    auto pick = [&](int& rot, int nrot, const char* what, auto&& pass) {
+        float best = -1.0f;
+        int best_rot = 0;
+        rot = 0;
+        for (int rep = 0; rep < 2; ++rep) pass();
+        for (rot = 0; rot < nrot; ++rot) {
+            for (int rep = 0; rep < 3; ++rep) {
+                if (rep == 1) (void)hipEventRecord(ev.a, c->stream);
+                pass();
+            }
+            (void)hipEventRecord(ev.b, c->stream);
+            float ms = 0.0f;
+            if (hipEventSynchronize(ev.b) != hipSuccess || hipEventElapsedTime(&ms, ev.a, ev.b) != hipSuccess) { best = -1.0f; break; }
+            if (c->sw.rot_debug) fprintf(stderr, "rri: tile rotation %d: %.4f ms per %s\n", rot, ms / 2.0f, what);
+            if (best < 0.0f || ms < best) { best = ms; best_rot = rot; }
+        }
+        rot = best > 0.0f ? best_rot : 0;
+        c->carry_valid = false;
+        c->carry_topic = -1;
+    };
     if (plain) {
         // the read-only pass moves by ~1 % with the rotation (0.643 against 0.650 ms at BASELINE config 3, the same way in every
         // round of three processes): the same calibration on X, 8 passes once per handle
-        float best = -1.0f;
-        int best_rot = 0;
-        for (int rot = -1; rot < 2; ++rot) {                 // -1: two warm passes
-            c->rot_x = std::max(rot, 0);
-            for (int rep = 0; rep < (rot < 0 ? 2 : 3); ++rep) {
-                if (rot >= 0 && rep == 1) (void)hipEventRecord(e0, c->stream);
-                DISPATCH_RO(c, (L::template pass<true, true>(c, 0, 0)));
-            }
-            if (rot < 0) continue;
-            (void)hipEventRecord(e1, c->stream);
-            float ms = 0.0f;
-            if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { best = -1.0f; break; }
-            if (c->sw.rot_debug) fprintf(stderr, "rri: tile rotation %d: %.4f ms per read-only pass\n", rot, ms / 2.0f);
-            if (best < 0.0f || ms < best) { best = ms; best_rot = rot; }
-        }
-        c->rot_x = best > 0.0f ? best_rot : 0;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        c->carry_valid = false;
-        c->carry_topic = -1;
+        pick(c->rot_x, 2, "read-only pass", [&]() { DISPATCH_RO(c, (L::template pass<true, true>(c, 0, 0))); });
         return;
     }
     if (!c->resid_valid) {
@@ -1699,29 +1745,8 @@ void calibrate_rot(rri_ctx* c) {
     // one at 1.42, four at 1.50-1.53 whatever the rotation; physically contiguous memory: always 1.54 --
     // profiles/r04_rmw_buffer_probe.log).  Trying a large residual in several places until one ran fast found none in 40 places
     // (10 processes) on a box whose buffers were slow: the first allocation is kept.
-    c->rot_r = 0;
-    for (int rep = 0; rep < 2; ++rep) null_update();   // (the first passes of a process run ~5 % slow: not the rotation's doing)
-    // the better of the rotations 0 and 1 (or 0 .. RRI_ROT_CAL-1), by null updates; a launch or a wait that fails: rotation 0
-    float best = -1.0f;
-    int best_rot = 0;
-    const int nrot = c->sw.rot_cal > 1 ? std::min(c->sw.rot_cal, 8) : 2;
-    for (int rot = 0; rot < nrot; ++rot) {
-        c->rot_r = rot;
-        for (int rep = 0; rep < 3; ++rep) {
-            if (rep == 1) (void)hipEventRecord(e0, c->stream);
-            null_update();
-        }
-        (void)hipEventRecord(e1, c->stream);
-        float ms = 0.0f;
-        if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { best = -1.0f; break; }
-        if (c->sw.rot_debug) fprintf(stderr, "rri: tile rotation %d: %.4f ms per null update\n", rot, ms / 2.0f);
-        if (best < 0.0f || ms < best) { best = ms; best_rot = rot; }
-    }
-    c->rot_r = best > 0.0f ? best_rot : 0;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    c->carry_valid = false;          // the null updates left their own row products and column sums in the scratch arrays
-    c->carry_topic = -1;
+    // rotations 0 and 1 (or 0 .. RRI_ROT_CAL-1), by null updates
+    pick(c->rot_r, c->sw.rot_cal > 1 ? std::min(c->sw.rot_cal, 8) : 2, "null update", null_update);
 }
 
 // ---- T fixed: the W half of all topics of a sweep as one launch (k_wsweep_rows) ---------------------------------------
@@ -1738,16 +1763,10 @@ static_assert(WCOL_TILES == 1, "enqueue_wsweep assumes one 64-row tile per k_wco
 bool enqueue_wsweep(rri_ctx* c, int sweep, int t0) {
     const int k = c->k;
     const size_t f8 = sizeof(double);
-    if (!c->Gfull && hipMalloc((void**)&c->Gfull, (size_t)k * k * f8) != hipSuccess) { c->Gfull = nullptr; (void)hipGetLastError(); return false; }
-    if (!c->Wsweep0 && hipMalloc((void**)&c->Wsweep0, (size_t)k * c->ldw * f8) != hipSuccess) { c->Wsweep0 = nullptr; (void)hipGetLastError(); return false; }
-    if (!c->wsum_part && hipMalloc((void**)&c->wsum_part, (size_t)k * c->nwb * f8) != hipSuccess) { c->wsum_part = nullptr; (void)hipGetLastError(); return false; }
-    if (!c->wsums && hipMalloc((void**)&c->wsums, (size_t)k * f8) != hipSuccess) { c->wsums = nullptr; (void)hipGetLastError(); return false; }
-    static bool attr_set[64] = {};
-    const int dv = c->device & 63;
-    if (!attr_set[dv]) {
-        if (hipFuncSetAttribute((const void*)k_wsweep_rows, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess) { (void)hipGetLastError(); return false; }
-        attr_set[dv] = true;
-    }
+    if (dev_ensure(c, c->Gfull, (size_t)k * k * f8) != hipSuccess || dev_ensure(c, c->Wsweep0, (size_t)k * c->ldw * f8) != hipSuccess ||
+        dev_ensure(c, c->wsum_part, (size_t)k * c->nwb * f8) != hipSuccess || dev_ensure(c, c->wsums, (size_t)k * f8) != hipSuccess)
+        return false;
+    if (allow_lds<k_wsweep_rows>(c, 152 * 1024) != hipSuccess) return false;
     flush_wcheck(c, sweep, t0);     // (a column check left by steps before T was fixed)
     if (!c->q_valid) {           // X T^T: once per T, reused by every topic and every sweep
         DISPATCH_RO(c, L::xtt(c));
@@ -1900,16 +1919,11 @@ hipError_t onchip_ordered_launch(rri_ctx* c, const void* fn, int grid, size_t sh
 }
 template <typename SX, int RPW, bool DBG = false, bool PROJ = false, int KT = 3>
 hipError_t onchip_launch(rri_ctx* c, const OnchipGeom& g, const OnchipArgs& a) {
-    static bool attr_set[64] = {};
-    const int dv = c->device & 63;
     const void* fn = (const void*)k_onchip_sweeps<SX, RPW, DBG, PROJ, KT>;
-    if (!attr_set[dv]) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e != hipSuccess) { if (getenv("RRI_ONCHIP_DEBUG")) fprintf(stderr, "rri: hipFuncSetAttribute\n"); return e; }
-        attr_set[dv] = true;
-    }
+    hipError_t e = allow_lds<k_onchip_sweeps<SX, RPW, DBG, PROJ, KT>>(c, 152 * 1024);
+    if (e != hipSuccess) { if (getenv("RRI_ONCHIP_DEBUG")) fprintf(stderr, "rri: hipFuncSetAttribute\n"); return e; }
     int per_cu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_onchip_sweeps<SX, RPW, DBG, PROJ, KT>, ONCHIP_THREADS, g.shmem);
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_onchip_sweeps<SX, RPW, DBG, PROJ, KT>, ONCHIP_THREADS, g.shmem);
     if (getenv("RRI_ONCHIP_DEBUG")) fprintf(stderr, "rri: occupancy %d per CU (%s), %d CUs\n", per_cu, hipGetErrorString(e), c->n_cu);
     if (e != hipSuccess) return e;
     if ((i64)per_cu * c->n_cu < g.G) return hipErrorCooperativeLaunchTooLarge;     // the hand-overs need every workgroup resident
@@ -1921,22 +1935,21 @@ bool enqueue_onchip(rri_ctx* c, Cursor cur) {
     if (!onchip_geometry(c, &g)) return false;
     const int k = c->k;
     if (!c->mkZ) {
-        if (hipMalloc((void**)&c->mkZ, (size_t)2 * g.G * c->LD * 8) != hipSuccess) { c->mkZ = nullptr; return false; }
-        if (hipMalloc((void**)&c->mkG, (size_t)2 * g.G * (k + 2) * 8) != hipSuccess) return false;
-        if (hipMalloc((void**)&c->mkP, (size_t)2 * 64 * (k + 1) * 8) != hipSuccess) return false;
-        if (hipMalloc((void**)&c->mkbar, (size_t)(128 + g.G) * sizeof(unsigned)) != hipSuccess) return false;
-        if (hipMalloc((void**)&c->mkX, (size_t)2 * c->LD * 8) != hipSuccess) return false;
-        if (hipMalloc((void**)&c->mkT, (size_t)2 * c->LD * 8) != hipSuccess) return false;
-        if (hipMalloc((void**)&c->objE, (size_t)ONCHIP_UNTIL_CAP * 256 * 8) != hipSuccess) return false;
-        if (hipMalloc((void**)&c->objhist, (size_t)ONCHIP_UNTIL_CAP * 8) != hipSuccess) return false;
-        if (hipMalloc((void**)&c->objdec, (size_t)ONCHIP_UNTIL_CAP * 8) != hipSuccess) return false;
-        (void)hipMemsetAsync(c->mkZ, 0, (size_t)2 * g.G * c->LD * 8, c->stream);
-        (void)hipMemsetAsync(c->mkG, 0, (size_t)2 * g.G * (k + 2) * 8, c->stream);
-        (void)hipMemsetAsync(c->mkP, 0, (size_t)2 * 64 * (k + 1) * 8, c->stream);
+        const bool all = dev_alloc(c, c->mkZ, (size_t)2 * g.G * c->LD * 8, true) == hipSuccess &&
+                         dev_alloc(c, c->mkG, (size_t)2 * g.G * (k + 2) * 8, true) == hipSuccess &&
+                         dev_alloc(c, c->mkP, (size_t)2 * 64 * (k + 1) * 8, true) == hipSuccess &&
+                         dev_alloc(c, c->mkbar, (size_t)(128 + g.G) * sizeof(unsigned)) == hipSuccess &&
+                         dev_alloc(c, c->mkX, (size_t)2 * c->LD * 8) == hipSuccess && dev_alloc(c, c->mkT, (size_t)2 * c->LD * 8) == hipSuccess &&
+                         dev_alloc(c, c->objE, (size_t)ONCHIP_UNTIL_CAP * 256 * 8) == hipSuccess &&
+                         dev_alloc(c, c->objhist, (size_t)ONCHIP_UNTIL_CAP * 8) == hipSuccess &&
+                         dev_alloc(c, c->objdec, (size_t)ONCHIP_UNTIL_CAP * 8) == hipSuccess;
+        if (!all) {     // all nine or none: the next call starts from mkZ again
+            dev_release(c, c->mkZ); dev_release(c, c->mkG); dev_release(c, c->mkP); dev_release(c, c->mkbar); dev_release(c, c->mkX);
+            dev_release(c, c->mkT); dev_release(c, c->objE); dev_release(c, c->objhist); dev_release(c, c->objdec);
+            return false;
+        }
     }
-    if (!c->mkG || !c->mkP || !c->mkbar || !c->mkX || !c->mkT || !c->objE || !c->objhist || !c->objdec) return false;
-    if (!c->Wsafe && hipMalloc((void**)&c->Wsafe, (size_t)k * c->ldw * 8) != hipSuccess) { c->Wsafe = nullptr; return false; }
-    if (!c->Tsafe && hipMalloc((void**)&c->Tsafe, (size_t)k * c->LD * 8) != hipSuccess) { c->Tsafe = nullptr; return false; }
+    if (dev_ensure(c, c->Wsafe, (size_t)k * c->ldw * 8) != hipSuccess || dev_ensure(c, c->Tsafe, (size_t)k * c->LD * 8) != hipSuccess) return false;
     (void)hipMemsetAsync(c->mkbar, 0, (size_t)(128 + g.G) * sizeof(unsigned), c->stream);
     OnchipArgs a{};
     a.X = c->X; a.ldx = c->ldx; a.n = (int)c->n; a.d = (int)c->d; a.LD = (int)c->LD; a.k = k;
@@ -1967,7 +1980,7 @@ bool enqueue_onchip(rri_ctx* c, Cursor cur) {
     a.p = kparams(c); a.st = c->st;
     a.dbg = nullptr;
     if (getenv("RRI_ONCHIP_TIMING")) {           // diagnostics: per-section ticks of the last launch, printed at the next one
-        static long long* dbg = nullptr;
+        static long long* dbg = nullptr;     // no handle's buffer: it lives as long as the process and is never freed
         if (!dbg && hipMalloc((void**)&dbg, 32 * sizeof(long long)) != hipSuccess) dbg = nullptr;
         if (dbg) {
             long long h[32];
@@ -2279,90 +2292,54 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     c->red_elems = round_up(std::max<i64>(c->LD + (i64)GRAM_SLICES * (k + 2), weighted ? 2 * c->LD + 2 : 0), 4);
 
     const size_t f8 = sizeof(double);
-    const size_t es_x = c->es;
-    CR(hipMalloc((void**)&c->W, (size_t)k * c->ldw * f8));
-    CR(hipMalloc((void**)&c->T, (size_t)k * c->LD * f8));
-    CR(hipMemsetAsync(c->T, 0, (size_t)k * c->LD * f8, c->stream));
-    CR(hipMalloc((void**)&c->Ypart, (size_t)c->npanels * n * f8));
-    CR(hipMemsetAsync(c->Ypart, 0, (size_t)c->npanels * n * f8, c->stream));
-    CR(hipMalloc((void**)&c->Zpart, (size_t)c->nrb * c->LD * f8));
-    CR(hipMemsetAsync(c->Zpart, 0, (size_t)c->nrb * c->LD * f8, c->stream));
+    CR(dev_alloc(c, c->W, (size_t)k * c->ldw * f8));
+    CR(dev_alloc(c, c->T, (size_t)k * c->LD * f8, true));
+    CR(dev_alloc(c, c->Ypart, (size_t)c->npanels * n * f8, true));
+    CR(dev_alloc(c, c->Zpart, (size_t)c->nrb * c->LD * f8, true));
     const size_t grows = (size_t)std::max(c->nwb, c->nrb);      // k_wcol leaves a row per 64-row tile, the fused pass one per row block
     c->gpart_n = c->nwb;
     c->xy_stride = (int)std::max<size_t>(std::max<size_t>(grows, (size_t)c->nwb * WCOL_TILES), (size_t)std::max(c->n_cu, 1));   // the on-chip sweep leaves one per CU
-    CR(hipMalloc((void**)&c->Gpart, grows * (k + 2) * sizeof(double)));
-    CR(hipMemsetAsync(c->Gpart, 0, grows * (k + 2) * sizeof(double), c->stream));
-    CR(hipMalloc((void**)&c->XYpart, (size_t)k * c->xy_stride * f8));
-    CR(hipMemsetAsync(c->XYpart, 0, (size_t)k * c->xy_stride * f8, c->stream));
-    CR(hipMalloc((void**)&c->red, (size_t)c->red_elems * f8));
-    CR(hipMemsetAsync(c->red, 0, (size_t)c->red_elems * f8, c->stream));
-    c->own_red = true;
-    CR(hipMalloc((void**)&c->xraw, (size_t)c->LD * f8));
-    CR(hipMemsetAsync(c->xraw, 0, (size_t)c->LD * f8, c->stream));
+    CR(dev_alloc(c, c->Gpart, grows * (k + 2) * f8, true));
+    CR(dev_alloc(c, c->XYpart, (size_t)k * c->xy_stride * f8, true));
+    CR(dev_alloc(c, c->red, (size_t)c->red_elems * f8, true));
+    CR(dev_alloc(c, c->xraw, (size_t)c->LD * f8, true));
     const size_t ttn = (size_t)std::max(c->nsplit, c->ntb32);   // k_tgram: nsplit column slices; k_trow_small: one per 32 columns
     c->ttpart_n = c->nsplit;
-    CR(hipMalloc((void**)&c->Ttpart, ttn * k * f8));
-    CR(hipMemsetAsync(c->Ttpart, 0, ttn * k * f8, c->stream));
-    CR(hipMalloc((void**)&c->Qt, (size_t)k * c->ldw * f8));
+    CR(dev_alloc(c, c->Ttpart, ttn * k * f8, true));
+    CR(dev_alloc(c, c->Qt, (size_t)k * c->ldw * f8));
     const size_t ntp = (size_t)std::max(c->ntb, c->ntb32);
-    CR(hipMalloc((void**)&c->tpart, ntp * sizeof(double)));
-    CR(hipMemsetAsync(c->tpart, 0, ntp * sizeof(double), c->stream));
-    CR(hipMalloc((void**)&c->tpart_idx, ntp * sizeof(i64)));
-    CR(hipMalloc((void**)&c->normpart, 256 * 3 * sizeof(double)));
-    CR(hipMalloc((void**)&c->objbuf, (size_t)(2 * k * k + k) * sizeof(double)));
-    CR(hipMalloc((void**)&c->dtmp, 16 * sizeof(double)));
-    CR(hipMalloc((void**)&c->itmp, 16 * sizeof(i64)));
+    CR(dev_alloc(c, c->tpart, ntp * f8, true));
+    CR(dev_alloc(c, c->tpart_idx, ntp * sizeof(i64)));
+    CR(dev_alloc(c, c->normpart, 256 * 3 * f8));
+    CR(dev_alloc(c, c->objbuf, (size_t)(2 * k * k + k) * f8));
+    CR(dev_alloc(c, c->dtmp, 16 * f8));
+    CR(dev_alloc(c, c->itmp, 16 * sizeof(i64)));
+    // The flavours' own buffers, each in the order its flavour has always asked for them (calibrate_rot: the speed of a
+    // read-modify-write pass belongs to the buffer's placement).  The stored residual first: k_resid writes the d real columns only
+    // and the passes stream all LD, so the pad columns must hold zeros (recycled memory there once held NaN patterns, which
+    // fmax(numer, 0) turned into zero rows of W)
+    const bool keeps_resid = explicit_resid || (weighted && !c->sparse);
+    if (keeps_resid) CR(dev_alloc(c, c->E, (size_t)n * c->LD * c->es, c->LD != d));
     if (weighted) {
-        const i64 zn = std::max<i64>(c->LD, n);
-        if (!c->sparse) {
-            CR(hipMalloc(&c->E, (size_t)n * c->LD * es_x));
-            // k_resid writes the d real columns only; the passes stream all LD: the pad columns must hold zeros
-            // (recycled memory there once held NaN patterns, which fmax(numer, 0) turned into zero rows of W)
-            if (c->LD != d) CR(hipMemsetAsync(c->E, 0, (size_t)n * c->LD * es_x, c->stream));
-        }
-        CR(hipMalloc((void**)&c->Y2part, (size_t)c->npanels * n * f8));
-        CR(hipMemsetAsync(c->Y2part, 0, (size_t)c->npanels * n * f8, c->stream));
-        CR(hipMalloc((void**)&c->Z2part, (size_t)c->nrb * c->LD * f8));
-        CR(hipMemsetAsync(c->Z2part, 0, (size_t)c->nrb * c->LD * f8, c->stream));
+        CR(dev_alloc(c, c->Y2part, (size_t)c->npanels * n * f8, true));
+        CR(dev_alloc(c, c->Z2part, (size_t)c->nrb * c->LD * f8, true));
         if (!c->sparse) {
             c->cpart_rows = (int)std::max<i64>(256, (n + 2047) / 2048);
-            CR(hipMalloc((void**)&c->Cpart, (size_t)c->cpart_rows * c->LD * f8));
-            CR(hipMemsetAsync(c->Cpart, 0, (size_t)c->cpart_rows * c->LD * f8, c->stream));
-            CR(hipMalloc((void**)&c->N2part, (size_t)c->cpart_rows * c->LD * f8));
-            CR(hipMemsetAsync(c->N2part, 0, (size_t)c->cpart_rows * c->LD * f8, c->stream));
+            CR(dev_alloc(c, c->Cpart, (size_t)c->cpart_rows * c->LD * f8, true));
+            CR(dev_alloc(c, c->N2part, (size_t)c->cpart_rows * c->LD * f8, true));
         }
-        CR(hipMalloc((void**)&c->dtv, (size_t)c->LD * f8));
-        CR(hipMalloc((void**)&c->dwv, (size_t)n * f8));
-        CR(hipMalloc((void**)&c->wold, (size_t)n * f8));
-        CR(hipMalloc((void**)&c->zeros, (size_t)zn * f8));
-        CR(hipMemsetAsync(c->zeros, 0, (size_t)zn * f8, c->stream));
-        CR(hipMemsetAsync(c->dtv, 0, (size_t)c->LD * f8, c->stream));
-        if (c->sparse) {
-            CR(hipMalloc((void**)&c->sp_Tt, (size_t)d * c->kp * f8));
-            CR(hipMemsetAsync(c->sp_Tt, 0, (size_t)d * c->kp * f8, c->stream));
-        }
+        CR(dev_alloc(c, c->dtv, (size_t)c->LD * f8, true));
     }
-    if (sparse_x) {
-        CR(hipMalloc((void**)&c->sp_Tt, (size_t)d * c->kp * f8));
-        CR(hipMemsetAsync(c->sp_Tt, 0, (size_t)d * c->kp * f8, c->stream));
-    }
-    if (explicit_resid) {
-        const i64 zn = std::max<i64>(c->LD, n);
-        CR(hipMalloc(&c->E, (size_t)n * c->LD * es_x));
-        if (c->LD != d) CR(hipMemsetAsync(c->E, 0, (size_t)n * c->LD * es_x, c->stream));   // pad columns stay zero
-        CR(hipMalloc((void**)&c->dwv, (size_t)n * f8));
-        CR(hipMemsetAsync(c->dwv, 0, (size_t)n * f8, c->stream));
-        CR(hipMalloc((void**)&c->told, (size_t)c->LD * f8));
-        CR(hipMemsetAsync(c->told, 0, (size_t)c->LD * f8, c->stream));
-        CR(hipMalloc((void**)&c->zeros, (size_t)zn * f8));
-        CR(hipMemsetAsync(c->zeros, 0, (size_t)zn * f8, c->stream));
-    }
-    CR(hipMalloc((void**)&c->st, sizeof(DevState)));
-    CR(hipMemsetAsync(c->st, 0, sizeof(DevState), c->stream));
+    if (weighted || explicit_resid) CR(dev_alloc(c, c->dwv, (size_t)n * f8, explicit_resid));
+    if (weighted) CR(dev_alloc(c, c->wold, (size_t)n * f8));
+    if (explicit_resid) CR(dev_alloc(c, c->told, (size_t)c->LD * f8, true));
+    if (weighted || explicit_resid) CR(dev_alloc(c, c->zeros, (size_t)std::max<i64>(c->LD, n) * f8, true));
+    if (c->sparse) CR(dev_alloc(c, c->sp_Tt, (size_t)d * c->kp * f8, true));
+    CR(dev_alloc(c, c->st, sizeof(DevState), true));
     // opt in to large dynamic LDS where a kernel needs it
-    if (dtype == RRI_F32) CR(LaunchX<float>::set_attrs());
-    else if (dtype == RRI_F64) CR(LaunchX<double>::set_attrs());
-    else CR(LaunchX<_Float16>::set_attrs());
+    if (dtype == RRI_F32) CR(LaunchX<float>::set_attrs(c));
+    else if (dtype == RRI_F64) CR(LaunchX<double>::set_attrs(c));
+    else CR(LaunchX<_Float16>::set_attrs(c));
     CR(hipStreamSynchronize(c->stream));
 #undef CR
     *out = c;
@@ -2373,18 +2350,10 @@ rri_status rri_destroy(rri_ctx* c) {
     if (!c) return RRI_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->own_X) (void)hipFree(c->X);
-    if (c->own_M) (void)hipFree(c->M);
-    void* bufs[] = {c->E, (void*)c->W, (void*)c->T, (void*)c->Wprev, (void*)c->Tprev,                     (void*)c->Ypart, (void*)c->Zpart, (void*)c->xraw, (void*)c->Ttpart, (void*)c->Gpart,
-                    (void*)c->tpart, (void*)c->tpart_idx, (void*)c->rowobj, (void*)c->rowpos, (void*)c->normpart,
-                    (void*)c->dtmp, (void*)c->itmp, (void*)c->resetT, (void*)c->resetW, (void*)c->st, (void*)c->Y2part,
-                    (void*)c->Z2part, (void*)c->Mbits, (void*)c->Qt, (void*)c->dtv, (void*)c->dwv, (void*)c->wold, (void*)c->zeros,
-                    (void*)c->XYpart, (void*)c->objbuf, (void*)c->told, (void*)c->Cpart, (void*)c->N2part, (void*)c->Mcols, (void*)c->Gfull, (void*)c->Wsweep0, (void*)c->wsum_part, (void*)c->wsums, (void*)c->ctail, (void*)c->cand, (void*)c->mkZ, (void*)c->mkG, (void*)c->mkP, (void*)c->mkX, (void*)c->mkT, (void*)c->objE, (void*)c->objhist, (void*)c->objdec, (void*)c->mkbar, (void*)c->Wsafe, (void*)c->Tsafe, (void*)c->sp_rowptr, (void*)c->sp_col, c->sp_x, c->sp_e, (void*)c->sp_Tt, (void*)c->spx_work, (void*)c->rowhat,
-                    (void*)c->sp[0].segptr, (void*)c->sp[0].idx, c->sp[0].val, (void*)c->sp[0].perm, (void*)c->sp[0].work,
-                    (void*)c->sp[1].segptr, (void*)c->sp[1].idx, c->sp[1].val, (void*)c->sp[1].perm, (void*)c->sp[1].work};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (c->own_red && c->red) (void)hipFree(c->red);
+    for (const auto& o : c->owned) {
+        (void)hipFree(o.p);
+        dev_count(-1, o.bytes);
+    }
     for (int i = 0; i < 4; ++i)
         for (auto& tl : c->timed[i]) { (void)hipEventDestroy(tl.a); (void)hipEventDestroy(tl.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
@@ -2398,12 +2367,7 @@ rri_status rri_upload_X(rri_ctx* c, const void* host, int64_t ld, int32_t host_d
     CHECK_CTX(c);
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->X && !c->own_X) c->X = nullptr;
-    if (!c->X) {
-        HIPCHK(c, hipMalloc(&c->X, (size_t)c->n * c->LD * c->es));
-        c->own_X = true;
-        if (c->LD != c->d) HIPCHK(c, hipMemsetAsync(c->X, 0, (size_t)c->n * c->LD * c->es, c->stream));
-    }
+    if (!dev_owned(c, &c->X)) HIPCHK(c, dev_alloc(c, c->X, (size_t)c->n * c->LD * c->es, c->LD != c->d));   // (none yet, or a bound one)
     c->ldx = c->LD;
     c->store_err[0] = c->store_err[1] = 0.0;
     rri_status s = to_device(c, host, ld, host_dtype, c->X, c->ldx, c->n, c->d, c->dtype);
@@ -2418,12 +2382,7 @@ rri_status rri_upload_mask(rri_ctx* c, const void* host, int64_t ld, int32_t hos
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     if (!c->weighted) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=1");
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->M && !c->own_M) c->M = nullptr;
-    if (!c->M) {
-        HIPCHK(c, hipMalloc(&c->M, (size_t)c->n * c->LD * c->es));
-        c->own_M = true;
-        if (c->LD != c->d) HIPCHK(c, hipMemsetAsync(c->M, 0, (size_t)c->n * c->LD * c->es, c->stream));
-    }
+    if (!dev_owned(c, &c->M)) HIPCHK(c, dev_alloc(c, c->M, (size_t)c->n * c->LD * c->es, c->LD != c->d));   // (none yet, or a bound one)
     c->ldm = c->LD;
     rri_status s = to_device(c, host, ld, host_dtype, c->M, c->ldm, c->n, c->d, c->dtype);
     if (s == RRI_OK) {
@@ -2431,17 +2390,16 @@ rri_status rri_upload_mask(rri_ctx* c, const void* host, int64_t ld, int32_t hos
         changed(c, CH_M);
         DISPATCH(c, s = L::pack_mask_if_binary(c));
         if (s != RRI_OK) return fail(c, s, "packing the mask failed");
-        if (c->Mbits && c->own_M) { (void)hipFree(c->M); c->M = nullptr; c->own_M = false; }   // bits replace it
+        if (c->Mbits) dev_release(c, c->M);   // bits replace it
     }
     return s;
 }
 
 namespace {
 struct CsrDev {   // device copies of the host CSR arrays of one call
-    i64* indptr = nullptr;
-    int* indices = nullptr;
-    void* data = nullptr;
-    ~CsrDev() { (void)hipFree(indptr); (void)hipFree(indices); (void)hipFree(data); }
+    DevTmp indptr, indices, data;
+    const i64* ip() const { return (const i64*)indptr.p; }
+    const int* ix() const { return (const int*)indices.p; }
 };
 rri_status csr_to_device(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data, int64_t nnz,
                          int32_t data_dtype, CsrDev& out) {
@@ -2453,13 +2411,13 @@ rri_status csr_to_device(rri_ctx* c, const int64_t* indptr, const int32_t* indic
     for (i64 p = 0; p < nnz; ++p)
         if (indices[p] < 0 || indices[p] >= c->d) return fail(c, RRI_ERR_INVALID, "column index out of range at %lld", p);
     const size_t ds = dtype_size(data_dtype);
-    HIPCHK(c, hipMalloc((void**)&out.indptr, (size_t)(c->n + 1) * sizeof(i64)));
-    HIPCHK(c, hipMalloc((void**)&out.indices, (size_t)std::max<i64>(nnz, 1) * sizeof(int)));
-    HIPCHK(c, hipMalloc(&out.data, (size_t)std::max<i64>(nnz, 1) * ds));
-    HIPCHK(c, hipMemcpyAsync(out.indptr, indptr, (size_t)(c->n + 1) * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, out.indptr.alloc((size_t)(c->n + 1) * sizeof(i64)));
+    HIPCHK(c, out.indices.alloc((size_t)std::max<i64>(nnz, 1) * sizeof(int)));
+    HIPCHK(c, out.data.alloc((size_t)std::max<i64>(nnz, 1) * ds));
+    HIPCHK(c, hipMemcpyAsync(out.indptr.p, indptr, (size_t)(c->n + 1) * sizeof(i64), hipMemcpyHostToDevice, c->stream));
     if (nnz > 0) {
-        HIPCHK(c, hipMemcpyAsync(out.indices, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(out.data, data, (size_t)nnz * ds, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out.indices.p, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out.data.p, data, (size_t)nnz * ds, hipMemcpyHostToDevice, c->stream));
     }
     return RRI_OK;
 }
@@ -2478,20 +2436,16 @@ rri_status rri_upload_X_csr(rri_ctx* c, const int64_t* indptr, const int32_t* in
     CsrDev dv;
     rri_status s = csr_to_device(c, indptr, indices, data, nnz, data_dtype, dv);
     if (s != RRI_OK) return s;
-    if (c->X && !c->own_X) c->X = nullptr;
-    if (!c->X) {
-        HIPCHK(c, hipMalloc(&c->X, (size_t)c->n * c->LD * c->es));
-        c->own_X = true;
-    }
+    if (!dev_owned(c, &c->X)) HIPCHK(c, dev_alloc(c, c->X, (size_t)c->n * c->LD * c->es));   // (none yet, or a bound one)
     c->ldx = c->LD;
     HIPCHK(c, hipMemsetAsync(c->X, 0, (size_t)c->n * c->LD * c->es, c->stream));
     const unsigned nb = (unsigned)((c->n + 3) / 4);
     if (c->dtype == RRI_F32) {
-        if (data_dtype == RRI_F32) hipLaunchKernelGGL((k_csr_scatter<float, float>), dim3(nb), dim3(256), 0, c->stream, dv.indptr, dv.indices, (const float*)dv.data, c->n, (float*)c->X, c->ldx);
-        else hipLaunchKernelGGL((k_csr_scatter<double, float>), dim3(nb), dim3(256), 0, c->stream, dv.indptr, dv.indices, (const double*)dv.data, c->n, (float*)c->X, c->ldx);
+        if (data_dtype == RRI_F32) hipLaunchKernelGGL((k_csr_scatter<float, float>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const float*)dv.data.p, c->n, (float*)c->X, c->ldx);
+        else hipLaunchKernelGGL((k_csr_scatter<double, float>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const double*)dv.data.p, c->n, (float*)c->X, c->ldx);
     } else {
-        if (data_dtype == RRI_F32) hipLaunchKernelGGL((k_csr_scatter<float, double>), dim3(nb), dim3(256), 0, c->stream, dv.indptr, dv.indices, (const float*)dv.data, c->n, (double*)c->X, c->ldx);
-        else hipLaunchKernelGGL((k_csr_scatter<double, double>), dim3(nb), dim3(256), 0, c->stream, dv.indptr, dv.indices, (const double*)dv.data, c->n, (double*)c->X, c->ldx);
+        if (data_dtype == RRI_F32) hipLaunchKernelGGL((k_csr_scatter<float, double>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const float*)dv.data.p, c->n, (double*)c->X, c->ldx);
+        else hipLaunchKernelGGL((k_csr_scatter<double, double>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const double*)dv.data.p, c->n, (double*)c->X, c->ldx);
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_X = true;
@@ -2550,9 +2504,9 @@ static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int
                         hipLaunchKernelGGL((k_sp_permute<typename L::Elem>), dim3(2048), dim3(256), 0, c->stream,
                                            (const typename L::Elem*)c->sp_x, (const int*)c->sp[w].perm, c->sp[w].count,
                                            (typename L::Elem*)c->sp[w].val));
-    if (c->spx_work) { (void)hipFree(c->spx_work); c->spx_work = nullptr; }
+    dev_release(c, c->spx_work);
     const int nw0 = c->sp[0].nwork, nw1 = c->sp[1].nwork;
-    HIPCHK(c, hipMalloc((void**)&c->spx_work, (size_t)std::max(1, nw0 + nw1) * sizeof(SpWork)));
+    HIPCHK(c, dev_alloc(c, c->spx_work, (size_t)std::max(1, nw0 + nw1) * sizeof(SpWork)));
     if (nw0 > 0) HIPCHK(c, hipMemcpyAsync(c->spx_work, c->sp[0].work, (size_t)nw0 * sizeof(SpWork), hipMemcpyDeviceToDevice, c->stream));
     if (nw1 > 0) HIPCHK(c, hipMemcpyAsync(c->spx_work + nw0, c->sp[1].work, (size_t)nw1 * sizeof(SpWork), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2571,20 +2525,17 @@ rri_status rri_upload_mask_csr_pattern(rri_ctx* c, const int64_t* indptr, const 
     CsrDev dv;
     rri_status s = csr_to_device(c, indptr, indices, data, nnz, data_dtype, dv);
     if (s != RRI_OK) return s;
-    if (c->M && c->own_M) (void)hipFree(c->M);
-    c->M = nullptr;
-    c->own_M = false;
+    dev_release(c, c->M);
     c->ldm = c->LD;
-    if (c->Mbits) { (void)hipFree(c->Mbits); c->Mbits = nullptr; }
-    if (c->Mcols) { (void)hipFree(c->Mcols); c->Mcols = nullptr; }
+    dev_release(c, c->Mbits);
+    dev_release(c, c->Mcols);
     c->mcols_tried = false;
     c->ldb = (c->LD + 3) / 4;
     const size_t words = (size_t)((c->n + 7) / 8) * c->ldb;
-    HIPCHK(c, hipMalloc((void**)&c->Mbits, words * sizeof(unsigned)));
-    HIPCHK(c, hipMemsetAsync(c->Mbits, 0, words * sizeof(unsigned), c->stream));
+    HIPCHK(c, dev_alloc(c, c->Mbits, words * sizeof(unsigned), true));
     const unsigned nb = (unsigned)((c->n + 3) / 4);
-    if (data_dtype == RRI_F32) hipLaunchKernelGGL((k_csr_pattern_bits<float>), dim3(nb), dim3(256), 0, c->stream, dv.indptr, dv.indices, (const float*)dv.data, c->n, c->Mbits, c->ldb);
-    else hipLaunchKernelGGL((k_csr_pattern_bits<double>), dim3(nb), dim3(256), 0, c->stream, dv.indptr, dv.indices, (const double*)dv.data, c->n, c->Mbits, c->ldb);
+    if (data_dtype == RRI_F32) hipLaunchKernelGGL((k_csr_pattern_bits<float>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const float*)dv.data.p, c->n, c->Mbits, c->ldb);
+    else hipLaunchKernelGGL((k_csr_pattern_bits<double>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const double*)dv.data.p, c->n, c->Mbits, c->ldb);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_M = true;
     changed(c, CH_M);
@@ -2600,28 +2551,21 @@ rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indi
                           CsrDev& dv, int target_items) {
     i64 longest_row = 0;
     for (i64 r = 0; r < c->n; ++r) longest_row = std::max<i64>(longest_row, (i64)(indptr[r + 1] - indptr[r]));
-    void* old[] = {(void*)c->sp_rowptr, (void*)c->sp_col, c->sp_x, c->sp_e};
-    for (void* b : old)
-        if (b) (void)hipFree(b);
-    c->sp_rowptr = dv.indptr; dv.indptr = nullptr;
-    c->sp_col = dv.indices; dv.indices = nullptr;
-    c->sp_x = nullptr; c->sp_e = nullptr;
-    const size_t cnt = (size_t)std::max<i64>(nnz, 1);
-    HIPCHK(c, hipMalloc(&c->sp_x, cnt * c->es));
+    dev_release(c, c->sp_rowptr); dev_release(c, c->sp_col); dev_release(c, c->sp_x); dev_release(c, c->sp_e);
+    dev_adopt(c, c->sp_rowptr, dv.indptr);     // from here on they are the handle's, whatever fails below
+    dev_adopt(c, c->sp_col, dv.indices);
+    HIPCHK(c, dev_alloc(c, c->sp_x, (size_t)std::max<i64>(nnz, 1) * c->es));
     if (nnz > 0) {   // values -> storage type (dv.data holds them in the caller's type)
         const bool hf = data_dtype == RRI_F32, df = c->dtype == RRI_F32;
-        if (hf && df) launch_convert<float, float, false>(c, dv.data, nnz, c->sp_x, nnz, 1, nnz);
-        else if (hf) launch_convert<float, double, false>(c, dv.data, nnz, c->sp_x, nnz, 1, nnz);
-        else if (df) launch_convert<double, float, false>(c, dv.data, nnz, c->sp_x, nnz, 1, nnz);
-        else launch_convert<double, double, false>(c, dv.data, nnz, c->sp_x, nnz, 1, nnz);
+        if (hf && df) launch_convert<float, float, false>(c, dv.data.p, nnz, c->sp_x, nnz, 1, nnz);
+        else if (hf) launch_convert<float, double, false>(c, dv.data.p, nnz, c->sp_x, nnz, 1, nnz);
+        else if (df) launch_convert<double, float, false>(c, dv.data.p, nnz, c->sp_x, nnz, 1, nnz);
+        else launch_convert<double, double, false>(c, dv.data.p, nnz, c->sp_x, nnz, 1, nnz);
     }
     // the two blocked copies: counting sort on the host, stable, so offsets ascend inside a segment
     for (int w = 0; w < 2; ++w) {
         rri_ctx::SpCopy& cp = c->sp[w];
-        void* oldc[] = {(void*)cp.segptr, (void*)cp.idx, cp.val, (void*)cp.perm, (void*)cp.work};
-        for (void* b : oldc)
-            if (b) (void)hipFree(b);
-        cp.segptr = nullptr; cp.idx = nullptr; cp.val = nullptr; cp.perm = nullptr; cp.work = nullptr;
+        dev_release(c, cp.segptr); dev_release(c, cp.idx); dev_release(c, cp.val); dev_release(c, cp.perm); dev_release(c, cp.work);
         const i64 nseg = cp.nseg, stride = nseg + 1;
         std::vector<i64> sp((size_t)cp.nblk * stride, 0);
         // count: entry (r, j) lives in block (gather index / bw), segment (the other index)
@@ -2696,12 +2640,11 @@ rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indi
         // lanes per segment: 4 quads of 4 entries per lane and iteration
         const i64 avg = nnz / std::max<i64>(1, (i64)cp.nblk * nseg);
         cp.lps = avg >= 768 ? 64 : avg >= 384 ? 32 : avg >= 192 ? 16 : 8;
-        HIPCHK(c, hipMalloc((void**)&cp.segptr, sp.size() * sizeof(i64)));
-        HIPCHK(c, hipMalloc((void**)&cp.idx, cntp * sizeof(unsigned short)));
-        HIPCHK(c, hipMalloc(&cp.val, cntp * c->es));
-        HIPCHK(c, hipMemsetAsync(cp.val, 0, cntp * c->es, c->stream));
-        HIPCHK(c, hipMalloc((void**)&cp.perm, cntp * sizeof(int)));
-        HIPCHK(c, hipMalloc((void**)&cp.work, std::max<size_t>(1, work.size()) * sizeof(SpWork)));
+        HIPCHK(c, dev_alloc(c, cp.segptr, sp.size() * sizeof(i64)));
+        HIPCHK(c, dev_alloc(c, cp.idx, cntp * sizeof(unsigned short)));
+        HIPCHK(c, dev_alloc(c, cp.val, cntp * c->es, true));
+        HIPCHK(c, dev_alloc(c, cp.perm, cntp * sizeof(int)));
+        HIPCHK(c, dev_alloc(c, cp.work, std::max<size_t>(1, work.size()) * sizeof(SpWork)));
         HIPCHK(c, hipMemcpyAsync(cp.segptr, sp.data(), sp.size() * sizeof(i64), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(cp.idx, bidx.data(), cntp * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(cp.perm, perm.data(), cntp * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -2733,7 +2676,7 @@ rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int3
     const int target_items = std::max(1, c->n_cu);
     s = build_sp_store(c, indptr, indices, nnz, data_dtype, dv, target_items);
     if (s != RRI_OK) return s;
-    HIPCHK(c, hipMalloc(&c->sp_e, (size_t)std::max<i64>(nnz, 1) * c->es));
+    HIPCHK(c, dev_alloc(c, c->sp_e, (size_t)std::max<i64>(nnz, 1) * c->es));
     c->have_X = true;
     c->have_M = true;
     changed(c, CH_X | CH_M);
@@ -2756,9 +2699,8 @@ rri_status rri_bind_X_device(rri_ctx* c, const void* dev, int64_t ld) {
     if (c->d % c->VN) return fail(c, RRI_ERR_INVALID, "binding device X needs d %% %d == 0 (no pad columns)", c->VN);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());   // the memory may have been produced on another stream a moment ago
-    if (c->X && c->own_X) (void)hipFree(c->X);
+    dev_release(c, c->X);
     c->X = const_cast<void*>(dev);
-    c->own_X = false;
     c->ldx = ld;
     c->store_err[0] = c->store_err[1] = 0.0;   // bound memory is taken as it is: nothing was rounded here
     c->have_X = true;
@@ -2776,9 +2718,8 @@ rri_status rri_bind_mask_device(rri_ctx* c, const void* dev, int64_t ld) {
     if (c->d % c->VN) return fail(c, RRI_ERR_INVALID, "binding a device mask needs d %% %d == 0", c->VN);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());   // the mask is read at once (bit-packing): it must be complete
-    if (c->M && c->own_M) (void)hipFree(c->M);
+    dev_release(c, c->M);
     c->M = const_cast<void*>(dev);
-    c->own_M = false;
     c->ldm = ld;
     c->have_M = true;
     changed(c, CH_M);
@@ -2974,7 +2915,7 @@ rri_status rri_apply_reset_max_resid(rri_ctx* c, int32_t t, int64_t* row_chosen)
     CHECK_CTX(c);
     if (t < 0 || t >= c->k) return fail(c, RRI_ERR_INVALID, "topic out of range");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->rowpos) HIPCHK(c, hipMalloc((void**)&c->rowpos, (size_t)c->n * sizeof(double)));
+    HIPCHK(c, dev_ensure(c, c->rowpos, (size_t)c->n * sizeof(double)));
     HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
     DISPATCH_RO(c, L::resid(c, false, false, nullptr, c->rowpos));
     hipLaunchKernelGGL(k_vec_sum_argmax, dim3(1), dim3(1024), 0, c->stream, (const double*)c->rowpos, c->n,
@@ -3022,8 +2963,8 @@ rri_status rri_apply_reset_vectors(rri_ctx* c, int32_t t, const double* T_row, c
     CHECK_CTX(c);
     if (t < 0 || t >= c->k) return fail(c, RRI_ERR_INVALID, "topic out of range");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->resetT) HIPCHK(c, hipMalloc((void**)&c->resetT, (size_t)c->d * sizeof(double)));
-    if (!c->resetW) HIPCHK(c, hipMalloc((void**)&c->resetW, (size_t)c->n * sizeof(double)));
+    HIPCHK(c, dev_ensure(c, c->resetT, (size_t)c->d * sizeof(double)));
+    HIPCHK(c, dev_ensure(c, c->resetW, (size_t)c->n * sizeof(double)));
     if (T_row) HIPCHK(c, hipMemcpyAsync(c->resetT, T_row, (size_t)c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (W_col) HIPCHK(c, hipMemcpyAsync(c->resetW, W_col, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     LK::set_row_col(c, t, T_row ? c->resetT : nullptr, W_col ? c->resetW : nullptr);
@@ -3136,7 +3077,7 @@ static rri_status objective_terms(rri_ctx* c, double out[3], double* tn) {
     if (!c->have_X || !c->have_W || !c->have_T) return fail(c, RRI_ERR_INVALID, "X, W, T must be set");
     if (c->weighted && !c->have_M) return fail(c, RRI_ERR_INVALID, "weighted handle without a mask");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->rowobj) HIPCHK(c, hipMalloc((void**)&c->rowobj, (size_t)c->n * sizeof(double)));
+    HIPCHK(c, dev_ensure(c, c->rowobj, (size_t)c->n * sizeof(double)));
     if (c->weighted) {
         // the objective needs M .* (X - W T) -- which is the maintained residual: store it while it is being
         // computed, and the sweep that follows skips its own rebuild (nmf() asks for the objective after
@@ -3195,7 +3136,7 @@ static rri_status objective_terms(rri_ctx* c, double out[3], double* tn) {
         // X on CSR, without the cross terms of a complete sweep: ||X - W T||^2 = sum_pattern r^2 + (<W^T W, T T^T> -
         // sum_pattern (W T)_ij^2) -- outside the pattern the residual is -(W T)_ij, whose squares are the Gram term less the
         // pattern's share
-        if (!c->rowhat) HIPCHK(c, hipMalloc((void**)&c->rowhat, (size_t)c->n * sizeof(double)));
+        HIPCHK(c, dev_ensure(c, c->rowhat, (size_t)c->n * sizeof(double)));
         DISPATCH(c, L::sp_resid(c, false, c->rowobj, nullptr, c->rowhat));
         const int k = c->k;
         double* gw = c->objbuf;
@@ -3299,10 +3240,11 @@ rri_status rri_masked_rmse(rri_ctx* c, const int64_t* ij, const double* vals, in
     double s = 0.0;
     hipError_t e = hipSuccess;
     if (count > 0 && !bad) {
-        i64* dij = nullptr;
-        double* dv = nullptr;
-        e = hipMalloc((void**)&dij, (size_t)count * 2 * sizeof(i64));
-        if (e == hipSuccess) e = hipMalloc((void**)&dv, (size_t)count * sizeof(double));
+        DevTmp tij, tv;
+        e = tij.alloc((size_t)count * 2 * sizeof(i64));
+        if (e == hipSuccess) e = tv.alloc((size_t)count * sizeof(double));
+        i64* dij = (i64*)tij.p;
+        double* dv = (double*)tv.p;
         if (e == hipSuccess) e = hipMemcpyAsync(dij, ij, (size_t)count * 2 * sizeof(i64), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(dv, vals, (size_t)count * sizeof(double), hipMemcpyHostToDevice, c->stream);
         double h[256];
@@ -3311,8 +3253,6 @@ rri_status rri_masked_rmse(rri_ctx* c, const int64_t* ij, const double* vals, in
             e = hipMemcpyAsync(h, c->normpart, sizeof h, hipMemcpyDeviceToHost, c->stream);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (dij) (void)hipFree(dij);
-        if (dv) (void)hipFree(dv);
         if (e == hipSuccess)
             for (int b = 0; b < 256; ++b) s += h[b];
     }
@@ -3336,8 +3276,8 @@ rri_status rri_masked_rmse(rri_ctx* c, const int64_t* ij, const double* vals, in
 rri_status rri_snapshot(rri_ctx* c) {
     CHECK_CTX(c);
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->Wprev) HIPCHK(c, hipMalloc((void**)&c->Wprev, (size_t)c->k * c->ldw * 8));
-    if (!c->Tprev) HIPCHK(c, hipMalloc((void**)&c->Tprev, (size_t)c->k * c->LD * 8));
+    HIPCHK(c, dev_ensure(c, c->Wprev, (size_t)c->k * c->ldw * 8));
+    HIPCHK(c, dev_ensure(c, c->Tprev, (size_t)c->k * c->LD * 8));
     HIPCHK(c, hipMemcpyAsync(c->Wprev, c->W, (size_t)c->k * c->ldw * 8, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->Tprev, c->T, (size_t)c->k * c->LD * 8, hipMemcpyDeviceToDevice, c->stream));
     return RRI_OK;
@@ -3718,7 +3658,7 @@ rri_status rri_scale_X(rri_ctx* c, const double* col_scale, int32_t normalize_ro
     CHECK_CTX(c);
     REFUSE_F16(c, "rewriting X in place (a second rounding: preprocess on the host, X is then rounded once at upload)");
     if (c->weighted || !c->have_X || c->sparse_x) return fail(c, RRI_ERR_INVALID, "needs an unweighted handle with a dense X");
-    if (!c->own_X) return fail(c, RRI_ERR_INVALID, "X is bound caller memory: it is not rewritten in place");
+    if (!dev_owned(c, &c->X)) return fail(c, RRI_ERR_INVALID, "X is bound caller memory: it is not rewritten in place");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
     DevTmp sd, inv;
@@ -3838,9 +3778,8 @@ rri_status rri_bind_reduce_buffer(rri_ctx* c, void* dev_ptr, int64_t n_elems) {
     CHECK_CTX(c);
     if (!dev_ptr || n_elems < c->red_elems || ((uintptr_t)dev_ptr) % 16)
         return fail(c, RRI_ERR_INVALID, "reduce buffer needs >= %lld elements, 16-byte aligned", c->red_elems);
-    if (c->own_red && c->red) (void)hipFree(c->red);
+    dev_release(c, c->red);
     c->red = (double*)dev_ptr;
-    c->own_red = false;
     changed(c, CH_SCRATCH);
     return RRI_OK;
 }
@@ -3952,7 +3891,7 @@ rri_status rri_resid_row_argmax(rri_ctx* c, double* value, int64_t* local_row) {
     CHECK_CTX(c);
     if (!value || !local_row) return fail(c, RRI_ERR_INVALID, "NULL output");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->rowpos) HIPCHK(c, hipMalloc((void**)&c->rowpos, (size_t)c->n * sizeof(double)));
+    HIPCHK(c, dev_ensure(c, c->rowpos, (size_t)c->n * sizeof(double)));
     DISPATCH_RO(c, L::resid(c, false, false, nullptr, c->rowpos));
     hipLaunchKernelGGL(k_vec_sum_argmax, dim3(1), dim3(1024), 0, c->stream, (const double*)c->rowpos, c->n,
                        (double*)nullptr, c->itmp);
@@ -4058,12 +3997,9 @@ rri_status rri_attach_comm(rri_ctx* c, rri_comm* comm, int64_t row_offset, int64
     if (row_offset < 0 || n_global < row_offset + c->n) return fail(c, RRI_ERR_INVALID, "row block [%lld, %lld) outside 0..%lld", (long long)row_offset, (long long)(row_offset + c->n), (long long)n_global);
     if (comm->nccl && comm->device != c->device) return fail(c, RRI_ERR_INVALID, "communicator lives on device %d, handle on %d", comm->device, c->device);
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->ctail) {
-        HIPCHK(c, hipMalloc((void**)&c->ctail, 8 * sizeof(double)));
-        HIPCHK(c, hipMemsetAsync(c->ctail, 0, 8 * sizeof(double), c->stream));
-    }
-    if (c->cand) { (void)hipFree(c->cand); c->cand = nullptr; }
-    HIPCHK(c, hipMalloc((void**)&c->cand, (size_t)2 * comm->world * sizeof(double)));
+    HIPCHK(c, dev_ensure(c, c->ctail, 8 * sizeof(double), true));
+    dev_release(c, c->cand);
+    HIPCHK(c, dev_alloc(c, c->cand, (size_t)2 * comm->world * sizeof(double)));
     c->comm = comm;
     c->row_offset = row_offset;
     c->n_global = n_global;
@@ -4137,6 +4073,12 @@ rri_status rri_layout_info(rri_ctx* c, int64_t* out, int32_t n) {
     return RRI_OK;
 }
 
+rri_status rri_device_memory(int64_t* buffers, int64_t* bytes) {
+    if (buffers) *buffers = g_dev_buffers.load();
+    if (bytes) *bytes = g_dev_bytes.load();
+    return RRI_OK;
+}
+
 rri_status rri_debug_xcc(rri_ctx* c, int32_t* out, int32_t count) {
     CHECK_CTX(c);
     if (!out || count < 1 || count > 4096) return fail(c, RRI_ERR_INVALID, "bad count");
@@ -4194,23 +4136,19 @@ rri_status rri_bench_stream_copy(rri_ctx* c, int32_t reps, double* avg_ms) {
     if (!c->have_X || reps < 1 || c->sparse) return fail(c, RRI_ERR_INVALID, "a dense X must be set and reps >= 1");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->n * c->ldx * c->es;
-    void* dst = nullptr;
-    HIPCHK(c, hipMalloc(&dst, bytes));
-    hipEvent_t a, b;
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
+    DevTmp dst;
+    EventPair ev;
+    HIPCHK(c, dst.alloc(bytes));
+    HIPCHK(c, ev.create());
     const i64 nvec = (i64)(bytes / 16);
-    hipLaunchKernelGGL(k_stream_copy, dim3(256 * 8), dim3(256), 0, c->stream, (const float4*)c->X, (float4*)dst, nvec);
-    (void)hipEventRecord(a, c->stream);
+    hipLaunchKernelGGL(k_stream_copy, dim3(256 * 8), dim3(256), 0, c->stream, (const float4*)c->X, (float4*)dst.p, nvec);
+    (void)hipEventRecord(ev.a, c->stream);
     for (int r = 0; r < reps; ++r)
-        hipLaunchKernelGGL(k_stream_copy, dim3(256 * 8), dim3(256), 0, c->stream, (const float4*)c->X, (float4*)dst, nvec);
-    (void)hipEventRecord(b, c->stream);
+        hipLaunchKernelGGL(k_stream_copy, dim3(256 * 8), dim3(256), 0, c->stream, (const float4*)c->X, (float4*)dst.p, nvec);
+    (void)hipEventRecord(ev.b, c->stream);
     hipError_t e = hipStreamSynchronize(c->stream);
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, a, b);
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    (void)hipFree(dst);
+    (void)hipEventElapsedTime(&ms, ev.a, ev.b);
     if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "stream copy failed: %s", hipGetErrorString(e));
     if (avg_ms) *avg_ms = ms / reps;
     return RRI_OK;
@@ -4226,13 +4164,12 @@ rri_status rri_bench_rank1_update(rri_ctx* c, int32_t reps, double* avg_ms) {
     // into it (non-trivial row and column factors; R stays finite: it moves by reps * w_0 t_0^T) and takes the row
     // dots against T[0,:] and the column sums against W[:,0] of the result -- the work of rri_residual_update
     const size_t bytes = (size_t)c->n * c->ldx * c->es;
-    void* R = nullptr;
-    HIPCHK(c, hipMalloc(&R, bytes));
-    (void)hipMemcpyAsync(R, c->X, bytes, hipMemcpyDeviceToDevice, c->stream);
+    DevTmp R;
+    EventPair ev;
+    HIPCHK(c, R.alloc(bytes));
+    HIPCHK(c, ev.create());
+    (void)hipMemcpyAsync(R.p, c->X, bytes, hipMemcpyDeviceToDevice, c->stream);
     (void)hipMemsetAsync(c->st, 0, 16, c->stream);
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
     const int tm = c->timing;
     c->timing = 0;
     auto once = [&]() {
@@ -4240,20 +4177,17 @@ rri_status rri_bench_rank1_update(rri_ctx* c, int32_t reps, double* avg_ms) {
             typename L::Upd u;
             u.a = c->W;
             u.b = c->T;
-            L::rank_update(c, R, c->ldx, u, c->T, c->W);
+            L::rank_update(c, R.p, c->ldx, u, c->T, c->W);
         });
     };
     once();
-    (void)hipEventRecord(e0, c->stream);
+    (void)hipEventRecord(ev.a, c->stream);
     for (int r = 0; r < reps; ++r) once();
-    (void)hipEventRecord(e1, c->stream);
+    (void)hipEventRecord(ev.b, c->stream);
     hipError_t e = hipStreamSynchronize(c->stream);
     c->timing = tm;
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(R);
+    (void)hipEventElapsedTime(&ms, ev.a, ev.b);
     changed(c, CH_SCRATCH);
     if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "rank-one bench failed: %s", hipGetErrorString(e));
     if (avg_ms) *avg_ms = ms / reps;

@@ -64,6 +64,14 @@ def check_storage_options(dtype, weighted=False, schedule='gram', sparse_x=False
     return dt
 
 
+def device_memory():
+    """(buffers, bytes) of the device allocations that the handles of this process own right now (rri_device_memory): bound
+    tensors and the temporaries of a call are not counted, and after every close() both are back where they were."""
+    buffers, nbytes = C.c_int64(0), C.c_int64(0)
+    _capi.load_library().rri_device_memory(C.byref(buffers), C.byref(nbytes))
+    return int(buffers.value), int(nbytes.value)
+
+
 class RRIEngine(object):
     def __init__(self, n, d, k, dtype=np.float32, weighted=False, device=0, stream=None, schedule='gram', sparse_x=False):
         """schedule (unweighted handles): 'gram' -- the residual is never formed, one read of X per topic step

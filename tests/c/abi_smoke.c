@@ -203,5 +203,8 @@ int main(void) {
         free(R0); free(R1); free(av); free(bv); free(y); free(z);
     }
     free(Ws); free(Ts); free(X); free(W); free(T); free(W0); free(T0);
+    /* every handle of this process has been destroyed: none of them may still own device memory */
+    int64_t buffers = -1, bytes = -1;
+    if (rri_device_memory(&buffers, &bytes) != RRI_OK || buffers != 0 || bytes != 0) { fprintf(stderr, "%lld device buffers (%lld bytes) outlive their handles\n", (long long)buffers, (long long)bytes); return 1; }
     return 0;
 }
