@@ -1253,14 +1253,21 @@ rri_status to_device_half(rri_ctx* c, const void* host, i64 ld, int host_dtype, 
     return RRI_OK;
 }
 
-// host (rows x cols, stride ld, host_dtype) -> device (stride ldd, dev_dtype).
-// transpose: the device image is cols x rows (dst[c][r] = host[r][c]).
-rri_status to_device(rri_ctx* c, const void* host, i64 ld, int host_dtype, void* dev, i64 ldd, i64 rows,
-                     i64 cols, int dev_dtype, bool transpose = false) {
+// the argument checks of to_device, for the callers that change the handle before they get there (rri_upload_X, rri_upload_mask):
+// a refused call leaves the handle as it was
+rri_status check_host_matrix(rri_ctx* c, const void* host, i64 ld, int host_dtype, i64 cols, int dev_dtype) {
     if (!host || ld < cols) return fail(c, RRI_ERR_INVALID, "bad host matrix (ld=%lld < cols=%lld)", ld, cols);
     // a float16 host buffer goes onto a float16 handle only (nothing else is ever given as halves)
     if (host_dtype != RRI_F32 && host_dtype != RRI_F64 && !(host_dtype == RRI_F16 && dev_dtype == RRI_F16))
         return fail(c, RRI_ERR_INVALID, "bad host dtype");
+    return RRI_OK;
+}
+
+// host (rows x cols, stride ld, host_dtype) -> device (stride ldd, dev_dtype).
+// transpose: the device image is cols x rows (dst[c][r] = host[r][c]).
+rri_status to_device(rri_ctx* c, const void* host, i64 ld, int host_dtype, void* dev, i64 ldd, i64 rows,
+                     i64 cols, int dev_dtype, bool transpose = false) {
+    if (rri_status s = check_host_matrix(c, host, ld, host_dtype, cols, dev_dtype)) return s;
     const size_t hs = dtype_size(host_dtype);
     const size_t ds = dtype_size(dev_dtype);
     if (dev_dtype == RRI_F16) return to_device_half(c, host, ld, host_dtype, dev, ldd, rows, cols, transpose);
@@ -2366,6 +2373,7 @@ rri_status rri_destroy(rri_ctx* c) {
 rri_status rri_upload_X(rri_ctx* c, const void* host, int64_t ld, int32_t host_dtype) {
     CHECK_CTX(c);
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
+    if (rri_status s = check_host_matrix(c, host, ld, host_dtype, c->d, c->dtype)) return s;
     HIPCHK(c, hipSetDevice(c->device));
     if (!dev_owned(c, &c->X)) HIPCHK(c, dev_alloc(c, c->X, (size_t)c->n * c->LD * c->es, c->LD != c->d));   // (none yet, or a bound one)
     c->ldx = c->LD;
@@ -2381,6 +2389,7 @@ rri_status rri_upload_mask(rri_ctx* c, const void* host, int64_t ld, int32_t hos
     REFUSE_F16(c, "a mask");
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     if (!c->weighted) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=1");
+    if (rri_status s = check_host_matrix(c, host, ld, host_dtype, c->d, c->dtype)) return s;
     HIPCHK(c, hipSetDevice(c->device));
     if (!dev_owned(c, &c->M)) HIPCHK(c, dev_alloc(c, c->M, (size_t)c->n * c->LD * c->es, c->LD != c->d));   // (none yet, or a bound one)
     c->ldm = c->LD;
@@ -4130,12 +4139,16 @@ rri_status rri_synchronize(rri_ctx* c) {
     return RRI_OK;
 }
 
+// Bytes from the first element of X to the end of its last row: n - 1 strides and one row of LD elements (a bound X has LD = d
+// and may be a slice of a wider array: the ldx - d elements behind its last row are not the handle's to read).
+static size_t x_span_bytes(const rri_ctx* c) { return ((size_t)(c->n - 1) * c->ldx + c->LD) * c->es; }
+
 rri_status rri_bench_stream_copy(rri_ctx* c, int32_t reps, double* avg_ms) {
     CHECK_CTX(c);
     REFUSE_F16(c, "the stream-copy yardstick");
     if (!c->have_X || reps < 1 || c->sparse) return fail(c, RRI_ERR_INVALID, "a dense X must be set and reps >= 1");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)c->n * c->ldx * c->es;
+    const size_t bytes = x_span_bytes(c);
     DevTmp dst;
     EventPair ev;
     HIPCHK(c, dst.alloc(bytes));
@@ -4163,7 +4176,7 @@ rri_status rri_bench_rank1_update(rri_ctx* c, int32_t reps, double* avg_ms) {
     // scratch residual R = copy of X; every repetition folds the rank-one term w_0 t_0^T of the handle's own factors
     // into it (non-trivial row and column factors; R stays finite: it moves by reps * w_0 t_0^T) and takes the row
     // dots against T[0,:] and the column sums against W[:,0] of the result -- the work of rri_residual_update
-    const size_t bytes = (size_t)c->n * c->ldx * c->es;
+    const size_t bytes = x_span_bytes(c);
     DevTmp R;
     EventPair ev;
     HIPCHK(c, R.alloc(bytes));
