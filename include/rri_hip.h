@@ -375,8 +375,11 @@ rri_status rri_onchip_info(rri_ctx* ctx, int32_t* eligible, int64_t* launches);
  *   15     dense weighted: the last T-row step took nw = (w^2)^T M from the mask-only kernel, not from the pass
  *   16     dense handles: read-only passes deal their row blocks interleaved (few workgroups)
  *   17     row blocks of the last mask-only correction launch (0 before the first);   18  compute units of the device (the cap
- *          of a blocked copy's work items) */
-#define RRI_LAYOUT_FIELDS 19
+ *          of a blocked copy's work items)
+ *   19     the read-only pass streams the packed 28-bit copy of an fp32 X (RRI_X_PACK; decided by the first sweep after X was set);
+ *          20  the first top byte of its window;   21  tiles (8 rows x 1024 columns) with an element outside the window, read as
+ *          fp32 (with more than 1/8 of them flagged there is no copy: 19 is 0, 21 and 22 say why);   22  tiles in all */
+#define RRI_LAYOUT_FIELDS 23
 rri_status rri_layout_info(rri_ctx* ctx, int64_t* out, int32_t n);
 /* The exchanges of that launch poll a bounded number of times.  When its workgroups cannot all run at once (a device shared
  * with another process, CUs masked away) the launch gives up, and the call does what the reference's sweep does under any

@@ -136,6 +136,8 @@ struct rri_switches {
     bool rot_debug = false;    // RRI_ROT_DEBUG (set): calibrate_rot prints its timings
     bool mask_bits = true;     // RRI_MASK_BITS=0: a 0/1 mask stays an fp array (no bit-packed copy)
     double pass_cache_mb = PASS_CACHE_MB;   // RRI_PASS_CACHE_MB: what of the Infinity Cache a topic step may fill (pass_keep); 0: all of X streams
+    int x_pack = -1;           // RRI_X_PACK: the packed 28-bit copy of an fp32 X for the read-only pass (xpack_ensure): 0 never, 1 wherever the
+                               // pass can read it, unset: where X does not fit the budget of pass_keep
 };
 
 struct rri_ctx {
@@ -165,6 +167,13 @@ struct rri_ctx {
     int rot_x = 0, rot_r = 0;
     bool rot_done = false;
     int keep_q = -1;   // read-only pass over X: row blocks loaded with default policy, the others non-temporally; -1: all of X plain (pass_keep)
+    // the packed copy of an fp32 X that the read-only pass streams instead of X (rri_xpack.hpp; xpack_ensure): 3.5 bytes per element
+    unsigned char *xp = nullptr, *xp_flags = nullptr;   // the records; one flag byte per 8-row chunk and column group (tile)
+    unsigned* xp_hmax = nullptr;                        // device: the largest top byte of X inside [1, 0x7e]
+    bool xp_valid = false;      // the passes read xp: it was built from the X the handle holds and few enough tiles are flagged
+    bool xp_done = false;       // ... or the question is settled for this X (not wanted, no memory, too many flagged tiles)
+    int xp_base = 0;            // the window of top bytes: xp_base .. xp_base + 14
+    i64 xp_flagged = 0, xp_tiles = 0;
     bool gfull_valid = false;   // Gfull = T T^T of the current T (k_wsweep_rows)
     double *Gfull = nullptr, *Wsweep0 = nullptr, *wsum_part = nullptr, *wsums = nullptr;   // whole-sweep W half with T fixed: lazily allocated
     double *Y2part = nullptr, *Z2part = nullptr, *dtv = nullptr, *dwv = nullptr, *wold = nullptr, *zeros = nullptr;  // weighted
@@ -311,7 +320,11 @@ static inline bool ro_pass_interleaved(const rri_ctx* c) { return c->npanels * c
 // read only while resid_valid holds; every rebuild resets them (resid_rebuilt).  pending_wcheck is no cache but a verdict still
 // owed on the column sums in Gpart: it is taken before Gpart is overwritten (flush_wcheck) and dropped only with the run it
 // belongs to (CH_ENDED).  A step that PRODUCES one of these sets it itself, next to its launch; what makes one stale is said
-// here, by what changed, and nowhere else.
+// here, by what changed, and nowhere else.  xp_valid / xp_done qualify the packed copy of X (xpack_ensure) and go exactly where
+// x_sq_valid goes: the copy is of the X the handle held, the passes read the fp32 X again from that moment and the next sweep
+// builds the copy anew.  keep_q is NOT recomputed at that moment (it is set where the copy is decided, xpack_ensure): single topic
+// steps between a new X and the next sweep read the fp32 X with the kept row-block count of the 3.5-byte blocks, about 14 % more
+// kept bytes than the budget of pass_keep -- a cache policy, no bit of any result -- until that sweep recomputes it.
 // Coarser than the table on purpose: any change from outside the schedule drops the first four rows together, and a new X drops
 // Gfull as well.  A narrower rule would move where an fp32 residual is rebuilt, and with it the low bits of a run.
 enum : unsigned {
@@ -340,7 +353,7 @@ static void changed(rri_ctx* c, unsigned what) {
     if ((what & (CH_T_ROW | CH_W_COL)) && !(what & CH_E_FOLLOWS)) c->resid_valid = false;
     if (what & (CH_T_ROW | CH_W_COL | CH_PENALTY)) c->obj_track_valid = false;
     if (what & (CH_X | CH_T | CH_T_ROW)) { c->q_valid = false; c->gfull_valid = false; }
-    if (what & CH_X) c->x_sq_valid = false;
+    if (what & CH_X) { c->x_sq_valid = false; c->xp_valid = false; c->xp_done = false; }
     if (what & CH_ENDED) c->pending_wcheck = false;
 }
 // E has just been rebuilt from the current W and T: nothing is pending on it
@@ -631,12 +644,12 @@ struct LaunchX {
     static int stream_whole(const rri_ctx* c) {
         return (double)c->n * (double)c->LD * (double)c->es > 192.0e6 ? 0 : -1;
     }
-    template <bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS>
+    template <bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS, bool PK>
     static void pass_k(rri_ctx* c, void* Xp, i64 ldp, const double* trow, const double* wc, const Upd& u, const TgramJob& job,
                        int keep) {
         const int ncols = (int)std::min<i64>(ldp, c->LD);
         typedef typename std::conditional<(UPD > 0), SX, const SX>::type XT;
-        hipLaunchKernelGGL((k_pass<SX, DO_Y, DO_Z, UPD, U, NT, RS>), dim3(c->npanels * c->nrb + job.nblocks), dim3(256),
+        hipLaunchKernelGGL((k_pass<SX, DO_Y, DO_Z, UPD, U, NT, RS, PK>), dim3(c->npanels * c->nrb + job.nblocks), dim3(256),
                            pass_shmem(c, UPD), c->stream, (XT*)Xp, ldp, (int)c->n, ncols, trow, wc, c->Ypart,
                            c->Zpart, c->LD, c->rpb, c->npanels, u.a, u.b, u.a2, u.b2, u.b2sub, (const DevState*)c->st, job,
                            // interleaved row chunks: the workgroups running at one time walk ONE window of the matrix, as a
@@ -645,20 +658,22 @@ struct LaunchX {
                            // -- reads and writes of a window stay in the DRAM pages that are open
                            ((ro_pass_interleaved(c) || UPD > 0) ? c->nrb : 0) |
                                ((c->sw.pass_rot >= 0 ? c->sw.pass_rot : (UPD > 0 ? c->rot_r : c->rot_x)) << 27),
-                           keep);
+                           keep, PK ? (const unsigned char*)c->xp : nullptr, PK ? (const unsigned char*)c->xp_flags : nullptr,
+                           PK ? c->xp_base : 0);
     }
     // The read-only pass: 8 rows in flight per wave, the row dots (DO_Y) through LDS row sums.  The read-modify-write variants:
     // 16 rows in flight per wave, row dots by DPP wave sums -- 0.665 against 0.639 of 8 TB/s for the 8-row LDS row-sum variant
     // at C3 (profiles/r02_residual_schedule_geometry.log).  (The LDS-DMA ring k_pass_dma measured between +3 % and -9 % against
     // this pass, profiles/r04_pass_dma_ab.log, and was removed.)
     // keep: -1 = default-policy loads (and stores) throughout; >= 0: non-temporal, but for `keep` row blocks of a read-only pass
-    template <bool DO_Y, bool DO_Z, int UPD>
+    // PK: the read-only pass of an fp32 handle over the packed copy of X (c->xp; flagged tiles from Xp itself)
+    template <bool DO_Y, bool DO_Z, int UPD, bool PK = false>
     static void pass_cfg(rri_ctx* c, void* Xp, i64 ldp, const double* trow, const double* wc, int keep, const Upd& u = Upd{},
                          const TgramJob& job = TgramJob{}) {
         constexpr int U = UPD > 0 ? 16 : 8;
         constexpr bool RS = UPD == 0 && DO_Y;
-        if (keep >= 0) pass_k<DO_Y, DO_Z, UPD, U, true, RS>(c, Xp, ldp, trow, wc, u, job, keep);
-        else pass_k<DO_Y, DO_Z, UPD, U, false, RS>(c, Xp, ldp, trow, wc, u, job, 0);
+        if (keep >= 0) pass_k<DO_Y, DO_Z, UPD, U, true, RS, PK>(c, Xp, ldp, trow, wc, u, job, keep);
+        else pass_k<DO_Y, DO_Z, UPD, U, false, RS, PK>(c, Xp, ldp, trow, wc, u, job, 0);
     }
     // row dots against T[t,:] (DO_Y) and column sums against W[:,tz] (DO_Z); `job`: the Gram row of T[t,:] rides along
     template <bool DO_Y, bool DO_Z>
@@ -667,6 +682,12 @@ struct LaunchX {
         if constexpr (!RO) {
             if (c->sparse_x) {    // X on CSR: the read-only pass over its two blocked copies (no side job: the caller runs k_tgram)
                 spx_pass<DO_Y, DO_Z>(c, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw);
+                return;
+            }
+        }
+        if constexpr (std::is_same<SX, float>::value) {
+            if (c->xp_valid) {
+                pass_cfg<DO_Y, DO_Z, 0, true>(c, c->X, c->ldx, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw, c->keep_q, Upd{}, job);
                 return;
             }
         }
@@ -1808,10 +1829,61 @@ bool enqueue_wsweep(rri_ctx* c, int sweep, int t0) {
     return true;
 }
 
+// ---- the packed copy of an fp32 X (rri_xpack.hpp) ---------------------------------------------------------------------
+// The read-only pass is at the HBM read ceiling and X never changes between sweeps, so the handle keeps a lossless copy of
+// 3.5 bytes per element and the pass streams that.  Built lazily by the first sweep that would read it, for dense fp32 handles
+// of the Gram form on the launch-per-phase schedule, plain or row-sharded; by default only where X does not fit the budget of
+// pass_keep (a cached X gains nothing from fewer bytes).  Two kernels: the largest top byte (the window's base must be final
+// before anything is encoded), then the encoder, which sets the flag byte of every tile that holds an element outside the
+// window.  The host reads the flags once: with more than 1/8 of the tiles flagged the copy is released and the handle runs
+// as it did before.  An allocation that fails means no copy, and no error.
+int pass_keep(const rri_ctx* c);
+void xpack_release(rri_ctx* c) {
+    dev_release(c, c->xp); dev_release(c, c->xp_flags); dev_release(c, c->xp_hmax);
+    c->xp_valid = false;
+    c->xp_flagged = c->xp_tiles = 0;
+    c->xp_base = 0;
+    c->keep_q = pass_keep(c);
+}
+void xpack_ensure(rri_ctx* c) {
+    if (c->xp_done) return;
+    // sweeps with T fixed run the whole-sweep W half and no pass: nothing is built for them and nothing is settled, so that the
+    // first sweep after the parameters change decides (a copy that exists stays: xp_done is set then)
+    if (wsweep_ok(c)) return;
+    c->xp_done = true;
+    c->xp_valid = false;
+    c->keep_q = pass_keep(c);
+    const bool reads_x = c->dtype == RRI_F32 && !c->weighted && !c->explicit_resid && !c->sparse && c->have_X;
+    if (!reads_x || c->sw.x_pack == 0 || (c->sw.x_pack < 0 && c->keep_q < 0)) { xpack_release(c); return; }
+    const i64 nitems = (c->n + xpack::ROWS - 1) / xpack::ROWS * c->npanels;
+    if (dev_ensure(c, c->xp, (size_t)nitems * 4 * xpack::RECORD_BYTES) != hipSuccess || dev_ensure(c, c->xp_flags, (size_t)nitems) != hipSuccess ||
+        dev_ensure(c, c->xp_hmax, sizeof(unsigned)) != hipSuccess) { xpack_release(c); return; }
+    const int ncols = (int)std::min<i64>(c->ldx, c->LD);     // what the fp32 row loop reads (pass_k)
+    const unsigned grid = (unsigned)std::min<i64>(nitems, 8192);
+    std::vector<unsigned char> flags((size_t)nitems);
+    unsigned hmax = 0;
+    (void)hipMemsetAsync(c->xp_hmax, 0, sizeof(unsigned), c->stream);
+    (void)hipMemsetAsync(c->xp_flags, 0, (size_t)nitems, c->stream);
+    hipLaunchKernelGGL(k_xpack_max, dim3(grid), dim3(256), 0, c->stream, (const float*)c->X, c->ldx, (int)c->n, ncols, c->npanels, nitems, c->xp_hmax);
+    hipLaunchKernelGGL(k_xpack_encode, dim3(grid), dim3(256), 0, c->stream, (const float*)c->X, c->ldx, (int)c->n, ncols, c->npanels, nitems,
+                       (const unsigned*)c->xp_hmax, c->xp, c->xp_flags);
+    if (hipMemcpyAsync(flags.data(), c->xp_flags, (size_t)nitems, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipMemcpyAsync(&hmax, c->xp_hmax, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); xpack_release(c); return; }
+    i64 flagged = 0;
+    for (unsigned char f : flags) flagged += f != 0;
+    if (flagged * 8 > nitems) { xpack_release(c); c->xp_flagged = flagged; c->xp_tiles = nitems; return; }
+    c->xp_base = (int)xpack::base_of(hmax);
+    c->xp_flagged = flagged;
+    c->xp_tiles = nitems;
+    c->xp_valid = true;
+    c->keep_q = pass_keep(c);      // row blocks of 3.5 bytes per element: more of them fit
+}
+
 // sweeps [cur .. s_end) of the current call
 void enqueue_range(rri_ctx* c, Cursor cur, int s_end) {
     const int k = c->k;
-    if (cur.sweep < s_end) calibrate_rot(c);
+    if (cur.sweep < s_end) { xpack_ensure(c); calibrate_rot(c); }
     if (c->weighted) {
         for (int s = cur.sweep; s < s_end; ++s) {
             const int t0 = (s == cur.sweep) ? cur.topic : 0;
@@ -2135,8 +2207,10 @@ int pass_keep(const rri_ctx* c) {
                                 2.0 * (double)c->npanels * (double)c->n + 2.0 * (double)c->k * (double)c->LD +
                                 2.0 * (double)c->nwb * (double)(c->k + 2));
     const double budget = c->sw.pass_cache_mb * 1.0e6 - chain;
-    const double block = (double)c->rpb * (double)c->LD * (double)c->es;
-    if ((double)c->n * (double)c->LD * (double)c->es <= budget) return -1;
+    // bytes per element and columns of what the pass reads: X, or its packed copy (whole 1024-column groups of 3.5 bytes)
+    const double eb = c->xp_valid ? 3.5 : (double)c->es, cols = c->xp_valid ? (double)c->npanels * 1024.0 : (double)c->LD;
+    const double block = (double)c->rpb * cols * eb;
+    if ((double)c->n * cols * eb <= budget) return -1;
     return budget > 0.0 ? (int)std::min((double)c->nrb, std::floor(budget / block)) : 0;
 }
 
@@ -2155,6 +2229,7 @@ rri_switches read_switches() {
     sw.rot_debug = getenv("RRI_ROT_DEBUG") != nullptr;
     if (const char* e = getenv("RRI_MASK_BITS")) sw.mask_bits = atoi(e) != 0;
     if (const char* e = getenv("RRI_PASS_CACHE_MB")) sw.pass_cache_mb = std::max(0.0, atof(e));
+    if (const char* e = getenv("RRI_X_PACK")) sw.x_pack = atoi(e) != 0;
     return sw;
 }
 
@@ -4077,7 +4152,8 @@ rri_status rri_layout_info(rri_ctx* c, int64_t* out, int32_t n) {
         dense_w && wtrow_small(c) ? 1 : 0,
         dense_w && c->nw_mask ? 1 : 0,
         !c->sparse && ro_pass_interleaved(c) ? 1 : 0,
-        c->wcorr_nrb, c->n_cu};
+        c->wcorr_nrb, c->n_cu,
+        c->xp_valid ? 1 : 0, c->xp_valid ? c->xp_base : 0, c->xp_flagged, c->xp_tiles};
     for (int i = 0; i < n && i < RRI_LAYOUT_FIELDS; ++i) out[i] = v[i];
     return RRI_OK;
 }

@@ -29,6 +29,7 @@
 
 #include "rri_device.hpp"
 #include "rri_hip.h"
+#include "rri_xpack.hpp"
 
 namespace rri {
 
@@ -72,6 +73,7 @@ struct KParams {
 // =========================================================================================
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 template <typename SX> struct XVec;
 template <> struct XVec<float> {
@@ -166,6 +168,27 @@ __device__ __forceinline__ void tgram_block(const double* __restrict__ T, i64 ld
     }
 }
 
+// What a row does with its unpacked elements xe[] (the row dots against tv, the column sums against wv), and what ends a chunk
+// of U rows: shared by the fp32 / float64 / float16 row loop and the packed one, which differ in how xe[] is filled.
+#define RRI_PASS_ROW_SUMS \
+            double yp = 0.0;                                                                                      \
+        _Pragma("unroll")                                                                                         \
+            for (int e = 0; e < VN; ++e) {                                                                        \
+                if (DO_Y) yp = fma(xe[e], tv[e], yp);                                                             \
+                if (DO_Z) zacc[e] = fma(wv, xe[e], zacc[e]);                                                      \
+            }                                                                                                     \
+            if constexpr (DO_Y && RS) wave_rowsum8_park(tile, u, lane, yp);                                       \
+            else if (DO_Y) {                                                                                      \
+                /* the same six DPP steps as wave_sum: the total where they leave it (lane 63), stored from there */ \
+                const double tot = wave_sum_lane63<double>(yp);                                                   \
+                if (lane == 63) ysh[wave * rpb + l0 + u] = tot;                                                   \
+            }
+#define RRI_PASS_CHUNK_SUMS \
+        if constexpr (DO_Y && RS) {                                                                               \
+            const double tot = wave_rowsum8_finish(tile, lane);                                                   \
+            if ((lane & 7) == 0) ysh[wave * rpb + l0 + (lane >> 3)] = tot;                                        \
+        }
+
 // The row loop of k_pass with the load policy LNT.  A macro, because the kernel needs the loop twice (a workgroup of a
 // non-temporal read-only pass takes default-policy loads in its kept row blocks) and every function form costs registers: as
 // a lambda -- even one called once -- the float64 read-only pass takes 82 VGPRs instead of 74, 5 waves per SIMD instead of 6.
@@ -202,23 +225,42 @@ __device__ __forceinline__ void tgram_block(const double* __restrict__ T, i64 ld
                 /* the stored residual is what later passes read: continue with the ROUNDED values */             \
                 if constexpr (sizeof(SX) == 4) XV::unpack(rounded, xe);                                           \
             }                                                                                                     \
-            double yp = 0.0;                                                                                      \
+            RRI_PASS_ROW_SUMS                                                                                     \
+        }                                                                                                         \
+        RRI_PASS_CHUNK_SUMS                                                                                       \
+    }
+
+// The row loop over the packed copy of an fp32 X (rri_xpack.hpp; PK): the chunk of 8 rows is one 7 KiB record per wave, seven
+// 16-byte loads per lane instead of eight, unpacked into the same xe[] in the same order, so every sum keeps its bits.  Rows
+// past n and columns past ncols were encoded as +0; a lane with col >= ncols skips its loads as in the fp32 loop (codes of
+// all ones: zeros).
+#define RRI_PASS_ROWS_PK(LNT) \
+    for (int l0 = 0; l0 < rpb; l0 += U) {                                                                         \
+        const int r = grow(l0);                                                                                   \
+        if (r >= n) break;                                                                                        \
+        const u32x4* rec = reinterpret_cast<const u32x4*>(XP + xpack::record_offset((unsigned)r >> 3,             \
+                                                          (unsigned)(pg * 4 + wave), (unsigned)npg * 4u)) + lane; \
+        unsigned xw[4 * xpack::SLOTS];                                                                            \
         _Pragma("unroll")                                                                                         \
-            for (int e = 0; e < VN; ++e) {                                                                        \
-                if (DO_Y) yp = fma(xe[e], tv[e], yp);                                                             \
-                if (DO_Z) zacc[e] = fma(wv, xe[e], zacc[e]);                                                      \
-            }                                                                                                     \
-            if constexpr (DO_Y && RS) wave_rowsum8_park(tile, u, lane, yp);                                       \
-            else if (DO_Y) {                                                                                      \
-                /* the same six DPP steps as wave_sum: the total where they leave it (lane 63), stored from there */ \
-                const double tot = wave_sum_lane63<double>(yp);                                                   \
-                if (lane == 63) ysh[wave * rpb + l0 + u] = tot;                                                   \
-            }                                                                                                     \
+        for (int i = 0; i < (int)xpack::SLOTS; ++i) {                                                             \
+            const unsigned fill = i == (int)xpack::CODE_SLOT ? ~0u : 0u;                                          \
+            u32x4 v = u32x4{fill, fill, fill, fill};                                                              \
+            if (ok) v = stream_load<LNT>(rec + i * (int)xpack::LANES);                                            \
+            xw[4 * i] = v[0]; xw[4 * i + 1] = v[1]; xw[4 * i + 2] = v[2]; xw[4 * i + 3] = v[3];                   \
         }                                                                                                         \
-        if constexpr (DO_Y && RS) {                                                                               \
-            const double tot = wave_rowsum8_finish(tile, lane);                                                   \
-            if ((lane & 7) == 0) ysh[wave * rpb + l0 + (lane >> 3)] = tot;                                        \
+        _Pragma("unroll")                                                                                         \
+        for (int u = 0; u < U; ++u) {                                                                             \
+            const int rr = r + u;                                                                                 \
+            double wv = 0.0;                                                                                      \
+            if (DO_Z && rr < n) wv = wsh[l0 + u];                                                                 \
+            unsigned xb[4];                                                                                       \
+            xpack::decode_row(xw, u, base4, xb);                                                                  \
+            double xe[VN];                                                                                        \
+        _Pragma("unroll")                                                                                         \
+            for (int e = 0; e < VN; ++e) xe[e] = (double)__uint_as_float(xb[e]);                                  \
+            RRI_PASS_ROW_SUMS                                                                                     \
         }                                                                                                         \
+        RRI_PASS_CHUNK_SUMS                                                                                       \
     }
 
 // Block = 4 waves = 4 ADJACENT column panels (one per wave, 64 lanes * 16 B each) x one row block.
@@ -228,7 +270,10 @@ __device__ __forceinline__ void tgram_block(const double* __restrict__ T, i64 ld
 // UPD = 0: X is read only.  UPD = 1: R <- R - a b^T.  UPD = 2: R <- R - a b^T - a2 (b2 - b2sub)^T, the two pending
 // rank-one terms of one topic step of the explicit-residual schedule (dw_{t-1} t_{t-1}^T and w_t dt_t^T; b2sub = the
 // T row before its update, so dt is formed in registers).  a, a2 come through LDS, b, b2 live in registers.
-template <typename SX, bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS>
+// PK: the workgroup reads its rows from the packed copy XP (fp32, UPD = 0) unless one of its tiles is flagged (xflags: one byte
+// per 8-row chunk and column group, set where an element is outside the window of xbase .. xbase + 14): then it runs today's
+// loop on X.  ONE policy per workgroup for the whole row loop, taken in the prologue.
+template <typename SX, bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS, bool PK = false>
 __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0), SX, const SX>::type* __restrict__ X,
                                               i64 ldx, int n, int ncols,
                                               const double* __restrict__ trow, const double* __restrict__ wcol,
@@ -237,7 +282,9 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
                                               const double* __restrict__ bvec, const double* __restrict__ avec2,
                                               const double* __restrict__ bvec2, const double* __restrict__ bsub2,
                                               const DevState* __restrict__ st, const TgramJob job, int nrb_il_rot,
-                                              int keep_q) {
+                                              int keep_q, const unsigned char* __restrict__ XP = nullptr,
+                                              const unsigned char* __restrict__ xflags = nullptr, int xbase = 0) {
+    static_assert(!PK || (std::is_same<SX, float>::value && UPD == 0 && U == 8), "the packed copy is of a read-only fp32 X");
     typedef XVec<SX> XV;
     typedef typename XV::type V;
     constexpr int VN = XV::N;
@@ -275,6 +322,13 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
         return nrb_il > 0 ? ((li / U) * nrb_il + rb) * U + (li % U) : rb * rpb + li;
     };
     const int col = (pg * 4 + wave) * PW + lane * VN;
+    int xflag = 0;
+    if constexpr (PK) {
+        for (int l0 = (int)threadIdx.x * U; l0 < rpb; l0 += 256 * U) {
+            const int g = grow(l0);
+            if (g < n) xflag |= xflags[(i64)(g >> 3) * npg + pg];
+        }
+    }
     if (DO_Z || UPD > 0) {
         for (int i = threadIdx.x; i < rpb; i += 256) {
             const int g = grow(i);
@@ -282,8 +336,10 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
             if (UPD > 0) ash[i] = g < n ? avec[g] : 0.0;
             if (UPD > 1) ash2[i] = g < n ? avec2[g] : 0.0;
         }
-        __syncthreads();
-    }
+        if constexpr (PK) xflag = __syncthreads_or(xflag);
+        else __syncthreads();
+    } else if constexpr (PK) xflag = __syncthreads_or(xflag);
+    const unsigned base4 = (unsigned)xbase * 0x01010101u;
     const bool ok = col < ncols;
     const bool wave_has_cols = (pg * 4 + wave) * PW < ncols;   // wave-uniform
     double tv[VN], zacc[VN], bv[VN], bv2[VN];
@@ -297,7 +353,17 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
     if (wave_has_cols) {
         // keep_q of the nrb row blocks, spread evenly over the launch order, are read with default-policy loads and stay in
         // the Infinity Cache from pass to pass; the others stream past it (host: pass_keep in rri_hip.hip)
-        if constexpr (NT && UPD == 0) {
+        if constexpr (PK && NT) {
+            // three expansions, not four: a flagged workgroup streams its fp32 rows whether its row block is a kept one or not
+            const unsigned nrb = ((unsigned)gridDim.x - (unsigned)job.nblocks) / (unsigned)npg;
+            const bool kept = ((unsigned)(rb + 1) * (unsigned)keep_q) / nrb != ((unsigned)rb * (unsigned)keep_q) / nrb;
+            if (xflag) { RRI_PASS_ROWS(true) }
+            else if (kept) { RRI_PASS_ROWS_PK(false) }
+            else { RRI_PASS_ROWS_PK(true) }
+        } else if constexpr (PK) {
+            if (xflag) { RRI_PASS_ROWS(false) }
+            else { RRI_PASS_ROWS_PK(false) }
+        } else if constexpr (NT && UPD == 0) {
             const unsigned nrb = ((unsigned)gridDim.x - (unsigned)job.nblocks) / (unsigned)npg;
             const bool kept = ((unsigned)(rb + 1) * (unsigned)keep_q) / nrb != ((unsigned)rb * (unsigned)keep_q) / nrb;
             if (kept) { RRI_PASS_ROWS(false) }
@@ -322,6 +388,62 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
 }
 
 #undef RRI_PASS_ROWS
+#undef RRI_PASS_ROWS_PK
+#undef RRI_PASS_ROW_SUMS
+#undef RRI_PASS_CHUNK_SUMS
+
+// =========================================================================================
+// The two one-time kernels behind the packed copy (rri_xpack.hpp), in the geometry of the pass: a work item is one 8-row chunk
+// of one column group, a wave takes one of its four 256-column panels, a lane 8 rows x 4 columns, read exactly where the fp32
+// row loop reads them (rows < n, columns < ncols; everything else counts as +0).
+// k_xpack_max: the largest top byte in [1, 0x7e] present in X (one integer max: *hmax, zeroed before the launch).
+// k_xpack_encode: reads X once more and writes the copy; a tile with an element outside the window of *hmax gets its flag byte
+// set by a plain vector store of the constant 1 (the flags were zeroed before the launch).
+// =========================================================================================
+__device__ __forceinline__ void xpack_load_lane(const float* __restrict__ X, i64 ldx, int n, int ncols, int q, int col,
+                                                unsigned (&bits)[xpack::ROWS][xpack::COLS]) {
+#pragma unroll
+    for (int u = 0; u < (int)xpack::ROWS; ++u) {
+        const int rr = q * (int)xpack::ROWS + u;
+        u32x4 v = u32x4{0u, 0u, 0u, 0u};
+        if (rr < n && col < ncols) v = *reinterpret_cast<const u32x4*>(X + (i64)rr * ldx + col);
+        bits[u][0] = v[0]; bits[u][1] = v[1]; bits[u][2] = v[2]; bits[u][3] = v[3];
+    }
+}
+__global__ __launch_bounds__(256) void k_xpack_max(const float* __restrict__ X, i64 ldx, int n, int ncols, int npg, i64 nitems,
+                                                   unsigned* __restrict__ hmax) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned m = 0u;
+    for (i64 it = blockIdx.x; it < nitems; it += gridDim.x) {
+        const int q = (int)(it / npg), pg = (int)(it % npg);
+        unsigned bits[xpack::ROWS][xpack::COLS];
+        xpack_load_lane(X, ldx, n, ncols, q, (pg * 4 + wave) * 256 + lane * 4, bits);
+#pragma unroll
+        for (int u = 0; u < (int)xpack::ROWS; ++u)
+#pragma unroll
+            for (int e = 0; e < (int)xpack::COLS; ++e) m = max(m, xpack::window_candidate(bits[u][e]));
+    }
+    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
+    if (lane == 0 && m != 0u) atomicMax(hmax, m);
+}
+__global__ __launch_bounds__(256) void k_xpack_encode(const float* __restrict__ X, i64 ldx, int n, int ncols, int npg, i64 nitems,
+                                                      const unsigned* __restrict__ hmax, unsigned char* __restrict__ XP,
+                                                      unsigned char* __restrict__ xflags) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned base = xpack::base_of(*hmax);
+    for (i64 it = blockIdx.x; it < nitems; it += gridDim.x) {
+        const int q = (int)(it / npg), pg = (int)(it % npg);
+        unsigned bits[xpack::ROWS][xpack::COLS], out[4 * xpack::SLOTS];
+        xpack_load_lane(X, ldx, n, ncols, q, (pg * 4 + wave) * 256 + lane * 4, bits);
+        bool bad;
+        xpack::encode_lane(bits, base, out, bad);
+        u32x4* rec = reinterpret_cast<u32x4*>(XP + xpack::record_offset((unsigned)q, (unsigned)(pg * 4 + wave), (unsigned)npg * 4u)) + lane;
+#pragma unroll
+        for (int i = 0; i < (int)xpack::SLOTS; ++i)
+            rec[i * (int)xpack::LANES] = u32x4{out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]};
+        if (bad) xflags[it] = 1;
+    }
+}
 
 // =========================================================================================
 // k_colsums: column sums of X against NV row-vectors at once (X^T Q for the randomized SVD behind NNDSVD,

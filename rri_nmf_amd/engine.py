@@ -714,20 +714,21 @@ class RRIEngine(object):
     # rri_layout_info: four values per copy of a blocked store (row copy, then column copy), then one value per name
     LAYOUT_COPY_FIELDS = ('nblk', 'bw', 'lps', 'nwork')
     LAYOUT_FIELDS = ('rpb', 'nrb', 'npanels', 'mask_bits', 'mask_cols', 'mask_density', 'wtrow_small', 'nw_from_mask',
-                     'interleaved', 'wcorr_nrb', 'n_cu')
+                     'interleaved', 'wcorr_nrb', 'n_cu', 'x_pack', 'x_pack_base', 'x_pack_flagged', 'x_pack_tiles')
     assert 2 * len(LAYOUT_COPY_FIELDS) + len(LAYOUT_FIELDS) == _capi.RRI_LAYOUT_FIELDS
 
     def layout_info(self):
         """what the handle decided (rri_layout_info): per-copy values of a blocked CSR store as (row copy, column copy) pairs --
         nblk, bw, lps, nwork -- the pass geometry rpb / nrb / npanels, and which routes of the dense weighted step are taken
-        (mask_density is None until the first topic step has measured it; nw_from_mask is what the last T-row step did)"""
+        (mask_density is None until the first topic step has measured it; nw_from_mask is what the last T-row step did), and the
+        packed copy of an fp32 X: x_pack (the read-only pass streams it), x_pack_base, x_pack_flagged of x_pack_tiles tiles"""
         nc = len(self.LAYOUT_COPY_FIELDS)
         out = (C.c_int64 * _capi.RRI_LAYOUT_FIELDS)()
         self._check(self._lib.rri_layout_info(self._h, out, _capi.RRI_LAYOUT_FIELDS))
         v = [int(x) for x in out]
         info = {name: (v[i], v[nc + i]) for i, name in enumerate(self.LAYOUT_COPY_FIELDS)}
         info.update(zip(self.LAYOUT_FIELDS, v[2 * nc:]))
-        for name in ('mask_bits', 'mask_cols', 'wtrow_small', 'nw_from_mask', 'interleaved'):
+        for name in ('mask_bits', 'mask_cols', 'wtrow_small', 'nw_from_mask', 'interleaved', 'x_pack'):
             info[name] = bool(info[name])
         info['mask_density'] = None if info['mask_density'] < 0 else info['mask_density'] * 1e-9
         return info
