@@ -1450,10 +1450,8 @@ void enqueue_W_half(rri_ctx* c, int sweep, int t) {
             DISPATCH_RO(c, (L::template pass<true, false>(c, t, tn, job)));
             LK::wcol<true, false>(c, t, tn, sweep);
         }
-        // position of the NEXT step, where a resumed run continues
-        int ns = sweep, np = t + 1;
-        if (np == k) { np = 0; ns = sweep + 1; }
-        wcheck_now(c, t, ns, np);
+        const StepPos next = next_step(sweep, t, k);
+        wcheck_now(c, t, next.sweep, next.pos);
         c->carry_valid = false;
     }
     changed(c, CH_W_COL);
@@ -1692,13 +1690,12 @@ void enqueue_wW_half(rri_ctx* c, int sweep, int t, bool defer_check = false) {
     changed(c, CH_W_COL | CH_E_FOLLOWS);
     c->dw_pending = true;     // dwv x T[t,:]: folded in by the pass of the next step (dense: into E, under the mask; pattern-only: the row copy)
     c->dw_topic = t;
-    int ns = sweep, np = t + 1;
-    if (np == k) { np = 0; ns = sweep + 1; }
+    const StepPos next = next_step(sweep, t, k);
     if (defer_check) {   // row-sharded: the verdict needs the global column sum; it rides on the next topic's all-reduce
         c->pending_wcheck = true;
         c->pending_wcheck_topic = t;
     } else {
-        wcheck_now(c, t, ns, np);
+        wcheck_now(c, t, next.sweep, next.pos);
     }
     c->carry_valid = carry_next;
     c->carry_topic = tn;

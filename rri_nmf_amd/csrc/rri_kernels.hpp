@@ -24,40 +24,16 @@
 // instead of the ~1e-4 an fp32 accumulation gives on these iterations.
 // Rare branches (reset conditions, unbounded problems, dead columns) set DevState::halt;
 // every later kernel of the queue then returns at once and the host resolves the event.
+// The rules that decide them, and DevState and KParams, are in rri_halt.hpp.
 #pragma once
 #include <type_traits>
 
 #include "rri_device.hpp"
+#include "rri_halt.hpp"
 #include "rri_hip.h"
 #include "rri_xpack.hpp"
 
 namespace rri {
-
-enum { HALT_EVENT_RESET_T = 1, HALT_EVENT_RESET_W = 2,
-       HALT_EVENT_STOP = 3,    // the persistent sweep: the stop rule of nmf.py:510 held at the end of sweep halt_sweep - 1
-       HALT_ERR_UNBOUNDED = -4, HALT_ERR_W_COL_ZERO = -5, HALT_ERR_NOT_IMPLEMENTED = -6 };
-enum { RESET_NONE = 0, RESET_MAX_RESID = 1, RESET_RANDOM = 2 };
-
-struct DevState {
-    int halt;        // 0 = running, >0 event, <0 error
-    int halt_topic;  // topic the event refers to
-    int halt_sweep;  // position of the DETECTING step
-    int halt_pos;
-    int tmode;       // qf_min branch of the current T row: 0 c>0, 1 c<=0 bounds, 2 c<=0 one-hot
-    int proj_iters;  // Michelot iterations of the last projection (diagnostic)
-    int pad0;        // k_wsweep_verdict: first column k_wsweep_repair restores after a reset event (0: none); cleared with halt
-    int pad1;
-    double nt1;      // 1-norm of the unprojected T-row solution (qf_min's nx, nmf.py:447)
-    double nt;       // ||T[t,:]||^2
-    double sumT;
-    double theta;
-    double obj_track;   // the persistent sweep: objective of the launch's last sweep minus 1/2 ||X||^2 (OnchipArgs.track)
-};
-
-struct KParams {
-    int fix_W, fix_T, project_T, has_trs, has_wrs, reset_method, resets_left, pad;
-    double t_row_sum, w_row_sum, reg_w_l1, reg_w_l2, reg_t_l1, reg_t_l2, eps;
-};
 
 // =========================================================================================
 // k_pass: the fused streaming pass over X.
@@ -161,9 +137,7 @@ __device__ __forceinline__ void tgram_block(const double* __restrict__ T, i64 ld
             const int mode = st->tmode;
             st->nt1 = (mode == 0) ? ps : 1.0;
             st->sumT = ps;
-            if (!(ps > 1e-10) && p.reset_method != RESET_NONE && p.resets_left > 0) {
-                st->halt = HALT_EVENT_RESET_T; st->halt_topic = t; st->halt_sweep = sweep; st->halt_pos = t;
-            }
+            if (trow_resets(ps, p)) halt_set(st, HALT_EVENT_RESET_T, t, sweep, t);
         }
     }
 }
@@ -619,15 +593,10 @@ __global__ __launch_bounds__(256) void k_wcol(double* __restrict__ Wt, i64 ldw, 
         cden = tts[t] + p.reg_w_l2;                   // denom = nt + reg_w_l2 (nmf.py:465)
         __syncthreads();
         if (tid == 0) tts[t] = 0.0;                   // Tt[t] = 0 (nmf.py:732)
-        if (!(cden > 0.0)) {
-            // scalar c<=0 with s=None (optimization.py:60-67): entries jump to ub, or unbounded
-            if (p.has_wrs && p.w_row_sum != 0.0) mode = 1;
-            else {
-                if (blockIdx.x == 0 && tid == 0) {
-                    st->halt = HALT_ERR_UNBOUNDED; st->halt_topic = t; st->halt_sweep = sweep; st->halt_pos = t;
-                }
-                return;
-            }
+        mode = wcol_denominator_mode(cden, p);        // scalar c<=0 with s=None (optimization.py:60-67): entries at ub, or unbounded
+        if (mode < 0) {
+            if (blockIdx.x == 0 && tid == 0) halt_set(st, mode, t, sweep, t);
+            return;
         }
     }
     __syncthreads();
@@ -778,11 +747,8 @@ __global__ __launch_bounds__(64) void k_wsweep_rows(double* __restrict__ Wt, dou
             if (t >= k || t < t0) continue;           // (wave-uniform)
             const double* gr = gsh + (size_t)t * kp;
             const double cden = gr[t] + p.reg_w_l2;   // denom = nt + reg_w_l2 (nmf.py:465)
-            int mode = 0;
-            if (!(cden > 0.0)) {                      // scalar c <= 0 with s = None (optimization.py:60-67): entries jump to ub, or
-                if (p.has_wrs && p.w_row_sum != 0.0) mode = 1;
-                else continue;                        // unbounded -- k_wsweep_verdict reports it at this topic; the column stays
-            }
+            const int mode = wcol_denominator_mode(cden, p);   // scalar c <= 0 with s = None (optimization.py:60-67): entries at ub, or
+            if (mode < 0) continue;                   // unbounded -- k_wsweep_verdict reports it at this topic; the column stays
             double dot = acc[j];
 #pragma unroll
             for (int j2 = 0; j2 < 4; ++j2)
@@ -833,19 +799,16 @@ __global__ __launch_bounds__(1024) void k_wsweep_verdict(const double* __restric
     if (threadIdx.x != 0) return;
     for (int t = t0; t < k; ++t) {
         const double cden = G[(i64)t * k + t] + p.reg_w_l2;
-        if (!(cden > 0.0) && !(p.has_wrs && p.w_row_sum != 0.0)) {
-            st->halt = HALT_ERR_UNBOUNDED; st->halt_topic = t; st->halt_sweep = sweep; st->halt_pos = t;
+        const int mode = wcol_denominator_mode(cden, p);
+        if (mode < 0) {
+            halt_set(st, mode, t, sweep, t);
             return;
         }
-        const double a = ssum[t];
-        const bool ev = (a <= 1e-10) && p.reset_method != RESET_NONE && p.resets_left > 0;
-        const bool err = !ev && !(a > 0.0);
-        if (ev || err) {
-            st->halt = ev ? HALT_EVENT_RESET_W : HALT_ERR_W_COL_ZERO;
-            st->halt_topic = t;
-            st->halt_sweep = t + 1 == k ? sweep + 1 : sweep;     // position of the NEXT step, where a resumed run continues
-            st->halt_pos = t + 1 == k ? 0 : t + 1;
-            if (ev) st->pad0 = t + 1;
+        const int code = wcol_code(ssum[t], p);
+        if (code != 0) {
+            const StepPos next = next_step(sweep, t, k);         // where a resumed run continues
+            halt_set(st, code, t, next.sweep, next.pos);
+            if (code == HALT_EVENT_RESET_W) st->pad0 = t + 1;
             return;
         }
     }
@@ -884,14 +847,10 @@ __global__ __launch_bounds__(256) void k_wcol_resid(double* __restrict__ Wt, i64
     if (UPDATE) {
         nt = ordered_sum<8>(Ttpart + t, k, 0, nsplit, 1);      // ||T[t,:]||^2 from the slices of k_tgram
         cden = nt + p.reg_w_l2;                                // denom = nt + reg_w_l2 (nmf.py:465)
-        if (!(cden > 0.0)) {
-            if (p.has_wrs && p.w_row_sum != 0.0) mode = 1;     // optimization.py:60-67
-            else {
-                if (blockIdx.x == 0 && threadIdx.x == 0) {
-                    st->halt = HALT_ERR_UNBOUNDED; st->halt_topic = t; st->halt_sweep = sweep; st->halt_pos = t;
-                }
-                return;
-            }
+        mode = wcol_denominator_mode(cden, p);                 // optimization.py:60-67
+        if (mode < 0) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) halt_set(st, mode, t, sweep, t);
+            return;
         }
     }
     double wnew = 0.0, dwi = 0.0, wn = 0.0;
@@ -993,33 +952,18 @@ __global__ __launch_bounds__(128) void k_trow_numer(double* __restrict__ T, i64 
     __shared__ double gsh[RRI_MAX_K];
     const double nw = red_gram(red, ldz, k, k);
     if (check_prev) {
-        const double sw = red_gram(red, ldz, k, k + 1);
-        const bool ev = (sw <= 1e-10) && p.reset_method != RESET_NONE && p.resets_left > 0;
-        const bool err = !ev && !(sw > 0.0);
-        if (ev || err) {
-            if (blockIdx.x == 0 && tid == 0) {
-                st->halt = ev ? HALT_EVENT_RESET_W : HALT_ERR_W_COL_ZERO;
-                st->halt_topic = tprev; st->halt_sweep = sweep; st->halt_pos = t;
-            }
+        const int code = wcol_code(red_gram(red, ldz, k, k + 1), p);
+        if (code != 0) {
+            if (blockIdx.x == 0 && tid == 0) halt_set(st, code, tprev, sweep, t);
             return;
         }
     }
     const double c = nw + p.reg_t_l2;  // denom = nw + reg_t_l2 (nmf.py:438)
     const bool project = p.project_T && p.has_trs;
-    int mode = 0;
-    if (!(c > 0.0)) {
-        if (!project) {
-            if (p.has_trs && p.t_row_sum != 0.0) mode = 1;
-            else mode = HALT_ERR_UNBOUNDED;
-        } else {
-            mode = (p.t_row_sum == 1.0) ? 2 : HALT_ERR_NOT_IMPLEMENTED;
-        }
-        if (mode < 0) {
-            if (blockIdx.x == 0 && tid == 0) {
-                st->halt = mode; st->halt_topic = t; st->halt_sweep = sweep; st->halt_pos = t;
-            }
-            return;
-        }
+    const int mode = trow_denominator_mode(c, p);   // optimization.py:60-73
+    if (mode < 0) {
+        if (blockIdx.x == 0 && tid == 0) halt_set(st, mode, t, sweep, t);
+        return;
     }
     for (int l = tid; l < k; l += 128) gsh[l] = (l == t) ? (resid_form ? -nw : 0.0) : red_gram(red, ldz, k, l);
     __syncthreads();
@@ -1124,33 +1068,18 @@ __global__ __launch_bounds__(1024) void k_trow_small(double* __restrict__ T, i64
     __syncthreads();
     const double nw = gsh[k];
     if (check_prev) {
-        const double sw = gsh[k + 1];
-        const bool ev = (sw <= 1e-10) && p.reset_method != RESET_NONE && p.resets_left > 0;
-        const bool err = !ev && !(sw > 0.0);
-        if (ev || err) {
-            if (blockIdx.x == 0 && tid == 0) {
-                st->halt = ev ? HALT_EVENT_RESET_W : HALT_ERR_W_COL_ZERO;
-                st->halt_topic = tprev; st->halt_sweep = sweep; st->halt_pos = t;
-            }
+        const int code = wcol_code(gsh[k + 1], p);
+        if (code != 0) {
+            if (blockIdx.x == 0 && tid == 0) halt_set(st, code, tprev, sweep, t);
             return;
         }
     }
     const double c = nw + p.reg_t_l2;  // denom = nw + reg_t_l2 (nmf.py:438)
     const bool project = p.project_T && p.has_trs;
-    int mode = 0;
-    if (!(c > 0.0)) {
-        if (!project) {
-            if (p.has_trs && p.t_row_sum != 0.0) mode = 1;
-            else mode = HALT_ERR_UNBOUNDED;
-        } else {
-            mode = (p.t_row_sum == 1.0) ? 2 : HALT_ERR_NOT_IMPLEMENTED;
-        }
-        if (mode < 0) {
-            if (blockIdx.x == 0 && tid == 0) {
-                st->halt = mode; st->halt_topic = t; st->halt_sweep = sweep; st->halt_pos = t;
-            }
-            return;
-        }
+    const int mode = trow_denominator_mode(c, p);   // optimization.py:60-73
+    if (mode < 0) {
+        if (blockIdx.x == 0 && tid == 0) halt_set(st, mode, t, sweep, t);
+        return;
     }
     if (blockIdx.x == 0)   // the reduce buffer as k_reduce leaves it: slice 0 carries the sums, the rest zeros
         for (int i = tid; i < GRAM_SLICES * (k + 2); i += 1024) red[ldz + i] = i < k + 2 ? gsh[i] : 0.0;
@@ -1281,8 +1210,7 @@ __global__ __launch_bounds__(1024) void k_trow_final(double* __restrict__ T, i64
         for (int j = tid; j < d; j += blockDim.x) sumT += xraw[j];
         sumT = block_sum(sumT, scratch);
     }
-    bool event = false;
-    if (sumT > 1e-10 || p.reset_method == RESET_NONE) {
+    if (trow_kept(sumT, p)) {
         // nmf.py:759-761: project again when the row is not on the simplex to 1e-15
         if (p.has_trs && p.t_row_sum != 0.0 && p.project_T && fabs(sumT - p.t_row_sum) > 1e-15) {
             int it2 = 0;
@@ -1291,8 +1219,6 @@ __global__ __launch_bounds__(1024) void k_trow_final(double* __restrict__ T, i64
             iters += it2;
             row_dirty = true;
         }
-    } else if (p.resets_left > 0) {
-        event = true;
     }
     if (row_dirty) {
         __syncthreads();
@@ -1302,7 +1228,7 @@ __global__ __launch_bounds__(1024) void k_trow_final(double* __restrict__ T, i64
         st->nt1 = nx;
         st->sumT = sumT;
         st->proj_iters = iters;
-        if (event) { st->halt = HALT_EVENT_RESET_T; st->halt_topic = t; st->halt_sweep = sweep; st->halt_pos = t; }
+        if (trow_resets(sumT, p)) halt_set(st, HALT_EVENT_RESET_T, t, sweep, t);
     }
 }
 
@@ -1330,13 +1256,8 @@ __global__ __launch_bounds__(64) void k_check_red(const double* __restrict__ red
                                                   int sweep, int pos, KParams p, DevState* st) {
     if (st->halt) return;
     if (threadIdx.x == 0) {
-        const double sw = red_gram(red, ldz, k, k + 1);
-        const bool ev = (sw <= 1e-10) && p.reset_method != RESET_NONE && p.resets_left > 0;
-        const bool err = !ev && !(sw > 0.0);
-        if (ev || err) {
-            st->halt = ev ? HALT_EVENT_RESET_W : HALT_ERR_W_COL_ZERO;
-            st->halt_topic = tprev; st->halt_sweep = sweep; st->halt_pos = pos;
-        }
+        const int code = wcol_code(red_gram(red, ldz, k, k + 1), p);
+        if (code != 0) halt_set(st, code, tprev, sweep, pos);
     }
 }
 
@@ -1349,12 +1270,8 @@ __global__ __launch_bounds__(256) void k_check_wcol(const double* __restrict__ G
     a = ordered_sum<8>(Gpart + k + 1, k + 2, threadIdx.x, nwb, (int)blockDim.x);
     a = block_sum(a, scratch);
     if (threadIdx.x == 0) {
-        const bool ev = (a <= 1e-10) && p.reset_method != RESET_NONE && p.resets_left > 0;
-        const bool err = !ev && !(a > 0.0);
-        if (ev || err) {
-            st->halt = ev ? HALT_EVENT_RESET_W : HALT_ERR_W_COL_ZERO;
-            st->halt_topic = tprev; st->halt_sweep = sweep; st->halt_pos = pos;
-        }
+        const int code = wcol_code(a, p);
+        if (code != 0) halt_set(st, code, tprev, sweep, pos);
     }
 }
 

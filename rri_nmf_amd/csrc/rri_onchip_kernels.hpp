@@ -603,13 +603,17 @@ __global__ __launch_bounds__(ONCHIP_THREADS) void k_onchip_sweeps(OnchipArgs a) 
                     RRI_STAMP(0);
                     const double nw = gsh[k];
                     int code = 0;
+                    // The four rules met inside the step loop keep their own text here -- wcol_code and trow_denominator_mode
+                    // just below, trow_resets and wcol_denominator_mode in phase B: through rri_halt.hpp each of them moves the
+                    // register allocation of the loop, and the call at 10000 x 1000, k = 20 ran 6 % slower.  They restate
+                    // rri_halt.hpp; everything else of the kernel (halt_set, the projected row, the last column) calls it.
                     if (chk) {
                         const double sw = gsh[k + 1];
                         const bool ev = (sw <= 1e-10) && p.reset_method != RESET_NONE && p.resets_left > 0;
                         const bool err = !ev && !(sw > 0.0);
                         if (ev || err) {
                             code = ev ? HALT_EVENT_RESET_W : HALT_ERR_W_COL_ZERO;
-                            if (b == 0 && tid == 0) { st->halt = code; st->halt_topic = tprev; st->halt_sweep = s; st->halt_pos = t; }
+                            if (b == 0 && tid == 0) halt_set(st, code, tprev, s, t);
                         }
                     }
                     const double c = nw + p.reg_t_l2;          // denom = nw + reg_t_l2 (nmf.py:438)
@@ -619,7 +623,7 @@ __global__ __launch_bounds__(ONCHIP_THREADS) void k_onchip_sweeps(OnchipArgs a) 
                         else mode = HALT_ERR_UNBOUNDED;
                         if (mode < 0) {
                             code = mode;
-                            if (b == 0 && tid == 0) { st->halt = code; st->halt_topic = t; st->halt_sweep = s; st->halt_pos = t; }
+                            if (b == 0 && tid == 0) halt_set(st, code, t, s, t);
                         }
                     }
                     if (a.track == 2 && t == 0 && s > a.s0 && code == 0) {
@@ -650,7 +654,7 @@ __global__ __launch_bounds__(ONCHIP_THREADS) void k_onchip_sweeps(OnchipArgs a) 
                         }
                         if (stop) {
                             code = HALT_EVENT_STOP;
-                            if (b == 0 && tid == 0) { st->halt = code; st->halt_topic = -1; st->halt_sweep = s; st->halt_pos = 0; }
+                            if (b == 0 && tid == 0) halt_set(st, code, -1, s, 0);
                         }
                     }
                     RRI_JIT(4u);
@@ -748,7 +752,7 @@ __global__ __launch_bounds__(ONCHIP_THREADS) void k_onchip_sweeps(OnchipArgs a) 
                                 const double th1 = onchip_wave_theta(rowsh, a.d, p.t_row_sum, false, 0.0, OnchipThetaStart{false, 0.0, 0.0},
                                                                      &all, &vmax, &sp, &it1);
                                 double th2 = 0.0, again = 0.0;
-                                if ((sp > 1e-10 || p.reset_method == RESET_NONE) && p.t_row_sum != 0.0 && fabs(sp - p.t_row_sum) > 1e-15) {
+                                if (trow_kept(sp, p) && p.t_row_sum != 0.0 && fabs(sp - p.t_row_sum) > 1e-15) {
                                     again = 1.0;                              // nmf.py:759-761: project again
                                     th2 = onchip_wave_theta(rowsh, a.d, p.t_row_sum, true, th1, OnchipThetaStart{true, sp, fmax(vmax - th1, 0.0)},
                                                             &all2, &vmax2, &sp2, &it2);
@@ -774,7 +778,7 @@ __global__ __launch_bounds__(ONCHIP_THREADS) void k_onchip_sweeps(OnchipArgs a) 
                                 }
                             }
                             if (b == 0 && tid == 0) st->theta = th1;
-                            if (!(sumT > 1e-10 || p.reset_method == RESET_NONE) && p.resets_left > 0) {
+                            if (trow_resets(sumT, p)) {
                                 code = HALT_EVENT_RESET_T;
                                 halt_bit = 0x80000000u;
                             }
@@ -783,7 +787,7 @@ __global__ __launch_bounds__(ONCHIP_THREADS) void k_onchip_sweeps(OnchipArgs a) 
                         RRI_STAMP(12);                         // projected
                         if (b == 0 && tid == 0) {
                             st->nt1 = nx; st->sumT = sumT; st->proj_iters = iters;
-                            if (code != 0) { st->halt = code; st->halt_topic = t; st->halt_sweep = s; st->halt_pos = t; }
+                            if (code != 0) halt_set(st, code, t, s, t);
                         }
                         if (code == 0 && tid < CWA && j0 + tid < a.d) {
                             const double x = rowsh[j0 + tid];
@@ -865,9 +869,7 @@ __global__ __launch_bounds__(ONCHIP_THREADS) void k_onchip_sweeps(OnchipArgs a) 
                         st->sumT = ps;
                     }
                     if (!(ps > 1e-10) && p.reset_method != RESET_NONE && p.resets_left > 0) {
-                        if (b == 0 && tid == 0) {
-                            st->halt = HALT_EVENT_RESET_T; st->halt_topic = t; st->halt_sweep = s; st->halt_pos = t;
-                        }
+                        if (b == 0 && tid == 0) halt_set(st, HALT_EVENT_RESET_T, t, s, t);
                         return;                            // every workgroup: the same sums, the same verdict
                     }
                 }
@@ -876,9 +878,7 @@ __global__ __launch_bounds__(ONCHIP_THREADS) void k_onchip_sweeps(OnchipArgs a) 
                 if (!(cden > 0.0)) {
                     if (p.has_wrs && p.w_row_sum != 0.0) wmode = 1;
                     else {
-                        if (b == 0 && tid == 0) {
-                            st->halt = HALT_ERR_UNBOUNDED; st->halt_topic = t; st->halt_sweep = s; st->halt_pos = t;
-                        }
+                        if (b == 0 && tid == 0) halt_set(st, HALT_ERR_UNBOUNDED, t, s, t);
                         return;
                     }
                 }
@@ -980,12 +980,8 @@ __global__ __launch_bounds__(ONCHIP_THREADS) void k_onchip_sweeps(OnchipArgs a) 
         if (__syncthreads_or(failed)) goto sync_failed;
         const double v = wave_sum<double>(((cs[0] + cs[1]) + cs[2]) + cs[3]);
         if (tid == 0) {
-            const bool ev = (v <= 1e-10) && p.reset_method != RESET_NONE && p.resets_left > 0;
-            const bool err = !ev && !(v > 0.0);
-            if (ev || err) {
-                st->halt = ev ? HALT_EVENT_RESET_W : HALT_ERR_W_COL_ZERO;
-                st->halt_topic = tprev; st->halt_sweep = a.s_end; st->halt_pos = 0;
-            }
+            const int code = wcol_code(v, p);
+            if (code != 0) halt_set(st, code, tprev, a.s_end, 0);
         }
     }
     // the objective of the launch's last sweep (minus the constant 1/2 ||X||^2): the workgroups' shares, polled like everything
@@ -1007,7 +1003,7 @@ __global__ __launch_bounds__(ONCHIP_THREADS) void k_onchip_sweeps(OnchipArgs a) 
     return;
 sync_failed:
     if (b == 0 && tid == 0 && st->halt == 0) {
-        st->halt = HALT_ERR_GRID_SYNC; st->halt_topic = -1; st->halt_sweep = 0; st->halt_pos = 0;
+        halt_set(st, HALT_ERR_GRID_SYNC, -1, 0, 0);
     }
 }
 

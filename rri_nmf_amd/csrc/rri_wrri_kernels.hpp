@@ -476,12 +476,18 @@ __global__ __launch_bounds__(256) void k_wmcorr_cols(const unsigned* __restrict_
     }
 }
 
+// the column check of the weighted flavour on (a, f) = (sum of the new column, > 0 when a negative denominator was seen):
+// wwcol_code (rri_halt.hpp), at the position the caller names
+__device__ __forceinline__ void wcol_verdict(double a, double f, int tprev, int sweep, int pos, const KParams& p, DevState* st) {
+    const int code = wwcol_code(a, f, p);
+    if (code != 0) halt_set(st, code, tprev, sweep, pos);
+}
+
 // Both fixed-order reductions of a weighted T-row step in one launch (they were two launches of k_reduce), with the
 // correction above:  red[j] = sum_b Zpart[b][j] - tprow[j] sum_b Cpart[b][j] ,  red[ldz + j] = sum_b Z2part[b][j].
 // Cpart == NULL: no term pending.  Row-sharded runs all-reduce red afterwards: the correction is a sum over rows like z.
 // check_prev: the column verdict of the last W update (nmf.py:471-476, 793-816; k_wcheck_wcol's) is taken here, by workgroup 0,
 // at the position of THIS step -- the T-row kernel that follows returns at once when it halts the run: one launch less per step.
-__device__ __forceinline__ void wcol_verdict(double a, double f, int tprev, int sweep, int pos, const KParams& p, DevState* st);
 __global__ __launch_bounds__(1024) void k_wreduce(const double* __restrict__ Zpart, const double* __restrict__ Z2part, i64 ldz,
                                                   int nrb, int nrb2, const double* __restrict__ Cpart, int nrbc,
                                                   const double* __restrict__ tprow, double* __restrict__ red,
@@ -563,8 +569,6 @@ __global__ __launch_bounds__(128) void k_wtrow(const double* __restrict__ T, i64
     if (tid == 0) { tpart[blockIdx.x] = s; flags[blockIdx.x] = ng > 0.0 ? 1 : 0; }
 }
 
-__device__ __forceinline__ void wcol_verdict(double a, double f, int tprev, int sweep, int pos, const KParams& p, DevState* st);
-
 // Where few row blocks leave partial column sums (pattern-only handles: one per 10240 rows; small dense problems), the column
 // verdict of the last W update (k_wcheck_wcol), the two reductions (k_reduce on Zpart and Z2part) and k_wtrow are ONE launch:
 // four dependent 5-us kernels per topic step become one (round 3: the six small kernels between two passes were 34 us of a
@@ -586,11 +590,9 @@ __global__ __launch_bounds__(128) void k_wtrow_small(const double* __restrict__ 
         double f = ordered_sum<8>(Gpart + k, k + 2, tid, nwb, 128);
         a = block_sum(a, scratch);
         f = block_sum(f, scratch);
-        const bool unb = f > 0.0 && !p.has_wrs;
-        const bool ev = (a <= 1e-10) && p.reset_method != RESET_NONE && p.resets_left > 0;
-        const bool err = !ev && !(a > 0.0);
-        if (unb || ev || err) {
-            if (blockIdx.x == 0 && tid == 0) wcol_verdict(a, f, tprev, sweep, t, p, st);
+        const int code = wwcol_code(a, f, p);
+        if (code != 0) {
+            if (blockIdx.x == 0 && tid == 0) halt_set(st, code, tprev, sweep, t);
             return;
         }
     }
@@ -635,7 +637,7 @@ __global__ __launch_bounds__(1024) void k_wtrow_final(double* __restrict__ T, i6
     const double anyneg = block_sum(pf, scratch);
     const bool project = p.project_T && p.has_trs;
     if (anyneg > 0.0 && !project && !p.has_trs) {     // any(c<0) and s is None and ub is None
-        if (tid == 0) { st->halt = HALT_ERR_UNBOUNDED; st->halt_topic = t; st->halt_sweep = sweep; st->halt_pos = t; }
+        if (tid == 0) halt_set(st, HALT_ERR_UNBOUNDED, t, sweep, t);
         return;
     }
     double sumT = nx;
@@ -648,15 +650,12 @@ __global__ __launch_bounds__(1024) void k_wtrow_final(double* __restrict__ T, i6
         for (int j = tid; j < d; j += blockDim.x) s2 += xraw[j];
         sumT = block_sum(s2, scratch);
     }
-    bool event = false;
-    if (sumT > 1e-10 || p.reset_method == RESET_NONE) {
+    if (trow_kept(sumT, p)) {
         if (p.has_trs && p.t_row_sum != 0.0 && p.project_T && fabs(sumT - p.t_row_sum) > 1e-15) {
             int it2 = 0;
             const double th = simplex_theta(xraw, d, p.t_row_sum, scratch, &it2);
             for (int j = tid; j < d; j += blockDim.x) xraw[j] = fmax(xraw[j] - th, 0.0);
         }
-    } else if (p.resets_left > 0) {
-        event = true;
     }
     __syncthreads();
     const double sw = scale_w ? nx : 1.0;
@@ -668,7 +667,7 @@ __global__ __launch_bounds__(1024) void k_wtrow_final(double* __restrict__ T, i6
     if (tid == 0) {
         st->nt1 = nx;
         st->sumT = sumT;
-        if (event) { st->halt = HALT_EVENT_RESET_T; st->halt_topic = t; st->halt_sweep = sweep; st->halt_pos = t; }
+        if (trow_resets(sumT, p)) halt_set(st, HALT_EVENT_RESET_T, t, sweep, t);
     }
 }
 
@@ -701,22 +700,6 @@ __global__ __launch_bounds__(256) void k_wwcol(double* __restrict__ Wt, i64 ldw,
         double* gp = Gpart + (i64)blockIdx.x * (k + 2);
         gp[k] = ng;
         gp[k + 1] = sw;
-    }
-}
-
-// column check for the weighted flavour: unbounded (negative denominator without ub) first, then the
-// reset / assert logic of k_check_wcol.  (a, f) = (sum of the new column, 1 when a negative denominator was seen).
-__device__ __forceinline__ void wcol_verdict(double a, double f, int tprev, int sweep, int pos, const KParams& p,
-                                             DevState* st) {
-    if (f > 0.0 && !p.has_wrs) {
-        st->halt = HALT_ERR_UNBOUNDED; st->halt_topic = tprev; st->halt_sweep = sweep; st->halt_pos = pos;
-        return;
-    }
-    const bool ev = (a <= 1e-10) && p.reset_method != RESET_NONE && p.resets_left > 0;
-    const bool err = !ev && !(a > 0.0);
-    if (ev || err) {
-        st->halt = ev ? HALT_EVENT_RESET_W : HALT_ERR_W_COL_ZERO;
-        st->halt_topic = tprev; st->halt_sweep = sweep; st->halt_pos = pos;
     }
 }
 
