@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "rri_hip.h"
+#include "rri_pick.hpp"
 #include "rri_kernels.hpp"
 #include "rri_wrri_kernels.hpp"
 #include "rri_sparse_kernels.hpp"
@@ -672,8 +673,7 @@ struct LaunchX {
                          const TgramJob& job = TgramJob{}) {
         constexpr int U = UPD > 0 ? 16 : 8;
         constexpr bool RS = UPD == 0 && DO_Y;
-        if (keep >= 0) pass_k<DO_Y, DO_Z, UPD, U, true, RS, PK>(c, Xp, ldp, trow, wc, u, job, keep);
-        else pass_k<DO_Y, DO_Z, UPD, U, false, RS, PK>(c, Xp, ldp, trow, wc, u, job, 0);
+        pick_bool(keep >= 0, [&](auto nt) { pass_k<DO_Y, DO_Z, UPD, U, nt, RS, PK>(c, Xp, ldp, trow, wc, u, job, nt ? keep : 0); });
     }
     // row dots against T[t,:] (DO_Y) and column sums against W[:,tz] (DO_Z); `job`: the Gram row of T[t,:] rides along
     template <bool DO_Y, bool DO_Z>
@@ -685,13 +685,11 @@ struct LaunchX {
                 return;
             }
         }
-        if constexpr (std::is_same<SX, float>::value) {
-            if (c->xp_valid) {
-                pass_cfg<DO_Y, DO_Z, 0, true>(c, c->X, c->ldx, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw, c->keep_q, Upd{}, job);
-                return;
-            }
-        }
-        pass_cfg<DO_Y, DO_Z, 0>(c, c->X, c->ldx, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw, c->keep_q, Upd{}, job);
+        // the packed copy of X exists for an fp32 handle only: no PK pass is built for another storage type
+        constexpr bool F32 = std::is_same<SX, float>::value;
+        pick_bool(F32 && c->xp_valid, [&](auto PK) {
+            if constexpr (F32 || !PK) pass_cfg<DO_Y, DO_Z, 0, PK>(c, c->X, c->ldx, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw, c->keep_q, Upd{}, job);
+        });
     }
     // explicit-residual schedule: the same products over the stored residual R (c->E, stride LD)
     static void rpass_colsums(rri_ctx* c, int tz) {
@@ -703,38 +701,27 @@ struct LaunchX {
     static void rank_update(rri_ctx* c, void* R, i64 ldr, const Upd& u, const double* trow, const double* wc,
                             const TgramJob& job = TgramJob{}) {
         TimedScope ts(c, 3);
-        if (u.a2) pass_cfg<true, true, 2>(c, R, ldr, trow, wc, stream_whole(c), u, job);
-        else pass_cfg<true, true, 1>(c, R, ldr, trow, wc, stream_whole(c), u, job);
-    }
-    template <bool DO_Y, bool DO_Z, bool UPD2, bool WRITE, bool MBITS, int U, bool RS>
-    static void wpass_k(rri_ctx* c, const double* trow, const double* wc, const double* a1, const double* b1,
-                        const double* a2, const double* b2) {
-        if constexpr (DO_Z && MBITS) {      // a sparse 0/1 mask: nw comes from k_wmcorr_cols, the pass leaves Z2part alone
-            if (nw_from_mask(c)) { wpass_k2<DO_Y, DO_Z, UPD2, WRITE, MBITS, U, RS, false>(c, trow, wc, a1, b1, a2, b2); return; }
-        }
-        wpass_k2<DO_Y, DO_Z, UPD2, WRITE, MBITS, U, RS, DO_Z>(c, trow, wc, a1, b1, a2, b2);
+        pick_int<2, 1>(u.a2 ? 2 : 1, [&](auto upd) { pass_cfg<true, true, upd>(c, R, ldr, trow, wc, stream_whole(c), u, job); });
     }
     template <bool DO_Y, bool DO_Z, bool UPD2, bool WRITE, bool MBITS, int U, bool RS, bool DO_Z2>
-    static void wpass_k2(rri_ctx* c, const double* trow, const double* wc, const double* a1, const double* b1,
-                         const double* a2, const double* b2) {
+    static void wpass_k(rri_ctx* c, const double* trow, const double* wc, const double* a1, const double* b1,
+                        const double* a2, const double* b2) {
         const int ncols = (int)std::min<i64>(c->ldx, c->LD);
         const int rot = (c->sw.pass_rot >= 0 ? c->sw.pass_rot : c->rot_r) << 27;
+        auto launch = [&](auto kernel, int grid_flags) {
+            hipLaunchKernelGGL(kernel, dim3(c->npanels * c->nrb), dim3(256), (11 * (size_t)c->rpb + 4 * 8 * 72) * sizeof(double),
+                               c->stream, (SX*)c->E, (const SX*)c->M, c->LD, c->ldm, (const unsigned*)c->Mbits, c->ldb, (int)c->n,
+                               ncols, trow, wc, a1, b1, a2, b2, c->Ypart, c->Y2part, c->Zpart, c->Z2part, c->LD, c->rpb, c->npanels,
+                               (const DevState*)c->st, grid_flags);
+        };
         if constexpr (DO_Y && WRITE && U == 4 && (DO_Z2 || !DO_Z)) {
             // the one-pass step, 4 rows in flight: the build for four waves per SIMD (the compiler's own register count, 130,
             // gives 3); the step whose nw comes from the mask (DO_Z && !DO_Z2) takes k_wpass below
-            hipLaunchKernelGGL((k_wpass_occ4<SX, DO_Y, DO_Z, UPD2, WRITE, U, true, MBITS, RS, DO_Z2>), dim3(c->npanels * c->nrb),
-                               dim3(256), (11 * (size_t)c->rpb + 4 * 8 * 72) * sizeof(double), c->stream, (SX*)c->E,
-                               (const SX*)c->M, c->LD, c->ldm, (const unsigned*)c->Mbits, c->ldb, (int)c->n, ncols, trow,
-                               wc, a1, b1, a2, b2, c->Ypart, c->Y2part, c->Zpart, c->Z2part, c->LD, c->rpb, c->npanels,
-                               (const DevState*)c->st, c->nrb | rot);
+            launch(k_wpass_occ4<SX, DO_Y, DO_Z, UPD2, WRITE, U, true, MBITS, RS, DO_Z2>, c->nrb | rot);
         } else {
-            hipLaunchKernelGGL((k_wpass<SX, DO_Y, DO_Z, UPD2, WRITE, U, true, MBITS, RS, DO_Z2>), dim3(c->npanels * c->nrb),
-                               dim3(256), (11 * (size_t)c->rpb + 4 * 8 * 72) * sizeof(double), c->stream, (SX*)c->E,
-                               (const SX*)c->M, c->LD, c->ldm, (const unsigned*)c->Mbits, c->ldb, (int)c->n, ncols, trow,
-                               wc, a1, b1, a2, b2, c->Ypart, c->Y2part, c->Zpart, c->Z2part, c->LD, c->rpb, c->npanels,
-                               (const DevState*)c->st,
-                               // interleaved row chunks for the passes that write E back (read-modify-write), as for k_pass<UPD>
-                               ((WRITE || ro_pass_interleaved(c)) ? c->nrb : 0) | rot);
+            // interleaved row chunks for the passes that write E back (read-modify-write), as for k_pass<UPD>
+            launch(k_wpass<SX, DO_Y, DO_Z, UPD2, WRITE, U, true, MBITS, RS, DO_Z2>,
+                   ((WRITE || ro_pass_interleaved(c)) ? c->nrb : 0) | rot);
         }
     }
     // Rows in flight.  The one-pass step (row products and a write): 4, DPP row sums -- 1.458 ms at BASELINE config 5 against
@@ -747,13 +734,20 @@ struct LaunchX {
                       const double* a2, const double* b2) {
         TimedScope ts(c, 3);
         if (c->sparse) { sp_wpass<DO_Y, DO_Z, UPD2, WRITE>(c, trow, wc, a1, b1, a2, b2); return; }
-        if constexpr (DO_Y && WRITE) {
-            if (c->Mbits) wpass_k<DO_Y, DO_Z, UPD2, WRITE, true, 4, false>(c, trow, wc, a1, b1, a2, b2);
-            else wpass_k<DO_Y, DO_Z, UPD2, WRITE, false, 4, false>(c, trow, wc, a1, b1, a2, b2);
-        } else {
-            if (c->Mbits) wpass_k<DO_Y, DO_Z, UPD2, WRITE, true, 8, DO_Y>(c, trow, wc, a1, b1, a2, b2);
-            else wpass_k<DO_Y, DO_Z, UPD2, WRITE, false, (DO_Y ? 8 : 4), DO_Y>(c, trow, wc, a1, b1, a2, b2);
-        }
+        pick_bool(c->Mbits != nullptr, [&](auto mbits) {
+            constexpr bool MBITS = mbits;
+            constexpr bool ONE = DO_Y && WRITE;
+            constexpr int U = ONE ? 4 : (MBITS || DO_Y) ? 8 : 4;
+            constexpr bool RS = !ONE && DO_Y;
+            // the second column sum rides with the first, but for a sparse 0/1 mask: there nw comes from k_wmcorr_cols and the
+            // pass leaves Z2part alone
+            bool z2 = DO_Z;
+            if constexpr (DO_Z && MBITS) z2 = !nw_from_mask(c);
+            pick_bool(z2, [&](auto do_z2) {
+                // DO_Z2 differs from DO_Z in that one case only: nothing else is ever launched, so nothing else is built
+                if constexpr (do_z2 == DO_Z || (DO_Z && MBITS)) wpass_k<DO_Y, DO_Z, UPD2, WRITE, MBITS, U, RS, do_z2>(c, trow, wc, a1, b1, a2, b2);
+            });
+        });
     }
     // c = M^T (wn .* dw) as row-block partials in Cpart (k_wmcorr): the correction of the column sums a one-pass topic step
     // leaves behind.  Geometry: ~4 workgroups per CU, row blocks of a multiple of 64 rows, at most 4096 (32 KiB of LDS).
@@ -794,12 +788,14 @@ struct LaunchX {
             c->wcorr_nrb = (int)nrb;
             const dim3 grid((unsigned)(npg * nrb));
             const size_t sh = (size_t)rpb * sizeof(double) * ((dw && nw) ? 2 : 1);
-#define RRI_WMC(HD, NW_) hipLaunchKernelGGL((k_wmcorr_cols<HD, NW_>), grid, dim3(256), sh, c->stream, (const unsigned*)c->Mcols, c->LD, \
-                                            (int)c->n, (int)c->LD, wn, dw, c->Cpart, c->N2part, c->LD, (int)rpb, npg, (const DevState*)c->st)
-            if (dw && nw) RRI_WMC(true, true);
-            else if (dw) RRI_WMC(true, false);
-            else if (nw) RRI_WMC(false, true);
-#undef RRI_WMC
+            pick_bool(dw != nullptr, [&](auto has_dw) {
+                pick_bool(nw, [&](auto has_nw) {
+                    // nothing pending and no nw wanted: nothing is launched, and no such kernel is built
+                    if constexpr (has_dw || has_nw)
+                        hipLaunchKernelGGL((k_wmcorr_cols<has_dw, has_nw>), grid, dim3(256), sh, c->stream, (const unsigned*)c->Mcols, c->LD,
+                                           (int)c->n, (int)c->LD, wn, dw, c->Cpart, c->N2part, c->LD, (int)rpb, npg, (const DevState*)c->st);
+                });
+            });
             return;
         }
         if (!dw) return;
@@ -834,12 +830,7 @@ struct LaunchX {
     static void sp_blk(rri_ctx* c, int which, const double* B1, const double* B2, const double* V, const double* A1,
                        const double* A2, double* S1, double* S2, i64 lds) {
         const rri_ctx::SpCopy& cp = c->sp[which];
-        switch (cp.lps) {
-            case 8: sp_blk_k<DO_S, UPD2, WRITE, 8>(c, cp, B1, B2, V, A1, A2, S1, S2, lds); break;
-            case 16: sp_blk_k<DO_S, UPD2, WRITE, 16>(c, cp, B1, B2, V, A1, A2, S1, S2, lds); break;
-            case 32: sp_blk_k<DO_S, UPD2, WRITE, 32>(c, cp, B1, B2, V, A1, A2, S1, S2, lds); break;
-            default: sp_blk_k<DO_S, UPD2, WRITE, 64>(c, cp, B1, B2, V, A1, A2, S1, S2, lds); break;
-        }
+        pick_int<8, 16, 32, 64>(cp.lps, [&](auto lps) { sp_blk_k<DO_S, UPD2, WRITE, lps>(c, cp, B1, B2, V, A1, A2, S1, S2, lds); });
     }
     // the same operation as wpass on the two copies of the pattern residual: row products from the row copy
     // (one Ypart "panel" per column block), column sums from the column copy (one Zpart row per row block)
@@ -871,6 +862,19 @@ struct LaunchX {
         const int bwmax = std::max(DO_Y ? c->sp[0].bw : 0, DO_Z ? c->sp[1].bw : 0);
         hipLaunchKernelGGL((k_spx_pass<SX>), dim3(items), dim3(1024), spx_lds_bytes(bwmax), c->stream, a,
                            (const DevState*)c->st);
+    }
+    // k_spx_rowtot (totals) or k_spx_scale on the canonical CSR: one group of 8 lanes per row, a whole wave from 64 entries per
+    // row on -- the summation order of a row is fixed by the shape
+    static void spx_scale(rri_ctx* c, const double* sdev, double* tot, unsigned long long* nzero, bool totals) {
+        pick_int<64, 8>(c->nnz / std::max<i64>(c->n, 1) >= 64 ? 64 : 8, [&](auto LPS) {
+            const unsigned nb = (unsigned)((c->n + 256 / LPS - 1) / (256 / LPS));
+            if (totals)
+                hipLaunchKernelGGL((k_spx_rowtot<SX, LPS>), dim3(nb), dim3(256), 0, c->stream, (const i64*)c->sp_rowptr,
+                                   (const int*)c->sp_col, (const SX*)c->sp_x, c->n, sdev, tot, nzero);
+            else
+                hipLaunchKernelGGL((k_spx_scale<SX, LPS>), dim3(nb), dim3(256), 0, c->stream, (const i64*)c->sp_rowptr,
+                                   (const int*)c->sp_col, (SX*)c->sp_x, c->n, sdev, (const double*)tot);
+        });
     }
     static void spx_xtt(rri_ctx* c, const double* Tm, int m, double* out) {   // out (m x n) = (X Tm^T)^T on the CSR
         const i64 total = (i64)m * c->d;
@@ -947,10 +951,7 @@ struct LaunchX {
             const int mm = std::min(64, m - l0);
             const double* Tp = Tm + (i64)l0 * c->LD;
             double* op = out + (i64)l0 * c->ldw;
-            if (mm <= 16) xtt_mfma_k<1>(c, Tp, mm, op);
-            else if (mm <= 32) xtt_mfma_k<2>(c, Tp, mm, op);
-            else if (mm <= 48) xtt_mfma_k<3>(c, Tp, mm, op);
-            else xtt_mfma_k<4>(c, Tp, mm, op);
+            pick_int<1, 2, 3, 4>((mm + 15) / 16, [&](auto nt) { xtt_mfma_k<nt>(c, Tp, mm, op); });      // 16 rows of Tm per tile
         }
     }
     static void xtt(rri_ctx* c) {
@@ -976,95 +977,59 @@ struct LaunchX {
     static size_t resid_shmem(const rri_ctx* c) {
         return ((size_t)(resid_w_resident(c) ? c->k : 32) * 64 + 32 * 64) * sizeof(double) + 64 * 17 * sizeof(double);
     }
+    // X - W T by 64-row blocks: its row sums (rowobj, rowpos; the objective and the max-residual reset) and, with write_e, the
+    // residual itself into c->E (under the mask if masked).  A read-only handle has no mask and writes nothing, whatever is
+    // asked: MASKED = WRITE_E = false with null mask and E arguments is all it launches, and all that is built for it.
     static void resid(rri_ctx* c, bool masked, bool write_e, double* rowobj, double* rowpos) {
-        if constexpr (RO) {
-            resid_ro(c, rowobj, rowpos);       // no mask, nothing written: the two things a read-only handle asks of the residual
-            return;
-        } else {
-            resid_rw(c, masked, write_e, rowobj, rowpos);
+        if constexpr (!RO) {
+            if (c->sparse) { sp_resid(c, write_e, rowobj, rowpos); return; }   // outside the pattern nothing contributes
         }
-    }
-    // the row sums of the residual alone (objective, max-residual reset): MASKED = false, WRITE_E = false
-    static void resid_ro(rri_ctx* c, double* rowobj, double* rowpos) {
-        const unsigned nb = (unsigned)((c->n + 63) / 64);
-        if (c->k <= 64) {
-            const int ks = c->k <= 16 ? 4 : c->k <= 32 ? 8 : c->k <= 48 ? 12 : c->k <= 52 ? 13 : 16;
-            const size_t shm = 2 * (size_t)(4 * ks) * RESID_TS * sizeof(double);
-#define RRI_RESID_RO(KS_)                                                                                                    \
-    hipLaunchKernelGGL((k_resid_mfma<SX, false, false, KS_, 4, true>), dim3(nb, 1u), dim3(256), shm, c->stream, (const SX*)c->X, \
-                       c->ldx, (const SX*)nullptr, (i64)0, (const unsigned*)nullptr, (i64)0, (const double*)c->W, c->ldw,        \
-                       (const double*)c->T, c->LD, (int)c->n, (int)c->d, c->k, rowobj, rowpos, (SX*)nullptr, c->LD,              \
-                       (int)round_up(c->d, 64))
-            switch (ks) {
-                case 4: RRI_RESID_RO(4); break;
-                case 8: RRI_RESID_RO(8); break;
-                case 12: RRI_RESID_RO(12); break;
-                case 13: RRI_RESID_RO(13); break;
-                default: RRI_RESID_RO(16); break;
-            }
-#undef RRI_RESID_RO
-            return;
-        }
-        hipLaunchKernelGGL((k_resid<SX, false, false>), dim3(nb), dim3(256), resid_shmem(c), c->stream, (const SX*)c->X, c->ldx,
-                           (const SX*)nullptr, (i64)0, (const unsigned*)nullptr, (i64)0, (const double*)c->W, c->ldw,
-                           (const double*)c->T, c->LD, (int)c->n, (int)c->d, c->k, rowobj, rowpos, (SX*)nullptr, c->LD,
-                           resid_w_resident(c) ? 1 : 0);
-    }
-    static void resid_rw(rri_ctx* c, bool masked, bool write_e, double* rowobj, double* rowpos) {
-        if (c->sparse) { sp_resid(c, write_e, rowobj, rowpos); return; }   // outside the pattern nothing contributes
+        const SX* M = RO ? nullptr : (const SX*)c->M;
+        const unsigned* Mbits = RO ? nullptr : (const unsigned*)c->Mbits;
+        SX* E = RO ? nullptr : (SX*)c->E;
+        const i64 ldm = RO ? 0 : c->ldm, ldb = RO ? 0 : c->ldb;
+        auto flavour = [&](auto&& f) {     // f(MASKED, WRITE_E)
+            if constexpr (RO) f(std::false_type{}, std::false_type{});
+            else pick_bool(masked, [&](auto mk) { pick_bool(write_e, [&](auto we) { f(mk, we); }); });
+        };
         const unsigned nb = (unsigned)((c->n + 63) / 64);
         if (c->k <= 64) {   // the k-panel product on the matrix cores
             const int ks = c->k <= 16 ? 4 : c->k <= 32 ? 8 : c->k <= 48 ? 12 : c->k <= 52 ? 13 : 16;
             const size_t shm = 2 * (size_t)(4 * ks) * RESID_TS * sizeof(double);
             const bool sums = rowobj || rowpos;      // a plain rebuild wants neither: its epilogue is convert, subtract, store
-            // column ranges per row block (the rebuild without row sums): ~12 rounds of the chip's 2 workgroups per CU or more, so
-            // that the last, partly filled round costs a twelfth and not a quarter
-            int nsplit = 1;
-            if (!sums && write_e) {
-                const i64 per_round = 2 * (i64)std::max(c->n_cu, 1);
-                nsplit = (int)std::min<i64>((c->d + 63) / 64, std::max<i64>(1, (12 * per_round + nb - 1) / nb));
-            }
-            const int dchunk = (int)round_up((c->d + nsplit - 1) / nsplit, 64);
-            const unsigned ny = (unsigned)((c->d + dchunk - 1) / dchunk);
-#define RRI_RESID_M2(MK, WE, KS_, SM)                                                                                \
-    hipLaunchKernelGGL((k_resid_mfma<SX, MK, WE, KS_, 4, SM>), dim3(nb, (SM) ? 1u : ny), dim3(256), shm, c->stream, (const SX*)c->X, c->ldx, \
-                       (const SX*)c->M, c->ldm, (const unsigned*)c->Mbits, c->ldb, (const double*)c->W, c->ldw,      \
-                       (const double*)c->T, c->LD, (int)c->n, (int)c->d, c->k, rowobj, rowpos, (SX*)c->E, c->LD, (SM) ? (int)round_up(c->d, 64) : dchunk)
-// a residual written without its row sums (the per-sweep rebuild of the explicit-residual schedule) skips them; !(WE)
-// keeps the first branch from instantiating a kernel that no WRITE_E = false caller can reach
-#define RRI_RESID_M(MK, WE, KS_)                           \
-    do {                                                   \
-        if (WE && !sums) RRI_RESID_M2(MK, WE, KS_, !(WE)); \
-        else RRI_RESID_M2(MK, WE, KS_, true);              \
-    } while (0)
-#define RRI_RESID_K(MK, WE)                          \
-    switch (ks) {                                    \
-        case 4: RRI_RESID_M(MK, WE, 4); break;       \
-        case 8: RRI_RESID_M(MK, WE, 8); break;       \
-        case 12: RRI_RESID_M(MK, WE, 12); break;     \
-        case 13: RRI_RESID_M(MK, WE, 13); break;     \
-        default: RRI_RESID_M(MK, WE, 16); break;     \
-    }
-            if (masked && write_e) RRI_RESID_K(true, true)
-            else if (masked) RRI_RESID_K(true, false)
-            else if (write_e) RRI_RESID_K(false, true)
-            else RRI_RESID_K(false, false)
-#undef RRI_RESID_K
-#undef RRI_RESID_M
-#undef RRI_RESID_M2
+            flavour([&](auto mk, auto we) {
+                constexpr bool MK = mk, WE = we;
+                pick_int<4, 8, 12, 13, 16>(ks, [&](auto KS) {
+                    // a residual written without its row sums (the per-sweep rebuild of the explicit-residual schedule) skips them
+                    pick_bool(sums || !WE, [&](auto sm) {
+                        constexpr bool SM = sm;
+                        // SM = false exists only for WRITE_E = true: no WRITE_E = false caller can reach it, so it is not built
+                        if constexpr (SM || WE) {
+                            unsigned ny = 1u;
+                            int dchunk = (int)round_up(c->d, 64);
+                            if constexpr (!SM) {
+                                // column ranges per row block: ~12 rounds of the chip's 2 workgroups per CU or more, so that the
+                                // last, partly filled round costs a twelfth and not a quarter
+                                const i64 per_round = 2 * (i64)std::max(c->n_cu, 1);
+                                const int nsplit = (int)std::min<i64>((c->d + 63) / 64, std::max<i64>(1, (12 * per_round + nb - 1) / nb));
+                                dchunk = (int)round_up((c->d + nsplit - 1) / nsplit, 64);
+                                ny = (unsigned)((c->d + dchunk - 1) / dchunk);
+                            }
+                            hipLaunchKernelGGL((k_resid_mfma<SX, MK, WE, KS, 4, SM>), dim3(nb, ny), dim3(256), shm, c->stream,
+                                               (const SX*)c->X, c->ldx, M, ldm, Mbits, ldb, (const double*)c->W, c->ldw,
+                                               (const double*)c->T, c->LD, (int)c->n, (int)c->d, c->k, rowobj, rowpos, E, c->LD, dchunk);
+                        }
+                    });
+                });
+            });
             return;
         }
         const size_t sh = resid_shmem(c);
-#define RRI_RESID(MK, WE)                                                                                       \
-    hipLaunchKernelGGL((k_resid<SX, MK, WE>), dim3(nb), dim3(256), sh, c->stream, (const SX*)c->X, c->ldx,      \
-                       (const SX*)c->M, c->ldm, (const unsigned*)c->Mbits, c->ldb, (const double*)c->W, c->ldw,   \
-                       (const double*)c->T, c->LD, (int)c->n, (int)c->d, c->k, rowobj, rowpos, (SX*)c->E, c->LD,       \
-                       resid_w_resident(c) ? 1 : 0)
-        if (masked && write_e) RRI_RESID(true, true);
-        else if (masked) RRI_RESID(true, false);
-        else if (write_e) RRI_RESID(false, true);
-        else RRI_RESID(false, false);
-#undef RRI_RESID
+        flavour([&](auto mk, auto we) {
+            hipLaunchKernelGGL((k_resid<SX, mk, we>), dim3(nb), dim3(256), sh, c->stream, (const SX*)c->X, c->ldx, M, ldm, Mbits, ldb,
+                               (const double*)c->W, c->ldw, (const double*)c->T, c->LD, (int)c->n, (int)c->d, c->k, rowobj, rowpos, E,
+                               c->LD, resid_w_resident(c) ? 1 : 0);
+        });
     }
     static void reset_row(rri_ctx* c) {
         if constexpr (!RO) {
@@ -1233,12 +1198,22 @@ struct LK {  // float64-only kernels
 };
 
 // ---- upload / download with conversion -------------------------------------------------------
-template <typename Src, typename Dst, bool TR>
-void launch_convert(rri_ctx* c, const void* src, i64 lds_, void* dst, i64 ldd, i64 rows, i64 cols) {
+// dst (stride ldd) <- src (rows x cols, stride lds_), transposed if asked (dst is then cols x rows); the element types by
+// their dtype codes, float32 or float64 each
+void launch_convert(rri_ctx* c, int src_dtype, int dst_dtype, bool transpose, const void* src, i64 lds_, void* dst, i64 ldd,
+                    i64 rows, i64 cols) {
     const i64 total = rows * cols;
     const unsigned nb = (unsigned)std::min<i64>(4096, (total + 255) / 256);
-    hipLaunchKernelGGL((k_convert2d<Src, Dst, TR>), dim3(nb ? nb : 1), dim3(256), 0, c->stream, (const Src*)src,
-                       lds_, (Dst*)dst, ldd, rows, cols);
+    pick_type<float, double>(src_dtype, [&](auto s) {
+        typedef typename decltype(s)::type Src;
+        pick_type<float, double>(dst_dtype, [&](auto d) {
+            typedef typename decltype(d)::type Dst;
+            pick_bool(transpose, [&](auto tr) {
+                hipLaunchKernelGGL((k_convert2d<Src, Dst, tr>), dim3(nb ? nb : 1), dim3(256), 0, c->stream, (const Src*)src,
+                                   lds_, (Dst*)dst, ldd, rows, cols);
+            });
+        });
+    });
 }
 
 // host (rows x cols, stride ld; float32, float64 or float16) -> device float16 (the X of an RRI_F16 handle): one rounding to
@@ -1255,13 +1230,11 @@ rri_status to_device_half(rri_ctx* c, const void* host, i64 ld, int host_dtype, 
     HIPCHK(c, tmp.alloc((size_t)rows * cols * hs));
     HIPCHK(c, part.alloc((size_t)nb * 3 * sizeof(double)));
     HIPCHK(c, hipMemcpy2DAsync(tmp.p, cols * hs, host, ld * hs, cols * hs, rows, hipMemcpyHostToDevice, c->stream));
-#define RRI_HALF(SRC)                                                                                                  \
-    hipLaunchKernelGGL((k_store_half<SRC>), dim3(nb), dim3(256), 0, c->stream, (const SRC*)tmp.p, cols, (_Float16*)dev, ldd, \
-                       rows, cols, (double*)part.p)
-    if (host_dtype == RRI_F32) RRI_HALF(float);
-    else if (host_dtype == RRI_F64) RRI_HALF(double);
-    else RRI_HALF(_Float16);
-#undef RRI_HALF
+    pick_type<float, double, _Float16>(host_dtype, [&](auto src) {
+        typedef typename decltype(src)::type Src;
+        hipLaunchKernelGGL((k_store_half<Src>), dim3(nb), dim3(256), 0, c->stream, (const Src*)tmp.p, cols, (_Float16*)dev, ldd,
+                           rows, cols, (double*)part.p);
+    });
     std::vector<double> h((size_t)nb * 3);
     HIPCHK(c, hipMemcpyAsync(h.data(), part.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1303,17 +1276,7 @@ rri_status to_device(rri_ctx* c, const void* host, i64 ld, int host_dtype, void*
     hipError_t e = hipMemcpy2DAsync(tmp.p, cols * hs, host, ld * hs, cols * hs, rows, hipMemcpyHostToDevice,
                                     c->stream);
     if (e == hipSuccess) {
-        const bool hf = host_dtype == RRI_F32, df = dev_dtype == RRI_F32;
-#define RRI_CONV(SRC, DST)                                                                  \
-    do {                                                                                    \
-        if (transpose) launch_convert<SRC, DST, true>(c, tmp.p, cols, dev, ldd, rows, cols);  \
-        else launch_convert<SRC, DST, false>(c, tmp.p, cols, dev, ldd, rows, cols);           \
-    } while (0)
-        if (hf && df) RRI_CONV(float, float);
-        else if (hf) RRI_CONV(float, double);
-        else if (df) RRI_CONV(double, float);
-        else RRI_CONV(double, double);
-#undef RRI_CONV
+        launch_convert(c, host_dtype, dev_dtype, transpose, tmp.p, cols, dev, ldd, rows, cols);
         e = hipStreamSynchronize(c->stream);
     }
     if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
@@ -1336,20 +1299,8 @@ rri_status to_host(rri_ctx* c, const void* dev, i64 ldd, void* host, i64 ld, int
     }
     DevTmp tmp;
     HIPCHK(c, tmp.alloc((size_t)rows * cols * hs));
-    {
-        const bool hf = host_dtype == RRI_F32, df = dev_dtype == RRI_F32;
-        // source is the device image; for a transposed image its shape is cols x rows
-#define RRI_CONV(SRC, DST)                                                                     \
-    do {                                                                                       \
-        if (transpose) launch_convert<SRC, DST, true>(c, dev, ldd, tmp.p, cols, cols, rows);   \
-        else launch_convert<SRC, DST, false>(c, dev, ldd, tmp.p, cols, rows, cols);            \
-    } while (0)
-        if (df && hf) RRI_CONV(float, float);
-        else if (df) RRI_CONV(float, double);
-        else if (hf) RRI_CONV(double, float);
-        else RRI_CONV(double, double);
-#undef RRI_CONV
-    }
+    // source is the device image; for a transposed image its shape is cols x rows
+    launch_convert(c, dev_dtype, host_dtype, transpose, dev, ldd, tmp.p, cols, transpose ? cols : rows, transpose ? rows : cols);
     hipError_t e = hipMemcpy2DAsync(host, ld * hs, tmp.p, cols * hs, cols * hs, rows, hipMemcpyDeviceToHost,
                                     c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1668,11 +1619,13 @@ void enqueue_wW_half(rri_ctx* c, int sweep, int t, bool defer_check = false) {
         const double* wt_t = c->W + (i64)t * c->ldw;
         const double* wnx = c->W + (i64)tn * c->ldw;
         const bool cn = (k > 1) && !c->prm.fix_T;
-        if (!pend_w && b1 == c->zeros) {
-            if (cn) DISPATCH(c, (L::template wpass<true, true, false, false>(c, trow, wnx, c->zeros, c->zeros, nullptr, nullptr)));
-            else DISPATCH(c, (L::template wpass<true, false, false, false>(c, trow, nullptr, c->zeros, c->zeros, nullptr, nullptr)));
-        } else if (cn) DISPATCH(c, (L::template wpass<true, true, true, true>(c, trow, wnx, wt_t, b1, a2, b2)));
-        else DISPATCH(c, (L::template wpass<true, false, true, true>(c, trow, nullptr, wt_t, b1, a2, b2)));
+        const bool pend = pend_w || b1 != c->zeros;
+        pick_bool(cn, [&](auto CN) {
+            pick_bool(pend, [&](auto PEND) {
+                DISPATCH(c, (L::template wpass<true, CN, PEND, PEND>(c, trow, CN ? wnx : nullptr, PEND ? wt_t : c->zeros, PEND ? b1 : c->zeros,
+                                                                     PEND ? a2 : nullptr, PEND ? b2 : nullptr)));
+            });
+        });
     }
     {
         TimedScope ts(c, 1);
@@ -1684,8 +1637,9 @@ void enqueue_wW_half(rri_ctx* c, int sweep, int t, bool defer_check = false) {
     const double* wn = c->W + (i64)tn * c->ldw;
     if (sp_merged) {
         TimedScope ts(c, 3);          // the column copy: both terms of this step, the column sums of the next topic
-        if (carry_next) DISPATCH(c, (L::template sp_blk<true, true, true>(c, 1, c->wold, c->dwv, wn, b1, trow, c->Zpart, c->Z2part, c->LD)));
-        else DISPATCH(c, (L::template sp_blk<false, true, true>(c, 1, c->wold, c->dwv, wn, b1, trow, c->Zpart, c->Z2part, c->LD)));
+        pick_bool(carry_next, [&](auto CN) {
+            DISPATCH(c, (L::template sp_blk<CN, true, true>(c, 1, c->wold, c->dwv, wn, b1, trow, c->Zpart, c->Z2part, c->LD)));
+        });
     }
     changed(c, CH_W_COL | CH_E_FOLLOWS);
     c->dw_pending = true;     // dwv x T[t,:]: folded in by the pass of the next step (dense: into E, under the mask; pattern-only: the row copy)
@@ -1933,10 +1887,13 @@ constexpr int ONCHIP_MAX_RPW = 20;    // rows per wave held in registers (float4
 // (round 4, compiler's resource report: plain 18 rows / 253 VGPRs, with the projection 14 rows / 249; 20 rows spilled 10 / 16 -- and
 // 68 in round 3's build: the allocation moves with every edit, the report of `python -m rri_nmf_amd.build --report` is the record)
 constexpr int ONCHIP_MAX_RPW_K64 = 18, ONCHIP_MAX_RPW_K64_PROJ = 14;
-int onchip_rpw_cap(const rri_ctx* c, bool proj) {
-    const int cap = c->k > ONCHIP_SMALL_K ? (proj ? ONCHIP_MAX_RPW_K64_PROJ : ONCHIP_MAX_RPW_K64) : ONCHIP_MAX_RPW;
-    return c->dtype == RRI_F32 ? cap : cap / 2;       // float64 X: 8 registers per row and lane
+// The rows per wave an instantiation of k_onchip_sweeps holds (its RPW): every (storage type, PROJ, KT) is built twice, for
+// `few` rows (8) and for the most the registers take, so that a small problem does not carry the large build's registers
+constexpr int onchip_rpw(bool f32, bool proj, int kt, bool few) {
+    const int rows = few ? 8 : kt == 8 ? (proj ? ONCHIP_MAX_RPW_K64_PROJ : ONCHIP_MAX_RPW_K64) : ONCHIP_MAX_RPW;
+    return f32 ? rows : rows / 2;       // float64 X: 8 registers per row and lane
 }
+int onchip_rpw_cap(const rri_ctx* c, bool proj) { return onchip_rpw(c->dtype == RRI_F32, proj, c->k > ONCHIP_SMALL_K ? 8 : 3, false); }
 bool onchip_geometry(const rri_ctx* c, OnchipGeom* g) {
     const bool proj = !LK::light(c);                   // the projection stage stages the whole T row per worker: d <= 1024
     if (c->LD > (proj ? 1024 : 2048) || c->n_cu < 1) return false;
@@ -1993,7 +1950,7 @@ hipError_t onchip_ordered_launch(rri_ctx* c, const void* fn, int grid, size_t sh
     if (le == hipSuccess && g_onchip_last[dv]) (void)hipEventRecord(g_onchip_last[dv], c->stream);
     return le;
 }
-template <typename SX, int RPW, bool DBG = false, bool PROJ = false, int KT = 3>
+template <typename SX, int RPW, bool DBG, bool PROJ, int KT>
 hipError_t onchip_launch(rri_ctx* c, const OnchipGeom& g, const OnchipArgs& a) {
     const void* fn = (const void*)k_onchip_sweeps<SX, RPW, DBG, PROJ, KT>;
     hipError_t e = allow_lds<k_onchip_sweeps<SX, RPW, DBG, PROJ, KT>>(c, 152 * 1024);
@@ -2083,20 +2040,23 @@ bool enqueue_onchip(rri_ctx* c, Cursor cur) {
         const bool timed = c->timing > 0 && c->timed[0].size() < 400000;
         if (timed) { tl.a = get_event(c); tl.b = get_event(c); (void)hipEventRecord(tl.a, c->stream); }
         const bool proj = !LK::light(c);          // project_T_each_iter with a t_row_sum: the topic-model instantiation
-        if (c->k > ONCHIP_SMALL_K) {              // k-term dots of 8 terms per lane (k <= 64); no diagnostics build
-            if (c->dtype == RRI_F64) {
-                if (proj) e = g.rpw <= 4 ? onchip_launch<double, 4, false, true, 8>(c, g, a) : onchip_launch<double, ONCHIP_MAX_RPW_K64_PROJ / 2, false, true, 8>(c, g, a);
-                else e = g.rpw <= 4 ? onchip_launch<double, 4, false, false, 8>(c, g, a) : onchip_launch<double, ONCHIP_MAX_RPW_K64 / 2, false, false, 8>(c, g, a);
-            } else if (proj) e = g.rpw <= 8 ? onchip_launch<float, 8, false, true, 8>(c, g, a) : onchip_launch<float, ONCHIP_MAX_RPW_K64_PROJ, false, true, 8>(c, g, a);
-            else e = g.rpw <= 8 ? onchip_launch<float, 8, false, false, 8>(c, g, a) : onchip_launch<float, ONCHIP_MAX_RPW_K64, false, false, 8>(c, g, a);
-        } else if (c->dtype == RRI_F64) {         // 8 registers per row and lane: half the rows of the fp32 instantiations
-            if (proj) e = g.rpw <= 4 ? onchip_launch<double, 4, false, true>(c, g, a) : onchip_launch<double, ONCHIP_MAX_RPW / 2, false, true>(c, g, a);
-            else e = g.rpw <= 4 ? onchip_launch<double, 4>(c, g, a) : onchip_launch<double, ONCHIP_MAX_RPW / 2>(c, g, a);
-        } else if (proj && a.dbg) e = g.rpw <= 8 ? onchip_launch<float, 8, true, true>(c, g, a) : onchip_launch<float, ONCHIP_MAX_RPW, true, true>(c, g, a);
-        else if (proj) e = g.rpw <= 8 ? onchip_launch<float, 8, false, true>(c, g, a) : onchip_launch<float, ONCHIP_MAX_RPW, false, true>(c, g, a);
-        else if (a.dbg) e = g.rpw <= 8 ? onchip_launch<float, 8, true>(c, g, a) : onchip_launch<float, ONCHIP_MAX_RPW, true>(c, g, a);
-        else if (g.rpw <= 8) e = onchip_launch<float, 8>(c, g, a);
-        else e = onchip_launch<float, ONCHIP_MAX_RPW>(c, g, a);
+        e = pick_type<double, float>(c->dtype, [&](auto sx) {
+            typedef typename decltype(sx)::type SX;
+            constexpr bool F32 = std::is_same<SX, float>::value;
+            return pick_bool(c->k > ONCHIP_SMALL_K, [&](auto large_k) {
+                constexpr int KT = large_k ? 8 : 3;      // k-term dots of 8 terms per lane (k <= 64), or of 3
+                return pick_bool(proj, [&](auto PROJ) {
+                    return pick_bool(g.rpw <= onchip_rpw(F32, PROJ, KT, true), [&](auto few) {
+                        constexpr int RPW = onchip_rpw(F32, PROJ, KT, few);
+                        return pick_bool(a.dbg != nullptr, [&](auto dbg) {
+                            // the diagnostics build exists for fp32, KT = 3 only: everywhere else a.dbg is ignored
+                            constexpr bool DBG = dbg && F32 && KT == 3;
+                            return onchip_launch<SX, RPW, DBG, PROJ, KT>(c, g, a);
+                        });
+                    });
+                });
+            });
+        });
         if (timed) { (void)hipEventRecord(tl.b, c->stream); c->timed[0].push_back(tl); }
     }
     if (e != hipSuccess) {
@@ -2521,13 +2481,13 @@ rri_status rri_upload_X_csr(rri_ctx* c, const int64_t* indptr, const int32_t* in
     c->ldx = c->LD;
     HIPCHK(c, hipMemsetAsync(c->X, 0, (size_t)c->n * c->LD * c->es, c->stream));
     const unsigned nb = (unsigned)((c->n + 3) / 4);
-    if (c->dtype == RRI_F32) {
-        if (data_dtype == RRI_F32) hipLaunchKernelGGL((k_csr_scatter<float, float>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const float*)dv.data.p, c->n, (float*)c->X, c->ldx);
-        else hipLaunchKernelGGL((k_csr_scatter<double, float>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const double*)dv.data.p, c->n, (float*)c->X, c->ldx);
-    } else {
-        if (data_dtype == RRI_F32) hipLaunchKernelGGL((k_csr_scatter<float, double>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const float*)dv.data.p, c->n, (double*)c->X, c->ldx);
-        else hipLaunchKernelGGL((k_csr_scatter<double, double>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const double*)dv.data.p, c->n, (double*)c->X, c->ldx);
-    }
+    pick_type<float, double>(data_dtype, [&](auto s) {
+        typedef typename decltype(s)::type Src;
+        pick_type<float, double>(c->dtype, [&](auto d) {
+            typedef typename decltype(d)::type Dst;
+            hipLaunchKernelGGL((k_csr_scatter<Src, Dst>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const Src*)dv.data.p, c->n, (Dst*)c->X, c->ldx);
+        });
+    });
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_X = true;
     changed(c, CH_X);
@@ -2615,8 +2575,10 @@ rri_status rri_upload_mask_csr_pattern(rri_ctx* c, const int64_t* indptr, const 
     const size_t words = (size_t)((c->n + 7) / 8) * c->ldb;
     HIPCHK(c, dev_alloc(c, c->Mbits, words * sizeof(unsigned), true));
     const unsigned nb = (unsigned)((c->n + 3) / 4);
-    if (data_dtype == RRI_F32) hipLaunchKernelGGL((k_csr_pattern_bits<float>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const float*)dv.data.p, c->n, c->Mbits, c->ldb);
-    else hipLaunchKernelGGL((k_csr_pattern_bits<double>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const double*)dv.data.p, c->n, c->Mbits, c->ldb);
+    pick_type<float, double>(data_dtype, [&](auto s) {
+        typedef typename decltype(s)::type Src;
+        hipLaunchKernelGGL((k_csr_pattern_bits<Src>), dim3(nb), dim3(256), 0, c->stream, dv.ip(), dv.ix(), (const Src*)dv.data.p, c->n, c->Mbits, c->ldb);
+    });
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_M = true;
     changed(c, CH_M);
@@ -2637,11 +2599,7 @@ rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indi
     dev_adopt(c, c->sp_col, dv.indices);
     HIPCHK(c, dev_alloc(c, c->sp_x, (size_t)std::max<i64>(nnz, 1) * c->es));
     if (nnz > 0) {   // values -> storage type (dv.data holds them in the caller's type)
-        const bool hf = data_dtype == RRI_F32, df = c->dtype == RRI_F32;
-        if (hf && df) launch_convert<float, float, false>(c, dv.data.p, nnz, c->sp_x, nnz, 1, nnz);
-        else if (hf) launch_convert<float, double, false>(c, dv.data.p, nnz, c->sp_x, nnz, 1, nnz);
-        else if (df) launch_convert<double, float, false>(c, dv.data.p, nnz, c->sp_x, nnz, 1, nnz);
-        else launch_convert<double, double, false>(c, dv.data.p, nnz, c->sp_x, nnz, 1, nnz);
+        launch_convert(c, data_dtype, c->dtype, false, dv.data.p, nnz, c->sp_x, nnz, 1, nnz);
     }
     // the two blocked copies: counting sort on the host, stable, so offsets ascend inside a segment
     for (int w = 0; w < 2; ++w) {
@@ -3791,25 +3749,6 @@ rri_status rri_csr_column_positive_counts(rri_ctx* c, double* df_out) {
     return RRI_OK;
 }
 
-extern "C++" {
-// one group of 8 lanes per row, a whole wave from 64 entries per row on: the summation order of a row is fixed by the shape
-template <typename SX, int LPS>
-static void launch_spx_scale_lps(rri_ctx* c, const double* sdev, double* tot, unsigned long long* nzero, bool totals) {
-    const unsigned nb = (unsigned)((c->n + 256 / LPS - 1) / (256 / LPS));
-    if (totals)
-        hipLaunchKernelGGL((k_spx_rowtot<SX, LPS>), dim3(nb), dim3(256), 0, c->stream, (const i64*)c->sp_rowptr,
-                           (const int*)c->sp_col, (const SX*)c->sp_x, c->n, sdev, tot, nzero);
-    else
-        hipLaunchKernelGGL((k_spx_scale<SX, LPS>), dim3(nb), dim3(256), 0, c->stream, (const i64*)c->sp_rowptr,
-                           (const int*)c->sp_col, (SX*)c->sp_x, c->n, sdev, (const double*)tot);
-}
-template <typename SX>
-static void launch_spx_scale(rri_ctx* c, const double* sdev, double* tot, unsigned long long* nzero, bool totals) {
-    if (c->nnz / std::max<i64>(c->n, 1) >= 64) launch_spx_scale_lps<SX, 64>(c, sdev, tot, nzero, totals);
-    else launch_spx_scale_lps<SX, 8>(c, sdev, tot, nzero, totals);
-}
-}
-
 rri_status rri_csr_scale_X(rri_ctx* c, const double* col_scale, int32_t normalize_rows, int64_t* zero_rows_out) {
     CHECK_CTX(c);
     if (!c->sparse_x || !c->have_X) return fail(c, RRI_ERR_INVALID, "needs an RRI_UNWEIGHTED_SPARSE handle with an X");
@@ -3826,7 +3765,7 @@ rri_status rri_csr_scale_X(rri_ctx* c, const double* col_scale, int32_t normaliz
         HIPCHK(c, tt.alloc((size_t)c->n * sizeof(double)));
         HIPCHK(c, nz.alloc(sizeof(unsigned long long)));
         HIPCHK(c, hipMemsetAsync(nz.p, 0, sizeof(unsigned long long), c->stream));
-        DISPATCH(c, launch_spx_scale<typename L::Elem>(c, (const double*)sd.p, (double*)tt.p, (unsigned long long*)nz.p, true));
+        DISPATCH(c, L::spx_scale(c, (const double*)sd.p, (double*)tt.p, (unsigned long long*)nz.p, true));
         unsigned long long zero_rows = 0;
         HIPCHK(c, hipMemcpyAsync(&zero_rows, nz.p, sizeof(zero_rows), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3836,7 +3775,7 @@ rri_status rri_csr_scale_X(rri_ctx* c, const double* col_scale, int32_t normaliz
             return RRI_OK;
         }
     }
-    DISPATCH(c, launch_spx_scale<typename L::Elem>(c, (const double*)sd.p, (double*)tt.p, nullptr, false));
+    DISPATCH(c, L::spx_scale(c, (const double*)sd.p, (double*)tt.p, nullptr, false));
     if (c->nnz > 0)
         DISPATCH(c, for (int w = 0; w < 2; ++w)
                         hipLaunchKernelGGL((k_sp_permute<typename L::Elem>), dim3(2048), dim3(256), 0, c->stream,
