@@ -121,6 +121,8 @@ struct rri_comm {
 // What of the 256 MiB Infinity Cache the default-policy traffic of one topic step may fill, in MB (1e6 bytes): the chain's own
 // working set and, in what is left, a fixed part of X (pass_keep).  Chosen on sweeps/s by tools/pass_keep_probe.py.
 constexpr double PASS_CACHE_MB = 256.0;
+// the most rows a workgroup of the read-only pass walks on a dense fp32 handle of the Gram form: the size that streams the packed copy of X (rri_create)
+constexpr int PK_ROWS_MAX = 512;
 
 // The environment switches a handle keeps: read once, by rri_create (read_switches), so that a handle created later under
 // another environment cannot change the schedule of one that is already running (INTEGRATION.md lists them)
@@ -137,6 +139,8 @@ struct rri_switches {
     bool rot_debug = false;    // RRI_ROT_DEBUG (set): calibrate_rot prints its timings
     bool mask_bits = true;     // RRI_MASK_BITS=0: a 0/1 mask stays an fp array (no bit-packed copy)
     double pass_cache_mb = PASS_CACHE_MB;   // RRI_PASS_CACHE_MB: what of the Infinity Cache a topic step may fill (pass_keep); 0: all of X streams
+    int pk_rows = 0;           // RRI_PASS_PK_GEOM=<rows>[i|c] (diagnostics): rows per workgroup of the read-only pass (rounded up to 16, at most the
+    int pk_il = -1;            // LDS cap) and interleaved (i) or contiguous (c) chunks, for dense fp32 handles of the Gram form (rri_create)
     int x_pack = -1;           // RRI_X_PACK: the packed 28-bit copy of an fp32 X for the read-only pass (xpack_ensure): 0 never, 1 wherever the
                                // pass can read it, unset: where X does not fit the budget of pass_keep
 };
@@ -167,6 +171,7 @@ struct rri_ctx {
     // of the two for THIS handle's buffers (calibrate_rot); RRI_PASS_ROT forces one for all
     int rot_x = 0, rot_r = 0;
     bool rot_done = false;
+    int ro_il = -1;    // read-only pass: interleaved (1) or contiguous (0) row chunks forced by RRI_PASS_PK_GEOM; -1: by the workgroup count
     int keep_q = -1;   // read-only pass over X: row blocks loaded with default policy, the others non-temporally; -1: all of X plain (pass_keep)
     // the packed copy of an fp32 X that the read-only pass streams instead of X (rri_xpack.hpp; xpack_ensure): 3.5 bytes per element
     unsigned char *xp = nullptr, *xp_flags = nullptr;   // the records; one flag byte per 8-row chunk and column group (tile)
@@ -306,7 +311,7 @@ struct rri_ctx {
 };
 // read-only passes deal their row blocks as interleaved chunks only while the launch has few workgroups (the passes that write
 // the matrix back always do): ONE predicate for the launch sites and for rri_layout_info
-static inline bool ro_pass_interleaved(const rri_ctx* c) { return c->npanels * c->nrb <= 1024; }
+static inline bool ro_pass_interleaved(const rri_ctx* c) { return c->ro_il >= 0 ? c->ro_il != 0 : c->npanels * c->nrb <= 1024; }
 
 // ---- what a handle keeps between steps and calls, and what each piece was computed from ------------------------------------
 //                                              X   M   W   T   scratch  penalties
@@ -2187,6 +2192,11 @@ rri_switches read_switches() {
     if (const char* e = getenv("RRI_MASK_BITS")) sw.mask_bits = atoi(e) != 0;
     if (const char* e = getenv("RRI_PASS_CACHE_MB")) sw.pass_cache_mb = std::max(0.0, atof(e));
     if (const char* e = getenv("RRI_X_PACK")) sw.x_pack = atoi(e) != 0;
+    if (const char* e = getenv("RRI_PASS_PK_GEOM")) {
+        char* end = nullptr;
+        sw.pk_rows = (int)std::min<long>(std::max<long>(0, strtol(e, &end, 10)), 1 << 20);
+        sw.pk_il = (end && *end == 'i') ? 1 : (end && *end == 'c') ? 0 : -1;
+    }
     return sw;
 }
 
@@ -2301,6 +2311,21 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     }
     rpb = std::max<i64>(rpb, 32);
     rpb = std::min<i64>(round_up(rpb, 16), rpb_cap);
+    // A dense fp32 handle of the Gram form walks at most PK_ROWS_MAX rows per workgroup: more than that it only ever got from the
+    // LDS cap (560), which takes 1024 workgroups of 1024 columns -- an X of 2 GB and more, which streams the packed copy
+    // (xpack_ensure).  The 560 were tuned on the fp32 stream (above), and in the copy that stride is 7/8 of it.  Known at ONE
+    // shape only, BASELINE config 3, and jagged there -- engines made alternately in one process, three visits each: 560 rows
+    // 0.5758 ms per pass (0.5684 .. 0.5760), 528 0.5640, 512 0.5516 (0.5491 .. 0.5520), 496 0.5541, 480 0.5637, 448 0.5648, 400
+    // 0.5500; 560 interleaved 0.5790 (profiles/r13_xpack_refill_steps.log, tools/pk_geom_probe.py; DESIGN 4.5 has the second
+    // process, the fp32 stream at 512 rows and another shape).  The rule looks at n, d, storage and flavour only, not at
+    // RRI_X_PACK or RRI_PASS_CACHE_MB: tests/test_xpack_gpu.py and tests/test_pass_keep_gpu.py compare W, T and the objective bit
+    // for bit across those switches at 60007 x 10004, where the cap decides, so a handle must have the same geometry -- the same
+    // order of its partial sums -- with the copy and without it; it keeps it when the copy is released.  RRI_PASS_PK_GEOM
+    // (diagnostics) sets other rows and the chunk order for such handles.
+    if (dtype == RRI_F32 && !weighted && !explicit_resid && !c->sparse) {
+        rpb = c->sw.pk_rows > 0 ? std::min<i64>(round_up(std::max(c->sw.pk_rows, 16), 16), rpb_cap) : std::min<i64>(rpb, PK_ROWS_MAX);
+        if (c->sw.pk_rows > 0) c->ro_il = c->sw.pk_il;
+    }
     c->rpb = (int)rpb;
     c->nrb = (int)((n + rpb - 1) / rpb);
     if (c->sparse) {
