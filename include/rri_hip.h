@@ -68,7 +68,16 @@ enum { RRI_F32 = 0, RRI_F64 = 1,     /* storage type of X, mask, residual in HBM
         * the four other flavours; the handle refuses everything that would rewrite X or needs a mask, a residual or a CSR store
         * (rri_scale_X, rri_column_positive_counts, rri_upload_mask*, rri_bind_mask_device, rri_upload_X_csr, rri_upload_observed_csr,
         * rri_residual_*, rri_get_residual, rri_bench_*) and rri_attach_comm, and never takes the persistent on-chip path. */
-       RRI_F16 = 2 };
+       RRI_F16 = 2,
+       /* counts (unsigned bytes, 0..255) with a float64 scale per row and per column kept on the handle: the second store of a
+        * dense X that is only read.  The X every kernel sees is (C[i,j] * cscale[j]) * rscale[i], formed in float64 where it is
+        * read -- byte -> float -> double is exact -- so the store costs no rounding at all, a quarter of the fp32 bytes per pass,
+        * and tf-idf and row normalisation are two vector updates (rri_scale_X writes no matrix on such a handle).  Refused and
+        * allowed exactly as RRI_F16 is, but for the two preprocessing calls, which it takes; both scale vectors are ones after
+        * rri_create and after every rri_upload_X / rri_bind_X_device (rri_set_X_scales, rri_get_X_scales).  A scale may be zero or
+        * negative (the idf of a term that occurs in every document is a tiny negative number). */
+       /* (code 3 stays unassigned: rri_create has always refused it with RRI_ERR_INVALID) */
+       RRI_U8 = 4 };
 /* rri_create's `weighted`: the flavour of the handle */
 enum { RRI_UNWEIGHTED = 0, RRI_WEIGHTED_DENSE = 1, RRI_WEIGHTED_SPARSE = 2, RRI_UNWEIGHTED_RESIDUAL = 3,
        RRI_UNWEIGHTED_SPARSE = 4 };
@@ -102,7 +111,7 @@ typedef struct rri_event {
 
 /* ---- lifetime ------------------------------------------------------------------ */
 uint32_t   rri_abi_version(void);
-/* dtype: RRI_F32 / RRI_F64, or RRI_F16 with RRI_UNWEIGHTED (see the enum).  weighted: RRI_UNWEIGHTED; RRI_WEIGHTED_DENSE reserves the mask and masked-residual
+/* dtype: RRI_F32 / RRI_F64, or RRI_F16 / RRI_U8 with RRI_UNWEIGHTED (see the enum).  weighted: RRI_UNWEIGHTED; RRI_WEIGHTED_DENSE reserves the mask and masked-residual
  * buffers of the elementwise-weighted flavour (WRRI, nmf.py:687-701,735-746) as dense n x d arrays;
  * RRI_WEIGHTED_SPARSE keeps that flavour on a 0/1 observation pattern only (rri_upload_observed_csr).
  * RRI_UNWEIGHTED_RESIDUAL is the unweighted flavour on the EXPLICIT residual R = X - W T (kept in HBM beside X): every
@@ -126,19 +135,23 @@ const char* rri_last_error(const rri_ctx* ctx);   /* NULL ctx: error of the last
 /* ---- data: replaces the numpy arrays nmf() holds (nmf.py:272,351,867-868) --------- */
 /* host_dtype: RRI_F32 / RRI_F64 of the HOST buffer; converted to the handle's dtype.  rri_upload_X on an RRI_F16 handle also
  * takes a host buffer of halves (RRI_F16); whatever the host type, a value that is not finite as a float16 (|x| >= 65520, inf,
- * NaN) fails the call with RRI_ERR_INVALID and leaves the handle without an X. */
+ * NaN) fails the call with RRI_ERR_INVALID and leaves the handle without an X.  On an RRI_U8 handle the host buffer is RRI_F32,
+ * RRI_F64 or RRI_U8 (bytes, taken as they are); a value that is not an integer in 0..255 (fractions, negatives, inf, NaN) fails
+ * the call the same way, and a successful upload sets both scale vectors to ones. */
 rri_status rri_upload_X(rri_ctx* ctx, const void* host, int64_t ld, int32_t host_dtype);
 rri_status rri_upload_mask(rri_ctx* ctx, const void* host, int64_t ld, int32_t host_dtype); /* W_mat */
 /* Zero-copy alternative: X (and mask) already in device memory in the handle's dtype,
  * row-major with row stride ld (a multiple of 16 bytes, base 16-byte aligned).  The calls synchronise the device
  * once, so memory just produced on another stream is complete (rri_bind_mask_device reads the mask at once to
  * bit-pack it); later changes to the memory are the caller's to order against the handle's stream. */
-/* (an RRI_F16 handle binds an array of halves, e.g. a torch.float16 tensor: ld a multiple of 8 elements) */
+/* (an RRI_F16 handle binds an array of halves, e.g. a torch.float16 tensor: ld a multiple of 8 elements; an RRI_U8 handle an
+ * array of bytes, e.g. a torch.uint8 tensor: base 8-byte aligned, ld and d multiples of 8 elements; both scale vectors are ones
+ * afterwards) */
 rri_status rri_bind_X_device(rri_ctx* ctx, const void* dev, int64_t ld);
 /* What storing X cost: out[0] = sum (x - stored(x))^2, out[1] = sum x^2 over the matrix given to the last rri_upload_X of an
  * RRI_F16 handle (float64 sums in a fixed order; sqrt(out[0] / out[1]) is the relative Frobenius distance between the caller's
- * X and the X the handle factorises -- the rounding nmf() adds to a float64 run, nmf.py:272).  Zeros on float32 / float64 handles
- * and for bound arrays, which are taken as they are. */
+ * X and the X the handle factorises -- the rounding nmf() adds to a float64 run, nmf.py:272).  Zeros on float32 / float64 / uint8
+ * handles (what RRI_U8 accepts it stores exactly) and for bound arrays, which are taken as they are. */
 rri_status rri_storage_error(rri_ctx* ctx, double out[2]);
 rri_status rri_bind_mask_device(rri_ctx* ctx, const void* dev, int64_t ld);
 /* Ingestion without host densification (the reference densifies with .toarray(), sklearn_interface.py:78-102):
@@ -259,9 +272,17 @@ rri_status rri_sparse_range_finder(rri_ctx* ctx, const double* Q0, int32_t m, in
  *   rri_scale_X                 X[i,j] <- (X[i,j] * col_scale[j]) / (sum_j X[i,j] * col_scale[j] + spacing(1)) when
  *                               normalize_rows != 0 (rows summing to < 1e-10 become 1/d: normalize, matrixops.py:139-147),
  *                               else X[i,j] * col_scale[j] (X * idf, matrixops.py:172); col_scale == NULL: all ones.
- * float64 arithmetic, rounded to the handle's storage type when stored. */
+ * float64 arithmetic, rounded to the handle's storage type when stored.
+ * On an RRI_U8 handle no matrix is written: df counts the stored counts > 0 whatever the scales are, and rri_scale_X does
+ *   cscale[j] *= col_scale[j];  normalize_rows: rscale[i] *= 1 / (sum_j C[i,j] * cscale[j] * rscale[i] + spacing(1)).
+ * Counts cannot hold the dense row 1/d: when rows would sum to < 1e-10 the call changes nothing and fails with RRI_ERR_INVALID,
+ * its message (rri_last_error) starting with their number: "<count> row(s) ...". */
 rri_status rri_column_positive_counts(rri_ctx* ctx, double* df_out);
 rri_status rri_scale_X(rri_ctx* ctx, const double* col_scale, int32_t normalize_rows);
+/* The two scale vectors of an RRI_U8 handle (RRI_ERR_INVALID on every other): row_scale has n entries, col_scale d, float64 on the
+ * host.  set: NULL leaves that vector as it is; a change of a scale is a change of X.  get: NULL skips that vector. */
+rri_status rri_set_X_scales(rri_ctx* ctx, const double* row_scale, const double* col_scale);
+rri_status rri_get_X_scales(rri_ctx* ctx, double* row_out, double* col_out);
 /* The same two steps (matrixops.py:124-179) on the X of an RRI_UNWEIGHTED_SPARSE handle; RRI_ERR_INVALID on every other handle
  * and before rri_upload_X_csr.  The stored values are rewritten and both blocked copies gathered from them again.
  *   rri_csr_column_positive_counts  df[j] = number of STORED entries of column j that are > 0 (explicit zeros do not count):

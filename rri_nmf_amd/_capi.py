@@ -18,6 +18,7 @@ RRI_ERR_INVALID, RRI_ERR_HIP, RRI_ERR_UNSUPPORTED = -1, -2, -3
 RRI_ERR_UNBOUNDED, RRI_ERR_W_COL_ZERO, RRI_ERR_NOT_IMPLEMENTED, RRI_ERR_COMM = -4, -5, -6, -7
 RRI_COMM_ID_BYTES = 128
 RRI_F32, RRI_F64, RRI_F16 = 0, 1, 2   # RRI_F16: the dense X of an RRI_UNWEIGHTED handle only (include/rri_hip.h)
+RRI_U8 = 4                            # ... and so is RRI_U8: counts 0..255, one byte each, with float64 row and column scales
 # rri_create's `weighted`: the flavour of the handle
 RRI_UNWEIGHTED, RRI_WEIGHTED_DENSE, RRI_WEIGHTED_SPARSE, RRI_UNWEIGHTED_RESIDUAL, RRI_UNWEIGHTED_SPARSE = 0, 1, 2, 3, 4
 RESET_NONE, RESET_MAX_RESID_DOCUMENT, RESET_RANDOM = 0, 1, 2
@@ -88,6 +89,8 @@ PROTOTYPES = {
     'rri_sparse_range_finder': (_I32, [_P, C.POINTER(_D), _I32, _I32, _I32, C.POINTER(_D), C.POINTER(_D)]),
     'rri_column_positive_counts': (_I32, [_P, C.POINTER(_D)]),
     'rri_scale_X': (_I32, [_P, C.POINTER(_D), _I32]),
+    'rri_set_X_scales': (_I32, [_P, C.POINTER(_D), C.POINTER(_D)]),
+    'rri_get_X_scales': (_I32, [_P, C.POINTER(_D), C.POINTER(_D)]),
     'rri_csr_column_positive_counts': (_I32, [_P, C.POINTER(_D)]),
     'rri_csr_scale_X': (_I32, [_P, C.POINTER(_D), _I32, C.POINTER(_I64)]),
     'rri_comm_unique_id': (_I32, [C.POINTER(C.c_uint8)]),

@@ -176,6 +176,8 @@ struct rri_ctx {
     // the packed copy of an fp32 X that the read-only pass streams instead of X (rri_xpack.hpp; xpack_ensure): 3.5 bytes per element
     unsigned char *xp = nullptr, *xp_flags = nullptr;   // the records; one flag byte per 8-row chunk and column group (tile)
     unsigned* xp_hmax = nullptr;                        // device: the largest top byte of X inside [1, 0x7e]
+    // RRI_U8: the X every kernel sees is (C[i][j] * cscale[j]) * rscale[i]; rscale[n], cscale[LD] (pad columns: 1), ones until set
+    double *rscale = nullptr, *cscale = nullptr;
     bool xp_valid = false;      // the passes read xp: it was built from the X the handle holds and few enough tiles are flagged
     bool xp_done = false;       // ... or the question is settled for this X (not wanted, no memory, too many flagged tiles)
     int xp_base = 0;            // the window of top bytes: xp_base .. xp_base + 14
@@ -322,6 +324,7 @@ static inline bool ro_pass_interleaved(const rri_ctx* c) { return c->ro_il >= 0 
 //   q_valid                                    x           x                        Qt = X T^T
 //   gfull_valid                                            x                        Gfull = T T^T
 //   x_sq_valid                                 x                                    x_sq = ||X||^2
+// (X of an RRI_U8 handle: the counts AND its two scale vectors -- a changed scale is CH_X.)
 // (scratch: Zpart / Gpart / red, which other entry points borrow.)  resid_fresh, dt_pending and dw_pending qualify E and are
 // read only while resid_valid holds; every rebuild resets them (resid_rebuilt).  pending_wcheck is no cache but a verdict still
 // owed on the column sums in Gpart: it is taken before Gpart is overwritten (flush_wcheck) and dropped only with the run it
@@ -615,13 +618,16 @@ struct TimedScope {
 };
 
 // element sizes of the storage types (0: not a storage type)
-size_t dtype_size(int dt) { return dt == RRI_F32 ? 4 : dt == RRI_F64 ? 8 : dt == RRI_F16 ? 2 : 0; }
+size_t dtype_size(int dt) { return dt == RRI_F32 ? 4 : dt == RRI_F64 ? 8 : dt == RRI_F16 ? 2 : dt == RRI_U8 ? 1 : 0; }
+// the two stores of a dense X that is only ever read (RRI_UNWEIGHTED, Gram form): float16, and uint8 counts with scales
+bool ro_store(int dt) { return dt == RRI_F16 || dt == RRI_U8; }
+const char* dtype_name(int dt) { return dt == RRI_F32 ? "RRI_F32" : dt == RRI_F64 ? "RRI_F64" : dt == RRI_F16 ? "RRI_F16" : dt == RRI_U8 ? "RRI_U8" : "?"; }
 
-// a float16 handle reached a kernel family that does not exist for it: reported like a failed step of an enqueued sequence
+// a read-only store (float16, uint8) reached a kernel family that does not exist for it: reported like a failed step of an enqueued sequence
 void f16_unreachable(rri_ctx* c) {
     if (c->comm_status == RRI_OK) {
         c->comm_status = RRI_ERR_UNSUPPORTED;
-        c->err = "this operation rewrites X or needs a mask, a residual or a CSR store: not available on an RRI_F16 handle";
+        c->err = "this operation rewrites X or needs a mask, a residual or a CSR store: not available on an RRI_F16 or RRI_U8 handle";
     }
 }
 
@@ -632,7 +638,9 @@ struct LaunchX {
     typedef SX Elem;
     // float16 storage is read-only (RRI_F16: dense X, Gram form): only the members DISPATCH_RO reaches are ever instantiated for
     // it, and inside those the branches to the CSR, masked and residual-writing kernels are compiled out
-    static constexpr bool RO = std::is_same<SX, _Float16>::value;
+    // uint8 storage (RRI_U8) is the same handle with counts and two scale vectors (xscale)
+    static constexpr bool RO = std::is_same<SX, _Float16>::value || std::is_same<SX, unsigned char>::value;
+    static XScale xscale(const rri_ctx* c) { return XScale{c->rscale, c->cscale}; }
     // row-dot slots of the 4 waves, the active W column, (UPD: one or two arrays of rank-one row factors,) the row-sum tiles
     static size_t pass_shmem(const rri_ctx* c, int upd) {
         return ((5 + upd) * (size_t)c->rpb + 4 * 8 * 72) * sizeof(double);
@@ -665,7 +673,7 @@ struct LaunchX {
                            ((ro_pass_interleaved(c) || UPD > 0) ? c->nrb : 0) |
                                ((c->sw.pass_rot >= 0 ? c->sw.pass_rot : (UPD > 0 ? c->rot_r : c->rot_x)) << 27),
                            keep, PK ? (const unsigned char*)c->xp : nullptr, PK ? (const unsigned char*)c->xp_flags : nullptr,
-                           PK ? c->xp_base : 0);
+                           PK ? c->xp_base : 0, (const double*)c->rscale, (const double*)c->cscale);
     }
     // The read-only pass: 8 rows in flight per wave, the row dots (DO_Y) through LDS row sums.  The read-modify-write variants:
     // 16 rows in flight per wave, row dots by DPP wave sums -- 0.665 against 0.639 of 8 TB/s for the 8-row LDS row-sum variant
@@ -949,7 +957,7 @@ struct LaunchX {
         const size_t sh = 2 * 64 * (size_t)(16 * NT + 1) * sizeof(double) + 4 * 16 * (size_t)(64 + VN) * sizeof(SX);
         (void)allow_lds<k_xtt_mfma<SX, NT>>(c, 160 * 1024);
         hipLaunchKernelGGL((k_xtt_mfma<SX, NT>), dim3((unsigned)((c->n + 63) / 64)), dim3(256), sh, c->stream,
-                           (const SX*)c->X, c->ldx, Tm, c->LD, (int)c->n, (int)c->d, m, out, c->ldw);
+                           (const SX*)c->X, c->ldx, Tm, c->LD, (int)c->n, (int)c->d, m, out, c->ldw, xscale(c));
     }
     static void xtt_any(rri_ctx* c, const double* Tm, int m, double* out) {   // out (m x n) = (X Tm^T)^T
         for (int l0 = 0; l0 < m; l0 += 64) {     // the product on the matrix cores, up to 64 rows of Tm per launch
@@ -971,7 +979,7 @@ struct LaunchX {
         const int ncols = (int)std::min<i64>(c->ldx, c->LD);
         hipLaunchKernelGGL((k_colsums<SX, NV>), dim3(c->npanels * c->nrb), dim3(256), (size_t)NV * c->rpb * sizeof(double),
                            c->stream, (const SX*)c->X, c->ldx, (int)c->n, ncols, Qt, c->ldw, nv, zmulti, c->LD, c->rpb,
-                           c->npanels, c->nrb);
+                           c->npanels, c->nrb, xscale(c));
         const int nb = (int)((c->LD + 31) / 32);
         for (int v = 0; v < nv; ++v)
             hipLaunchKernelGGL(k_reduce, dim3(nb), dim3(1024), 0, c->stream,
@@ -1022,7 +1030,7 @@ struct LaunchX {
                             }
                             hipLaunchKernelGGL((k_resid_mfma<SX, MK, WE, KS, 4, SM>), dim3(nb, ny), dim3(256), shm, c->stream,
                                                (const SX*)c->X, c->ldx, M, ldm, Mbits, ldb, (const double*)c->W, c->ldw,
-                                               (const double*)c->T, c->LD, (int)c->n, (int)c->d, c->k, rowobj, rowpos, E, c->LD, dchunk);
+                                               (const double*)c->T, c->LD, (int)c->n, (int)c->d, c->k, rowobj, rowpos, E, c->LD, dchunk, xscale(c));
                         }
                     });
                 });
@@ -1033,7 +1041,7 @@ struct LaunchX {
         flavour([&](auto mk, auto we) {
             hipLaunchKernelGGL((k_resid<SX, mk, we>), dim3(nb), dim3(256), sh, c->stream, (const SX*)c->X, c->ldx, M, ldm, Mbits, ldb,
                                (const double*)c->W, c->ldw, (const double*)c->T, c->LD, (int)c->n, (int)c->d, c->k, rowobj, rowpos, E,
-                               c->LD, resid_w_resident(c) ? 1 : 0);
+                               c->LD, resid_w_resident(c) ? 1 : 0, xscale(c));
         });
     }
     static void reset_row(rri_ctx* c) {
@@ -1049,7 +1057,7 @@ struct LaunchX {
         }
         hipLaunchKernelGGL((k_reset_row<SX>), dim3((unsigned)((c->d + 255) / 256)), dim3(256), 0, c->stream,
                            (const SX*)c->X, c->ldx, (const double*)c->W, c->ldw, (const double*)c->T, c->LD,
-                           (int)c->d, c->k, (const i64*)c->itmp, c->xraw);
+                           (int)c->d, c->k, (const i64*)c->itmp, c->xraw, xscale(c));
     }
     static hipError_t set_attrs(const rri_ctx* c) {
         hipError_t e = allow_lds<k_resid<SX, false, false>>(c, 160 * 1024);
@@ -1064,7 +1072,7 @@ struct LaunchX {
 };
 
 // Everything that writes X, the mask or a residual, or reads a CSR store: float32 and float64 only.  A float16 handle
-// (RRI_F16) is refused at the entry points that lead here; should one arrive all the same, nothing is launched and the call
+// (RRI_F16; RRI_U8 likewise) is refused at the entry points that lead here; should one arrive all the same, nothing is launched and the call
 // that enqueued the sequence ends with RRI_ERR_UNSUPPORTED (f16_unreachable) -- never the double branch on 2-byte data.
 #define DISPATCH(c, expr)                       \
     do {                                        \
@@ -1079,7 +1087,7 @@ struct LaunchX {
         }                                       \
     } while (0)
 // The kernels that only READ a dense X (the pass with UPD = 0, X T^T, X^T Q, the residual's row sums, the reset row, ||X||^2):
-// the three storage types.
+// the four storage types (rri_create admits no other code).
 #define DISPATCH_RO(c, expr)                    \
     do {                                        \
         if ((c)->dtype == RRI_F32) {            \
@@ -1088,8 +1096,11 @@ struct LaunchX {
         } else if ((c)->dtype == RRI_F64) {     \
             typedef LaunchX<double> L;          \
             expr;                               \
-        } else {                                \
+        } else if ((c)->dtype == RRI_F16) {     \
             typedef LaunchX<_Float16> L;        \
+            expr;                               \
+        } else {                                \
+            typedef LaunchX<unsigned char> L;   \
             expr;                               \
         }                                       \
     } while (0)
@@ -1252,12 +1263,55 @@ rri_status to_device_half(rri_ctx* c, const void* host, i64 ld, int host_dtype, 
     return RRI_OK;
 }
 
+// host (rows x cols, stride ld; float32, float64 or bytes) -> device bytes (the counts of an RRI_U8 handle).  Bytes are copied as
+// they are; a floating type goes through k_store_u8, and one value that is not an integer in 0..255 fails the call with
+// RRI_ERR_INVALID (the caller drops the X).  Nothing is rounded, so store_err stays zero.
+rri_status to_device_u8(rri_ctx* c, const void* host, i64 ld, int host_dtype, void* dev, i64 ldd, i64 rows, i64 cols,
+                        bool transpose) {
+    if (transpose) return fail(c, RRI_ERR_INVALID, "uint8 storage is for X only");
+    if (host_dtype == RRI_U8) {
+        HIPCHK(c, hipMemcpy2DAsync(dev, ldd, host, ld, cols, rows, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return RRI_OK;
+    }
+    const size_t hs = dtype_size(host_dtype);
+    const i64 total = rows * cols;
+    const unsigned nb = (unsigned)std::max<i64>(1, std::min<i64>(4096, (total + 255) / 256));
+    DevTmp tmp, part;
+    HIPCHK(c, tmp.alloc((size_t)rows * cols * hs));
+    HIPCHK(c, part.alloc((size_t)nb * sizeof(double)));
+    HIPCHK(c, hipMemcpy2DAsync(tmp.p, cols * hs, host, ld * hs, cols * hs, rows, hipMemcpyHostToDevice, c->stream));
+    pick_type<float, double>(host_dtype, [&](auto src) {
+        typedef typename decltype(src)::type Src;
+        hipLaunchKernelGGL((k_store_u8<Src>), dim3(nb), dim3(256), 0, c->stream, (const Src*)tmp.p, cols, (unsigned char*)dev, ldd,
+                           rows, cols, (double*)part.p);
+    });
+    std::vector<double> h((size_t)nb);
+    HIPCHK(c, hipMemcpyAsync(h.data(), part.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double bad = 0.0;
+    for (unsigned b = 0; b < nb; ++b) bad += h[b];
+    if (bad > 0.0)
+        return fail(c, RRI_ERR_INVALID, "value that is not an integer in 0..255 at upload (%.0f of them: fractions, negatives, > 255, inf or NaN)", bad);
+    return RRI_OK;
+}
+// both scale vectors of an RRI_U8 handle back to ones (a new X)
+rri_status reset_scales(rri_ctx* c) {
+    if (c->dtype != RRI_U8) return RRI_OK;
+    hipLaunchKernelGGL(k_fill, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream, c->rscale, c->n, 1.0);
+    hipLaunchKernelGGL(k_fill, dim3((unsigned)((c->LD + 255) / 256)), dim3(256), 0, c->stream, c->cscale, c->LD, 1.0);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RRI_OK;
+}
+
 // the argument checks of to_device, for the callers that change the handle before they get there (rri_upload_X, rri_upload_mask):
 // a refused call leaves the handle as it was
 rri_status check_host_matrix(rri_ctx* c, const void* host, i64 ld, int host_dtype, i64 cols, int dev_dtype) {
     if (!host || ld < cols) return fail(c, RRI_ERR_INVALID, "bad host matrix (ld=%lld < cols=%lld)", ld, cols);
     // a float16 host buffer goes onto a float16 handle only (nothing else is ever given as halves)
-    if (host_dtype != RRI_F32 && host_dtype != RRI_F64 && !(host_dtype == RRI_F16 && dev_dtype == RRI_F16))
+    // ... and a buffer of bytes onto a uint8 handle only
+    if (host_dtype != RRI_F32 && host_dtype != RRI_F64 && !(host_dtype == RRI_F16 && dev_dtype == RRI_F16) &&
+        !(host_dtype == RRI_U8 && dev_dtype == RRI_U8))
         return fail(c, RRI_ERR_INVALID, "bad host dtype");
     return RRI_OK;
 }
@@ -1270,6 +1324,7 @@ rri_status to_device(rri_ctx* c, const void* host, i64 ld, int host_dtype, void*
     const size_t hs = dtype_size(host_dtype);
     const size_t ds = dtype_size(dev_dtype);
     if (dev_dtype == RRI_F16) return to_device_half(c, host, ld, host_dtype, dev, ldd, rows, cols, transpose);
+    if (dev_dtype == RRI_U8) return to_device_u8(c, host, ld, host_dtype, dev, ldd, rows, cols, transpose);
     if (host_dtype == dev_dtype && !transpose) {
         HIPCHK(c, hipMemcpy2DAsync(dev, ldd * ds, host, ld * hs, cols * hs, rows, hipMemcpyHostToDevice,
                                    c->stream));
@@ -1293,7 +1348,7 @@ rri_status to_host(rri_ctx* c, const void* dev, i64 ldd, void* host, i64 ld, int
                    int dev_dtype, bool transpose = false) {
     if (!host || ld < cols) return fail(c, RRI_ERR_INVALID, "bad host matrix (ld=%lld < cols=%lld)", ld, cols);
     if (host_dtype != RRI_F32 && host_dtype != RRI_F64) return fail(c, RRI_ERR_INVALID, "bad host dtype");
-    if (dev_dtype != RRI_F32 && dev_dtype != RRI_F64) return fail(c, RRI_ERR_UNSUPPORTED, "nothing stored as float16 is read back");
+    if (dev_dtype != RRI_F32 && dev_dtype != RRI_F64) return fail(c, RRI_ERR_UNSUPPORTED, "nothing stored as float16 or uint8 is read back");
     const size_t hs = dtype_size(host_dtype);
     const size_t ds = dtype_size(dev_dtype);
     if (host_dtype == dev_dtype && !transpose) {
@@ -1928,7 +1983,7 @@ bool onchip_ok(const rri_ctx* c) {
     // a handle that fell back tries the persistent path again once its own back-off has run out (a burst on another stream or
     // process must not cost a long-lived handle the launch-bound speed-up for good); eligibility therefore depends on the clock
     if (c->onchip_off && steady_now_ns() < c->onchip_off_until) return false;
-    if (c->dtype == RRI_F16) return false;      // the persistent kernel has register layouts for 4- and 8-byte X only
+    if (ro_store(c->dtype)) return false;       // the persistent kernel has register layouts for 4- and 8-byte X only
     return c->sw.onchip && steady_now_ns() >= g_onchip_backoff_until.load() && !c->weighted && !c->explicit_resid && !c->comm && !c->sparse && c->k >= 2 &&
            c->k <= ONCHIP_MAX_K && !c->prm.fix_W && !c->prm.fix_T && c->ldx % c->VN == 0 && ((uintptr_t)c->X) % 16 == 0 &&
            onchip_geometry(c, &g);
@@ -2207,10 +2262,12 @@ const char* sparse_data_refusal(const rri_ctx* c) {
                        : "a sparse-pattern handle takes its data through rri_upload_observed_csr";
 }
 
-// the entry points that rewrite X in place, or need a mask, a residual, a CSR store or a scratch residual, on a float16 handle
-#define REFUSE_F16(c, what)                                                                                             \
-    if ((c)->dtype == RRI_F16)                                                                                          \
-        return fail((c), RRI_ERR_UNSUPPORTED, "%s is not available on an RRI_F16 handle (float16 stores a dense X that is only read)", what)
+// the entry points that rewrite X in place, or need a mask, a residual, a CSR store or a scratch residual, on a handle of one of
+// the two read-only stores (float16; uint8 counts with scales)
+#define REFUSE_RO(c, what)                                                                                              \
+    if (ro_store((c)->dtype))                                                                                           \
+        return fail((c), RRI_ERR_UNSUPPORTED, "%s is not available on an %s handle (%s stores a dense X that is only read)", what, \
+                    dtype_name((c)->dtype), (c)->dtype == RRI_F16 ? "float16" : "uint8")
 
 rri_status ready(rri_ctx* c) {
     if (!c->have_X || !c->have_W || !c->have_T || !c->have_params)
@@ -2233,7 +2290,8 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     if (!out) return RRI_ERR_INVALID;
     *out = nullptr;
     if (n < 1 || d < 1 || k < 1) return fail(nullptr, RRI_ERR_INVALID, "need n,d,k >= 1 (got %lld,%lld,%d)", n, d, k);
-    if (dtype != RRI_F32 && dtype != RRI_F64 && dtype != RRI_F16) return fail(nullptr, RRI_ERR_INVALID, "dtype must be RRI_F32, RRI_F64 or RRI_F16");
+    if (dtype != RRI_F32 && dtype != RRI_F64 && dtype != RRI_F16 && dtype != RRI_U8)
+        return fail(nullptr, RRI_ERR_INVALID, "dtype must be RRI_F32, RRI_F64, RRI_F16 or RRI_U8");
     if (n > 2000000000LL || d > 2000000000LL) return fail(nullptr, RRI_ERR_INVALID, "n, d must fit int32");
     if (k > RRI_MAX_K) return fail(nullptr, RRI_ERR_UNSUPPORTED, "k=%d is above the rank limit RRI_MAX_K = %d of the device path", k, RRI_MAX_K);
     int ndev = 0;
@@ -2243,6 +2301,14 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     if (weighted < 0 || weighted > 4)
         return fail(nullptr, RRI_ERR_INVALID, "weighted must be RRI_UNWEIGHTED, RRI_WEIGHTED_DENSE, RRI_WEIGHTED_SPARSE, "
                                               "RRI_UNWEIGHTED_RESIDUAL or RRI_UNWEIGHTED_SPARSE");
+    if (dtype == RRI_U8 && weighted != RRI_UNWEIGHTED) {
+        // counts are no store for a residual (signed, fractional), and a CSR store has no uint8 layout
+        static const char* const flavour[] = {"", "RRI_WEIGHTED_DENSE", "RRI_WEIGHTED_SPARSE", "RRI_UNWEIGHTED_RESIDUAL", "RRI_UNWEIGHTED_SPARSE"};
+        const bool rewritten = weighted == RRI_WEIGHTED_DENSE || weighted == RRI_UNWEIGHTED_RESIDUAL;
+        return fail(nullptr, RRI_ERR_UNSUPPORTED, "RRI_U8 stores read-only dense counts (RRI_UNWEIGHTED); %s %s", flavour[weighted],
+                    rewritten ? "keeps a stored residual, which counts 0..255 cannot hold"
+                              : "keeps its values in a CSR store, which has no uint8 layout");
+    }
     if (dtype == RRI_F16 && weighted != RRI_UNWEIGHTED) {
         // float16 is a store for an X that is only ever read.  The explicit residual and the dense weighted residual are rewritten
         // at every topic step (k S roundings to 11 bits over S sweeps); CSR values are a store of their own with its own layout
@@ -2262,9 +2328,9 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     c->sparse = weighted == RRI_WEIGHTED_SPARSE || sparse_x;
     c->kp = (int)round_up(k, 8);
     c->es = dtype_size(dtype);
-    c->VN = (int)(16 / c->es);          // elements per 16-byte load: 4, 2, or 8 (float16)
+    c->VN = dtype == RRI_U8 ? XVec<unsigned char>::N : (int)(16 / c->es);   // elements per load: 4, 2, 8 (float16); uint8: 8 per 8-byte load
     c->sw = read_switches();
-    c->PW = 64 * c->VN * 4;   // columns per workgroup: 4 waves x (64 lanes x 16 B)
+    c->PW = 64 * c->VN * 4;   // columns per workgroup: 4 waves x (64 lanes x one load)
     c->LD = round_up(d, c->VN);
 #define CR(call)                                                                                   \
     do {                                                                                           \
@@ -2399,11 +2465,18 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     if (explicit_resid) CR(dev_alloc(c, c->told, (size_t)c->LD * f8, true));
     if (weighted || explicit_resid) CR(dev_alloc(c, c->zeros, (size_t)std::max<i64>(c->LD, n) * f8, true));
     if (c->sparse) CR(dev_alloc(c, c->sp_Tt, (size_t)d * c->kp * f8, true));
+    if (dtype == RRI_U8) {
+        CR(dev_alloc(c, c->rscale, (size_t)n * f8));
+        CR(dev_alloc(c, c->cscale, (size_t)c->LD * f8));
+        hipLaunchKernelGGL(k_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->rscale, (i64)n, 1.0);
+        hipLaunchKernelGGL(k_fill, dim3((unsigned)((c->LD + 255) / 256)), dim3(256), 0, c->stream, c->cscale, c->LD, 1.0);
+    }
     CR(dev_alloc(c, c->st, sizeof(DevState), true));
     // opt in to large dynamic LDS where a kernel needs it
     if (dtype == RRI_F32) CR(LaunchX<float>::set_attrs(c));
     else if (dtype == RRI_F64) CR(LaunchX<double>::set_attrs(c));
-    else CR(LaunchX<_Float16>::set_attrs(c));
+    else if (dtype == RRI_F16) CR(LaunchX<_Float16>::set_attrs(c));
+    else CR(LaunchX<unsigned char>::set_attrs(c));
     CR(hipStreamSynchronize(c->stream));
 #undef CR
     *out = c;
@@ -2436,14 +2509,15 @@ rri_status rri_upload_X(rri_ctx* c, const void* host, int64_t ld, int32_t host_d
     c->ldx = c->LD;
     c->store_err[0] = c->store_err[1] = 0.0;
     rri_status s = to_device(c, host, ld, host_dtype, c->X, c->ldx, c->n, c->d, c->dtype);
-    // (a float16 upload that fails -- the range check -- has already overwritten the store: the handle then has no X)
-    if (s == RRI_OK || c->dtype == RRI_F16) { c->have_X = s == RRI_OK; changed(c, CH_X); }
+    // (a float16 or uint8 upload that fails -- the range check -- has already overwritten the store: the handle then has no X)
+    if (s == RRI_OK || ro_store(c->dtype)) { c->have_X = s == RRI_OK; changed(c, CH_X); }
+    if (s == RRI_OK) s = reset_scales(c);
     return s;
 }
 
 rri_status rri_upload_mask(rri_ctx* c, const void* host, int64_t ld, int32_t host_dtype) {
     CHECK_CTX(c);
-    REFUSE_F16(c, "a mask");
+    REFUSE_RO(c, "a mask");
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     if (!c->weighted) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=1");
     if (rri_status s = check_host_matrix(c, host, ld, host_dtype, c->d, c->dtype)) return s;
@@ -2495,7 +2569,7 @@ static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int
 rri_status rri_upload_X_csr(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data,
                             int64_t nnz, int32_t data_dtype) {
     CHECK_CTX(c);
-    REFUSE_F16(c, "X from CSR arrays");
+    REFUSE_RO(c, "X from CSR arrays");
     if (c->sparse_x) return upload_X_csr_kept(c, indptr, indices, data, nnz, data_dtype);
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     HIPCHK(c, hipSetDevice(c->device));
@@ -2584,7 +2658,7 @@ static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int
 rri_status rri_upload_mask_csr_pattern(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data,
                                        int64_t nnz, int32_t data_dtype) {
     CHECK_CTX(c);
-    REFUSE_F16(c, "a mask");
+    REFUSE_RO(c, "a mask");
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     if (!c->weighted) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=1");
     HIPCHK(c, hipSetDevice(c->device));
@@ -2726,7 +2800,7 @@ rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indi
 rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* values,
                                    int64_t nnz, int32_t data_dtype) {
     CHECK_CTX(c);
-    REFUSE_F16(c, "an observation pattern");
+    REFUSE_RO(c, "an observation pattern");
     if (!c->sparse || c->sparse_x) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=RRI_WEIGHTED_SPARSE");
     if (nnz >= 2147483647LL) return fail(c, RRI_ERR_UNSUPPORTED, "more than 2^31-1 observed entries");
     HIPCHK(c, hipSetDevice(c->device));
@@ -2758,8 +2832,9 @@ rri_status rri_storage_error(rri_ctx* c, double out[2]) {
 rri_status rri_bind_X_device(rri_ctx* c, const void* dev, int64_t ld) {
     CHECK_CTX(c);
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
-    if (!dev || ld < c->d || (ld * (i64)c->es) % 16 || ((uintptr_t)dev) % 16)
-        return fail(c, RRI_ERR_INVALID, "device X must be 16-byte aligned with a 16-byte-multiple row stride >= d");
+    const i64 vb = (i64)c->VN * (i64)c->es;      // bytes per load: 16 (uint8: 8)
+    if (!dev || ld < c->d || (ld * (i64)c->es) % vb || ((uintptr_t)dev) % vb)
+        return fail(c, RRI_ERR_INVALID, "device X must be %lld-byte aligned with a %lld-byte-multiple row stride >= d", vb, vb);
     if (c->d % c->VN) return fail(c, RRI_ERR_INVALID, "binding device X needs d %% %d == 0 (no pad columns)", c->VN);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());   // the memory may have been produced on another stream a moment ago
@@ -2769,12 +2844,12 @@ rri_status rri_bind_X_device(rri_ctx* c, const void* dev, int64_t ld) {
     c->store_err[0] = c->store_err[1] = 0.0;   // bound memory is taken as it is: nothing was rounded here
     c->have_X = true;
     changed(c, CH_X);
-    return RRI_OK;
+    return reset_scales(c);
 }
 
 rri_status rri_bind_mask_device(rri_ctx* c, const void* dev, int64_t ld) {
     CHECK_CTX(c);
-    REFUSE_F16(c, "a mask");
+    REFUSE_RO(c, "a mask");
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     if (!c->weighted) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=1");
     if (!dev || ld < c->d || (ld * (i64)c->es) % 16 || ((uintptr_t)dev) % 16)
@@ -3123,10 +3198,10 @@ static rri_status ensure_x_sq(rri_ctx* c) {
     if (c->x_sq_valid) return RRI_OK;
     if (c->sparse_x)    // the stored entries as one row
         DISPATCH(c, hipLaunchKernelGGL((k_sqsum<typename L::Elem>), dim3(256), dim3(256), 0, c->stream,
-                                       (const typename L::Elem*)c->sp_x, std::max<i64>(c->nnz, 1), (i64)1, c->nnz, c->normpart));
+                                       (const typename L::Elem*)c->sp_x, std::max<i64>(c->nnz, 1), (i64)1, c->nnz, c->normpart, XScale{nullptr, nullptr}));
     else
         DISPATCH_RO(c, hipLaunchKernelGGL((k_sqsum<typename L::Elem>), dim3(256), dim3(256), 0, c->stream,
-                                       (const typename L::Elem*)c->X, c->ldx, c->n, c->d, c->normpart));
+                                       (const typename L::Elem*)c->X, c->ldx, c->n, c->d, c->normpart, L::xscale(c)));
     double h[256];
     HIPCHK(c, hipMemcpyAsync(h, c->normpart, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3361,7 +3436,7 @@ rri_status rri_rollback(rri_ctx* c) {
 // ---- the explicit residual (RRI_UNWEIGHTED_RESIDUAL handles) --------------------------------------------------
 rri_status rri_residual_rebuild(rri_ctx* c) {
     CHECK_CTX(c);
-    REFUSE_F16(c, "the explicit residual");
+    REFUSE_RO(c, "the explicit residual");
     if (!c->explicit_resid) return fail(c, RRI_ERR_INVALID, "handle was not created with RRI_UNWEIGHTED_RESIDUAL");
     if (!c->have_X || !c->have_W || !c->have_T) return fail(c, RRI_ERR_INVALID, "X, W, T must be set");
     HIPCHK(c, hipSetDevice(c->device));
@@ -3372,7 +3447,7 @@ rri_status rri_residual_rebuild(rri_ctx* c) {
 
 rri_status rri_get_residual(rri_ctx* c, void* host, int64_t ld, int32_t host_dtype) {
     CHECK_CTX(c);
-    REFUSE_F16(c, "the explicit residual");
+    REFUSE_RO(c, "the explicit residual");
     if (!c->explicit_resid) return fail(c, RRI_ERR_INVALID, "handle was not created with RRI_UNWEIGHTED_RESIDUAL");
     HIPCHK(c, hipSetDevice(c->device));
     return to_host(c, c->E, c->LD, host, ld, host_dtype, c->n, c->d, c->dtype);
@@ -3381,7 +3456,7 @@ rri_status rri_get_residual(rri_ctx* c, void* host, int64_t ld, int32_t host_dty
 rri_status rri_residual_update(rri_ctx* c, const double* a, const double* b, const double* a2, const double* b2,
                                const double* trow, const double* wcol, double* y_out, double* z_out) {
     CHECK_CTX(c);
-    REFUSE_F16(c, "the explicit residual");
+    REFUSE_RO(c, "the explicit residual");
     if (!c->explicit_resid) return fail(c, RRI_ERR_INVALID, "handle was not created with RRI_UNWEIGHTED_RESIDUAL");
     if (!a || !b || !trow || !wcol || ((a2 == nullptr) != (b2 == nullptr)))
         return fail(c, RRI_ERR_INVALID, "a, b, trow, wcol are required; a2 and b2 come together");
@@ -3699,15 +3774,90 @@ rri_status rri_sparse_range_finder(rri_ctx* c, const double* Q0, int32_t m, int3
 }
 
 // ---- preprocessing of the resident X ---------------------------------------------------------------------------
+// rri_scale_X on an RRI_U8 handle: no matrix is written.  cscale .*= col_scale; with normalize_rows the row totals of the scaled
+// matrix come from the streaming pass against a row of ones (the scales are folded in there) and rscale_i *= 1 / (tot_i +
+// spacing(1)).  A row whose total is below 1e-10 would have to become the dense row 1/d: the column scales are then put back,
+// nothing has changed, and the call fails with the number of such rows at the start of its message.  What the handle has cached
+// of X is dropped by the caller, rri_scale_X, as for every other store.
+static rri_status scale_counts(rri_ctx* c, const double* col_scale, int32_t normalize_rows) {
+    if (!col_scale && !normalize_rows) return RRI_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
+    DevTmp sd, keep, ones, nz;
+    const unsigned nbd = (unsigned)((c->d + 255) / 256);
+    if (col_scale) {
+        HIPCHK(c, sd.alloc((size_t)c->d * sizeof(double)));
+        HIPCHK(c, keep.alloc((size_t)c->LD * sizeof(double)));
+        HIPCHK(c, hipMemcpyAsync(sd.p, col_scale, (size_t)c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(keep.p, c->cscale, (size_t)c->LD * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        hipLaunchKernelGGL(k_vec_mul, dim3(nbd), dim3(256), 0, c->stream, c->cscale, (const double*)sd.p, c->d);
+    }
+    if (normalize_rows) {
+        HIPCHK(c, ones.alloc((size_t)c->LD * sizeof(double)));
+        HIPCHK(c, nz.alloc(sizeof(unsigned long long)));
+        HIPCHK(c, hipMemsetAsync(nz.p, 0, sizeof(unsigned long long), c->stream));
+        hipLaunchKernelGGL(k_fill, dim3((unsigned)((c->LD + 255) / 256)), dim3(256), 0, c->stream, (double*)ones.p, c->LD, 1.0);
+        const int tsave = c->timing;
+        c->timing = 0;
+        typedef LaunchX<unsigned char> L;
+        L::pass_cfg<true, false, 0>(c, c->X, c->ldx, (const double*)ones.p, c->W, L::stream_whole(c));
+        c->timing = tsave;
+        const unsigned nbn = (unsigned)((c->n + 255) / 256);
+        hipLaunchKernelGGL((k_row_scale_update<false>), dim3(nbn), dim3(256), 0, c->stream, (const double*)c->Ypart, c->npanels,
+                           (int)c->n, c->rscale, (unsigned long long*)nz.p);
+        unsigned long long zero_rows = 0;
+        HIPCHK(c, hipMemcpyAsync(&zero_rows, nz.p, sizeof(zero_rows), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (zero_rows > 0) {
+            if (col_scale) {
+                HIPCHK(c, hipMemcpyAsync(c->cscale, keep.p, (size_t)c->LD * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+            }
+            return fail(c, RRI_ERR_INVALID, "%llu row(s) sum to less than 1e-10: normalisation would make them the dense row 1/d, which "
+                                            "counts cannot hold; X and its scales are unchanged", zero_rows);
+        }
+        hipLaunchKernelGGL((k_row_scale_update<true>), dim3(nbn), dim3(256), 0, c->stream, (const double*)c->Ypart, c->npanels,
+                           (int)c->n, c->rscale, (unsigned long long*)nullptr);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RRI_OK;
+}
+
+rri_status rri_set_X_scales(rri_ctx* c, const double* row_scale, const double* col_scale) {
+    CHECK_CTX(c);
+    if (c->dtype != RRI_U8) return fail(c, RRI_ERR_INVALID, "only an RRI_U8 handle has scale vectors");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (row_scale) HIPCHK(c, hipMemcpyAsync(c->rscale, row_scale, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (col_scale) HIPCHK(c, hipMemcpyAsync(c->cscale, col_scale, (size_t)c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // a changed scale is a changed X: through the one call that rescales an X, with nothing more to multiply in
+    if (!c->have_X || (!row_scale && !col_scale)) return RRI_OK;
+    return rri_scale_X(c, nullptr, 0);
+}
+
+rri_status rri_get_X_scales(rri_ctx* c, double* row_out, double* col_out) {
+    CHECK_CTX(c);
+    if (c->dtype != RRI_U8) return fail(c, RRI_ERR_INVALID, "only an RRI_U8 handle has scale vectors");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (row_out) HIPCHK(c, hipMemcpyAsync(row_out, c->rscale, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (col_out) HIPCHK(c, hipMemcpyAsync(col_out, c->cscale, (size_t)c->d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RRI_OK;
+}
+
 rri_status rri_column_positive_counts(rri_ctx* c, double* df_out) {
     CHECK_CTX(c);
-    REFUSE_F16(c, "preprocessing of the resident X (it ends in a rewrite of X, a second rounding: preprocess on the host)");
+    if (c->dtype == RRI_F16) REFUSE_RO(c, "preprocessing of the resident X (it ends in a rewrite of X, a second rounding: preprocess on the host)");
     if (!df_out) return fail(c, RRI_ERR_INVALID, "df_out is NULL");
     if (c->weighted || !c->have_X || c->sparse_x) return fail(c, RRI_ERR_INVALID, "needs an unweighted handle with a dense X");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
     const int ncols = (int)std::min<i64>(c->ldx, c->LD);
     HIPCHK(c, hipMemsetAsync(c->Zpart, 0, (size_t)c->nrb * c->LD * sizeof(double), c->stream));
+    if (c->dtype == RRI_U8)     // the stored counts, whatever the scales are (matrixops.tfidf counts on the raw matrix)
+        hipLaunchKernelGGL((k_col_count<unsigned char>), dim3(c->npanels * c->nrb), dim3(256), 0, c->stream,
+                           (const unsigned char*)c->X, c->ldx, (int)c->n, ncols, c->Zpart, c->LD, c->rpb, c->npanels);
+    else
     DISPATCH(c, hipLaunchKernelGGL((k_col_count<typename L::Elem>), dim3(c->npanels * c->nrb), dim3(256), 0, c->stream,
                                    (const typename L::Elem*)c->X, c->ldx, (int)c->n, ncols, c->Zpart, c->LD, c->rpb,
                                    c->npanels));
@@ -3720,8 +3870,13 @@ rri_status rri_column_positive_counts(rri_ctx* c, double* df_out) {
 
 rri_status rri_scale_X(rri_ctx* c, const double* col_scale, int32_t normalize_rows) {
     CHECK_CTX(c);
-    REFUSE_F16(c, "rewriting X in place (a second rounding: preprocess on the host, X is then rounded once at upload)");
+    if (c->dtype == RRI_F16) REFUSE_RO(c, "rewriting X in place (a second rounding: preprocess on the host, X is then rounded once at upload)");
     if (c->weighted || !c->have_X || c->sparse_x) return fail(c, RRI_ERR_INVALID, "needs an unweighted handle with a dense X");
+    if (c->dtype == RRI_U8) {       // no matrix is written: the two scale vectors take it (the pass behind the row totals borrows Ypart)
+        const rri_status s = scale_counts(c, col_scale, normalize_rows);
+        changed(c, CH_X | CH_SCRATCH);
+        return s;
+    }
     if (!dev_owned(c, &c->X)) return fail(c, RRI_ERR_INVALID, "X is bound caller memory: it is not rewritten in place");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
@@ -4031,7 +4186,7 @@ rri_status rri_comm_destroy(rri_comm* m) {
 rri_status rri_attach_comm(rri_ctx* c, rri_comm* comm, int64_t row_offset, int64_t n_global) {
     CHECK_CTX(c);
     if (comm && c->sparse_x) return fail(c, RRI_ERR_UNSUPPORTED, "an RRI_UNWEIGHTED_SPARSE handle is not row-sharded");
-    if (comm && c->dtype == RRI_F16) return fail(c, RRI_ERR_UNSUPPORTED, "an RRI_F16 handle is not row-sharded (the combination has no test yet)");
+    if (comm && ro_store(c->dtype)) return fail(c, RRI_ERR_UNSUPPORTED, "an %s handle is not row-sharded (the combination has no test yet)", dtype_name(c->dtype));
     if (!comm) {              // detach
         c->comm = nullptr;
         c->row_offset = 0;
@@ -4182,7 +4337,7 @@ static size_t x_span_bytes(const rri_ctx* c) { return ((size_t)(c->n - 1) * c->l
 
 rri_status rri_bench_stream_copy(rri_ctx* c, int32_t reps, double* avg_ms) {
     CHECK_CTX(c);
-    REFUSE_F16(c, "the stream-copy yardstick");
+    REFUSE_RO(c, "the stream-copy yardstick");
     if (!c->have_X || reps < 1 || c->sparse) return fail(c, RRI_ERR_INVALID, "a dense X must be set and reps >= 1");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = x_span_bytes(c);
@@ -4206,7 +4361,7 @@ rri_status rri_bench_stream_copy(rri_ctx* c, int32_t reps, double* avg_ms) {
 
 rri_status rri_bench_rank1_update(rri_ctx* c, int32_t reps, double* avg_ms) {
     CHECK_CTX(c);
-    REFUSE_F16(c, "the rank-one residual update");
+    REFUSE_RO(c, "the rank-one residual update");
     if (!c->have_X || !c->have_W || !c->have_T || reps < 1 || c->weighted || c->sparse_x)
         return fail(c, RRI_ERR_INVALID, "an unweighted handle with a dense X, W, T set and reps >= 1");
     HIPCHK(c, hipSetDevice(c->device));

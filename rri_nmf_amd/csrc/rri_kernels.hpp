@@ -96,7 +96,45 @@ template <> struct XVec<_Float16> {
     }
 };
 
-// streaming load of one 16-byte vector; NT = non-temporal (X is read once per pass, never reused)
+// uint8 storage (RRI_U8): counts 0..255 of a read-only handle of the Gram form.  byte -> float (the per-byte convert instruction)
+// -> double is exact.  The X the kernels see is (C[i][j] * cscale[j]) * rscale[i] (XScale below): the two vectors never enter a row
+// loop -- X^T w = cscale .* (C^T (rscale .* w)) and X t = rscale .* (C (cscale .* t)), so they are applied where an operand vector
+// is loaded and where a partial sum is stored.  pack() only re-packs values read as bytes (the ragged edge of k_xtt_mfma).
+// 8 elements per 8-byte load: the register layout of the float16 pass (tv[8], zacc[8], 8 rows in flight; 202 VGPRs, 2 waves per
+// SIMD) and its geometry -- a workgroup of k_pass / k_colsums covers 2048 columns -- at half the bytes per row: 0.260 ms per pass
+// at 100000 x 10000.  16 elements per 16-byte load (4096 columns per workgroup) takes tv[16] and zacc[16]: 256 VGPRs and 100 AGPRs,
+// one wave per SIMD, 0.418 ms; it was measured beside this one in one process and removed.
+typedef unsigned char u8x8 __attribute__((ext_vector_type(8)));
+template <> struct XVec<unsigned char> {
+    typedef u8x8 type;
+    static constexpr int N = 8;
+    static __device__ __forceinline__ void unpack(const u8x8& v, double (&o)[8]) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (double)(float)v[e];
+    }
+    static __device__ __forceinline__ u8x8 pack(const double (&o)[8]) {
+        u8x8 r;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) r[e] = (unsigned char)o[e];
+        return r;
+    }
+    static __device__ __forceinline__ u8x8 zero() { return u8x8{0, 0, 0, 0, 0, 0, 0, 0}; }
+};
+// The two float64 scale vectors of an RRI_U8 handle: row[n], col[LD] (pad columns hold 1).  Both NULL for every other storage type,
+// whose kernels never look at them (`if constexpr` on XSCALED).
+struct XScale {
+    const double* row;
+    const double* col;
+};
+template <typename SX> constexpr bool XSCALED = std::is_same<SX, unsigned char>::value;
+// element (i, j) as the handle's X: (c * s_j) * r_i, in this order everywhere an element is formed on its own
+template <typename SX>
+__device__ __forceinline__ double x_elem(const SX* __restrict__ X, i64 ldx, i64 i, i64 j, const XScale& xs) {
+    if constexpr (XSCALED<SX>) return ((double)(float)X[i * ldx + j] * xs.col[j]) * xs.row[i];
+    else return (double)X[i * ldx + j];
+}
+
+// streaming load of one vector (16 bytes; 8 for uint8 counts); NT = non-temporal (X is read once per pass, never reused)
 template <bool NT, typename V>
 __device__ __forceinline__ V stream_load(const V* p) {
     if constexpr (NT) return __builtin_nontemporal_load(p);
@@ -257,7 +295,10 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
                                               const double* __restrict__ bvec2, const double* __restrict__ bsub2,
                                               const DevState* __restrict__ st, const TgramJob job, int nrb_il_rot,
                                               int keep_q, const unsigned char* __restrict__ XP = nullptr,
-                                              const unsigned char* __restrict__ xflags = nullptr, int xbase = 0) {
+                                              const unsigned char* __restrict__ xflags = nullptr, int xbase = 0,
+                                              const double* __restrict__ rscale = nullptr,
+                                              const double* __restrict__ cscale = nullptr) {
+    static_assert(!XSCALED<SX> || UPD == 0, "counts with scales are only read");
     static_assert(!PK || (std::is_same<SX, float>::value && UPD == 0 && U == 8), "the packed copy is of a read-only fp32 X");
     typedef XVec<SX> XV;
     typedef typename XV::type V;
@@ -306,7 +347,8 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
     if (DO_Z || UPD > 0) {
         for (int i = threadIdx.x; i < rpb; i += 256) {
             const int g = grow(i);
-            if (DO_Z) wsh[i] = g < n ? wcol[g] : 0.0;
+            if constexpr (XSCALED<SX>) { if (DO_Z) wsh[i] = g < n ? wcol[g] * rscale[g] : 0.0; }
+            else if (DO_Z) wsh[i] = g < n ? wcol[g] : 0.0;
             if (UPD > 0) ash[i] = g < n ? avec[g] : 0.0;
             if (UPD > 1) ash2[i] = g < n ? avec2[g] : 0.0;
         }
@@ -320,7 +362,8 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
 #pragma unroll
     for (int e = 0; e < VN; ++e) {
         zacc[e] = 0.0;
-        tv[e] = (DO_Y && ok) ? trow[col + e] : 0.0;
+        if constexpr (XSCALED<SX>) tv[e] = (DO_Y && ok) ? trow[col + e] * cscale[col + e] : 0.0;
+        else tv[e] = (DO_Y && ok) ? trow[col + e] : 0.0;
         bv[e] = (UPD > 0 && ok) ? bvec[col + e] : 0.0;
         bv2[e] = (UPD > 1 && ok) ? bvec2[col + e] - bsub2[col + e] : 0.0;
     }
@@ -347,7 +390,10 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
         }
         if (DO_Z && ok) {
 #pragma unroll
-            for (int e = 0; e < VN; ++e) Zpart[(i64)rb * ldz + col + e] = zacc[e];
+            for (int e = 0; e < VN; ++e) {
+                if constexpr (XSCALED<SX>) Zpart[(i64)rb * ldz + col + e] = zacc[e] * cscale[col + e];
+                else Zpart[(i64)rb * ldz + col + e] = zacc[e];
+            }
         }
     } else if (DO_Y) {
         for (int i = lane; i < rpb; i += 64) ysh[wave * rpb + i] = 0.0;
@@ -356,7 +402,11 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
         __syncthreads();
         for (int i = threadIdx.x; i < rpb; i += 256) {
             const int g = grow(i);
-            if (g < n) Ypart[(i64)pg * n + g] = (ysh[i] + ysh[rpb + i]) + (ysh[2 * rpb + i] + ysh[3 * rpb + i]);
+            if constexpr (XSCALED<SX>) {
+                if (g < n) Ypart[(i64)pg * n + g] = ((ysh[i] + ysh[rpb + i]) + (ysh[2 * rpb + i] + ysh[3 * rpb + i])) * rscale[g];
+            } else {
+                if (g < n) Ypart[(i64)pg * n + g] = (ysh[i] + ysh[rpb + i]) + (ysh[2 * rpb + i] + ysh[3 * rpb + i]);
+            }
         }
     }
 }
@@ -428,7 +478,8 @@ __global__ __launch_bounds__(256) void k_xpack_encode(const float* __restrict__ 
 template <typename SX, int NV>
 __global__ __launch_bounds__(256) void k_colsums(const SX* __restrict__ X, i64 ldx, int n, int ncols,
                                                  const double* __restrict__ Qt, i64 ldq, int nv,
-                                                 double* __restrict__ Zmulti, i64 ldz, int rpb, int npg, int nrb) {
+                                                 double* __restrict__ Zmulti, i64 ldz, int rpb, int npg, int nrb,
+                                                 const XScale xs) {
     typedef XVec<SX> XV;
     typedef typename XV::type V;
     constexpr int VN = XV::N;
@@ -443,7 +494,8 @@ __global__ __launch_bounds__(256) void k_colsums(const SX* __restrict__ X, i64 l
     const int col = (pg * 4 + wave) * PW + lane * VN;
     for (int i = threadIdx.x; i < (row1 - row0) * NV; i += 256) {
         const int v = i / (row1 - row0), r = i - v * (row1 - row0);
-        wsh[v * rpb + r] = v < nv ? Qt[(i64)v * ldq + row0 + r] : 0.0;
+        if constexpr (XSCALED<SX>) wsh[v * rpb + r] = v < nv ? Qt[(i64)v * ldq + row0 + r] * xs.row[row0 + r] : 0.0;
+        else wsh[v * rpb + r] = v < nv ? Qt[(i64)v * ldq + row0 + r] : 0.0;
     }
     __syncthreads();
     if ((pg * 4 + wave) * PW >= ncols) return;       // wave-uniform
@@ -475,7 +527,10 @@ __global__ __launch_bounds__(256) void k_colsums(const SX* __restrict__ X, i64 l
 #pragma unroll
         for (int v = 0; v < NV; ++v)
 #pragma unroll
-            for (int e = 0; e < VN; ++e) Zmulti[((i64)v * nrb + rb) * ldz + col + e] = acc[v][e];
+            for (int e = 0; e < VN; ++e) {
+                if constexpr (XSCALED<SX>) Zmulti[((i64)v * nrb + rb) * ldz + col + e] = acc[v][e] * xs.col[col + e];
+                else Zmulti[((i64)v * nrb + rb) * ldz + col + e] = acc[v][e];
+            }
     }
 }
 
@@ -1334,7 +1389,7 @@ __global__ __launch_bounds__(256) void k_resid(const SX* __restrict__ X, i64 ldx
                                                const double* __restrict__ Wt, i64 ldw, const double* __restrict__ T,
                                                i64 ldt, int n, int d, int k, double* __restrict__ rowobj,
                                                double* __restrict__ rowpos, SX* __restrict__ E, i64 lde,
-                                               int w_resident) {
+                                               int w_resident, const XScale xs) {
     typedef double S;
     constexpr int KC = 32;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1387,7 +1442,7 @@ __global__ __launch_bounds__(256) void k_resid(const SX* __restrict__ X, i64 ldx
             for (int b = 0; b < 4; ++b) {
                 const i64 j = c0 + tx * 4 + b;
                 if (j >= d) continue;
-                S e = (S)X[i * ldx + j] - acc[a][b];
+                S e = x_elem(X, ldx, i, j, xs) - acc[a][b];
                 const S m = !MASKED ? S(1)
                                     : (Mb ? (S)((Mb[(i >> 3) * ldb + (j >> 2)] >> ((int)((i & 7) << 2) + (int)(j & 3))) & 1u)
                                           : (S)M[i * ldm + j]);
@@ -1437,7 +1492,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2)))
                                                     const double* __restrict__ Wt, i64 ldw,
                                                     const double* __restrict__ T, i64 ldt, int n, int d, int k,
                                                     double* __restrict__ rowobj, double* __restrict__ rowpos,
-                                                    SX* __restrict__ E, i64 lde, int dchunk) {
+                                                    SX* __restrict__ E, i64 lde, int dchunk, const XScale xs) {
     // blockIdx.y: the column range [y dchunk, (y+1) dchunk) of the row block (dchunk a multiple of 64; the builds that take row
     // sums run with one range).  A row block over ALL columns is a long workgroup, and 1563 of them on 256 CUs x 2 are 3.05
     // rounds: the last 26 ran a fourth round on an empty chip.
@@ -1458,7 +1513,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2)))
     const int slot = 16 * (tc & 3) + (tc >> 2);
     constexpr int NST = (kp + WAVES - 1) / WAVES;
     double stage[NST];
-    typedef typename std::conditional<sizeof(SX) <= 4, float, double>::type XR;   // (a float16 X is staged as float: exact)
+    // (a float16 X is staged as float: exact; counts are staged as float64, with both scales already applied: (c s_j) r_i)
+    typedef typename std::conditional<sizeof(SX) <= 4 && !XSCALED<SX>, float, double>::type XR;
     XR xq[4][4];                                     // the lane's 4 rows x 4 consecutive columns of X, as stored
     XR xn[4][4];                                     // ... of the NEXT step: requested at the start of a step, so that
                                                      // nothing issued late in a step is waited for before its barrier
@@ -1496,9 +1552,18 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2)))
                     done = true;
                 }
             }
+            if constexpr (XSCALED<SX>) {                // the 4 counts of a row are one 4-byte word (row stride a multiple of 8)
+                if (i < n && j + 3 < d) {
+                    const unsigned w = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(X + i * ldx + j));
+                    const double ri = xs.row[i];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) dst[r][c] = ((double)(float)((w >> (8 * c)) & 0xffu) * xs.col[j + c]) * ri;
+                    done = true;
+                }
+            }
             if (!done) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) dst[r][c] = (i < n && j + c < d) ? (XR)X[i * ldx + j + c] : XR(0);
+                for (int c = 0; c < 4; ++c) dst[r][c] = (i < n && j + c < d) ? (XR)x_elem(X, ldx, i, j + c, xs) : XR(0);
             }
         }
     };
@@ -1657,10 +1722,11 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(2)))
 // =========================================================================================
 template <typename SX, int NT>
 __global__ __launch_bounds__(256) void k_xtt_mfma(const SX* __restrict__ X, i64 ldx, const double* __restrict__ T,
-                                                  i64 ldt, int n, int d, int m, double* __restrict__ Qt, i64 ldq) {
+                                                  i64 ldt, int n, int d, int m, double* __restrict__ Qt, i64 ldq,
+                                                  const XScale sc) {
     typedef XVec<SX> XV;
     typedef typename XV::type V;
-    constexpr int VN = XV::N;                 // elements per 16-byte vector: 4 (fp32) or 2 (fp64)
+    constexpr int VN = XV::N;                 // elements per vector: 4 (fp32), 2 (fp64), 8 (float16, uint8)
     constexpr int TS = 16 * NT + 1;           // row stride of the T tile [column][topic]
     constexpr int XS = 64 + VN;               // row stride of the X tile (elements)
     constexpr int NI = (16 * NT) / 4;         // T rows per thread and tile
@@ -1677,7 +1743,8 @@ __global__ __launch_bounds__(256) void k_xtt_mfma(const SX* __restrict__ X, i64 
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int l = tr + 4 * i;
-            stage[i] = (l < m && c0 + tc < d) ? T[(i64)l * ldt + c0 + tc] : 0.0;
+            if constexpr (XSCALED<SX>) stage[i] = (l < m && c0 + tc < d) ? T[(i64)l * ldt + c0 + tc] * sc.col[c0 + tc] : 0.0;
+            else stage[i] = (l < m && c0 + tc < d) ? T[(i64)l * ldt + c0 + tc] : 0.0;
         }
     };
     auto park = [&](int buf) {
@@ -1745,7 +1812,8 @@ __global__ __launch_bounds__(256) void k_xtt_mfma(const SX* __restrict__ X, i64 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const i64 i = row0 + lg + 4 * r;
-            if (l < m && i < n) Qt[(i64)l * ldq + i] = acc[c][r];
+            if constexpr (XSCALED<SX>) { if (l < m && i < n) Qt[(i64)l * ldq + i] = acc[c][r] * sc.row[i]; }
+            else if (l < m && i < n) Qt[(i64)l * ldq + i] = acc[c][r];
         }
     }
 }
@@ -1769,13 +1837,14 @@ __global__ __launch_bounds__(256) void k_norms(const double* __restrict__ A, i64
 
 // sum of squares of the stored X (float64 accumulation): out[b] partial of block b
 template <typename SX>
-__global__ __launch_bounds__(256) void k_sqsum(const SX* __restrict__ X, i64 ldx, i64 n, i64 d, double* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_sqsum(const SX* __restrict__ X, i64 ldx, i64 n, i64 d, double* __restrict__ out,
+                                               const XScale xs) {
     __shared__ double scratch[40];
     double s = 0.0;
     const i64 total = n * d;
     for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
         const i64 r = idx / d, c = idx - r * d;
-        const double v = (double)X[r * ldx + c];
+        const double v = x_elem(X, ldx, r, c, xs);
         s = fma(v, v, s);
     }
     s = block_sum(s, scratch);
@@ -1952,13 +2021,14 @@ __global__ __launch_bounds__(1024) void k_vec_sum_argmax(const double* __restric
 template <typename SX>
 __global__ __launch_bounds__(256) void k_reset_row(const SX* __restrict__ X, i64 ldx, const double* __restrict__ Wt,
                                                    i64 ldw, const double* __restrict__ T, i64 ldt, int d, int k,
-                                                   const i64* __restrict__ mi_ptr, double* __restrict__ rowout) {
+                                                   const i64* __restrict__ mi_ptr, double* __restrict__ rowout,
+                                                   const XScale xs) {
     const i64 mi = *mi_ptr;
     const i64 j = (i64)blockIdx.x * 256 + threadIdx.x;
     if (j >= d) return;
     double acc = 0.0;
     for (int l = 0; l < k; ++l) acc = fma(Wt[(i64)l * ldw + mi], T[(i64)l * ldt + j], acc);
-    rowout[j] = fmax((double)X[mi * ldx + j] - acc, 0.0);
+    rowout[j] = fmax(x_elem(X, ldx, mi, j, xs) - acc, 0.0);
 }
 // step 2: T[t,:] = row ; W[:,t] = e_mi (nmf.py:774-776)
 __global__ __launch_bounds__(256) void k_reset_commit(double* __restrict__ Wt, i64 ldw, double* __restrict__ T,
@@ -2052,6 +2122,51 @@ __global__ __launch_bounds__(256) void k_store_half(const Src* __restrict__ src,
     sx = block_sum(sx, scratch);
     bad = block_sum(bad, scratch);
     if (threadIdx.x == 0) { part[3 * blockIdx.x] = se; part[3 * blockIdx.x + 1] = sx; part[3 * blockIdx.x + 2] = bad; }
+}
+
+// Upload of a uint8 X from a floating host type: dst = the value as a byte, and part[b] = how many values of block b are not
+// integers in 0..255 (fractions, negatives, inf, NaN: the comparison is false for NaN).  Nothing is rounded: one such value fails
+// the upload.
+template <typename Src>
+__global__ __launch_bounds__(256) void k_store_u8(const Src* __restrict__ src, i64 lds_, unsigned char* __restrict__ dst, i64 ldd,
+                                                  i64 rows, i64 cols, double* __restrict__ part) {
+    __shared__ double scratch[40];
+    const i64 total = rows * cols;
+    double bad = 0.0;
+    for (i64 idx = (i64)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (i64)gridDim.x * 256) {
+        const i64 r = idx / cols, c = idx - r * cols;
+        const double x = (double)src[r * lds_ + c];
+        const bool good = x >= 0.0 && x <= 255.0 && x == floor(x);
+        dst[r * ldd + c] = good ? (unsigned char)(int)x : (unsigned char)0;
+        if (!good) bad += 1.0;
+    }
+    bad = block_sum(bad, scratch);
+    if (threadIdx.x == 0) part[blockIdx.x] = bad;
+}
+
+// vec[0 .. total) = value (the scale vectors of an RRI_U8 handle start as ones, pad columns included)
+__global__ __launch_bounds__(256) void k_fill(double* __restrict__ vec, i64 total, double value) {
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i < total) vec[i] = value;
+}
+// Row normalisation of an RRI_U8 handle: Ypart holds the row totals sum_j c_ij cscale_j rscale_i as panels (the pass against a row
+// of ones).  inv_i = 1 / (tot_i + spacing(1)); rows with a total below 1e-10 are counted (nzero) and nothing is written for
+// them.  APPLY: rscale_i *= inv_i -- launched only once the count came back zero.
+template <bool APPLY>
+__global__ __launch_bounds__(256) void k_row_scale_update(const double* __restrict__ Ypart, int npanels, int n,
+                                                          double* __restrict__ rscale, unsigned long long* __restrict__ nzero) {
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double xs = 0.0;
+    xs = ordered_sum<8>(Ypart + i, n, 0, npanels, 1);
+    xs += 2.220446049250313e-16;                      // np.spacing(1), matrixops.py:140
+    if constexpr (APPLY) rscale[i] *= 1.0 / xs;
+    else if (xs < 1e-10) atomicAdd(nzero, 1ull);
+}
+// cscale[j] *= s[j], j < d
+__global__ __launch_bounds__(256) void k_vec_mul(double* __restrict__ v, const double* __restrict__ s, i64 len) {
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i < len) v[i] *= s[i];
 }
 
 // plain 16-byte streaming copy: the achievable-HBM yardstick measured beside the pass kernel

@@ -36,6 +36,7 @@ template <typename T> struct type_tag { typedef T type; };
 template <typename T> constexpr int dtype_code = -1;
 template <> constexpr int dtype_code<float> = RRI_F32;
 template <> constexpr int dtype_code<double> = RRI_F64;
+template <> constexpr int dtype_code<unsigned char> = RRI_U8;
 #ifdef __FLT16_MANT_DIG__      // (a host compiler without the type still builds the rest)
 template <> constexpr int dtype_code<_Float16> = RRI_F16;
 #endif

@@ -9,8 +9,13 @@ whatever the store, and a float16 value converts to float64 exactly, so a float1
 X.astype(float16): one rounding, at upload, none afterwards.  float16 suits magnitudes below 65520 (upload_X raises ValueError
 beyond) and data of 11 significant bits: integers up to 2048 are exact; otherwise the relative rounding is 2^-11 above 6.1e-5
 and the absolute one 3e-8 below it.  `storage_relerr` says what it came to.
+The same handle also stores term counts: uint8, one byte per element, with a float64 scale per row and per column kept beside it.
+The X it factorises is (C[i, j] * cscale[j]) * rscale[i], formed in float64 wherever it is read, so tf-idf and row normalisation
+are two vector updates (no pass rewrites the matrix) and cost no rounding of the store at all.  upload_X refuses anything but the
+integers 0..255; `set_X_scales` / `X_scales` write and read the two vectors.
 """
 import ctypes as C
+import re
 
 import numpy as np
 
@@ -19,28 +24,30 @@ from ._capi import Params, Event
 
 EPS_DIV = float(np.spacing(10))  # nmf.py:52
 
-_NP2RRI = {np.dtype(np.float32): _capi.RRI_F32, np.dtype(np.float64): _capi.RRI_F64, np.dtype(np.float16): _capi.RRI_F16}
+_NP2RRI = {np.dtype(np.float32): _capi.RRI_F32, np.dtype(np.float64): _capi.RRI_F64, np.dtype(np.float16): _capi.RRI_F16,
+           np.dtype(np.uint8): _capi.RRI_U8}
+_READ_ONLY = (np.dtype(np.float16), np.dtype(np.uint8))        # stores of a dense X that is only ever read
 _HOST_TYPES = (np.dtype(np.float32), np.dtype(np.float64))     # what W, T, masks and CSR values travel as
 _RESET_CODES = {None: _capi.RESET_NONE, 'max_resid_document': _capi.RESET_MAX_RESID_DOCUMENT,
                 'random': _capi.RESET_RANDOM}
 
 
 class ZeroTotalRows(ValueError):
-    """Row normalisation of an X kept as CSR met `count` rows whose total is below 1e-10 -- empty documents, or documents made
-    only of terms that occur in every document (idf 0).  matrixops.normalize makes such a row the dense row 1/d, which a CSR
-    pattern cannot take: nothing was rewritten, the handle's X is unchanged."""
+    """Row normalisation of an X kept as CSR (or as uint8 counts) met `count` rows whose total is below 1e-10 -- empty documents,
+    or documents made only of terms that occur in every document (idf 0).  matrixops.normalize makes such a row the dense row
+    1/d, which a CSR pattern (or a matrix of counts) cannot take: nothing was rewritten, the handle's X is unchanged."""
 
     def __init__(self, count):
         ValueError.__init__(self, '%d row(s) of X sum to less than 1e-10: normalisation would make them dense (1/d), which an X '
-                                  'kept as CSR cannot hold; X was left unchanged' % count)
+                                  'kept as CSR or as counts cannot hold; X was left unchanged' % count)
         self.count = int(count)
 
 
-def _as_host(a, what, half=False):
+def _as_host(a, what, half=False, keep=None):
     """C-contiguous float32/float64 view or copy of a matrix (never mutates the caller's); half: a float16 array stays one
-    (the X of a float16 handle)"""
+    (the X of a float16 handle); keep: another dtype that stays as it is (uint8 for the X of a uint8 handle)"""
     a = np.asarray(a)
-    if a.dtype not in _HOST_TYPES and not (half and a.dtype == np.float16):
+    if a.dtype not in _HOST_TYPES and not (half and a.dtype == np.float16) and not (keep is not None and a.dtype == keep):
         a = a.astype(np.float64)
     if a.ndim != 2:
         raise ValueError('%s must be a 2-d array' % what)
@@ -49,18 +56,18 @@ def _as_host(a, what, half=False):
 
 def check_storage_options(dtype, weighted=False, schedule='gram', sparse_x=False):
     """The storage type of a handle against its flavour, before anything touches the library: float32 / float64 for all,
-    float16 for the unweighted flavour in the Gram form on a dense X only (the one handle whose stored matrix is never
-    rewritten).  Returns the numpy dtype; ValueError names what does not combine."""
+    float16 and uint8 (counts with row and column scales) for the unweighted flavour in the Gram form on a dense X only (the one
+    handle whose stored matrix is never rewritten).  Returns the numpy dtype; ValueError names what does not combine."""
     dt = np.dtype(dtype)
     if dt not in _NP2RRI:
-        raise ValueError('dtype must be float32, float64 or float16')
-    if dt == np.float16:
+        raise ValueError('dtype must be float32, float64 or float16 (or uint8 for counts 0..255)')
+    if dt in _READ_ONLY:
         refused = [name for name, on in (('weighted=%r' % (weighted,), bool(weighted)),
                                          ("schedule='residual'", schedule == 'residual'),
                                          ('sparse_x=True', bool(sparse_x))) if on]
         if refused:
-            raise ValueError('dtype=float16 stores a dense X that is only read (unweighted, schedule=\'gram\'); it does not '
-                             'combine with %s' % ', '.join(refused))
+            raise ValueError('dtype=%s stores a dense X that is only read (unweighted, schedule=\'gram\'); it does not '
+                             'combine with %s' % (dt.name, ', '.join(refused)))
     return dt
 
 
@@ -197,8 +204,10 @@ class RRIEngine(object):
     # ---- data ---------------------------------------------------------------------------
     def upload_X(self, X):
         """a float16 handle takes float16 / float32 / float64 arrays as they are and rounds once, from that type; a value
-        outside the float16 range raises ValueError and leaves the handle without an X"""
-        X = _as_host(X, 'X', half=self.dtype == np.float16)
+        outside the float16 range raises ValueError and leaves the handle without an X.  A uint8 handle takes uint8 / float32 /
+        float64 arrays; a value that is not an integer in 0..255 raises ValueError and leaves the handle without an X, and both
+        scale vectors are ones again afterwards"""
+        X = _as_host(X, 'X', half=self.dtype == np.float16, keep=np.uint8 if self.dtype == np.uint8 else None)
         if X.shape != (self.n, self.d):
             raise ValueError('X has wrong dimensions')
         self._check(self._lib.rri_upload_X(self._h, X.ctypes.data, X.strides[0] // X.itemsize, _NP2RRI[X.dtype]))
@@ -206,7 +215,7 @@ class RRIEngine(object):
     @property
     def storage_relerr(self):
         """||X - stored(X)||_F / ||X||_F of the last upload_X on a float16 handle (rri_storage_error); 0.0 on float32 / float64
-        handles, for bound arrays and for an all-zero X"""
+        and uint8 handles (what a uint8 handle accepts it stores exactly), for bound arrays and for an all-zero X"""
         out = (C.c_double * 2)()
         self._check(self._lib.rri_storage_error(self._h, out))
         return float(np.sqrt(out[0] / out[1])) if out[1] > 0.0 else 0.0
@@ -518,7 +527,36 @@ class RRIEngine(object):
             if col_scale.size != self.d:
                 raise ValueError('col_scale must have d entries')
             ptr = col_scale.ctypes.data_as(C.POINTER(C.c_double))
-        self._check(self._lib.rri_scale_X(self._h, ptr, int(bool(normalize_rows))))
+        st = self._lib.rri_scale_X(self._h, ptr, int(bool(normalize_rows)))
+        if st == _capi.RRI_ERR_INVALID and self.dtype == np.uint8:
+            # counts cannot hold the dense row 1/d that normalize makes of an empty row: nothing was changed, the message starts
+            # with how many there are (include/rri_hip.h)
+            m = re.match(r'(\d+) row', self._err())
+            if m:
+                raise ZeroTotalRows(int(m.group(1)))
+        self._check(st)
+
+    def set_X_scales(self, row_scale=None, col_scale=None):
+        """uint8 handles: the X that is factorised is (C * col_scale) * row_scale[:, None]; None leaves a vector as it is"""
+        ptrs = []
+        keep = []
+        for v, size, what in ((row_scale, self.n, 'row_scale must have n entries'), (col_scale, self.d, 'col_scale must have d entries')):
+            if v is None:
+                ptrs.append(None)
+                continue
+            v = np.ascontiguousarray(v, dtype=np.float64).ravel()
+            if v.size != size:
+                raise ValueError(what)
+            keep.append(v)
+            ptrs.append(v.ctypes.data_as(C.POINTER(C.c_double)))
+        self._check(self._lib.rri_set_X_scales(self._h, ptrs[0], ptrs[1]))
+
+    def X_scales(self):
+        """(row_scale, col_scale) of a uint8 handle, float64"""
+        r, s = np.empty(self.n, dtype=np.float64), np.empty(self.d, dtype=np.float64)
+        self._check(self._lib.rri_get_X_scales(self._h, r.ctypes.data_as(C.POINTER(C.c_double)),
+                                               s.ctypes.data_as(C.POINTER(C.c_double))))
+        return r, s
 
     def preprocess(self, tfidf=False, normalize=False):
         """tf-idf and/or row normalisation of the resident X, as matrixops.tfidf / normalize produce them.
@@ -609,7 +647,7 @@ class RRIEngine(object):
                               store_gradients (nmf.py:454-456)
           draw(m)             the Gaussian mechanism (see sweep_with_T_noise)"""
         d, k = self.d, self.k
-        ld = -(-d // (16 // self.dtype.itemsize)) * (16 // self.dtype.itemsize)
+        ld = self._row_stride()
         for t in range(k):
             self.topic_reduce_local(t)
             self.topic_finish(-1)                       # the column check of topic t-1 (nmf.py:471-476)
@@ -639,6 +677,11 @@ class RRIEngine(object):
         self.topic_finish(-1)
         self._stepping_event()
 
+    def _row_stride(self):
+        """LD of the handle (rri_create): d rounded up to the elements of one load -- 16 bytes, but 8 for uint8 counts"""
+        vn = 8 if self.dtype == np.uint8 else 16 // self.dtype.itemsize
+        return -(-self.d // vn) * vn
+
     def _topic_sums(self, t, ld, with_wR=True):
         """(reduce buffer, wR, nw, T[t,:] or None) after rri_topic_reduce_local(t): the sums _compute_update_T returns
         (nmf.py:670-676 plain, :687-701 weighted)"""
@@ -660,7 +703,7 @@ class RRIEngine(object):
     def topic_sums(self, t):
         """(wR, nw) of topic t for the factors now on the device: w_t^T (X - sum_{j != t} w_j t_j) and ||w_t||^2, or
         their weighted counterparts (d-vectors)"""
-        ld = -(-self.d // (16 // self.dtype.itemsize)) * (16 // self.dtype.itemsize)
+        ld = self._row_stride()
         self.topic_reduce_local(t)
         _, wR, nw, _ = self._topic_sums(t, ld)
         return np.array(wR), (np.array(nw) if self.weighted else nw)

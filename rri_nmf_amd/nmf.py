@@ -5,6 +5,9 @@ Same signature, defaults, return keys and error behaviour as the reference; keyw
 additions select the device side:
     dtype   storage type of X (and the mask) in HBM: float32 or float64.  None = float32 when X is
             float32, else float64.  The arithmetic is float64 either way (see csrc/rri_kernels.hpp).
+            uint8 (never chosen by itself, not even for a uint8 input): term counts 0..255 at one byte each, with a float64 scale
+            per row and per column on the handle -- X = diag(r) C diag(s) exactly in float64; `preprocess` then only updates the
+            two vectors on the device (no rounding, no pass that rewrites X).  Refuses what float16 refuses, and w_row.
             float16 (never chosen by itself, not even for a float16 input): a dense X without weights in the Gram form is only
             ever read, so it may be stored in half the bytes of float32 -- X is rounded ONCE, at upload (preprocessing and w_row
             are applied in float64 on the host first), and since a float16 value is exact in float64 the call returns what
@@ -153,7 +156,7 @@ def _device_free_bytes(device):
 
 
 def preprocess_route(csr_handle, x_is_sparse, normalize=False, has_empty_row=False, W_mat=False, w_row=False,
-                     host_callbacks=False, half=False, group=False):
+                     host_callbacks=False, half=False, group=False, counts=False):
     """Where the `preprocess` option of nmf() runs: 'device' (X goes up raw and is rewritten there) or 'host' (matrixops on the
     host before the upload).  csr_handle: the answer of sparse_x_route -- X is kept as CSR on the device; x_is_sparse: X is a
     scipy sparse matrix; the other arguments say what the call asks for.
@@ -162,9 +165,13 @@ def preprocess_route(csr_handle, x_is_sparse, normalize=False, has_empty_row=Fal
       a CSR handle: 'device' -- unless rows are to be normalised and one of them stores nothing: normalize makes it the dense row
       1/d, which the pattern cannot take, and np.diff(indptr) shows it before anything is uploaded: 'host';
       every other X, a scipy sparse one that is densified on the device included: 'device' (the dense kernel writes such rows);
-      row-sharded (group): a dense X without weights or callbacks runs on the device, everything else is not built."""
+      row-sharded (group): a dense X without weights or callbacks runs on the device, everything else is not built;
+      counts (uint8 storage): always 'device' -- tf-idf and normalisation are the handle's two scale vectors there, and the host
+      route would leave non-integers to store (callbacks are shown the scaled matrix, rebuilt on the host from the scales)."""
     if group and (x_is_sparse or csr_handle or W_mat or w_row or host_callbacks):
         raise NotImplementedError('row-sharded preprocessing runs on the device: a dense X without weights or callbacks')
+    if counts:
+        return 'device'
     if W_mat or w_row or host_callbacks or half:
         return 'host'
     if csr_handle and normalize and has_empty_row:
@@ -177,9 +184,10 @@ def _route_of_call(X, spec, sparse_X=None, dtype=None, device=0, W_mat=None, w_r
     """(preprocess_route's answer, sparse_x_route's answer or None where that one is not asked) for the arguments of an nmf() call
     with preprocessing `spec` = (tfidf, normalize); X is the caller's or nmf()'s converted one"""
     half = dtype is not None and np.dtype(dtype) == np.float16
+    counts = dtype is not None and np.dtype(dtype) == np.uint8
     xs = scipy.sparse.issparse(X)
     csr = None
-    if W_mat is None and w_row is None and schedule == 'gram' and not half and group is None:
+    if W_mat is None and w_row is None and schedule == 'gram' and not half and not counts and group is None:
         n, d = X.shape
         free = _device_free_bytes(device) if (sparse_X is None and xs) else 0
         csr = sparse_x_route(sparse_X, xs, n, d, np.dtype(dtype or np.float64).itemsize, free)
@@ -187,7 +195,8 @@ def _route_of_call(X, spec, sparse_X=None, dtype=None, device=0, W_mat=None, w_r
     if csr and spec[1]:
         empty = bool(np.any(np.diff(X.tocsr().indptr) == 0)) if xs else not bool(np.all(np.any(np.asarray(X) != 0, axis=1)))
     route = preprocess_route(bool(csr), xs, normalize=spec[1], has_empty_row=empty, W_mat=W_mat is not None,
-                             w_row=w_row is not None, host_callbacks=host_callbacks, half=half, group=group is not None)
+                             w_row=w_row is not None, host_callbacks=host_callbacks, half=half, group=group is not None,
+                             counts=counts)
     return route, csr
 
 
@@ -530,6 +539,20 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         if scipy.sparse.issparse(X):
             raise ValueError('dtype=float16 stores a dense X; a scipy sparse X stays sparse on the device with sparse_X=True '
                              '(float32 / float64 values), or pass X.toarray()')
+    counts = dtype is not None and np.dtype(dtype) == np.uint8
+    if counts:
+        # uint8 stores counts that are only read, with a float64 scale per row and per column: the same handle as float16's.
+        # w_row would have to go into the row scales (folded on the host it leaves non-integers): not built
+        refused = [name for name, on in (('W_mat', W_mat is not None), ("schedule='residual'", schedule == 'residual'),
+                                         ('sparse_X=True', bool(sparse_X)), ('group=', group is not None),
+                                         ('w_row', w_row is not None))
+                   if on]
+        if refused:
+            raise ValueError('dtype=uint8 stores dense, unweighted counts that the Gram form only reads; it does not combine '
+                             'with %s' % ', '.join(refused))
+        if scipy.sparse.issparse(X):
+            raise ValueError('dtype=uint8 stores a dense X; a scipy sparse X stays sparse on the device with sparse_X=True '
+                             '(float32 / float64 values), or pass X.toarray()')
     if group is not None:
         # host work that would need the other ranks' rows (the SVD behind the NNDSVD start, document frequencies,
         # per-row weights with their refit) or that decides per rank (callbacks) is not part of the sharded call
@@ -557,6 +580,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         noise = gaussian(0, np.sqrt(sigma2))            # draws from numpy's global RNG, as the reference's does
         draw_noise = lambda m: np.asarray(noise.rvs(m), dtype=np.float64).ravel()
     X_given, W_mat_given = X, W_mat
+    X_seen = None       # the X of the host callbacks where it is not X itself (uint8 storage with device preprocessing)
     # scipy sparse X / 0-1 sparse W_mat are ingested as CSR (no host densification); row weights need a dense X
     if scipy.sparse.issparse(X):
         X = X.tocsr() if w_row is None else X.toarray()
@@ -578,6 +602,12 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             X, rtv['idf'] = _preprocess_on_host(X, *spec)
         else:
             device_spec = {'tfidf': spec[0], 'normalize': spec[1]}
+        if counts and spec[1]:
+            # normalize makes an empty row the dense row 1/d, which counts cannot hold -- and no other store is chosen silently
+            n_empty = int(X.shape[0] - np.count_nonzero(np.any(X, axis=1)))
+            if n_empty:
+                raise ValueError('%d row(s) of X are empty: normalisation would make them dense (1/d), which dtype=uint8 cannot '
+                                 'store; drop them or choose a floating-point dtype' % n_empty)
     n, d = X.shape
 
     # ---- option sanity, exactly as nmf.py:280-315 ---------------------------------------------
@@ -668,6 +698,9 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             try:
                 idf = eng.preprocess(**device_spec)
             except ZeroTotalRows as exc:
+                if counts:      # (rows made only of terms that occur in every document: their tf-idf total is 0)
+                    raise ValueError('%d row(s) of X have a tf-idf total below 1e-10: normalisation would make them dense (1/d), '
+                                     'which dtype=uint8 cannot store' % exc.count)
                 # a CSR handle met a row that normalisation makes dense (a document of terms that occur everywhere: idf 0) and
                 # left X as it was: this matrix is preprocessed on the host after all, and no handle is kept for it
                 logger.info('%s -- preprocessing on the host instead' % exc)
@@ -686,6 +719,10 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             device_spec = {'tfidf': idf if idf is not None else False, 'normalize': device_spec['normalize']}
             on_device = True                 # the preprocessed X exists only on the device
             X_init = _ResidentX(eng)
+            if counts and host_callbacks:
+                # what the callbacks are shown: the matrix the handle factorises, rebuilt from its scales in the handle's own order
+                rscale, cscale = eng.X_scales()
+                X_seen = (np.asarray(X, dtype=np.float64) * cscale) * rscale[:, None]
         if resident is not None and res_key is not None and not reused:
             resident.engine, resident.key, resident.idf = eng, res_key, rtv.get('idf')
             resident.given = (X_given, W_mat_given)
@@ -704,8 +741,10 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         def current():
             return eng.get_W(), eng.get_T()
 
+        if X_seen is None:
+            X_seen = X
         for f in diagnostics:
-            rtv['diagnostics'][f.__name__].append(f(X, W, T))
+            rtv['diagnostics'][f.__name__].append(f(X_seen, W, T))
 
         iter_cputime, obj_history = [], []
         last_score = np.inf
@@ -773,7 +812,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
                         this_score = eng.masked_rmse(*entries)
                     else:
                         Wh, Th = current()
-                        this_score = early_stop(X, Wh, Th)
+                        this_score = early_stop(X_seen, Wh, Th)
                 elif compute_obj_each_iter:
                     this_score = np.inf if not obj_history else obj_history[-1]
                 logger.info('Iter %d stopping score %.3f' % (iter_no, this_score))
@@ -793,7 +832,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
                 numer_it, denom_it = [], []
                 rtv['numer_W'][iter_no], rtv['denom_W'][iter_no] = numer_it, denom_it
                 if not fix_T:
-                    observe = _gradient_recorder(eng, X, W_mat, ind_rows_to_store, numer_it, denom_it)
+                    observe = _gradient_recorder(eng, X_seen, W_mat, ind_rows_to_store, numer_it, denom_it)
             if draw_noise is None and observe is None:
                 eng.sweep(1)                      # the topic loop, nmf.py:415-476
             else:
@@ -808,7 +847,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             if diagnostics:
                 Wh, Th = current()
                 for f in diagnostics:
-                    rtv['diagnostics'][f.__name__].append(f(X, Wh, Th))
+                    rtv['diagnostics'][f.__name__].append(f(X_seen, Wh, Th))
             logger.info('\tTime: %.3fsec' % (time.time() - sweep_t0))
             out_of_time = time.time() - wall0 >= max_time
             if group is not None:            # rank 0's clock decides for everybody
@@ -829,7 +868,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
 
         W, T = current()
         n_resets_used = eng.n_resets_used
-        if half:
+        if half or counts:
             rtv['x_storage_relerr'] = eng.storage_relerr
         keep_handle = resident is not None and resident.engine is eng
     finally:

@@ -278,15 +278,19 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
                     reg_w_l1=self.wr1, reg_w_l2=self.wr2, reg_t_l1=self.tr1, reg_t_l2=self.tr2,
                     random_state=self.random_state,
                     **self._preprocess_kwargs(idf=self.idf if self.handle_tfidf else None),
-                    # the storage options of nmf_kwargs the fold-in follows: X kept as CSR on the device, and a float16 store
-                    # (without it the fold-in would upload the new rows at 8 bytes per entry)
+                    # the storage options of nmf_kwargs the fold-in follows: X kept as CSR on the device, and a float16 or uint8
+                    # store (without it the fold-in would upload the new rows at 8 bytes per entry)
                     **({'sparse_X': self.nmf_kwargs['sparse_X']} if 'sparse_X' in self.nmf_kwargs else {}),
-                    **({'dtype': np.float16} if self._half_storage() else {}))
+                    **({'dtype': self._read_only_storage()} if self._read_only_storage() is not None else {}))
         return soln['W']
 
-    def _half_storage(self):
+    def _read_only_storage(self):
+        """np.float16 or np.uint8 where nmf_kwargs asks for one of the two stores of an X that is only read, else None"""
         dt = self.nmf_kwargs.get('dtype')
-        return dt is not None and np.dtype(dt) == np.float16
+        for store in (np.float16, np.uint8):
+            if dt is not None and np.dtype(dt) == store:
+                return store
+        return None
 
     def constrained_transform(self, X):
         return self.transform(X)
