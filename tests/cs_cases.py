@@ -13,6 +13,12 @@ Shape: n, d, k = 700, 333, 6, planted_X(seed=5) and scaled_init(seed=6) as the t
 before.  Two exceptions, both forced by rri_bind_X_device, which refuses a d that is no multiple of 16 bytes / itemsize:
 the float32 flavour runs at d = 336 and the directed bind_X_device and bind_mask_device cases (float64) at d = 334.
 
+The uint8 flavour ('gram-u8', d = 336, a multiple of its 8-byte loads) stores counts C with zeros and two float64 vectors; its X is
+(C * s) * r[:, None].  The model holds C, r and s next to X: upload_X and bind_X (a torch.uint8 tensor) put both vectors back to
+ones, set_X_scales(salt) replaces the row vector, the column vector or both, scale_X multiplies s, and preprocess leaves the
+oracle's normalize(tfidf(X)) of the scaled matrix, with s * idf and r / row total in the vectors.  Nothing is rounded twice, so
+scale_X and preprocess are in its alphabet at the float64 tolerance, and -- as they write no matrix -- also on a bound X.
+
 What the operations deviate from a plain nmf() call in, and why:
   * 'simplex' (t_row_sum=1 with project_T_each_iter): rri_oracle.nmf projects the T it is given before its first sweep, as the
     reference does, and rri_sweep does not (the driver nmf.py projects and sets T).  So set_params('simplex') is the driver's
@@ -76,6 +82,9 @@ FLAVOURS = {
     # the directed bind_X_device / bind_mask_device cases only (no random sequences): float64 at an even d
     'gram-bind': dict(kind='plain', dtype=np.float64, d=D_BIND, env={'RRI_ONCHIP': '0'}),
     'weighted-bind': dict(kind='weighted', dtype=np.float64, d=D_BIND, env={}),
+    # uint8 counts C with float64 row and column scales r, s (RRI_U8): X = (C * s) * r[:, None], nothing rounded.  Appended last:
+    # draw_sequence seeds by the position in RANDOM_FLAVOURS, and the sequences of the flavours above stay what they were
+    'gram-u8': dict(kind='plain', dtype=np.uint8, d=D_F32, env={}),
 }
 RANDOM_FLAVOURS = [f for f in FLAVOURS if not f.endswith('-bind')]
 DIRECTED_ONLY = ['bind_mask']        # operations that no random alphabet has: bind_mask_device refuses the odd d of the weighted flavours
@@ -108,7 +117,15 @@ def alphabet(flavour):
         # scale_X rewrites a float32 X in place: a second rounding whose order the model would have to mirror; the float64
         # flavours own it.  In exchange this flavour's d lets it bind
         ops = [o for o in ops if o not in ('scale_X', 'preprocess')] + ['bind_X']
+    if f['dtype'] == np.uint8:
+        # the two bandwidth probes are refused on this store (they write an X-sized buffer of the storage type); scale_X and
+        # preprocess write the scale vectors only, so nothing is rounded twice and they stay, also on a bound X
+        ops = [o for o in ops if o not in ('bench_rank1', 'bench_copy')] + ['bind_X', 'set_X_scales']
     return ops
+
+
+def is_counts(flavour):
+    return FLAVOURS[flavour]['dtype'] == np.uint8
 
 
 def category(name):
@@ -160,7 +177,9 @@ COVERAGE = {
 NO_CHANGED = {'rri_X_times': 'X_times', 'rri_sparse_range_finder': 'sparse_range_finder', 'rri_bench_stream_copy': 'bench_copy',
               'rri_snapshot': 'snapshot', 'rri_objective': 'objective', 'rri_objective_parts': 'objective_parts',
               'rri_residual_rebuild': 'residual_check', 'rri_update_T_row': 'update_T_row', 'rri_update_W_col': 'update_W_col',
-              'rri_apply_reset_vectors': 'reset', 'rri_sweep': 'sweep', 'rri_csr_column_positive_counts': 'preprocess_csr'}
+              'rri_apply_reset_vectors': 'reset', 'rri_sweep': 'sweep', 'rri_csr_column_positive_counts': 'preprocess_csr',
+              # drops what the handle computed from X through rri_scale_X(c, nullptr, 0), not by a changed() of its own
+              'rri_set_X_scales': 'set_X_scales'}
 EXCLUDED_METHODS = {'attach_group': 'the sharded and group tests own it', 'bind_reduce_buffer': 'the sharded and group tests own it',
                     'topic_reduce_local': 'sharded', 'topic_finish': 'sharded', 'topic_finish_w': 'sharded',
                     'reduce_read': 'sharded', 'reduce_write': 'sharded', 'reduce_buffer': 'sharded',
@@ -175,7 +194,7 @@ OP_METHODS = {
     'X_times': ['X_times'], 'Xt_times': ['Xt_times'], 'range_finder': ['range_finder'], 'sparse_range_finder': ['sparse_range_finder'],
     'colcounts': ['column_positive_counts'], 'bench_rank1': ['bench_rank1_update'], 'bench_copy': ['bench_stream_copy'],
     'residual_update': ['residual_update'], 'objective': ['objective'], 'objective_parts': ['objective_parts'],
-    'residual_check': ['residual_rebuild', 'get_residual'],
+    'residual_check': ['residual_rebuild', 'get_residual'], 'set_X_scales': ['set_X_scales'],
 }
 
 
@@ -189,9 +208,25 @@ def _sparse_ish(X, salt):
     return X * (np.random.RandomState(1000 + salt).rand(*X.shape) < 0.35)
 
 
+def counts_of(X):
+    """term counts 0..255 of a non-negative X with zeros, in float64: the positive entries 40 on average, clipped at 255"""
+    return np.minimum(np.round(40.0 * X / X[X > 0].mean()), 255.0)
+
+
+def x_scales(d, salt):
+    """(row_scale or None, col_scale or None) of set_X_scales(salt): the row vector only, the column vector only, or both, drawn
+    from 10^U(-1, 1)"""
+    rs = np.random.RandomState(10000 + salt)
+    r, s = 10.0 ** rs.uniform(-1, 1, N), 10.0 ** rs.uniform(-1, 1, d)
+    return (r, None, r)[salt % 3], (None, s, s)[salt % 3]
+
+
 def other_X(d, salt, dtype, sparse):
-    """another X of the same family; three salts in four give one with zeros, as do the kinds whose X is sparse"""
+    """another X of the same family; three salts in four give one with zeros, as do the kinds whose X is sparse; for the uint8
+    store counts, always with zeros"""
     X = planted_X(N, d, K, seed=15 + salt, dtype=np.float64)
+    if dtype == np.uint8:
+        return counts_of(_sparse_ish(X, salt))
     if sparse or salt % 4:
         X = _sparse_ish(X, salt)
     return stored(X, dtype)
@@ -218,6 +253,8 @@ def start(flavour):
     f = FLAVOURS[flavour]
     d, kind = f['d'], f['kind']
     X = planted_X(N, d, K, seed=5, dtype=np.float64)
+    if f['dtype'] == np.uint8:
+        X = counts_of(_sparse_ish(X, 0))
     W0, T0 = scaled_init(X, K, seed=6)
     M = None
     if kind == 'csr':
@@ -263,11 +300,12 @@ class LegalState(object):
     """What the next draw and the bounds may depend on, cheap to follow without running the oracle: the generator follows it
     alone, the model follows it next to its arrays (Model.apply), so there is one copy of these rules."""
 
-    def __init__(self, kind):
+    def __init__(self, kind, counts=False):
         self.pname = 'free'
         self.has_snap = False
-        self.x_bound = False                # X is bound caller memory: rri_scale_X refuses it
-        self.x_has_zeros = kind == 'csr'    # preprocess needs an X with zeros (see the module docstring)
+        self.counts = counts                # a uint8 store: X always has zeros, and a bound X is rescaled like any other
+        self.x_bound = False                # X is bound caller memory: rri_scale_X refuses it, unless it writes scale vectors only
+        self.x_has_zeros = kind == 'csr' or counts    # preprocess needs an X with zeros (see the module docstring)
         self.t_feasible = False             # the rows of T sum to 1
         self.snap_feasible = False
         # could the cross terms of a whole sweep be valid (xy_valid)?  Only if the last operation that changed the state was a
@@ -283,7 +321,7 @@ class LegalState(object):
             return not p.get('fix_T')
         if n == 'update_W_col':
             return not p.get('fix_W')
-        if n in ('scale_X', 'preprocess') and self.x_bound:
+        if n in ('scale_X', 'preprocess') and self.x_bound and not self.counts:
             return False
         if n == 'preprocess':
             return self.x_has_zeros
@@ -311,7 +349,7 @@ class LegalState(object):
             self.t_feasible = False
         elif n in ('upload_X', 'bind_X'):
             self.x_bound = n == 'bind_X'
-            self.x_has_zeros = bool(a % 4)          # other_X
+            self.x_has_zeros = bool(a % 4) or self.counts          # other_X
 
 
 class Model(object):
@@ -324,7 +362,10 @@ class Model(object):
         self.kind, self.d, self.dtype = self.f['kind'], self.f['d'], self.f['dtype']
         self.X, self.M, self.W0, self.T0 = start(flavour)
         self.W, self.T = self.W0.copy(), self.T0.copy()
-        self.ls = LegalState(self.kind)
+        self.counts = is_counts(flavour)
+        if self.counts:         # X = (C * s) * r[:, None]; upload_X and bind_X put both vectors back to ones
+            self.C, self.r, self.s = self.X, np.ones(N), np.ones(self.d)
+        self.ls = LegalState(self.kind, self.counts)
         self.snap = None
         self.skip_col = None        # column of W the last operation leaves to the next W half (update_T_row)
 
@@ -419,11 +460,25 @@ class Model(object):
             self.W[:, a] = col
         elif n in ('upload_X', 'bind_X', 'upload_X_csr'):
             self.X = other_X(self.d, a, self.dtype, sparse=self.kind == 'csr')
+            if self.counts:
+                self.C, self.r, self.s = self.X, np.ones(N), np.ones(self.d)
+        elif n == 'set_X_scales':
+            r, s = x_scales(self.d, a)
+            self.r, self.s = self.r if r is None else r, self.s if s is None else s
+            self.X = scaled_counts(self.C, self.r, self.s)
         elif n == 'scale_X':
-            self.X = self.X * col_scale(self.d, a)
+            if self.counts:
+                self.s = self.s * col_scale(self.d, a)
+                self.X = scaled_counts(self.C, self.r, self.s)
+            else:
+                self.X = self.X * col_scale(self.d, a)
         elif n in ('preprocess', 'preprocess_csr'):
             before = float(self.X.mean())
-            self.X = oracle().normalize(oracle().tfidf(self.X))
+            Xt = oracle().tfidf(self.X)
+            if self.counts:     # what the two vectors hold afterwards; X itself is the oracle's, as for every other store
+                idf = np.asarray(oracle().tfidf(self.X, return_idf=True)[1], dtype=np.float64).ravel()
+                self.s, self.r = self.s * idf, self.r / (np.asarray(Xt.sum(1)).ravel() + np.spacing(1))
+            self.X = oracle().normalize(Xt)
             self.W = self.W * (float(self.X.mean()) / before)
         elif n in ('upload_mask', 'bind_mask'):
             self.M = weights(self.d, a)
@@ -451,7 +506,15 @@ class Model(object):
         return None
 
     def state(self):
-        return dict(X=self.X, M=self.M, W=self.W.copy(), T=self.T.copy(), pname=self.pname)
+        st = dict(X=self.X, M=self.M, W=self.W.copy(), T=self.T.copy(), pname=self.pname)
+        if self.counts:
+            st.update(C=self.C, r=self.r, s=self.s)
+        return st
+
+
+def scaled_counts(C, r, s):
+    """the X of a uint8 handle, in the order its kernels multiply: (C * s) * r[:, None]"""
+    return np.ascontiguousarray((C * s) * r[:, None])
 
 
 def rescale_after_preprocess(X):
@@ -544,6 +607,8 @@ def apply_engine(e, m, op):
         return e.upload_X_csr(sp.csr_matrix(other_X(d, a, dt, True)))
     if n == 'scale_X':
         return e.scale_X(col_scale(d, a))
+    if n == 'set_X_scales':
+        return e.set_X_scales(*x_scales(d, a))
     if n in ('preprocess', 'preprocess_csr'):
         W = e.get_W()
         idf = e.preprocess(tfidf=True, normalize=True) if n == 'preprocess' else e._preprocess_csr(True, True)
@@ -596,7 +661,7 @@ def relfro(a, b):
 
 
 def factor_tol(flavour):
-    return 1e-9 if FLAVOURS[flavour]['dtype'] == np.float64 else 1e-7
+    return 1e-7 if FLAVOURS[flavour]['dtype'] == np.float32 else 1e-9       # uint8 counts with float64 scales: nothing is rounded
 
 
 def objective_tol(m, want):
@@ -737,7 +802,8 @@ def healthy(flavour, ops):
 DEFAULT_SEEDS = 24
 REDRAWS = {('gram-onchip', 2): 1, ('gram-onchip', 3): 1, ('gram-onchip', 7): 1, ('gram-onchip', 9): 1, ('gram-onchip', 13): 1,
            ('gram-onchip', 19): 1, ('gram-phases', 14): 1, ('residual', 10): 1, ('residual', 13): 1, ('csr', 3): 1, ('csr', 6): 1,
-           ('csr', 10): 1, ('csr', 12): 1, ('csr', 22): 1, ('gram-fp32', 9): 1}
+           ('csr', 10): 1, ('csr', 12): 1, ('csr', 22): 1, ('gram-fp32', 9): 1,
+           ('gram-u8', 21): 1}
 
 
 def random_sequence(flavour, seed):
@@ -758,15 +824,20 @@ def draw_sequence(flavour, seed, attempt):
     by = {STATE: [x for x in names if category(x) == STATE], LOOK: [x for x in names if category(x) == LOOK]}
     slots = [STATE] * 6 + [LOOK] * 3 + ['any']
     rs.shuffle(slots)
-    m = LegalState(FLAVOURS[flavour]['kind'])
+    m = LegalState(FLAVOURS[flavour]['kind'], is_counts(flavour))
     ops = []
     for slot in slots:
         pool = names if slot == 'any' else by[slot]
         for _ in range(100):
             op = draw_op(rs, pool[int(rs.randint(len(pool)))])
             # preprocess is legal only after an X with zeros went up: taken every other time it could be, or it is hardly seen
-            if 'preprocess' in pool and m.legal(Op('preprocess')) and not any(o.name == 'preprocess' for o in ops) and rs.rand() < 0.5:
+            # (counts always have zeros: there it is drawn like any other operation)
+            if 'preprocess' in pool and not m.counts and m.legal(Op('preprocess')) and not any(o.name == 'preprocess' for o in ops) and rs.rand() < 0.5:
                 op = Op('preprocess')
+            # counts: a changed scale matters to what a sweep or an objective has just left on the handle, and right behind one of
+            # those it is one of the 15 state-changing operations of a pool of 21: taken every other time it could be
+            if m.counts and 'set_X_scales' in pool and ops and ops[-1].name in ('sweep', 'objective', 'objective_parts') and rs.rand() < 0.5:
+                op = draw_op(rs, 'set_X_scales')
             if m.legal(op):
                 break
         else:
@@ -801,6 +872,8 @@ class Case(object):
       ('penalty', j)     the objective with the penalties before operation j
       ('objective', j)   the objective of the W and T before operation j (what the persistent launch left)
       ('factors', j, fields)  the last operation (a sweep) run from the current state with `fields` as they were before operation j
+      ('T_row', j)       the last operation (update_T_row) with the row computed from the X before operation j
+      ('scales', j)      the last two operations (sweep(1), objective) on the current counts under the scales before operation j
     """
 
     def __init__(self, name, row, flavour, ops, stale=None, waived=None, raises=None):
@@ -868,6 +941,23 @@ for _name, _b in (('Xt_times', ('Xt_times', 1)), ('column_positive_counts', ('co
 CASES.append(_case('ended-zero_column', 'carry_valid / pending_wcheck (CH_ENDED)', 'gram-phases',
                    [('zero_W_column', 2), S1, ('set_W', 3), S1], raises=1,
                    waived='an error is a verdict, not a value'))
+# ---- the uint8 store: the two scale vectors are per-handle state and a part of X -------------------------------------------------
+_SC = ('set_X_scales', 5)       # 5 % 3 == 2: both vectors
+CASES.append(_case('x_sq-set_X_scales', 'x_sq_valid', 'gram-u8', [S1, OBJ, _SC, S1, OBJ], stale=('x_sq', 2)))
+CASES.append(_case('xy-set_X_scales', 'xy_run / xy_valid', 'gram-u8', [S1, OBJ, _SC, OBJ], stale=('xy', 2)))
+CASES.append(_case('q-set_X_scales', 'q_valid / gfull_valid', 'gram-u8', [('set_params', 'fix_T'), S1, _SC, S1],
+                   stale=('factors', 2, ('X',))))
+# carry_valid: the partial sums of topic 0 that a free sweep leaves were taken from the old X; unlike an overwritten scratch
+# buffer, that is a value the oracle has
+CASES.append(_case('carry-set_X_scales-sweep', 'carry_valid / carry_topic', 'gram-u8', [S1, _SC, S1], stale=('factors', 1, ('X',))))
+CASES.append(_case('carry-set_X_scales-update_T_row', 'carry_valid / carry_topic', 'gram-u8', [S1, _SC, ('update_T_row', 0)],
+                   stale=('T_row', 1)))
+# a new X puts both vectors back to ones: the stale handle factorises the new counts under the old scales
+for _name, _chg in (('upload_X', ('upload_X', 2)), ('bind_X', ('bind_X', 2))):
+    CASES.append(_case('scales-reset-by-%s' % _name, 'rscale / cscale', 'gram-u8', [_SC, S1, _chg, S1, OBJ], stale=('scales', 2)))
+# rri_scale_X on a bound X, which only this store allows
+CASES.append(_case('q-scale_X-bound', 'q_valid / gfull_valid', 'gram-u8',
+                   [('bind_X', 3), ('set_params', 'fix_T'), S1, ('scale_X', 7), S1], stale=('factors', 3, ('X',))))
 CASES = {c.name: c for c in CASES}
 
 
@@ -899,4 +989,17 @@ def stale_reference(case):
             src[f] = old[f]
         W, T = m.sweep_from(src['X'], src['M'], src['W'], src['T'], case.ops[-1].arg, pname=cur['pname'])
         return (m.W, m.T), (W, T)
+    if kind == 'T_row':
+        t = case.ops[-1].arg
+        ms = Model(case.flavour)
+        ms.ls.pname, ms.X, ms.W, ms.T = cur['pname'], old['X'], cur['W'], cur['T']
+        T = m.T.copy()
+        T[t, :] = ms.half_T(t)
+        return (m.W, m.T), (m.W, T)
+    if kind == 'scales':
+        assert [o.name for o in case.ops[-2:]] == ['sweep', 'objective']
+        before = states[-2]
+        Xs = scaled_counts(before['C'], old['r'], old['s'])
+        W, T = m.sweep_from(Xs, None, before['W'], before['T'], case.ops[-2].arg, pname=before['pname'])
+        return answers[-1], m.objective_at(Xs, None, W, T)
     raise KeyError(kind)

@@ -1,4 +1,4 @@
-"""Matrices with a row stride larger than their width, inside bands of NaN: the cases of tests/test_strided_bind_gpu.py
+"""Matrices with a row stride larger than their width, inside bands of NaN (uint8: of 0xFF): the cases of tests/test_strided_bind_gpu.py
 (tests/test_ld_cases_cpu.py checks the cases and the builder themselves, without a GPU).
 
 rri_bind_X_device and rri_bind_mask_device take a row stride ld >= d, so that a slice Xwide[r0:r0 + n, c0:c0 + d] of a wider
@@ -15,10 +15,17 @@ allocation, so a read past the last row lands in the band, never outside the all
 of the streaming pass (rri_layout_info field 8, asserted by the GPU test), so a row block that starts inside the matrix ends
 inside the allocation.
 
+uint8 counts (RRI_U8) have no NaN.  Their guard byte is 0xFF, the largest count: a read at the wrong stride or past row n pulls
+255s into a sum, far outside every bound that the sums are held to against the float64 reference (the band is then seen through
+the reference, not through a non-finite output).  What is lost against NaN: a read past column d whose value is multiplied by an
+operand of 0 adds 255 * 0 = 0 and stays invisible, where NaN * 0 is NaN.  Such a read is also harmless.  A write is seen as
+before, bit for bit.  Their vectors are 8 bytes (VN = 8, a workgroup of the pass spans 2048 columns), their matrices counts
+0 .. 255 with zeros.
+
 The builder works on numpy arrays (the CPU test) and on torch tensors (the GPU test): guarded(np, ...) / guarded(torch, ...).
 
-Case table, VN = 16 / itemsize (the elements of a 16-byte vector; binding needs d % VN == 0):
-    d       one column tile (d < 64) | three column tiles, the last ragged | two column panels of the streaming pass (4 KiB each)
+Case table, VN = 16 / itemsize (the elements of a 16-byte vector; uint8: the 8 of an 8-byte one; binding needs d % VN == 0):
+    d       one column tile (d < 64) | three column tiles, the last ragged | two column panels of the streaming pass (256 vectors each)
     n       130 and 203 (3 and 4 row blocks of 64, both ragged) for the two small d; 70 for the two-panel d
     ld, c0  (d + VN, 0): the smallest legal pad;  (d + 65 VN, VN): a pad wider than the 64 vectors one wave covers, and a column
             offset -- a lane whose column test took ld for d still reads inside the allocation, and reads NaN
@@ -28,15 +35,27 @@ import collections
 import numpy as np
 
 G = 256
-STORES = {'fp32': np.float32, 'fp64': np.float64, 'fp16': np.float16}
-WIDTHS = {'fp32': (36, 140, 1028), 'fp64': (38, 142, 516), 'fp16': (40, 136, 2056)}
+STORES = {'fp32': np.float32, 'fp64': np.float64, 'fp16': np.float16, 'u8': np.uint8}
+WIDTHS = {'fp32': (36, 140, 1028), 'fp64': (38, 142, 516), 'fp16': (40, 136, 2056), 'u8': (40, 136, 2056)}
+GUARD_BYTE = 0xFF
 ROWS_SMALL, ROWS_TWO_PANELS = (130, 203), (70,)
 
 Case = collections.namedtuple('Case', 'name store dtype n d ld c0')
 
 
 def vn_of(dtype):
-    return 16 // np.dtype(dtype).itemsize
+    """elements of one load of the handle: a 16-byte vector; uint8 counts take 8-byte loads"""
+    return 8 if np.dtype(dtype) == np.uint8 else 16 // np.dtype(dtype).itemsize
+
+
+def guard_of(dtype):
+    """what every element outside the matrix holds"""
+    return GUARD_BYTE if np.dtype(dtype) == np.uint8 else float('nan')
+
+
+def is_guard(a):
+    """element-wise: does a (a numpy array of a storage type) hold the guard value?"""
+    return a == GUARD_BYTE if a.dtype == np.uint8 else np.isnan(a)
 
 
 def strides_of(d, dtype):
@@ -73,7 +92,7 @@ def cases(store=None, widths=None, rows=None, pads=None):
     return out
 
 
-_INT_NAME = {2: 'int16', 4: 'int32', 8: 'int64'}
+_INT_NAME = {1: 'int8', 2: 'int16', 4: 'int32', 8: 'int64'}
 
 
 def _is_numpy(xp):
@@ -103,7 +122,7 @@ class Guarded(object):
             self.buf[g:g + n, c0:c0 + d] = values
             base = self.buf.ctypes.data
         else:
-            self.buf = xp.full((rows, ld), float('nan'), dtype=getattr(xp, np.dtype(values.dtype).name), device=device)
+            self.buf = xp.full((rows, ld), guard_of(values.dtype), dtype=getattr(xp, np.dtype(values.dtype).name), device=device)
             self.buf[g:g + n, c0:c0 + d] = xp.from_numpy(values).to(device)
             base = self.buf.data_ptr()
         self.view = self.buf[g:g + n, c0:c0 + d]
@@ -141,12 +160,12 @@ class Guarded(object):
 
 
 def _aligned_full(rows, ld, dtype, align=64):
-    """a NaN-filled rows x ld numpy array whose first element sits at a multiple of `align` bytes"""
+    """a rows x ld numpy array of guard values whose first element sits at a multiple of `align` bytes"""
     dtype = np.dtype(dtype)
     raw = np.empty(rows * ld * dtype.itemsize + align, dtype=np.uint8)
     skip = (-raw.ctypes.data) % align
     buf = raw[skip:skip + rows * ld * dtype.itemsize].view(dtype).reshape(rows, ld)
-    buf[...] = np.nan
+    buf[...] = guard_of(dtype)
     return buf
 
 
@@ -155,7 +174,23 @@ def guarded(xp, values, ld, c0, g=G, device=None):
 
 
 def case_matrix(case, seed=0):
-    """the matrix of a case in its storage type: positive, low rank plus noise, rounded once (planted_X's recipe at any size)"""
+    """the matrix of a case in its storage type: positive, low rank plus noise, rounded once (planted_X's recipe at any size);
+    uint8: counts 0 .. 255 with zeros, round(40 P / mean(P)) clipped (count_problem of tests/test_count_storage_gpu.py)"""
     from rri_nmf_amd.synthetic import planted_X
     c = CASES[case] if isinstance(case, str) else case
-    return np.ascontiguousarray(planted_X(c.n, c.d, 6, seed=seed + c.n + c.d, dtype=np.float64).astype(c.dtype))
+    P = planted_X(c.n, c.d, 6, seed=seed + c.n + c.d, dtype=np.float64)
+    if np.dtype(c.dtype) == np.uint8:
+        P = np.minimum(np.round(40.0 * P / P.mean()), 255.0)
+    return np.ascontiguousarray(P.astype(c.dtype))
+
+
+def case_scales(case, seed=0):
+    """(row_scale, col_scale) of a uint8 case, log-uniform over 0.1 .. 10: set after the bind, which puts both back to ones"""
+    c = CASES[case] if isinstance(case, str) else case
+    rs = np.random.RandomState(seed + 7 * c.n + c.d)
+    return 10.0 ** rs.uniform(-1, 1, c.n), 10.0 ** rs.uniform(-1, 1, c.d)
+
+
+def scaled(C, r, s):
+    """the float64 matrix a uint8 handle factorises: (C * s) * r[:, None]"""
+    return np.ascontiguousarray((np.asarray(C, dtype=np.float64) * s) * r[:, None])

@@ -3,9 +3,10 @@ coverage list is the code's, and that the seeded sequences are what they promise
 
 Every directed case whose staleness can be written in oracle terms carries a stale reference: what a handle that kept the named
 value would answer (old T and X for Qt / Gfull, old X for ||X||^2, old W / T / X for the cross terms, old penalties or old
-factors for the tracked objective, old mask / W / T for E).  It must lie at least 1e3 times the case's tolerance away from the
-true answer.  Waived, with the reason in the case: the carry cases and the foreign residual update (an overwritten buffer is no
-value the oracle has), the legitimate stored-E path (nothing is stale) and the error case (a verdict, not a value)."""
+factors for the tracked objective, old mask / W / T for E; for the uint8 store the old scale vectors, also under new counts,
+and the old X for the carried partial sums of topic 0).  It must lie at least 1e3 times the case's tolerance away from the true
+answer.  Waived, with the reason in the case: the carry cases after a borrower and the foreign residual update (an overwritten
+buffer is no value the oracle has), the legitimate stored-E path (nothing is stale) and the error case (a verdict, not a value)."""
 import os
 import re
 
@@ -124,6 +125,37 @@ def test_the_random_sequences_meet_their_quotas(flavour):
         assert repr(ops[-2]) == 'sweep(1)' and repr(ops[-1]) == 'objective'
         seen |= set(names)
     assert seen == set(cs.alphabet(flavour)), 'never drawn in the default seeds: %s' % sorted(set(cs.alphabet(flavour)) - seen)
+
+
+def test_the_sequences_of_the_earlier_flavours_are_what_they_were():
+    """draw_sequence seeds by the position of a flavour in RANDOM_FLAVOURS: the uint8 flavour is appended after all others, so the
+    24 default sequences of the seven flavours before it, and their redraws, are those that ran before it existed (the digest
+    was taken from the module as it was then)"""
+    import hashlib
+    earlier = ['gram-onchip', 'gram-phases', 'residual', 'weighted', 'pattern', 'csr', 'gram-fp32']
+    assert cs.RANDOM_FLAVOURS == earlier + ['gram-u8'] and list(cs.FLAVOURS)[-1] == 'gram-u8'
+    h = hashlib.sha256()
+    for flavour in earlier:
+        for seed in range(24):
+            h.update(repr((flavour, seed, cs.random_sequence(flavour, seed))).encode())
+    assert h.hexdigest() == '9e0401d0fbd8dd1ea8897eb0db008bf5d8f96a8aaf8410c89329acce878e7085'
+    before = {('gram-onchip', 2): 1, ('gram-onchip', 3): 1, ('gram-onchip', 7): 1, ('gram-onchip', 9): 1, ('gram-onchip', 13): 1,
+              ('gram-onchip', 19): 1, ('gram-phases', 14): 1, ('residual', 10): 1, ('residual', 13): 1, ('csr', 3): 1, ('csr', 6): 1,
+              ('csr', 10): 1, ('csr', 12): 1, ('csr', 22): 1, ('gram-fp32', 9): 1}
+    assert {key: val for key, val in cs.REDRAWS.items() if key[0] != 'gram-u8'} == before
+
+
+def test_the_uint8_model_keeps_counts_and_scales_consistent_with_its_X():
+    """after every operation of every default sequence the model's X is (C * s) * r[:, None] of the C, r, s it holds (to the
+    rounding of preprocess, which takes X from the oracle), and a new X has both vectors at one"""
+    for seed in range(cs.DEFAULT_SEEDS):
+        m = cs.Model('gram-u8')
+        for op in cs.random_sequence('gram-u8', seed):
+            m.apply(op)
+            assert cs.relfro(cs.scaled_counts(m.C, m.r, m.s), m.X) < 1e-14, (seed, op)
+            assert np.array_equal(m.C, np.round(m.C)) and m.C.min() == 0 and m.C.max() <= 255
+            if op.name in ('upload_X', 'bind_X'):
+                assert np.array_equal(m.r, np.ones(cs.N)) and np.array_equal(m.s, np.ones(m.d)) and np.array_equal(m.X, m.C)
 
 
 @pytest.mark.parametrize('flavour', cs.RANDOM_FLAVOURS)

@@ -212,6 +212,32 @@ def test_sweep_after_a_call_that_ended_in_an_error(monkeypatch):
     run_case(monkeypatch, case.flavour, case.ops, raises=case.raises)
 
 
+# ---- the uint8 store: the scale vectors are a part of X ----------------------------------------------------------------------
+@pytest.mark.parametrize('row', ['x_sq', 'xy', 'q'])
+def test_a_changed_scale_drops_what_came_from_X(monkeypatch, row):
+    """rri_set_X_scales on a uint8 handle between the operations that fill and use ||X||^2 (x_sq_valid), the cross terms of a
+    sweep (xy_valid) and Qt = X T^T of a fixed-T sweep (q_valid): it calls no changed() itself but goes through rri_scale_X"""
+    directed(monkeypatch, row + '-set_X_scales')
+
+
+@pytest.mark.parametrize('then', ['sweep', 'update_T_row'])
+def test_carry_after_a_changed_scale(monkeypatch, then):
+    """carry_valid: a free sweep leaves the partial sums of topic 0 taken from X; both scale vectors change; sweep(1) or
+    update_T_row(0) must take them from the new X"""
+    directed(monkeypatch, 'carry-set_X_scales-' + then)
+
+
+@pytest.mark.parametrize('route', ['upload_X', 'bind_X'])
+def test_a_new_X_puts_the_scales_back_to_ones(monkeypatch, route):
+    """set_X_scales, sweep(1), other counts uploaded or bound, sweep(1), objective(): the new counts are factorised as they are"""
+    directed(monkeypatch, 'scales-reset-by-' + route)
+
+
+def test_fixed_T_products_after_scaling_a_bound_X(monkeypatch):
+    """q_valid on bound memory: only a uint8 handle rescales a bound X (it writes the column scales, no matrix)"""
+    directed(monkeypatch, 'q-scale_X-bound')
+
+
 @pytest.mark.parametrize('seed', range(cs.n_seeds()))
 @pytest.mark.parametrize('flavour', cs.RANDOM_FLAVOURS)
 def test_random_sequence(monkeypatch, flavour, seed):

@@ -223,6 +223,49 @@ def test_single_steps_at_the_geometry_edges(n, d):
             assert_rel(e.objective(), orc.true_objective(X, W, T), 1e-12, 'objective after the steps')
 
 
+# Row blocks that are not the 32-row minimum.  rri_create takes ceil(n / (total / npanels)) rows with total = 1024 if that gives
+# 192 rows or more and with total = 512 otherwise, then max(., 32), rounded up to 16:
+#   6011 x 4099: LD 4104, 3 panels, 512 / 3 = 170 blocks, ceil(6011 / 170) = 36 -> 48 rows, 126 blocks, the last of 11 rows
+#   8209 x 6150: LD 6152, 4 panels, 512 / 4 = 128 blocks, ceil(8209 / 128) = 65 -> 80 rows, 103 blocks, the last of 49 rows
+#                (six interleaved chunks of 8 rows and one row)
+# 378 and 412 workgroups: interleaved chunks.
+BLOCK_SHAPES = {'6011x4099-48rows': (6011, 4099, 3, 48, 126, 11), '8209x6150-80rows': (8209, 6150, 4, 80, 103, 49)}
+
+
+@pytest.mark.parametrize('shape', list(BLOCK_SHAPES))
+def test_single_steps_with_row_blocks_above_the_minimum(shape):
+    """several panels times a hundred row blocks of 48 and 80 rows with a ragged last block: the objective right after
+    set_W / set_T, the max-residual row and the reset row of the last row, and single topic steps, against the oracle on X64"""
+    orc = oracle()
+    n, d, npanels, rpb, nrb, last = BLOCK_SHAPES[shape]
+    for k, flags in ((2, 'topic'), (50, 'plain')):
+        C, r, s, X, W0, T0 = count_problem(n, d, k, seed=n + d)
+        with engine(n, d, k, dtype=U8) as e:
+            info = e.layout_info()
+            assert (info['npanels'], info['rpb'], info['nrb']) == (npanels, rpb, nrb) and n - (nrb - 1) * rpb == last, info
+            assert info['interleaved'] and npanels * nrb <= 1024, info
+            loaded(e, C, r, s, W0, T0, **FLAGS[flags])
+            got, want = e.objective(), orc.true_objective(X, W0, T0)
+            print('%s k=%d %s: objective after set factors, relative error %.3e' % (shape, k, flags, abs(got - want) / abs(want)))
+            assert_rel(got, want, 1e-12, 'objective right after set_W / set_T')
+            R = X - W0 @ T0
+            pos = (np.maximum(R, 0.0) ** 2).sum(axis=1)
+            val, row = e.resid_row_argmax()
+            assert row == int(np.argmax(pos)), (row, int(np.argmax(pos)))
+            print('%s k=%d %s: max-residual row %d (row block %d), relative error %.3e' % (
+                shape, k, flags, row, row // rpb, abs(val - pos.max()) / pos.max()))
+            assert_rel(val, pos.max(), 1e-12, 'sum_j max(X - W T, 0)^2 of the max-residual row')
+            i = n - 1
+            assert_elementwise(e.reset_row(i)[None, :], np.maximum(R[i], 0.0)[None, :], resid_bound(X[i:], W0[i:], T0),
+                               'reset row %d (the last row of the ragged block)' % i)
+            del R
+            check_steps(e, X, k, FLAGS[flags])
+            W, T = e.get_W(), e.get_T()
+            got, want = e.objective(), orc.true_objective(X, W, T)
+            print('%s k=%d %s: objective after the steps, relative error %.3e' % (shape, k, flags, abs(got - want) / abs(want)))
+            assert_rel(got, want, 1e-12, 'objective after the steps')
+
+
 XT_M = [1, 16, 17, 33, 49, 64, 65, 129]
 XTQ_M = [1, 8, 9, 17]
 

@@ -7,7 +7,7 @@ of this process own.  No numerics, no tolerance.  torch.cuda.mem_get_info is dev
 shared device, so it is not used.  Every case collects garbage and reads its own baseline first: fixtures of other modules may
 hold handles.  Nothing is tested by making an allocation fail.
 
-Shapes: n, d, k = 300, 130, 5 -- pad columns in every storage type (LD = 132 in float32, 136 in float64 and float16); d = 128 for
+Shapes: n, d, k = 300, 130, 5 -- pad columns in every storage type (LD = 132 in float32, 136 in float64, float16 and uint8); d = 128 for
 the bind cases (rri_bind_X_device refuses pad columns); the persistent sweep at (50, 30, 3), the smallest shape of
 tests/test_onchip_gpu.py.
 """
@@ -42,7 +42,7 @@ def engine(*a, **kw):
 
 
 def ld_of(d, dtype):
-    vn = 16 // np.dtype(dtype).itemsize
+    vn = 8 if np.dtype(dtype) == np.uint8 else 16 // np.dtype(dtype).itemsize       # uint8 counts: 8-byte loads
     return -(-d // vn) * vn
 
 
@@ -65,6 +65,27 @@ def reset_max_resid(e, t):
 # flavour -> (RRIEngine keywords, upload(e, X)).  The sparse flavours see X on a 20 % pattern (no empty row).
 def _dense(e, X):
     e.upload_X(X.astype(e.dtype))
+
+
+def counts_of(X):
+    """counts 0 .. 255 with the values of X at 40 on average"""
+    return np.minimum(np.round(40.0 * X / X.mean()), 255.0).astype(np.uint8)
+
+
+def scales_of(X, seed=6):
+    """row and column scales that take counts_of(X) back to the size of X (the factors of problem() start there)"""
+    rs = np.random.RandomState(seed)
+    return (X.mean() / 40.0) * (0.5 + rs.rand(X.shape[0])), 0.5 + rs.rand(X.shape[1])
+
+
+def _counts(e, X):
+    """uint8 counts: X is the handle's, and so are the two scale vectors (n and LD float64, there from rri_create on)"""
+    created = memory()
+    e.upload_X(counts_of(X))
+    own = memory()
+    assert own == (created[0] + 1, created[1] + X.shape[0] * ld_of(X.shape[1], np.uint8)), (own, created)
+    e.set_X_scales(*scales_of(X))
+    assert memory() == own, 'rri_set_X_scales writes the vectors the handle has'
 
 
 def _weighted_fp(e, X):
@@ -94,6 +115,7 @@ FLAVOURS = {
     'weighted-dense-01-mask': (dict(dtype=np.float64, weighted=True), _weighted_01),
     'weighted-sparse': (dict(dtype=np.float64, weighted='sparse'), _pattern),
     'unweighted-sparse': (dict(dtype=np.float64, sparse_x=True), _csr),
+    'unweighted-u8': (dict(dtype=np.uint8), _counts),
 }
 
 
@@ -249,6 +271,34 @@ def _replace_csr(method):
     return steps
 
 
+def _replace_counts(e):
+    """a second X from each of the three host types a uint8 handle takes"""
+    C = counts_of(problem()[0])
+    e.upload_X(C)
+    yield None
+    for host in (np.float32, np.float64, np.uint8):
+        e.upload_X(np.ascontiguousarray(C[::-1].astype(host)))
+        yield None
+
+
+def _rescale_counts(e):
+    """the scale vectors are written where they are; the temporaries of a normalisation are given back"""
+    X = problem()[0]
+    e.upload_X(counts_of(X) * (np.random.RandomState(5).rand(N, D) < 0.5))        # with zeros: a term in every document has idf 0
+    yield None
+    for seed in (1, 2):
+        e.set_X_scales(*scales_of(X, seed))
+        yield None
+        e.set_X_scales(None, scales_of(X, seed + 2)[1])
+        yield None
+        e.scale_X(None, True)
+        yield None
+        e.scale_X(0.5 + np.random.RandomState(seed).rand(D), True)
+        yield None
+        e.preprocess(tfidf=True, normalize=True)
+        yield None
+
+
 REPLACEMENTS = {
     'upload_X': (dict(dtype=np.float32), _replace_X),
     'upload_mask': (dict(dtype=np.float64, weighted=True), _replace_mask),
@@ -256,6 +306,8 @@ REPLACEMENTS = {
     'upload_X_csr-kept': (dict(dtype=np.float64, sparse_x=True), _replace_csr('upload_X_csr')),
     'upload_observed_csr': (dict(dtype=np.float64, weighted='sparse'), _replace_csr('upload_observed_csr')),
     'upload_mask_csr_pattern': (dict(dtype=np.float64, weighted=True), _replace_csr('upload_mask_csr_pattern')),
+    'upload_X-u8': (dict(dtype=np.uint8), _replace_counts),
+    'set_X_scales-u8': (dict(dtype=np.uint8), _rescale_counts),
 }
 
 
@@ -344,3 +396,48 @@ def test_borrowed_memory_is_not_counted_and_not_freed():
     assert memory() == base
     torch.cuda.synchronize()
     assert float(tX.sum()) == x_sum and float(tM.sum()) == m_sum
+
+
+def test_counts_bound_after_an_upload_and_uploaded_after_a_bind():
+    """a uint8 handle: binding gives the handle's own X back (one buffer, n x LD bytes), an upload after a bind allocates it
+    again, and neither touches the two scale vectors, which stay the handle's; the bound tensor is never counted, and close()
+    leaves it as it was.  (Not an entry of REPLACEMENTS: a handle with a bound X owns less than one with its own.)"""
+    import torch
+    base = baseline()
+    X, W0, T0 = problem(d=D_BIND)
+    Cn = counts_of(X)
+    r, s = scales_of(X)
+    x_bytes = N * ld_of(D_BIND, np.uint8)
+    tC = torch.from_numpy(Cn).to('cuda:0').contiguous()
+    e = engine(N, D_BIND, K, dtype=np.uint8)
+    try:
+        created = memory()
+        e.upload_X(Cn)
+        assert memory() == (created[0] + 1, created[1] + x_bytes)
+        e.set_X_scales(r, s), e.set_W(W0), e.set_T(T0)
+        e.set_params(reset_topic_method=None)
+        own = memory()
+        assert own == (created[0] + 1, created[1] + x_bytes)
+        torch.cuda.synchronize()
+        c_sum = int(tC.sum())
+        e.bind_X_device(tC.data_ptr(), D_BIND)
+        assert memory() == created
+        e.set_X_scales(r, s)
+        e.scale_X(None, True)                         # legal on a bound X of this store: no matrix is written
+        assert memory() == created
+        e.sweep(1)
+        swept = memory()                              # (with what the sweep allocated on first use)
+        e.upload_X(Cn)
+        assert memory() == (swept[0] + 1, swept[1] + x_bytes)
+        e.bind_X_device(tC.data_ptr(), D_BIND)
+        assert memory() == swept
+        e.upload_X(Cn.astype(np.float64))
+        assert memory() == (swept[0] + 1, swept[1] + x_bytes)
+        e.set_X_scales(r, s)
+        e.sweep(1)
+        e.synchronize()
+    finally:
+        e.close()
+    assert memory() == base
+    torch.cuda.synchronize()
+    assert int(tC.sum()) == c_sum

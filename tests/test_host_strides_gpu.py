@@ -11,6 +11,10 @@ does) with ld = cols + 3:
   * ld < cols, or a host type the call does not take: RRI_ERR_INVALID, nothing changed.
 
 Shapes: (n, d, k) = (203, 141, 5) -- ragged in every tile, pad columns in the handle's own stride -- and (1, 37, 1).
+
+A uint8 handle (RRI_U8) takes its counts from float32, float64 and uint8 host buffers.  The pad of a float buffer holds NaN, which
+is no count and would be refused if it were read; the pad of a byte buffer holds 0xFF, which no element of the matrix does.  What
+is compared is the stored matrix, both scale vectors, and the state as for every other store.
 """
 import numpy as np
 import pytest
@@ -23,7 +27,7 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = {'n203xd141xk5': (203, 141, 5), 'n1xd37xk1': (1, 37, 1)}
 PAD = 3
-F = {'fp32': np.float32, 'fp64': np.float64, 'fp16': np.float16}
+F = {'fp32': np.float32, 'fp64': np.float64, 'fp16': np.float16, 'u8': np.uint8}
 SENTINEL = {2: 0x5A5A, 4: 0x5A5A5A5A, 8: 0x5A5A5A5A5A5A5A5A}
 UINT = {2: np.uint16, 4: np.uint32, 8: np.uint64}
 
@@ -39,9 +43,26 @@ def problem(n, d, k):
     return X, W0, T0
 
 
+def count_problem(n, d, k):
+    """counts 0 .. 254 with zeros, row and column scales over 0.1 .. 10, and a start scaled to (C * s) * r[:, None]"""
+    X, _, _ = problem(n, d, k)
+    C = np.minimum(np.round(40.0 * (X - 0.05) / X.mean()), 254.0)
+    C[:, d // 4] = 0.0
+    rs = np.random.RandomState(n + d + 2)
+    r, s = 10.0 ** rs.uniform(-1, 1, n), 10.0 ** rs.uniform(-1, 1, d)
+    W0, T0 = scaled_init((C * s) * r[:, None], k, seed=n + d + 1)
+    return C, r, s, W0, T0
+
+
+def stored_matrix(e):
+    return e.X_times(np.eye(e.d))
+
+
 def padded(a, fill=np.nan):
     """a copy of `a` inside rows of cols + PAD elements, the pad filled; returns (buffer, ld)"""
     a = np.ascontiguousarray(a)
+    if a.dtype == np.uint8:
+        fill = 0xFF
     buf = np.full((a.shape[0], a.shape[1] + PAD), fill, dtype=a.dtype)
     buf[:, :a.shape[1]] = a
     return buf, buf.shape[1]
@@ -113,6 +134,31 @@ def test_a_strided_input_leaves_the_state_of_the_contiguous_call(flavour, store,
         assert err[1] > 0.0, 'the upload rounded: rri_storage_error must say so'
 
 
+@pytest.mark.parametrize('shape', list(SHAPES))
+@pytest.mark.parametrize('host', ['fp32', 'fp64', 'u8'])
+def test_strided_counts_leave_the_state_of_the_contiguous_call(host, shape):
+    """rri_upload_X of a uint8 handle with ld = d + 3 from each host type it takes: the stored matrix, both scale vectors (ones
+    after an upload, whatever they were), the storage error and the state after set factors and one sweep"""
+    n, d, k = SHAPES[shape]
+    C, r, s, W0, T0 = count_problem(n, d, k)
+    a = np.ascontiguousarray(C.astype(F[host]))
+    out = []
+    for strided in (False, True):
+        with engine(n, d, k, dtype=np.uint8) as e:
+            e.upload_X(np.zeros((n, d), dtype=np.uint8))
+            e.set_X_scales(r, s)                      # the upload below must put them back
+            buf, ld = padded(a) if strided else (a, d)
+            if strided:
+                assert not (buf[:, d:] <= 255).any() if host != 'u8' else ((buf[:, d:] == 0xFF).all() and (a != 0xFF).all())
+            assert call(e, 'rri_upload_X', buf, ld) == _capi.RRI_OK, e._err()
+            got = [stored_matrix(e)] + list(e.X_scales()) + [e.storage_relerr]
+            assert np.array_equal(got[0], C) and np.array_equal(got[1], np.ones(n)) and np.array_equal(got[2], np.ones(d)) and got[3] == 0.0
+            e.set_X_scales(r, s)
+            e.set_W(W0); e.set_T(T0); e.set_params(reset_topic_method=None)
+            out.append(got + [stored_matrix(e)] + state(e))
+    assert_same_state(out[0], out[1], 'rri_upload_X of counts with ld = cols + %d from %s' % (PAD, host))
+
+
 OUTPUTS = [('plain', store, hx, which) for store in ('fp32', 'fp64') for hx in ('fp32', 'fp64') for which in ('rri_get_W', 'rri_get_T')]
 OUTPUTS += [('residual', store, hx, 'rri_get_residual') for store in ('fp32', 'fp64') for hx in ('fp32', 'fp64')]
 
@@ -151,22 +197,35 @@ def test_a_strided_output_fills_its_columns_and_keeps_the_pad(flavour, store, ho
             assert call(e, which, again, cols) == _capi.RRI_OK and again.tobytes() == want.tobytes()
 
 
-@pytest.mark.parametrize('flavour,store', [('plain', 'fp32'), ('plain', 'fp64'), ('plain', 'fp16'), ('weighted', 'fp64')])
+@pytest.mark.parametrize('flavour,store', [('plain', 'fp32'), ('plain', 'fp64'), ('plain', 'fp16'), ('weighted', 'fp64'), ('plain', 'u8')])
 def test_a_refused_input_changes_nothing(flavour, store):
-    """ld < cols and a host type the call does not take: RRI_ERR_INVALID, and W, T, the objective and rri_storage_error are what
-    they were (a float16 handle used to lose its X, and every handle its storage error, before the arguments were looked at)"""
+    """ld < cols, a NULL host pointer and a host type the call does not take: RRI_ERR_INVALID, and W, T, the objective and rri_storage_error are what
+    they were (a float16 handle used to lose its X, and every handle its storage error, before the arguments were looked at).
+    A uint8 handle with scales: its stored matrix and both scale vectors too; float16 halves are no host type of its X."""
     n, d, k = SHAPES['n203xd141xk5']
     X, W0, T0 = problem(n, d, k)
     M = (np.random.RandomState(1).rand(n, d) < 0.5).astype(np.float64) if flavour == 'weighted' else None
     Xin = X if store == 'fp16' else X.astype(F[store])          # (float16: rounded at upload, so rri_storage_error is not zero)
+    scales = None
+    if store == 'u8':
+        X, r, s, W0, T0 = count_problem(n, d, k)
+        Xin, scales = X.astype(np.uint8), (r, s)
+
+    def seen(e):
+        out = (e.get_W(), e.get_T(), e.objective(), e.storage_relerr)
+        return out + ((stored_matrix(e),) + e.X_scales() if scales else ())
     with engine(n, d, k, dtype=F[store], **flavour_kw(flavour)) as e:
         e.upload_X(Xin)
+        if scales:
+            e.set_X_scales(*scales)
         if M is not None:
             e.upload_mask(M)
         e.set_W(W0); e.set_T(T0); e.set_params(reset_topic_method=None, **({'t_row_sum': 1.0} if M is not None else {}))
-        before = e.get_W(), e.get_T(), e.objective(), e.storage_relerr
+        before = seen(e)
         assert (before[3] > 0.0) is (store == 'fp16')
-        other = 2.0 * X + 1.0, 3.0 * W0 + 1.0, 3.0 * T0 + 1.0
+        if scales:
+            assert np.array_equal(before[4], (X * s) * r[:, None]) and np.array_equal(before[5], r) and np.array_equal(before[6], s)
+        other = (X + 1.0 if scales else 2.0 * X + 1.0), 3.0 * W0 + 1.0, 3.0 * T0 + 1.0         # (counts: still counts)
         calls = [('rri_upload_X', other[0].astype(F[store]), d), ('rri_upload_X', other[0], d),
                  ('rri_set_W', other[1], k), ('rri_set_T', other[2], d)]
         if M is not None:
@@ -175,24 +234,38 @@ def test_a_refused_input_changes_nothing(flavour, store):
             a = np.ascontiguousarray(a)
             assert call(e, name, a, cols - 1) == _capi.RRI_ERR_INVALID, name
             assert 'ld=' in e._err()
-            after = e.get_W(), e.get_T(), e.objective(), e.storage_relerr
+            after = seen(e)
             assert_same_state(before, after, name + ' with ld = cols - 1')
+        # no host matrix at all: a NULL pointer with a good ld and a type the call takes (the refusal that shares its branch with ld)
+        nulls = [('rri_upload_X', d, _NP2RRI[np.dtype(F[store])]), ('rri_upload_X', d, _capi.RRI_F64), ('rri_set_W', k, _capi.RRI_F64),
+                 ('rri_set_T', d, _capi.RRI_F64)]
+        if M is not None:
+            nulls.append(('rri_upload_mask', d, _capi.RRI_F64))
+        for name, cols, code in nulls:
+            assert getattr(e._lib, name)(e._h, None, cols, code) == _capi.RRI_ERR_INVALID, (name, code)
+            assert 'bad host matrix' in e._err(), (name, code, e._err())
+            after = seen(e)
+            assert_same_state(before, after, '%s with a NULL host pointer' % name)
         # a host type the call does not take: no such code at all, and halves for anything but the X of a float16 handle
         bad_types = [('rri_upload_X', 99), ('rri_set_W', 99), ('rri_set_T', 99), ('rri_set_W', _capi.RRI_F16)]
         if store != 'fp16':
             bad_types.append(('rri_upload_X', _capi.RRI_F16))
+        if store == 'u8':
+            bad_types += [('rri_set_W', _capi.RRI_U8), ('rri_set_T', _capi.RRI_U8)]     # bytes are a host type of its X alone
         if M is not None:
             bad_types += [('rri_upload_mask', 99), ('rri_upload_mask', _capi.RRI_F16)]
         room = np.ones((max(n, k), max(d, k)))                  # large enough for any of them, whatever the type is read as
         for name, code in bad_types:
             assert getattr(e._lib, name)(e._h, room.ctypes.data, room.shape[1], code) == _capi.RRI_ERR_INVALID, (name, code)
             assert 'host dtype' in e._err(), (name, code, e._err())
-            after = e.get_W(), e.get_T(), e.objective(), e.storage_relerr
+            after = seen(e)
             assert_same_state(before, after, '%s with host type %d' % (name, code))
         e.sweep(1)
         swept = e.get_W(), e.get_T()
     with engine(n, d, k, dtype=F[store], **flavour_kw(flavour)) as e:
         e.upload_X(Xin)
+        if scales:
+            e.set_X_scales(*scales)
         if M is not None:
             e.upload_mask(M)
         e.set_W(W0); e.set_T(T0); e.set_params(reset_topic_method=None, **({'t_row_sum': 1.0} if M is not None else {}))
@@ -200,12 +273,17 @@ def test_a_refused_input_changes_nothing(flavour, store):
         assert_same_state((e.get_W(), e.get_T()), swept, 'a sweep after the refused calls')
 
 
-@pytest.mark.parametrize('store', ['fp32', 'fp64', 'fp16'])
+@pytest.mark.parametrize('store', ['fp32', 'fp64', 'fp16', 'u8'])
 def test_a_column_slice_given_to_the_engine_equals_its_copy(store):
-    """through RRIEngine: a column-sliced numpy view (Xw[:, 3:3 + d], strides (ld, 1)) given to upload_X / set_T / set_W"""
+    """through RRIEngine: a column-sliced numpy view (Xw[:, 3:3 + d], strides (ld, 1)) given to upload_X / set_T / set_W
+    (uint8 counts: the columns beside the slice hold 0xFF; scales are set on both handles after the upload)"""
     n, d, k = SHAPES['n203xd141xk5']
     X, W0, T0 = problem(n, d, k)
-    wide = lambda a: np.pad(a, ((0, 0), (3, 4)), constant_values=np.nan)[:, 3:3 + a.shape[1]]
+    wide = lambda a: np.pad(a, ((0, 0), (3, 4)), constant_values=0xFF if a.dtype == np.uint8 else np.nan)[:, 3:3 + a.shape[1]]
+    scales = None
+    if store == 'u8':
+        X, r, s, W0, T0 = count_problem(n, d, k)
+        scales = (r, s)
     Xs = X.astype(F[store])
     out = []
     for view in (False, True):
@@ -213,5 +291,7 @@ def test_a_column_slice_given_to_the_engine_equals_its_copy(store):
             args = [wide(a) if view else np.ascontiguousarray(a) for a in (Xs, W0, T0)]
             assert args[0].flags['C_CONTIGUOUS'] is not view
             e.upload_X(args[0]); e.set_W(args[1]); e.set_T(args[2]); e.set_params(reset_topic_method=None)
-            out.append(state(e))
+            if scales:
+                e.set_X_scales(*scales)
+            out.append([stored_matrix(e)] + state(e))
     assert_same_state(out[0], out[1], 'a column-sliced view')

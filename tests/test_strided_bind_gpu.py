@@ -15,6 +15,11 @@ handle B is bound to the guarded slice on the device; both get the same W0, T0 a
       it had before the bind: bound memory is never written.
 
 The weighted cases bind X and the mask from two allocations with DIFFERENT strides, so a swapped ldx / ldm shows.
+
+uint8 counts (RRI_U8) join every test the float16 cases join.  Their band is the byte 0xFF (tests/ld_cases.py says what that sees
+and what it cannot), so for them (a) says nothing and (c) carries the check: a 255 in a sum is far outside every bound.  Both twins
+get log-uniform row and column scales AFTER the upload / the bind, which puts both vectors back to ones, and the reference is the
+oracle on (C * s) * r[:, None].  One test is theirs alone: rri_scale_X on bound memory, which writes the scale vectors only.
 """
 import contextlib
 import threading
@@ -35,6 +40,7 @@ FLAGS = {'plain': dict(), 'topic': TOPIC}
 SWEEP_TOL = 2e-9                    # test_hip_parity.py: same algorithm, another summation order
 STORED_FP32_TOL = 5e-3              # test_fuzz_gpu.py: a maintained fp32 residual is rounded at every update
 DENSE = ('fp32', 'fp64')            # the storage types of everything that is not the read-only Gram form
+READ_ONLY = ('fp16', 'u8')          # the stores that never take the persistent launch
 
 
 def engine(*a, **kw):
@@ -58,9 +64,10 @@ class Twins(object):
 
 
 @contextlib.contextmanager
-def twins(case, k=K, kind='plain', X=None, M=None, bind_only=False):
-    """A: uploaded, B: bound to the guarded slice(s).  X / M: host matrices (default: the case's own X, no mask).  On exit both
-    handles are closed, the device is synchronised and every guarded allocation is compared with what it was (d)."""
+def twins(case, k=K, kind='plain', X=None, M=None, bind_only=False, scales=None):
+    """A: uploaded, B: bound to the guarded slice(s).  X / M: host matrices (default: the case's own X, no mask).  uint8: both
+    get scales (default: the case's own) once X is there, and X64 is the scaled matrix.  On exit both handles are closed, the
+    device is synchronised and every guarded allocation is compared with what it was (d)."""
     import torch
     c = lc.CASES[case]
     X = lc.case_matrix(c) if X is None else np.ascontiguousarray(np.asarray(X).astype(c.dtype))
@@ -71,6 +78,10 @@ def twins(case, k=K, kind='plain', X=None, M=None, bind_only=False):
         kw['weighted'] = True
     t = Twins()
     t.case, t.X, t.X64 = c, X, np.ascontiguousarray(X.astype(np.float64))
+    t.scales = None
+    if c.store == 'u8':
+        t.scales = lc.case_scales(c) if scales is None else scales
+        t.X64 = lc.scaled(X, *t.scales)
     t.gx = lc.guarded(torch, X, c.ld, c.c0, device='cuda:0')
     t.gm = None
     if M is not None:
@@ -89,6 +100,10 @@ def twins(case, k=K, kind='plain', X=None, M=None, bind_only=False):
         t.B.bind_X_device(t.gx.ptr, t.gx.ld)
         if M is not None:
             t.B.bind_mask_device(t.gm.ptr, t.gm.ld)
+        if t.scales is not None:
+            for e in (t.A, t.B):
+                if e is not None:
+                    e.set_X_scales(*t.scales)
         assert lc.G >= t.B.layout_info()['rpb'], 'the guard rows must cover a row block of the pass: %r' % (t.B.layout_info(),)
         yield t
     finally:
@@ -157,14 +172,14 @@ def check_sweeps(t, W0, T0, sweeps, flags, tol, what, same_bits=True, M=None):
 
 # ---- RRI_UNWEIGHTED: sweeps -------------------------------------------------------------------------------------------------
 SWEEP_PARAMS = [(name, flags, route) for name in lc.CASES for flags in FLAGS
-                for route in (('phases',) if lc.CASES[name].store == 'fp16' else ('phases', 'default'))]
+                for route in (('phases',) if lc.CASES[name].store in READ_ONLY else ('phases', 'default'))]
 
 
 @pytest.mark.parametrize('case,flags,route', SWEEP_PARAMS, ids=['%s-%s-%s' % p for p in SWEEP_PARAMS])
 def test_two_sweeps(monkeypatch, case, flags, route):
     """route 'phases': RRI_ONCHIP=0, the launch-per-phase schedule (k_pass with ldx, non-temporal or plain); 'default': the
-    persistent launch wherever the shape is eligible (its loader takes a.ldx).  A float16 handle never takes that launch, so it
-    has the one route."""
+    persistent launch wherever the shape is eligible (its loader takes a.ldx).  A float16 or uint8 handle never takes that
+    launch, so it has the one route."""
     c = lc.CASES[case]
     if route == 'phases':
         monkeypatch.setenv('RRI_ONCHIP', '0')
@@ -276,8 +291,16 @@ def test_max_resid_row_and_reset_row(case, k):
     c = lc.CASES[case]
     X = lc.case_matrix(c).astype(np.float64)
     star = c.n - 1
-    X[star] += 2.0 * X.max()
-    with twins(case, k=k, X=X) as t:
+    scales = None
+    if c.store == 'u8':         # counts end at 255: the other rows a quarter of theirs, and the largest row scale twice over
+        X = np.floor(X / 4.0)
+        X[star] = 255.0
+        r, s = lc.case_scales(c)
+        r[star] = 2.0 * r.max()
+        scales = (r, s)
+    else:
+        X[star] += 2.0 * X.max()
+    with twins(case, k=k, X=X, scales=scales) as t:
         W0, T0 = start(c, t.X64, k)
         R = t.X64 - W0 @ T0
         pos = (np.maximum(R, 0.0) ** 2).sum(axis=1)
@@ -363,6 +386,51 @@ def test_column_positive_counts_and_scale_X_refused(case):
         assert np.array_equal(t.B.column_positive_counts(), b)
 
 
+@pytest.mark.parametrize('case', [n for n in STEP_CASES if lc.CASES[n].store == 'u8'])
+def test_counts_are_rescaled_on_bound_memory(case):
+    """What only a uint8 handle allows on bound memory: rri_scale_X and the preprocessing on top of it write the two scale
+    vectors, no matrix.  column_positive_counts(), scale_X(col, False), scale_X(None, True) and preprocess(tfidf, normalize)
+    succeed on the bound slice, each leaves every byte of the allocation as it was and the stored matrix equal to the uploaded
+    twin's bit for bit, and the end is matrixops.normalize(matrixops.tfidf(C)) to 1e-14 (tests/test_count_storage_gpu.py)."""
+    import torch
+    from rri_nmf_amd.matrixops import tfidf, normalize
+    c = lc.CASES[case]
+    C = lc.case_matrix(c)
+    C[np.random.RandomState(3).rand(c.n, c.d) < 0.33] = 0
+    C[c.n - 1] = 1                                  # the last row, whose lower neighbour is the band, is in every count
+    C[:, 5] = 0
+    ones = (np.ones(c.n), np.ones(c.d))
+    with twins(case, X=C, scales=ones) as t:
+        stored = lambda e: e.X_times(np.eye(c.d))
+
+        def settled(what):
+            torch.cuda.synchronize()
+            t.gx.check('the allocation X was bound in, after ' + what)
+            a, b = both(t, stored)
+            assert_same_bits(a, b, 'the stored matrix after ' + what)
+            assert_same_bits(t.A.X_scales(), t.B.X_scales(), 'the scale vectors after ' + what)
+            return b
+        a, b = both(t, lambda e: e.column_positive_counts())
+        assert_same_bits(a, b, 'column_positive_counts')
+        assert np.array_equal(b, (C > 0).sum(axis=0).astype(np.float64))
+        assert np.array_equal(settled('column_positive_counts'), C)
+        col = 0.5 + np.random.RandomState(4).rand(c.d)
+        both(t, lambda e: e.scale_X(col, False))
+        assert np.array_equal(settled('scale_X(col, False)'), C * col)
+        both(t, lambda e: e.scale_X(None, True))
+        got = settled('scale_X(None, True)')
+        assert relfro(got, normalize(C * col)) < 1e-14, relfro(got, normalize(C * col))
+        for e in (t.A, t.B):
+            e.set_X_scales(*ones)
+        ia, ib = both(t, lambda e: e.preprocess(tfidf=True, normalize=True))
+        Xt, idf = tfidf(C.astype(np.float64), return_idf=True)
+        assert np.array_equal(ia, ib) and np.array_equal(ib, np.asarray(idf, dtype=np.float64).ravel())
+        got = settled('preprocess(tfidf=True, normalize=True)')
+        err = relfro(got, normalize(Xt))
+        print('%s: preprocess on the bound slice against matrixops: relfro %.3e' % (case, err))
+        assert err < 1e-14, err
+
+
 @pytest.mark.parametrize('case', [n for n in STEP_CASES if lc.CASES[n].store in DENSE and lc.CASES[n].c0])
 def test_bench_kernels_stay_inside_the_slice(case):
     """rri_bench_stream_copy and rri_bench_rank1_update copy X into a scratch buffer: from the first element of the slice to the
@@ -379,7 +447,8 @@ def test_bench_kernels_stay_inside_the_slice(case):
         assert_finite((t.B.get_W(), t.B.get_T()), 'a sweep after the bench calls')
 
 
-STREAM_CASES = ['fp32-n203xd140-ld400-c4', 'fp64-n203xd142-ld272-c2', 'fp16-n203xd136-ld656-c8', 'fp32-n70xd1028-ld1032-c0']
+STREAM_CASES = ['fp32-n203xd140-ld400-c4', 'fp64-n203xd142-ld272-c2', 'fp16-n203xd136-ld656-c8', 'fp32-n70xd1028-ld1032-c0',
+                'u8-n203xd136-ld656-c8']
 
 
 @pytest.mark.parametrize('case', STREAM_CASES)
@@ -681,12 +750,15 @@ def test_two_ranks_bound_to_row_blocks_of_one_allocation(name):
 @pytest.mark.parametrize('kind,pair', [('plain', ('fp32-n203xd140-ld144-c0', 'fp32-n203xd140-ld400-c4')),
                                       ('plain', ('fp64-n203xd142-ld272-c2', 'fp64-n203xd142-ld144-c0')),
                                       ('plain', ('fp16-n203xd136-ld144-c0', 'fp16-n203xd136-ld656-c8')),
-                                      ('residual', ('fp32-n203xd140-ld400-c4', 'fp32-n203xd140-ld144-c0'))],
-                         ids=['fp32', 'fp64', 'fp16', 'residual-fp32'])
+                                      ('residual', ('fp32-n203xd140-ld400-c4', 'fp32-n203xd140-ld144-c0')),
+                                      ('plain', ('u8-n203xd136-ld144-c0', 'u8-n203xd136-ld656-c8'))],
+                         ids=['fp32', 'fp64', 'fp16', 'residual-fp32', 'u8'])
 def test_rebinding_leaves_no_stale_stride(monkeypatch, kind, pair):
     """bind slice 1, sweep, bind slice 2 -- another matrix in another allocation with another ld --, sweep: the same bits as a
     fresh handle bound to slice 2 that took the same steps on the launch-per-phase schedule (changed(c, CH_X) drops whatever
-    was derived from the first X or its stride)"""
+    was derived from the first X or its stride).  uint8: each bind is followed by its own scales; the second bind must have put
+    the first ones back to ones before.
+    """
     import torch
     monkeypatch.setenv('RRI_ONCHIP', '0')
     c1, c2 = lc.CASES[pair[0]], lc.CASES[pair[1]]
@@ -696,6 +768,10 @@ def test_rebinding_leaves_no_stale_stride(monkeypatch, kind, pair):
     g2 = lc.guarded(torch, X2, c2.ld, c2.c0, device='cuda:0')
     torch.cuda.synchronize()
     X64 = X2.astype(np.float64)
+    u8 = c2.store == 'u8'
+    if u8:
+        sc1, sc2 = lc.case_scales(c1, seed=1), lc.case_scales(c2, seed=2)
+        X64 = lc.scaled(X2, *sc2)
     W0, T0 = start(c2, X64, K)
     kw = dict(dtype=c2.dtype, **(dict(schedule='residual') if kind == 'residual' else {}))
 
@@ -703,6 +779,9 @@ def test_rebinding_leaves_no_stale_stride(monkeypatch, kind, pair):
         """what both handles do once slice 2 is bound"""
         e.bind_X_device(g2.ptr, g2.ld)
         assert lc.G >= e.layout_info()['rpb'], 'the guard rows must cover a row block of the pass: %r' % (e.layout_info(),)
+        if u8:
+            assert np.array_equal(e.X_scales()[0], np.ones(c2.n)) and np.array_equal(e.X_scales()[1], np.ones(c2.d))
+            e.set_X_scales(*sc2)
         e.set_W(W0); e.set_T(T0)
         e.sweep(1)
         out = [e.get_W(), e.get_T(), e.objective()]
@@ -712,6 +791,8 @@ def test_rebinding_leaves_no_stale_stride(monkeypatch, kind, pair):
     with engine(c1.n, c1.d, K, **kw) as e:
         e.bind_X_device(g1.ptr, g1.ld)
         assert lc.G >= e.layout_info()['rpb']
+        if u8:
+            e.set_X_scales(*sc1)
         e.set_W(W0); e.set_T(T0); e.set_params(reset_topic_method=None)
         e.sweep(1)
         e.objective()
