@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "rri_hip.h"
+#include "rri_layout.hpp"
 #include "rri_pick.hpp"
 #include "rri_kernels.hpp"
 #include "rri_wrri_kernels.hpp"
@@ -118,33 +119,7 @@ struct rri_comm {
     bool aborted = false;                      // a rank left a collective sequence half way: the communicator is unusable
 };
 
-// What of the 256 MiB Infinity Cache the default-policy traffic of one topic step may fill, in MB (1e6 bytes): the chain's own
-// working set and, in what is left, a fixed part of X (pass_keep).  Chosen on sweeps/s by tools/pass_keep_probe.py.
-constexpr double PASS_CACHE_MB = 256.0;
-// the most rows a workgroup of the read-only pass walks on a dense fp32 handle of the Gram form: the size that streams the packed copy of X (rri_create)
-constexpr int PK_ROWS_MAX = 512;
-
-// The environment switches a handle keeps: read once, by rri_create (read_switches), so that a handle created later under
-// another environment cannot change the schedule of one that is already running (INTEGRATION.md lists them)
-struct rri_switches {
-    bool onchip = true;        // RRI_ONCHIP=0: never the register-resident persistent sweep (rri_onchip_kernels.hpp)
-    bool onchip_obj = true;    // RRI_ONCHIP_OBJ=0: the persistent sweep does not leave the objective of its last sweep (rri_objective takes the Gram kernels)
-    bool wsweep = true;        // RRI_WSWEEP=0: runs with T fixed take the launch-per-topic W half (k_tgram, k_wcol, k_check_wcol per topic)
-    bool obj_direct = false;   // RRI_OBJ_DIRECT=1: the objective always through the residual (k_resid)
-    bool wmcorr_cols = true;   // RRI_WMCORR_COLS=0: the mask-only correction always walks every bit (k_wmcorr), also on a sparse mask
-    bool wnw_mask = true;      // RRI_WNW_MASK=0: the one-pass step keeps taking nw = (w^2)^T M in the read-modify-write pass on a sparse 0/1 mask too
-    int pass_rot = -1;         // RRI_PASS_ROT=0..7: rotate the tiles of the passes inside every group of 8 workgroups (another XCD per tile) by this
-                               // much; unset: the handle's own calibrated 0 or 1 (calibrate_rot)
-    int rot_cal = 1;           // RRI_ROT_CAL=0: no calibration, rotation 0; 1: rotations {0, 1}; n > 1: rotations 0 .. n-1
-    bool rot_debug = false;    // RRI_ROT_DEBUG (set): calibrate_rot prints its timings
-    bool mask_bits = true;     // RRI_MASK_BITS=0: a 0/1 mask stays an fp array (no bit-packed copy)
-    double pass_cache_mb = PASS_CACHE_MB;   // RRI_PASS_CACHE_MB: what of the Infinity Cache a topic step may fill (pass_keep); 0: all of X streams
-    int pk_rows = 0;           // RRI_PASS_PK_GEOM=<rows>[i|c] (diagnostics): rows per workgroup of the read-only pass (rounded up to 16, at most the
-    int pk_il = -1;            // LDS cap) and interleaved (i) or contiguous (c) chunks, for dense fp32 handles of the Gram form (rri_create)
-    int x_pack = -1;           // RRI_X_PACK: the packed 28-bit copy of an fp32 X for the read-only pass (xpack_ensure): 0 never, 1 wherever the
-                               // pass can read it, unset: where X does not fit the budget of pass_keep
-};
-
+// (the environment switches a handle keeps, rri_switches, and every rule of its geometry: rri_layout.hpp)
 struct rri_ctx {
     i64 n = 0, d = 0, LD = 0;
     int k = 0, dtype = RRI_F32, weighted = 0, device = 0;
@@ -154,6 +129,7 @@ struct rri_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     rri_switches sw;
+    DensePlan plan;   // what dense_plan (rri_layout.hpp) decided at rri_create; the geometry members below are copies of its fields
 
     void *X = nullptr, *M = nullptr, *E = nullptr;
     i64 ldx = 0, ldm = 0;
@@ -311,9 +287,7 @@ struct rri_ctx {
 
     std::string err;
 };
-// read-only passes deal their row blocks as interleaved chunks only while the launch has few workgroups (the passes that write
-// the matrix back always do): ONE predicate for the launch sites and for rri_layout_info
-static inline bool ro_pass_interleaved(const rri_ctx* c) { return c->ro_il >= 0 ? c->ro_il != 0 : c->npanels * c->nrb <= 1024; }
+static inline bool ro_pass_interleaved(const rri_ctx* c) { return rri::ro_pass_interleaved(c->ro_il, c->npanels, c->nrb); }
 
 // ---- what a handle keeps between steps and calls, and what each piece was computed from ------------------------------------
 //                                              X   M   W   T   scratch  penalties
@@ -398,7 +372,6 @@ rri_status fail(rri_ctx* c, rri_status code, const char* fmt, ...) {
 #define CHECK_CTX(c) \
     if (!(c)) return RRI_ERR_INVALID
 
-i64 round_up(i64 a, i64 b) { return (a + b - 1) / b * b; }
 
 // ---- who owns device memory ("Who owns device memory") ------------------------------------------------------------
 // temporary device buffer that is released on every return path
@@ -618,7 +591,11 @@ struct TimedScope {
 };
 
 // element sizes of the storage types (0: not a storage type)
-size_t dtype_size(int dt) { return dt == RRI_F32 ? 4 : dt == RRI_F64 ? 8 : dt == RRI_F16 ? 2 : dt == RRI_U8 ? 1 : 0; }
+// the loads the kernels are written for are the loads the plan counts columns in
+static_assert(load_elems(RRI_F32) == XVec<float>::N, "fp32: elements per load");
+static_assert(load_elems(RRI_F64) == XVec<double>::N, "float64: elements per load");
+static_assert(load_elems(RRI_F16) == XVec<_Float16>::N, "float16: elements per load");
+static_assert(load_elems(RRI_U8) == XVec<unsigned char>::N, "uint8: elements per load");
 // the two stores of a dense X that is only ever read (RRI_UNWEIGHTED, Gram form): float16, and uint8 counts with scales
 bool ro_store(int dt) { return dt == RRI_F16 || dt == RRI_U8; }
 const char* dtype_name(int dt) { return dt == RRI_F32 ? "RRI_F32" : dt == RRI_F64 ? "RRI_F64" : dt == RRI_F16 ? "RRI_F16" : dt == RRI_U8 ? "RRI_U8" : "?"; }
@@ -763,7 +740,7 @@ struct LaunchX {
         });
     }
     // c = M^T (wn .* dw) as row-block partials in Cpart (k_wmcorr): the correction of the column sums a one-pass topic step
-    // leaves behind.  Geometry: ~4 workgroups per CU, row blocks of a multiple of 64 rows, at most 4096 (32 KiB of LDS).
+    // leaves behind.  Geometry: wmcorr_grid / wmcorr_cols_grid (rri_layout.hpp).
     // the column-major copy of the packed mask, on first use (one-off: a kernel, a count, one synchronisation)
     static bool mask_cols(rri_ctx* c) {
         if (!c->Mbits || !c->sw.wmcorr_cols) return false;
@@ -793,13 +770,11 @@ struct LaunchX {
         TimedScope ts(c, 2);
         if (mask_cols(c)) {     // a sparse 0/1 mask: the set bits only
             const bool nw = nw_from_mask(c);
-            const int npg = (int)((c->LD + 255) / 256);
-            // 16 workgroups per CU (4: 60 us, 8: 48, 16: 46, 32: 44 at BASELINE config 5)
-            i64 nrb = std::min<i64>(256, std::max<i64>(1, (16 * (i64)std::max(c->n_cu, 1) + npg - 1) / npg));
-            i64 rpb = std::min<i64>(2048, round_up((c->n + nrb - 1) / nrb, 32));
-            nrb = (c->n + rpb - 1) / rpb;            // <= cpart_rows (256, or n / 2048 where that is more: rri_create)
-            c->wcorr_nrb = (int)nrb;
-            const dim3 grid((unsigned)(npg * nrb));
+            const WmcorrGrid g = wmcorr_cols_grid(c->n, c->LD, c->n_cu);
+            const int npg = g.npg;
+            const i64 rpb = g.rpb;
+            c->wcorr_nrb = g.wcorr_nrb;
+            const dim3 grid((unsigned)(npg * g.nrb));
             const size_t sh = (size_t)rpb * sizeof(double) * ((dw && nw) ? 2 : 1);
             pick_bool(dw != nullptr, [&](auto has_dw) {
                 pick_bool(nw, [&](auto has_nw) {
@@ -813,11 +788,10 @@ struct LaunchX {
         }
         if (!dw) return;
         const bool bits = c->Mbits != nullptr;
-        const int npg = bits ? (int)((c->ldb + 255) / 256) : c->npanels;
-        i64 nrb = std::min<i64>(256, std::max<i64>(1, (4 * (i64)std::max(c->n_cu, 1) + npg - 1) / npg));
-        i64 rpb = std::min<i64>(4096, round_up((c->n + nrb - 1) / nrb, 64));
-        nrb = (c->n + rpb - 1) / rpb;
-        c->wcorr_nrb = (int)std::min<i64>(nrb, c->cpart_rows);     // (cpart_rows covers every n: see rri_create)
+        const WmcorrGrid g = wmcorr_grid(c->n, bits, c->ldb, c->npanels, c->n_cu, c->cpart_rows);
+        const int npg = g.npg;
+        const i64 nrb = g.nrb, rpb = g.rpb;
+        c->wcorr_nrb = g.wcorr_nrb;
         const int ncols = (int)std::min<i64>(bits ? c->ldb * 4 : c->ldm, c->LD);
         if (bits)      // (a packed mask: rows whose factor is zero are skipped)
             hipLaunchKernelGGL((k_wmcorr<SX, true, true>), dim3((unsigned)(npg * nrb)), dim3(256), (size_t)rpb * sizeof(double), c->stream,
@@ -876,10 +850,9 @@ struct LaunchX {
         hipLaunchKernelGGL((k_spx_pass<SX>), dim3(items), dim3(1024), spx_lds_bytes(bwmax), c->stream, a,
                            (const DevState*)c->st);
     }
-    // k_spx_rowtot (totals) or k_spx_scale on the canonical CSR: one group of 8 lanes per row, a whole wave from 64 entries per
-    // row on -- the summation order of a row is fixed by the shape
+    // k_spx_rowtot (totals) or k_spx_scale on the canonical CSR, a group of spx_scale_lps lanes per row
     static void spx_scale(rri_ctx* c, const double* sdev, double* tot, unsigned long long* nzero, bool totals) {
-        pick_int<64, 8>(c->nnz / std::max<i64>(c->n, 1) >= 64 ? 64 : 8, [&](auto LPS) {
+        pick_int<64, 8>(spx_scale_lps(c->nnz, c->n), [&](auto LPS) {
             const unsigned nb = (unsigned)((c->n + 256 / LPS - 1) / (256 / LPS));
             if (totals)
                 hipLaunchKernelGGL((k_spx_rowtot<SX, LPS>), dim3(nb), dim3(256), 0, c->stream, (const i64*)c->sp_rowptr,
@@ -1007,7 +980,7 @@ struct LaunchX {
         };
         const unsigned nb = (unsigned)((c->n + 63) / 64);
         if (c->k <= 64) {   // the k-panel product on the matrix cores
-            const int ks = c->k <= 16 ? 4 : c->k <= 32 ? 8 : c->k <= 48 ? 12 : c->k <= 52 ? 13 : 16;
+            const int ks = resid_ks(c->k);
             const size_t shm = 2 * (size_t)(4 * ks) * RESID_TS * sizeof(double);
             const bool sums = rowobj || rowpos;      // a plain rebuild wants neither: its epilogue is convert, subtract, store
             flavour([&](auto mk, auto we) {
@@ -1018,17 +991,9 @@ struct LaunchX {
                         constexpr bool SM = sm;
                         // SM = false exists only for WRITE_E = true: no WRITE_E = false caller can reach it, so it is not built
                         if constexpr (SM || WE) {
-                            unsigned ny = 1u;
-                            int dchunk = (int)round_up(c->d, 64);
-                            if constexpr (!SM) {
-                                // column ranges per row block: ~12 rounds of the chip's 2 workgroups per CU or more, so that the
-                                // last, partly filled round costs a twelfth and not a quarter
-                                const i64 per_round = 2 * (i64)std::max(c->n_cu, 1);
-                                const int nsplit = (int)std::min<i64>((c->d + 63) / 64, std::max<i64>(1, (12 * per_round + nb - 1) / nb));
-                                dchunk = (int)round_up((c->d + nsplit - 1) / nsplit, 64);
-                                ny = (unsigned)((c->d + dchunk - 1) / dchunk);
-                            }
-                            hipLaunchKernelGGL((k_resid_mfma<SX, MK, WE, KS, 4, SM>), dim3(nb, ny), dim3(256), shm, c->stream,
+                            const ResidGrid g = resid_grid(c->n, c->d, c->n_cu, SM);      // without the row sums: column ranges per row block
+                            const int dchunk = g.dchunk;
+                            hipLaunchKernelGGL((k_resid_mfma<SX, MK, WE, KS, 4, SM>), dim3(g.nb, g.ny), dim3(256), shm, c->stream,
                                                (const SX*)c->X, c->ldx, M, ldm, Mbits, ldb, (const double*)c->W, c->ldw,
                                                (const double*)c->T, c->LD, (int)c->n, (int)c->d, c->k, rowobj, rowpos, E, c->LD, dchunk, xscale(c));
                         }
@@ -1152,9 +1117,7 @@ struct LK {  // float64-only kernels
         trow_final_if_needed(c, t, sweep, force_final);
     }
     // launch-bound sizes: k_reduce and k_trow_numer as one launch (every workgroup reduces the Gram partials itself)
-    static bool small(const rri_ctx* c) {
-        return (double)gpart_rows(c) * (c->k + 2) * c->ntb32 <= 4.0e6;
-    }
+    static bool small(const rri_ctx* c) { return rri::trow_small(gpart_rows(c), c->k, c->ntb32); }
     static void trow_small(rri_ctx* c, int t, int check_prev, int tprev, int sweep, bool force_final) {
         hipLaunchKernelGGL(k_trow_small, dim3(c->ntb32), dim3(1024), 0, c->stream, c->T, c->LD, (int)c->d, c->k, t,
                            (const double*)c->Zpart, c->nrb, (const double*)c->Gpart, gpart_rows(c), c->red, c->LD, c->xraw,
@@ -1565,7 +1528,7 @@ void w_reduce(rri_ctx* c, bool take_check = false, int sweep = 0, int pos = 0) {
 
 // few row blocks of partial column sums, one device: the column verdict, both reductions and the closed form of the T row are
 // ONE launch (k_wtrow_small)
-bool wtrow_small(const rri_ctx* c) { return !c->comm && c->nrb <= 64; }
+bool wtrow_small(const rri_ctx* c) { return rri::wtrow_small(c->comm != nullptr, c->nrb); }
 
 // column sums (a, nw) of topic t over the current E into red[0 .. 2 LD)
 // `fused`: the caller goes straight on to enqueue_wT_solve(..., fused) -- rri_sweep does; the split stepping of
@@ -1848,7 +1811,8 @@ bool enqueue_wsweep(rri_ctx* c, int sweep, int t0) {
 // before anything is encoded), then the encoder, which sets the flag byte of every tile that holds an element outside the
 // window.  The host reads the flags once: with more than 1/8 of the tiles flagged the copy is released and the handle runs
 // as it did before.  An allocation that fails means no copy, and no error.
-int pass_keep(const rri_ctx* c);
+// how the read-only pass loads X (rri_ctx::keep_q): the rule and its reasons are pass_keep of rri_layout.hpp
+int pass_keep(const rri_ctx* c) { return rri::pass_keep(c->plan, c->k, c->ldw, c->es, c->xp_valid, c->sw.pass_cache_mb); }
 void xpack_release(rri_ctx* c) {
     dev_release(c, c->xp); dev_release(c, c->xp_flags); dev_release(c, c->xp_hmax);
     c->xp_valid = false;
@@ -1866,7 +1830,7 @@ void xpack_ensure(rri_ctx* c) {
     c->keep_q = pass_keep(c);
     const bool reads_x = c->dtype == RRI_F32 && !c->weighted && !c->explicit_resid && !c->sparse && c->have_X;
     if (!reads_x || c->sw.x_pack == 0 || (c->sw.x_pack < 0 && c->keep_q < 0)) { xpack_release(c); return; }
-    const i64 nitems = (c->n + xpack::ROWS - 1) / xpack::ROWS * c->npanels;
+    const i64 nitems = xpack_tiles(c->n, c->npanels, xpack::ROWS);
     if (dev_ensure(c, c->xp, (size_t)nitems * 4 * xpack::RECORD_BYTES) != hipSuccess || dev_ensure(c, c->xp_flags, (size_t)nitems) != hipSuccess ||
         dev_ensure(c, c->xp_hmax, sizeof(unsigned)) != hipSuccess) { xpack_release(c); return; }
     const int ncols = (int)std::min<i64>(c->ldx, c->LD);     // what the fp32 row loop reads (pass_k)
@@ -1883,7 +1847,7 @@ void xpack_ensure(rri_ctx* c) {
         hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); xpack_release(c); return; }
     i64 flagged = 0;
     for (unsigned char f : flags) flagged += f != 0;
-    if (flagged * 8 > nitems) { xpack_release(c); c->xp_flagged = flagged; c->xp_tiles = nitems; return; }
+    if (xpack_too_many_flagged(flagged, nitems)) { xpack_release(c); c->xp_flagged = flagged; c->xp_tiles = nitems; return; }
     c->xp_base = (int)xpack::base_of(hmax);
     c->xp_flagged = flagged;
     c->xp_tiles = nitems;
@@ -1940,36 +1904,9 @@ void enqueue_range(rri_ctx* c, Cursor cur, int s_end) {
 }
 
 // ---- register-resident persistent sweeps (rri_onchip_kernels.hpp) ---------------------------------------------
-struct OnchipGeom { int CG, RG, rows_wg, rpw, NA, kS, G; size_t shmem; };
-constexpr int ONCHIP_UNTIL_CAP = 512;   // sweeps per launch of rri_sweep_until (a slot row of 256 shares each)
-constexpr int ONCHIP_MAX_RPW = 20;    // rows per wave held in registers (float4 each): 32 spills at 256 VGPRs
-// beyond ONCHIP_SMALL_K topics the k-term dots keep 8 terms per lane and the registers take fewer resident rows WITHOUT a spill
-// (round 4, compiler's resource report: plain 18 rows / 253 VGPRs, with the projection 14 rows / 249; 20 rows spilled 10 / 16 -- and
-// 68 in round 3's build: the allocation moves with every edit, the report of `python -m rri_nmf_amd.build --report` is the record)
-constexpr int ONCHIP_MAX_RPW_K64 = 18, ONCHIP_MAX_RPW_K64_PROJ = 14;
-// The rows per wave an instantiation of k_onchip_sweeps holds (its RPW): every (storage type, PROJ, KT) is built twice, for
-// `few` rows (8) and for the most the registers take, so that a small problem does not carry the large build's registers
-constexpr int onchip_rpw(bool f32, bool proj, int kt, bool few) {
-    const int rows = few ? 8 : kt == 8 ? (proj ? ONCHIP_MAX_RPW_K64_PROJ : ONCHIP_MAX_RPW_K64) : ONCHIP_MAX_RPW;
-    return f32 ? rows : rows / 2;       // float64 X: 8 registers per row and lane
-}
-int onchip_rpw_cap(const rri_ctx* c, bool proj) { return onchip_rpw(c->dtype == RRI_F32, proj, c->k > ONCHIP_SMALL_K ? 8 : 3, false); }
+// (OnchipGeom, onchip_rpw and the limits of the geometry: rri_layout.hpp)
 bool onchip_geometry(const rri_ctx* c, OnchipGeom* g) {
-    const bool proj = !LK::light(c);                   // the projection stage stages the whole T row per worker: d <= 1024
-    if (c->LD > (proj ? 1024 : 2048) || c->n_cu < 1) return false;
-    g->G = std::min(c->n_cu, 256);                     // the workers take 16 partials per lane group: G <= 16 ONCHIP_PG
-    g->CG = c->LD <= 256 ? 1 : c->LD <= 512 ? 2 : c->LD <= 1024 ? 4 : 8;
-    g->RG = ONCHIP_WAVES / g->CG;
-    g->rows_wg = (int)((c->n + g->G - 1) / g->G);
-    g->rpw = (g->rows_wg + g->RG - 1) / g->RG;
-    g->NA = (int)((c->LD + ONCHIP_CWA - 1) / ONCHIP_CWA);      // workgroups that also own a column slice of T
-    g->kS = c->k | 1;                                  // odd row stride of the LDS copy of W: no bank conflicts down a column
-    if (g->rpw > onchip_rpw_cap(c, proj) || g->NA > 64 || g->NA > g->G || (i64)g->rows_wg * g->kS > 6144) return false;
-    const size_t doubles = (size_t)g->rows_wg * g->kS + (size_t)c->k * ONCHIP_CWA + (c->k + 2) + (c->k + 1) +
-                           (size_t)ONCHIP_PG * ONCHIP_CWA + (size_t)g->CG * g->rows_wg + 2 * (size_t)g->rows_wg +
-                           (size_t)ONCHIP_WAVES * 256 + (size_t)ONCHIP_WAVES * 8 * 72 + 1024 + 40;
-    g->shmem = doubles * sizeof(double);
-    return g->shmem <= 150 * 1024;
+    return rri::onchip_geometry(c->n, c->LD, c->k, c->dtype == RRI_F32, !LK::light(c), c->n_cu, g);
 }
 // A persistent launch that gave up means the device is shared with somebody whose grids collide with ours: every handle of the
 // process keeps off the persistent path until this time (steady clock, ns), so that a process that makes a handle per nmf()
@@ -1984,9 +1921,9 @@ bool onchip_ok(const rri_ctx* c) {
     // process must not cost a long-lived handle the launch-bound speed-up for good); eligibility therefore depends on the clock
     if (c->onchip_off && steady_now_ns() < c->onchip_off_until) return false;
     if (ro_store(c->dtype)) return false;       // the persistent kernel has register layouts for 4- and 8-byte X only
-    return c->sw.onchip && steady_now_ns() >= g_onchip_backoff_until.load() && !c->weighted && !c->explicit_resid && !c->comm && !c->sparse && c->k >= 2 &&
-           c->k <= ONCHIP_MAX_K && !c->prm.fix_W && !c->prm.fix_T && c->ldx % c->VN == 0 && ((uintptr_t)c->X) % 16 == 0 &&
-           onchip_geometry(c, &g);
+    return c->sw.onchip && steady_now_ns() >= g_onchip_backoff_until.load() && !c->weighted && !c->explicit_resid && !c->comm && !c->sparse &&
+           !c->prm.fix_W && !c->prm.fix_T && c->ldx % c->VN == 0 && ((uintptr_t)c->X) % 16 == 0 &&
+           onchip_shape_ok(c->n, c->LD, c->k, c->dtype == RRI_F32, !LK::light(c), c->n_cu, &g);
 }
 // Two persistent grids on one device (two handles on two streams) must not each hold a part of the CUs while waiting for
 // the rest: inside a process EVERY persistent launch -- whatever its instantiation -- waits for the one before it on the same
@@ -2213,24 +2150,6 @@ rri_status clear_halt(rri_ctx* c) {
     return RRI_OK;
 }
 
-// How the read-only pass over a dense X loads it (rri_ctx::keep_q).  Between two passes the other kernels of a topic step load
-// and store, with default policy, W (read by k_wcol), the column-sum and row-dot partials (written by the pass, read by
-// k_reduce / k_wcol), T (read and written) and the Gram partials: a line of X survives in the Infinity Cache from one pass to
-// the next only while it and all of that fit (MI355X: about 256 MiB).  What the chain leaves of the capacity C is the budget of
-// X: an X inside it is read with default-policy loads throughout (-1); of a larger one, as many whole row blocks as fit, the
-// same ones in every pass, and the rest non-temporally, which neither allocates there nor evicts (k_pass).  C = 0 streams all.
-int pass_keep(const rri_ctx* c) {
-    const double chain = 8.0 * ((double)c->k * (double)c->ldw + 2.0 * (double)c->nrb * (double)c->LD +
-                                2.0 * (double)c->npanels * (double)c->n + 2.0 * (double)c->k * (double)c->LD +
-                                2.0 * (double)c->nwb * (double)(c->k + 2));
-    const double budget = c->sw.pass_cache_mb * 1.0e6 - chain;
-    // bytes per element and columns of what the pass reads: X, or its packed copy (whole 1024-column groups of 3.5 bytes)
-    const double eb = c->xp_valid ? 3.5 : (double)c->es, cols = c->xp_valid ? (double)c->npanels * 1024.0 : (double)c->LD;
-    const double block = (double)c->rpb * cols * eb;
-    if ((double)c->n * cols * eb <= budget) return -1;
-    return budget > 0.0 ? (int)std::min((double)c->nrb, std::floor(budget / block)) : 0;
-}
-
 // The only place that reads the switches a handle keeps: an unset variable means the default, whatever the handles
 // created before this one were created under
 rri_switches read_switches() {
@@ -2301,37 +2220,24 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     if (weighted < 0 || weighted > 4)
         return fail(nullptr, RRI_ERR_INVALID, "weighted must be RRI_UNWEIGHTED, RRI_WEIGHTED_DENSE, RRI_WEIGHTED_SPARSE, "
                                               "RRI_UNWEIGHTED_RESIDUAL or RRI_UNWEIGHTED_SPARSE");
-    if (dtype == RRI_U8 && weighted != RRI_UNWEIGHTED) {
-        // counts are no store for a residual (signed, fractional), and a CSR store has no uint8 layout
+    if (ro_store(dtype) && weighted != RRI_UNWEIGHTED) {
+        // Both are stores for a dense X that is only ever read.  Counts are no store for a residual (signed, fractional); float16
+        // would round the explicit residual and the dense weighted residual, which are rewritten at every topic step (k S
+        // roundings to 11 bits over S sweeps); CSR values are a store of their own with its own layout, which has neither
+        static const struct { int dtype; const char *stores, *rewritten, *csr; } refusal[] = {
+            {RRI_U8, "RRI_U8 stores read-only dense counts (RRI_UNWEIGHTED)", "keeps a stored residual, which counts 0..255 cannot hold",
+             "keeps its values in a CSR store, which has no uint8 layout"},
+            {RRI_F16, "RRI_F16 stores a read-only dense X (RRI_UNWEIGHTED)",
+             "rewrites its stored residual at every topic step, which float16 would round every time",
+             "keeps its values in a CSR store, which has no float16 layout"}};
         static const char* const flavour[] = {"", "RRI_WEIGHTED_DENSE", "RRI_WEIGHTED_SPARSE", "RRI_UNWEIGHTED_RESIDUAL", "RRI_UNWEIGHTED_SPARSE"};
         const bool rewritten = weighted == RRI_WEIGHTED_DENSE || weighted == RRI_UNWEIGHTED_RESIDUAL;
-        return fail(nullptr, RRI_ERR_UNSUPPORTED, "RRI_U8 stores read-only dense counts (RRI_UNWEIGHTED); %s %s", flavour[weighted],
-                    rewritten ? "keeps a stored residual, which counts 0..255 cannot hold"
-                              : "keeps its values in a CSR store, which has no uint8 layout");
-    }
-    if (dtype == RRI_F16 && weighted != RRI_UNWEIGHTED) {
-        // float16 is a store for an X that is only ever read.  The explicit residual and the dense weighted residual are rewritten
-        // at every topic step (k S roundings to 11 bits over S sweeps); CSR values are a store of their own with its own layout
-        static const char* const flavour[] = {"", "RRI_WEIGHTED_DENSE", "RRI_WEIGHTED_SPARSE", "RRI_UNWEIGHTED_RESIDUAL", "RRI_UNWEIGHTED_SPARSE"};
-        const bool rewritten = weighted == RRI_WEIGHTED_DENSE || weighted == RRI_UNWEIGHTED_RESIDUAL;
-        return fail(nullptr, RRI_ERR_UNSUPPORTED, "RRI_F16 stores a read-only dense X (RRI_UNWEIGHTED); %s %s", flavour[weighted],
-                    rewritten ? "rewrites its stored residual at every topic step, which float16 would round every time"
-                              : "keeps its values in a CSR store, which has no float16 layout");
+        for (const auto& r : refusal)
+            if (r.dtype == dtype)
+                return fail(nullptr, RRI_ERR_UNSUPPORTED, "%s; %s %s", r.stores, flavour[weighted], rewritten ? r.rewritten : r.csr);
     }
     rri_ctx* c = new rri_ctx();
-    const bool explicit_resid = weighted == RRI_UNWEIGHTED_RESIDUAL;
-    const bool sparse_x = weighted == RRI_UNWEIGHTED_SPARSE;
-    if (explicit_resid || sparse_x) weighted = RRI_UNWEIGHTED;   // the same flavour of the algorithm: another schedule / storage
-    c->explicit_resid = explicit_resid;
-    c->sparse_x = sparse_x;
-    c->n = n; c->d = d; c->k = k; c->dtype = dtype; c->weighted = weighted; c->device = device;
-    c->sparse = weighted == RRI_WEIGHTED_SPARSE || sparse_x;
-    c->kp = (int)round_up(k, 8);
-    c->es = dtype_size(dtype);
-    c->VN = dtype == RRI_U8 ? XVec<unsigned char>::N : (int)(16 / c->es);   // elements per load: 4, 2, 8 (float16); uint8: 8 per 8-byte load
-    c->sw = read_switches();
-    c->PW = 64 * c->VN * 4;   // columns per workgroup: 4 waves x (64 lanes x one load)
-    c->LD = round_up(d, c->VN);
+    c->device = device;
 #define CR(call)                                                                                   \
     do {                                                                                           \
         hipError_t e_ = (call);                                                                    \
@@ -2346,98 +2252,39 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     if (stream) c->stream = (hipStream_t)stream;
     else { CR(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
 
-    // geometry of the streaming pass
-    c->npanels = (int)((c->LD + c->PW - 1) / c->PW);
-    // Workgroups: a multiple of 512 (2 per CU: with 525 on 256 CUs some CUs get three and the pass waits for them),
-    // as many as possible up to 2048 while each still walks ~192 rows or more -- with 49 rows each (20000 x 5000 at
-    // 2048 workgroups) ramp-up and tail cost 13 % of the pass (profiles/r01_pass_workgroups_mid_size.log).
-    // LDS per workgroup = (5 rows-doubles plain | 11 weighted) * rpb + 4 row-sum tiles (18 KiB): kept under 40 KiB so
-    // that 4 workgroups (16 waves) fit a CU's 160 KiB -- with 62 KiB the weighted passes ran at 2 workgroups per CU
-    // and 20 % slower.  (The explicit update kernel takes a sixth array and may run at 3 per CU.)
-    const i64 rpb_cap = ((40 * 1024 - 4 * 8 * 72 * 8) / ((weighted ? 11 : explicit_resid ? 7 : 5) * 8)) / 16 * 16;
-    i64 rpb = 0;
-    {
-        // handles whose passes write a residual back (explicit-residual, dense weighted): the read-modify-write pass
-        // likes ~8192 workgroups of >= 96 rows (+3 % at C3 for the residual schedule, +6 % for the weighted one)
-        // (round 4) the one-pass weighted step: ~16384 workgroups of >= 48 rows -- 1.40 against 1.50 - 1.55 ms per pass at BASELINE
-        // config 5, engines made alternately in one process; 24576: the same, 32768: 1.44; the partial column sums grow with the
-        // row blocks, +17 us per launch of the T-row chain (profiles/r04_wpass_one_variants.log)
-        const bool rmw = explicit_resid || weighted == RRI_WEIGHTED_DENSE;
-        // (round 4, late) the read-only pass: at most 1024 -- which at BASELINE config 3 means the LDS cap below decides, 560 rows per
-        // workgroup and 1790 workgroups instead of 496 rows and 2020: 0.647-0.653 against 0.662-0.664 ms in four processes of five,
-        // equal in the fifth (N-way in one process, tools/env_ab.py; the row count is a stride between concurrent streams and
-        // the pass is sensitive to it: 544 rows, between the two, 0.695 ms -- profiles/r04_pass_rows_per_workgroup.log)
-        const int total_max = weighted == RRI_WEIGHTED_DENSE ? 16384 : rmw ? 8192 : 1024;
-        const i64 rows_min = weighted == RRI_WEIGHTED_DENSE ? 48 : rmw ? 96 : 192;
-        for (int total = total_max; total >= 512 && rpb == 0; total -= 512) {
-            const int nrb_t = std::max(1, total / c->npanels);
-            const i64 r = (n + nrb_t - 1) / nrb_t;
-            if (r >= rows_min || total == 512) rpb = r;
-        }
+    // the plan (rri_layout.hpp: every rule and its reasons), copied into the members the launch sites read
+    c->sw = read_switches();
+    const DensePlan p = c->plan = dense_plan(n, d, k, dtype, weighted, c->sw, c->n_cu);
+    const bool explicit_resid = p.explicit_resid;
+    weighted = p.weighted;   // the explicit-residual and the CSR-X handle are the unweighted flavour of the algorithm
+    c->explicit_resid = p.explicit_resid; c->sparse_x = p.sparse_x; c->sparse = p.sparse;
+    c->n = n; c->d = d; c->k = k; c->dtype = dtype; c->weighted = weighted;
+    c->kp = p.kp; c->es = dtype_size(dtype); c->VN = p.VN; c->PW = p.PW; c->LD = p.LD;
+    c->npanels = p.npanels; c->rpb = p.rpb; c->nrb = p.nrb; c->ro_il = p.ro_il;
+    for (int w = 0; w < 2 && p.sparse; ++w) {
+        rri_ctx::SpCopy& cp = c->sp[w];
+        cp.gdim = p.sp[w].gdim; cp.nseg = p.sp[w].nseg; cp.nblk = p.sp[w].nblk; cp.bw = p.sp[w].bw;
     }
-    rpb = std::max<i64>(rpb, 32);
-    rpb = std::min<i64>(round_up(rpb, 16), rpb_cap);
-    // A dense fp32 handle of the Gram form walks at most PK_ROWS_MAX rows per workgroup: more than that it only ever got from the
-    // LDS cap (560), which takes 1024 workgroups of 1024 columns -- an X of 2 GB and more, which streams the packed copy
-    // (xpack_ensure).  The 560 were tuned on the fp32 stream (above), and in the copy that stride is 7/8 of it.  Known at ONE
-    // shape only, BASELINE config 3, and jagged there -- engines made alternately in one process, three visits each: 560 rows
-    // 0.5758 ms per pass (0.5684 .. 0.5760), 528 0.5640, 512 0.5516 (0.5491 .. 0.5520), 496 0.5541, 480 0.5637, 448 0.5648, 400
-    // 0.5500; 560 interleaved 0.5790 (profiles/r13_xpack_refill_steps.log, tools/pk_geom_probe.py; DESIGN 4.5 has the second
-    // process, the fp32 stream at 512 rows and another shape).  The rule looks at n, d, storage and flavour only, not at
-    // RRI_X_PACK or RRI_PASS_CACHE_MB: tests/test_xpack_gpu.py and tests/test_pass_keep_gpu.py compare W, T and the objective bit
-    // for bit across those switches at 60007 x 10004, where the cap decides, so a handle must have the same geometry -- the same
-    // order of its partial sums -- with the copy and without it; it keeps it when the copy is released.  RRI_PASS_PK_GEOM
-    // (diagnostics) sets other rows and the chunk order for such handles.
-    if (dtype == RRI_F32 && !weighted && !explicit_resid && !c->sparse) {
-        rpb = c->sw.pk_rows > 0 ? std::min<i64>(round_up(std::max(c->sw.pk_rows, 16), 16), rpb_cap) : std::min<i64>(rpb, PK_ROWS_MAX);
-        if (c->sw.pk_rows > 0) c->ro_il = c->sw.pk_il;
-    }
-    c->rpb = (int)rpb;
-    c->nrb = (int)((n + rpb - 1) / rpb);
-    if (c->sparse) {
-        // no dense pass: the row copy is cut into column blocks (= Ypart panels), the column copy into row blocks
-        // (= Zpart rows); block widths so that three factor tables of a block fit SP_BLOCK_BYTES of LDS
-        const i64 block_bytes = SP_BLOCK_BYTES;
-        // (X on CSR: ONE table of float64 factors per block, spx_block_cap -- k_spx_pass)
-        const i64 cap = sparse_x ? std::min<i64>(spx_block_cap(), std::max<i64>(64, (block_bytes / 8 - 64) / 64 * 64))
-                                 : block_bytes / (3 * (i64)c->es);
-        for (int w = 0; w < 2; ++w) {
-            rri_ctx::SpCopy& cp = c->sp[w];
-            cp.gdim = w == 0 ? d : n;
-            cp.nseg = w == 0 ? n : d;
-            cp.nblk = (int)((cp.gdim + cap - 1) / cap);
-            cp.bw = (int)round_up((cp.gdim + cp.nblk - 1) / cp.nblk, 64);
-        }
-        c->npanels = c->sp[0].nblk;
-        c->nrb = c->sp[1].nblk;
-    }
-    c->nwb = (int)((n + 64 * WCOL_TILES - 1) / (64 * WCOL_TILES));   // k_wcol blocks = rows of Gpart
-    c->nwb256 = (int)((n + 255) / 256);
+    c->nwb = p.nwb; c->nwb256 = p.nwb256; c->ntb = p.ntb; c->ntb32 = p.ntb32; c->nsplit = p.nsplit;
+    c->red_elems = p.red_elems; c->xy_stride = p.xy_stride; c->cpart_rows = p.cpart_rows;
     c->ldw = n;
     c->keep_q = pass_keep(c);
-    c->ntb = (int)((d + 127) / 128);
-    c->ntb32 = (int)((c->LD + 31) / 32);
     c->tpart_n = c->ntb;
-    c->nsplit = (int)std::max<i64>(1, std::min<i64>(8, d / 2048));
-    c->red_elems = round_up(std::max<i64>(c->LD + (i64)GRAM_SLICES * (k + 2), weighted ? 2 * c->LD + 2 : 0), 4);
+    c->gpart_n = c->nwb;
+    c->ttpart_n = c->nsplit;
 
     const size_t f8 = sizeof(double);
     CR(dev_alloc(c, c->W, (size_t)k * c->ldw * f8));
     CR(dev_alloc(c, c->T, (size_t)k * c->LD * f8, true));
     CR(dev_alloc(c, c->Ypart, (size_t)c->npanels * n * f8, true));
     CR(dev_alloc(c, c->Zpart, (size_t)c->nrb * c->LD * f8, true));
-    const size_t grows = (size_t)std::max(c->nwb, c->nrb);      // k_wcol leaves a row per 64-row tile, the fused pass one per row block
-    c->gpart_n = c->nwb;
-    c->xy_stride = (int)std::max<size_t>(std::max<size_t>(grows, (size_t)c->nwb * WCOL_TILES), (size_t)std::max(c->n_cu, 1));   // the on-chip sweep leaves one per CU
-    CR(dev_alloc(c, c->Gpart, grows * (k + 2) * f8, true));
+    CR(dev_alloc(c, c->Gpart, (size_t)p.gpart_rows * (k + 2) * f8, true));
     CR(dev_alloc(c, c->XYpart, (size_t)k * c->xy_stride * f8, true));
     CR(dev_alloc(c, c->red, (size_t)c->red_elems * f8, true));
     CR(dev_alloc(c, c->xraw, (size_t)c->LD * f8, true));
-    const size_t ttn = (size_t)std::max(c->nsplit, c->ntb32);   // k_tgram: nsplit column slices; k_trow_small: one per 32 columns
-    c->ttpart_n = c->nsplit;
-    CR(dev_alloc(c, c->Ttpart, ttn * k * f8, true));
+    CR(dev_alloc(c, c->Ttpart, (size_t)p.ttpart_rows * k * f8, true));
     CR(dev_alloc(c, c->Qt, (size_t)k * c->ldw * f8));
-    const size_t ntp = (size_t)std::max(c->ntb, c->ntb32);
+    const size_t ntp = (size_t)p.tpart_rows;
     CR(dev_alloc(c, c->tpart, ntp * f8, true));
     CR(dev_alloc(c, c->tpart_idx, ntp * sizeof(i64)));
     CR(dev_alloc(c, c->normpart, 256 * 3 * f8));
@@ -2454,7 +2301,6 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
         CR(dev_alloc(c, c->Y2part, (size_t)c->npanels * n * f8, true));
         CR(dev_alloc(c, c->Z2part, (size_t)c->nrb * c->LD * f8, true));
         if (!c->sparse) {
-            c->cpart_rows = (int)std::max<i64>(256, (n + 2047) / 2048);
             CR(dev_alloc(c, c->Cpart, (size_t)c->cpart_rows * c->LD * f8, true));
             CR(dev_alloc(c, c->N2part, (size_t)c->cpart_rows * c->LD * f8, true));
         }
@@ -2542,14 +2388,9 @@ struct CsrDev {   // device copies of the host CSR arrays of one call
     const int* ix() const { return (const int*)indices.p; }
 };
 rri_status csr_to_device(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data, int64_t nnz,
-                         int32_t data_dtype, CsrDev& out) {
-    if (!indptr || (nnz > 0 && (!indices || !data)) || nnz < 0) return fail(c, RRI_ERR_INVALID, "bad CSR arrays");
-    if (data_dtype != RRI_F32 && data_dtype != RRI_F64) return fail(c, RRI_ERR_INVALID, "bad CSR data dtype");
-    if (indptr[0] != 0 || indptr[c->n] != nnz) return fail(c, RRI_ERR_INVALID, "indptr does not span nnz");
-    for (i64 r = 0; r < c->n; ++r)
-        if (indptr[r + 1] < indptr[r]) return fail(c, RRI_ERR_INVALID, "indptr not monotone at row %lld", r);
-    for (i64 p = 0; p < nnz; ++p)
-        if (indices[p] < 0 || indices[p] >= c->d) return fail(c, RRI_ERR_INVALID, "column index out of range at %lld", p);
+                         int32_t data_dtype, CsrDev& out, CsrRules rules = CSR_COLUMNS) {
+    const std::string bad = csr_check(indptr, indices, data, nnz, data_dtype, c->n, c->d, rules);
+    if (!bad.empty()) return fail(c, RRI_ERR_INVALID, "%s", bad.c_str());
     const size_t ds = dtype_size(data_dtype);
     HIPCHK(c, out.indptr.alloc((size_t)(c->n + 1) * sizeof(i64)));
     HIPCHK(c, out.indices.alloc((size_t)std::max<i64>(nnz, 1) * sizeof(int)));
@@ -2601,43 +2442,19 @@ rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indi
 static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data,
                                     int64_t nnz, int32_t data_dtype) {
     if (nnz >= 2147483647LL) return fail(c, RRI_ERR_UNSUPPORTED, "more than 2^31-1 stored entries");
-    if (!indptr || (nnz > 0 && (!indices || !data)) || nnz < 0) return fail(c, RRI_ERR_INVALID, "bad CSR arrays");
-    if (data_dtype != RRI_F32 && data_dtype != RRI_F64) return fail(c, RRI_ERR_INVALID, "bad CSR data dtype");
-    if (indptr[0] != 0 || indptr[c->n] != nnz) return fail(c, RRI_ERR_INVALID, "indptr does not span nnz");
-    for (i64 r = 0; r < c->n; ++r)
-        if (indptr[r + 1] < indptr[r]) return fail(c, RRI_ERR_INVALID, "indptr not monotone at row %lld", r);
+    std::string bad = csr_check(indptr, indices, data, nnz, data_dtype, c->n, c->d, CSR_ROWS);
+    if (!bad.empty()) return fail(c, RRI_ERR_INVALID, "%s", bad.c_str());
     HIPCHK(c, hipSetDevice(c->device));
     // column indices sorted inside every row (a sorted host copy where the caller's are not); duplicates are refused
-    const size_t ds = dtype_size(data_dtype);
     std::vector<int32_t> sidx;
     std::vector<unsigned char> sval;
-    for (i64 r = 0; r < c->n; ++r) {
-        bool sorted = true;
-        for (i64 p = indptr[r] + 1; p < indptr[r + 1] && sorted; ++p) sorted = indices[p] > indices[p - 1];
-        if (sorted) continue;
-        if (sidx.empty()) {
-            sidx.assign(indices, indices + nnz);
-            sval.assign((const unsigned char*)data, (const unsigned char*)data + (size_t)nnz * ds);
-        }
-        std::vector<i64> ord((size_t)(indptr[r + 1] - indptr[r]));
-        for (size_t q = 0; q < ord.size(); ++q) ord[q] = indptr[r] + (i64)q;
-        std::stable_sort(ord.begin(), ord.end(), [&](i64 a, i64 b) { return indices[a] < indices[b]; });
-        for (size_t q = 0; q < ord.size(); ++q) {
-            sidx[(size_t)indptr[r] + q] = indices[ord[q]];
-            std::memcpy(sval.data() + ((size_t)indptr[r] + q) * ds, (const unsigned char*)data + (size_t)ord[q] * ds, ds);
-        }
-    }
-    if (!sidx.empty()) { indices = sidx.data(); data = sval.data(); }
-    for (i64 r = 0; r < c->n; ++r)
-        for (i64 p = indptr[r] + 1; p < indptr[r + 1]; ++p)
-            if (indices[p] == indices[p - 1])
-                return fail(c, RRI_ERR_INVALID, "row %lld stores column %d twice (sum the duplicates first)", r, indices[p]);
+    if (csr_sort_rows(indptr, indices, data, c->n, nnz, dtype_size(data_dtype), sidx, sval)) { indices = sidx.data(); data = sval.data(); }
+    bad = csr_duplicates(indptr, indices, c->n);
+    if (!bad.empty()) return fail(c, RRI_ERR_INVALID, "%s", bad.c_str());
     CsrDev dv;
     rri_status s = csr_to_device(c, indptr, indices, data, nnz, data_dtype, dv);
     if (s != RRI_OK) return s;
-    // one launch runs the items of both copies: half of the chip's CUs each, so that all of them are ONE round of workgroups
-    const int target_items = std::max(1, c->n_cu / 2);
-    s = build_sp_store(c, indptr, indices, nnz, data_dtype, dv, target_items);
+    s = build_sp_store(c, indptr, indices, nnz, data_dtype, dv, sp_target_items(c->n_cu, true));
     if (s != RRI_OK) return s;
     if (nnz > 0)
         DISPATCH(c, for (int w = 0; w < 2; ++w)
@@ -2692,7 +2509,6 @@ namespace {
 rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indices, int64_t nnz, int32_t data_dtype,
                           CsrDev& dv, int target_items) {
     i64 longest_row = 0;
-    for (i64 r = 0; r < c->n; ++r) longest_row = std::max<i64>(longest_row, (i64)(indptr[r + 1] - indptr[r]));
     dev_release(c, c->sp_rowptr); dev_release(c, c->sp_col); dev_release(c, c->sp_x); dev_release(c, c->sp_e);
     dev_adopt(c, c->sp_rowptr, dv.indptr);     // from here on they are the handle's, whatever fails below
     dev_adopt(c, c->sp_col, dv.indices);
@@ -2700,94 +2516,28 @@ rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indi
     if (nnz > 0) {   // values -> storage type (dv.data holds them in the caller's type)
         launch_convert(c, data_dtype, c->dtype, false, dv.data.p, nnz, c->sp_x, nnz, 1, nnz);
     }
-    // the two blocked copies: counting sort on the host, stable, so offsets ascend inside a segment
+    // the two blocked copies, built on the host (build_sp_copy, rri_layout.hpp)
     for (int w = 0; w < 2; ++w) {
         rri_ctx::SpCopy& cp = c->sp[w];
         dev_release(c, cp.segptr); dev_release(c, cp.idx); dev_release(c, cp.val); dev_release(c, cp.perm); dev_release(c, cp.work);
-        const i64 nseg = cp.nseg, stride = nseg + 1;
-        std::vector<i64> sp((size_t)cp.nblk * stride, 0);
-        // count: entry (r, j) lives in block (gather index / bw), segment (the other index)
-        for (i64 r = 0; r < c->n; ++r)
-            for (i64 p = indptr[r]; p < indptr[r + 1]; ++p) {
-                const i64 j = indices[p];
-                const i64 g = w == 0 ? j : r, sgm = w == 0 ? r : j;
-                sp[(size_t)((g / cp.bw) * stride + sgm + 1)] += 1;
-            }
-        i64 run = 0;   // exclusive prefix over (block, segment); every block row keeps nseg + 1 pointers.
-        // Segments are padded to multiples of 4 entries (k_sp_blk moves quads).
-        for (int b = 0; b < cp.nblk; ++b) {
-            i64* row = sp.data() + (size_t)b * stride;
-            row[0] = run;
-            for (i64 q = 1; q <= nseg; ++q) {
-                run += (row[q] + 3) / 4 * 4;
-                row[q] = run;
-            }
-        }
-        cp.count = run;
-        const size_t cntp = (size_t)std::max<i64>(run, 4);
-        std::vector<unsigned short> bidx(cntp, (unsigned short)cp.bw);      // pads: the zero slot of the factor tables
-        std::vector<int> perm(cntp, -1);
-        {
-            std::vector<i64> fill((size_t)cp.nblk * nseg);
-            for (int b = 0; b < cp.nblk; ++b)
-                for (i64 q = 0; q < nseg; ++q) fill[(size_t)b * nseg + q] = sp[(size_t)b * stride + q];
-            for (i64 r = 0; r < c->n; ++r)
-                for (i64 p = indptr[r]; p < indptr[r + 1]; ++p) {
-                    const i64 j = indices[p];
-                    const i64 g = w == 0 ? j : r, sgm = w == 0 ? r : j;
-                    const i64 b = g / cp.bw;
-                    const i64 q = fill[(size_t)(b * nseg + sgm)]++;
-                    bidx[(size_t)q] = (unsigned short)(g - b * cp.bw);
-                    perm[(size_t)q] = (int)p;
-                }
-        }
-        // Work items: runs of segments of one block, at most `target_items` in all and of equal entry count -- ONE round of
-        // workgroups (a 1024-thread workgroup with the block's tables per CU).  Round 2 cut "about 3 x 256" items and got
-        // 774-780: three rounds of the 256 CUs and a fourth for the last few, a quarter of every launch with the chip idle
-        // (profiles/r03_sp_blk_probe.log: 138 -> 115 us per pass).  Every (block, segment) belongs to exactly one item --
-        // also the empty ones, whose sums the consumers still read.
-        std::vector<SpWork> work;
-        {
-            std::vector<i64> eb((size_t)cp.nblk);
-            i64 total = 0;
-            for (int b = 0; b < cp.nblk; ++b) {
-                const i64* row = sp.data() + (size_t)b * stride;
-                eb[(size_t)b] = row[nseg] - row[0];
-                total += eb[(size_t)b];
-            }
-            const i64 spare = std::max<i64>(0, (i64)target_items - cp.nblk);      // every block needs one item; the rest by share
-            for (int b = 0; b < cp.nblk; ++b) {
-                const i64* row = sp.data() + (size_t)b * stride;
-                i64 items_b = 1 + (total > 0 ? spare * eb[(size_t)b] / total : 0);
-                items_b = std::max<i64>(1, std::min<i64>(items_b, eb[(size_t)b] / 4096));      // no items of a few entries
-                i64 s0 = 0;
-                for (i64 j = 1; j <= items_b && s0 < nseg; ++j) {
-                    i64 s1 = nseg;
-                    if (j < items_b) {
-                        const i64 want = row[0] + eb[(size_t)b] * j / items_b;     // first segment boundary at or past the j-th share
-                        s1 = std::lower_bound(row + s0 + 1, row + nseg, want) - row;
-                        s1 = std::min<i64>(std::max<i64>(s1, s0 + 1), nseg);
-                    }
-                    work.push_back(SpWork{b, (int)s0, (int)s1, w});
-                    s0 = s1;
-                }
-                if (s0 < nseg) work.push_back(SpWork{b, (int)s0, (int)nseg, w});
-            }
-        }
-        cp.nwork = (int)work.size();
-        // lanes per segment: 4 quads of 4 entries per lane and iteration
-        const i64 avg = nnz / std::max<i64>(1, (i64)cp.nblk * nseg);
-        cp.lps = avg >= 768 ? 64 : avg >= 384 ? 32 : avg >= 192 ? 16 : 8;
-        HIPCHK(c, dev_alloc(c, cp.segptr, sp.size() * sizeof(i64)));
+        SpDims dims;
+        dims.nblk = cp.nblk; dims.bw = cp.bw; dims.nseg = cp.nseg; dims.gdim = cp.gdim;
+        const SpCopyHost h = build_sp_copy(indptr, indices, c->n, nnz, w, dims, target_items);
+        const size_t cntp = h.idx.size();
+        cp.count = h.count;
+        cp.nwork = (int)h.work.size();
+        cp.lps = h.lps;
+        longest_row = h.longest_row;
+        HIPCHK(c, dev_alloc(c, cp.segptr, h.segptr.size() * sizeof(i64)));
         HIPCHK(c, dev_alloc(c, cp.idx, cntp * sizeof(unsigned short)));
         HIPCHK(c, dev_alloc(c, cp.val, cntp * c->es, true));
         HIPCHK(c, dev_alloc(c, cp.perm, cntp * sizeof(int)));
-        HIPCHK(c, dev_alloc(c, cp.work, std::max<size_t>(1, work.size()) * sizeof(SpWork)));
-        HIPCHK(c, hipMemcpyAsync(cp.segptr, sp.data(), sp.size() * sizeof(i64), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(cp.idx, bidx.data(), cntp * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(cp.perm, perm.data(), cntp * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        if (!work.empty())
-            HIPCHK(c, hipMemcpyAsync(cp.work, work.data(), work.size() * sizeof(SpWork), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, dev_alloc(c, cp.work, std::max<size_t>(1, h.work.size()) * sizeof(SpWork)));
+        HIPCHK(c, hipMemcpyAsync(cp.segptr, h.segptr.data(), h.segptr.size() * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(cp.idx, h.idx.data(), cntp * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(cp.perm, h.perm.data(), cntp * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        if (!h.work.empty())
+            HIPCHK(c, hipMemcpyAsync(cp.work, h.work.data(), h.work.size() * sizeof(SpWork), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));   // the host vectors go out of scope
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2805,14 +2555,9 @@ rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int3
     if (nnz >= 2147483647LL) return fail(c, RRI_ERR_UNSUPPORTED, "more than 2^31-1 observed entries");
     HIPCHK(c, hipSetDevice(c->device));
     CsrDev dv;   // validates the arrays; its device copies of indptr / indices become the CSR copy
-    rri_status s = csr_to_device(c, indptr, indices, values, nnz, data_dtype, dv);
+    rri_status s = csr_to_device(c, indptr, indices, values, nnz, data_dtype, dv, CSR_INCREASING);
     if (s != RRI_OK) return s;
-    for (i64 r = 0; r < c->n; ++r)
-        for (i64 p = indptr[r] + 1; p < indptr[r + 1]; ++p)
-            if (indices[p] <= indices[p - 1])
-                return fail(c, RRI_ERR_INVALID, "column indices of row %lld are not strictly increasing", r);
-    const int target_items = std::max(1, c->n_cu);
-    s = build_sp_store(c, indptr, indices, nnz, data_dtype, dv, target_items);
+    s = build_sp_store(c, indptr, indices, nnz, data_dtype, dv, sp_target_items(c->n_cu, false));
     if (s != RRI_OK) return s;
     HIPCHK(c, dev_alloc(c, c->sp_e, (size_t)std::max<i64>(nnz, 1) * c->es));
     c->have_X = true;
@@ -2832,7 +2577,7 @@ rri_status rri_storage_error(rri_ctx* c, double out[2]) {
 rri_status rri_bind_X_device(rri_ctx* c, const void* dev, int64_t ld) {
     CHECK_CTX(c);
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
-    const i64 vb = (i64)c->VN * (i64)c->es;      // bytes per load: 16 (uint8: 8)
+    const i64 vb = load_bytes(c->dtype);      // 16 (uint8: 8)
     if (!dev || ld < c->d || (ld * (i64)c->es) % vb || ((uintptr_t)dev) % vb)
         return fail(c, RRI_ERR_INVALID, "device X must be %lld-byte aligned with a %lld-byte-multiple row stride >= d", vb, vb);
     if (c->d % c->VN) return fail(c, RRI_ERR_INVALID, "binding device X needs d %% %d == 0 (no pad columns)", c->VN);
@@ -2852,7 +2597,8 @@ rri_status rri_bind_mask_device(rri_ctx* c, const void* dev, int64_t ld) {
     REFUSE_RO(c, "a mask");
     if (c->sparse) return fail(c, RRI_ERR_UNSUPPORTED, "%s", sparse_data_refusal(c));
     if (!c->weighted) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=1");
-    if (!dev || ld < c->d || (ld * (i64)c->es) % 16 || ((uintptr_t)dev) % 16)
+    const i64 vb = load_bytes(c->dtype);      // 16: a mask has the storage type of a weighted handle, fp32 or float64
+    if (!dev || ld < c->d || (ld * (i64)c->es) % vb || ((uintptr_t)dev) % vb)
         return fail(c, RRI_ERR_INVALID, "device mask must be 16-byte aligned with a 16-byte-multiple row stride >= d");
     if (c->d % c->VN) return fail(c, RRI_ERR_INVALID, "binding a device mask needs d %% %d == 0", c->VN);
     HIPCHK(c, hipSetDevice(c->device));
@@ -3691,7 +3437,6 @@ struct TallQR {
     double *part = nullptr, *Gdev = nullptr, *Lp = nullptr;   // gram partials [npart_max][64][64], G (m x m), packed L (64 x 64 + 64)
     std::vector<double> G, L = std::vector<double>((size_t)64 * 64 + 64, 0.0);   // L: the same entries are written for a given m
 };
-int tall_gram_parts(i64 rows) { return (int)std::max<i64>(1, std::min<i64>(512, (rows + TG_ROWS - 1) / TG_ROWS)); }
 
 rri_status cholqr_tall(rri_ctx* c, double* Y, i64 rows, int m, TallQR& q) {
     const int npart = tall_gram_parts(rows);

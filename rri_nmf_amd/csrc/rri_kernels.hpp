@@ -31,6 +31,7 @@
 #include "rri_device.hpp"
 #include "rri_halt.hpp"
 #include "rri_hip.h"
+#include "rri_layout.hpp"
 #include "rri_xpack.hpp"
 
 namespace rri {
@@ -616,8 +617,7 @@ __global__ __launch_bounds__(256) void k_scale2d(SX* __restrict__ X, i64 ldx, i6
 // topic tn (CARRY), one thread per row of W.  Gpart[b][0..k) = sum_i wn_i W[i,:], [k] = sum wn_i^2,
 // [k+1] = sum_i W[i,t] (new).  T T[t]^T arrives as nsplit partial vectors from k_tgram.
 // =========================================================================================
-constexpr int WCOL_TILES = 1;   // 64-row tiles per k_wcol block (1 = most blocks in flight)
-constexpr int GRAM_SLICES = RRI_GRAM_SLICES;  // k_reduce sums the Gpart rows in this many slices; consumers add the slices
+// (WCOL_TILES, the 64-row tiles per k_wcol block, and GRAM_SLICES, the slices k_reduce sums the Gpart rows in: rri_layout.hpp)
 
 template <bool UPDATE, bool CARRY>
 __global__ __launch_bounds__(256) void k_wcol(double* __restrict__ Wt, i64 ldw, int n, int k, int t, int tn,
@@ -1896,8 +1896,7 @@ __global__ __launch_bounds__(256) void k_lsolve_rows(double* __restrict__ A, i64
 // thread (ta, tb) the entries (tb + 16 i, ta + 16 j): in a step all lanes read one row -- 16 consecutive doubles per j across ta
 // (one 128-byte run per half wave, no bank shared) and 4 broadcast addresses per i.  Workgroup w takes the tiles w, w + grid, ...
 // in that order and leaves its sum at part[w][64][64] (entries a <= b < m only; the lower half is never read): no atomics,
-// the same bits on every run for a given grid.
-constexpr int TG_ROWS = 32;
+// the same bits on every run for a given grid.  (TG_ROWS = 32: rri_layout.hpp)
 __global__ __launch_bounds__(256) void k_tall_gram_part(const double* __restrict__ Y, i64 rows, int m, double* __restrict__ part) {
     __shared__ double tile[TG_ROWS * 64];
     const int ta = threadIdx.x & 15, tb = threadIdx.x >> 4;

@@ -44,15 +44,13 @@
 // of a hang.
 #pragma once
 #include "rri_kernels.hpp"
+#include "rri_layout.hpp"
 
 namespace rri {
 
 enum { HALT_ERR_GRID_SYNC = -8 };
-constexpr int ONCHIP_THREADS = 512, ONCHIP_WAVES = ONCHIP_THREADS / 64;
-constexpr int ONCHIP_SMALL_K = 22;    // k + 2 Gram entries = 8 waves x 3 in flight: one round of loads in phase A (KT = 3)
-constexpr int ONCHIP_MAX_K = 64;      // KT = 8: two rounds beyond k = 46
-constexpr int ONCHIP_CWA = 32;          // columns of T per worker
-constexpr int ONCHIP_PG = ONCHIP_THREADS / ONCHIP_CWA;   // groups of workgroup partials in the column-sum reduction
+// ONCHIP_THREADS, ONCHIP_WAVES, ONCHIP_SMALL_K, ONCHIP_MAX_K, ONCHIP_CWA, ONCHIP_PG: rri_layout.hpp (through rri_kernels.hpp), next to
+// the host geometry that is computed from them
 
 struct OnchipArgs {
     const void* X; i64 ldx; int n, d, LD, k;      // X in the handle's storage type (the kernel is instantiated per type)

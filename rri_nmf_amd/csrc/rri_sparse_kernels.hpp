@@ -17,6 +17,7 @@
 // schedule: the sparse formulation moves fewer bytes below ~47 % density (at the 5 % of BASELINE config 5: 9x).
 #pragma once
 #include "rri_kernels.hpp"
+#include "rri_layout.hpp"
 
 namespace rri {
 
@@ -30,11 +31,9 @@ namespace rri {
 //
 // Factors are rounded to the table type TF on BOTH sides (the per-segment scalars too), so the CSR and the CSC
 // copy apply bit-identical corrections; for an fp32 handle that is the rounding the stored residual has anyway.
-constexpr int SP_BLOCK_BYTES = 120 * 1024;
+// (SP_BLOCK_BYTES = 120 KiB, spx_block_cap and the work item SpWork are in rri_layout.hpp, with the host code that cuts the blocks)
 template <typename SX> struct SpTab { typedef float type; };
 template <> struct SpTab<double> { typedef double type; };
-
-struct SpWork { int blk, s0, s1, pad; };   // one workgroup: segments [s0, s1) of block blk
 
 template <int LPS>
 __device__ __forceinline__ double group_sum(double v) {
@@ -187,7 +186,6 @@ __global__ __launch_bounds__(1024) void k_sp_blk(const SpWork* __restrict__ work
 // What k_sp_blk learnt is kept: quads of entries per load, 8 in flight per lane, plain loads, pads into the zero slot of the
 // table (offset bw) rather than a branch per entry, and at most n_cu items in all, cut by entry count (the host's work lists).
 constexpr int SPX_UNR = 8;
-__host__ __device__ constexpr i64 spx_block_cap() { return (i64)(SP_BLOCK_BYTES / 8 - 64) / 64 * 64; }
 __host__ __device__ constexpr size_t spx_lds_bytes(int bw) { return (size_t)(bw + 1) * sizeof(double); }
 
 template <typename SX>

@@ -24,7 +24,8 @@ before, bit for bit.  Their vectors are 8 bytes (VN = 8, a workgroup of the pass
 
 The builder works on numpy arrays (the CPU test) and on torch tensors (the GPU test): guarded(np, ...) / guarded(torch, ...).
 
-Case table, VN = 16 / itemsize (the elements of a 16-byte vector; uint8: the 8 of an 8-byte one; binding needs d % VN == 0):
+Case table, VN = 16 / itemsize (the elements of a 16-byte vector; uint8: the 8 of an 8-byte one; binding needs d % VN == 0 -- load_elems
+and load_bytes of rri_nmf_amd/csrc/rri_layout.hpp, which tests/test_layout_cpu.py holds to vn_of and strides_of below):
     d       one column tile (d < 64) | three column tiles, the last ragged | two column panels of the streaming pass (256 vectors each)
     n       130 and 203 (3 and 4 row blocks of 64, both ragged) for the two small d; 70 for the two-panel d
     ld, c0  (d + VN, 0): the smallest legal pad;  (d + 65 VN, VN): a pad wider than the 64 vectors one wave covers, and a column

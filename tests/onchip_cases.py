@@ -3,10 +3,11 @@ reach: the cases of tests/test_onchip_edges_gpu.py (tests/test_onchip_cases_cpu.
 
 Three things, none of which needs a device:
 
-    geometry(n, d, k, store, proj, n_cu)    a SECOND WORDING of onchip_geometry / onchip_ok / the few-most choice of
-                                            enqueue_onchip (rri_hip.hip), written from DESIGN 4.2 and the comments there -- not
-                                            generated from the C++: the library's eligibility is checked against it on both sides
-                                            of every limit, so when a limit moves, this file moves with it by hand
+    geometry(n, d, k, store, proj, n_cu)    a SECOND WORDING of onchip_geometry / onchip_shape_ok / onchip_rpw (rri_layout.hpp) and
+                                            the few-most choice of enqueue_onchip (rri_hip.hip), written from DESIGN 4.2 and the
+                                            comments there -- not generated from the C++: the library's eligibility (on a device)
+                                            and the header itself (tests/test_layout_cpu.py, no device) are checked against it on
+                                            both sides of every limit, so when a limit moves, this file moves with it by hand
     edge_cases(n_cu)                        (name, n, d, k, store, flags, expect_eligible): one limit moves per case, everything
                                             else stays small; computed from G = min(n_cu, 256), so that on a device that reports
                                             fewer CUs the shapes still sit on the edges
@@ -17,7 +18,7 @@ Three things, none of which needs a device:
 and the yardstick: oracle_run(), the float64 oracle's topic loop (oracle/rri_oracle.py:448-483 -- its own qf_min, residual
 products and reset handlers) on X AS STORED, X.astype(store).astype(float64), with the resets it made and every sum it judged.
 
-The rules restated (rri_hip.hip "register-resident persistent sweeps"; rri_onchip_kernels.hpp constants):
+The rules restated (rri_layout.hpp "register-resident persistent sweeps" and its ONCHIP_* constants):
 
     LD        d rounded up to a 16-byte multiple of the storage type (4 columns of fp32, 2 of float64)
     G         min(n_cu, 256) workgroups of 8 waves

@@ -1,9 +1,9 @@
 """Cases, layout formulas and rounding bounds shared by tests/test_weighted_sparse_buckets_gpu.py (device) and
 tests/test_weighted_sparse_layout_cpu.py (no device).
 
-Layout.  sp_layout / dense_layout restate what rri_create and build_sp_store (rri_hip.hip) decide for a handle; the GPU
-tests compare them with what the handle reports (rri_layout_info), the CPU test runs them over the case lists below and asserts
-that every bucket has a case.
+Layout.  sp_layout / dense_layout restate what dense_plan, sp_dims and build_sp_copy (rri_nmf_amd/csrc/rri_layout.hpp) decide for a
+handle; the GPU tests compare them with what the handle reports (rri_layout_info), the CPU test runs them over the case lists
+below and asserts that every bucket has a case, and tests/test_layout_cpu.py holds the C++ to them over the same lists.
 
 Bounds.  The weighted flavour keeps E = M .* (X - W T) in the storage type and rewrites it by rank-one corrections.  StepBound
 carries, next to the float64 reference, a matrix B >= |E_device - E_true| entry by entry:
