@@ -297,6 +297,31 @@ rri_status rri_get_X_scales(rri_ctx* ctx, double* row_out, double* col_out);
  *                               *zero_rows_out = 0.  zero_rows_out may be NULL only when normalize_rows == 0. */
 rri_status rri_csr_column_positive_counts(rri_ctx* ctx, double* df_out);
 rri_status rri_csr_scale_X(rri_ctx* ctx, const double* col_scale, int32_t normalize_rows, int64_t* zero_rows_out);
+/* Uniform rows of an RRI_UNWEIGHTED_SPARSE handle: the dense rows that normalisation makes of zero-total rows, kept BESIDE the
+ * pattern.  With U a sorted list of rows and c a value, the X every entry point of the handle sees is X = S + c e_U 1^T: S is
+ * the stored CSR with zeros in the rows of U, and row i in U is the dense row c for every column j < d.  Sweeps (both halves
+ * free or fixed), the objective in both forms, the max-residual reset (a uniform row can win it: T[t,:] becomes the dense
+ * max(c - (W T)_i, 0)), rri_X_times / rri_Xt_times and rri_sparse_range_finder all work on that X; each adds the rows' share
+ * in a fixed order, float64, no atomics, so a rerun is bit-identical.  With U empty (the default) nothing is launched for it.
+ * RRI_ERR_INVALID on every other handle and before rri_upload_X_csr; rri_upload_X_csr empties U.
+ *   rri_set_uniform_rows      declares rows[0 .. count) of the resident X as the dense row `value`: their stored values become 0
+ *                             (the pattern is unchanged) and both blocked copies are gathered again.  rows may be unsorted; they
+ *                             are kept sorted.  count == 0 clears the list.  A list the handle already has is REPLACED (its rows
+ *                             stay rows of zeros unless listed again).  RRI_ERR_INVALID, with nothing changed, for a duplicate, a
+ *                             row outside [0, n), a non-finite value.  Everything the handle has cached of X is dropped.
+ *                             The list is replaced after the store has been rewritten: a call that fails on the device keeps
+ *                             the list the handle had.
+ *   rri_get_uniform_rows      *count_out = |U|, *value_out = c (0 while U is empty), rows_out[0 .. |U|) = U when capacity >= |U|.
+ *                             rows_out == NULL asks for the count alone; a capacity that is too small is RRI_ERR_INVALID.
+ *   rri_csr_scale_X_uniform   rri_csr_scale_X, except that rows with tot[i] < 1e-10 do not stop it: they take zeros, every other
+ *                             row the normalised values, and the handle keeps them as its uniform rows with the value 1.0 / d
+ *                             (float64, as matrixops.py:146 writes it).  *uniform_rows_out = |U| (may be NULL).  Without
+ *                             normalize_rows there are no totals and no uniform rows.
+ * On a handle that HAS uniform rows rri_csr_scale_X, rri_csr_scale_X_uniform and rri_csr_column_positive_counts answer
+ * RRI_ERR_INVALID and leave X alone: a second preprocessing of such an X is not built. */
+rri_status rri_set_uniform_rows(rri_ctx* ctx, const int32_t* rows, int64_t count, double value);
+rri_status rri_get_uniform_rows(rri_ctx* ctx, int32_t* rows_out, int64_t capacity, int64_t* count_out, double* value_out);
+rri_status rri_csr_scale_X_uniform(rri_ctx* ctx, const double* col_scale, int32_t normalize_rows, int64_t* uniform_rows_out);
 
 /* ---- row-sharded multi-GPU inside the library (one process per GPU; SURVEY 8b "sharded by row block internally",
  *      8e).  The reference has one call for the whole X (nmf.py:98-108); here every rank creates a handle for its row
@@ -369,7 +394,8 @@ rri_status rri_objective_parts(rri_ctx* ctx, double out[3]);
 /* ---- measurement --------------------------------------------------------------- */
 /* HIP-event timing of the streaming kernels on the handle's stream.  kernel_id:
  * 0 = fused X pass (row dots + column sums), 1 = W-column update, 2 = T-row update chain,
- * 3 = rank-one residual update (explicit-residual / WRRI flavour). */
+ * 3 = rank-one residual update (explicit-residual / WRRI flavour); on an RRI_UNWEIGHTED_SPARSE handle with uniform rows: the
+ *     launch that adds their share after every X pass (also inside the bracket of id 0). */
 /* on = 0: off; on = N > 0: bracket every N-th launch of each kernel id with an event pair (N = 1: all).
  * An event record costs a bubble of a few microseconds on the stream, so sample when the timed region is
  * also the throughput measurement. */

@@ -93,6 +93,9 @@ PROTOTYPES = {
     'rri_get_X_scales': (_I32, [_P, C.POINTER(_D), C.POINTER(_D)]),
     'rri_csr_column_positive_counts': (_I32, [_P, C.POINTER(_D)]),
     'rri_csr_scale_X': (_I32, [_P, C.POINTER(_D), _I32, C.POINTER(_I64)]),
+    'rri_set_uniform_rows': (_I32, [_P, C.POINTER(_I32), _I64, _D]),
+    'rri_get_uniform_rows': (_I32, [_P, C.POINTER(_I32), _I64, C.POINTER(_I64), C.POINTER(_D)]),
+    'rri_csr_scale_X_uniform': (_I32, [_P, C.POINTER(_D), _I32, C.POINTER(_I64)]),
     'rri_comm_unique_id': (_I32, [C.POINTER(C.c_uint8)]),
     'rri_comm_create': (_I32, [C.POINTER(_P), C.POINTER(C.c_uint8), _I32, _I32, _I32]),
     'rri_comm_create_host': (_I32, [C.POINTER(_P), _I32, _I32, ALLREDUCE_FN, ALLGATHER_FN, BROADCAST_FN, _P]),

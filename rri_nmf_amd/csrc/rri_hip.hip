@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <mutex>
@@ -188,6 +189,17 @@ struct rri_ctx {
     bool sparse_x = false;
     SpWork* spx_work = nullptr;
     double* rowhat = nullptr;   // per-row sum of (W T)_ij^2 over the pattern (the objective's fallback)
+    // uniform rows of that handle (rri_set_uniform_rows, rri_csr_scale_X_uniform): X = S + uni_value e_U 1^T, S the stored CSR
+    // with zeros in the rows of U = uni_rows (sorted, device).  uni_n == 0: nothing of this is launched anywhere
+    int* uni_rows = nullptr;
+    i64 uni_n = 0;
+    double uni_value = 0.0;
+    double* uni_part = nullptr;   // [64][64] column sums of an operand panel by row chunks (k_spu_panel_part)
+    // what the next rri_csr_scale_X is asked for besides scaling (consumed there, the one place that rewrites this X):
+    enum { UNI_REQ_NONE = 0, UNI_REQ_COLLECT = 1, UNI_REQ_ZERO = 2 };
+    int uni_req = UNI_REQ_NONE;
+    const int* uni_req_rows = nullptr;   // UNI_REQ_ZERO: the rows that take zeros (device, the caller's), and how many
+    i64 uni_req_n = 0;
     // dense weighted, one read-modify-write pass per topic step: the column sums a pass leaves for the next T row lack the
     // rank-one term of the W update that follows it; k_wmcorr takes that term from the mask alone (Cpart: its partials)
     double* Cpart = nullptr;
@@ -299,6 +311,8 @@ static inline bool ro_pass_interleaved(const rri_ctx* c) { return rri::ro_pass_i
 //   gfull_valid                                            x                        Gfull = T T^T
 //   x_sq_valid                                 x                                    x_sq = ||X||^2
 // (X of an RRI_U8 handle: the counts AND its two scale vectors -- a changed scale is CH_X.)
+// (X of an RRI_UNWEIGHTED_SPARSE handle: the stored CSR AND its uniform rows -- a changed list or value is CH_X; the list itself
+// is no cache: only rri_set_uniform_rows, rri_csr_scale_X_uniform and a new X, rri_upload_X_csr, which empties it, write it.)
 // (scratch: Zpart / Gpart / red, which other entry points borrow.)  resid_fresh, dt_pending and dw_pending qualify E and are
 // read only while resid_valid holds; every rebuild resets them (resid_rebuilt).  pending_wcheck is no cache but a verdict still
 // owed on the column sums in Gpart: it is taken before Gpart is overwritten (flush_wcheck) and dropped only with the run it
@@ -845,18 +859,30 @@ struct LaunchX {
         a.F[0] = trow; a.S[0] = c->Ypart; a.lds[0] = c->n;
         a.F[1] = wc; a.S[1] = c->Zpart; a.lds[1] = c->LD;
         const int items = (DO_Y ? c->sp[0].nwork : 0) + (DO_Z ? c->sp[1].nwork : 0);
+        // (upload_X_csr_kept refuses a copy without a work item: every pass writes its partials, to which the uniform rows' share
+        // below is added)
         if (items < 1) return;
         const int bwmax = std::max(DO_Y ? c->sp[0].bw : 0, DO_Z ? c->sp[1].bw : 0);
         hipLaunchKernelGGL((k_spx_pass<SX>), dim3(items), dim3(1024), spx_lds_bytes(bwmax), c->stream, a,
                            (const DevState*)c->st);
+        if (c->uni_n > 0) {   // the uniform rows' share, into block 0 of the partials the pass has just written
+            TimedScope tu(c, 3);   // (timing id 3 has no other user on this handle; id 0's bracket, in pass(), holds both launches)
+            const int nzb = DO_Z ? (int)((c->d + 1023) / 1024) : 0;
+            hipLaunchKernelGGL((k_spu_pass<DO_Y, DO_Z>), dim3(nzb + (DO_Y ? 1 : 0)), dim3(1024), 0, c->stream,
+                               (const int*)c->uni_rows, (int)c->uni_n, c->uni_value, trow, c->d, wc, c->Ypart, c->Zpart, nzb,
+                               (const DevState*)c->st);
+        }
     }
     // k_spx_rowtot (totals) or k_spx_scale on the canonical CSR, a group of spx_scale_lps lanes per row
-    static void spx_scale(rri_ctx* c, const double* sdev, double* tot, unsigned long long* nzero, bool totals) {
+    static void spx_scale(rri_ctx* c, const double* sdev, double* tot, unsigned long long* nzero, bool totals, bool uni = false) {
         pick_int<64, 8>(spx_scale_lps(c->nnz, c->n), [&](auto LPS) {
             const unsigned nb = (unsigned)((c->n + 256 / LPS - 1) / (256 / LPS));
             if (totals)
                 hipLaunchKernelGGL((k_spx_rowtot<SX, LPS>), dim3(nb), dim3(256), 0, c->stream, (const i64*)c->sp_rowptr,
                                    (const int*)c->sp_col, (const SX*)c->sp_x, c->n, sdev, tot, nzero);
+            else if (uni)     // rows with a total below 1e-10 take zeros (rri_csr_scale_X_uniform)
+                hipLaunchKernelGGL((k_spx_scale<SX, LPS, true>), dim3(nb), dim3(256), 0, c->stream, (const i64*)c->sp_rowptr,
+                                   (const int*)c->sp_col, (SX*)c->sp_x, c->n, sdev, (const double*)tot);
             else
                 hipLaunchKernelGGL((k_spx_scale<SX, LPS>), dim3(nb), dim3(256), 0, c->stream, (const i64*)c->sp_rowptr,
                                    (const int*)c->sp_col, (SX*)c->sp_x, c->n, sdev, (const double*)tot);
@@ -869,6 +895,9 @@ struct LaunchX {
         hipLaunchKernelGGL((k_spx_xtt<SX>), dim3((unsigned)((c->n + 3) / 4)), dim3(256), 0, c->stream,
                            (const i64*)c->sp_rowptr, (const int*)c->sp_col, (const SX*)c->sp_x, c->n,
                            (const double*)c->sp_Tt, m, c->kp, out, c->ldw);
+        if (c->sparse_x && c->uni_n > 0)
+            hipLaunchKernelGGL(k_spu_xtt, dim3(m), dim3(256), 0, c->stream, (const int*)c->uni_rows, (int)c->uni_n, c->uni_value,
+                               Tm, c->LD, c->d, out, c->ldw);
     }
     static void sp_spmm(rri_ctx* c, int which, const double* B, int m, double* part, double* out) {
         const rri_ctx::SpCopy& cp = c->sp[which];
@@ -879,6 +908,23 @@ struct LaunchX {
         const i64 count = cp.nseg * m;
         hipLaunchKernelGGL(k_sp_sum_blocks, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream,
                            (const double*)part, count, cp.nblk, out);
+        spu_spmm(c, which, B, m, out);
+    }
+    // the uniform rows' share of a product: X B gets c (1^T B) in the rows of U, X^T Q gets c (e_U^T Q) in every row j < d
+    static void spu_spmm(rri_ctx* c, int which, const double* B, int m, double* out) {
+        if (!c->sparse_x || c->uni_n < 1) return;
+        const int* U = c->uni_rows;
+        const int nu = (int)c->uni_n;
+        if (which == 0) {
+            const i64 chunk = std::max<i64>(1024, (c->d + 63) / 64);
+            const int nb = (int)((c->d + chunk - 1) / chunk);      // <= 64 rows of uni_part
+            hipLaunchKernelGGL(k_spu_panel_part, dim3(nb), dim3(1024), 0, c->stream, B, c->d, m, chunk, c->uni_part);
+            hipLaunchKernelGGL(k_spu_panel_rows, dim3((unsigned)((nu + 3) / 4)), dim3(256), 0, c->stream, U, nu, c->uni_value,
+                               (const double*)c->uni_part, nb, m, out);
+        } else {
+            hipLaunchKernelGGL(k_spu_panel_all, dim3((unsigned)((c->d + 255) / 256)), dim3(1024), 0, c->stream, U, nu, c->uni_value,
+                               B, m, c->d, out);
+        }
     }
     // the same product between two device panels of the range finder (rri_sparse_range_finder): with one block the sum over the
     // blocks is a copy, and the product is written where it is wanted
@@ -888,6 +934,7 @@ struct LaunchX {
         hipLaunchKernelGGL((k_sp_spmm<SX>), dim3((unsigned)((cp.nseg + 3) / 4)), dim3(256), 0, c->stream,
                            (const i64*)cp.segptr, cp.nseg, 1, (const unsigned short*)cp.idx, (const int*)cp.perm,
                            (const SX*)c->sp_x, cp.bw, B, m, out);
+        spu_spmm(c, which, B, m, out);
     }
     static void sp_resid(rri_ctx* c, bool write_e, double* rowobj, double* rowpos, double* rowhat = nullptr) {
         const i64 total = (i64)c->k * c->d;
@@ -897,6 +944,10 @@ struct LaunchX {
                            c->stream, (const i64*)c->sp_rowptr, (const int*)c->sp_col, (const SX*)c->sp_x, c->n,
                            (const double*)c->W, c->ldw, (const double*)c->sp_Tt, c->k, c->kp,
                            write_e ? (SX*)c->sp_e : (SX*)nullptr, rowobj, rowpos, rowhat);
+        if (c->sparse_x && c->uni_n > 0 && (rowobj || rowpos || rowhat))     // the dense rows of U replace their entries
+            hipLaunchKernelGGL(k_spu_resid, dim3((unsigned)c->uni_n), dim3(256), (size_t)c->k * sizeof(double), c->stream,
+                               (const int*)c->uni_rows, c->uni_value, (const double*)c->W, c->ldw, (const double*)c->T, c->LD, c->d,
+                               c->k, rowobj, rowpos, rowhat);
         if (write_e && c->nnz > 0)
             for (int w = 0; w < 2; ++w)
                 hipLaunchKernelGGL((k_sp_permute<SX>), dim3(2048), dim3(256), 0, c->stream, (const SX*)c->sp_e,
@@ -1017,6 +1068,10 @@ struct LaunchX {
                                    c->stream, (const i64*)c->sp_rowptr, (const int*)c->sp_col, (const SX*)c->sp_x,
                                    (const double*)c->W, c->ldw, (const double*)c->T, c->LD, c->k, (const i64*)c->itmp,
                                    c->xraw);
+                if (c->sparse_x && c->uni_n > 0)     // a uniform row won: its reset row is dense
+                    hipLaunchKernelGGL(k_spu_reset_row, dim3((unsigned)((c->d + 255) / 256)), dim3(256), 0, c->stream,
+                                       (const int*)c->uni_rows, (int)c->uni_n, c->uni_value, (const double*)c->W, c->ldw,
+                                       (const double*)c->T, c->LD, c->d, c->k, (const i64*)c->itmp, c->xraw);
                 return;
             }
         }
@@ -2454,6 +2509,11 @@ static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int
     CsrDev dv;
     rri_status s = csr_to_device(c, indptr, indices, data, nnz, data_dtype, dv);
     if (s != RRI_OK) return s;
+    // from here on the store is being replaced: the uniform rows were rows of the X that goes, and a new X has none -- cleared
+    // first, so that an upload that fails further down leaves no list beside a store it does not describe
+    dev_release(c, c->uni_rows);
+    c->uni_n = 0;
+    c->uni_value = 0.0;
     s = build_sp_store(c, indptr, indices, nnz, data_dtype, dv, sp_target_items(c->n_cu, true));
     if (s != RRI_OK) return s;
     if (nnz > 0)
@@ -2463,6 +2523,9 @@ static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int
                                            (typename L::Elem*)c->sp[w].val));
     dev_release(c, c->spx_work);
     const int nw0 = c->sp[0].nwork, nw1 = c->sp[1].nwork;
+    // every block of a copy has a work item, an empty one included, so every X pass writes all of its partials: the launches that
+    // add to them afterwards (the uniform rows' share) rely on it
+    if (nw0 < 1 || nw1 < 1) return fail(c, RRI_ERR_HIP, "a blocked copy of X has no work item (%d, %d)", nw0, nw1);
     HIPCHK(c, dev_alloc(c, c->spx_work, (size_t)std::max(1, nw0 + nw1) * sizeof(SpWork)));
     if (nw0 > 0) HIPCHK(c, hipMemcpyAsync(c->spx_work, c->sp[0].work, (size_t)nw0 * sizeof(SpWork), hipMemcpyDeviceToDevice, c->stream));
     if (nw1 > 0) HIPCHK(c, hipMemcpyAsync(c->spx_work + nw0, c->sp[1].work, (size_t)nw1 * sizeof(SpWork), hipMemcpyDeviceToDevice, c->stream));
@@ -2953,6 +3016,7 @@ static rri_status ensure_x_sq(rri_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->x_sq = 0.0;
     for (int b = 0; b < 256; ++b) c->x_sq += h[b];
+    if (c->sparse_x && c->uni_n > 0) c->x_sq += (double)c->uni_n * (double)c->d * (c->uni_value * c->uni_value);   // the rows of U
     c->x_sq_valid = true;
     return RRI_OK;
 }
@@ -3659,10 +3723,13 @@ rri_status rri_scale_X(rri_ctx* c, const double* col_scale, int32_t normalize_ro
 }
 
 // ... and of an X kept as CSR (rri_sparse_kernels.hpp: k_spx_poscount, k_spx_rowtot, k_spx_scale)
+static const char* const uni_refusal = "the handle has uniform rows: its X was preprocessed already, and a second preprocessing of "
+                                       "such an X is not built (rri_upload_X_csr starts again)";
 rri_status rri_csr_column_positive_counts(rri_ctx* c, double* df_out) {
     CHECK_CTX(c);
     if (!df_out) return fail(c, RRI_ERR_INVALID, "df_out is NULL");
     if (!c->sparse_x || !c->have_X) return fail(c, RRI_ERR_INVALID, "needs an RRI_UNWEIGHTED_SPARSE handle with an X");
+    if (c->uni_n > 0) return fail(c, RRI_ERR_INVALID, "%s", uni_refusal);
     HIPCHK(c, hipSetDevice(c->device));
     DevTmp out;
     HIPCHK(c, out.alloc((size_t)c->d * sizeof(double)));
@@ -3674,14 +3741,31 @@ rri_status rri_csr_column_positive_counts(rri_ctx* c, double* df_out) {
     return RRI_OK;
 }
 
+// Every rewrite of the resident CSR X ends HERE -- the stored values written, both blocked copies gathered again, the cached
+// state dropped (changed) --, the calls about uniform rows included: they leave their request in c->uni_req and call this function,
+// as rri_set_X_scales ends in rri_scale_X.
+//   UNI_REQ_COLLECT    (rri_csr_scale_X_uniform) rows whose total is below 1e-10 do not stop the call: they take zeros and become
+//                      the handle's uniform rows, value 1 / d
+//   UNI_REQ_ZERO       (rri_set_uniform_rows) the rows uni_req_rows[0 .. uni_req_n) take zeros; nothing is scaled.  The caller
+//                      makes them the handle's list once this has succeeded
+// The handle's list, its length and its value change only after the last step that can fail: a call that fails leaves them alone.
 rri_status rri_csr_scale_X(rri_ctx* c, const double* col_scale, int32_t normalize_rows, int64_t* zero_rows_out) {
     CHECK_CTX(c);
+    const int req = c->uni_req;
+    c->uni_req = rri_ctx::UNI_REQ_NONE;
+    const bool uni = req == rri_ctx::UNI_REQ_COLLECT, zeroing = req == rri_ctx::UNI_REQ_ZERO;
+    const int* zero_rows_list = c->uni_req_rows;
+    const i64 zero_rows_n = zeroing ? c->uni_req_n : 0;
+    c->uni_req_rows = nullptr;
+    c->uni_req_n = 0;
     if (!c->sparse_x || !c->have_X) return fail(c, RRI_ERR_INVALID, "needs an RRI_UNWEIGHTED_SPARSE handle with an X");
+    if (c->uni_n > 0 && !zeroing) return fail(c, RRI_ERR_INVALID, "%s", uni_refusal);
     if (zero_rows_out) *zero_rows_out = 0;
-    if (!col_scale && !normalize_rows) return RRI_OK;
+    if (!col_scale && !normalize_rows && !zeroing) return RRI_OK;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
-    DevTmp sd, tt, nz;
+    DevTmp sd, tt, nz, list, keep;
+    i64 nuni = 0;
     if (col_scale) {
         HIPCHK(c, sd.alloc((size_t)c->d * sizeof(double)));
         HIPCHK(c, hipMemcpyAsync(sd.p, col_scale, (size_t)c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -3694,20 +3778,98 @@ rri_status rri_csr_scale_X(rri_ctx* c, const double* col_scale, int32_t normaliz
         unsigned long long zero_rows = 0;
         HIPCHK(c, hipMemcpyAsync(&zero_rows, nz.p, sizeof(zero_rows), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (zero_rows > 0) {      // normalize would make these rows dense (1/d): nothing has been written, X is what it was
+        if (zero_rows > 0 && !uni) {      // normalize would make these rows dense (1/d): nothing has been written, X is what it was
             if (!zero_rows_out) return fail(c, RRI_ERR_INVALID, "%llu rows sum to less than 1e-10 and zero_rows_out is NULL", zero_rows);
             *zero_rows_out = (int64_t)zero_rows;
             return RRI_OK;
         }
+        if (zero_rows > 0) {              // their list, in row order (k_spu_collect), before anything is written
+            const size_t list_bytes = ((size_t)c->n * sizeof(int) + 7) & ~(size_t)7;      // the count sits behind the list, aligned
+            HIPCHK(c, list.alloc(list_bytes + sizeof(i64)));
+            i64* cnt = (i64*)((char*)list.p + list_bytes);
+            hipLaunchKernelGGL(k_spu_collect, dim3(1), dim3(1024), 0, c->stream, (const double*)tt.p, c->n, (int*)list.p, cnt);
+            HIPCHK(c, hipMemcpyAsync(&nuni, cnt, sizeof(i64), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (nuni != (i64)zero_rows) return fail(c, RRI_ERR_HIP, "uniform rows: %lld listed, %llu counted", (long long)nuni, zero_rows);
+            HIPCHK(c, dev_ensure(c, c->uni_part, (size_t)64 * 64 * sizeof(double)));
+            HIPCHK(c, keep.alloc((size_t)nuni * sizeof(int)));      // (becomes the handle's at the end)
+            HIPCHK(c, hipMemcpyAsync(keep.p, list.p, (size_t)nuni * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+        }
     }
-    DISPATCH(c, L::spx_scale(c, (const double*)sd.p, (double*)tt.p, nullptr, false));
+    if (zeroing) {
+        if (zero_rows_n > 0 && c->nnz > 0)
+            DISPATCH(c, hipLaunchKernelGGL((k_spu_zero_rows<typename L::Elem>), dim3((unsigned)((zero_rows_n + 3) / 4)), dim3(256), 0, c->stream,
+                                           zero_rows_list, (int)zero_rows_n, (const i64*)c->sp_rowptr, (typename L::Elem*)c->sp_x));
+    } else {
+        DISPATCH(c, L::spx_scale(c, (const double*)sd.p, (double*)tt.p, nullptr, false, nuni > 0));
+    }
     if (c->nnz > 0)
         DISPATCH(c, for (int w = 0; w < 2; ++w)
                         hipLaunchKernelGGL((k_sp_permute<typename L::Elem>), dim3(2048), dim3(256), 0, c->stream,
                                            (const typename L::Elem*)c->sp_x, (const int*)c->sp[w].perm, c->sp[w].count,
                                            (typename L::Elem*)c->sp[w].val));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (nuni > 0) {
+        dev_adopt(c, c->uni_rows, keep);
+        c->uni_n = nuni;
+        c->uni_value = 1.0 / (double)c->d;      // as the reference writes it (matrixops.py:146)
+        if (zero_rows_out) *zero_rows_out = (int64_t)nuni;
+    }
     changed(c, CH_X);
+    return RRI_OK;
+}
+
+rri_status rri_csr_scale_X_uniform(rri_ctx* c, const double* col_scale, int32_t normalize_rows, int64_t* uniform_rows_out) {
+    CHECK_CTX(c);
+    c->uni_req = rri_ctx::UNI_REQ_COLLECT;
+    return rri_csr_scale_X(c, col_scale, normalize_rows, uniform_rows_out);
+}
+
+// ---- uniform rows of an RRI_UNWEIGHTED_SPARSE handle: X = S + value e_U 1^T ---------------------------------------------------
+rri_status rri_set_uniform_rows(rri_ctx* c, const int32_t* rows, int64_t count, double value) {
+    CHECK_CTX(c);
+    if (!c->sparse_x) return fail(c, RRI_ERR_INVALID, "uniform rows need an RRI_UNWEIGHTED_SPARSE handle");
+    if (!c->have_X) return fail(c, RRI_ERR_INVALID, "uniform rows are rows of the resident X: call rri_upload_X_csr first");
+    if (count < 0 || count > c->n || (count > 0 && !rows)) return fail(c, RRI_ERR_INVALID, "bad list of uniform rows (0 <= count <= n)");
+    if (!std::isfinite(value)) return fail(c, RRI_ERR_INVALID, "the value of the uniform rows is not finite");
+    std::vector<int32_t> u(rows, rows + count);
+    std::sort(u.begin(), u.end());
+    for (int64_t q = 0; q < count; ++q) {
+        if (u[(size_t)q] < 0 || (i64)u[(size_t)q] >= c->n) return fail(c, RRI_ERR_INVALID, "uniform row %d is out of range (n = %lld)", (int)u[(size_t)q], (long long)c->n);
+        if (q > 0 && u[(size_t)q] == u[(size_t)q - 1]) return fail(c, RRI_ERR_INVALID, "uniform row %d is listed twice", (int)u[(size_t)q]);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (count == 0 && c->uni_n == 0) return RRI_OK;      // nothing to clear: nothing changes, nothing is dropped
+    DevTmp t;
+    if (count > 0) {
+        HIPCHK(c, t.alloc((size_t)count * sizeof(int)));
+        HIPCHK(c, hipMemcpyAsync(t.p, u.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, dev_ensure(c, c->uni_part, (size_t)64 * 64 * sizeof(double)));
+    }
+    // the stored values of these rows become 0 (rows of an earlier list hold zeros already and stay ordinary rows of zeros), the
+    // copies are gathered again and what the handle has cached of X is dropped: where every rewrite of this X ends
+    c->uni_req = rri_ctx::UNI_REQ_ZERO;
+    c->uni_req_rows = (const int*)t.p;
+    c->uni_req_n = count;
+    if (rri_status s = rri_csr_scale_X(c, nullptr, 0, nullptr)) return s;      // (the handle keeps the list it had)
+    if (count > 0) dev_adopt(c, c->uni_rows, t);
+    else dev_release(c, c->uni_rows);
+    c->uni_n = count;
+    c->uni_value = count > 0 ? value : 0.0;
+    return RRI_OK;
+}
+
+rri_status rri_get_uniform_rows(rri_ctx* c, int32_t* rows_out, int64_t capacity, int64_t* count_out, double* value_out) {
+    CHECK_CTX(c);
+    if (!c->sparse_x) return fail(c, RRI_ERR_INVALID, "uniform rows need an RRI_UNWEIGHTED_SPARSE handle");
+    if (count_out) *count_out = (int64_t)c->uni_n;
+    if (value_out) *value_out = c->uni_value;
+    if (!rows_out || c->uni_n == 0) return RRI_OK;      // a query of the count, or nothing to copy
+    if (capacity < c->uni_n) return fail(c, RRI_ERR_INVALID, "rows_out holds %lld entries, the handle has %lld uniform rows", (long long)capacity, (long long)c->uni_n);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(rows_out, c->uni_rows, (size_t)c->uni_n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return RRI_OK;
 }
 

@@ -369,6 +369,7 @@ __global__ __launch_bounds__(256) void k_sp_permute(const SX* __restrict__ e, co
 //                   with tot_i < 1e-10 -- normalize's zero_sum_fix makes those DENSE rows 1/d, which a CSR pattern cannot take, so
 //                   the host launches nothing further when there is one and X stays as it was
 //   k_spx_scale     x_ij <- (1 / tot_i) * (double(x_ij) * s_j), or double(x_ij) * s_j without tot; rounded once, when stored
+//                   (UNI: 0 in the rows with tot_i < 1e-10, which the handle then keeps as uniform rows, below)
 template <typename SX>
 __global__ __launch_bounds__(256) void k_spx_poscount(const i64* __restrict__ segptr, i64 nseg, int nblk,
                                                       const SX* __restrict__ val, double* __restrict__ df) {
@@ -406,7 +407,7 @@ __global__ __launch_bounds__(256) void k_spx_rowtot(const i64* __restrict__ rowp
     }
 }
 
-template <typename SX, int LPS>
+template <typename SX, int LPS, bool UNI = false>
 __global__ __launch_bounds__(256) void k_spx_scale(const i64* __restrict__ rowptr, const int* __restrict__ col,
                                                    SX* __restrict__ xval, i64 n, const double* __restrict__ s,
                                                    const double* __restrict__ tot) {
@@ -415,6 +416,10 @@ __global__ __launch_bounds__(256) void k_spx_scale(const i64* __restrict__ rowpt
     if (i >= n) return;
     const i64 p0 = rowptr[i], p1 = rowptr[i + 1];
     const double r = tot ? 1.0 / tot[i] : 1.0;
+    if (UNI && tot && tot[i] < 1e-10) {                      // a uniform row (rri_csr_scale_X_uniform): stored zeros
+        for (i64 p = p0 + sub; p < p1; p += LPS) xval[p] = SX(0);
+        return;
+    }
     for (i64 p = p0 + sub; p < p1; p += LPS) {
         const double x = (double)xval[p];
         const double t = s ? x * s[col[p]] : x;              // X * idf               (matrixops.py:172)
@@ -480,6 +485,180 @@ __global__ __launch_bounds__(256) void k_sp_reset_row(const i64* __restrict__ ro
     double acc = 0.0;
     for (int l = 0; l < k; ++l) acc = fma(Wt[(i64)l * ldw + mi], T[(i64)l * ldt + j], acc);
     out[j] = fmax((double)xval[p] - acc, 0.0);
+}
+
+
+// ---- uniform rows of an X kept as CSR (rri_set_uniform_rows, rri_csr_scale_X_uniform) -----------------------------------------
+// normalize's zero_sum_fix (matrixops.py:143-147) turns a row whose total is below 1e-10 into the DENSE row 1/d.  The pattern
+// cannot hold it, but such rows are few and all alike: with U their sorted list and c their value, X = S + c e_U 1^T, where S is
+// the stored CSR with zeros in the rows of U.  Every product with X is the product with S (the kernels above, unchanged) plus a
+// term of O(|U| + n + d) work, added by one small launch AFTER the product into what the product left.  Every sum below has a
+// fixed order (thread-strided partial sums, then block_sum or a loop over the partials), float64, no atomics; all sums over
+// columns run over j < d, never over the pad columns.  With U empty none of these kernels is launched.
+
+// the topic step: Ypart[0][i] += c sum_j trow[j] for i in U (the last workgroup), Zpart[0][j] += c sum_{i in U} wc[i] for j < d
+// (workgroups 0 .. nzb-1, each taking the |U| terms itself): block 0 of the partials that k_wcol / k_reduce / k_trow_* add in order
+template <bool DO_Y, bool DO_Z>
+__global__ __launch_bounds__(1024) void k_spu_pass(const int* __restrict__ U, int nu, double cval,
+                                                   const double* __restrict__ trow, i64 d, const double* __restrict__ wc,
+                                                   double* __restrict__ Ypart0, double* __restrict__ Zpart0, int nzb,
+                                                   const DevState* __restrict__ st) {
+    if (st->halt) return;
+    __shared__ double scratch[16];
+    if (DO_Z && (int)blockIdx.x < nzb) {
+        double a = 0.0;
+        for (int u = threadIdx.x; u < nu; u += 1024) a += wc[U[u]];
+        a = block_sum(a, scratch);
+        const i64 j = (i64)blockIdx.x * 1024 + threadIdx.x;
+        if (j < d) Zpart0[j] += cval * a;
+    } else if (DO_Y) {
+        double a = 0.0;
+        for (i64 j = threadIdx.x; j < d; j += 1024) a += trow[j];
+        a = block_sum(a, scratch);
+        for (int u = threadIdx.x; u < nu; u += 1024) Ypart0[U[u]] += cval * a;
+    }
+}
+
+// T fixed: Qt[l][i] += c sum_j Tm[l][j] for i in U; one workgroup per row l of Tm
+__global__ __launch_bounds__(256) void k_spu_xtt(const int* __restrict__ U, int nu, double cval, const double* __restrict__ Tm,
+                                                 i64 ldt, i64 d, double* __restrict__ Qt, i64 ldq) {
+    __shared__ double scratch[4];
+    const int l = blockIdx.x;
+    double a = 0.0;
+    for (i64 j = threadIdx.x; j < d; j += 256) a += Tm[(i64)l * ldt + j];
+    a = block_sum(a, scratch);
+    for (int u = threadIdx.x; u < nu; u += 256) Qt[(i64)l * ldq + U[u]] += cval * a;
+}
+
+// sh[v] = sum over r in [r0, r1) of B[row(r)][v], v < m <= 64, row(r) = idx ? idx[r] : r; B row-major with m columns.  1024 threads:
+// 16 groups of 64 lanes take every 16th row, the groups are added in order.  sh: 17 x 64 doubles; the result is in sh[16 * 64 + v]
+__device__ __forceinline__ void spu_panel_sum(const double* __restrict__ B, const int* __restrict__ idx, i64 r0, i64 r1, int m,
+                                              double* sh) {
+    const int v = threadIdx.x & 63, g = threadIdx.x >> 6;
+    double a = 0.0;
+    if (v < m)
+        for (i64 r = r0 + g; r < r1; r += 16) a += B[(idx ? (i64)idx[r] : r) * m + v];
+    sh[g * 64 + v] = a;
+    __syncthreads();
+    if (g == 0) {
+        double t = 0.0;
+        for (int q = 0; q < 16; ++q) t += sh[q * 64 + v];
+        sh[16 * 64 + v] = t;
+    }
+    __syncthreads();
+}
+// X B: part[b][v] = sum of B's rows of chunk b (rows < d), then out[i][v] += c sum_b part[b][v] for i in U
+__global__ __launch_bounds__(1024) void k_spu_panel_part(const double* __restrict__ B, i64 d, int m, i64 chunk,
+                                                         double* __restrict__ part) {
+    __shared__ double sh[17 * 64];
+    const i64 r0 = (i64)blockIdx.x * chunk;
+    spu_panel_sum(B, nullptr, r0, r0 + chunk < d ? r0 + chunk : d, m, sh);
+    if (threadIdx.x < 64) part[(i64)blockIdx.x * 64 + threadIdx.x] = sh[16 * 64 + threadIdx.x];
+}
+__global__ __launch_bounds__(256) void k_spu_panel_rows(const int* __restrict__ U, int nu, double cval,
+                                                        const double* __restrict__ part, int nb, int m, double* __restrict__ out) {
+    const int v = threadIdx.x & 63;
+    const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= nu || v >= m) return;
+    double t = 0.0;
+    for (int b = 0; b < nb; ++b) t += part[(i64)b * 64 + v];
+    out[(i64)U[u] * m + v] += cval * t;
+}
+// X^T Q: out[j][v] += c sum_{i in U} Q[i][v] for every j < d; a workgroup takes the |U| rows itself, then 256 rows of out
+__global__ __launch_bounds__(1024) void k_spu_panel_all(const int* __restrict__ U, int nu, double cval, const double* __restrict__ Q,
+                                                        int m, i64 d, double* __restrict__ out) {
+    __shared__ double sh[17 * 64];
+    spu_panel_sum(Q, U, 0, nu, m, sh);
+    const int v = threadIdx.x & 63, g = threadIdx.x >> 6;
+    if (v >= m) return;
+    const double add = cval * sh[16 * 64 + v];
+    const i64 j0 = (i64)blockIdx.x * 256;
+    for (i64 j = j0 + g; j < j0 + 256 && j < d; j += 16) out[j * m + v] += add;
+}
+
+// the residual of a uniform row is dense: r_ij = c - (W T)_ij for all j < d.  One workgroup per row of U, T read coalesced along
+// j (k d work per row); it REPLACES what k_sp_resid left for that row (there: the row's stored zeros)
+//   rowobj[i] = sum_j r^2,  rowpos[i] = sum_j max(r, 0)^2,  rowhat[i] = sum_j (W T)_ij^2     (all j < d: the objective's
+//   pattern form subtracts rowhat from <W^T W, T T^T>, which for this row leaves exactly sum_j r^2)
+__global__ __launch_bounds__(256) void k_spu_resid(const int* __restrict__ U, double cval, const double* __restrict__ Wt, i64 ldw,
+                                                   const double* __restrict__ T, i64 ldt, i64 d, int k,
+                                                   double* __restrict__ rowobj, double* __restrict__ rowpos,
+                                                   double* __restrict__ rowhat) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double* wsh = reinterpret_cast<double*>(smem);   // [k]
+    __shared__ double scratch[4];
+    const i64 i = U[blockIdx.x];
+    for (int l = threadIdx.x; l < k; l += 256) wsh[l] = Wt[(i64)l * ldw + i];
+    __syncthreads();
+    double obj = 0.0, pos = 0.0, hat = 0.0;
+    for (i64 j = threadIdx.x; j < d; j += 256) {
+        double acc = 0.0;
+        for (int l = 0; l < k; ++l) acc = fma(wsh[l], T[(i64)l * ldt + j], acc);
+        const double r = cval - acc;
+        obj = fma(r, r, obj);
+        const double rp = fmax(r, 0.0);
+        pos = fma(rp, rp, pos);
+        hat = fma(acc, acc, hat);
+    }
+    obj = block_sum(obj, scratch);
+    pos = block_sum(pos, scratch);
+    hat = block_sum(hat, scratch);
+    if (threadIdx.x == 0) {
+        if (rowobj) rowobj[i] = obj;
+        if (rowpos) rowpos[i] = pos;
+        if (rowhat) rowhat[i] = hat;
+    }
+}
+
+// the reset row when row mi = *row_idx is uniform: out[j] = max(c - W[mi,:] T[:,j], 0) for all j < d (after k_sp_reset_row,
+// whose entries for that row it overwrites); any other row: nothing
+__global__ __launch_bounds__(256) void k_spu_reset_row(const int* __restrict__ U, int nu, double cval, const double* __restrict__ Wt,
+                                                       i64 ldw, const double* __restrict__ T, i64 ldt, i64 d, int k,
+                                                       const i64* __restrict__ row_idx, double* __restrict__ out) {
+    const i64 mi = *row_idx;
+    int lo = 0, hi = nu;                 // U is sorted: first entry >= mi
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((i64)U[mid] < mi) lo = mid + 1; else hi = mid;
+    }
+    if (lo >= nu || (i64)U[lo] != mi) return;
+    const i64 j = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (j >= d) return;
+    double acc = 0.0;
+    for (int l = 0; l < k; ++l) acc = fma(Wt[(i64)l * ldw + mi], T[(i64)l * ldt + j], acc);
+    out[j] = fmax(cval - acc, 0.0);
+}
+
+// the stored values of the rows of U become 0 (the pattern stays); one wave per row
+template <typename SX>
+__global__ __launch_bounds__(256) void k_spu_zero_rows(const int* __restrict__ U, int nu, const i64* __restrict__ rowptr,
+                                                       SX* __restrict__ xval) {
+    const int u = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= nu) return;
+    const i64 i = U[u];
+    for (i64 p = rowptr[i] + (threadIdx.x & 63); p < rowptr[i + 1]; p += 64) xval[p] = SX(0);
+}
+
+// rows with tot_i < 1e-10 in row order (rri_csr_scale_X_uniform): one workgroup, a contiguous range of rows per thread, counted,
+// scanned and then written -- no atomics, so the list comes out sorted.  rows: room for n entries
+__global__ __launch_bounds__(1024) void k_spu_collect(const double* __restrict__ tot, i64 n, int* __restrict__ rows,
+                                                      i64* __restrict__ count) {
+    __shared__ int cnt[1024];
+    const i64 per = (n + 1023) / 1024;
+    const i64 i0 = (i64)threadIdx.x * per, i1 = i0 + per < n ? i0 + per : n;
+    int c = 0;
+    for (i64 i = i0; i < i1; ++i) c += tot[i] < 1e-10 ? 1 : 0;
+    cnt[threadIdx.x] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int a = 0;
+        for (int t = 0; t < 1024; ++t) { const int v = cnt[t]; cnt[t] = a; a += v; }
+        *count = a;
+    }
+    __syncthreads();
+    int o = cnt[threadIdx.x];
+    for (i64 i = i0; i < i1; ++i)
+        if (tot[i] < 1e-10) rows[o++] = (int)i;
 }
 
 }  // namespace rri

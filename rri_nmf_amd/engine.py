@@ -558,11 +558,15 @@ class RRIEngine(object):
                                                s.ctypes.data_as(C.POINTER(C.c_double))))
         return r, s
 
-    def preprocess(self, tfidf=False, normalize=False):
+    def preprocess(self, tfidf=False, normalize=False, uniform_rows=False):
         """tf-idf and/or row normalisation of the resident X, as matrixops.tfidf / normalize produce them.
-        tfidf: True (idf from this X), an idf vector (transform of new documents), or False.  Returns the idf used."""
+        tfidf: True (idf from this X), an idf vector (transform of new documents), or False.  Returns the idf used.
+        uniform_rows=True (a handle that keeps X as CSR only): rows whose total is below 1e-10 become the handle's uniform rows,
+        the dense row 1/d kept beside the pattern (uniform_rows()), and ZeroTotalRows is never raised."""
         if self.sparse_x:
-            return self._preprocess_csr(tfidf, normalize)
+            return self._preprocess_csr(tfidf, normalize, uniform_rows)
+        if uniform_rows:
+            raise ValueError('uniform_rows=True needs a handle that keeps X as CSR (sparse_x=True)')
         idf = None
         if tfidf is True:
             df = self.column_positive_counts()
@@ -578,10 +582,11 @@ class RRIEngine(object):
             self.scale_X(idf, normalize)
         return idf
 
-    def _preprocess_csr(self, tfidf, normalize):
+    def _preprocess_csr(self, tfidf, normalize, uniform_rows=False):
         """preprocess() on a handle that keeps X as CSR (rri_csr_column_positive_counts, rri_csr_scale_X): the stored values are
         rewritten.  Row normalisation turns a row whose total is below 1e-10 into the dense row 1/d (matrixops.py:143-147),
-        which the pattern cannot hold: ZeroTotalRows is raised then and X is what it was before the call."""
+        which the pattern cannot hold: ZeroTotalRows is raised then and X is what it was before the call -- or, with
+        uniform_rows, those rows take zeros and the handle keeps them as uniform rows (rri_csr_scale_X_uniform)."""
         as_ptr = lambda v: v.ctypes.data_as(C.POINTER(C.c_double))
         idf = None
         if tfidf is True:
@@ -594,11 +599,35 @@ class RRIEngine(object):
                 raise ValueError('col_scale must have d entries')
         if idf is not None or normalize:
             zero_rows = C.c_int64(0)
-            self._check(self._lib.rri_csr_scale_X(self._h, None if idf is None else as_ptr(idf), int(bool(normalize)),
-                                                  C.byref(zero_rows)))
-            if zero_rows.value:
+            scale = self._lib.rri_csr_scale_X_uniform if uniform_rows else self._lib.rri_csr_scale_X
+            self._check(scale(self._h, None if idf is None else as_ptr(idf), int(bool(normalize)), C.byref(zero_rows)))
+            if zero_rows.value and not uniform_rows:
                 raise ZeroTotalRows(int(zero_rows.value))
         return idf
+
+    def set_uniform_rows(self, rows, value):
+        """Declares rows of the resident CSR X as the dense row `value` (every column j < d): X = S + value * e_U 1^T, where S is
+        the stored CSR with zeros in those rows.  An empty list clears them; a second call replaces the list."""
+        rows = np.asarray(rows).ravel()
+        if rows.size and rows.dtype.kind not in 'iu':
+            raise ValueError('uniform rows are row indices: integers, not %s' % rows.dtype)
+        # what int32 cannot hold is refused here, not wrapped into a row the handle would accept
+        beyond = rows[(rows < np.iinfo(np.int32).min) | (rows > np.iinfo(np.int32).max)] if rows.size else rows
+        if beyond.size:
+            raise ValueError('uniform row %d is out of range (n = %d)' % (int(beyond[0]), self.n))
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        ptr =rows.ctypes.data_as(C.POINTER(C.c_int32)) if rows.size else None
+        self._check(self._lib.rri_set_uniform_rows(self._h, ptr, int(rows.size), float(value)))
+
+    def uniform_rows(self):
+        """(rows, value): the sorted int32 list of the handle's uniform rows and their value (empty, 0.0 by default)"""
+        count, value = C.c_int64(0), C.c_double(0.0)
+        self._check(self._lib.rri_get_uniform_rows(self._h, None, 0, C.byref(count), C.byref(value)))
+        rows = np.empty(int(count.value), dtype=np.int32)
+        if rows.size:
+            self._check(self._lib.rri_get_uniform_rows(self._h, rows.ctypes.data_as(C.POINTER(C.c_int32)), int(rows.size),
+                                                       C.byref(count), C.byref(value)))
+        return rows, float(value.value)
 
     # ---- row-sharded stepping -----------------------------------------------------------
     def reduce_buffer(self):

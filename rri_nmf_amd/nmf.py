@@ -37,6 +37,13 @@ additions select the device side:
             densify a scipy sparse X on the device (False); None = densify, unless the dense array would not fit the
             device's free memory (sparse_x_route).  With True: no W_mat, schedule='residual', group=, w_row,
             store_gradients or Gaussian mechanism.
+    uniform_rows  True: `preprocess` with row normalisation stays on the device for an X kept as CSR even when it has empty
+            documents, or documents whose tf-idf total is 0.  normalize makes each of those the dense row 1/d, which the CSR
+            pattern cannot hold; the handle keeps them as a short list BESIDE the pattern instead (X = S + (1/d) e_U 1^T) and adds
+            their share to every product with X, so nothing is preprocessed on the host, nothing is uploaded twice and a
+            ResidentProblem is kept.  The call must end on a CSR handle (sparse_X=True, or the automatic CSR route); no W_mat,
+            w_row, group=, schedule='residual', float16 / uint8 storage or host callbacks.  None / False (default): such a
+            matrix is preprocessed on the host, as before.
 
 What runs where
     host (numpy, once):   argument checks, warnings and sentinel returns (nmf.py:280-315), the
@@ -156,14 +163,15 @@ def _device_free_bytes(device):
 
 
 def preprocess_route(csr_handle, x_is_sparse, normalize=False, has_empty_row=False, W_mat=False, w_row=False,
-                     host_callbacks=False, half=False, group=False, counts=False):
+                     host_callbacks=False, half=False, group=False, counts=False, uniform_rows=False):
     """Where the `preprocess` option of nmf() runs: 'device' (X goes up raw and is rewritten there) or 'host' (matrixops on the
     host before the upload).  csr_handle: the answer of sparse_x_route -- X is kept as CSR on the device; x_is_sparse: X is a
     scipy sparse matrix; the other arguments say what the call asks for.
       weights, per-row weights, callbacks that see X on the host (diagnostics, store_gradients, a plain early_stop function) and
       float16 storage need the preprocessed X in host memory: 'host';
       a CSR handle: 'device' -- unless rows are to be normalised and one of them stores nothing: normalize makes it the dense row
-      1/d, which the pattern cannot take, and np.diff(indptr) shows it before anything is uploaded: 'host';
+      1/d, which the pattern cannot take, and np.diff(indptr) shows it before anything is uploaded: 'host' -- but with
+      uniform_rows the handle keeps such rows beside the pattern: 'device' whatever has_empty_row says;
       every other X, a scipy sparse one that is densified on the device included: 'device' (the dense kernel writes such rows);
       row-sharded (group): a dense X without weights or callbacks runs on the device, everything else is not built;
       counts (uint8 storage): always 'device' -- tf-idf and normalisation are the handle's two scale vectors there, and the host
@@ -174,13 +182,13 @@ def preprocess_route(csr_handle, x_is_sparse, normalize=False, has_empty_row=Fal
         return 'device'
     if W_mat or w_row or host_callbacks or half:
         return 'host'
-    if csr_handle and normalize and has_empty_row:
+    if csr_handle and normalize and has_empty_row and not uniform_rows:
         return 'host'
     return 'device'
 
 
 def _route_of_call(X, spec, sparse_X=None, dtype=None, device=0, W_mat=None, w_row=None, host_callbacks=False,
-                   schedule='gram', group=None):
+                   schedule='gram', group=None, uniform_rows=False):
     """(preprocess_route's answer, sparse_x_route's answer or None where that one is not asked) for the arguments of an nmf() call
     with preprocessing `spec` = (tfidf, normalize); X is the caller's or nmf()'s converted one"""
     half = dtype is not None and np.dtype(dtype) == np.float16
@@ -192,11 +200,11 @@ def _route_of_call(X, spec, sparse_X=None, dtype=None, device=0, W_mat=None, w_r
         free = _device_free_bytes(device) if (sparse_X is None and xs) else 0
         csr = sparse_x_route(sparse_X, xs, n, d, np.dtype(dtype or np.float64).itemsize, free)
     empty = False
-    if csr and spec[1]:
+    if csr and spec[1] and not uniform_rows:      # (uniform rows: no row is looked at before the upload)
         empty = bool(np.any(np.diff(X.tocsr().indptr) == 0)) if xs else not bool(np.all(np.any(np.asarray(X) != 0, axis=1)))
     route = preprocess_route(bool(csr), xs, normalize=spec[1], has_empty_row=empty, W_mat=W_mat is not None,
                              w_row=w_row is not None, host_callbacks=host_callbacks, half=half, group=group is not None,
-                             counts=counts)
+                             counts=counts, uniform_rows=bool(uniform_rows))
     return route, csr
 
 
@@ -501,7 +509,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         diagnostics=[], store_gradients=False,
         ind_rows_to_store=None, eps_gauss_t=None, delta_gauss_t=None,
         *, dtype=None, device=0, device_init=None, sparse_pattern=None, preprocess=None, schedule='gram', group=None,
-        resident=None, sparse_X=None):
+        resident=None, sparse_X=None, uniform_rows=None):
     """Non-negative factorisation X ~ W T by rank-one residue iteration; see the module docstring and
     the reference's docstring (nmf.py:109-269) for the parameters.  Returns a dict with 'W', 'T',
     'iter_cputime' (wall seconds since the start, per sweep), 'random_state' and, when the objective
@@ -512,11 +520,29 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     the step names.  Without weights, host callbacks or float16 storage X is uploaded raw and rewritten on the device
     (preprocess_route): a dense X and a scipy sparse X that is densified there in place, an X kept as CSR (sparse_X) in its
     stored values -- except that normalising a CSR X with an empty row, or one whose tf-idf total is 0, would make that row
-    dense: such a matrix, like every other case, is preprocessed on the host.  The idf used comes back as rtv['idf'].
+    dense: such a matrix, like every other case, is preprocessed on the host -- unless uniform_rows=True, with which the CSR handle
+    keeps those rows as the dense row 1/d beside its pattern and the matrix stays on the device route (module docstring).  The idf
+    used comes back as rtv['idf'].
     resident (keyword only): a ResidentProblem that keeps the device handle -- X uploaded and preprocessed -- from one call to
     the next on the same problem (see there)."""
     if sparse_X is not None and not isinstance(sparse_X, (bool, np.bool_)):
         raise ValueError('sparse_X must be True, False or None')
+    if uniform_rows is not None and not isinstance(uniform_rows, (bool, np.bool_)):
+        raise ValueError('uniform_rows must be True, False or None')
+    if uniform_rows:
+        # uniform rows live on the handle that keeps X as CSR, and nothing on the host ever sees the preprocessed X
+        host_side = bool(diagnostics) or bool(store_gradients) or \
+            (callable(early_stop) and getattr(early_stop, 'device_entries', None) is None)
+        refused = [name for name, on in (('W_mat', W_mat is not None), ('w_row', w_row is not None),
+                                         ('group=', group is not None), ("schedule='residual'", schedule == 'residual'),
+                                         ('dtype=float16', dtype is not None and np.dtype(dtype) == np.float16),
+                                         ('dtype=uint8', dtype is not None and np.dtype(dtype) == np.uint8),
+                                         ('host callbacks (diagnostics, store_gradients, an early_stop function)', host_side),
+                                         ('sparse_X=False', sparse_X is not None and not sparse_X))
+                   if on]
+        if refused:
+            raise ValueError('uniform_rows=True keeps the rows that normalisation makes dense beside the pattern of an X kept as '
+                             'CSR on one device; it does not combine with %s' % ', '.join(refused))
     if sparse_X:
         # the handle that keeps X as CSR is the unweighted flavour in the Gram form on one device, stepped by rri_sweep
         refused = [name for name, on in (('W_mat', W_mat is not None), ("schedule='residual'", schedule == 'residual'),
@@ -597,7 +623,11 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             (callable(early_stop) and getattr(early_stop, 'device_entries', None) is None)
         # (float16 storage: tf-idf and normalisation in float64 on the host, so that X is rounded once, at upload -- the device
         # route would round the raw X and then rewrite it)
-        route, csr_route = _route_of_call(X, spec, sparse_X, dtype, device, W_mat, w_row, host_callbacks, schedule, group)
+        route, csr_route = _route_of_call(X, spec, sparse_X, dtype, device, W_mat, w_row, host_callbacks, schedule, group,
+                                          uniform_rows)
+        if uniform_rows and not csr_route:
+            raise ValueError('uniform_rows=True needs an X kept as CSR on the device: pass sparse_X=True (the automatic route '
+                             'densifies this X)')
         if route == 'host':
             X, rtv['idf'] = _preprocess_on_host(X, *spec)
         else:
@@ -608,6 +638,9 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             if n_empty:
                 raise ValueError('%d row(s) of X are empty: normalisation would make them dense (1/d), which dtype=uint8 cannot '
                                  'store; drop them or choose a floating-point dtype' % n_empty)
+    elif uniform_rows and not _route_of_call(X, (False, False), sparse_X, dtype, device, W_mat, w_row, False, schedule, group)[1]:
+        raise ValueError('uniform_rows=True needs an X kept as CSR on the device: pass sparse_X=True (the automatic route '
+                         'densifies this X)')
     n, d = X.shape
 
     # ---- option sanity, exactly as nmf.py:280-315 ---------------------------------------------
@@ -673,7 +706,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             raise ValueError('resident= keeps a handle for plain calls: no group, no w_row, no host-side preprocessing')
         tf_opt = None if device_spec is None else (device_spec['tfidf'] if isinstance(device_spec['tfidf'], bool) else 'given')
         res_key = (tuple(X.shape), str(getattr(X, 'dtype', None)), W_mat_given is None, int(k), str(sdt), device,
-                   sparse_pattern, schedule, sparse_X,
+                   sparse_pattern, schedule, sparse_X, bool(uniform_rows),
                    None if device_spec is None else (tf_opt, bool(device_spec['normalize'])))
         if tf_opt == 'given':
             res_key = None               # an idf vector from outside: not worth telling apart -- a fresh handle
@@ -696,7 +729,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         on_device = device_init if device_init is not None else (float(n) * d >= DEVICE_INIT_MIN_ELEMS)
         if device_spec is not None and not reused:
             try:
-                idf = eng.preprocess(**device_spec)
+                idf = eng.preprocess(uniform_rows=True, **device_spec) if uniform_rows else eng.preprocess(**device_spec)
             except ZeroTotalRows as exc:
                 if counts:      # (rows made only of terms that occur in every document: their tf-idf total is 0)
                     raise ValueError('%d row(s) of X have a tf-idf total below 1e-10: normalisation would make them dense (1/d), '

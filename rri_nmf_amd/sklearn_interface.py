@@ -240,8 +240,8 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
     @staticmethod
     def _takes_holder(X, kw):
         """keep_resident on a scipy sparse X: nmf() keeps a handle when the preprocessing asked for runs on the device
-        (nmf.preprocess_route); where it runs on the host -- a CSR handle and an empty row to normalise -- there is no holder, as
-        for every sparse X before the CSR handle preprocessed on the device"""
+        (nmf.preprocess_route); where it runs on the host -- a CSR handle and an empty row to normalise, without
+        nmf_kwargs' uniform_rows=True -- there is no holder, as for every sparse X before the CSR handle preprocessed on the device"""
         if not sp.issparse(X):
             return True
         spec = _nmf_module._preprocess_spec(kw.get('preprocess'))
@@ -249,7 +249,7 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
             return False
         route, _ = _nmf_module._route_of_call(X, spec, kw.get('sparse_X'), kw.get('dtype'), kw.get('device', 0), kw.get('W_mat'),
                                               kw.get('w_row'), bool(kw.get('diagnostics')) or bool(kw.get('store_gradients')),
-                                              kw.get('schedule', 'gram'), kw.get('group'))
+                                              kw.get('schedule', 'gram'), kw.get('group'), bool(kw.get('uniform_rows')))
         return route == 'device'
 
     def release(self):
@@ -281,6 +281,8 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
                     # the storage options of nmf_kwargs the fold-in follows: X kept as CSR on the device, and a float16 or uint8
                     # store (without it the fold-in would upload the new rows at 8 bytes per entry)
                     **({'sparse_X': self.nmf_kwargs['sparse_X']} if 'sparse_X' in self.nmf_kwargs else {}),
+                    # ... and with it the uniform rows that keep new documents without a term on the device route
+                    **({'uniform_rows': self.nmf_kwargs['uniform_rows']} if 'uniform_rows' in self.nmf_kwargs else {}),
                     **({'dtype': self._read_only_storage()} if self._read_only_storage() is not None else {}))
         return soln['W']
 

@@ -3,7 +3,7 @@ NMF_TM_Estimator(handle_tfidf=True, handle_normalization=True, nmf_kwargs={'spar
 keep_resident=True saves per one_iter(X_csr) call.
 
     python tools/e2e_sparse_tfidf_probe.py [--density 0.002 0.01 0.05] [--reps 5] [--calls 20] [--label NAME] [--out FILE.jsonl]
-                                           [--tree DIR] [--routes default products]
+                                           [--tree DIR] [--routes default products] [--empty-rows 0.001] [--uniform-rows both]
 
 100000 x 10000 Zipf counts (tools/sparse_x_probe.zipf_counts), k = 50, fp32 storage, 30 sweeps per fit.  One JSON line per
 density: medians over --reps fits of the wall time and of its parts --
@@ -17,7 +17,13 @@ them one by one; host LU / QR between them is not in it).  --routes default prod
 turn, rep by rep (one line per route): `products` hides sparse_range_finder from the engine, which is the start as it was before
 that call existed -- the two sides of the comparison on one device in one process.
 --tree DIR imports rri_nmf_amd from another checkout (built there), to put two commits side by side on one device; --label
-names the line."""
+names the line.
+--empty-rows F empties that share of the documents (seeded), as vocabulary pruning does: normalisation makes each the dense row
+1/d, which sends the call to the host route -- unless nmf_kwargs carries uniform_rows=True (--uniform-rows on).  --uniform-rows
+both fits and calls one_iter without and with the option in turn, rep by rep (one line per setting, `uniform_rows` says which;
+without the option the calls are those of the commits before it), and the line with the option also carries the handle's own
+timing of one sampled sweep: the X pass (`pass_us`, which brackets both launches) and the launch that adds the uniform rows'
+share after it (`uniform_us`), per topic-step launch."""
 import argparse
 import json
 import os
@@ -142,7 +148,11 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--tree', default=os.path.dirname(HERE))
     ap.add_argument('--routes', nargs='+', default=['default'], choices=['default', 'products'])
+    ap.add_argument('--empty-rows', type=float, default=0.0)
+    ap.add_argument('--uniform-rows', default='off', choices=['off', 'on', 'both'])
     args = ap.parse_args()
+    if args.uniform_rows != 'off':
+        return main_uniform(args)
     engine, nmf, si = load_package(args.tree)
     clock = Clock()
     instrument(engine, nmf, clock)
@@ -191,6 +201,90 @@ def main():
             if keep:
                 est.release()
         emit(args, rec)
+
+
+def with_empty_rows(X, share, seed=7):
+    """X with that share of its rows emptied (the pattern loses them: no stored zeros)"""
+    if share <= 0:
+        return X
+    import scipy.sparse as sp
+    n = X.shape[0]
+    rows = np.random.RandomState(seed).choice(n, size=max(1, int(round(share * n))), replace=False)
+    keep = np.ones(n)
+    keep[rows] = 0.0
+    Y = (sp.diags(keep) @ X).tocsr()
+    Y.eliminate_zeros()
+    Y.sort_indices()
+    return Y
+
+
+def pass_timing(engine, X, W, T):
+    """one sampled sweep from the fitted W, T on a handle with the uniform rows of X: microseconds per launch of the X pass's
+    bracket (timing id 0: k_spx_pass and, inside it, the uniform rows' launch) and of that launch alone (id 3)"""
+    n, d = X.shape
+    k = T.shape[0]
+    with engine.RRIEngine(n, d, k, dtype=np.float32, sparse_x=True) as e:
+        e.upload_X_csr(X.astype(np.float32))
+        e.preprocess(tfidf=True, normalize=True, uniform_rows=True)
+        e.set_W(W); e.set_T(T)
+        e.set_params(project_T_each_iter=True, t_row_sum=1.0, w_row_sum=1.0)
+        e.sweep(2)
+        e.timing_enable(True)
+        e.sweep(1)
+        e.timing_enable(False)
+        (n0, ms0), (n3, ms3) = e.timing_read(0), e.timing_read(3)
+        return {'uniform_rows': int(e.uniform_rows()[0].size), 'pass_launches': n0, 'pass_us': 1e3 * ms0 / max(n0, 1),
+                'uniform_launches': n3, 'uniform_us': 1e3 * ms3 / max(n3, 1)}
+
+
+def main_uniform(args):
+    """--uniform-rows on / both: the fits and the one_iter calls of main(), per setting of nmf_kwargs' uniform_rows"""
+    engine, nmf, si = load_package(args.tree)
+    clock = Clock()
+    instrument(engine, nmf, clock)
+    n, d, k = 100000, 10000, 50
+    modes = {'on': [True], 'both': [False, True]}[args.uniform_rows]
+
+    def kwargs(mode):
+        extra = {'uniform_rows': True} if mode else {}
+        return dict(handle_tfidf=True, handle_normalization=True, random_state=0,
+                    nmf_kwargs=dict({'sparse_X': True, 'dtype': np.float32, 'eps_stop': -1}, **extra))
+    for dens in args.density:
+        X = with_empty_rows(zipf_counts(n, d, dens, seed=int(dens * 1e4)), args.empty_rows)
+        base = {'tool': 'e2e_sparse_tfidf_probe', 'label': args.label, 'shape': [n, d], 'k': k, 'density_asked': dens,
+                'nnz': int(X.nnz), 'density': X.nnz / float(n * d), 'empty_rows': int(np.sum(np.diff(X.indptr) == 0))}
+        for mode in modes:
+            si.NMF_TM_Estimator(n, d, k, max_iter=2, **kwargs(mode)).fit(X)          # warm-up
+        runs = {mode: {'walls': [], 'parts': [], 'sweeps': [], 'rf': []} for mode in modes}
+        for _ in range(args.reps):
+            for mode in modes:                                                       # the settings in turn, rep by rep
+                est = si.NMF_TM_Estimator(n, d, k, max_iter=30, **kwargs(mode))
+                clock.reset()
+                t0 = time.perf_counter()
+                est.fit(X)
+                r = runs[mode]
+                r['walls'].append(time.perf_counter() - t0)
+                r['parts'].append(dict(clock.t))
+                r['rf'].append(0.0)
+                r['sweeps'].append(len(est.nmf_outputs['iter_cputime']))
+        ests = {mode: si.NMF_TM_Estimator(n, d, k, max_iter=2, keep_resident=True, **kwargs(mode)).fit(X) for mode in modes}
+        calls = {mode: [] for mode in modes}
+        for _ in range(args.calls):
+            for mode in modes:
+                t0 = time.perf_counter()
+                ests[mode].one_iter(X)
+                calls[mode].append(time.perf_counter() - t0)
+        for mode in modes:
+            rec = dict(base, uniform_rows=bool(mode), fit=fit_record(runs[mode]))
+            holder = getattr(ests[mode], '_resident', None)
+            if args.calls > 0:
+                rec['one_iter_keep_resident'] = {'ms_median': 1e3 * median(calls[mode]), 'ms_min': 1e3 * min(calls[mode]),
+                                                 'ms_max': 1e3 * max(calls[mode]),
+                                                 'handle_reuses': int(holder.reuses) if holder is not None else 0}
+            ests[mode].release()
+            if mode:
+                rec['timing'] = pass_timing(engine, X, np.asarray(ests[mode].W), np.asarray(ests[mode].T))
+            emit(args, rec)
 
 
 if __name__ == '__main__':
