@@ -40,6 +40,8 @@ extern "C" {
 #define RRI_GRAM_SLICES 8
 /* largest rank k a handle takes */
 #define RRI_MAX_K 1024
+/* longest list rri_topn_rows returns per row */
+#define RRI_MAX_TOPN 64
 
 typedef struct rri_ctx rri_ctx;   /* opaque: one nmf() call (or one row shard of it) on one GPU */
 typedef struct rri_comm rri_comm; /* opaque: the communicator of a row-sharded run, one per process */
@@ -238,6 +240,23 @@ rri_status rri_argmax_rows(rri_ctx* ctx, int32_t* out_host);
  * names its entry, the others say "on another rank"), nobody is left waiting, and the ranks stay in step for the next call. */
 rri_status rri_masked_rmse(rri_ctx* ctx, const int64_t* ij, const double* vals, int64_t count,
                            double clip_lo, double clip_hi, double* out);
+/* The topn best columns of W T for each of `count` rows: what a recommender shows a user.  For a requested row i the score of
+ * column j is s_ij = sum_t W[i,t] T[t,j] in float64; eligible are the columns 0 .. d-1 that the row does not exclude and whose
+ * score is not NaN; the order is larger score first and, among equal scores, smaller column first (a total order: the answer
+ * does not depend on how the work is split).  idx_out[r * topn ..] takes the first min(topn, eligible) columns of that order,
+ * val_out their scores clipped to [clip_lo, clip_hi] -- the ranking uses the UNCLIPPED score; a NaN bound leaves that side open
+ * -- and the slots after them the index -1 and the value NaN.  Nothing of size n x d exists anywhere: the scores are formed tile
+ * by tile on the matrix cores and only the lists leave the chip.
+ *   rows          count row indices in [0, n), any order, duplicates allowed; NULL: rows 0 .. count-1
+ *   excl_indptr   NULL: nothing excluded.  Else a CSR pattern with one row per REQUEST (count + 1 entries, starting at 0,
+ *                 monotone); excl_indices: per request strictly ascending columns in [0, d)
+ * Blocking; reads the handle's current W and T (both must have been set: a handle with factors and no X will do, rri_create
+ * allocates nothing of size n x d) and works on every flavour and storage type.  Writes nothing a later sweep reads and keeps no
+ * buffer: rri_device_memory is what it was.  On a row-sharded handle the rows are local ones and the call is not collective.
+ * RRI_ERR_INVALID: a NULL handle or output, count < 0, a row out of range, factors not set, a malformed exclusion;
+ * RRI_ERR_UNSUPPORTED: topn outside 1 .. RRI_MAX_TOPN; count == 0: RRI_OK, nothing launched (outputs may be NULL). */
+rri_status rri_topn_rows(rri_ctx* ctx, const int64_t* rows, int64_t count, int32_t topn, const int64_t* excl_indptr,
+                         const int32_t* excl_indices, double clip_lo, double clip_hi, int32_t* idx_out, double* val_out);
 /* device-side copy of (W,T) for the early-stop rollback of nmf.py:360-363,393-407 */
 rri_status rri_snapshot(rri_ctx* ctx);
 rri_status rri_rollback(rri_ctx* ctx);
@@ -395,7 +414,8 @@ rri_status rri_objective_parts(rri_ctx* ctx, double out[3]);
 /* HIP-event timing of the streaming kernels on the handle's stream.  kernel_id:
  * 0 = fused X pass (row dots + column sums), 1 = W-column update, 2 = T-row update chain,
  * 3 = rank-one residual update (explicit-residual / WRRI flavour); on an RRI_UNWEIGHTED_SPARSE handle with uniform rows: the
- *     launch that adds their share after every X pass (also inside the bracket of id 0). */
+ *     launch that adds their share after every X pass (also inside the bracket of id 0),
+ * 4 = the launch of rri_topn_rows. */
 /* on = 0: off; on = N > 0: bracket every N-th launch of each kernel id with an event pair (N = 1: all).
  * An event record costs a bubble of a few microseconds on the stream, so sample when the timed region is
  * also the throughput measurement. */

@@ -39,6 +39,7 @@
 #include "rri_wrri_kernels.hpp"
 #include "rri_sparse_kernels.hpp"
 #include "rri_onchip_kernels.hpp"
+#include "rri_topn_kernels.hpp"
 
 using namespace rri;
 
@@ -293,8 +294,8 @@ struct rri_ctx {
     long onchip_fallbacks = 0;
 
     int timing = 0;            // 0 off, N > 0: time every N-th launch of each kernel id
-    long timing_seq[4] = {0, 0, 0, 0};
-    std::vector<TimedLaunch> timed[4];
+    long timing_seq[5] = {0, 0, 0, 0, 0};   // kernel ids of rri_timing_read
+    std::vector<TimedLaunch> timed[5];
     std::vector<hipEvent_t> event_pool;
 
     std::string err;
@@ -1228,6 +1229,17 @@ struct LK {  // float64-only kernels
     static void masked_sqerr(rri_ctx* c, const i64* ij, const double* vals, i64 count, double lo, double hi) {
         hipLaunchKernelGGL(k_masked_sqerr, dim3(256), dim3(256), 0, c->stream, (const double*)c->W, c->ldw,
                            (const double*)c->T, c->LD, c->k, ij, vals, count, lo, hi, c->normpart);
+    }
+    // the N best columns of W T for `count` requested rows (rri_topn_kernels.hpp); reads W and T, writes the two outputs only
+    static hipError_t topn_rows(rri_ctx* c, const i64* rows, i64 count, int N, const i64* eptr, const int* eidx, double lo,
+                                double hi, int* idx_out, double* val_out) {
+        const hipError_t e = allow_lds<k_topn_rows>(c, 64 * 1024);
+        if (e != hipSuccess) return e;
+        TimedScope ts(c, 4);
+        hipLaunchKernelGGL(k_topn_rows, dim3((unsigned)((count + TOPN_ROWS - 1) / TOPN_ROWS)), dim3(256), topn_lds_bytes(N),
+                           c->stream, (const double*)c->W, c->ldw, (const double*)c->T, c->LD, (int)c->d, c->k, rows, count, N,
+                           eptr, eidx, lo, hi, idx_out, val_out);
+        return hipGetLastError();
     }
 };
 
@@ -2392,7 +2404,7 @@ rri_status rri_destroy(rri_ctx* c) {
         (void)hipFree(o.p);
         dev_count(-1, o.bytes);
     }
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 5; ++i)
         for (auto& tl : c->timed[i]) { (void)hipEventDestroy(tl.a); (void)hipEventDestroy(tl.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -3219,6 +3231,44 @@ rri_status rri_masked_rmse(rri_ctx* c, const int64_t* ij, const double* vals, in
     if (tot[3] > 0.0) return fail(c, RRI_ERR_HIP, "masked rmse failed on another rank");
     if (!(tot[1] > 0.0)) return fail(c, RRI_ERR_INVALID, "no entry on any rank");
     *out = std::sqrt(tot[0] / tot[1]);
+    return RRI_OK;
+}
+
+// The N best columns of W T per requested row (rri_topn.hpp has the order).  Reads the handle's W and T; everything else it
+// needs -- row list, exclusion CSR, outputs -- lives in temporaries of the call, so no sum a later sweep reads is touched and
+// rri_device_memory reports what it reported before.  Rank-local on a row-sharded handle: no collective.
+rri_status rri_topn_rows(rri_ctx* c, const int64_t* rows, int64_t count, int32_t topn, const int64_t* excl_indptr,
+                         const int32_t* excl_indices, double clip_lo, double clip_hi, int32_t* idx_out, double* val_out) {
+    CHECK_CTX(c);
+    char why[200] = "";
+    const int bad = topn_check_request(c->n, c->d, rows, count, topn, RRI_MAX_TOPN, excl_indptr, excl_indices, why, sizeof why);
+    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+    if (count == 0) return RRI_OK;
+    if (!idx_out || !val_out) return fail(c, RRI_ERR_INVALID, "an output array is NULL");
+    if (!c->have_W || !c->have_T) return fail(c, RRI_ERR_INVALID, "W and T must be set first");
+    if ((count + TOPN_ROWS - 1) / TOPN_ROWS > 0x7fffffffLL) return fail(c, RRI_ERR_INVALID, "count %lld is too large for one call", (long long)count);
+    HIPCHK(c, hipSetDevice(c->device));
+    const i64 nex = excl_indptr ? excl_indptr[count] : 0;
+    DevTmp trows, tptr, tidx, tj, tv;
+    if (rows) HIPCHK(c, trows.alloc((size_t)count * sizeof(i64)));
+    if (excl_indptr) {
+        HIPCHK(c, tptr.alloc((size_t)(count + 1) * sizeof(i64)));
+        HIPCHK(c, tidx.alloc((size_t)std::max<i64>(nex, 1) * sizeof(int)));
+    }
+    HIPCHK(c, tj.alloc((size_t)count * topn * sizeof(int)));
+    HIPCHK(c, tv.alloc((size_t)count * topn * sizeof(double)));
+    if (rows) HIPCHK(c, hipMemcpyAsync(trows.p, rows, (size_t)count * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+    if (excl_indptr) {
+        HIPCHK(c, hipMemcpyAsync(tptr.p, excl_indptr, (size_t)(count + 1) * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+        if (nex > 0) HIPCHK(c, hipMemcpyAsync(tidx.p, excl_indices, (size_t)nex * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    }
+    hipError_t e = LK::topn_rows(c, (const i64*)trows.p, count, topn, (const i64*)tptr.p, (const int*)tidx.p, clip_lo, clip_hi,
+                                 (int*)tj.p, (double*)tv.p);
+    if (e == hipSuccess) e = hipMemcpyAsync(idx_out, tj.p, (size_t)count * topn * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(val_out, tv.p, (size_t)count * topn * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "top-N rows failed: %s", hipGetErrorString(e));
     return RRI_OK;
 }
 
@@ -4208,13 +4258,13 @@ rri_status rri_onchip_fallbacks(rri_ctx* c, int64_t* fallbacks) {
 rri_status rri_timing_enable(rri_ctx* c, int32_t on) {
     CHECK_CTX(c);
     c->timing = on < 0 ? 0 : on;
-    for (int i = 0; i < 4; ++i) c->timing_seq[i] = 0;
+    for (int i = 0; i < 5; ++i) c->timing_seq[i] = 0;
     return RRI_OK;
 }
 
 rri_status rri_timing_read(rri_ctx* c, int32_t id, int64_t* launches, double* total_ms) {
     CHECK_CTX(c);
-    if (id < 0 || id > 3) return fail(c, RRI_ERR_INVALID, "kernel_id out of range");
+    if (id < 0 || id > 4) return fail(c, RRI_ERR_INVALID, "kernel_id out of range");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     double tot = 0.0;

@@ -452,6 +452,37 @@ class RRIEngine(object):
                                               float(lo), float(hi), C.byref(out)))
         return float(out.value)
 
+    def topn_rows(self, rows=None, n_top=10, exclude=None, clip=(None, None)):
+        """The n_top best columns of W T for the listed rows (None: all n), scored and selected on the device: (idx int32
+        (m, n_top), val float64 (m, n_top)).  Ranked by the unclipped score, larger first, equal scores by the smaller column;
+        columns of `exclude` -- a scipy sparse matrix with one row per REQUESTED row, of which only the pattern counts -- and
+        columns whose score is NaN are left out; a row with fewer than n_top columns left is padded with index -1 and value NaN.
+        The returned values are clipped to clip = (lo, hi), None leaving a side open.  Reads the handle's current factors and
+        changes nothing; row-sharded: local rows, no collective."""
+        if rows is None:
+            m, rows_p = self.n, None
+        else:
+            rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
+            m, rows_p = rows.size, rows.ctypes.data_as(C.POINTER(C.c_int64))
+        n_top = int(n_top)
+        ptr_p = ind_p = None
+        if exclude is not None:
+            import scipy.sparse as sp
+            E = sp.csr_matrix(exclude, copy=True)       # sorted and deduplicated on a copy: the caller's arrays stay as they are
+            if E.shape != (m, self.d):
+                raise ValueError('exclude must have one row per requested row and d columns: %r, not %r' % ((m, self.d), E.shape))
+            E.sum_duplicates()
+            E.sort_indices()
+            indptr = np.ascontiguousarray(E.indptr, dtype=np.int64)
+            indices = np.ascontiguousarray(E.indices, dtype=np.int32)
+            ptr_p, ind_p = indptr.ctypes.data_as(C.POINTER(C.c_int64)), indices.ctypes.data_as(C.POINTER(C.c_int32))
+        lo, hi = (float('nan') if b is None else float(b) for b in clip)
+        idx = np.empty((m, max(n_top, 0)), dtype=np.int32)
+        val = np.empty((m, max(n_top, 0)), dtype=np.float64)
+        self._check(self._lib.rri_topn_rows(self._h, rows_p, m, n_top, ptr_p, ind_p, lo, hi,
+                                            idx.ctypes.data_as(C.POINTER(C.c_int32)), val.ctypes.data_as(C.POINTER(C.c_double))))
+        return idx, val
+
     def snapshot(self):
         self._check(self._lib.rri_snapshot(self._h))
 

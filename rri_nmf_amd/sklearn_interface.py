@@ -10,6 +10,9 @@ from sklearn.model_selection import train_test_split
 from sklearn.utils.validation import check_X_y, check_array
 
 from . import nmf as _nmf_module
+from .engine import RRIEngine
+
+_RECOMMEND_CHUNK = 1 << 20      # users per rri_topn_rows call of NMF_RS_Estimator.recommend
 
 
 def _nmf(*a, **kw):
@@ -50,6 +53,16 @@ def _observed_mask(X):
     return M
 
 
+def _pairs_pattern(ij, shape):
+    """the CSR pattern (ones, sorted columns, no duplicates) of a list of (i, j) pairs, whatever their values"""
+    ij = np.asarray(ij, dtype=np.intp)
+    A = sp.coo_matrix((np.ones(len(ij)), (ij[:, 0], ij[:, 1])), shape=shape).tocsr()
+    A.sum_duplicates()
+    A.sort_indices()
+    A.data[:] = 1.0
+    return A
+
+
 def _ratings_matrix(values, ij, shape):
     """the ratings as a CSR matrix: what the reference densifies with .toarray() (sklearn_interface.py:78-97)
     stays sparse here -- nmf() then keeps X, W_mat and the residual on the observed entries only"""
@@ -81,6 +94,7 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
         """X: (m, 2) index pairs (i, j); y: the m observed values X[i, j]."""
         X, y = check_X_y(X, y)
         self.min_rating, self.max_rating = np.min(y), np.max(y)
+        self.seen_ = _pairs_pattern(X, (self.n, self.d))     # every pair given, the hold-out below included (recommend)
         grp = self.nmf_kwargs.get('group')
         if grp is not None:
             # row-sharded fit (one rank's rows, LOCAL row indices in X): the clip bounds of predictions and of the early-stop
@@ -147,6 +161,38 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
             sl = slice(lo, lo + (1 << 20))
             out[sl] = np.einsum('ek,ke->e', W[i[sl], :], T[:, j[sl]])
         return np.clip(out, self.min_rating, self.max_rating)
+
+    def recommend(self, users=None, n_items=10, exclude_seen=True):
+        """The n_items best items for each of `users` (row indices, any order, duplicates allowed; None: every user), scored
+        and selected on the device (rri_topn_rows): (items int32 (m, n_items), scores float64 (m, n_items)).  Items are ranked by
+        the unclipped prediction W[i, :] T[:, j], larger first, equal predictions by the smaller item; the scores returned are
+        clipped to the rating range, the numbers `predict` gives for those pairs.  exclude_seen leaves out the pairs given to fit
+        (seen_, the hold-out included); a user with fewer than n_items items left gets item -1 and score NaN in the last slots.
+        No n x d product is formed anywhere, and there is no host route: without a GPU the call raises RRIHipUnavailable."""
+        if np.ndim(self.W) != 2 or np.ndim(self.T) != 2:
+            raise ValueError('the estimator is not fitted: it has no W and T')
+        if exclude_seen and getattr(self, 'seen_', None) is None:
+            raise ValueError('exclude_seen=True needs the pairs given to fit (seen_), which this estimator does not have')
+        W = self.W.toarray() if sp.issparse(self.W) else np.asarray(self.W)       # sparsify() was called: dense copies
+        T = self.T.toarray() if sp.issparse(self.T) else np.asarray(self.T)
+        n, d = W.shape[0], T.shape[1]
+        users = np.arange(n, dtype=np.int64) if users is None else np.asarray(users, dtype=np.int64).reshape(-1)
+        if users.size and (users.min() < 0 or users.max() >= n):
+            raise ValueError('users must be row indices in [0, %d)' % n)
+        n_items = int(n_items)
+        items = np.empty((users.size, max(n_items, 0)), dtype=np.int32)
+        scores = np.empty((users.size, max(n_items, 0)), dtype=np.float64)
+        eng = RRIEngine(n, d, W.shape[1], dtype=np.float64, weighted=False, device=self.nmf_kwargs.get('device', 0))
+        try:        # factors only: such a handle holds nothing of size n x d
+            eng.set_W(W)
+            eng.set_T(T)
+            for lo in range(0, users.size, _RECOMMEND_CHUNK):
+                u = users[lo:lo + _RECOMMEND_CHUNK]
+                items[lo:lo + u.size], scores[lo:lo + u.size] = eng.topn_rows(
+                    u, n_items, exclude=self.seen_[u] if exclude_seen else None, clip=(self.min_rating, self.max_rating))
+        finally:
+            eng.close()
+        return items, scores
 
     def predict(self, X):
         X = check_array(X)
