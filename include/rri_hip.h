@@ -257,6 +257,27 @@ rri_status rri_masked_rmse(rri_ctx* ctx, const int64_t* ij, const double* vals, 
  * RRI_ERR_UNSUPPORTED: topn outside 1 .. RRI_MAX_TOPN; count == 0: RRI_OK, nothing launched (outputs may be NULL). */
 rri_status rri_topn_rows(rri_ctx* ctx, const int64_t* rows, int64_t count, int32_t topn, const int64_t* excl_indptr,
                          const int32_t* excl_indices, double clip_lo, double clip_hi, int32_t* idx_out, double* val_out);
+/* The rank of listed columns in the total order of their rows: what hit rate, recall@N, NDCG@N, MRR, AUC and mean percentile
+ * rank of held-out pairs are computed from.  Request q has the row rows[q] (NULL: row q), the exclusion segment of rri_topn_rows
+ * (excl_indptr NULL: none) and the TARGET segment tgt_indices[tgt_indptr[q] .. tgt_indptr[q + 1]): columns strictly ascending
+ * inside [0, d); tgt_indptr is required.  Scores, eligibility and order are those of rri_topn_rows.  For target column j of
+ * request q, at its place in tgt_indices:
+ *   rank_out  the number of eligible columns j' != j that stand before j in the order -- the 0-based place j would have in an
+ *             unbounded rri_topn_rows list; the request's other targets count as competitors --, or -1 when j is itself not
+ *             eligible (excluded, or its score is NaN);
+ *   val_out   the score of j clipped to [clip_lo, clip_hi] (a NaN bound leaves that side open), NaN when j is not eligible: the
+ *             bits rri_topn_rows returns for that column;
+ * and eligible_out[q] (may be NULL) takes the number of eligible columns of request q.  There is no cap on the targets of a
+ * request.  The counts are integers formed without atomics: the answer does not depend on how the work is split.
+ * Like rri_topn_rows the call needs W and T set and nothing else, works on every flavour and storage type, writes nothing a
+ * later sweep reads and keeps no buffer; on a row-sharded handle the rows are local ones and the call is not collective.
+ * RRI_ERR_INVALID: a NULL handle or output, count < 0, a row out of range, factors not set, tgt_indptr NULL, malformed targets or
+ * exclusion; count == 0 or no target at all: RRI_OK, nothing launched and no output written (the outputs may be NULL). */
+rri_status rri_rank_entries(rri_ctx* ctx, const int64_t* rows, int64_t count,
+                            const int64_t* tgt_indptr, const int32_t* tgt_indices,
+                            const int64_t* excl_indptr, const int32_t* excl_indices,
+                            double clip_lo, double clip_hi,
+                            int32_t* rank_out, double* val_out, int32_t* eligible_out);
 /* device-side copy of (W,T) for the early-stop rollback of nmf.py:360-363,393-407 */
 rri_status rri_snapshot(rri_ctx* ctx);
 rri_status rri_rollback(rri_ctx* ctx);
@@ -415,7 +436,7 @@ rri_status rri_objective_parts(rri_ctx* ctx, double out[3]);
  * 0 = fused X pass (row dots + column sums), 1 = W-column update, 2 = T-row update chain,
  * 3 = rank-one residual update (explicit-residual / WRRI flavour); on an RRI_UNWEIGHTED_SPARSE handle with uniform rows: the
  *     launch that adds their share after every X pass (also inside the bracket of id 0),
- * 4 = the launch of rri_topn_rows. */
+ * 4 = the launch of rri_topn_rows, 5 = the launch of rri_rank_entries. */
 /* on = 0: off; on = N > 0: bracket every N-th launch of each kernel id with an event pair (N = 1: all).
  * An event record costs a bubble of a few microseconds on the stream, so sample when the timed region is
  * also the throughput measurement. */

@@ -81,6 +81,8 @@ PROTOTYPES = {
     'rri_masked_rmse': (_I32, [_P, C.POINTER(_I64), C.POINTER(_D), _I64, _D, _D, C.POINTER(_D)]),
     'rri_topn_rows': (_I32, [_P, C.POINTER(_I64), _I64, _I32, C.POINTER(_I64), C.POINTER(_I32), _D, _D, C.POINTER(_I32),
                              C.POINTER(_D)]),
+    'rri_rank_entries': (_I32, [_P, C.POINTER(_I64), _I64, C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I32),
+                                _D, _D, C.POINTER(_I32), C.POINTER(_D), C.POINTER(_I32)]),
     'rri_residual_rebuild': (_I32, [_P]),
     'rri_residual_update': (_I32, [_P] + [C.POINTER(_D)] * 8),
     'rri_get_residual': (_I32, [_P, _P, _I64, _I32]),

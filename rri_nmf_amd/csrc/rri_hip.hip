@@ -40,6 +40,7 @@
 #include "rri_sparse_kernels.hpp"
 #include "rri_onchip_kernels.hpp"
 #include "rri_topn_kernels.hpp"
+#include "rri_rank_kernels.hpp"
 
 using namespace rri;
 
@@ -294,8 +295,8 @@ struct rri_ctx {
     long onchip_fallbacks = 0;
 
     int timing = 0;            // 0 off, N > 0: time every N-th launch of each kernel id
-    long timing_seq[5] = {0, 0, 0, 0, 0};   // kernel ids of rri_timing_read
-    std::vector<TimedLaunch> timed[5];
+    long timing_seq[6] = {0, 0, 0, 0, 0, 0};   // kernel ids of rri_timing_read
+    std::vector<TimedLaunch> timed[6];
     std::vector<hipEvent_t> event_pool;
 
     std::string err;
@@ -1239,6 +1240,18 @@ struct LK {  // float64-only kernels
         hipLaunchKernelGGL(k_topn_rows, dim3((unsigned)((count + TOPN_ROWS - 1) / TOPN_ROWS)), dim3(256), topn_lds_bytes(N),
                            c->stream, (const double*)c->W, c->ldw, (const double*)c->T, c->LD, (int)c->d, c->k, rows, count, N,
                            eptr, eidx, lo, hi, idx_out, val_out);
+        return hipGetLastError();
+    }
+    // the ranks of listed columns of W T, piece by piece (rri_rank_kernels.hpp); reads W and T, writes the three outputs only
+    static hipError_t rank_entries(rri_ctx* c, const i64* rows, const RankPiece* pieces, i64 npieces, const int* tidx,
+                                   const i64* eptr, const int* eidx, double lo, double hi, int* rank_out, double* val_out,
+                                   int* elig_out) {
+        const hipError_t e = allow_lds<k_rank_entries>(c, (int)rank_lds_bytes());
+        if (e != hipSuccess) return e;
+        TimedScope ts(c, 5);
+        hipLaunchKernelGGL(k_rank_entries, dim3((unsigned)((npieces + RANK_PIECES - 1) / RANK_PIECES)), dim3(256), rank_lds_bytes(),
+                           c->stream, (const double*)c->W, c->ldw, (const double*)c->T, c->LD, (int)c->d, c->k, rows, pieces, npieces,
+                           tidx, eptr, eidx, lo, hi, rank_out, val_out, elig_out);
         return hipGetLastError();
     }
 };
@@ -2404,7 +2417,7 @@ rri_status rri_destroy(rri_ctx* c) {
         (void)hipFree(o.p);
         dev_count(-1, o.bytes);
     }
-    for (int i = 0; i < 5; ++i)
+    for (int i = 0; i < 6; ++i)
         for (auto& tl : c->timed[i]) { (void)hipEventDestroy(tl.a); (void)hipEventDestroy(tl.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -3269,6 +3282,54 @@ rri_status rri_topn_rows(rri_ctx* c, const int64_t* rows, int64_t count, int32_t
     const hipError_t es = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "top-N rows failed: %s", hipGetErrorString(e));
+    return RRI_OK;
+}
+
+// The rank of listed columns in the total order of their rows of W T (rri_rank.hpp has the semantics).  Reads the handle's W
+// and T; row list, target and exclusion CSR, the pieces and the outputs live in temporaries of the call, so no sum a later sweep
+// reads is touched and rri_device_memory reports what it reported before.  Rank-local on a row-sharded handle: no collective.
+rri_status rri_rank_entries(rri_ctx* c, const int64_t* rows, int64_t count, const int64_t* tgt_indptr, const int32_t* tgt_indices,
+                            const int64_t* excl_indptr, const int32_t* excl_indices, double clip_lo, double clip_hi,
+                            int32_t* rank_out, double* val_out, int32_t* eligible_out) {
+    CHECK_CTX(c);
+    char why[200] = "";
+    if (rank_check_request(c->n, c->d, rows, count, tgt_indptr, tgt_indices, excl_indptr, excl_indices, why, sizeof why) != TOPN_REQ_OK)
+        return fail(c, RRI_ERR_INVALID, "%s", why);
+    const i64 ntg = count > 0 ? tgt_indptr[count] : 0;
+    if (count == 0 || ntg == 0) return RRI_OK;
+    if (!rank_out || !val_out) return fail(c, RRI_ERR_INVALID, "an output array is NULL");
+    if (!c->have_W || !c->have_T) return fail(c, RRI_ERR_INVALID, "W and T must be set first");
+    std::vector<RankPiece> pieces((size_t)rank_cut_pieces(tgt_indptr, count, nullptr));
+    const i64 npieces = rank_cut_pieces(tgt_indptr, count, pieces.data());
+    if ((npieces + RANK_PIECES - 1) / RANK_PIECES > 0x7fffffffLL) return fail(c, RRI_ERR_INVALID, "count %lld is too large for one call", (long long)count);
+    HIPCHK(c, hipSetDevice(c->device));
+    const i64 nex = excl_indptr ? excl_indptr[count] : 0;
+    DevTmp trows, tpc, ttg, tptr, tidx, tr, tv, te;
+    if (rows) HIPCHK(c, trows.alloc((size_t)count * sizeof(i64)));
+    HIPCHK(c, tpc.alloc((size_t)npieces * sizeof(RankPiece)));
+    HIPCHK(c, ttg.alloc((size_t)ntg * sizeof(int)));
+    if (excl_indptr) {
+        HIPCHK(c, tptr.alloc((size_t)(count + 1) * sizeof(i64)));
+        HIPCHK(c, tidx.alloc((size_t)std::max<i64>(nex, 1) * sizeof(int)));
+    }
+    HIPCHK(c, tr.alloc((size_t)ntg * sizeof(int)));
+    HIPCHK(c, tv.alloc((size_t)ntg * sizeof(double)));
+    if (eligible_out) HIPCHK(c, te.alloc((size_t)count * sizeof(int)));
+    if (rows) HIPCHK(c, hipMemcpyAsync(trows.p, rows, (size_t)count * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tpc.p, pieces.data(), (size_t)npieces * sizeof(RankPiece), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ttg.p, tgt_indices, (size_t)ntg * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (excl_indptr) {
+        HIPCHK(c, hipMemcpyAsync(tptr.p, excl_indptr, (size_t)(count + 1) * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+        if (nex > 0) HIPCHK(c, hipMemcpyAsync(tidx.p, excl_indices, (size_t)nex * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    }
+    hipError_t e = LK::rank_entries(c, (const i64*)trows.p, (const RankPiece*)tpc.p, npieces, (const int*)ttg.p, (const i64*)tptr.p,
+                                    (const int*)tidx.p, clip_lo, clip_hi, (int*)tr.p, (double*)tv.p, (int*)te.p);
+    if (e == hipSuccess) e = hipMemcpyAsync(rank_out, tr.p, (size_t)ntg * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(val_out, tv.p, (size_t)ntg * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && eligible_out) e = hipMemcpyAsync(eligible_out, te.p, (size_t)count * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);      // the pieces (host memory of this call) have been read by now too
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "rank entries failed: %s", hipGetErrorString(e));
     return RRI_OK;
 }
 
@@ -4258,13 +4319,13 @@ rri_status rri_onchip_fallbacks(rri_ctx* c, int64_t* fallbacks) {
 rri_status rri_timing_enable(rri_ctx* c, int32_t on) {
     CHECK_CTX(c);
     c->timing = on < 0 ? 0 : on;
-    for (int i = 0; i < 5; ++i) c->timing_seq[i] = 0;
+    for (int i = 0; i < 6; ++i) c->timing_seq[i] = 0;
     return RRI_OK;
 }
 
 rri_status rri_timing_read(rri_ctx* c, int32_t id, int64_t* launches, double* total_ms) {
     CHECK_CTX(c);
-    if (id < 0 || id > 4) return fail(c, RRI_ERR_INVALID, "kernel_id out of range");
+    if (id < 0 || id > 5) return fail(c, RRI_ERR_INVALID, "kernel_id out of range");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     double tot = 0.0;

@@ -14,6 +14,7 @@ The X it factorises is (C[i, j] * cscale[j]) * rscale[i], formed in float64 wher
 are two vector updates (no pass rewrites the matrix) and cost no rounding of the store at all.  upload_X refuses anything but the
 integers 0..255; `set_X_scales` / `X_scales` write and read the two vectors.
 """
+import collections
 import ctypes as C
 import re
 
@@ -30,6 +31,10 @@ _READ_ONLY = (np.dtype(np.float16), np.dtype(np.uint8))        # stores of a den
 _HOST_TYPES = (np.dtype(np.float32), np.dtype(np.float64))     # what W, T, masks and CSR values travel as
 _RESET_CODES = {None: _capi.RESET_NONE, 'max_resid_document': _capi.RESET_MAX_RESID_DOCUMENT,
                 'random': _capi.RESET_RANDOM}
+
+
+# what RRIEngine.rank_entries returns: the canonical CSR of the targets, rank and val aligned with indices, eligible per request
+RankResult = collections.namedtuple('RankResult', 'indptr indices rank val eligible')
 
 
 class ZeroTotalRows(ValueError):
@@ -482,6 +487,43 @@ class RRIEngine(object):
         self._check(self._lib.rri_topn_rows(self._h, rows_p, m, n_top, ptr_p, ind_p, lo, hi,
                                             idx.ctypes.data_as(C.POINTER(C.c_int32)), val.ctypes.data_as(C.POINTER(C.c_double))))
         return idx, val
+
+    def rank_entries(self, rows, targets, exclude=None, clip=(None, None)):
+        """The rank of listed columns in the order of topn_rows, counted on the device (rri_rank_entries).  `targets` and
+        `exclude` are scipy sparse matrices with one row per REQUESTED row (rows None: all n), of which only the pattern counts;
+        both are sorted and deduplicated on copies.  Returns a RankResult: indptr, indices (the canonical CSR of the targets),
+        rank int32 aligned with indices -- the number of eligible columns that stand before the target, its 0-based place in an
+        unbounded top-N list, or -1 when the target is excluded or its score is NaN --, val float64 (the clipped score, NaN for
+        such a target) and eligible int32, one per request.  Without any target nothing is launched and eligible holds -1.
+        Reads the handle's current factors and changes nothing; row-sharded: local rows, no collective."""
+        import scipy.sparse as sp
+        if rows is None:
+            m, rows_p = self.n, None
+        else:
+            rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
+            m, rows_p = rows.size, rows.ctypes.data_as(C.POINTER(C.c_int64))
+
+        def pattern(A, what):
+            A = sp.csr_matrix(A, copy=True)             # sorted and deduplicated on a copy: the caller's arrays stay as they are
+            if A.shape != (m, self.d):
+                raise ValueError('%s must have one row per requested row and d columns: %r, not %r' % (what, (m, self.d), A.shape))
+            A.sum_duplicates()
+            A.sort_indices()
+            return np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int32)
+        I64P, I32P = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        tptr, tind = pattern(targets, 'targets')
+        eptr_p = eind_p = None
+        if exclude is not None:
+            eptr, eind = pattern(exclude, 'exclude')
+            eptr_p, eind_p = eptr.ctypes.data_as(I64P), eind.ctypes.data_as(I32P)
+        lo, hi = (float('nan') if b is None else float(b) for b in clip)
+        rank = np.empty(tind.size, dtype=np.int32)
+        val = np.empty(tind.size, dtype=np.float64)
+        eligible = np.full(m, -1, dtype=np.int32)
+        self._check(self._lib.rri_rank_entries(self._h, rows_p, m, tptr.ctypes.data_as(I64P), tind.ctypes.data_as(I32P), eptr_p, eind_p,
+                                               lo, hi, rank.ctypes.data_as(I32P), val.ctypes.data_as(C.POINTER(C.c_double)),
+                                               eligible.ctypes.data_as(I32P)))
+        return RankResult(tptr, tind, rank, val, eligible)
 
     def snapshot(self):
         self._check(self._lib.rri_snapshot(self._h))

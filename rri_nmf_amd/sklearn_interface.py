@@ -194,6 +194,134 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
             eng.close()
         return items, scores
 
+    def _pairs_of(self, X, y=None):
+        """(i, j, y) of what rank / ranking_score are given: (m, 2) index pairs as predict takes them, or an n x d matrix (dense
+        or scipy sparse) whose stored non-zeros are the pairs, in the order of X.nonzero(), their values standing in for a y
+        that is not given.  A dense array with two columns is read as pairs."""
+        n, d = np.shape(self.W)[0], np.shape(self.T)[1]
+        if sp.issparse(X) or (np.ndim(X) == 2 and np.shape(X) == (n, d) and d != 2):
+            if X.shape != (n, d):
+                raise ValueError('a matrix of pairs must be %d x %d, not %r' % (n, d, X.shape))
+            if sp.issparse(X):
+                C = X.tocoo()                   # what X.nonzero() does, keeping the values
+                keep = C.data != 0
+                i, j, vals = C.row[keep], C.col[keep], C.data[keep]
+            else:
+                i, j = np.nonzero(X)
+                vals = np.asarray(X)[i, j]
+            y = vals if y is None else y
+        else:
+            ij = np.asarray(check_array(X, ensure_min_samples=0), dtype=np.int64) if np.size(X) else np.zeros((0, 2), dtype=np.int64)
+            if ij.ndim != 2 or ij.shape[1] != 2:
+                raise ValueError('pairs must be an (m, 2) array of (row, column) indices')
+            i, j = ij[:, 0], ij[:, 1]
+        i, j = np.asarray(i, dtype=np.int64), np.asarray(j, dtype=np.int64)
+        if i.size and (i.min() < 0 or i.max() >= n or j.min() < 0 or j.max() >= d):
+            raise ValueError('pairs must be (row, column) indices inside %d x %d' % (n, d))
+        if y is not None:
+            y = np.asarray(y, dtype=np.float64).ravel()
+            if y.size != i.size:
+                raise ValueError('y must hold one value per pair: %d, not %d' % (i.size, y.size))
+        return i, j, y
+
+    def rank(self, X, exclude_seen=True):
+        """The place of each given pair (user i, item j) among user i's items, counted on the device (rri_rank_entries):
+        (rank int32 (m,), eligible int32 (m,)), aligned with the pairs as given -- a pair given twice gets its answer twice.  X is
+        (m, 2) index pairs or an n x d matrix whose stored non-zeros are the pairs (the order is that of X.nonzero()).  rank is
+        the number of the user's eligible items that `recommend` would list before item j (by the unclipped prediction, larger
+        first, equal predictions by the smaller item; the user's other pairs compete like any item), eligible the number of items
+        the user has to choose from.  exclude_seen leaves out the pairs given to fit (seen_, the hold-out included); a pair that
+        is itself in seen_ is not eligible and gets rank -1 -- it is not taken out of the exclusion silently --, as does a pair
+        whose prediction is NaN.  No n x d product is formed, and there is no host route: without a GPU the call raises
+        RRIHipUnavailable."""
+        if np.ndim(self.W) != 2 or np.ndim(self.T) != 2:
+            raise ValueError('the estimator is not fitted: it has no W and T')
+        if exclude_seen and getattr(self, 'seen_', None) is None:
+            raise ValueError('exclude_seen=True needs the pairs given to fit (seen_), which this estimator does not have')
+        i, j, _ = self._pairs_of(X)
+        W = self.W.toarray() if sp.issparse(self.W) else np.asarray(self.W)       # sparsify() was called: dense copies
+        T = self.T.toarray() if sp.issparse(self.T) else np.asarray(self.T)
+        n, d = W.shape[0], T.shape[1]
+        targets = _pairs_pattern(np.column_stack((i, j)), (n, d))                 # every pair once, columns ascending
+        users = np.flatnonzero(np.diff(targets.indptr))
+        rank_csr = np.empty(targets.nnz, dtype=np.int32)
+        eligible_user = np.full(n, -1, dtype=np.int32)
+        eng = RRIEngine(n, d, W.shape[1], dtype=np.float64, weighted=False, device=self.nmf_kwargs.get('device', 0))
+        try:        # factors only: such a handle holds nothing of size n x d
+            eng.set_W(W)
+            eng.set_T(T)
+            for lo in range(0, users.size, _RECOMMEND_CHUNK):
+                u = users[lo:lo + _RECOMMEND_CHUNK]
+                res = eng.rank_entries(u, targets[u], exclude=self.seen_[u] if exclude_seen else None,
+                                       clip=(self.min_rating, self.max_rating))
+                # the users ascend and each has all its pairs in one chunk: the chunk's targets are one stretch of the CSR
+                rank_csr[targets.indptr[u[0]]:targets.indptr[u[-1] + 1]] = res.rank
+                eligible_user[u] = res.eligible
+        finally:
+            eng.close()
+        keys = np.repeat(np.arange(n, dtype=np.int64), np.diff(targets.indptr)) * d + targets.indices
+        pos = np.searchsorted(keys, i * d + j)
+        return rank_csr[pos], eligible_user[i]
+
+    def ranking_score(self, X, y=None, n_items=10, exclude_seen=True, relevant_from=None):
+        """Ranking metrics of held-out pairs from their full-row ranks (`rank`): a dict.  X as in `rank`; with relevant_from
+        only the pairs whose value (y, or the stored value of a matrix X) is at least relevant_from are targets; a pair given
+        twice is one target.  n_items (N) is any positive integer.  With P_u the number of eligible targets of user u, L_u the
+        user's eligible count and r_0 < ... < r_{P-1} the user's target ranks:
+          hit_rate   mean over users with P_u >= 1 of [any r < N]
+          precision  ... of #{r < N} / N
+          recall     ... of #{r < N} / P_u
+          ndcg       ... of sum_{r < N} 1 / log2(r + 2) over sum_{p < min(N, P_u)} 1 / log2(p + 2)
+          mrr        ... of 1 / (1 + r_0)
+          auc        mean over users with P_u >= 1 and L_u > P_u of 1 - sum_a (r_a - a) / (P_u (L_u - P_u))
+          mean_percentile_rank   mean over eligible targets with L_u > 1 of r / (L_u - 1)
+        and n_items, users (how many were averaged), targets, targets_not_eligible (rank -1: in seen_ under exclude_seen, or a
+        NaN prediction).  Without an eligible target the metrics are NaN and the counts say why.  Computed on the host in
+        float64; each rank of a row-sharded fit scores its own rows."""
+        n_items = int(n_items)
+        if n_items < 1:
+            raise ValueError('n_items must be a positive integer, not %d' % n_items)
+        if np.ndim(self.W) != 2 or np.ndim(self.T) != 2:
+            raise ValueError('the estimator is not fitted: it has no W and T')
+        i, j, y = self._pairs_of(X, y)
+        if relevant_from is not None:
+            if y is None:
+                raise ValueError('relevant_from needs the values y of the pairs')
+            keep = y >= relevant_from
+            i, j = i[keep], j[keep]
+        d = np.shape(self.T)[1]
+        key, first = np.unique(i * d + j, return_index=True)                     # every pair once
+        i, j = i[first], j[first]
+        rank, eligible = self.rank(np.column_stack((i, j)), exclude_seen=exclude_seen)
+        ok = rank >= 0
+        out = {'n_items': n_items, 'targets': int(i.size), 'targets_not_eligible': int((~ok).sum())}
+        users, uid = np.unique(i[ok], return_inverse=True)
+        out['users'] = int(users.size)
+        names = ('hit_rate', 'precision', 'recall', 'ndcg', 'mrr', 'auc', 'mean_percentile_rank')
+        if users.size == 0:
+            out.update((name, float('nan')) for name in names)
+            return out
+        r, L = rank[ok].astype(np.float64), eligible[ok].astype(np.float64)
+        order = np.lexsort((r, uid))                                              # by user, the user's ranks ascending
+        r, L, uid = r[order], L[order], uid[order]
+        P = np.bincount(uid).astype(np.float64)
+        start = np.concatenate(([0], np.cumsum(P)[:-1])).astype(np.int64)
+        a = np.arange(r.size) - start[uid]                                        # the target's place among its user's targets
+        Lu = L[start]
+        hit = r < n_items
+        hits = np.bincount(uid, weights=hit)
+        ideal = np.concatenate(([0.0], np.cumsum(1.0 / np.log2(np.arange(min(n_items, int(P.max()))) + 2.0))))
+        out['hit_rate'] = float(np.mean(hits > 0))
+        out['precision'] = float(np.mean(hits / n_items))
+        out['recall'] = float(np.mean(hits / P))
+        out['ndcg'] = float(np.mean(np.bincount(uid, weights=hit / np.log2(r + 2.0)) / ideal[np.minimum(n_items, P).astype(np.int64)]))
+        out['mrr'] = float(np.mean(1.0 / (1.0 + r[start])))
+        room = Lu > P
+        out['auc'] = float(np.mean(1.0 - np.bincount(uid, weights=r - a)[room] / (P[room] * (Lu[room] - P[room])))) if room.any() else float('nan')
+        wide = L > 1
+        out['mean_percentile_rank'] = float(np.mean(r[wide] / (L[wide] - 1.0))) if wide.any() else float('nan')
+        return out
+
     def predict(self, X):
         X = check_array(X)
         # the reference indexes with the float array check_array returns, which modern numpy rejects
