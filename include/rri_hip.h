@@ -42,6 +42,8 @@ extern "C" {
 #define RRI_MAX_K 1024
 /* longest list rri_topn_rows returns per row */
 #define RRI_MAX_TOPN 64
+/* most words per group rri_cooccurrence_counts takes: one bit per slot of a 32-bit word */
+#define RRI_MAX_COOC_WORDS 32
 
 typedef struct rri_ctx rri_ctx;   /* opaque: one nmf() call (or one row shard of it) on one GPU */
 typedef struct rri_comm rri_comm; /* opaque: the communicator of a row-sharded run, one per process */
@@ -278,6 +280,28 @@ rri_status rri_rank_entries(rri_ctx* ctx, const int64_t* rows, int64_t count,
                             const int64_t* excl_indptr, const int32_t* excl_indices,
                             double clip_lo, double clip_hi,
                             int32_t* rank_out, double* val_out, int32_t* eligible_out);
+/* Document and co-document frequencies of groups of words: the two integer tables that topic coherence (UMass, PMI, NPMI over
+ * document co-occurrence) is computed from.  The corpus is a CSR PATTERN of n_rows x n_cols: indptr (n_rows + 1 entries, from 0,
+ * monotone) and indices (strictly ascending inside every row, inside [0, n_cols)); a stored entry means "the word occurs in the
+ * document", there are no values (drop explicit zeros first).  n_rows and n_cols belong to the request, not to the handle: a
+ * reference corpus need not be the training matrix.  words is n_groups x group_size, row-major: a column in [0, n_cols) or -1 for
+ * an empty slot, empty slots anywhere, a column at most once inside one group and in any number of groups.
+ *   df_out    n_groups x group_size: the number of rows that contain words[g, a];
+ *   codf_out  n_groups x group_size x group_size: the number of rows that contain both words[g, a] and words[g, b]; symmetric,
+ *             codf[g, a, a] = df[g, a];
+ * a -1 slot has 0 in its row and its column.  The counts are integers summed exactly: the answer does not depend on how the work
+ * is split, and two calls return the same bits.
+ * Blocking.  The handle supplies the device, the stream and the error text and nothing else: no X, W or T is needed, every flavour
+ * and storage type will do, nothing a later sweep reads is written, no buffer is kept (rri_device_memory is what it was), and on
+ * a handle with a communicator the call is not collective -- counts of row blocks add, so a caller sums them.  The request is
+ * checked before any HIP call.
+ * RRI_ERR_INVALID: a NULL handle, array or output, a negative size, a malformed CSR pattern, a word out of range or twice in one
+ * group; RRI_ERR_UNSUPPORTED: group_size outside 1 .. RRI_MAX_COOC_WORDS or n_groups outside 1 .. RRI_MAX_K; n_rows == 0 or no
+ * stored entry: RRI_OK, the outputs zeroed, nothing launched. */
+rri_status rri_cooccurrence_counts(rri_ctx* ctx, const int64_t* indptr, const int32_t* indices,
+                                   int64_t n_rows, int64_t n_cols,
+                                   const int32_t* words, int32_t n_groups, int32_t group_size,
+                                   int64_t* df_out, int64_t* codf_out);
 /* device-side copy of (W,T) for the early-stop rollback of nmf.py:360-363,393-407 */
 rri_status rri_snapshot(rri_ctx* ctx);
 rri_status rri_rollback(rri_ctx* ctx);
@@ -436,7 +460,8 @@ rri_status rri_objective_parts(rri_ctx* ctx, double out[3]);
  * 0 = fused X pass (row dots + column sums), 1 = W-column update, 2 = T-row update chain,
  * 3 = rank-one residual update (explicit-residual / WRRI flavour); on an RRI_UNWEIGHTED_SPARSE handle with uniform rows: the
  *     launch that adds their share after every X pass (also inside the bracket of id 0),
- * 4 = the launch of rri_topn_rows, 5 = the launch of rri_rank_entries. */
+ * 4 = the launch of rri_topn_rows, 5 = the launch of rri_rank_entries,
+ * 6 = the launches of rri_cooccurrence_counts: two per row chunk (masks, then counts), each in a bracket of its own. */
 /* on = 0: off; on = N > 0: bracket every N-th launch of each kernel id with an event pair (N = 1: all).
  * An event record costs a bubble of a few microseconds on the stream, so sample when the timed region is
  * also the throughput measurement. */

@@ -14,6 +14,7 @@ RRI_GRAM_SLICES = 8     # include/rri_hip.h
 RRI_LAYOUT_FIELDS = 23  # include/rri_hip.h
 RRI_MAX_K = 1024        # include/rri_hip.h: rri_create refuses a larger k (RRI_ERR_UNSUPPORTED)
 RRI_MAX_TOPN = 64       # include/rri_hip.h: the longest list rri_topn_rows returns per row
+RRI_MAX_COOC_WORDS = 32     # include/rri_hip.h: the most words per group rri_cooccurrence_counts takes
 RRI_OK, RRI_PAUSED = 0, 1
 RRI_ERR_INVALID, RRI_ERR_HIP, RRI_ERR_UNSUPPORTED = -1, -2, -3
 RRI_ERR_UNBOUNDED, RRI_ERR_W_COL_ZERO, RRI_ERR_NOT_IMPLEMENTED, RRI_ERR_COMM = -4, -5, -6, -7
@@ -83,6 +84,8 @@ PROTOTYPES = {
                              C.POINTER(_D)]),
     'rri_rank_entries': (_I32, [_P, C.POINTER(_I64), _I64, C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I32),
                                 _D, _D, C.POINTER(_I32), C.POINTER(_D), C.POINTER(_I32)]),
+    'rri_cooccurrence_counts': (_I32, [_P, C.POINTER(_I64), C.POINTER(_I32), _I64, _I64, C.POINTER(_I32), _I32, _I32,
+                                       C.POINTER(_I64), C.POINTER(_I64)]),
     'rri_residual_rebuild': (_I32, [_P]),
     'rri_residual_update': (_I32, [_P] + [C.POINTER(_D)] * 8),
     'rri_get_residual': (_I32, [_P, _P, _I64, _I32]),

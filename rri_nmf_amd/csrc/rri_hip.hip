@@ -29,6 +29,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -41,6 +42,7 @@
 #include "rri_onchip_kernels.hpp"
 #include "rri_topn_kernels.hpp"
 #include "rri_rank_kernels.hpp"
+#include "rri_cooc_kernels.hpp"
 
 using namespace rri;
 
@@ -295,8 +297,8 @@ struct rri_ctx {
     long onchip_fallbacks = 0;
 
     int timing = 0;            // 0 off, N > 0: time every N-th launch of each kernel id
-    long timing_seq[6] = {0, 0, 0, 0, 0, 0};   // kernel ids of rri_timing_read
-    std::vector<TimedLaunch> timed[6];
+    long timing_seq[7] = {0, 0, 0, 0, 0, 0, 0};   // kernel ids of rri_timing_read
+    std::vector<TimedLaunch> timed[7];
     std::vector<hipEvent_t> event_pool;
 
     std::string err;
@@ -1252,6 +1254,43 @@ struct LK {  // float64-only kernels
         hipLaunchKernelGGL(k_rank_entries, dim3((unsigned)((npieces + RANK_PIECES - 1) / RANK_PIECES)), dim3(256), rank_lds_bytes(),
                            c->stream, (const double*)c->W, c->ldw, (const double*)c->T, c->LD, (int)c->d, c->k, rows, pieces, npieces,
                            tidx, eptr, eidx, lo, hi, rank_out, val_out, elig_out);
+        return hipGetLastError();
+    }
+    // the masks of the rows [ch.r0, ch.r1) of a CSR pattern and the pair counts of those masks, added to codf
+    // (rri_cooc_kernels.hpp); reads the call's temporaries and writes masks and codf only
+    static hipError_t cooc_chunk(rri_ctx* c, const i64* indptr, const int* indices, const int* mptr, const int* ment,
+                                 const CoocChunk& ch, int lps, int n_groups, int group_size, unsigned* masks,
+                                 unsigned long long* codf) {
+        const size_t lds = cooc_mask_lds_bytes(n_groups);
+        hipError_t e = lps == 64 ? allow_lds<k_cooc_masks<64>>(c, (int)cooc_mask_lds_bytes(RRI_MAX_K))
+                                 : allow_lds<k_cooc_masks<8>>(c, (int)cooc_mask_lds_bytes(RRI_MAX_K));
+        if (e != hipSuccess) return e;
+        const dim3 tiles((unsigned)(ch.rows_pad / COOC_TILE_ROWS));
+        {
+            TimedScope ts(c, 6);
+            if (lps == 64)
+                hipLaunchKernelGGL(k_cooc_masks<64>, tiles, dim3(256), lds, c->stream, indptr, indices, mptr, ment, ch.r0, ch.r1,
+                                   n_groups, ch.rows_pad, masks);
+            else
+                hipLaunchKernelGGL(k_cooc_masks<8>, tiles, dim3(256), lds, c->stream, indptr, indices, mptr, ment, ch.r0, ch.r1,
+                                   n_groups, ch.rows_pad, masks);
+        }
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        {
+            TimedScope ts(c, 6);
+            const dim3 pieces((unsigned)((ch.rows_pad + COOC_COUNT_ROWS - 1) / COOC_COUNT_ROWS), (unsigned)n_groups);
+            auto count = [&](auto ppt) {
+                hipLaunchKernelGGL(k_cooc_count<decltype(ppt)::value>, pieces, dim3(256), 0, c->stream, (const unsigned*)masks,
+                                   ch.rows_pad, group_size, codf);
+            };
+            switch (cooc_count_ppt(group_size)) {
+                case 1: count(std::integral_constant<int, 1>()); break;
+                case 2: count(std::integral_constant<int, 2>()); break;
+                case 4: count(std::integral_constant<int, 4>()); break;
+                default: count(std::integral_constant<int, 9>()); break;
+            }
+        }
         return hipGetLastError();
     }
 };
@@ -2417,7 +2456,7 @@ rri_status rri_destroy(rri_ctx* c) {
         (void)hipFree(o.p);
         dev_count(-1, o.bytes);
     }
-    for (int i = 0; i < 6; ++i)
+    for (int i = 0; i < 7; ++i)
         for (auto& tl : c->timed[i]) { (void)hipEventDestroy(tl.a); (void)hipEventDestroy(tl.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -3330,6 +3369,56 @@ rri_status rri_rank_entries(rri_ctx* c, const int64_t* rows, int64_t count, cons
     const hipError_t es = hipStreamSynchronize(c->stream);      // the pieces (host memory of this call) have been read by now too
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "rank entries failed: %s", hipGetErrorString(e));
+    return RRI_OK;
+}
+
+// Document and co-document frequencies of groups of words over a CSR pattern (rri_cooc.hpp has the semantics).  The handle gives
+// the device, the stream and the error text: nothing it holds is read or written, so the call needs no X, W or T, touches no sum
+// a later sweep reads, and is not collective (counts of row blocks add).  The pattern, the membership table, the masks of a row
+// chunk and the counts live in temporaries of the call: rri_device_memory reports what it reported before.  The request is
+// checked before the handle and before any HIP call.
+rri_status rri_cooccurrence_counts(rri_ctx* c, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
+                                   const int32_t* words, int32_t n_groups, int32_t group_size, int64_t* df_out, int64_t* codf_out) {
+    char why[200] = "";
+    const int bad = cooc_check_request(indptr, indices, n_rows, n_cols, words, n_groups, group_size, why, sizeof why);
+    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+    CHECK_CTX(c);
+    if (!df_out || !codf_out) return fail(c, RRI_ERR_INVALID, "an output array is NULL");
+    const size_t M = (size_t)group_size, ndf = (size_t)n_groups * M, nco = ndf * M;
+    std::fill(df_out, df_out + ndf, (int64_t)0);
+    std::fill(codf_out, codf_out + nco, (int64_t)0);
+    const i64 nnz = indptr[n_rows];
+    if (n_rows == 0 || nnz == 0) return RRI_OK;
+    const CoocMemb memb = cooc_build_memb(words, n_groups, group_size, n_cols);
+    if (memb.ent.empty()) return RRI_OK;            // every slot is empty
+    std::vector<CoocChunk> chunks;
+    cooc_cut_rows(n_rows, n_groups, COOC_MASK_BUDGET, &chunks);
+    i64 pad_max = 0;
+    for (const CoocChunk& ch : chunks) pad_max = std::max(pad_max, ch.rows_pad);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevTmp tptr, tidx, tmp, tme, tmask, tco;
+    HIPCHK(c, tptr.alloc((size_t)(n_rows + 1) * sizeof(i64)));
+    HIPCHK(c, tidx.alloc((size_t)nnz * sizeof(int)));
+    HIPCHK(c, tmp.alloc(memb.ptr.size() * sizeof(int)));
+    HIPCHK(c, tme.alloc(memb.ent.size() * sizeof(int)));
+    HIPCHK(c, tmask.alloc((size_t)pad_max * n_groups * sizeof(unsigned)));
+    HIPCHK(c, tco.alloc(nco * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemcpyAsync(tptr.p, indptr, (size_t)(n_rows + 1) * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tidx.p, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tmp.p, memb.ptr.data(), memb.ptr.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tme.p, memb.ent.data(), memb.ent.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(tco.p, 0, nco * sizeof(unsigned long long), c->stream));
+    const int lps = cooc_lps(nnz, n_rows);
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; i < chunks.size() && e == hipSuccess; ++i)
+        e = LK::cooc_chunk(c, (const i64*)tptr.p, (const int*)tidx.p, (const int*)tmp.p, (const int*)tme.p, chunks[i], lps, n_groups,
+                           group_size, (unsigned*)tmask.p, (unsigned long long*)tco.p);
+    if (e == hipSuccess) e = hipMemcpyAsync(codf_out, tco.p, nco * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);      // the membership table (host memory of this call) has been read by now too
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "co-occurrence counts failed: %s", hipGetErrorString(e));
+    for (size_t g = 0; g < (size_t)n_groups; ++g)
+        for (size_t a = 0; a < M; ++a) df_out[g * M + a] = codf_out[(g * M + a) * M + a];
     return RRI_OK;
 }
 
@@ -4319,13 +4408,13 @@ rri_status rri_onchip_fallbacks(rri_ctx* c, int64_t* fallbacks) {
 rri_status rri_timing_enable(rri_ctx* c, int32_t on) {
     CHECK_CTX(c);
     c->timing = on < 0 ? 0 : on;
-    for (int i = 0; i < 6; ++i) c->timing_seq[i] = 0;
+    for (int i = 0; i < 7; ++i) c->timing_seq[i] = 0;
     return RRI_OK;
 }
 
 rri_status rri_timing_read(rri_ctx* c, int32_t id, int64_t* launches, double* total_ms) {
     CHECK_CTX(c);
-    if (id < 0 || id > 5) return fail(c, RRI_ERR_INVALID, "kernel_id out of range");
+    if (id < 0 || id > 6) return fail(c, RRI_ERR_INVALID, "kernel_id out of range");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     double tot = 0.0;

@@ -525,6 +525,33 @@ class RRIEngine(object):
                                                eligible.ctypes.data_as(I32P)))
         return RankResult(tptr, tind, rank, val, eligible)
 
+    def cooccurrence_counts(self, A, words):
+        """Document and co-document frequencies of groups of words, counted on the device (rri_cooccurrence_counts).  A is a scipy
+        sparse matrix, documents x dictionary, of which only the pattern counts: a stored non-zero means that the word occurs in
+        the document (explicit zeros are dropped, duplicates summed and the rows sorted on a copy; the caller's matrix stays as it
+        is).  `words` is array-like (g, M) of columns of A, -1 for an empty slot, a column at most once per group, M <= 32.
+        Returns (df int64 (g, M), codf int64 (g, M, M)): the number of documents that contain words[g, a], and the number that
+        contain both words[g, a] and words[g, b].  A need not have the handle's shape; the handle's factors and X are neither read
+        nor changed, and on a row-sharded handle the call is not collective (counts of row blocks add)."""
+        import scipy.sparse as sp
+        A = sp.csr_matrix(A, copy=True)
+        A.sum_duplicates()
+        A.eliminate_zeros()
+        A.sort_indices()
+        words = np.ascontiguousarray(np.asarray(words, dtype=np.int32))
+        if words.ndim != 2:
+            raise ValueError('words must be a (groups, words per group) array, not %r' % (words.shape,))
+        g, M = words.shape
+        indptr = np.ascontiguousarray(A.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(A.indices, dtype=np.int32)
+        df = np.zeros((g, M), dtype=np.int64)
+        codf = np.zeros((g, M, M), dtype=np.int64)
+        I64P, I32P = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        self._check(self._lib.rri_cooccurrence_counts(self._h, indptr.ctypes.data_as(I64P), indices.ctypes.data_as(I32P), A.shape[0],
+                                                      A.shape[1], words.ctypes.data_as(I32P), g, M, df.ctypes.data_as(I64P),
+                                                      codf.ctypes.data_as(I64P)))
+        return df, codf
+
     def snapshot(self):
         self._check(self._lib.rri_snapshot(self._h))
 

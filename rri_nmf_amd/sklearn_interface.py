@@ -479,3 +479,80 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
         calc = _nmf_module.TrueObjComputer(np.asarray(X), W, self.T, 0, 0, 0, 0, None, None)
         sse = 2.0 * calc.true_objective()
         return 1 - sse / sst
+
+    def top_words(self, n_words=10):
+        """The n_words heaviest words of every topic: (k, n_words) int32 columns of T.  A topic's words are ordered by the larger
+        entry of its row of T first and, among equal entries, by the smaller column (the order of rri_topn.hpp); only positive
+        entries qualify, and the slots after them hold -1.  Taken on the host -- T is k x d --, from a sparsified T as well."""
+        if np.ndim(self.T) != 2:
+            raise ValueError('the estimator is not fitted: it has no T')
+        n_words = int(n_words)
+        if n_words < 1:
+            raise ValueError('n_words must be a positive integer')
+        T = self.T.tocsr() if sp.issparse(self.T) else np.asarray(self.T)
+        out = np.full((T.shape[0], n_words), -1, dtype=np.int32)
+        for t in range(T.shape[0]):
+            row = T[t].toarray().ravel() if sp.issparse(T) else T[t]
+            cand = np.flatnonzero(row > 0)                            # ascending columns; NaN does not qualify
+            best = cand[np.argsort(-row[cand], kind='stable')][:n_words]      # stable: equal entries keep the smaller column first
+            out[t, :best.size] = best
+        return out
+
+    def coherence(self, X, n_words=10, measure='npmi', eps=1.0, words=None):
+        """Topic coherence over document co-occurrence in the corpus X (n' x d, any number of documents): a dict.
+
+        A word OCCURS in a document where X has a stored non-zero: presence is taken from X as given, without tf-idf or
+        normalisation (an idf of 0 would erase a word).  X is scipy sparse, or dense -- which is converted to CSR on the host
+        first, the slow way in.  `words` ((g, M), -1 for an empty slot, M <= 32) overrides top_words(n_words).  The document
+        frequencies D_a and co-document frequencies D_ab of each topic's words are counted on the device
+        (rri_cooccurrence_counts); there is no host route for them: without a GPU the call raises RRIHipUnavailable.
+
+        The measures are taken on the host in float64.  With N documents, over the pairs of slots a < b in top-word order:
+          'umass'  log((D_ab + eps) / D_a);                     undefined when D_a = 0
+          'pmi'    log((D_ab + eps) N / (D_a D_b));             undefined when D_a D_b = 0
+          'npmi'   -1 when D_ab = 0, 1 when D_ab = N, else log(p_ab / (p_a p_b)) / (-log p_ab) with p = D / N;
+                   undefined when D_a D_b = 0; eps is not used
+        A topic's figure is the mean over its defined pairs (pairs with an empty slot are no pairs).
+
+        Returns measure, per_topic (NaN for a topic without a defined pair), mean (the nanmean of per_topic), words, df (g, M),
+        codf (g, M, M), documents (N), pairs_undefined (per topic) and diversity: the number of distinct words among all non-empty
+        slots divided by the number of those slots."""
+        if measure not in ('umass', 'pmi', 'npmi'):
+            raise ValueError("measure must be 'umass', 'pmi' or 'npmi', not %r" % (measure,))
+        if np.ndim(self.T) != 2:
+            raise ValueError('the estimator is not fitted: it has no T')
+        d = np.shape(self.T)[1]
+        A = X.tocsr() if sp.issparse(X) else sp.csr_matrix(np.asarray(X))
+        if A.shape[1] != d:
+            raise ValueError('X must have the %d columns of T, not %d' % (d, A.shape[1]))
+        words = self.top_words(n_words) if words is None else np.array(words, dtype=np.int32, ndmin=2)
+        if words.ndim != 2:
+            raise ValueError('words must be a (groups, words per group) array')
+        eng = RRIEngine(1, 1, 1, dtype=np.float64, weighted=False, device=self.nmf_kwargs.get('device', 0))
+        try:        # the handle gives the device and the stream: it holds nothing of the corpus's size
+            df, codf = eng.cooccurrence_counts(A, words)
+        finally:
+            eng.close()
+        N = int(A.shape[0])
+        a, b = np.triu_indices(words.shape[1], 1)
+        is_pair = (words[:, a] >= 0) & (words[:, b] >= 0)
+        Da, Db, Dab = (np.asarray(v, dtype=np.float64) for v in (df[:, a], df[:, b], codf[:, a, b]))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            if measure == 'umass':
+                defined = is_pair & (Da > 0)
+                val = np.log((Dab + eps) / Da)
+            elif measure == 'pmi':
+                defined = is_pair & (Da * Db > 0)
+                val = np.log((Dab + eps) * N / (Da * Db))
+            else:
+                defined = is_pair & (Da * Db > 0)
+                val = np.log((Dab / N) / ((Da / N) * (Db / N))) / -np.log(Dab / N)
+                val = np.where(Dab == 0, -1.0, np.where(Dab == N, 1.0, val))
+            count = defined.sum(axis=1)
+            per_topic = np.where(count > 0, np.where(defined, val, 0.0).sum(axis=1) / count, np.nan)
+        used = words[words >= 0]
+        return {'measure': measure, 'per_topic': per_topic,
+                'mean': float(np.nanmean(per_topic)) if np.any(count > 0) else float('nan'),
+                'words': words, 'df': df, 'codf': codf, 'documents': N,
+                'pairs_undefined': (is_pair & ~defined).sum(axis=1),
+                'diversity': float(np.unique(used).size) / used.size if used.size else float('nan')}
