@@ -302,6 +302,29 @@ rri_status rri_cooccurrence_counts(rri_ctx* ctx, const int64_t* indptr, const in
                                    int64_t n_rows, int64_t n_cols,
                                    const int32_t* words, int32_t n_groups, int32_t group_size,
                                    int64_t* df_out, int64_t* codf_out);
+/* The log-likelihood of stored counts under the rows of W T: what the held-out perplexity of a topic model is computed from.
+ * A call has `count` requests.  Request q has a row i = rows[q] of W (rows NULL: i = q, so count <= n; duplicates allowed, any
+ * order) and a segment of a CSR matrix WITH values: indices[indptr[q] .. indptr[q + 1]) and values[...], the columns strictly
+ * ascending inside [0, d), the values finite and >= 0; indptr has count + 1 entries, from 0, monotone.  For entry e of the segment,
+ * with column j and value v:  p_e = sum_t W[i,t] T[t,j] in float64;  term_e = 0 exactly when v == 0, else
+ * v * log(p_e < floor ? floor : p_e) -- a NaN p_e stays NaN, and with floor == 0 and p_e == 0 the term is -inf.
+ *   ll_out[q]       sum_e term_e
+ *   mass_out[q]     sum_e v
+ *   floored_out[q]  the number of entries with v > 0 and p_e < floor
+ * Every sum is taken in an order that depends on k and on the request's own segment only: a request scored alone and among
+ * others returns the same bits, and so do two calls.  Nothing is scaled: when every row of W T is a distribution, ll is a
+ * log-likelihood.
+ * Blocking.  Reads the handle's current W and T (both must be set; a factors-only handle will do, every flavour and storage
+ * type), writes nothing a later sweep reads and keeps no buffer (rri_device_memory is what it was); on a row-sharded handle the
+ * rows are local and the call is not collective.  The entries travel in chunks of whole requests of at most 64 MiB at 12 bytes
+ * per entry.  The request is checked before any HIP call.
+ * RRI_ERR_INVALID: a NULL handle, indptr or output, NULL indices or values with entries present, indptr not from 0 or not
+ * monotone, a column out of range or not strictly ascending, a negative, NaN or infinite value, a row out of range, count < 0,
+ * a negative, NaN or infinite floor, W or T not set; RRI_ERR_UNSUPPORTED: 12 d > 64 MiB (a full row would not fit a chunk);
+ * count == 0 or no entry at all: RRI_OK, the outputs zeroed, nothing launched. */
+rri_status rri_entries_loglik(rri_ctx* ctx, const int64_t* rows, int64_t count,
+                              const int64_t* indptr, const int32_t* indices, const double* values,
+                              double floor, double* ll_out, double* mass_out, int64_t* floored_out);
 /* device-side copy of (W,T) for the early-stop rollback of nmf.py:360-363,393-407 */
 rri_status rri_snapshot(rri_ctx* ctx);
 rri_status rri_rollback(rri_ctx* ctx);
@@ -461,7 +484,9 @@ rri_status rri_objective_parts(rri_ctx* ctx, double out[3]);
  * 3 = rank-one residual update (explicit-residual / WRRI flavour); on an RRI_UNWEIGHTED_SPARSE handle with uniform rows: the
  *     launch that adds their share after every X pass (also inside the bracket of id 0),
  * 4 = the launch of rri_topn_rows, 5 = the launch of rri_rank_entries,
- * 6 = the launches of rri_cooccurrence_counts: two per row chunk (masks, then counts), each in a bracket of its own. */
+ * 6 = the launches of rri_cooccurrence_counts: two per row chunk (masks, then counts), each in a bracket of its own,
+ * 7 = the launches of rri_entries_loglik: the transposed copy of T once per call, then two per chunk of requests (entries, then
+ *     the sum over a request's pieces), each in a bracket of its own. */
 /* on = 0: off; on = N > 0: bracket every N-th launch of each kernel id with an event pair (N = 1: all).
  * An event record costs a bubble of a few microseconds on the stream, so sample when the timed region is
  * also the throughput measurement. */

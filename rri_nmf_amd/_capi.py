@@ -86,6 +86,8 @@ PROTOTYPES = {
                                 _D, _D, C.POINTER(_I32), C.POINTER(_D), C.POINTER(_I32)]),
     'rri_cooccurrence_counts': (_I32, [_P, C.POINTER(_I64), C.POINTER(_I32), _I64, _I64, C.POINTER(_I32), _I32, _I32,
                                        C.POINTER(_I64), C.POINTER(_I64)]),
+    'rri_entries_loglik': (_I32, [_P, C.POINTER(_I64), _I64, C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_D), _D,
+                                  C.POINTER(_D), C.POINTER(_D), C.POINTER(_I64)]),
     'rri_residual_rebuild': (_I32, [_P]),
     'rri_residual_update': (_I32, [_P] + [C.POINTER(_D)] * 8),
     'rri_get_residual': (_I32, [_P, _P, _I64, _I32]),

@@ -43,6 +43,7 @@
 #include "rri_topn_kernels.hpp"
 #include "rri_rank_kernels.hpp"
 #include "rri_cooc_kernels.hpp"
+#include "rri_loglik_kernels.hpp"
 
 using namespace rri;
 
@@ -297,8 +298,8 @@ struct rri_ctx {
     long onchip_fallbacks = 0;
 
     int timing = 0;            // 0 off, N > 0: time every N-th launch of each kernel id
-    long timing_seq[7] = {0, 0, 0, 0, 0, 0, 0};   // kernel ids of rri_timing_read
-    std::vector<TimedLaunch> timed[7];
+    long timing_seq[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // kernel ids of rri_timing_read
+    std::vector<TimedLaunch> timed[8];
     std::vector<hipEvent_t> event_pool;
 
     std::string err;
@@ -1290,6 +1291,47 @@ struct LK {  // float64-only kernels
                 case 4: count(std::integral_constant<int, 4>()); break;
                 default: count(std::integral_constant<int, 9>()); break;
             }
+        }
+        return hipGetLastError();
+    }
+    // the transposed copy of T that k_loglik_entries reads: Tt (d x kp), the pad column of an odd k zero
+    static hipError_t loglik_transpose(rri_ctx* c, double* Tt) {
+        const int kp = loglik_kp(c->k);
+        const i64 total = (i64)c->k * c->d;
+        TimedScope ts(c, 7);
+        if (kp != c->k) {
+            const hipError_t e = hipMemsetAsync(Tt, 0, (size_t)c->d * kp * sizeof(double), c->stream);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((k_convert2d<double, double, true>), dim3((unsigned)std::min<i64>(4096, (total + 255) / 256)),
+                           dim3(256), 0, c->stream, (const double*)c->T, c->LD, Tt, (i64)kp, (i64)c->k, c->d);
+        return hipGetLastError();
+    }
+    // the partials of a chunk's pieces and their sums per request (rri_loglik_kernels.hpp); reads W, Tt and the call's
+    // temporaries, writes the partials and the chunk's three outputs only
+    static hipError_t loglik_chunk(rri_ctx* c, const double* Tt, const i64* rows, i64 q0, i64 nreq, const LoglikPiece* pieces,
+                                   i64 npieces, const i64* first, const int* indices, const double* values, double floor,
+                                   double* pll, double* pmass, i64* pfl, double* ll, double* mass, i64* fl) {
+        const size_t lds = 4 * (size_t)loglik_kp(c->k) * sizeof(double);
+        {
+            TimedScope ts(c, 7);
+            const dim3 grid((unsigned)((npieces + 3) / 4));
+            auto entries = [&](auto lanes) {
+                hipLaunchKernelGGL(k_loglik_entries<decltype(lanes)::value>, grid, dim3(256), lds, c->stream, (const double*)c->W,
+                                   c->ldw, Tt, c->k, rows, q0, pieces, npieces, indices, values, floor, pll, pmass, pfl);
+            };
+            switch (loglik_lanes(c->k)) {
+                case 4: entries(std::integral_constant<int, 4>()); break;
+                case 16: entries(std::integral_constant<int, 16>()); break;
+                default: entries(std::integral_constant<int, 64>()); break;      // a measurement build (-DRRI_LOGLIK_LANES=64) only
+            }
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        {
+            TimedScope ts(c, 7);
+            hipLaunchKernelGGL(k_loglik_sum, dim3((unsigned)((nreq + 255) / 256)), dim3(256), 0, c->stream, first, nreq,
+                               (const double*)pll, (const double*)pmass, (const i64*)pfl, ll, mass, fl);
         }
         return hipGetLastError();
     }
@@ -2456,7 +2498,7 @@ rri_status rri_destroy(rri_ctx* c) {
         (void)hipFree(o.p);
         dev_count(-1, o.bytes);
     }
-    for (int i = 0; i < 7; ++i)
+    for (int i = 0; i < 8; ++i)
         for (auto& tl : c->timed[i]) { (void)hipEventDestroy(tl.a); (void)hipEventDestroy(tl.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -3419,6 +3461,76 @@ rri_status rri_cooccurrence_counts(rri_ctx* c, const int64_t* indptr, const int3
     if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "co-occurrence counts failed: %s", hipGetErrorString(e));
     for (size_t g = 0; g < (size_t)n_groups; ++g)
         for (size_t a = 0; a < M; ++a) df_out[g * M + a] = codf_out[(g * M + a) * M + a];
+    return RRI_OK;
+}
+
+// The log-likelihood of stored counts under the rows of W T (rri_loglik.hpp has the semantics).  Reads the handle's W and T; the
+// transposed copy of T, the row list, the entries of a chunk, its pieces, their partials and the outputs live in temporaries of
+// the call, sized for the largest chunk and reused by the next one, so no sum a later sweep reads is touched and
+// rri_device_memory reports what it reported before.  Rank-local on a row-sharded handle: no collective.  The request is
+// checked before any HIP call.
+rri_status rri_entries_loglik(rri_ctx* c, const int64_t* rows, int64_t count, const int64_t* indptr, const int32_t* indices,
+                              const double* values, double floor, double* ll_out, double* mass_out, int64_t* floored_out) {
+    CHECK_CTX(c);
+    char why[200] = "";
+    const int bad = loglik_check_request(c->n, c->d, rows, count, indptr, indices, values, floor, ll_out, mass_out, floored_out, why, sizeof why);
+    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+    if (count == 0) return RRI_OK;
+    std::fill(ll_out, ll_out + count, 0.0);
+    std::fill(mass_out, mass_out + count, 0.0);
+    std::fill(floored_out, floored_out + count, (int64_t)0);
+    if (indptr[count] == 0) return RRI_OK;
+    if (!c->have_W || !c->have_T) return fail(c, RRI_ERR_INVALID, "W and T must be set first");
+    std::vector<LoglikChunk> chunks;
+    loglik_cut_chunks(indptr, count, LL_UPLOAD_BUDGET, &chunks);
+    i64 req_max = 0, ent_max = 0, pc_max = 0;
+    for (const LoglikChunk& ch : chunks) {
+        req_max = std::max<i64>(req_max, ch.q1 - ch.q0);
+        ent_max = std::max<i64>(ent_max, indptr[ch.q1] - indptr[ch.q0]);
+        pc_max = std::max<i64>(pc_max, loglik_cut_pieces(indptr, ch.q0, ch.q1, nullptr, nullptr));
+    }
+    if (req_max > 0x7fffffffLL) return fail(c, RRI_ERR_INVALID, "count %lld is too large for one call", (long long)count);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int kp = loglik_kp(c->k);
+    DevTmp tTt, trows, tpc, tfirst, tidx, tval, tpl, tpm, tpf, tll, tms, tfl;
+    HIPCHK(c, tTt.alloc((size_t)c->d * kp * sizeof(double)));
+    if (rows) HIPCHK(c, trows.alloc((size_t)req_max * sizeof(i64)));
+    HIPCHK(c, tpc.alloc((size_t)pc_max * sizeof(LoglikPiece)));
+    HIPCHK(c, tfirst.alloc((size_t)(req_max + 1) * sizeof(i64)));
+    HIPCHK(c, tidx.alloc((size_t)ent_max * sizeof(int)));
+    HIPCHK(c, tval.alloc((size_t)ent_max * sizeof(double)));
+    HIPCHK(c, tpl.alloc((size_t)pc_max * sizeof(double)));
+    HIPCHK(c, tpm.alloc((size_t)pc_max * sizeof(double)));
+    HIPCHK(c, tpf.alloc((size_t)pc_max * sizeof(i64)));
+    HIPCHK(c, tll.alloc((size_t)req_max * sizeof(double)));
+    HIPCHK(c, tms.alloc((size_t)req_max * sizeof(double)));
+    HIPCHK(c, tfl.alloc((size_t)req_max * sizeof(i64)));
+    hipError_t e = LK::loglik_transpose(c, (double*)tTt.p);
+    std::vector<LoglikPiece> pieces((size_t)pc_max);
+    std::vector<int64_t> first((size_t)req_max + 1);
+    for (size_t i = 0; i < chunks.size() && e == hipSuccess; ++i) {
+        const i64 q0 = chunks[i].q0, nreq = chunks[i].q1 - q0, e0 = indptr[q0], nent = indptr[chunks[i].q1] - e0;
+        if (nent == 0) continue;                                // only requests without entries: their outputs are 0 already
+        const i64 npieces = loglik_cut_pieces(indptr, q0, chunks[i].q1, pieces.data(), first.data());
+        if (rows) e = hipMemcpyAsync(trows.p, rows + q0, (size_t)nreq * sizeof(i64), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(tpc.p, pieces.data(), (size_t)npieces * sizeof(LoglikPiece), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(tfirst.p, first.data(), (size_t)(nreq + 1) * sizeof(i64), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(tidx.p, indices + e0, (size_t)nent * sizeof(int), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(tval.p, values + e0, (size_t)nent * sizeof(double), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess)
+            e = LK::loglik_chunk(c, (const double*)tTt.p, (const i64*)trows.p, q0, nreq, (const LoglikPiece*)tpc.p, npieces,
+                                 (const i64*)tfirst.p, (const int*)tidx.p, (const double*)tval.p, floor, (double*)tpl.p,
+                                 (double*)tpm.p, (i64*)tpf.p, (double*)tll.p, (double*)tms.p, (i64*)tfl.p);
+        if (e == hipSuccess) e = hipMemcpyAsync(ll_out + q0, tll.p, (size_t)nreq * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(mass_out + q0, tms.p, (size_t)nreq * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(floored_out + q0, tfl.p, (size_t)nreq * sizeof(i64), hipMemcpyDeviceToHost, c->stream);
+        // the pieces (host memory that the next chunk rewrites) have been read, and the temporaries are free for the next chunk
+        const hipError_t es = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = es;
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "entries log-likelihood failed: %s", hipGetErrorString(e));
     return RRI_OK;
 }
 
@@ -4408,13 +4520,13 @@ rri_status rri_onchip_fallbacks(rri_ctx* c, int64_t* fallbacks) {
 rri_status rri_timing_enable(rri_ctx* c, int32_t on) {
     CHECK_CTX(c);
     c->timing = on < 0 ? 0 : on;
-    for (int i = 0; i < 7; ++i) c->timing_seq[i] = 0;
+    for (int i = 0; i < 8; ++i) c->timing_seq[i] = 0;
     return RRI_OK;
 }
 
 rri_status rri_timing_read(rri_ctx* c, int32_t id, int64_t* launches, double* total_ms) {
     CHECK_CTX(c);
-    if (id < 0 || id > 6) return fail(c, RRI_ERR_INVALID, "kernel_id out of range");
+    if (id < 0 || id > 7) return fail(c, RRI_ERR_INVALID, "kernel_id out of range");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     double tot = 0.0;

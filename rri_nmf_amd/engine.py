@@ -552,6 +552,40 @@ class RRIEngine(object):
                                                       codf.ctypes.data_as(I64P)))
         return df, codf
 
+    def entries_loglik(self, rows, A, floor=0.0):
+        """The log-likelihood of stored counts under the rows of W T, summed per request on the device (rri_entries_loglik).  A is
+        a scipy sparse matrix with one row per REQUESTED row of W (rows None: all n) and d columns; its stored values are the
+        counts, finite and >= 0.  Returns (ll float64 (m,), mass float64 (m,), floored int64 (m,)): for request q with row i and
+        the stored entries (j, v) of row q of A, ll = sum v log(max(p, floor)) with p = (W T)[i, j], an entry with v == 0 adding
+        exactly 0; mass = sum v; floored the number of entries with v > 0 and p < floor.  Explicit zeros are kept.  A is sorted and
+        its duplicates summed on a copy when it is not canonical, and copied only where its arrays do not have the dtypes the
+        library reads; the caller's matrix stays as it is.  Reads the handle's current factors and changes nothing; a request
+        returns the same bits alone and among others; row-sharded: local rows, no collective."""
+        import scipy.sparse as sp
+        if rows is None:
+            m, rows_p = self.n, None
+        else:
+            rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
+            m, rows_p = rows.size, rows.ctypes.data_as(C.POINTER(C.c_int64))
+        if not sp.isspmatrix_csr(A):
+            A = sp.csr_matrix(A)
+        if A.shape != (m, self.d):
+            raise ValueError('A must have one row per requested row and d columns: %r, not %r' % ((m, self.d), A.shape))
+        if not A.has_canonical_format:
+            A = A.copy()
+            A.sum_duplicates()                          # sorts the rows as well; explicit zeros stay
+        indptr = np.ascontiguousarray(A.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(A.indices, dtype=np.int32)
+        values = np.ascontiguousarray(A.data, dtype=np.float64)
+        ll = np.zeros(m, dtype=np.float64)
+        mass = np.zeros(m, dtype=np.float64)
+        floored = np.zeros(m, dtype=np.int64)
+        I64P, I32P, DP = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._check(self._lib.rri_entries_loglik(self._h, rows_p, m, indptr.ctypes.data_as(I64P), indices.ctypes.data_as(I32P),
+                                                 values.ctypes.data_as(DP), float(floor), ll.ctypes.data_as(DP),
+                                                 mass.ctypes.data_as(DP), floored.ctypes.data_as(I64P)))
+        return ll, mass, floored
+
     def snapshot(self):
         self._check(self._lib.rri_snapshot(self._h))
 

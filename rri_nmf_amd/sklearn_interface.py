@@ -556,3 +556,76 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
                 'words': words, 'df': df, 'codf': codf, 'documents': N,
                 'pairs_undefined': (is_pair & ~defined).sum(axis=1),
                 'diversity': float(np.unique(used).size) / used.size if used.size else float('nan')}
+
+    def log_likelihood(self, X, W=None, floor=1e-12):
+        """The log-likelihood of the term counts X (n' x d, any number of documents) under the fitted topics: a dict.
+
+        Document i is scored under the distribution p_i = W[i, :] T / Z_i over the dictionary, Z_i = sum_t W[i, t] sum_j T[t, j]
+        being formed on the host so that every row of W T sums to one (a fitted model has Z_i = 1 up to rounding; a row with
+        Z_i == 0 is left as it is, so all its entries are floored).  W is self.transform(X) when None, else the given n' x k
+        weights, and no fold-in runs.  X is scipy sparse, or dense -- which is converted to CSR on the host first, the slow way
+        in; its stored values are the counts as given (no tf-idf, no normalisation), finite and >= 0.  The sums
+        sum_j X[i, j] log(max(p_ij, floor)) over the stored entries are taken on the device (rri_entries_loglik), so nothing of
+        size n' x d exists anywhere; there is no host route for them: without a GPU the call raises RRIHipUnavailable.
+
+        Returns per_document (n',), tokens (n',: the sum of a document's counts), floored (n',: its entries with a positive
+        count whose p lies below floor), log_likelihood (the sum of per_document), per_token (that over the sum of tokens),
+        perplexity = exp(-per_token), floor and documents (n').  Without any token per_token and perplexity are NaN."""
+        if np.ndim(self.T) != 2:
+            raise ValueError('the estimator is not fitted: it has no T')
+        k, d = np.shape(self.T)
+        A = X.tocsr() if sp.issparse(X) else sp.csr_matrix(np.asarray(X))
+        if A.shape[1] != d:
+            raise ValueError('X must have the %d columns of T, not %d' % (d, A.shape[1]))
+        if W is None:
+            W = self.transform(X)
+        W = W.toarray() if sp.issparse(W) else np.asarray(W, dtype=np.float64)
+        if W.shape != (A.shape[0], k):
+            raise ValueError('W must be %r, one row per document of X, not %r' % ((A.shape[0], k), W.shape))
+        T = self.T.toarray() if sp.issparse(self.T) else np.asarray(self.T, dtype=np.float64)
+        Z = W.dot(T.sum(axis=1))
+        W = W / np.where(Z == 0, 1.0, Z)[:, None]
+        n = int(A.shape[0])
+        if n == 0:
+            ll, mass, floored = np.zeros(0), np.zeros(0), np.zeros(0, dtype=np.int64)
+        else:
+            eng = RRIEngine(n, d, k, dtype=np.float64, device=self.nmf_kwargs.get('device', 0))
+            try:        # a factors-only handle: it holds W and T and nothing of the corpus's size
+                eng.set_W(W)
+                eng.set_T(T)
+                ll, mass, floored = eng.entries_loglik(None, A, floor)
+            finally:
+                eng.close()
+        total, tokens = float(ll.sum()), float(mass.sum())
+        per_token = total / tokens if tokens > 0 else float('nan')
+        return {'per_document': ll, 'tokens': mass, 'floored': floored, 'log_likelihood': total, 'per_token': per_token,
+                'perplexity': float(np.exp(-per_token)), 'floor': float(floor), 'documents': n}
+
+    def perplexity(self, X, observed=None, floor=1e-12):
+        """exp(-log-likelihood per token) of the counts X under the fitted topics: log_likelihood(X, W, floor)['perplexity'] with
+        W = self.transform(observed if observed is not None else X).  With `observed` (n' x d, the same documents) this is document
+        completion: fold in on one part of each document's tokens and score the other (split_counts makes the two parts).  A
+        model that spreads every document evenly over the dictionary has perplexity d."""
+        return self.log_likelihood(X, W=self.transform(observed if observed is not None else X), floor=floor)['perplexity']
+
+
+def split_counts(X, held_out=0.5, random_state=0):
+    """Thin the integer counts X (n x d, scipy sparse or dense) binomially into (observed, held), two CSR matrices with
+    observed + held == X: every token of a stored count goes to `held` with probability held_out, independently, so
+    held = binomial(x, held_out) entry by entry (vectorised over the stored values, on the host).  For document completion:
+    NMF_TM_Estimator.perplexity(held, observed=observed).  Explicit zeros are dropped from both parts.  ValueError for values
+    that are negative or not whole numbers, or for a held_out outside (0, 1)."""
+    if not 0.0 < held_out < 1.0:
+        raise ValueError('held_out must lie inside (0, 1), not %r' % (held_out,))
+    A = sp.csr_matrix(X, copy=True)
+    A.sum_duplicates()
+    x = np.asarray(A.data)
+    if x.size and (not np.all(np.isfinite(x)) or np.any(x < 0) or np.any(x != np.floor(x))):
+        raise ValueError('split_counts needs counts: non-negative whole numbers')
+    rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+    h = rs.binomial(x.astype(np.int64), held_out).astype(A.dtype)
+    held = sp.csr_matrix((h, A.indices.copy(), A.indptr.copy()), shape=A.shape)
+    observed = sp.csr_matrix((x - h, A.indices.copy(), A.indptr.copy()), shape=A.shape)
+    held.eliminate_zeros()
+    observed.eliminate_zeros()
+    return observed, held
