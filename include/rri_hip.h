@@ -478,6 +478,33 @@ rri_status rri_poll(rri_ctx* ctx);
  * out[1] = sum W^2, out[2] = sum |W| (local rows); T terms are replicated. */
 rri_status rri_objective_parts(rri_ctx* ctx, double out[3]);
 
+/* ---- rows that left the device, kept as frozen statistics (online fits; rri_frozen.hpp) ---- */
+/* A T-row step sees the rows of X and W only through the sums a row-sharded run all-reduces.  Rows O whose W no longer changes
+ * are therefore replaced by B = W_O^T X_O (k x d, row-major), A = W_O^T W_O (k x k), s = 1^T W_O (k) and c = ||X_O||^2, all
+ * float64: one more rank that never moves.  While statistics are set, every T-row step and every column check of rri_sweep,
+ * rri_resume, rri_update_T_row and rri_topic_reduce_local / rri_topic_finish is that of the stacked problem [X_O; X] in which
+ * the rows W_O are never updated: the statistics are added on the device into the reduce buffer, after the handle's own sums
+ * (the Gram terms into slice 0).  The fused T-row launch of small sizes and the persistent sweep do not have that buffer and
+ * are not taken (rri_onchip_info: eligible = 0; rri_sweep_until: RRI_ERR_UNSUPPORTED); sweeps with T fixed ignore the
+ * statistics; rri_objective and rri_objective_parts[0] add the frozen rows' share 1/2 (c - 2 <B, T> + <A, T T^T>).  A reset
+ * of topic t (rri_apply_reset_max_resid, rri_apply_reset_vectors) zeroes row t of B, row and column t of A and s[t]: W[:,t] = 0
+ * of nmf.py:775 on the frozen rows; only the handle's own rows are reset candidates.
+ * Handles: RRI_UNWEIGHTED with RRI_F32 or RRI_F64 storage, and RRI_UNWEIGHTED_SPARSE without uniform rows.
+ * RRI_ERR_UNSUPPORTED, with nothing changed: weighted handles, RRI_UNWEIGHTED_RESIDUAL, RRI_F16 and RRI_U8, uniform rows, an
+ * attached communicator (and rri_attach_comm while statistics are set); rri_sweep, rri_update_T_row, rri_topic_reduce_local
+ * and rri_topic_finish with fix_W while statistics are set (the W[:,t] *= nt1 of nmf.py:450-452 would have to reach the frozen
+ * rows).  Arguments are checked before any HIP call. */
+/* Sets the statistics: all values finite, B, A, s >= 0, A symmetric, c >= 0; the count of absorbed rows starts from 0.
+ * B == NULL clears them (on any handle) and frees their device memory. */
+rri_status rri_frozen_set(rri_ctx* ctx, const double* B, const double* A, const double* s, double c);
+/* Reads them back; any pointer may be NULL.  RRI_ERR_INVALID when none are set. */
+rri_status rri_frozen_get(rri_ctx* ctx, double* B_out, double* A_out, double* s_out, double* c_out, int64_t* rows_out);
+/* F <- decay F + (W^T X, W^T W, 1^T W, ||X||^2) of the handle's own rows and current W, decay in (0, 1]; from zeros when
+ * nothing is set; the row count grows by n.  W^T X of a dense handle is one pass over X on the float64 matrix cores (k <= 128;
+ * one pass per 128 topics above), of a CSR handle the blocked product behind rri_Xt_times (cost ~ nnz).  No atomics: the same
+ * call on the same state leaves the same bits.  W, T and everything the handle keeps between steps are left as they were. */
+rri_status rri_frozen_absorb(rri_ctx* ctx, double decay);
+
 /* ---- measurement --------------------------------------------------------------- */
 /* HIP-event timing of the streaming kernels on the handle's stream.  kernel_id:
  * 0 = fused X pass (row dots + column sums), 1 = W-column update, 2 = T-row update chain,
@@ -486,7 +513,10 @@ rri_status rri_objective_parts(rri_ctx* ctx, double out[3]);
  * 4 = the launch of rri_topn_rows, 5 = the launch of rri_rank_entries,
  * 6 = the launches of rri_cooccurrence_counts: two per row chunk (masks, then counts), each in a bracket of its own,
  * 7 = the launches of rri_entries_loglik: the transposed copy of T once per call, then two per chunk of requests (entries, then
- *     the sum over a request's pieces), each in a bracket of its own. */
+ *     the sum over a request's pieces), each in a bracket of its own,
+ * 8 = the launches of rri_frozen_absorb: per chunk of topics the panel W^T X and the sum of its row-block partials (CSR: the
+ *     transposed copy of the chunk's columns of W, the blocked product and its accumulation) in one bracket, then W^T W with
+ *     1^T W in a bracket of its own.  (The addend of a handle with frozen statistics sits inside the bracket of id 2.) */
 /* on = 0: off; on = N > 0: bracket every N-th launch of each kernel id with an event pair (N = 1: all).
  * An event record costs a bubble of a few microseconds on the stream, so sample when the timed region is
  * also the throughput measurement. */

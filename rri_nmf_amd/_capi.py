@@ -88,6 +88,9 @@ PROTOTYPES = {
                                        C.POINTER(_I64), C.POINTER(_I64)]),
     'rri_entries_loglik': (_I32, [_P, C.POINTER(_I64), _I64, C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_D), _D,
                                   C.POINTER(_D), C.POINTER(_D), C.POINTER(_I64)]),
+    'rri_frozen_set': (_I32, [_P, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _D]),
+    'rri_frozen_get': (_I32, [_P, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I64)]),
+    'rri_frozen_absorb': (_I32, [_P, _D]),
     'rri_residual_rebuild': (_I32, [_P]),
     'rri_residual_update': (_I32, [_P] + [C.POINTER(_D)] * 8),
     'rri_get_residual': (_I32, [_P, _P, _I64, _I32]),

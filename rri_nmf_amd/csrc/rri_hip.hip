@@ -44,6 +44,7 @@
 #include "rri_rank_kernels.hpp"
 #include "rri_cooc_kernels.hpp"
 #include "rri_loglik_kernels.hpp"
+#include "rri_frozen_kernels.hpp"
 
 using namespace rri;
 
@@ -280,6 +281,13 @@ struct rri_ctx {
     i64 row_offset = 0, n_global = 0;
     double* ctail = nullptr;   // 8 doubles (device): small collectives (column verdicts, objective parts)
     double* cand = nullptr;    // 2 * world doubles (device): candidates of the max-residual reset
+    // rows that left the device, as frozen statistics (rri_frozen.hpp; rri_frozen_set / rri_frozen_absorb): B (k x LD, pad columns
+    // zero), A (k x k), s (k) and two doubles for a column check taken alone, all four allocated together and NULL together.
+    // They are inputs read at the point of use -- added into red after k_reduce, into fztail after k_colsum_tail -- and no cache:
+    // nothing the handle keeps between calls was computed from them
+    double *fzB = nullptr, *fzA = nullptr, *fzs = nullptr, *fztail = nullptr;
+    double fz_c = 0.0;         // ||X_O||^2
+    i64 fz_rows = 0;           // rows absorbed so far (rri_frozen_absorb counts them; rri_frozen_set starts from 0)
     rri_status comm_status = RRI_OK;   // first failure of a collective inside an enqueued sequence (or of a dispatch: f16_unreachable)
 
     // register-resident sweeps (rri_onchip_kernels.hpp): per-workgroup partial arrays and the grid barrier's counter
@@ -298,8 +306,8 @@ struct rri_ctx {
     long onchip_fallbacks = 0;
 
     int timing = 0;            // 0 off, N > 0: time every N-th launch of each kernel id
-    long timing_seq[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // kernel ids of rri_timing_read
-    std::vector<TimedLaunch> timed[8];
+    long timing_seq[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // kernel ids of rri_timing_read
+    std::vector<TimedLaunch> timed[9];
     std::vector<hipEvent_t> event_pool;
 
     std::string err;
@@ -1162,6 +1170,12 @@ struct LK {  // float64-only kernels
     static void wcol(rri_ctx* c, int t, int tn, int sweep) {
         wcol_src<UPDATE, CARRY>(c, t, tn, sweep, (const double*)c->Ypart, c->npanels);
     }
+    // the frozen rows' share of [w_t^T X | w_t^T W, ||w_t||^2, sum W[:,tprev]] into red (tprev < 0: no column check pending)
+    static void frozen_add(rri_ctx* c, int t, int tprev) {
+        if (!c->fzB) return;
+        hipLaunchKernelGGL(k_frozen_add, dim3((unsigned)((c->LD + 255) / 256)), dim3(256), 0, c->stream, c->red, c->LD, c->k, t,
+                           tprev, (const double*)c->fzB, (const double*)c->fzA, (const double*)c->fzs);
+    }
     static void reduce(rri_ctx* c) {
         const int nb = (int)((c->LD + 31) / 32) + GRAM_SLICES;
         hipLaunchKernelGGL(k_reduce, dim3(nb), dim3(1024), 0, c->stream, (const double*)c->Zpart, c->LD, c->nrb,
@@ -1497,6 +1511,15 @@ rri_status to_host(rri_ctx* c, const void* dev, i64 ldd, void* host, i64 ld, int
 // (where no T-row step follows that would carry it).  Row-sharded: the column sum is global, so the local share is
 // all-reduced first (2 doubles) and every rank reaches the same verdict.
 void wcheck_now(rri_ctx* c, int tprev, int sweep, int pos) {
+    if (!c->comm && c->fzB && !c->prm.fix_T) {
+        // frozen rows: the communicator's route with the all-reduce replaced by the addend s[tprev]
+        hipLaunchKernelGGL(k_colsum_tail, dim3(1), dim3(256), 0, c->stream, (const double*)c->Gpart, LK::gpart_rows(c),
+                           c->k, c->fztail, (const DevState*)c->st);
+        hipLaunchKernelGGL(k_frozen_add_tail, dim3(1), dim3(64), 0, c->stream, c->fztail, tprev, (const double*)c->fzs);
+        hipLaunchKernelGGL(k_wcheck_tail, dim3(1), dim3(64), 0, c->stream, (const double*)c->fztail, tprev, sweep, pos,
+                           kparams(c), c->st);
+        return;
+    }
     if (!c->comm) {
         if (c->weighted)
             hipLaunchKernelGGL(k_wcheck_wcol, dim3(1), dim3(256), 0, c->stream, (const double*)c->Gpart, c->nwb256, c->k,
@@ -1534,13 +1557,15 @@ void enqueue_T_half(rri_ctx* c, int sweep, int t, bool standalone) {
     {
         TimedScope ts(c, 2);
         const int chk = c->pending_wcheck ? 1 : 0;
-        if (LK::small(c) && !c->comm) {
+        if (LK::small(c) && !c->comm && !c->fzB && c->sw.trow_fused) {
             LK::trow_small(c, t, chk, c->pending_wcheck_topic, sweep, standalone);
         } else {
             // the one cross-row reduction of a topic step: [w_t^T X | slices of (w_t^T W, ||w_t||^2, sum W[:,t-1])];
-            // row-sharded, the ranks all-reduce it here, on the stream, between the two kernels
+            // row-sharded, the ranks all-reduce it here, on the stream, between the two kernels; frozen rows add
+            // their share at the same place
             LK::reduce(c);
             comm_allreduce(c, c->red, c->LD + (i64)GRAM_SLICES * (c->k + 2));
+            LK::frozen_add(c, t, chk ? c->pending_wcheck_topic : -1);
             LK::trow(c, t, chk, c->pending_wcheck_topic, sweep, standalone);
         }
         c->pending_wcheck = false;
@@ -2082,6 +2107,7 @@ bool onchip_ok(const rri_ctx* c) {
     // process must not cost a long-lived handle the launch-bound speed-up for good); eligibility therefore depends on the clock
     if (c->onchip_off && steady_now_ns() < c->onchip_off_until) return false;
     if (ro_store(c->dtype)) return false;       // the persistent kernel has register layouts for 4- and 8-byte X only
+    if (c->fzB) return false;                   // frozen rows enter through red, which the persistent kernel does not have
     return c->sw.onchip && steady_now_ns() >= g_onchip_backoff_until.load() && !c->weighted && !c->explicit_resid && !c->comm && !c->sparse &&
            !c->prm.fix_W && !c->prm.fix_T && c->ldx % c->VN == 0 && ((uintptr_t)c->X) % 16 == 0 &&
            onchip_shape_ok(c->n, c->LD, c->k, c->dtype == RRI_F32, !LK::light(c), c->n_cu, &g);
@@ -2318,6 +2344,7 @@ rri_switches read_switches() {
     if (const char* e = getenv("RRI_ONCHIP")) sw.onchip = atoi(e) != 0;
     if (const char* e = getenv("RRI_ONCHIP_OBJ")) sw.onchip_obj = atoi(e) != 0;
     if (const char* e = getenv("RRI_WSWEEP")) sw.wsweep = atoi(e) != 0;
+    if (const char* e = getenv("RRI_TROW_SMALL")) sw.trow_fused = atoi(e) != 0;
     if (const char* e = getenv("RRI_OBJ_DIRECT")) sw.obj_direct = atoi(e) != 0;
     if (const char* e = getenv("RRI_WMCORR_COLS")) sw.wmcorr_cols = atoi(e) != 0;
     if (const char* e = getenv("RRI_WNW_MASK")) sw.wnw_mask = atoi(e) != 0;
@@ -2348,6 +2375,41 @@ const char* sparse_data_refusal(const rri_ctx* c) {
     if (ro_store((c)->dtype))                                                                                           \
         return fail((c), RRI_ERR_UNSUPPORTED, "%s is not available on an %s handle (%s stores a dense X that is only read)", what, \
                     dtype_name((c)->dtype), (c)->dtype == RRI_F16 ? "float16" : "uint8")
+
+// ---- frozen rows (rri_frozen.hpp) -----------------------------------------------------------------------------------------
+// W fixed: the W[:,t] *= nt1 of a T-row step stays in the kept column, and would have to reach the frozen rows as well
+const char* const FROZEN_FIX_W_TEXT = "frozen statistics are set and fix_W is: the W[:,t] *= nt1 transfer of a T-row step would have to "
+                                      "reach the frozen rows (clear the statistics, or let W move)";
+bool frozen_fix_W(const rri_ctx* c) { return c->fzB && c->have_params && c->prm.fix_W; }
+// which handles take frozen statistics: unweighted, Gram form, dense float32 / float64 or CSR-resident X without uniform rows, one device
+const char* frozen_refusal(const rri_ctx* c) {
+    if (c->weighted == RRI_WEIGHTED_DENSE || c->weighted == RRI_WEIGHTED_SPARSE) return "a weighted handle sums its rows under a mask: frozen statistics are for unweighted handles";
+    if (c->explicit_resid) return "the explicit-residual schedule keeps R = X - W T of its own rows: frozen statistics need the Gram form";
+    if (ro_store(c->dtype)) return "frozen statistics are not available on an RRI_F16 or RRI_U8 handle";
+    if (c->sparse_x && c->uni_n > 0) return "frozen statistics are not available on a CSR handle with uniform rows";
+    if (c->comm) return "a communicator is attached: frozen statistics are for a handle on one device";
+    return nullptr;
+}
+void frozen_release(rri_ctx* c) {
+    dev_release(c, c->fzB); dev_release(c, c->fzA); dev_release(c, c->fzs); dev_release(c, c->fztail);
+    c->fz_c = 0.0;
+    c->fz_rows = 0;
+}
+// all four or none, zeroed
+hipError_t frozen_alloc(rri_ctx* c) {
+    if (c->fzB) return hipSuccess;
+    hipError_t e = dev_alloc(c, c->fzB, (size_t)c->k * c->LD * sizeof(double), true);
+    if (e == hipSuccess) e = dev_alloc(c, c->fzA, (size_t)c->k * c->k * sizeof(double), true);
+    if (e == hipSuccess) e = dev_alloc(c, c->fzs, (size_t)c->k * sizeof(double), true);
+    if (e == hipSuccess) e = dev_alloc(c, c->fztail, 2 * sizeof(double), true);
+    if (e != hipSuccess) frozen_release(c);
+    return e;
+}
+void frozen_clear_topic_dev(rri_ctx* c, int t) {
+    if (!c->fzB) return;
+    const i64 m = std::max<i64>(c->LD, c->k);
+    hipLaunchKernelGGL(k_frozen_clear, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, c->fzB, c->LD, c->fzA, c->k, c->fzs, t);
+}
 
 rri_status ready(rri_ctx* c) {
     if (!c->have_X || !c->have_W || !c->have_T || !c->have_params)
@@ -2498,7 +2560,7 @@ rri_status rri_destroy(rri_ctx* c) {
         (void)hipFree(o.p);
         dev_count(-1, o.bytes);
     }
-    for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < 9; ++i)
         for (auto& tl : c->timed[i]) { (void)hipEventDestroy(tl.a); (void)hipEventDestroy(tl.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -2890,6 +2952,7 @@ rri_status rri_sweep(rri_ctx* c, int32_t n_sweeps, int32_t* sweeps_done) {
     if (r != RRI_OK) return r;
     if (c->paused) return fail(c, RRI_ERR_INVALID, "a paused run is pending: resolve the event and call rri_resume");
     if (n_sweeps < 0) return fail(c, RRI_ERR_INVALID, "n_sweeps < 0");
+    if (frozen_fix_W(c)) return fail(c, RRI_ERR_UNSUPPORTED, "%s", FROZEN_FIX_W_TEXT);
     c->until.active = false;
     c->run_total = n_sweeps;
     r = clear_halt(c);
@@ -3005,6 +3068,7 @@ rri_status rri_apply_reset_max_resid(rri_ctx* c, int32_t t, int64_t* row_chosen)
     }
     DISPATCH_RO(c, L::reset_row(c));
     LK::reset_commit(c, t);
+    frozen_clear_topic_dev(c, t);      // W[:,t] = 0 (nmf.py:775) reaches the frozen rows: only the handle's rows were candidates
     i64 mi = -1;
     HIPCHK(c, hipMemcpyAsync(&mi, c->itmp, sizeof(i64), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3022,6 +3086,7 @@ rri_status rri_apply_reset_vectors(rri_ctx* c, int32_t t, const double* T_row, c
     if (T_row) HIPCHK(c, hipMemcpyAsync(c->resetT, T_row, (size_t)c->d * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (W_col) HIPCHK(c, hipMemcpyAsync(c->resetW, W_col, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     LK::set_row_col(c, t, T_row ? c->resetT : nullptr, W_col ? c->resetW : nullptr);
+    frozen_clear_topic_dev(c, t);      // the frozen rows get no share of a column drawn anew
     HIPCHK(c, hipStreamSynchronize(c->stream));
     reset_applied(c);
     HIPCHK(c, clear_halt(c) == RRI_OK ? hipSuccess : hipErrorUnknown);
@@ -3044,6 +3109,7 @@ rri_status rri_update_T_row(rri_ctx* c, int32_t t) {
     if (r != RRI_OK) return r;
     if (c->weighted) return fail(c, RRI_ERR_UNSUPPORTED, "half steps are not exposed for the weighted flavour");
     if (t < 0 || t >= c->k) return fail(c, RRI_ERR_INVALID, "topic out of range");
+    if (frozen_fix_W(c)) return fail(c, RRI_ERR_UNSUPPORTED, "%s", FROZEN_FIX_W_TEXT);
     HIPCHK(c, hipSetDevice(c->device));
     c->run_total = 1;
     r = clear_halt(c);
@@ -3235,12 +3301,37 @@ static rri_status objective_terms(rri_ctx* c, double out[3], double* tn) {
     return RRI_OK;
 }
 
-rri_status rri_objective_parts(rri_ctx* c, double out[3]) { return objective_terms(c, out, nullptr); }
+// the frozen rows' share of the stacked objective, 1/2 (c - 2 <B, T> + <A, T T^T>), added to the data term
+static rri_status frozen_objective_add(rri_ctx* c, double* data_term) {
+    if (!c->fzB) return RRI_OK;
+    const int k = c->k;
+    DevTmp tt, part;
+    HIPCHK(c, tt.alloc((size_t)k * k * sizeof(double)));
+    HIPCHK(c, part.alloc(256 * sizeof(double)));
+    hipLaunchKernelGGL(k_gram, dim3(k, k), dim3(256), 0, c->stream, (const double*)c->T, c->LD, c->d, k, (double*)tt.p);
+    hipLaunchKernelGGL(k_frozen_dot, dim3(256), dim3(256), 0, c->stream, (const double*)c->fzB, (const double*)c->T, (i64)k * c->LD,
+                       (double*)part.p);
+    std::vector<double> hA((size_t)k * k), hT((size_t)k * k);
+    double hp[256];
+    HIPCHK(c, hipMemcpyAsync(hA.data(), c->fzA, hA.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hT.data(), tt.p, hT.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hp, part.p, sizeof hp, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double bt = 0.0;
+    for (int b = 0; b < 256; ++b) bt += hp[b];
+    *data_term += frozen_objective_share(k, hA.data(), hT.data(), bt, c->fz_c);
+    return RRI_OK;
+}
+
+rri_status rri_objective_parts(rri_ctx* c, double out[3]) {
+    const rri_status r = objective_terms(c, out, nullptr);
+    return r == RRI_OK ? frozen_objective_add(c, &out[0]) : r;
+}
 
 rri_status rri_objective(rri_ctx* c, double* out) {
     CHECK_CTX(c);
     if (!out) return fail(c, RRI_ERR_INVALID, "out is NULL");
-    if (c->obj_track_valid && c->xy_valid && !c->weighted && !c->comm && !c->sw.obj_direct) {
+    if (c->obj_track_valid && c->xy_valid && !c->weighted && !c->comm && !c->sw.obj_direct && !c->fzB) {
         // the persistent sweep that has just ended left its objective (all terms but the constant): nothing to launch
         if (!c->have_X || !c->have_W || !c->have_T) return fail(c, RRI_ERR_INVALID, "X, W, T must be set");
         HIPCHK(c, hipSetDevice(c->device));
@@ -3251,6 +3342,8 @@ rri_status rri_objective(rri_ctx* c, double* out) {
     }
     double parts[3], nt[3];
     rri_status r = objective_terms(c, parts, nt);
+    if (r != RRI_OK) return r;
+    r = frozen_objective_add(c, &parts[0]);
     if (r != RRI_OK) return r;
     r = comm_allreduce_host(c, parts, 3);    // row-sharded: the terms over rows are sums over the ranks; T is replicated
     if (r != RRI_OK) return r;
@@ -4211,6 +4304,7 @@ rri_status rri_topic_reduce_local(rri_ctx* c, int32_t t) {
     if (c->explicit_resid) return fail(c, RRI_ERR_UNSUPPORTED, "row-sharded stepping runs the Gram-form schedule only");
     if (c->comm) return fail(c, RRI_ERR_INVALID, "a communicator is attached: rri_sweep does the collectives itself");
     if (t < 0 || t >= c->k) return fail(c, RRI_ERR_INVALID, "topic out of range");
+    if (frozen_fix_W(c)) return fail(c, RRI_ERR_UNSUPPORTED, "%s", FROZEN_FIX_W_TEXT);
     HIPCHK(c, hipSetDevice(c->device));
     if (c->weighted) {
         // red = [a (LD) | nw (LD) | sum and negative-denominator flag of the last updated column]
@@ -4234,6 +4328,7 @@ rri_status rri_topic_reduce_local(rri_ctx* c, int32_t t) {
         if (pend) return fail(c, RRI_ERR_INVALID, "carry lost while a sharded column check was pending");
     }
     LK::reduce(c);
+    LK::frozen_add(c, t, c->pending_wcheck ? c->pending_wcheck_topic : -1);
     return RRI_OK;
 }
 
@@ -4257,6 +4352,7 @@ rri_status rri_reduce_write(rri_ctx* c, const double* in, int64_t count) {
 
 rri_status rri_topic_finish(rri_ctx* c, int32_t t) {
     CHECK_CTX(c);
+    if (t >= 0 && frozen_fix_W(c)) return fail(c, RRI_ERR_UNSUPPORTED, "%s", FROZEN_FIX_W_TEXT);
     HIPCHK(c, hipSetDevice(c->device));
     if (c->weighted) {
         if (t >= c->k) return fail(c, RRI_ERR_INVALID, "topic out of range");
@@ -4406,6 +4502,7 @@ rri_status rri_attach_comm(rri_ctx* c, rri_comm* comm, int64_t row_offset, int64
     CHECK_CTX(c);
     if (comm && c->sparse_x) return fail(c, RRI_ERR_UNSUPPORTED, "an RRI_UNWEIGHTED_SPARSE handle is not row-sharded");
     if (comm && ro_store(c->dtype)) return fail(c, RRI_ERR_UNSUPPORTED, "an %s handle is not row-sharded (the combination has no test yet)", dtype_name(c->dtype));
+    if (comm && c->fzB) return fail(c, RRI_ERR_UNSUPPORTED, "frozen statistics are set: clear them before a communicator is attached");
     if (!comm) {              // detach
         c->comm = nullptr;
         c->row_offset = 0;
@@ -4520,13 +4617,13 @@ rri_status rri_onchip_fallbacks(rri_ctx* c, int64_t* fallbacks) {
 rri_status rri_timing_enable(rri_ctx* c, int32_t on) {
     CHECK_CTX(c);
     c->timing = on < 0 ? 0 : on;
-    for (int i = 0; i < 8; ++i) c->timing_seq[i] = 0;
+    for (int i = 0; i < 9; ++i) c->timing_seq[i] = 0;
     return RRI_OK;
 }
 
 rri_status rri_timing_read(rri_ctx* c, int32_t id, int64_t* launches, double* total_ms) {
     CHECK_CTX(c);
-    if (id < 0 || id > 7) return fail(c, RRI_ERR_INVALID, "kernel_id out of range");
+    if (id < 0 || id > 8) return fail(c, RRI_ERR_INVALID, "kernel_id out of range");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     double tot = 0.0;
@@ -4615,6 +4712,132 @@ rri_status rri_bench_rank1_update(rri_ctx* c, int32_t reps, double* avg_ms) {
     changed(c, CH_SCRATCH);
     if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "rank-one bench failed: %s", hipGetErrorString(e));
     if (avg_ms) *avg_ms = ms / reps;
+    return RRI_OK;
+}
+
+// ---- rows that left the device: frozen statistics (rri_frozen.hpp, rri_frozen_kernels.hpp) ---------------------------------
+// None of the three invalidates anything the handle keeps: the statistics are read where a step uses them, and the sums a
+// handle carries between steps (Zpart, Gpart, XYpart) are those of its own rows with or without them.
+rri_status rri_frozen_set(rri_ctx* c, const double* B, const double* A, const double* s, double cval) {
+    CHECK_CTX(c);
+    if (!B) {      // clear
+        (void)hipSetDevice(c->device);
+        if (c->fzB) (void)hipStreamSynchronize(c->stream);      // a step still reading them
+        frozen_release(c);
+        return RRI_OK;
+    }
+    if (const char* why = frozen_refusal(c)) return fail(c, RRI_ERR_UNSUPPORTED, "%s", why);
+    char msg[200] = "";
+    if (frozen_check_stats(c->k, c->d, B, A, s, cval, msg, sizeof msg) != FROZEN_OK) return fail(c, RRI_ERR_INVALID, "%s", msg);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, frozen_alloc(c));
+    HIPCHK(c, hipMemcpy2DAsync(c->fzB, (size_t)c->LD * 8, B, (size_t)c->d * 8, (size_t)c->d * 8, (size_t)c->k, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->fzA, A, (size_t)c->k * c->k * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->fzs, s, (size_t)c->k * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->fz_c = cval;
+    c->fz_rows = 0;
+    return RRI_OK;
+}
+
+rri_status rri_frozen_get(rri_ctx* c, double* B_out, double* A_out, double* s_out, double* c_out, int64_t* rows_out) {
+    CHECK_CTX(c);
+    if (!c->fzB) return fail(c, RRI_ERR_INVALID, "no frozen statistics are set");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (B_out) HIPCHK(c, hipMemcpy2DAsync(B_out, (size_t)c->d * 8, c->fzB, (size_t)c->LD * 8, (size_t)c->d * 8, (size_t)c->k, hipMemcpyDeviceToHost, c->stream));
+    if (A_out) HIPCHK(c, hipMemcpyAsync(A_out, c->fzA, (size_t)c->k * c->k * 8, hipMemcpyDeviceToHost, c->stream));
+    if (s_out) HIPCHK(c, hipMemcpyAsync(s_out, c->fzs, (size_t)c->k * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c_out) *c_out = c->fz_c;
+    if (rows_out) *rows_out = c->fz_rows;
+    return RRI_OK;
+}
+
+// the panel W^T X of the handle's rows into fzB: F <- decay F + W^T X
+static rri_status frozen_absorb_panel(rri_ctx* c, double decay) {
+    const int k = c->k;
+    if (c->sparse_x) {
+        // X on CSR: the blocked store's X^T Q (what rri_Xt_times runs), <= 64 topics per call; Q = the topics' columns of W
+        const rri_ctx::SpCopy& cp = c->sp[1];
+        const i64 brows = (i64)cp.nblk * cp.bw;
+        const int mmax = std::min(k, 64);
+        DevTmp q, part, res;
+        HIPCHK(c, q.alloc((size_t)brows * mmax * sizeof(double)));
+        HIPCHK(c, part.alloc((size_t)cp.nblk * cp.nseg * mmax * sizeof(double)));
+        HIPCHK(c, res.alloc((size_t)cp.nseg * mmax * sizeof(double)));
+        for (int t0 = 0; t0 < k; t0 += 64) {
+            const int m = std::min(64, k - t0);
+            const i64 total = (i64)m * c->n;
+            TimedScope ts(c, 8);
+            HIPCHK(c, hipMemsetAsync(q.p, 0, (size_t)brows * m * sizeof(double), c->stream));
+            hipLaunchKernelGGL((k_convert2d<double, double, true>), dim3((unsigned)std::max<i64>(1, std::min<i64>(4096, (total + 255) / 256))),
+                               dim3(256), 0, c->stream, (const double*)c->W + (i64)t0 * c->ldw, c->ldw, (double*)q.p, (i64)m, (i64)m, c->n);
+            DISPATCH(c, L::sp_spmm(c, 1, (const double*)q.p, m, (double*)part.p, (double*)res.p));
+            hipLaunchKernelGGL(k_frozen_axpy_t, dim3((unsigned)((c->d + 255) / 256), (unsigned)m), dim3(256), 0, c->stream,
+                               (const double*)res.p, m, (int)c->d, t0, decay, c->fzB, c->LD);
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));      // the temporaries go with this scope
+        return RRI_OK;
+    }
+    // dense: row blocks of whole 32-row steps.  Two workgroups fit a CU (128 accumulator registers per lane), and the grid is cut
+    // to at most two full rounds of them -- a handful of workgroups in a third round would cost half a round
+    const int cols_per_wg = std::min(k, FZ_CHUNK) <= 64 ? 256 : 128;
+    const i64 ncb = (c->d + cols_per_wg - 1) / cols_per_wg;
+    const i64 want = std::max<i64>(1, 4 * (i64)std::max(c->n_cu, 1) / ncb);
+    const i64 steps = (c->n + FZ_RCH - 1) / FZ_RCH;
+    const i64 nrb0 = std::max<i64>(1, std::min<i64>(std::min<i64>(want, 64), steps));
+    const int rows_per_block = (int)((steps + nrb0 - 1) / nrb0) * FZ_RCH;
+    const int nrb = (int)((c->n + rows_per_block - 1) / rows_per_block);
+    DevTmp part;
+    HIPCHK(c, part.alloc((size_t)nrb * std::min(k, FZ_CHUNK) * c->LD * sizeof(double)));
+    for (int t0 = 0; t0 < k; t0 += FZ_CHUNK) {
+        const int kc = std::min(FZ_CHUNK, k - t0);
+        TimedScope ts(c, 8);
+        DISPATCH(c, {
+            typedef typename L::Elem SX;
+            if (kc <= 64)
+                hipLaunchKernelGGL((k_wtx_panel<SX, 4, 4>), dim3((unsigned)((c->d + 255) / 256), (unsigned)nrb), dim3(256), 0, c->stream,
+                                   (const SX*)c->X, c->ldx, (int)c->n, (int)c->d, (const double*)c->W, c->ldw, t0, kc, rows_per_block,
+                                   (double*)part.p, c->LD);
+            else
+                hipLaunchKernelGGL((k_wtx_panel<SX, 8, 2>), dim3((unsigned)((c->d + 127) / 128), (unsigned)nrb), dim3(256), 0, c->stream,
+                                   (const SX*)c->X, c->ldx, (int)c->n, (int)c->d, (const double*)c->W, c->ldw, t0, kc, rows_per_block,
+                                   (double*)part.p, c->LD);
+        });
+        hipLaunchKernelGGL(k_panel_sum, dim3((unsigned)((c->d + 255) / 256), (unsigned)kc), dim3(256), 0, c->stream,
+                           (const double*)part.p, nrb, kc, c->LD, (int)c->d, t0, decay, c->fzB);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RRI_OK;
+}
+
+rri_status rri_frozen_absorb(rri_ctx* c, double decay) {
+    CHECK_CTX(c);
+    char msg[200] = "";
+    if (frozen_check_decay(decay, msg, sizeof msg) != FROZEN_OK) return fail(c, RRI_ERR_INVALID, "%s", msg);
+    if (const char* why = frozen_refusal(c)) return fail(c, RRI_ERR_UNSUPPORTED, "%s", why);
+    if (!c->have_X || !c->have_W) return fail(c, RRI_ERR_INVALID, "X and W must be set before their rows are absorbed");
+    HIPCHK(c, hipSetDevice(c->device));
+    rri_status r = ensure_x_sq(c);       // ||X||^2: what the objective keeps per X
+    if (r != RRI_OK) return r;
+    const bool fresh = !c->fzB;
+    HIPCHK(c, frozen_alloc(c));
+    r = frozen_absorb_panel(c, decay);
+    if (r == RRI_OK) {
+        TimedScope ts(c, 8);
+        hipLaunchKernelGGL(k_frozen_gram, dim3(c->k, c->k + 1), dim3(256), 0, c->stream, (const double*)c->W, c->ldw, c->n, c->k, decay,
+                           c->fzA, c->fzs);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (r == RRI_OK && e != hipSuccess) r = fail(c, RRI_ERR_HIP, "absorbing the handle's rows failed: %s", hipGetErrorString(e));
+    if (r == RRI_OK && c->comm_status != RRI_OK) { r = c->comm_status; c->comm_status = RRI_OK; }
+    if (r != RRI_OK) {
+        if (fresh) frozen_release(c);      // (statistics that were set before a failed absorb are no longer theirs: the caller sets them anew)
+        return r;
+    }
+    c->fz_c = decay * c->fz_c + c->x_sq;
+    c->fz_rows += c->n;
     return RRI_OK;
 }
 

@@ -47,6 +47,8 @@ struct rri_switches {
     bool onchip = true;        // RRI_ONCHIP=0: never the register-resident persistent sweep (rri_onchip_kernels.hpp)
     bool onchip_obj = true;    // RRI_ONCHIP_OBJ=0: the persistent sweep does not leave the objective of its last sweep (rri_objective takes the Gram kernels)
     bool wsweep = true;        // RRI_WSWEEP=0: runs with T fixed take the launch-per-topic W half (k_tgram, k_wcol, k_check_wcol per topic)
+    bool trow_fused = true;    // RRI_TROW_SMALL=0: launch-bound sizes keep k_reduce and k_trow_numer apart (never k_trow_small): the route of a
+                               // row-sharded handle and of one with frozen statistics
     bool obj_direct = false;   // RRI_OBJ_DIRECT=1: the objective always through the residual (k_resid)
     bool wmcorr_cols = true;   // RRI_WMCORR_COLS=0: the mask-only correction always walks every bit (k_wmcorr), also on a sparse mask
     bool wnw_mask = true;      // RRI_WNW_MASK=0: the one-pass step keeps taking nw = (w^2)^T M in the read-modify-write pass on a sparse 0/1 mask too

@@ -76,6 +76,53 @@ def check_storage_options(dtype, weighted=False, schedule='gram', sparse_x=False
     return dt
 
 
+class FrozenRows(object):
+    """Rows that left the device, as the sums a T-row step sees of them: B = W_O^T X_O (k, d), A = W_O^T W_O (k, k),
+    s = 1^T W_O (k,), c = ||X_O||^2, and how many rows went in.  Float64 copies; a value, never changed in place:
+    `decay(rho)` scales the four sums (the count stays), `+` adds two sets of rows of the same model."""
+
+    def __init__(self, B, A, s, c, rows=0):
+        self.B = np.array(B, dtype=np.float64, ndmin=2)
+        self.A = np.array(A, dtype=np.float64, ndmin=2)
+        self.s = np.array(s, dtype=np.float64).reshape(-1)
+        self.c = float(c)
+        self.rows = int(rows)
+        k = self.s.size
+        if self.A.shape != (k, k) or self.B.shape[0] != k:
+            raise ValueError('B must be (k, d), A (k, k) and s (k,): got %r, %r, %r' % (self.B.shape, self.A.shape, self.s.shape))
+
+    k = property(lambda self: self.s.size)
+    d = property(lambda self: self.B.shape[1])
+
+    @classmethod
+    def zeros(cls, k, d):
+        return cls(np.zeros((k, d)), np.zeros((k, k)), np.zeros(k), 0.0, 0)
+
+    @classmethod
+    def of(cls, X, W):
+        """the statistics of the rows X (dense or scipy sparse) with the factors W, on the host"""
+        X = X.toarray() if hasattr(X, 'toarray') else np.asarray(X, dtype=np.float64)
+        W = np.asarray(W, dtype=np.float64)
+        return cls(W.T.dot(X), W.T.dot(W), W.sum(0), float((X ** 2).sum()), X.shape[0])
+
+    def decay(self, rho):
+        if not 0.0 < rho <= 1.0:
+            raise ValueError('decay %r is outside (0, 1]' % (rho,))
+        return FrozenRows(rho * self.B, rho * self.A, rho * self.s, rho * self.c, self.rows)
+
+    def __add__(self, other):
+        if not isinstance(other, FrozenRows):
+            return NotImplemented
+        if (self.k, self.d) != (other.k, other.d):
+            raise ValueError('frozen statistics of different shapes: k, d = %r and %r' % ((self.k, self.d), (other.k, other.d)))
+        return FrozenRows(self.B + other.B, self.A + other.A, self.s + other.s, self.c + other.c, self.rows + other.rows)
+
+    def objective_share(self, T):
+        """the frozen rows' share of the stacked objective 1/2 ||X - W T||^2: 1/2 (c - 2 <B, T> + <A, T T^T>)"""
+        T = np.asarray(T, dtype=np.float64)
+        return 0.5 * ((self.c - 2.0 * (self.B * T).sum()) + (self.A * T.dot(T.T)).sum())
+
+
 def device_memory():
     """(buffers, bytes) of the device allocations that the handles of this process own right now (rri_device_memory): bound
     tensors and the temporaries of a call are not counted, and after every close() both are back where they were."""
@@ -585,6 +632,42 @@ class RRIEngine(object):
                                                  values.ctypes.data_as(DP), float(floor), ll.ctypes.data_as(DP),
                                                  mass.ctypes.data_as(DP), floored.ctypes.data_as(I64P)))
         return ll, mass, floored
+
+    # ---- rows that left the device: frozen statistics (online fits) ---------------------------------
+    def set_frozen(self, frozen):
+        """From here on every T-row step and column check of this handle is that of the stacked problem [X_O; X] whose rows O
+        are kept as `frozen` (a FrozenRows: B = W_O^T X_O, A = W_O^T W_O, s = 1^T W_O, c = ||X_O||^2) and never updated
+        (rri_frozen_set).  None clears them.  NotImplementedError on the handles that do not take them (weighted, residual
+        schedule, float16 / uint8, uniform rows, a group attached); ValueError for values that are negative, not finite or, for
+        A, not symmetric."""
+        if frozen is None:
+            return self.clear_frozen()
+        if frozen.k != self.k or frozen.d != self.d:
+            raise ValueError('frozen statistics are for k = %d, d = %d; the handle has k = %d, d = %d' % (frozen.k, frozen.d, self.k, self.d))
+        DP = C.POINTER(C.c_double)
+        B, A, s = (np.ascontiguousarray(a, dtype=np.float64) for a in (frozen.B, frozen.A, frozen.s))
+        self._check(self._lib.rri_frozen_set(self._h, B.ctypes.data_as(DP), A.ctypes.data_as(DP), s.ctypes.data_as(DP), float(frozen.c)))
+        self._frozen_rows0 = int(frozen.rows)
+
+    def clear_frozen(self):
+        """drops the statistics and frees their device memory (rri_frozen_set with B = NULL); harmless when none are set"""
+        self._check(self._lib.rri_frozen_set(self._h, None, None, None, 0.0))
+        self._frozen_rows0 = 0
+
+    def get_frozen(self):
+        """the statistics as the handle holds them (rri_frozen_get): a FrozenRows whose `rows` is the count of the FrozenRows
+        last set plus the rows absorbed since"""
+        B, A, s = np.empty((self.k, self.d)), np.empty((self.k, self.k)), np.empty(self.k)
+        c, rows = C.c_double(0.0), C.c_int64(0)
+        DP = C.POINTER(C.c_double)
+        self._check(self._lib.rri_frozen_get(self._h, B.ctypes.data_as(DP), A.ctypes.data_as(DP), s.ctypes.data_as(DP), C.byref(c), C.byref(rows)))
+        return FrozenRows(B, A, s, float(c.value), getattr(self, '_frozen_rows0', 0) + int(rows.value))
+
+    def absorb(self, decay=1.0):
+        """F <- decay F + (W^T X, W^T W, 1^T W, ||X||^2) of the handle's own rows and current W (rri_frozen_absorb): the rows
+        this handle holds join the frozen ones, from zeros when nothing is set; decay in (0, 1].  W, T and a sweep that follows
+        are unchanged by it, and the same call on the same state leaves the same bits."""
+        self._check(self._lib.rri_frozen_absorb(self._h, float(decay)))
 
     def snapshot(self):
         self._check(self._lib.rri_snapshot(self._h))

@@ -58,7 +58,7 @@ import time
 import numpy as np
 import scipy.sparse
 
-from .engine import RRIEngine, ZeroTotalRows
+from .engine import FrozenRows, RRIEngine, ZeroTotalRows
 from .initialization import initialize_nmf
 from .matrixops import normalize, proj_mat_to_simplex
 from .optimization import universal_stopping_condition
@@ -509,7 +509,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         diagnostics=[], store_gradients=False,
         ind_rows_to_store=None, eps_gauss_t=None, delta_gauss_t=None,
         *, dtype=None, device=0, device_init=None, sparse_pattern=None, preprocess=None, schedule='gram', group=None,
-        resident=None, sparse_X=None, uniform_rows=None):
+        resident=None, frozen=None, sparse_X=None, uniform_rows=None):
     """Non-negative factorisation X ~ W T by rank-one residue iteration; see the module docstring and
     the reference's docstring (nmf.py:109-269) for the parameters.  Returns a dict with 'W', 'T',
     'iter_cputime' (wall seconds since the start, per sweep), 'random_state' and, when the objective
@@ -524,7 +524,31 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     keeps those rows as the dense row 1/d beside its pattern and the matrix stays on the device route (module docstring).  The idf
     used comes back as rtv['idf'].
     resident (keyword only): a ResidentProblem that keeps the device handle -- X uploaded and preprocessed -- from one call to
-    the next on the same problem (see there)."""
+    the next on the same problem (see there).
+    frozen (keyword only): online fits.  A FrozenRows -- rows of earlier batches, kept as the sums B = W_O^T X_O, A = W_O^T W_O,
+    s = 1^T W_O, c = ||X_O||^2 -- is set on the handle after the upload: every T-row step and column check is then that of the
+    stacked problem [X_O; X] whose rows W_O never move, and the objective includes their share.  After the sweep loop, before
+    the final projection of W, this batch's rows are absorbed with the W they have then, and the sum comes back as
+    rtv['frozen'].  True: no rows are frozen yet -- nothing is set, the sweeps are those of a call without the option, the
+    batch is absorbed all the same (the first batch of an online fit).  Unweighted calls in the Gram form with float32 /
+    float64 or CSR storage on one device; no fix_W, w_row, early_stop, store_gradients or Gaussian mechanism."""
+    if frozen is not None:
+        if frozen is not True and not isinstance(frozen, FrozenRows):
+            raise ValueError('frozen must be a FrozenRows, True (absorb this batch, nothing frozen yet) or None')
+        if frozen is not True and (frozen.k != k or frozen.d != np.shape(X)[1]):
+            raise ValueError('frozen statistics are for k = %d, d = %d; this call has k = %d, d = %d'
+                             % (frozen.k, frozen.d, k, np.shape(X)[1]))
+        refused = [name for name, on in (('W_mat', W_mat is not None), ("schedule='residual'", schedule == 'residual'),
+                                         ('dtype=float16', dtype is not None and np.dtype(dtype) == np.float16),
+                                         ('dtype=uint8', dtype is not None and np.dtype(dtype) == np.uint8),
+                                         ('uniform_rows=True', bool(uniform_rows)), ('group=', group is not None),
+                                         ('fix_W', bool(fix_W)), ('w_row', w_row is not None), ('early_stop', bool(early_stop)),
+                                         ('store_gradients', bool(store_gradients)),
+                                         ('the Gaussian mechanism', bool(eps_gauss_t and delta_gauss_t)))
+                   if on]
+        if refused:
+            raise NotImplementedError('frozen= keeps earlier rows as sums beside an unweighted X in the Gram form on one device; '
+                                      'it does not combine with %s' % ', '.join(refused))
     if sparse_X is not None and not isinstance(sparse_X, (bool, np.bool_)):
         raise ValueError('sparse_X must be True, False or None')
     if uniform_rows is not None and not isinstance(uniform_rows, (bool, np.bool_)):
@@ -770,6 +794,8 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
                        t_row_sum=t_row_sum, w_row_sum=w_row_sum, reset_topic_method=reset_topic_method,
                        n_resets=n_resets, reg_w_l1=reg_w_l1, reg_w_l2=reg_w_l2, reg_t_l1=reg_t_l1,
                        reg_t_l2=reg_t_l2, fix_reset_seed=fix_reset_seed)
+        if frozen is not None:
+            eng.set_frozen(None if frozen is True else frozen)
 
         def current():
             return eng.get_W(), eng.get_T()
@@ -894,6 +920,13 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             iter_no += 1
 
         iter_cputime = [c - clock0 for c in iter_cputime]
+
+        if frozen is not None:
+            # this batch's rows join the frozen ones with the W the sweeps left (before the final projection); the handle is
+            # left without statistics, as it was found
+            eng.absorb(1.0)
+            rtv['frozen'] = eng.get_frozen()
+            eng.clear_frozen()
 
         # final row-wise projection of W (nmf.py:519-529)
         if not project_W_each_iter and w_row_sum is not None and not fix_W and do_final_project_W:

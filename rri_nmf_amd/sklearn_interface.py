@@ -445,6 +445,36 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
         self._solve(X, 1, 240)
         return self
 
+    def partial_fit(self, X, y=None, sweeps=3, decay=1.0):
+        """Online fit: one batch of documents joins the model (not in the reference).  The first call initialises from its
+        batch and runs `sweeps` sweeps -- what fit() does with max_iter = sweeps: one partial_fit on all rows from the same
+        start leaves the same W and T bit for bit.  Every later call folds its batch in with the current topics (transform),
+        runs `sweeps` sweeps in which the earlier batches take part as frozen rows (nmf(frozen=): their W no longer moves,
+        they enter every T-row update through their sums `self.frozen_`, scaled by `decay` in (0, 1] first), and absorbs the
+        batch.  self.W is the W of the last batch; with handle_tfidf the idf of the first batch is used throughout, as
+        transform does.  The options nmf(frozen=) refuses in nmf_kwargs are refused here."""
+        assert _all_nonnegative(X), 'X must be non-negative'
+        sweeps = int(sweeps)
+        if sweeps < 1:
+            raise ValueError('sweeps must be >= 1')
+        if not 0.0 < decay <= 1.0:
+            raise ValueError('decay %r is outside (0, 1]' % (decay,))
+        flags = dict(max_iter=sweeps, max_time=7200, project_W_each_iter=False, w_row_sum=1.0, project_T_each_iter=True,
+                     t_row_sum=1.0, do_final_project_W=self.do_final_project_W, reg_w_l1=self.wr1, reg_w_l2=self.wr2,
+                     reg_t_l1=self.tr1, reg_t_l2=self.tr2, random_state=self.random_state)
+        if getattr(self, 'frozen_', None) is None:
+            W_in, T_in = self._warm_start()
+            soln = _nmf(X, self.k, W_in=W_in, T_in=T_in, frozen=True, **dict(self._preprocess_kwargs(), **self.nmf_kwargs), **flags)
+            if self.handle_tfidf:
+                self.idf = soln['idf']
+        else:
+            W_in = self.transform(X)
+            kw = dict(self._preprocess_kwargs(idf=self.idf if self.handle_tfidf else None), **self.nmf_kwargs)
+            soln = _nmf(X, self.k, W_in=W_in, T_in=self.T, frozen=self.frozen_.decay(decay), **kw, **flags)
+        self.frozen_ = soln.pop('frozen')
+        self._keep(soln)
+        return self
+
     def transform(self, Xnew):
         """express Xnew in the fitted topics (4 sweeps over W with T fixed)"""
         soln = _nmf(Xnew, self.k, max_iter=4, max_time=7200, project_W_each_iter=False, w_row_sum=1.0,
