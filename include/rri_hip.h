@@ -325,6 +325,53 @@ rri_status rri_cooccurrence_counts(rri_ctx* ctx, const int64_t* indptr, const in
 rri_status rri_entries_loglik(rri_ctx* ctx, const int64_t* rows, int64_t count,
                               const int64_t* indptr, const int32_t* indices, const double* values,
                               double floor, double* ll_out, double* mass_out, int64_t* floored_out);
+/* ---- a CSR corpus that lives on the device ------------------------------------------------------------------------------------
+ * The evaluation calls above take a sparse corpus from the host on every call; a loop that scores the same corpus after every
+ * batch or sweep pays for the host's canonical copy and the upload each time, and counts that are already in device memory have
+ * to travel to the host and back.  An rri_corpus is that matrix, checked and made canonical ON the device, once.
+ * The raw matrix is n_rows x n_cols with nnz_stored entries: indptr (n_rows + 1 entries) and indices as RRI_I32 or RRI_I64, values
+ * as RRI_F32 or RRI_F64, or NULL for a pattern (every stored entry has the value 1; values_dtype is then not read).  Its rows may
+ * be unsorted, hold a column several times and hold explicit zeros.  It is refused, with the smallest offending position of the
+ * first broken rule in rri_last_error, for: indptr[0] != 0, a decreasing indptr, indptr[n_rows] != nnz_stored, a column outside
+ * [0, n_cols), a NaN or infinite value (all RRI_ERR_INVALID), n_cols >= 2^31 (RRI_ERR_UNSUPPORTED).  The check reads the arrays
+ * by position only and nothing else runs before it has passed: a malformed matrix never becomes an address.
+ * The canonical form: per row the columns ascend strictly, the stored entries of one column are added in float64 in their stored
+ * order, an entry whose sum is exactly 0 is dropped, a float32 value widens exactly; int32 indices, float64 values, int64 indptr.
+ * Two ingests of one matrix give the same bytes.
+ * rri_corpus_create: the handle supplies the device, the stream and the error text and nothing else; the corpus outlives it and
+ * serves every handle on the same device (one on another device: RRI_ERR_INVALID).  on_device = 0: the three arrays are host
+ * memory; they are uploaded as they are and checked and made canonical by the same kernels.  on_device = 1: they are device
+ * pointers on that device, whatever produced them has been synchronised by the caller, they are read during the call and never
+ * kept: the corpus owns its own copy.  Blocking.  RRI_ERR_INVALID also for a NULL handle or output pointer, a negative size, a
+ * NULL indptr, NULL indices with entries present, or an unknown dtype code; RRI_ERR_UNSUPPORTED also for a row of more than 2^30
+ * stored entries that is not canonical already.  On any failure *out is NULL and nothing is kept.
+ * The corpus's buffers are not handle-owned: rri_device_memory does not count them.  rri_corpus_memory is their own counter (the
+ * corpora alive in the process and their device bytes; either pointer may be NULL); the temporaries of an ingest are freed on
+ * every return path. */
+enum { RRI_I32 = 8, RRI_I64 = 9 };     /* dtype codes of the index arrays of rri_corpus_create */
+#define RRI_CORPUS_INFO_FIELDS 10
+typedef struct rri_corpus rri_corpus;  /* opaque */
+rri_status rri_corpus_create(rri_ctx* ctx, rri_corpus** out, int64_t n_rows, int64_t n_cols, int64_t nnz_stored,
+                             const void* indptr, int32_t indptr_dtype, const void* indices, int32_t indices_dtype,
+                             const void* values, int32_t values_dtype, int32_t on_device);
+rri_status rri_corpus_destroy(rri_corpus* corpus);
+/* out[0 .. n): rows, columns, stored entries, canonical entries, rows rewritten (rows that were not strictly ascending without a
+ * stored zero), duplicates merged (stored entries minus distinct columns, per row), zeros dropped (distinct columns whose sum is
+ * 0), negative canonical values, device bytes, long rows (rewritten rows too long for LDS) -- RRI_CORPUS_INFO_FIELDS of them, a
+ * longer out is zero-filled; *ingest_ms (may be NULL): the HIP-event time of the ingest's kernels. */
+rri_status rri_corpus_info(const rri_corpus* corpus, int64_t* out, int32_t n, double* ingest_ms);
+/* the canonical arrays on the host: indptr_out n_rows + 1, indices_out and values_out canonical entries each; any may be NULL */
+rri_status rri_corpus_get(rri_ctx* ctx, const rri_corpus* corpus, int64_t* indptr_out, int32_t* indices_out, double* values_out);
+rri_status rri_corpus_memory(int64_t* corpora, int64_t* bytes);
+/* rri_cooccurrence_counts over the pattern of a resident corpus: the same kernels read the resident arrays, nothing of the
+ * corpus's size is copied, the same counts. */
+rri_status rri_corpus_cooccurrence_counts(rri_ctx* ctx, const rri_corpus* corpus, const int32_t* words, int32_t n_groups,
+                                          int32_t group_size, int64_t* df_out, int64_t* codf_out);
+/* rri_entries_loglik over the whole of a resident corpus: request q is corpus row q, rows is NULL (row q of W) or n_rows rows of
+ * W; the outputs have n_rows entries.  The same bits as rri_entries_loglik on the canonical arrays.  RRI_ERR_INVALID also for a
+ * corpus with negative values or with n_cols != d; RRI_ERR_UNSUPPORTED for 12 d > 64 MiB as there. */
+rri_status rri_corpus_entries_loglik(rri_ctx* ctx, const rri_corpus* corpus, const int64_t* rows, double floor,
+                                     double* ll_out, double* mass_out, int64_t* floored_out);
 /* device-side copy of (W,T) for the early-stop rollback of nmf.py:360-363,393-407 */
 rri_status rri_snapshot(rri_ctx* ctx);
 rri_status rri_rollback(rri_ctx* ctx);

@@ -21,6 +21,8 @@ RRI_ERR_UNBOUNDED, RRI_ERR_W_COL_ZERO, RRI_ERR_NOT_IMPLEMENTED, RRI_ERR_COMM = -
 RRI_COMM_ID_BYTES = 128
 RRI_F32, RRI_F64, RRI_F16 = 0, 1, 2   # RRI_F16: the dense X of an RRI_UNWEIGHTED handle only (include/rri_hip.h)
 RRI_U8 = 4                            # ... and so is RRI_U8: counts 0..255, one byte each, with float64 row and column scales
+RRI_I32, RRI_I64 = 8, 9               # the index arrays of rri_corpus_create
+RRI_CORPUS_INFO_FIELDS = 10           # include/rri_hip.h: what rri_corpus_info fills
 # rri_create's `weighted`: the flavour of the handle
 RRI_UNWEIGHTED, RRI_WEIGHTED_DENSE, RRI_WEIGHTED_SPARSE, RRI_UNWEIGHTED_RESIDUAL, RRI_UNWEIGHTED_SPARSE = 0, 1, 2, 3, 4
 RESET_NONE, RESET_MAX_RESID_DOCUMENT, RESET_RANDOM = 0, 1, 2
@@ -88,6 +90,13 @@ PROTOTYPES = {
                                        C.POINTER(_I64), C.POINTER(_I64)]),
     'rri_entries_loglik': (_I32, [_P, C.POINTER(_I64), _I64, C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_D), _D,
                                   C.POINTER(_D), C.POINTER(_D), C.POINTER(_I64)]),
+    'rri_corpus_create': (_I32, [_P, C.POINTER(_P), _I64, _I64, _I64, _P, _I32, _P, _I32, _P, _I32, _I32]),
+    'rri_corpus_destroy': (_I32, [_P]),
+    'rri_corpus_info': (_I32, [_P, C.POINTER(_I64), _I32, C.POINTER(_D)]),
+    'rri_corpus_get': (_I32, [_P, _P, C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_D)]),
+    'rri_corpus_memory': (_I32, [C.POINTER(_I64), C.POINTER(_I64)]),
+    'rri_corpus_cooccurrence_counts': (_I32, [_P, _P, C.POINTER(_I32), _I32, _I32, C.POINTER(_I64), C.POINTER(_I64)]),
+    'rri_corpus_entries_loglik': (_I32, [_P, _P, C.POINTER(_I64), _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_I64)]),
     'rri_frozen_set': (_I32, [_P, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _D]),
     'rri_frozen_get': (_I32, [_P, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I64)]),
     'rri_frozen_absorb': (_I32, [_P, _D]),

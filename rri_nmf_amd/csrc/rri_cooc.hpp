@@ -38,6 +38,24 @@ RRI_TOPN_FN int cooc_slot(int32_t e) { return (int)(e & 31); }
 // does a row with mask m count for the pair of slots (a, b)?
 RRI_TOPN_FN unsigned cooc_pair(unsigned m, int a, int b) { return (m >> a) & (m >> b) & 1u; }
 
+// the words of a request whose sizes are in range: every one a column or -1, none twice in its group
+inline int cooc_check_words(int64_t n_cols, const int32_t* words, int32_t n_groups, int32_t group_size, char* msg, size_t msg_len) {
+    auto say = [&](int code, const char* what, long long a, long long b) {
+        if (msg && msg_len) snprintf(msg, msg_len, what, a, b);
+        return code;
+    };
+    for (int g = 0; g < n_groups; ++g) {
+        const int32_t* w = words + (size_t)g * group_size;
+        for (int a = 0; a < group_size; ++a) {
+            if (w[a] == -1) continue;
+            if (w[a] < 0 || w[a] >= n_cols) return say(TOPN_REQ_INVALID, "word %lld of group %lld is out of range", (long long)w[a], (long long)g);
+            for (int b = 0; b < a; ++b)
+                if (w[b] == w[a]) return say(TOPN_REQ_INVALID, "word %lld stands twice in group %lld", (long long)w[a], (long long)g);
+        }
+    }
+    return TOPN_REQ_OK;
+}
+
 // ---- a request, checked on the host before anything is copied -------------------------------------------------------------------
 // Returns TOPN_REQ_OK, TOPN_REQ_INVALID or TOPN_REQ_UNSUPPORTED (a group_size or n_groups outside its limits: a shape this
 // library does not count) and writes the first broken rule to msg.
@@ -64,16 +82,22 @@ inline int cooc_check_request(const int64_t* indptr, const int32_t* indices, int
         if (msg && msg_len) snprintf(msg, msg_len, "%s", bad.c_str());
         return TOPN_REQ_INVALID;
     }
-    for (int g = 0; g < n_groups; ++g) {
-        const int32_t* w = words + (size_t)g * group_size;
-        for (int a = 0; a < group_size; ++a) {
-            if (w[a] == -1) continue;
-            if (w[a] < 0 || w[a] >= n_cols) return say(TOPN_REQ_INVALID, "word %lld of group %lld is out of range", (long long)w[a], (long long)g);
-            for (int b = 0; b < a; ++b)
-                if (w[b] == w[a]) return say(TOPN_REQ_INVALID, "word %lld stands twice in group %lld", (long long)w[a], (long long)g);
-        }
-    }
-    return TOPN_REQ_OK;
+    return cooc_check_words(n_cols, words, n_groups, group_size, msg, msg_len);
+}
+// ... and the groups alone, against a corpus that is resident and canonical already (rri_corpus_cooccurrence_counts): the rules
+// of the request above that do not read the pattern, in the same order
+inline int cooc_check_groups(int64_t n_cols, const int32_t* words, int32_t n_groups, int32_t group_size, char* msg, size_t msg_len) {
+    auto say = [&](int code, const char* what, long long a, long long b) {
+        if (msg && msg_len) snprintf(msg, msg_len, what, a, b);
+        return code;
+    };
+    if (n_groups < 0) return say(TOPN_REQ_INVALID, "n_groups %lld is negative", (long long)n_groups, 0);
+    if (group_size < 0) return say(TOPN_REQ_INVALID, "group_size %lld is negative", (long long)group_size, 0);
+    if (group_size < 1 || group_size > RRI_MAX_COOC_WORDS)
+        return say(TOPN_REQ_UNSUPPORTED, "group_size %lld outside 1 .. %lld", (long long)group_size, (long long)RRI_MAX_COOC_WORDS);
+    if (n_groups < 1 || n_groups > RRI_MAX_K) return say(TOPN_REQ_UNSUPPORTED, "n_groups %lld outside 1 .. %lld", (long long)n_groups, (long long)RRI_MAX_K);
+    if (!words) return say(TOPN_REQ_INVALID, "words is NULL", 0, 0);
+    return cooc_check_words(n_cols, words, n_groups, group_size, msg, msg_len);
 }
 
 // ---- the membership table -----------------------------------------------------------------------------------------------------

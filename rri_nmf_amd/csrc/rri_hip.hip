@@ -45,6 +45,7 @@
 #include "rri_cooc_kernels.hpp"
 #include "rri_loglik_kernels.hpp"
 #include "rri_frozen_kernels.hpp"
+#include "rri_corpus_kernels.hpp"
 
 using namespace rri;
 
@@ -3512,17 +3513,15 @@ rri_status rri_rank_entries(rri_ctx* c, const int64_t* rows, int64_t count, cons
 // a later sweep reads, and is not collective (counts of row blocks add).  The pattern, the membership table, the masks of a row
 // chunk and the counts live in temporaries of the call: rri_device_memory reports what it reported before.  The request is
 // checked before the handle and before any HIP call.
-rri_status rri_cooccurrence_counts(rri_ctx* c, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
-                                   const int32_t* words, int32_t n_groups, int32_t group_size, int64_t* df_out, int64_t* codf_out) {
-    char why[200] = "";
-    const int bad = cooc_check_request(indptr, indices, n_rows, n_cols, words, n_groups, group_size, why, sizeof why);
-    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
-    CHECK_CTX(c);
+// what rri_cooccurrence_counts and rri_corpus_cooccurrence_counts share: everything after the request check.  The pattern is the
+// host's (d_indptr NULL: uploaded into temporaries of the call) or a resident one (d_indptr, d_indices: device pointers)
+static rri_status cooc_counts(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const i64* d_indptr, const int* d_indices,
+                              int64_t n_rows, int64_t n_cols, i64 nnz, const int32_t* words, int32_t n_groups, int32_t group_size,
+                              int64_t* df_out, int64_t* codf_out) {
     if (!df_out || !codf_out) return fail(c, RRI_ERR_INVALID, "an output array is NULL");
     const size_t M = (size_t)group_size, ndf = (size_t)n_groups * M, nco = ndf * M;
     std::fill(df_out, df_out + ndf, (int64_t)0);
     std::fill(codf_out, codf_out + nco, (int64_t)0);
-    const i64 nnz = indptr[n_rows];
     if (n_rows == 0 || nnz == 0) return RRI_OK;
     const CoocMemb memb = cooc_build_memb(words, n_groups, group_size, n_cols);
     if (memb.ent.empty()) return RRI_OK;            // every slot is empty
@@ -3532,21 +3531,27 @@ rri_status rri_cooccurrence_counts(rri_ctx* c, const int64_t* indptr, const int3
     for (const CoocChunk& ch : chunks) pad_max = std::max(pad_max, ch.rows_pad);
     HIPCHK(c, hipSetDevice(c->device));
     DevTmp tptr, tidx, tmp, tme, tmask, tco;
-    HIPCHK(c, tptr.alloc((size_t)(n_rows + 1) * sizeof(i64)));
-    HIPCHK(c, tidx.alloc((size_t)nnz * sizeof(int)));
+    if (!d_indptr) {
+        HIPCHK(c, tptr.alloc((size_t)(n_rows + 1) * sizeof(i64)));
+        HIPCHK(c, tidx.alloc((size_t)nnz * sizeof(int)));
+    }
     HIPCHK(c, tmp.alloc(memb.ptr.size() * sizeof(int)));
     HIPCHK(c, tme.alloc(memb.ent.size() * sizeof(int)));
     HIPCHK(c, tmask.alloc((size_t)pad_max * n_groups * sizeof(unsigned)));
     HIPCHK(c, tco.alloc(nco * sizeof(unsigned long long)));
-    HIPCHK(c, hipMemcpyAsync(tptr.p, indptr, (size_t)(n_rows + 1) * sizeof(i64), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(tidx.p, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (!d_indptr) {
+        HIPCHK(c, hipMemcpyAsync(tptr.p, indptr, (size_t)(n_rows + 1) * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(tidx.p, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        d_indptr = (const i64*)tptr.p;
+        d_indices = (const int*)tidx.p;
+    }
     HIPCHK(c, hipMemcpyAsync(tmp.p, memb.ptr.data(), memb.ptr.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(tme.p, memb.ent.data(), memb.ent.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(tco.p, 0, nco * sizeof(unsigned long long), c->stream));
     const int lps = cooc_lps(nnz, n_rows);
     hipError_t e = hipSuccess;
     for (size_t i = 0; i < chunks.size() && e == hipSuccess; ++i)
-        e = LK::cooc_chunk(c, (const i64*)tptr.p, (const int*)tidx.p, (const int*)tmp.p, (const int*)tme.p, chunks[i], lps, n_groups,
+        e = LK::cooc_chunk(c, d_indptr, d_indices, (const int*)tmp.p, (const int*)tme.p, chunks[i], lps, n_groups,
                            group_size, (unsigned*)tmask.p, (unsigned long long*)tco.p);
     if (e == hipSuccess) e = hipMemcpyAsync(codf_out, tco.p, nco * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
     const hipError_t es = hipStreamSynchronize(c->stream);      // the membership table (host memory of this call) has been read by now too
@@ -3557,17 +3562,25 @@ rri_status rri_cooccurrence_counts(rri_ctx* c, const int64_t* indptr, const int3
     return RRI_OK;
 }
 
+rri_status rri_cooccurrence_counts(rri_ctx* c, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
+                                   const int32_t* words, int32_t n_groups, int32_t group_size, int64_t* df_out, int64_t* codf_out) {
+    char why[200] = "";
+    const int bad = cooc_check_request(indptr, indices, n_rows, n_cols, words, n_groups, group_size, why, sizeof why);
+    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+    CHECK_CTX(c);
+    return cooc_counts(c, indptr, indices, nullptr, nullptr, n_rows, n_cols, indptr[n_rows], words, n_groups, group_size, df_out, codf_out);
+}
+
 // The log-likelihood of stored counts under the rows of W T (rri_loglik.hpp has the semantics).  Reads the handle's W and T; the
 // transposed copy of T, the row list, the entries of a chunk, its pieces, their partials and the outputs live in temporaries of
 // the call, sized for the largest chunk and reused by the next one, so no sum a later sweep reads is touched and
 // rri_device_memory reports what it reported before.  Rank-local on a row-sharded handle: no collective.  The request is
 // checked before any HIP call.
-rri_status rri_entries_loglik(rri_ctx* c, const int64_t* rows, int64_t count, const int64_t* indptr, const int32_t* indices,
-                              const double* values, double floor, double* ll_out, double* mass_out, int64_t* floored_out) {
-    CHECK_CTX(c);
-    char why[200] = "";
-    const int bad = loglik_check_request(c->n, c->d, rows, count, indptr, indices, values, floor, ll_out, mass_out, floored_out, why, sizeof why);
-    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+// what rri_entries_loglik and rri_corpus_entries_loglik share: everything after the request check.  The entries are the host's
+// (d_indices NULL: a chunk's entries are uploaded into temporaries of the call) or resident ones, which the kernels read in place
+static rri_status loglik_entries(rri_ctx* c, const int64_t* rows, int64_t count, const int64_t* indptr, const int32_t* indices,
+                                 const double* values, const int* d_indices, const double* d_values, double floor, double* ll_out,
+                                 double* mass_out, int64_t* floored_out) {
     if (count == 0) return RRI_OK;
     std::fill(ll_out, ll_out + count, 0.0);
     std::fill(mass_out, mass_out + count, 0.0);
@@ -3590,8 +3603,10 @@ rri_status rri_entries_loglik(rri_ctx* c, const int64_t* rows, int64_t count, co
     if (rows) HIPCHK(c, trows.alloc((size_t)req_max * sizeof(i64)));
     HIPCHK(c, tpc.alloc((size_t)pc_max * sizeof(LoglikPiece)));
     HIPCHK(c, tfirst.alloc((size_t)(req_max + 1) * sizeof(i64)));
-    HIPCHK(c, tidx.alloc((size_t)ent_max * sizeof(int)));
-    HIPCHK(c, tval.alloc((size_t)ent_max * sizeof(double)));
+    if (!d_indices) {
+        HIPCHK(c, tidx.alloc((size_t)ent_max * sizeof(int)));
+        HIPCHK(c, tval.alloc((size_t)ent_max * sizeof(double)));
+    }
     HIPCHK(c, tpl.alloc((size_t)pc_max * sizeof(double)));
     HIPCHK(c, tpm.alloc((size_t)pc_max * sizeof(double)));
     HIPCHK(c, tpf.alloc((size_t)pc_max * sizeof(i64)));
@@ -3608,11 +3623,12 @@ rri_status rri_entries_loglik(rri_ctx* c, const int64_t* rows, int64_t count, co
         if (rows) e = hipMemcpyAsync(trows.p, rows + q0, (size_t)nreq * sizeof(i64), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(tpc.p, pieces.data(), (size_t)npieces * sizeof(LoglikPiece), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(tfirst.p, first.data(), (size_t)(nreq + 1) * sizeof(i64), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(tidx.p, indices + e0, (size_t)nent * sizeof(int), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(tval.p, values + e0, (size_t)nent * sizeof(double), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && !d_indices) e = hipMemcpyAsync(tidx.p, indices + e0, (size_t)nent * sizeof(int), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && !d_indices) e = hipMemcpyAsync(tval.p, values + e0, (size_t)nent * sizeof(double), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess)
             e = LK::loglik_chunk(c, (const double*)tTt.p, (const i64*)trows.p, q0, nreq, (const LoglikPiece*)tpc.p, npieces,
-                                 (const i64*)tfirst.p, (const int*)tidx.p, (const double*)tval.p, floor, (double*)tpl.p,
+                                 (const i64*)tfirst.p, d_indices ? d_indices + e0 : (const int*)tidx.p,
+                                 d_indices ? d_values + e0 : (const double*)tval.p, floor, (double*)tpl.p,
                                  (double*)tpm.p, (i64*)tpf.p, (double*)tll.p, (double*)tms.p, (i64*)tfl.p);
         if (e == hipSuccess) e = hipMemcpyAsync(ll_out + q0, tll.p, (size_t)nreq * sizeof(double), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(mass_out + q0, tms.p, (size_t)nreq * sizeof(double), hipMemcpyDeviceToHost, c->stream);
@@ -3625,6 +3641,318 @@ rri_status rri_entries_loglik(rri_ctx* c, const int64_t* rows, int64_t count, co
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "entries log-likelihood failed: %s", hipGetErrorString(e));
     return RRI_OK;
+}
+
+rri_status rri_entries_loglik(rri_ctx* c, const int64_t* rows, int64_t count, const int64_t* indptr, const int32_t* indices,
+                              const double* values, double floor, double* ll_out, double* mass_out, int64_t* floored_out) {
+    CHECK_CTX(c);
+    char why[200] = "";
+    const int bad = loglik_check_request(c->n, c->d, rows, count, indptr, indices, values, floor, ll_out, mass_out, floored_out, why, sizeof why);
+    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+    return loglik_entries(c, rows, count, indptr, indices, values, nullptr, nullptr, floor, ll_out, mass_out, floored_out);
+}
+
+// ---- a CSR corpus that lives on the device (rri_corpus.hpp has the semantics, rri_corpus_kernels.hpp the kernels) ----------------
+// The canonical arrays belong to the corpus, not to a handle: rri_device_memory does not count them, rri_corpus_memory does.
+struct rri_corpus {
+    int device = 0;
+    i64 n_rows = 0, n_cols = 0, stored = 0, nnz = 0, rewritten = 0, dup = 0, zeros = 0, neg = 0, long_rows = 0;
+    i64* indptr = nullptr;       // n_rows + 1
+    int* indices = nullptr;      // nnz
+    double* values = nullptr;    // nnz
+    size_t bytes = 0;
+    std::vector<int64_t> h_indptr;   // the host's copy of the canonical indptr: the chunk and piece cutters run on it
+    double ingest_ms = 0.0;
+};
+std::atomic<long long> g_corpora{0}, g_corpus_bytes{0};
+
+namespace {
+// grid of a grid-stride kernel of 256 threads over `items`
+unsigned corpus_grid(i64 items) { return (unsigned)std::max<i64>(1, std::min<i64>(8192, (items + 255) / 256)); }
+size_t at_least(size_t bytes) { return bytes ? bytes : 8; }
+}  // namespace
+
+rri_status rri_corpus_create(rri_ctx* c, rri_corpus** out, int64_t n_rows, int64_t n_cols, int64_t nnz, const void* indptr,
+                             int32_t indptr_dtype, const void* indices, int32_t indices_dtype, const void* values,
+                             int32_t values_dtype, int32_t on_device) {
+    CHECK_CTX(c);
+    if (!out) return fail(c, RRI_ERR_INVALID, "the output pointer is NULL");
+    *out = nullptr;
+    const CorpusRaw raw{n_rows, n_cols, nnz, indptr, indptr_dtype, indices, indices_dtype, values, values_dtype};
+    char why[200] = "";
+    if (corpus_check_args(raw, why, sizeof why) != TOPN_REQ_OK) return fail(c, RRI_ERR_INVALID, "%s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t psz = corpus_dtype_size(indptr_dtype), isz = corpus_dtype_size(indices_dtype), vsz = corpus_dtype_size(values_dtype);
+    // the raw arrays on the device: the caller's own, or an upload as they are
+    DevTmp rp, ri, rv;
+    const void *dp = indptr, *di = indices, *dv = values;
+    if (!on_device) {
+        HIPCHK(c, rp.alloc((size_t)(n_rows + 1) * psz));
+        HIPCHK(c, hipMemcpyAsync(rp.p, indptr, (size_t)(n_rows + 1) * psz, hipMemcpyHostToDevice, c->stream));
+        dp = rp.p;
+        if (nnz > 0) {
+            HIPCHK(c, ri.alloc((size_t)nnz * isz));
+            HIPCHK(c, hipMemcpyAsync(ri.p, indices, (size_t)nnz * isz, hipMemcpyHostToDevice, c->stream));
+            di = ri.p;
+            if (values) {
+                HIPCHK(c, rv.alloc((size_t)nnz * vsz));
+                HIPCHK(c, hipMemcpyAsync(rv.p, values, (size_t)nnz * vsz, hipMemcpyHostToDevice, c->stream));
+                dv = rv.p;
+            }
+        }
+    }
+    const i64 words = (nnz + 63) / 64;
+    DevTmp tstat, tzb, tdb, tptr, tflag, tclen;
+    HIPCHK(c, tstat.alloc(CORPUS_STAT_WORDS * sizeof(u64)));
+    HIPCHK(c, tzb.alloc(at_least((size_t)words * sizeof(u64))));
+    HIPCHK(c, tdb.alloc(at_least((size_t)words * sizeof(u64))));
+    HIPCHK(c, tptr.alloc((size_t)(n_rows + 1) * sizeof(i64)));
+    HIPCHK(c, tflag.alloc(at_least((size_t)n_rows)));
+    HIPCHK(c, tclen.alloc(at_least((size_t)n_rows * sizeof(i64))));
+    u64* stats = (u64*)tstat.p;
+    HIPCHK(c, hipMemsetAsync(stats, 0xff, 8 * sizeof(u64), c->stream));
+    HIPCHK(c, hipMemsetAsync(stats + 8, 0, 8 * sizeof(u64), c->stream));
+    EventPair ev[4];          // the phases between two reads of the host: check, rows, copy and sorts, compaction
+    int phases = 0;
+    for (EventPair& p : ev) HIPCHK(c, p.create());
+    u64 h_stat[CORPUS_STAT_WORDS];
+
+    // 1. the check, by position only; nothing else runs before its verdict is read
+    HIPCHK(c, hipEventRecord(ev[phases].a, c->stream));
+    hipLaunchKernelGGL(k_corpus_check, dim3(corpus_grid(std::max<i64>(nnz, n_rows + 1))), dim3(256), 0, c->stream, dp, (int)indptr_dtype, di,
+                       (int)indices_dtype, dv, (int)values_dtype, (i64)n_rows, (i64)n_cols, (i64)nnz, stats, (u64*)tzb.p, (u64*)tdb.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev[phases++].b, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_stat, stats, sizeof h_stat, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int rule = 0; rule < 5; ++rule)
+        if (h_stat[rule] != ~0ull) {           // the first broken rule at its smallest position; the offending number is one element
+            const i64 pos = (i64)h_stat[rule];
+            int64_t ival = 0;
+            double dval = 0.0;
+            unsigned char el[8] = {0};
+            if (rule == 0 || rule == 2) {
+                HIPCHK(c, hipMemcpy(el, (const char*)dp + (size_t)pos * psz, psz, hipMemcpyDeviceToHost));
+                ival = corpus_idx(el, indptr_dtype, 0);
+            } else if (rule == 3) {
+                HIPCHK(c, hipMemcpy(el, (const char*)di + (size_t)pos * isz, isz, hipMemcpyDeviceToHost));
+                ival = corpus_idx(el, indices_dtype, 0);
+            } else if (rule == 4) {
+                HIPCHK(c, hipMemcpy(el, (const char*)dv + (size_t)pos * vsz, vsz, hipMemcpyDeviceToHost));
+                dval = corpus_val(el, values_dtype, 0);
+            }
+            corpus_rule_text(rule, pos, ival, dval, rule == 2 ? nnz : n_cols, why, sizeof why);
+            return fail(c, RRI_ERR_INVALID, "%s", why);
+        }
+    if (n_cols > 0x7fffffffLL) {
+        corpus_rule_text(5, 0, 0, 0.0, n_cols, why, sizeof why);
+        return fail(c, RRI_ERR_UNSUPPORTED, "%s", why);
+    }
+
+    // 2. a flag and a stored length per row from the marks of the check; indptr as int64
+    HIPCHK(c, hipEventRecord(ev[phases].a, c->stream));
+    hipLaunchKernelGGL(k_corpus_rows, dim3(corpus_grid(n_rows + 1)), dim3(256), 0, c->stream, dp, (int)indptr_dtype, (i64)n_rows,
+                       (const u64*)tzb.p, (const u64*)tdb.p, (i64*)tptr.p, (unsigned char*)tflag.p, (i64*)tclen.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev[phases++].b, c->stream));
+    std::vector<int64_t> h_ptr((size_t)n_rows + 1);
+    std::vector<unsigned char> h_flag((size_t)n_rows);
+    HIPCHK(c, hipMemcpyAsync(h_ptr.data(), tptr.p, (size_t)(n_rows + 1) * sizeof(i64), hipMemcpyDeviceToHost, c->stream));
+    if (n_rows > 0) HIPCHK(c, hipMemcpyAsync(h_flag.data(), tflag.p, (size_t)n_rows, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // the rows to rewrite, by class, ascending: [short | medium by padded length | long], and the long rows' places in the key buffer
+    std::vector<int64_t> list_short, list_long, keyoff;
+    std::vector<std::vector<int64_t>> list_medium;          // [log2 of the padded length]
+    i64 rewritten = 0, key_total = 0;
+    for (i64 r = 0; r < n_rows; ++r) {
+        const i64 len = h_ptr[(size_t)r + 1] - h_ptr[(size_t)r];
+        const int cls = corpus_row_class(h_flag[(size_t)r] != 0, len);
+        if (cls == CORPUS_ROW_CANONICAL) continue;
+        ++rewritten;
+        if (len > CORPUS_ROW_MAX) return fail(c, RRI_ERR_UNSUPPORTED, "row %lld has %lld stored entries and is not canonical: more than %lld are not rewritten", (long long)r, (long long)len, (long long)CORPUS_ROW_MAX);
+        if (cls == CORPUS_ROW_SHORT) list_short.push_back(r);
+        else if (cls == CORPUS_ROW_MEDIUM) {
+            int lg = 0;
+            while ((1ll << lg) < corpus_pad(len)) ++lg;
+            if (list_medium.size() <= (size_t)lg) list_medium.resize((size_t)lg + 1);
+            list_medium[(size_t)lg].push_back(r);
+        } else {
+            list_long.push_back(r);
+            keyoff.push_back(key_total);
+            key_total += corpus_pad(len);
+        }
+    }
+
+    // 3. the converting copy: the corpus itself when no row is to be rewritten, the staging otherwise
+    DevTmp sidx, sval;
+    HIPCHK(c, sidx.alloc(at_least((size_t)nnz * sizeof(int))));
+    HIPCHK(c, sval.alloc(at_least((size_t)nnz * sizeof(double))));
+    HIPCHK(c, hipEventRecord(ev[phases].a, c->stream));
+    if (nnz > 0) {
+        hipLaunchKernelGGL(k_corpus_copy, dim3(corpus_grid(nnz)), dim3(256), 0, c->stream, di, (int)indices_dtype, dv, (int)values_dtype,
+                           (i64)nnz, (int*)sidx.p, (double*)sval.p, rewritten ? (u64*)nullptr : stats + CORPUS_STAT_NEG);
+        HIPCHK(c, hipGetLastError());
+    }
+    DevTmp tlist, tkoff, tkeys, fptr, fidx, fval;
+    std::vector<int64_t> h_cptr;
+    i64 nnz_c = nnz;
+    if (rewritten) {
+        // 4. sort and merge the flagged rows into the staging, each at its raw offset
+        std::vector<int64_t> all(list_short);
+        for (const auto& l : list_medium) all.insert(all.end(), l.begin(), l.end());
+        all.insert(all.end(), list_long.begin(), list_long.end());
+        HIPCHK(c, tlist.alloc(all.size() * sizeof(i64)));
+        HIPCHK(c, hipMemcpyAsync(tlist.p, all.data(), all.size() * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+        const i64* dl = (const i64*)tlist.p;
+        if (!list_short.empty()) {
+            hipLaunchKernelGGL(k_corpus_sort_wave, dim3((unsigned)((list_short.size() + 3) / 4)), dim3(256), 0, c->stream, dl,
+                               (i64)list_short.size(), (const i64*)tptr.p, di, (int)indices_dtype, dv, (int)values_dtype, (int*)sidx.p,
+                               (double*)sval.p, (i64*)tclen.p, stats);
+            HIPCHK(c, hipGetLastError());
+        }
+        dl += list_short.size();
+        HIPCHK(c, allow_lds<k_corpus_sort_block<true>>(c, CORPUS_LDS_MAX * (int)sizeof(u64)));
+        for (size_t lg = 0; lg < list_medium.size(); ++lg) {
+            const size_t cnt = list_medium[lg].size();
+            if (!cnt) continue;
+            const i64 P = 1ll << lg;
+            hipLaunchKernelGGL(k_corpus_sort_block<true>, dim3((unsigned)cnt), dim3(P <= 1024 ? 256 : 1024), (size_t)P * sizeof(u64), c->stream,
+                               dl, (const i64*)nullptr, (u64*)nullptr, P, (const i64*)tptr.p, di, (int)indices_dtype, dv, (int)values_dtype,
+                               (int*)sidx.p, (double*)sval.p, (i64*)tclen.p, stats);
+            HIPCHK(c, hipGetLastError());
+            dl += cnt;
+        }
+        if (!list_long.empty()) {
+            HIPCHK(c, tkoff.alloc(keyoff.size() * sizeof(i64)));
+            HIPCHK(c, tkeys.alloc((size_t)key_total * sizeof(u64)));
+            HIPCHK(c, hipMemcpyAsync(tkoff.p, keyoff.data(), keyoff.size() * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(k_corpus_sort_block<false>, dim3((unsigned)list_long.size()), dim3(1024), 0, c->stream, dl, (const i64*)tkoff.p,
+                               (u64*)tkeys.p, (i64)0, (const i64*)tptr.p, di, (int)indices_dtype, dv, (int)values_dtype, (int*)sidx.p,
+                               (double*)sval.p, (i64*)tclen.p, stats);
+            HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, hipEventRecord(ev[phases++].b, c->stream));
+        // 5. the canonical lengths go to the host, which takes the prefix sum; the final arrays are written once
+        std::vector<int64_t> h_len((size_t)n_rows);
+        HIPCHK(c, hipMemcpyAsync(h_len.data(), tclen.p, (size_t)n_rows * sizeof(i64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));       // (the lists, host memory of this call, have been read by now too)
+        h_cptr.assign((size_t)n_rows + 1, 0);
+        for (i64 r = 0; r < n_rows; ++r) h_cptr[(size_t)r + 1] = h_cptr[(size_t)r] + h_len[(size_t)r];
+        nnz_c = h_cptr[(size_t)n_rows];
+        HIPCHK(c, fptr.alloc((size_t)(n_rows + 1) * sizeof(i64)));
+        HIPCHK(c, fidx.alloc(at_least((size_t)nnz_c * sizeof(int))));
+        HIPCHK(c, fval.alloc(at_least((size_t)nnz_c * sizeof(double))));
+        HIPCHK(c, hipMemcpyAsync(fptr.p, h_cptr.data(), (size_t)(n_rows + 1) * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(ev[phases].a, c->stream));
+        if (nnz_c > 0) {
+            hipLaunchKernelGGL(k_corpus_compact, dim3(corpus_grid(nnz_c)), dim3(256), 0, c->stream, (const i64*)fptr.p, (const i64*)tptr.p,
+                               (i64)n_rows, nnz_c, (const int*)sidx.p, (const double*)sval.p, (int*)fidx.p, (double*)fval.p,
+                               stats + CORPUS_STAT_NEG);
+            HIPCHK(c, hipGetLastError());
+        }
+    } else {
+        h_cptr = h_ptr;
+    }
+    HIPCHK(c, hipEventRecord(ev[phases++].b, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_stat, stats, sizeof h_stat, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double ms = 0.0;
+    for (int i = 0; i < phases; ++i) {
+        float t = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&t, ev[i].a, ev[i].b));
+        ms += t;
+    }
+    rri_corpus* k = new rri_corpus();
+    DevTmp &optr = rewritten ? fptr : tptr, &oidx = rewritten ? fidx : sidx, &oval = rewritten ? fval : sval;
+    k->device = c->device;
+    k->n_rows = n_rows; k->n_cols = n_cols; k->stored = nnz; k->nnz = nnz_c; k->rewritten = rewritten;
+    k->dup = (i64)h_stat[CORPUS_STAT_DUP]; k->zeros = (i64)h_stat[CORPUS_STAT_ZERO]; k->neg = (i64)h_stat[CORPUS_STAT_NEG];
+    k->long_rows = (i64)list_long.size();
+    k->indptr = (i64*)optr.p; k->indices = (int*)oidx.p; k->values = (double*)oval.p;
+    k->bytes = optr.bytes + oidx.bytes + oval.bytes;
+    optr.p = oidx.p = oval.p = nullptr;                      // the corpus owns them from here on
+    k->h_indptr = std::move(h_cptr);
+    k->ingest_ms = ms;
+    g_corpora += 1;
+    g_corpus_bytes += (long long)k->bytes;
+    *out = k;
+    return RRI_OK;
+}
+
+rri_status rri_corpus_destroy(rri_corpus* k) {
+    if (!k) return RRI_ERR_INVALID;
+    int before = 0;
+    const bool had = hipGetDevice(&before) == hipSuccess;
+    (void)hipSetDevice(k->device);
+    (void)hipFree(k->indptr);
+    (void)hipFree(k->indices);
+    (void)hipFree(k->values);
+    if (had) (void)hipSetDevice(before);
+    g_corpora -= 1;
+    g_corpus_bytes -= (long long)k->bytes;
+    delete k;
+    return RRI_OK;
+}
+
+rri_status rri_corpus_info(const rri_corpus* k, int64_t* out, int32_t n, double* ingest_ms) {
+    if (!k || (n > 0 && !out) || n < 0) return RRI_ERR_INVALID;
+    const int64_t f[RRI_CORPUS_INFO_FIELDS] = {k->n_rows, k->n_cols, k->stored, k->nnz, k->rewritten, k->dup, k->zeros, k->neg,
+                                               (int64_t)k->bytes, k->long_rows};
+    for (int i = 0; i < n && i < RRI_CORPUS_INFO_FIELDS; ++i) out[i] = f[i];
+    for (int i = RRI_CORPUS_INFO_FIELDS; i < n; ++i) out[i] = 0;
+    if (ingest_ms) *ingest_ms = k->ingest_ms;
+    return RRI_OK;
+}
+
+rri_status rri_corpus_memory(int64_t* corpora, int64_t* bytes) {
+    if (corpora) *corpora = g_corpora.load();
+    if (bytes) *bytes = g_corpus_bytes.load();
+    return RRI_OK;
+}
+
+// the handle gives the device, the stream and the error text; the corpus must live on the handle's device
+#define CHECK_CORPUS(c, k)                                                                                              \
+    do {                                                                                                                \
+        CHECK_CTX(c);                                                                                                   \
+        if (!(k)) return fail((c), RRI_ERR_INVALID, "the corpus is NULL");                                              \
+        if ((k)->device != (c)->device)                                                                                 \
+            return fail((c), RRI_ERR_INVALID, "the corpus lives on device %d, the handle on device %d", (k)->device, (c)->device); \
+    } while (0)
+
+rri_status rri_corpus_get(rri_ctx* c, const rri_corpus* k, int64_t* indptr_out, int32_t* indices_out, double* values_out) {
+    CHECK_CORPUS(c, k);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (indptr_out) std::copy(k->h_indptr.begin(), k->h_indptr.end(), indptr_out);
+    if (indices_out && k->nnz > 0) HIPCHK(c, hipMemcpyAsync(indices_out, k->indices, (size_t)k->nnz * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (values_out && k->nnz > 0) HIPCHK(c, hipMemcpyAsync(values_out, k->values, (size_t)k->nnz * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RRI_OK;
+}
+
+rri_status rri_corpus_cooccurrence_counts(rri_ctx* c, const rri_corpus* k, const int32_t* words, int32_t n_groups, int32_t group_size,
+                                          int64_t* df_out, int64_t* codf_out) {
+    CHECK_CORPUS(c, k);
+    char why[200] = "";
+    const int bad = cooc_check_groups(k->n_cols, words, n_groups, group_size, why, sizeof why);
+    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+    return cooc_counts(c, nullptr, nullptr, k->indptr, k->indices, k->n_rows, k->n_cols, k->nnz, words, n_groups, group_size, df_out,
+                       codf_out);
+}
+
+rri_status rri_corpus_entries_loglik(rri_ctx* c, const rri_corpus* k, const int64_t* rows, double floor, double* ll_out,
+                                     double* mass_out, int64_t* floored_out) {
+    CHECK_CORPUS(c, k);
+    if (!(floor >= 0.0) || std::isinf(floor)) return fail(c, RRI_ERR_INVALID, "floor %g is not a finite number >= 0", floor);
+    if (LL_ENTRY_BYTES * c->d > LL_UPLOAD_BUDGET)
+        return fail(c, RRI_ERR_UNSUPPORTED, "a full row of d = %lld entries does not fit the upload budget of %lld bytes", (long long)c->d, (long long)LL_UPLOAD_BUDGET);
+    if (k->n_cols != c->d) return fail(c, RRI_ERR_INVALID, "the corpus has %lld columns, W T has %lld", (long long)k->n_cols, (long long)c->d);
+    if (k->neg > 0) return fail(c, RRI_ERR_INVALID, "the corpus holds %lld negative values: counts are finite and >= 0", (long long)k->neg);
+    const i64 count = k->n_rows;
+    if (!rows && count > c->n) return fail(c, RRI_ERR_INVALID, "rows is NULL and count %lld exceeds the %lld rows of W", (long long)count, (long long)c->n);
+    if (count > 0 && (!ll_out || !mass_out || !floored_out)) return fail(c, RRI_ERR_INVALID, "an output array is NULL with %lld requests", (long long)count);
+    for (i64 q = 0; rows && q < count; ++q)
+        if (rows[q] < 0 || rows[q] >= c->n) return fail(c, RRI_ERR_INVALID, "rows[%lld] = %lld is out of range", (long long)q, (long long)rows[q]);
+    return loglik_entries(c, rows, count, k->h_indptr.data(), nullptr, nullptr, k->indices, k->values, floor, ll_out, mass_out, floored_out);
 }
 
 rri_status rri_snapshot(rri_ctx* c) {

@@ -131,6 +131,162 @@ def device_memory():
     return int(buffers.value), int(nbytes.value)
 
 
+def corpus_memory():
+    """(corpora, bytes) of the DeviceCorpus objects alive in this process and their device bytes (rri_corpus_memory): they belong
+    to no handle, so device_memory() does not count them, and after every close() both are back where they were."""
+    corpora, nbytes = C.c_int64(0), C.c_int64(0)
+    _capi.load_library().rri_corpus_memory(C.byref(corpora), C.byref(nbytes))
+    return int(corpora.value), int(nbytes.value)
+
+
+_INDEX_CODES = {'int32': _capi.RRI_I32, 'int64': _capi.RRI_I64}
+_VALUE_CODES = {'float32': _capi.RRI_F32, 'float64': _capi.RRI_F64}
+
+
+class DeviceCorpus(object):
+    """A sparse corpus that lives on the device: checked and made canonical there, once (rri_corpus_create), and then taken by
+    RRIEngine.cooccurrence_counts / entries_loglik and NMF_TM_Estimator.coherence / log_likelihood / perplexity in place of the
+    scipy matrix, without the host's canonical copy and the upload of every call.
+
+    X is a scipy sparse matrix (its arrays travel as they are: unsorted rows, duplicates and explicit zeros are dealt with on the
+    device), a dense array (converted to CSR on the host first, the slow way in) or a torch sparse-CSR tensor on the GPU, whose
+    arrays are read where they are (the corpus then lives on the tensor's device, whatever `device` says).  `from_device` takes the
+    three arrays as GPU tensors, `from_arrays` raw host arrays.  The canonical form: per row strictly
+    ascending columns, the stored entries of one column added in float64 in stored order, sums that are exactly 0 dropped; int32
+    indices, float64 values.  ValueError names the first broken rule of a malformed matrix (a column out of range, a NaN, an
+    indptr that decreases ...), NotImplementedError 2^31 columns or more.
+
+    shape; nnz (canonical entries); stored (entries as given); rows_rewritten, duplicates_merged, zeros_dropped (stored = nnz +
+    duplicates_merged + zeros_dropped); negatives (canonical values below 0: entries_loglik refuses such a corpus); device_bytes;
+    long_rows; ingest_ms (the HIP-event time of the ingest's kernels); device.  The corpus belongs to no handle: it serves every
+    RRIEngine on its device until close() (also: a context manager), and corpus_memory() counts it, device_memory() does not."""
+
+    def __init__(self, X, device=0):
+        import scipy.sparse as sp
+        self._c = C.c_void_p()
+        if hasattr(X, 'crow_indices') and hasattr(X, 'col_indices'):          # a torch sparse-CSR tensor
+            self._ingest_device(X.crow_indices(), X.col_indices(), X.values(), tuple(X.shape), None)      # where the tensor lives
+            return
+        A = X.tocsr() if sp.issparse(X) else sp.csr_matrix(np.asarray(X))
+        if not sp.isspmatrix_csr(A):
+            A = sp.csr_matrix(A)
+        self._ingest_host(A.indptr, A.indices, A.data, A.shape, device)
+
+    @classmethod
+    def from_arrays(cls, indptr, indices, values, shape, device=0):
+        """The corpus of three host arrays as they are -- what a scipy matrix holds, without scipy's own look at them: indptr and
+        indices int32 or int64 (other integers are widened), values float32 or float64 (others become float64) or None for a
+        pattern.  They are uploaded raw and checked on the device."""
+        self = cls.__new__(cls)
+        self._c = C.c_void_p()
+        self._ingest_host(indptr, indices, values, shape, device)
+        return self
+
+    def _ingest_host(self, indptr, indices, values, shape, device):
+        indptr, indices = (np.ascontiguousarray(a if a.dtype.name in _INDEX_CODES else a.astype(np.int64))
+                           for a in (np.asarray(indptr).reshape(-1), np.asarray(indices).reshape(-1)))
+        if values is not None:
+            values = np.asarray(values).reshape(-1)
+            values = np.ascontiguousarray(values if values.dtype.name in _VALUE_CODES else values.astype(np.float64))
+            if values.size != indices.size:
+                raise ValueError('values must have as many entries as indices (%d)' % indices.size)
+        if len(shape) != 2 or indptr.size != int(shape[0]) + 1:
+            raise ValueError('indptr must have shape[0] + 1 = %d entries' % (int(shape[0]) + 1))
+        self._ingest(shape, int(indices.size), indptr.ctypes.data, _INDEX_CODES[indptr.dtype.name], indices.ctypes.data,
+                     _INDEX_CODES[indices.dtype.name], values.ctypes.data if values is not None else None,
+                     _VALUE_CODES[values.dtype.name] if values is not None else _capi.RRI_F64, 0, device, (indptr, indices, values))
+
+    @classmethod
+    def from_device(cls, indptr, indices, values, shape, device=None):
+        """The corpus of three one-dimensional GPU tensors (anything with data_ptr(), dtype, device and numel(): torch tensors):
+        indptr int32 / int64 with shape[0] + 1 entries, indices int32 / int64, values float32 / float64 or None for a pattern
+        (every stored entry counts 1).  They are read during the call and not kept.  torch tensors' device is synchronised first;
+        whoever hands over other objects has synchronised what produced them."""
+        self = cls.__new__(cls)
+        self._c = C.c_void_p()
+        self._ingest_device(indptr, indices, values, tuple(shape), device)
+        return self
+
+    def _ingest_device(self, indptr, indices, values, shape, device):
+        def code(t, table, what):
+            name = str(t.dtype).split('.')[-1]
+            if name not in table:
+                raise TypeError('%s must be %s, not %s' % (what, ' or '.join(sorted(table)), t.dtype))
+            return table[name]
+        tensors = [t for t in (indptr, indices, values) if t is not None]
+        tensors = [t.contiguous() if hasattr(t, 'contiguous') else t for t in tensors]
+        index = {getattr(t.device, 'index', None) for t in tensors}
+        if any(getattr(t.device, 'type', 'cuda') != 'cuda' for t in tensors) or len(index) != 1:
+            raise ValueError('indptr, indices and values must be GPU tensors on one device')
+        dev = index.pop()
+        dev = 0 if dev is None else int(dev)
+        if device is not None and int(device) != dev:
+            raise ValueError('the tensors live on device %d, not on device %d' % (dev, int(device)))
+        if len(shape) != 2 or int(tensors[0].numel()) != int(shape[0]) + 1:
+            raise ValueError('indptr must have shape[0] + 1 = %d entries' % (int(shape[0]) + 1))
+        nnz = int(tensors[1].numel())
+        if values is not None and int(tensors[2].numel()) != nnz:
+            raise ValueError('values must have as many entries as indices (%d)' % nnz)
+        if type(tensors[0]).__module__.split('.')[0] == 'torch':
+            import torch
+            torch.cuda.synchronize(dev)
+        self._ingest(shape, nnz, tensors[0].data_ptr(), code(tensors[0], _INDEX_CODES, 'indptr'), tensors[1].data_ptr(),
+                     code(tensors[1], _INDEX_CODES, 'indices'), tensors[2].data_ptr() if values is not None else None,
+                     code(tensors[2], _VALUE_CODES, 'values') if values is not None else _capi.RRI_F64, 1, dev, tensors)
+
+    def _ingest(self, shape, stored, indptr, pdt, indices, idt, values, vdt, on_device, device, keep_alive):
+        self._lib = _capi.load_library()
+        self.device = int(device)
+        self.shape = (int(shape[0]), int(shape[1]))
+        with self._handle() as eng:
+            eng._check(self._lib.rri_corpus_create(eng._h, C.byref(self._c), self.shape[0], self.shape[1], stored,
+                                                   C.c_void_p(indptr), pdt, C.c_void_p(indices or None), idt,
+                                                   C.c_void_p(values or None), vdt, on_device))
+        del keep_alive
+        info, ms = (C.c_int64 * _capi.RRI_CORPUS_INFO_FIELDS)(), C.c_double(0.0)
+        self._lib.rri_corpus_info(self._c, info, _capi.RRI_CORPUS_INFO_FIELDS, C.byref(ms))
+        (_, _, self.stored, self.nnz, self.rows_rewritten, self.duplicates_merged, self.zeros_dropped, self.negatives,
+         self.device_bytes, self.long_rows) = (int(v) for v in info)
+        self.ingest_ms = float(ms.value)
+
+    def _handle(self):
+        """a handle for the device, the stream and the error text: it holds nothing of the corpus's size"""
+        return RRIEngine(1, 1, 1, dtype=np.float64, weighted=False, device=self.device)
+
+    def _ptr(self):
+        if not self._c:
+            raise ValueError('the corpus is closed')
+        return self._c
+
+    def to_scipy(self):
+        """the canonical matrix as a scipy CSR matrix with float64 data (scipy picks the index dtype): a download"""
+        import scipy.sparse as sp
+        indptr = np.zeros(self.shape[0] + 1, dtype=np.int64)
+        indices = np.zeros(self.nnz, dtype=np.int32)
+        values = np.zeros(self.nnz, dtype=np.float64)
+        with self._handle() as eng:
+            eng._check(self._lib.rri_corpus_get(eng._h, self._ptr(), indptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                indices.ctypes.data_as(C.POINTER(C.c_int32)), values.ctypes.data_as(C.POINTER(C.c_double))))
+        return sp.csr_matrix((values, indices, indptr), shape=self.shape)
+
+    def close(self):
+        if getattr(self, '_c', None) is not None and self._c:
+            self._lib.rri_corpus_destroy(self._c)
+            self._c = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown)
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class RRIEngine(object):
     def __init__(self, n, d, k, dtype=np.float32, weighted=False, device=0, stream=None, schedule='gram', sparse_x=False):
         """schedule (unweighted handles): 'gram' -- the residual is never formed, one read of X per topic step
@@ -572,6 +728,10 @@ class RRIEngine(object):
                                                eligible.ctypes.data_as(I32P)))
         return RankResult(tptr, tind, rank, val, eligible)
 
+    def _same_device(self, corpus):
+        if corpus.device != self.device:
+            raise ValueError('the corpus lives on device %d, the handle on device %d' % (corpus.device, self.device))
+
     def cooccurrence_counts(self, A, words):
         """Document and co-document frequencies of groups of words, counted on the device (rri_cooccurrence_counts).  A is a scipy
         sparse matrix, documents x dictionary, of which only the pattern counts: a stored non-zero means that the word occurs in
@@ -579,21 +739,29 @@ class RRIEngine(object):
         is).  `words` is array-like (g, M) of columns of A, -1 for an empty slot, a column at most once per group, M <= 32.
         Returns (df int64 (g, M), codf int64 (g, M, M)): the number of documents that contain words[g, a], and the number that
         contain both words[g, a] and words[g, b].  A need not have the handle's shape; the handle's factors and X are neither read
-        nor changed, and on a row-sharded handle the call is not collective (counts of row blocks add)."""
+        nor changed, and on a row-sharded handle the call is not collective (counts of row blocks add).  A may also be a DeviceCorpus
+        on the handle's device (ValueError on another): the same counts from the resident arrays (rri_corpus_cooccurrence_counts)."""
         import scipy.sparse as sp
-        A = sp.csr_matrix(A, copy=True)
-        A.sum_duplicates()
-        A.eliminate_zeros()
-        A.sort_indices()
         words = np.ascontiguousarray(np.asarray(words, dtype=np.int32))
         if words.ndim != 2:
             raise ValueError('words must be a (groups, words per group) array, not %r' % (words.shape,))
         g, M = words.shape
+        I64P, I32P = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        if isinstance(A, DeviceCorpus):             # resident and canonical already: nothing of the corpus's size is copied
+            self._same_device(A)
+            df = np.zeros((g, M), dtype=np.int64)
+            codf = np.zeros((g, M, M), dtype=np.int64)
+            self._check(self._lib.rri_corpus_cooccurrence_counts(self._h, A._ptr(), words.ctypes.data_as(I32P), g, M,
+                                                                 df.ctypes.data_as(I64P), codf.ctypes.data_as(I64P)))
+            return df, codf
+        A = sp.csr_matrix(A, copy=True)
+        A.sum_duplicates()
+        A.eliminate_zeros()
+        A.sort_indices()
         indptr = np.ascontiguousarray(A.indptr, dtype=np.int64)
         indices = np.ascontiguousarray(A.indices, dtype=np.int32)
         df = np.zeros((g, M), dtype=np.int64)
         codf = np.zeros((g, M, M), dtype=np.int64)
-        I64P, I32P = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
         self._check(self._lib.rri_cooccurrence_counts(self._h, indptr.ctypes.data_as(I64P), indices.ctypes.data_as(I32P), A.shape[0],
                                                       A.shape[1], words.ctypes.data_as(I32P), g, M, df.ctypes.data_as(I64P),
                                                       codf.ctypes.data_as(I64P)))
@@ -607,13 +775,24 @@ class RRIEngine(object):
         exactly 0; mass = sum v; floored the number of entries with v > 0 and p < floor.  Explicit zeros are kept.  A is sorted and
         its duplicates summed on a copy when it is not canonical, and copied only where its arrays do not have the dtypes the
         library reads; the caller's matrix stays as it is.  Reads the handle's current factors and changes nothing; a request
-        returns the same bits alone and among others; row-sharded: local rows, no collective."""
+        returns the same bits alone and among others; row-sharded: local rows, no collective.  A may also be a DeviceCorpus on the
+        handle's device (ValueError on another) with one row per request: the same bits as for A.to_scipy(), from the resident
+        arrays (rri_corpus_entries_loglik); its explicit zeros are gone, and one with negative values is refused."""
         import scipy.sparse as sp
         if rows is None:
             m, rows_p = self.n, None
         else:
             rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
             m, rows_p = rows.size, rows.ctypes.data_as(C.POINTER(C.c_int64))
+        I64P, I32P, DP = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        if isinstance(A, DeviceCorpus):             # the whole corpus, request q its row q; the kernels read the resident arrays
+            self._same_device(A)
+            if A.shape != (m, self.d):
+                raise ValueError('A must have one row per requested row and d columns: %r, not %r' % ((m, self.d), A.shape))
+            ll, mass, floored = np.zeros(m, dtype=np.float64), np.zeros(m, dtype=np.float64), np.zeros(m, dtype=np.int64)
+            self._check(self._lib.rri_corpus_entries_loglik(self._h, A._ptr(), rows_p, float(floor), ll.ctypes.data_as(DP),
+                                                            mass.ctypes.data_as(DP), floored.ctypes.data_as(I64P)))
+            return ll, mass, floored
         if not sp.isspmatrix_csr(A):
             A = sp.csr_matrix(A)
         if A.shape != (m, self.d):
@@ -627,7 +806,6 @@ class RRIEngine(object):
         ll = np.zeros(m, dtype=np.float64)
         mass = np.zeros(m, dtype=np.float64)
         floored = np.zeros(m, dtype=np.int64)
-        I64P, I32P, DP = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)
         self._check(self._lib.rri_entries_loglik(self._h, rows_p, m, indptr.ctypes.data_as(I64P), indices.ctypes.data_as(I32P),
                                                  values.ctypes.data_as(DP), float(floor), ll.ctypes.data_as(DP),
                                                  mass.ctypes.data_as(DP), floored.ctypes.data_as(I64P)))

@@ -10,7 +10,7 @@ from sklearn.model_selection import train_test_split
 from sklearn.utils.validation import check_X_y, check_array
 
 from . import nmf as _nmf_module
-from .engine import RRIEngine
+from .engine import RRIEngine, DeviceCorpus
 
 _RECOMMEND_CHUNK = 1 << 20      # users per rri_topn_rows call of NMF_RS_Estimator.recommend
 
@@ -533,7 +533,8 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
 
         A word OCCURS in a document where X has a stored non-zero: presence is taken from X as given, without tf-idf or
         normalisation (an idf of 0 would erase a word).  X is scipy sparse, or dense -- which is converted to CSR on the host
-        first, the slow way in.  `words` ((g, M), -1 for an empty slot, M <= 32) overrides top_words(n_words).  The document
+        first, the slow way in --, or a DeviceCorpus, which is counted where it lives: no canonical copy on the host and no upload,
+        the same counts.  `words` ((g, M), -1 for an empty slot, M <= 32) overrides top_words(n_words).  The document
         frequencies D_a and co-document frequencies D_ab of each topic's words are counted on the device
         (rri_cooccurrence_counts); there is no host route for them: without a GPU the call raises RRIHipUnavailable.
 
@@ -552,13 +553,14 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
         if np.ndim(self.T) != 2:
             raise ValueError('the estimator is not fitted: it has no T')
         d = np.shape(self.T)[1]
-        A = X.tocsr() if sp.issparse(X) else sp.csr_matrix(np.asarray(X))
+        A = X if isinstance(X, DeviceCorpus) else X.tocsr() if sp.issparse(X) else sp.csr_matrix(np.asarray(X))
         if A.shape[1] != d:
             raise ValueError('X must have the %d columns of T, not %d' % (d, A.shape[1]))
         words = self.top_words(n_words) if words is None else np.array(words, dtype=np.int32, ndmin=2)
         if words.ndim != 2:
             raise ValueError('words must be a (groups, words per group) array')
-        eng = RRIEngine(1, 1, 1, dtype=np.float64, weighted=False, device=self.nmf_kwargs.get('device', 0))
+        eng = RRIEngine(1, 1, 1, dtype=np.float64, weighted=False,
+                        device=A.device if isinstance(A, DeviceCorpus) else self.nmf_kwargs.get('device', 0))
         try:        # the handle gives the device and the stream: it holds nothing of the corpus's size
             df, codf = eng.cooccurrence_counts(A, words)
         finally:
@@ -597,6 +599,9 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
         in; its stored values are the counts as given (no tf-idf, no normalisation), finite and >= 0.  The sums
         sum_j X[i, j] log(max(p_ij, floor)) over the stored entries are taken on the device (rri_entries_loglik), so nothing of
         size n' x d exists anywhere; there is no host route for them: without a GPU the call raises RRIHipUnavailable.
+        X may also be a DeviceCorpus: its entries are scored where they live (the same bits as for X.to_scipy()); one that holds
+        negative values is refused.  With W=None the fold-in needs the matrix on the host, so the corpus is DOWNLOADED
+        (X.to_scipy()) for it: pass W to download nothing.
 
         Returns per_document (n',), tokens (n',: the sum of a document's counts), floored (n',: its entries with a positive
         count whose p lies below floor), log_likelihood (the sum of per_document), per_token (that over the sum of tokens),
@@ -604,11 +609,11 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
         if np.ndim(self.T) != 2:
             raise ValueError('the estimator is not fitted: it has no T')
         k, d = np.shape(self.T)
-        A = X.tocsr() if sp.issparse(X) else sp.csr_matrix(np.asarray(X))
+        A = X if isinstance(X, DeviceCorpus) else X.tocsr() if sp.issparse(X) else sp.csr_matrix(np.asarray(X))
         if A.shape[1] != d:
             raise ValueError('X must have the %d columns of T, not %d' % (d, A.shape[1]))
         if W is None:
-            W = self.transform(X)
+            W = self.transform(X.to_scipy() if isinstance(X, DeviceCorpus) else X)
         W = W.toarray() if sp.issparse(W) else np.asarray(W, dtype=np.float64)
         if W.shape != (A.shape[0], k):
             raise ValueError('W must be %r, one row per document of X, not %r' % ((A.shape[0], k), W.shape))
@@ -619,7 +624,7 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
         if n == 0:
             ll, mass, floored = np.zeros(0), np.zeros(0), np.zeros(0, dtype=np.int64)
         else:
-            eng = RRIEngine(n, d, k, dtype=np.float64, device=self.nmf_kwargs.get('device', 0))
+            eng = RRIEngine(n, d, k, dtype=np.float64, device=A.device if isinstance(A, DeviceCorpus) else self.nmf_kwargs.get('device', 0))
             try:        # a factors-only handle: it holds W and T and nothing of the corpus's size
                 eng.set_W(W)
                 eng.set_T(T)
@@ -635,8 +640,10 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
         """exp(-log-likelihood per token) of the counts X under the fitted topics: log_likelihood(X, W, floor)['perplexity'] with
         W = self.transform(observed if observed is not None else X).  With `observed` (n' x d, the same documents) this is document
         completion: fold in on one part of each document's tokens and score the other (split_counts makes the two parts).  A
-        model that spreads every document evenly over the dictionary has perplexity d."""
-        return self.log_likelihood(X, W=self.transform(observed if observed is not None else X), floor=floor)['perplexity']
+        model that spreads every document evenly over the dictionary has perplexity d.  X may be a DeviceCorpus: with a scipy
+        `observed` nothing is downloaded; without `observed` the fold-in downloads the corpus (X.to_scipy())."""
+        seen = observed if observed is not None else X
+        return self.log_likelihood(X, W=self.transform(seen.to_scipy() if isinstance(seen, DeviceCorpus) else seen), floor=floor)['perplexity']
 
 
 def split_counts(X, held_out=0.5, random_state=0):
