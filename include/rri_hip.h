@@ -372,6 +372,28 @@ rri_status rri_corpus_cooccurrence_counts(rri_ctx* ctx, const rri_corpus* corpus
  * corpus with negative values or with n_cols != d; RRI_ERR_UNSUPPORTED for 12 d > 64 MiB as there. */
 rri_status rri_corpus_entries_loglik(rri_ctx* ctx, const rri_corpus* corpus, const int64_t* rows, double floor,
                                      double* ll_out, double* mass_out, int64_t* floored_out);
+/* ---- the fit from a resident corpus ----------------------------------------------------------------------------------------------
+ * rri_upload_X_corpus: X of an RRI_UNWEIGHTED_SPARSE handle from a corpus, without the host.  The corpus's canonical arrays are
+ * copied device to device (12 bytes per entry, once) and the handle's blocked store -- the canonical CSR in the storage type and
+ * the two blocked copies with their segment pointers, 16-bit offsets, permutations, values and work items -- is built on the
+ * device by count, padded scan, claim and a sort of every claimed segment by canonical position: the same bytes as
+ * rri_upload_X_csr leaves for the same matrix on the same device, whatever the scheduling.  Only the segment pointers (8 nblk
+ * (nseg + 1) bytes per copy) cross to the host, where the work items are cut by the cutter of rri_upload_X_csr.  The handle owns
+ * all its buffers: the corpus is not modified, not kept, and may be destroyed right after the call.  Uniform rows are cleared
+ * as by rri_upload_X_csr.  Blocking.  RRI_ERR_INVALID for a NULL or destroyed corpus, one on another device, one whose shape is
+ * not (n, d), and for a handle that is not RRI_UNWEIGHTED_SPARSE; RRI_ERR_UNSUPPORTED for 2^31-1 canonical entries or more and
+ * for an RRI_F16 / RRI_U8 handle.  A refusal leaves the handle's store and every counter as they were.  Negative values are
+ * accepted, as by rri_upload_X_csr.
+ * rri_sparse_store_get: blocked copy `which` (0: rows as segments, 1: columns as segments) of any handle that has a blocked
+ * store, whichever route built it -- for tests and probes.  info[0 .. n_info): nblk, bw, nseg, gdim, count (entries incl. the
+ * padding of every segment to a multiple of 4), nwork, lps, nnz, longest row, and the HIP-event time in microseconds of the
+ * kernels of a device build (0: the host built the store) -- RRI_SPARSE_STORE_INFO_FIELDS of them, a longer info is zero-filled.
+ * segptr: nblk (nseg + 1) entries; idx, perm, val: max(count, 4) entries, val in the handle's storage type; work: 4 ints per
+ * item (block, first segment, end segment, copy).  Any array pointer may be NULL.  RRI_ERR_INVALID without a blocked store. */
+#define RRI_SPARSE_STORE_INFO_FIELDS 10
+rri_status rri_upload_X_corpus(rri_ctx* ctx, const rri_corpus* corpus);
+rri_status rri_sparse_store_get(rri_ctx* ctx, int32_t which, int64_t* info, int32_t n_info, int64_t* segptr, uint16_t* idx,
+                                int32_t* perm, void* val, int32_t* work);
 /* device-side copy of (W,T) for the early-stop rollback of nmf.py:360-363,393-407 */
 rri_status rri_snapshot(rri_ctx* ctx);
 rri_status rri_rollback(rri_ctx* ctx);

@@ -23,6 +23,7 @@ RRI_F32, RRI_F64, RRI_F16 = 0, 1, 2   # RRI_F16: the dense X of an RRI_UNWEIGHTE
 RRI_U8 = 4                            # ... and so is RRI_U8: counts 0..255, one byte each, with float64 row and column scales
 RRI_I32, RRI_I64 = 8, 9               # the index arrays of rri_corpus_create
 RRI_CORPUS_INFO_FIELDS = 10           # include/rri_hip.h: what rri_corpus_info fills
+RRI_SPARSE_STORE_INFO_FIELDS = 10     # ... and what rri_sparse_store_get fills
 # rri_create's `weighted`: the flavour of the handle
 RRI_UNWEIGHTED, RRI_WEIGHTED_DENSE, RRI_WEIGHTED_SPARSE, RRI_UNWEIGHTED_RESIDUAL, RRI_UNWEIGHTED_SPARSE = 0, 1, 2, 3, 4
 RESET_NONE, RESET_MAX_RESID_DOCUMENT, RESET_RANDOM = 0, 1, 2
@@ -97,6 +98,9 @@ PROTOTYPES = {
     'rri_corpus_memory': (_I32, [C.POINTER(_I64), C.POINTER(_I64)]),
     'rri_corpus_cooccurrence_counts': (_I32, [_P, _P, C.POINTER(_I32), _I32, _I32, C.POINTER(_I64), C.POINTER(_I64)]),
     'rri_corpus_entries_loglik': (_I32, [_P, _P, C.POINTER(_I64), _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_I64)]),
+    'rri_upload_X_corpus': (_I32, [_P, _P]),
+    'rri_sparse_store_get': (_I32, [_P, _I32, C.POINTER(_I64), _I32, C.POINTER(_I64), C.POINTER(C.c_uint16), C.POINTER(_I32), _P,
+                                    C.POINTER(_I32)]),
     'rri_frozen_set': (_I32, [_P, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), _D]),
     'rri_frozen_get': (_I32, [_P, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), C.POINTER(_I64)]),
     'rri_frozen_absorb': (_I32, [_P, _D]),

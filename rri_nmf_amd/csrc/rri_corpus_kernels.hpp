@@ -42,6 +42,34 @@ __device__ inline double corpus_shfl(double v, int src) {
     return __longlong_as_double((long long)(((u64)(unsigned)hi << 32) | (u64)(unsigned)lo));
 }
 
+// the two sorting networks, shared with the builder of the blocked store (rri_spbuild_kernels.hpp), whose key has the same shape.
+// A wave's 64 keys, one per lane, ascending by lane: a bitonic network of 21 lane exchanges
+__device__ inline u64 corpus_sort_wave_key(u64 key, int lane) {
+    for (int k = 2; k <= 64; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const u64 other = corpus_shfl_xor(key, j);
+            const bool take_min = ((lane & k) == 0) == ((lane & j) == 0);
+            key = take_min ? (key < other ? key : other) : (key < other ? other : key);
+        }
+    return key;
+}
+// P keys (a power of two; LDS or global), ascending, by the nt threads of one workgroup: the same network in place, a barrier per
+// stage.  The keys are written and a barrier has passed before the call; a barrier has passed when it returns
+__device__ inline void corpus_sort_keys(u64* keys, i64 P, int tid, int nt) {
+    for (i64 k = 2; k <= P; k <<= 1)
+        for (i64 j = k >> 1; j > 0; j >>= 1) {
+            for (i64 t = tid; t < (P >> 1); t += nt) {
+                const i64 i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), m = i | j;        // a pair that differs in bit j
+                const u64 a = keys[i], b = keys[m];
+                if ((a > b) == ((i & k) == 0)) {
+                    keys[i] = b;
+                    keys[m] = a;
+                }
+            }
+            __syncthreads();
+        }
+}
+
 __global__ __launch_bounds__(256) void k_corpus_check(const void* __restrict__ indptr, int pdt, const void* __restrict__ indices,
                                                       int idt, const void* __restrict__ values, int vdt, i64 n_rows, i64 n_cols,
                                                       i64 nnz, u64* __restrict__ err, u64* __restrict__ zero_bits,
@@ -130,12 +158,7 @@ __global__ __launch_bounds__(256) void k_corpus_sort_wave(const i64* __restrict_
     const i64 r = rows[item], lo = ptr64[r];
     const int len = (int)(ptr64[r + 1] - lo);                        // 1 .. CORPUS_WAVE_MAX
     u64 key = lane < len ? corpus_key(corpus_idx(indices, idt, lo + lane), lane) : CORPUS_KEY_PAD;
-    for (int k = 2; k <= 64; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const u64 other = corpus_shfl_xor(key, j);
-            const bool take_min = ((lane & k) == 0) == ((lane & j) == 0);
-            key = take_min ? (key < other ? key : other) : (key < other ? other : key);
-        }
+    key = corpus_sort_wave_key(key, lane);
     const bool valid = lane < len;                                   // the real keys stand below the pad
     const int col = (int)corpus_key_col(key);
     const double v = valid ? corpus_val(values, vdt, lo + corpus_key_pos(key)) : 0.0;
@@ -184,18 +207,7 @@ __global__ __launch_bounds__(1024) void k_corpus_sort_block(const i64* __restric
     if (tid < 2) tot[tid] = 0;
     for (i64 i = tid; i < P; i += nt) keys[i] = i < len ? corpus_key(corpus_idx(indices, idt, lo + i), i) : CORPUS_KEY_PAD;
     __syncthreads();
-    for (i64 k = 2; k <= P; k <<= 1)
-        for (i64 j = k >> 1; j > 0; j >>= 1) {
-            for (i64 t = tid; t < (P >> 1); t += nt) {
-                const i64 i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), m = i | j;        // a pair that differs in bit j
-                const u64 a = keys[i], b = keys[m];
-                if ((a > b) == ((i & k) == 0)) {
-                    keys[i] = b;
-                    keys[m] = a;
-                }
-            }
-            __syncthreads();
-        }
+    corpus_sort_keys(keys, P, tid, nt);
     // every thread takes a contiguous share of the sorted row and the runs that begin in it
     const i64 share = (len + nt - 1) / nt;
     const i64 a0 = (i64)tid * share < len ? (i64)tid * share : len, a1 = a0 + share < len ? a0 + share : len;

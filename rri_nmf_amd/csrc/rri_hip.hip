@@ -26,6 +26,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <mutex>
+#include <set>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -46,6 +47,7 @@
 #include "rri_loglik_kernels.hpp"
 #include "rri_frozen_kernels.hpp"
 #include "rri_corpus_kernels.hpp"
+#include "rri_spbuild_kernels.hpp"
 
 using namespace rri;
 
@@ -195,6 +197,7 @@ struct rri_ctx {
     // itself, read by k_spx_pass; spx_work = the items of copy 0 followed by those of copy 1 (SpWork.pad = copy)
     bool sparse_x = false;
     SpWork* spx_work = nullptr;
+    double spb_ms = 0.0;        // HIP-event time of the kernels that built the blocked store on the device (rri_upload_X_corpus); 0: the host built it
     double* rowhat = nullptr;   // per-row sum of (W T)_ij^2 over the pattern (the objective's fallback)
     // uniform rows of that handle (rri_set_uniform_rows, rri_csr_scale_X_uniform): X = S + uni_value e_U 1^T, S the stored CSR
     // with zeros in the rows of U = uni_rows (sorted, device).  uni_n == 0: nothing of this is launched anywhere
@@ -2628,8 +2631,15 @@ rri_status csr_to_device(rri_ctx* c, const int64_t* indptr, const int32_t* indic
 }
 }  // namespace
 
+namespace {
+struct CorpusArrays {   // the canonical arrays of an rri_corpus, where they are: int64 indptr, int32 indices, float64 values (device)
+    const i64* indptr;
+    const int* indices;
+    const double* values;
+};
+}  // namespace
 static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data,
-                                    int64_t nnz, int32_t data_dtype);
+                                    int64_t nnz, int32_t data_dtype, const CorpusArrays* resident = nullptr);
 
 rri_status rri_upload_X_csr(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data,
                             int64_t nnz, int32_t data_dtype) {
@@ -2661,29 +2671,44 @@ rri_status rri_upload_X_csr(rri_ctx* c, const int64_t* indptr, const int32_t* in
 namespace {
 rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indices, int64_t nnz, int32_t data_dtype,
                           CsrDev& dv, int target_items);
+rri_status build_sp_store_device(rri_ctx* c, CsrDev& dv, const double* values, int64_t nnz, int target_items);
 }
-// RRI_UNWEIGHTED_SPARSE: X stays CSR -- the canonical copy and the two blocked copies with X's values (k_spx_pass)
+// RRI_UNWEIGHTED_SPARSE: X stays CSR -- the canonical copy and the two blocked copies with X's values (k_spx_pass).  Two ways in,
+// one way out: host arrays (rri_upload_X_csr), which are checked, sorted and uploaded and whose blocked copies the host builds
+// (build_sp_store); or `resident`, the canonical arrays of a corpus (rri_upload_X_corpus, which has checked the request), which
+// are copied on the device and whose blocked copies are built there (build_sp_store_device).  The same bytes either way
 static rri_status upload_X_csr_kept(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* data,
-                                    int64_t nnz, int32_t data_dtype) {
+                                    int64_t nnz, int32_t data_dtype, const CorpusArrays* resident) {
     if (nnz >= 2147483647LL) return fail(c, RRI_ERR_UNSUPPORTED, "more than 2^31-1 stored entries");
-    std::string bad = csr_check(indptr, indices, data, nnz, data_dtype, c->n, c->d, CSR_ROWS);
-    if (!bad.empty()) return fail(c, RRI_ERR_INVALID, "%s", bad.c_str());
-    HIPCHK(c, hipSetDevice(c->device));
-    // column indices sorted inside every row (a sorted host copy where the caller's are not); duplicates are refused
+    CsrDev dv;
+    rri_status s = RRI_OK;
     std::vector<int32_t> sidx;
     std::vector<unsigned char> sval;
-    if (csr_sort_rows(indptr, indices, data, c->n, nnz, dtype_size(data_dtype), sidx, sval)) { indices = sidx.data(); data = sval.data(); }
-    bad = csr_duplicates(indptr, indices, c->n);
-    if (!bad.empty()) return fail(c, RRI_ERR_INVALID, "%s", bad.c_str());
-    CsrDev dv;
-    rri_status s = csr_to_device(c, indptr, indices, data, nnz, data_dtype, dv);
-    if (s != RRI_OK) return s;
+    if (resident) {
+        HIPCHK(c, hipSetDevice(c->device));
+        // the handle's own copies of the index arrays: the corpus is not kept and may go right after the call
+        HIPCHK(c, dv.indptr.alloc((size_t)(c->n + 1) * sizeof(i64)));
+        HIPCHK(c, dv.indices.alloc((size_t)std::max<i64>(nnz, 1) * sizeof(int)));
+        HIPCHK(c, hipMemcpyAsync(dv.indptr.p, resident->indptr, (size_t)(c->n + 1) * sizeof(i64), hipMemcpyDeviceToDevice, c->stream));
+        if (nnz > 0) HIPCHK(c, hipMemcpyAsync(dv.indices.p, resident->indices, (size_t)nnz * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        std::string bad = csr_check(indptr, indices, data, nnz, data_dtype, c->n, c->d, CSR_ROWS);
+        if (!bad.empty()) return fail(c, RRI_ERR_INVALID, "%s", bad.c_str());
+        HIPCHK(c, hipSetDevice(c->device));
+        // column indices sorted inside every row (a sorted host copy where the caller's are not); duplicates are refused
+        if (csr_sort_rows(indptr, indices, data, c->n, nnz, dtype_size(data_dtype), sidx, sval)) { indices = sidx.data(); data = sval.data(); }
+        bad = csr_duplicates(indptr, indices, c->n);
+        if (!bad.empty()) return fail(c, RRI_ERR_INVALID, "%s", bad.c_str());
+        s = csr_to_device(c, indptr, indices, data, nnz, data_dtype, dv);
+        if (s != RRI_OK) return s;
+    }
     // from here on the store is being replaced: the uniform rows were rows of the X that goes, and a new X has none -- cleared
     // first, so that an upload that fails further down leaves no list beside a store it does not describe
     dev_release(c, c->uni_rows);
     c->uni_n = 0;
     c->uni_value = 0.0;
-    s = build_sp_store(c, indptr, indices, nnz, data_dtype, dv, sp_target_items(c->n_cu, true));
+    s = resident ? build_sp_store_device(c, dv, resident->values, nnz, sp_target_items(c->n_cu, true))
+                 : build_sp_store(c, indptr, indices, nnz, data_dtype, dv, sp_target_items(c->n_cu, true));
     if (s != RRI_OK) return s;
     if (nnz > 0)
         DISPATCH(c, for (int w = 0; w < 2; ++w)
@@ -2741,6 +2766,7 @@ namespace {
 rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indices, int64_t nnz, int32_t data_dtype,
                           CsrDev& dv, int target_items) {
     i64 longest_row = 0;
+    c->spb_ms = 0.0;
     dev_release(c, c->sp_rowptr); dev_release(c, c->sp_col); dev_release(c, c->sp_x); dev_release(c, c->sp_e);
     dev_adopt(c, c->sp_rowptr, dv.indptr);     // from here on they are the handle's, whatever fails below
     dev_adopt(c, c->sp_col, dv.indices);
@@ -3665,6 +3691,13 @@ struct rri_corpus {
     double ingest_ms = 0.0;
 };
 std::atomic<long long> g_corpora{0}, g_corpus_bytes{0};
+// the corpora alive in the process: what rri_upload_X_corpus holds a caller's pointer against before it reads through it
+std::mutex g_corpus_lock;
+std::set<const rri_corpus*> g_corpus_alive;
+bool corpus_alive(const rri_corpus* k) {
+    std::lock_guard<std::mutex> hold(g_corpus_lock);
+    return k && g_corpus_alive.count(k) != 0;
+}
 
 namespace {
 // grid of a grid-stride kernel of 256 threads over `items`
@@ -3875,12 +3908,20 @@ rri_status rri_corpus_create(rri_ctx* c, rri_corpus** out, int64_t n_rows, int64
     k->ingest_ms = ms;
     g_corpora += 1;
     g_corpus_bytes += (long long)k->bytes;
+    {
+        std::lock_guard<std::mutex> hold(g_corpus_lock);
+        g_corpus_alive.insert(k);
+    }
     *out = k;
     return RRI_OK;
 }
 
 rri_status rri_corpus_destroy(rri_corpus* k) {
     if (!k) return RRI_ERR_INVALID;
+    {
+        std::lock_guard<std::mutex> hold(g_corpus_lock);
+        g_corpus_alive.erase(k);
+    }
     int before = 0;
     const bool had = hipGetDevice(&before) == hipSuccess;
     (void)hipSetDevice(k->device);
@@ -3953,6 +3994,173 @@ rri_status rri_corpus_entries_loglik(rri_ctx* c, const rri_corpus* k, const int6
     for (i64 q = 0; rows && q < count; ++q)
         if (rows[q] < 0 || rows[q] >= c->n) return fail(c, RRI_ERR_INVALID, "rows[%lld] = %lld is out of range", (long long)q, (long long)rows[q]);
     return loglik_entries(c, rows, count, k->h_indptr.data(), nullptr, nullptr, k->indices, k->values, floor, ll_out, mass_out, floored_out);
+}
+
+// ---- the blocked store of a CSR-X handle from a corpus (rri_spbuild.hpp has the steps, rri_spbuild_kernels.hpp the kernels) --------
+namespace {
+// build_sp_store for canonical arrays that are on the device: dv.indptr / dv.indices, the handle's own copies, are taken over as
+// the canonical CSR, `values` (float64, device) is converted into sp_x, and both blocked copies are counted, scanned, claimed and
+// sorted there.  What crosses to the host is segptr, 8 nblk (nseg + 1) bytes per copy, from which the work items are cut by the
+// cutter of the host route (sp_cut_work) and the segments too long for a wave's sort are listed; and the longest row.
+rri_status build_sp_store_device(rri_ctx* c, CsrDev& dv, const double* values, int64_t nnz, int target_items) {
+    c->spb_ms = 0.0;
+    dev_release(c, c->sp_rowptr); dev_release(c, c->sp_col); dev_release(c, c->sp_x); dev_release(c, c->sp_e);
+    dev_adopt(c, c->sp_rowptr, dv.indptr);     // from here on they are the handle's, whatever fails below
+    dev_adopt(c, c->sp_col, dv.indices);
+    HIPCHK(c, dev_alloc(c, c->sp_x, (size_t)std::max<i64>(nnz, 1) * c->es));
+    if (nnz > 0) launch_convert(c, RRI_F64, c->dtype, false, values, nnz, c->sp_x, nnz, 1, nnz);
+    DevTmp tlong;
+    HIPCHK(c, tlong.alloc(sizeof(int)));
+    HIPCHK(c, hipMemsetAsync(tlong.p, 0, sizeof(int), c->stream));
+    EventPair ev[4];          // per copy: count and scan; fill, claim and sort -- the phases between two reads of the host
+    for (EventPair& p : ev) HIPCHK(c, p.create());
+    const i64* rowptr = c->sp_rowptr;
+    const int* col = c->sp_col;
+    for (int w = 0; w < 2; ++w) {
+        rri_ctx::SpCopy& cp = c->sp[w];
+        dev_release(c, cp.segptr); dev_release(c, cp.idx); dev_release(c, cp.val); dev_release(c, cp.perm); dev_release(c, cp.work);
+        SpDims dims;
+        dims.nblk = cp.nblk; dims.bw = cp.bw; dims.nseg = cp.nseg; dims.gdim = cp.gdim;
+        const i64 stride = cp.nseg + 1, flat = (i64)cp.nblk * stride, tiles = (flat + SPB_SCAN_TILE - 1) / SPB_SCAN_TILE;
+        HIPCHK(c, dev_alloc(c, cp.segptr, (size_t)flat * sizeof(i64), true));
+        DevTmp part;
+        HIPCHK(c, part.alloc((size_t)tiles * sizeof(i64)));
+        // 1, 2: count, padded scan
+        HIPCHK(c, hipEventRecord(ev[2 * w].a, c->stream));
+        if (w == 0)
+            hipLaunchKernelGGL(k_spb_count_rows, dim3(corpus_grid(c->n * cp.nblk)), dim3(256), 0, c->stream, rowptr, col, c->n, cp.nblk, cp.bw,
+                               stride, cp.segptr, (int*)tlong.p);
+        else if (nnz > 0)
+            hipLaunchKernelGGL(k_spb_count_cols, dim3(corpus_grid(nnz)), dim3(256), 0, c->stream, rowptr, col, c->n, (i64)nnz, cp.bw, stride,
+                               (u64*)cp.segptr);
+        hipLaunchKernelGGL(k_spb_scan_part, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const i64*)cp.segptr, flat, (i64*)part.p);
+        hipLaunchKernelGGL(k_spb_scan_top, dim3(1), dim3(1024), 0, c->stream, (i64*)part.p, tiles);
+        hipLaunchKernelGGL(k_spb_scan_apply, dim3((unsigned)tiles), dim3(256), 0, c->stream, cp.segptr, flat, (const i64*)part.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(ev[2 * w].b, c->stream));
+        std::vector<i64> h_seg((size_t)flat);
+        HIPCHK(c, hipMemcpyAsync(h_seg.data(), cp.segptr, (size_t)flat * sizeof(i64), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        const i64 count = h_seg[(size_t)flat - 1];
+        if (count < nnz || count > nnz + 3 * (i64)cp.nblk * cp.nseg)
+            return fail(c, RRI_ERR_HIP, "the blocked copy %d counts %lld padded entries for %lld stored ones", w, (long long)count, (long long)nnz);
+        const size_t cntp = (size_t)std::max<i64>(count, 4);
+        cp.count = count;
+        HIPCHK(c, dev_alloc(c, cp.idx, cntp * sizeof(unsigned short)));
+        HIPCHK(c, dev_alloc(c, cp.val, cntp * c->es, true));
+        HIPCHK(c, dev_alloc(c, cp.perm, cntp * sizeof(int)));
+        // the work items, and the segments of copy 1 that a workgroup sorts, by the power of two they are padded to
+        std::vector<SpWork> work;
+        sp_cut_work(h_seg.data(), dims, w, target_items, work);
+        cp.nwork = (int)work.size();
+        cp.lps = sp_lanes_per_segment(nnz, dims);
+        HIPCHK(c, dev_alloc(c, cp.work, std::max<size_t>(1, work.size()) * sizeof(SpWork)));
+        if (!work.empty()) HIPCHK(c, hipMemcpyAsync(cp.work, work.data(), work.size() * sizeof(SpWork), hipMemcpyHostToDevice, c->stream));
+        std::vector<std::vector<i64>> lists;          // [log2 of the padded length]
+        std::vector<i64> all;
+        if (w == 1 && nnz > 0) {
+            for (int b = 0; b < cp.nblk; ++b)
+                for (i64 sg = 0; sg < cp.nseg; ++sg) {
+                    const i64 at = (i64)b * stride + sg, len = h_seg[(size_t)at + 1] - h_seg[(size_t)at];
+                    if (spbuild_wave_sorted(len)) continue;
+                    if (len > CORPUS_LDS_MAX) return fail(c, RRI_ERR_HIP, "a segment of %lld entries exceeds the block width", (long long)len);
+                    int lg = 0;
+                    while ((1ll << lg) < corpus_pad(len)) ++lg;
+                    if (lists.size() <= (size_t)lg) lists.resize((size_t)lg + 1);
+                    lists[(size_t)lg].push_back(at);
+                }
+            for (const auto& l : lists) all.insert(all.end(), l.begin(), l.end());
+        }
+        DevTmp keys, fill, tlist;
+        // 3, 4: the pads, the claim, the sort
+        HIPCHK(c, hipEventRecord(ev[2 * w + 1].a, c->stream));
+        hipLaunchKernelGGL(k_spb_fill, dim3(corpus_grid((i64)cntp)), dim3(256), 0, c->stream, cp.idx, cp.perm, (i64)cntp, cp.bw);
+        if (nnz > 0 && w == 0) {
+            hipLaunchKernelGGL(k_spb_claim_rows, dim3(corpus_grid(nnz)), dim3(256), 0, c->stream, rowptr, col, c->n, (i64)nnz, cp.nblk, cp.bw,
+                               stride, (const i64*)cp.segptr, cp.idx, cp.perm);
+        } else if (nnz > 0) {
+            const size_t nfill = (size_t)cp.nblk * (size_t)cp.nseg;
+            HIPCHK(c, keys.alloc(cntp * sizeof(u64)));
+            HIPCHK(c, fill.alloc(nfill * sizeof(int)));
+            HIPCHK(c, hipMemsetAsync(keys.p, 0xff, cntp * sizeof(u64), c->stream));        // CORPUS_KEY_PAD everywhere
+            HIPCHK(c, hipMemsetAsync(fill.p, 0, nfill * sizeof(int), c->stream));
+            hipLaunchKernelGGL(k_spb_claim_cols, dim3(corpus_grid(nnz)), dim3(256), 0, c->stream, rowptr, col, c->n, (i64)nnz, cp.bw, stride,
+                               cp.nseg, (const i64*)cp.segptr, (int*)fill.p, (u64*)keys.p);
+            hipLaunchKernelGGL(k_spb_sort_wave, dim3(corpus_grid((i64)nfill * 64)), dim3(256), 0, c->stream, (const i64*)cp.segptr, (i64)nfill,
+                               cp.nseg, (const u64*)keys.p, cp.idx, cp.perm, cp.bw);
+            HIPCHK(c, hipGetLastError());
+            if (!all.empty()) {
+                HIPCHK(c, tlist.alloc(all.size() * sizeof(i64)));
+                HIPCHK(c, hipMemcpyAsync(tlist.p, all.data(), all.size() * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+                HIPCHK(c, allow_lds<k_spb_sort_block>(c, CORPUS_LDS_MAX * (int)sizeof(u64)));
+                const i64* dl = (const i64*)tlist.p;
+                for (size_t lg = 0; lg < lists.size(); ++lg) {
+                    const size_t cnt = lists[lg].size();
+                    if (!cnt) continue;
+                    const i64 P = 1ll << lg;
+                    hipLaunchKernelGGL(k_spb_sort_block, dim3((unsigned)cnt), dim3(P <= 1024 ? 256 : 1024), (size_t)P * sizeof(u64), c->stream, dl,
+                                       (const i64*)cp.segptr, P, (const u64*)keys.p, cp.idx, cp.perm, cp.bw);
+                    HIPCHK(c, hipGetLastError());
+                    dl += cnt;
+                }
+            }
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(ev[2 * w + 1].b, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // the host vectors and the temporaries go out of scope
+    }
+    int longest = 0;
+    HIPCHK(c, hipMemcpy(&longest, tlong.p, sizeof(int), hipMemcpyDeviceToHost));
+    double ms = 0.0;
+    for (EventPair& p : ev) {
+        float t = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&t, p.a, p.b));
+        ms += t;
+    }
+    c->spb_ms = ms;
+    c->nnz = nnz;
+    c->sp_max_row = longest;
+    return RRI_OK;
+}
+}  // namespace
+
+rri_status rri_upload_X_corpus(rri_ctx* c, const rri_corpus* k) {
+    CHECK_CTX(c);
+    REFUSE_RO(c, "X from a corpus");
+    if (!c->sparse_x)
+        return fail(c, RRI_ERR_INVALID, "%s", c->sparse ? sparse_data_refusal(c)
+                                                         : "rri_upload_X_corpus builds the store of an RRI_UNWEIGHTED_SPARSE handle (X kept as CSR): "
+                                                           "this handle keeps a dense X");
+    const bool alive = corpus_alive(k);
+    char why[200] = "";
+    const int bad = spbuild_check_corpus(alive, alive ? k->n_rows : 0, alive ? k->n_cols : 0, alive ? k->nnz : 0, alive ? k->device : 0, c->n,
+                                         c->d, c->device, why, sizeof why);
+    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+    // the rest is the CSR upload's own: copies on the device, the store built there, the uniform rows cleared, the cached state reset
+    const CorpusArrays resident{k->indptr, k->indices, k->values};
+    return upload_X_csr_kept(c, nullptr, nullptr, nullptr, k->nnz, RRI_F64, &resident);
+}
+
+rri_status rri_sparse_store_get(rri_ctx* c, int32_t which, int64_t* info, int32_t n_info, int64_t* segptr, uint16_t* idx, int32_t* perm,
+                                void* val, int32_t* work) {
+    CHECK_CTX(c);
+    if (which != 0 && which != 1) return fail(c, RRI_ERR_INVALID, "which = %d: a handle has the blocked copies 0 and 1", (int)which);
+    if (n_info < 0 || (n_info > 0 && !info)) return fail(c, RRI_ERR_INVALID, "info is NULL with %d fields asked for", (int)n_info);
+    const rri_ctx::SpCopy& cp = c->sp[which];
+    if (!c->sparse || !c->have_X || !cp.segptr) return fail(c, RRI_ERR_INVALID, "the handle has no blocked store");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t f[RRI_SPARSE_STORE_INFO_FIELDS] = {cp.nblk, cp.bw, cp.nseg, cp.gdim, cp.count, cp.nwork, cp.lps, c->nnz, c->sp_max_row,
+                                                     (int64_t)std::llround(c->spb_ms * 1000.0)};
+    for (int i = 0; i < n_info && i < RRI_SPARSE_STORE_INFO_FIELDS; ++i) info[i] = f[i];
+    for (int i = RRI_SPARSE_STORE_INFO_FIELDS; i < n_info; ++i) info[i] = 0;
+    const size_t cntp = (size_t)std::max<i64>(cp.count, 4);
+    if (segptr) HIPCHK(c, hipMemcpyAsync(segptr, cp.segptr, (size_t)cp.nblk * (size_t)(cp.nseg + 1) * sizeof(i64), hipMemcpyDeviceToHost, c->stream));
+    if (idx) HIPCHK(c, hipMemcpyAsync(idx, cp.idx, cntp * sizeof(unsigned short), hipMemcpyDeviceToHost, c->stream));
+    if (perm) HIPCHK(c, hipMemcpyAsync(perm, cp.perm, cntp * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (val) HIPCHK(c, hipMemcpyAsync(val, cp.val, cntp * c->es, hipMemcpyDeviceToHost, c->stream));
+    if (work && cp.nwork > 0) HIPCHK(c, hipMemcpyAsync(work, cp.work, (size_t)cp.nwork * sizeof(SpWork), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RRI_OK;
 }
 
 rri_status rri_snapshot(rri_ctx* c) {

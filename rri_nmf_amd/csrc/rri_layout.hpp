@@ -213,6 +213,48 @@ inline int pass_keep(const DensePlan& p, int k, i64 ldw, size_t es, bool xp_vali
     return blocks >= (double)p.nrb ? p.nrb : (int)blocks;
 }
 
+// ---- the blocked store of a CSR pattern: work items -------------------------------------------------------------------------
+// Work items: runs of segments of one block, at most `target_items` in all and of equal entry count -- ONE round of
+// workgroups (a 1024-thread workgroup with the block's tables per CU).  Round 2 cut "about 3 x 256" items and got
+// 774-780: three rounds of the 256 CUs and a fourth for the last few, a quarter of every launch with the chip idle
+// (profiles/r03_sp_blk_probe.log: 138 -> 115 us per pass).  Every (block, segment) belongs to exactly one item --
+// also the empty ones, whose sums the consumers still read.  `segptr`: [nblk][nseg + 1], the padded prefix of the copy --
+// the host builder's (build_sp_copy) or the one the device builder left and the host read back (rri_spbuild.hpp): the one
+// cutter of both routes.
+inline void sp_cut_work(const i64* segptr, const SpDims& cp, int which, int target_items, std::vector<SpWork>& work) {
+    const i64 nseg = cp.nseg, stride = nseg + 1;
+    std::vector<i64> eb((size_t)cp.nblk);
+    i64 total = 0;
+    for (int b = 0; b < cp.nblk; ++b) {
+        const i64* row = segptr + (size_t)b * stride;
+        eb[(size_t)b] = row[nseg] - row[0];
+        total += eb[(size_t)b];
+    }
+    const i64 spare = std::max<i64>(0, (i64)target_items - cp.nblk);      // every block needs one item; the rest by share
+    for (int b = 0; b < cp.nblk; ++b) {
+        const i64* row = segptr + (size_t)b * stride;
+        i64 items_b = 1 + (total > 0 ? spare * eb[(size_t)b] / total : 0);
+        items_b = std::max<i64>(1, std::min<i64>(items_b, eb[(size_t)b] / 4096));      // no items of a few entries
+        i64 s0 = 0;
+        for (i64 j = 1; j <= items_b && s0 < nseg; ++j) {
+            i64 s1 = nseg;
+            if (j < items_b) {
+                const i64 want = row[0] + eb[(size_t)b] * j / items_b;     // first segment boundary at or past the j-th share
+                s1 = std::lower_bound(row + s0 + 1, row + nseg, want) - row;
+                s1 = std::min<i64>(std::max<i64>(s1, s0 + 1), nseg);
+            }
+            work.push_back(SpWork{b, (int)s0, (int)s1, which});
+            s0 = s1;
+        }
+        if (s0 < nseg) work.push_back(SpWork{b, (int)s0, (int)nseg, which});
+    }
+}
+// lanes per segment: 4 quads of 4 entries per lane and iteration
+inline int sp_lanes_per_segment(i64 nnz, const SpDims& cp) {
+    const i64 avg = nnz / std::max<i64>(1, (i64)cp.nblk * cp.nseg);
+    return avg >= 768 ? 64 : avg >= 384 ? 32 : avg >= 192 ? 16 : 8;
+}
+
 // ---- the blocked store of a CSR pattern: contents ------------------------------------------------------------------------
 // One blocked copy of a validated pattern (column indices strictly increasing in every row), on the host: counting sort, stable,
 // so offsets ascend inside a segment.  `target_items`: work items of the copy (SpWork.pad = the copy).
@@ -268,41 +310,8 @@ inline SpCopyHost build_sp_copy(const int64_t* indptr, const int32_t* indices, i
                 out.perm[(size_t)q] = (int)p;
             }
     }
-    // Work items: runs of segments of one block, at most `target_items` in all and of equal entry count -- ONE round of
-    // workgroups (a 1024-thread workgroup with the block's tables per CU).  Round 2 cut "about 3 x 256" items and got
-    // 774-780: three rounds of the 256 CUs and a fourth for the last few, a quarter of every launch with the chip idle
-    // (profiles/r03_sp_blk_probe.log: 138 -> 115 us per pass).  Every (block, segment) belongs to exactly one item --
-    // also the empty ones, whose sums the consumers still read.
-    {
-        std::vector<i64> eb((size_t)cp.nblk);
-        i64 total = 0;
-        for (int b = 0; b < cp.nblk; ++b) {
-            const i64* row = sp.data() + (size_t)b * stride;
-            eb[(size_t)b] = row[nseg] - row[0];
-            total += eb[(size_t)b];
-        }
-        const i64 spare = std::max<i64>(0, (i64)target_items - cp.nblk);      // every block needs one item; the rest by share
-        for (int b = 0; b < cp.nblk; ++b) {
-            const i64* row = sp.data() + (size_t)b * stride;
-            i64 items_b = 1 + (total > 0 ? spare * eb[(size_t)b] / total : 0);
-            items_b = std::max<i64>(1, std::min<i64>(items_b, eb[(size_t)b] / 4096));      // no items of a few entries
-            i64 s0 = 0;
-            for (i64 j = 1; j <= items_b && s0 < nseg; ++j) {
-                i64 s1 = nseg;
-                if (j < items_b) {
-                    const i64 want = row[0] + eb[(size_t)b] * j / items_b;     // first segment boundary at or past the j-th share
-                    s1 = std::lower_bound(row + s0 + 1, row + nseg, want) - row;
-                    s1 = std::min<i64>(std::max<i64>(s1, s0 + 1), nseg);
-                }
-                out.work.push_back(SpWork{b, (int)s0, (int)s1, w});
-                s0 = s1;
-            }
-            if (s0 < nseg) out.work.push_back(SpWork{b, (int)s0, (int)nseg, w});
-        }
-    }
-    // lanes per segment: 4 quads of 4 entries per lane and iteration
-    const i64 avg = nnz / std::max<i64>(1, (i64)cp.nblk * nseg);
-    out.lps = avg >= 768 ? 64 : avg >= 384 ? 32 : avg >= 192 ? 16 : 8;
+    sp_cut_work(sp.data(), cp, w, target_items, out.work);
+    out.lps = sp_lanes_per_segment(nnz, cp);
     return out;
 }
 

@@ -459,6 +459,39 @@ class RRIEngine(object):
         keep, args = self._csr_args(A)
         self._check(self._lib.rri_upload_X_csr(self._h, *args))
 
+    def upload_X_corpus(self, corpus):
+        """X of a sparse_x handle from a DeviceCorpus of the handle's shape and device (rri_upload_X_corpus): the canonical
+        arrays are copied device to device and the blocked store is built there -- the same bytes as upload_X_csr(
+        corpus.to_scipy()) leaves, without the download, the host's sorts and the uploads.  The corpus is not kept: it may be
+        closed right after the call."""
+        if tuple(corpus.shape) != (self.n, self.d):
+            raise ValueError('the corpus is %d x %d, the handle %d x %d' % (corpus.shape[0], corpus.shape[1], self.n, self.d))
+        self._check(self._lib.rri_upload_X_corpus(self._h, corpus._ptr()))
+
+    def sparse_store(self, which):
+        """Blocked copy `which` (0: rows as segments cut into column blocks, 1: columns as segments cut into row blocks) of a
+        handle that keeps X or its observation pattern as CSR (rri_sparse_store_get), for tests and probes: a dict with nblk, bw,
+        nseg, gdim, count, nwork, lps, nnz, longest_row, build_us (HIP-event time of a device build's kernels, 0 after a host
+        build) and the arrays segptr [nblk, nseg + 1], idx (uint16), perm (int32), val (the storage type) of max(count, 4)
+        entries each, work [nwork, 4]."""
+        info = (C.c_int64 * _capi.RRI_SPARSE_STORE_INFO_FIELDS)()
+        none = C.POINTER(C.c_int64)()
+        self._check(self._lib.rri_sparse_store_get(self._h, int(which), info, _capi.RRI_SPARSE_STORE_INFO_FIELDS, none, None, None, None, None))
+        names = ('nblk', 'bw', 'nseg', 'gdim', 'count', 'nwork', 'lps', 'nnz', 'longest_row', 'build_us')
+        out = dict(zip(names, (int(v) for v in info)))
+        cntp = max(out['count'], 4)
+        out['segptr'] = np.zeros((out['nblk'], out['nseg'] + 1), dtype=np.int64)
+        out['idx'] = np.zeros(cntp, dtype=np.uint16)
+        out['perm'] = np.zeros(cntp, dtype=np.int32)
+        out['val'] = np.zeros(cntp, dtype=self.dtype)
+        out['work'] = np.zeros((max(out['nwork'], 1), 4), dtype=np.int32)
+        self._check(self._lib.rri_sparse_store_get(
+            self._h, int(which), info, 0, out['segptr'].ctypes.data_as(C.POINTER(C.c_int64)),
+            out['idx'].ctypes.data_as(C.POINTER(C.c_uint16)), out['perm'].ctypes.data_as(C.POINTER(C.c_int32)),
+            out['val'].ctypes.data, out['work'].ctypes.data_as(C.POINTER(C.c_int32))))
+        out['work'] = out['work'][:out['nwork']]
+        return out
+
     def upload_mask_csr_pattern(self, A):
         """W_mat = [A != 0] of a scipy sparse matrix, bit-packed on the device"""
         keep, args = self._csr_args(A)

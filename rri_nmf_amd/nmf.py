@@ -58,8 +58,8 @@ import time
 import numpy as np
 import scipy.sparse
 
-from .engine import FrozenRows, RRIEngine, ZeroTotalRows
-from .initialization import initialize_nmf
+from .engine import DeviceCorpus, FrozenRows, RRIEngine, ZeroTotalRows
+from .initialization import _KNOWN as _KNOWN_INITS, initialize_nmf
 from .matrixops import normalize, proj_mat_to_simplex
 from .optimization import universal_stopping_condition
 
@@ -214,6 +214,15 @@ def _engine_with_problem(X, W_mat, k, sdt, device, sparse_pattern=None, schedule
     -- `sparse_pattern` True / False forces the choice --, else densified / bit-packed on the device (SURVEY.md 8f
     rank 3); dense inputs as they are.  Without weights, sparse_x_route decides whether X stays CSR on the device."""
     n, d = X.shape
+    if isinstance(X, DeviceCorpus):
+        # the canonical arrays are on the device: the handle copies them there and builds its blocked store there
+        eng = RRIEngine(n, d, k, dtype=sdt, device=device, sparse_x=True)
+        try:
+            eng.upload_X_corpus(X)
+        except Exception:
+            eng.close()
+            raise
+        return eng
     if W_mat is None and schedule == 'gram':
         xs = scipy.sparse.issparse(X)
         free = _device_free_bytes(device) if (sparse_X is None and xs) else 0
@@ -493,6 +502,32 @@ def _compute_update_T(X, W, T, t, store_gradients=False, ind_rows_to_store=None,
     return wR, nw, wR_store, nw_store
 
 
+def _check_corpus_call(X, sparse_X, W_mat, w_row, group, schedule, dtype, diagnostics, store_gradients, early_stop, gaussian,
+                       init, needs_init, device):
+    """nmf() with a DeviceCorpus as X: the corpus is kept as CSR on its device and nothing of it ever visits the host, so
+    whatever needs X there, or another store, is refused before any device call"""
+    if sparse_X is not None and not sparse_X:
+        raise ValueError('a DeviceCorpus X stays CSR on the device (sparse_X=True is implied): sparse_X=False would densify it')
+    host_stop = callable(early_stop) and getattr(early_stop, 'device_entries', None) is None
+    refused = [name for name, on in (('W_mat', W_mat is not None), ('w_row', w_row is not None), ('group=', group is not None),
+                                     ("schedule='residual'", schedule == 'residual'),
+                                     ('dtype=float16', dtype is not None and np.dtype(dtype) == np.float16),
+                                     ('dtype=uint8', dtype is not None and np.dtype(dtype) == np.uint8),
+                                     ('diagnostics', bool(diagnostics)), ('store_gradients', bool(store_gradients)),
+                                     ('an early_stop function without device_entries', host_stop),
+                                     ('the Gaussian mechanism', bool(gaussian)))
+               if on]
+    if refused:
+        raise ValueError('a DeviceCorpus X is kept as CSR on one device and never visits the host; it does not combine with %s'
+                         % ', '.join(refused))
+    if needs_init and init not in _KNOWN_INITS:
+        raise NotImplementedError('init=%r needs X on the host: a DeviceCorpus X is initialised through the device products '
+                                  '(one of %r), or pass W_in and T_in' % (init, _KNOWN_INITS[1:]))
+    if int(X.device) != int(device):
+        raise ValueError('the corpus lives on device %d, the call asks for device %d' % (X.device, device))
+    X._ptr()        # a closed corpus: ValueError
+
+
 def _sentinel(W, T):
     return {'W': W, 'T': T, 'obj_history': [-np.inf], 'iter_cputime': [0]}
 
@@ -532,12 +567,17 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     rtv['frozen'].  True: no rows are frozen yet -- nothing is set, the sweeps are those of a call without the option, the
     batch is absorbed all the same (the first batch of an online fit).  Unweighted calls in the Gram form with float32 /
     float64 or CSR storage on one device; no fix_W, w_row, early_stop, store_gradients or Gaussian mechanism."""
+    corpus = isinstance(X, DeviceCorpus)
+    if corpus:
+        _check_corpus_call(X, sparse_X, W_mat, w_row, group, schedule, dtype, diagnostics, store_gradients, early_stop,
+                           eps_gauss_t and delta_gauss_t, init, _is_empty(W_in) or _is_empty(T_in), device)
+        sparse_X = True
     if frozen is not None:
         if frozen is not True and not isinstance(frozen, FrozenRows):
             raise ValueError('frozen must be a FrozenRows, True (absorb this batch, nothing frozen yet) or None')
-        if frozen is not True and (frozen.k != k or frozen.d != np.shape(X)[1]):
+        if frozen is not True and (frozen.k != k or frozen.d != (X.shape if corpus else np.shape(X))[1]):
             raise ValueError('frozen statistics are for k = %d, d = %d; this call has k = %d, d = %d'
-                             % (frozen.k, frozen.d, k, np.shape(X)[1]))
+                             % (frozen.k, frozen.d, k, (X.shape if corpus else np.shape(X))[1]))
         refused = [name for name, on in (('W_mat', W_mat is not None), ("schedule='residual'", schedule == 'residual'),
                                          ('dtype=float16', dtype is not None and np.dtype(dtype) == np.float16),
                                          ('dtype=uint8', dtype is not None and np.dtype(dtype) == np.uint8),
@@ -632,7 +672,9 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     X_given, W_mat_given = X, W_mat
     X_seen = None       # the X of the host callbacks where it is not X itself (uint8 storage with device preprocessing)
     # scipy sparse X / 0-1 sparse W_mat are ingested as CSR (no host densification); row weights need a dense X
-    if scipy.sparse.issparse(X):
+    if corpus:
+        pass                                          # stays where it is: no host copy of X is made anywhere
+    elif scipy.sparse.issparse(X):
         X = X.tocsr() if w_row is None else X.toarray()
     elif sparse_X:
         X = scipy.sparse.csr_matrix(np.asarray(X))    # kept as CSR on the device
@@ -647,8 +689,9 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             (callable(early_stop) and getattr(early_stop, 'device_entries', None) is None)
         # (float16 storage: tf-idf and normalisation in float64 on the host, so that X is rounded once, at upload -- the device
         # route would round the raw X and then rewrite it)
-        route, csr_route = _route_of_call(X, spec, sparse_X, dtype, device, W_mat, w_row, host_callbacks, schedule, group,
-                                          uniform_rows)
+        # (a corpus: always the device; a row that normalisation would make dense shows there, and is refused below)
+        route, csr_route = ('device', True) if corpus else _route_of_call(X, spec, sparse_X, dtype, device, W_mat, w_row,
+                                                                          host_callbacks, schedule, group, uniform_rows)
         if uniform_rows and not csr_route:
             raise ValueError('uniform_rows=True needs an X kept as CSR on the device: pass sparse_X=True (the automatic route '
                              'densifies this X)')
@@ -662,7 +705,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             if n_empty:
                 raise ValueError('%d row(s) of X are empty: normalisation would make them dense (1/d), which dtype=uint8 cannot '
                                  'store; drop them or choose a floating-point dtype' % n_empty)
-    elif uniform_rows and not _route_of_call(X, (False, False), sparse_X, dtype, device, W_mat, w_row, False, schedule, group)[1]:
+    elif uniform_rows and not corpus and not _route_of_call(X, (False, False), sparse_X, dtype, device, W_mat, w_row, False, schedule, group)[1]:
         raise ValueError('uniform_rows=True needs an X kept as CSR on the device: pass sparse_X=True (the automatic route '
                          'densifies this X)')
     n, d = X.shape
@@ -755,6 +798,9 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             try:
                 idf = eng.preprocess(uniform_rows=True, **device_spec) if uniform_rows else eng.preprocess(**device_spec)
             except ZeroTotalRows as exc:
+                if corpus:      # there is no host matrix to fall back to
+                    raise ValueError('%s: pass uniform_rows=True, which keeps such rows of a DeviceCorpus beside its pattern '
+                                     'on the device' % exc)
                 if counts:      # (rows made only of terms that occur in every document: their tf-idf total is 0)
                     raise ValueError('%d row(s) of X have a tf-idf total below 1e-10: normalisation would make them dense (1/d), '
                                      'which dtype=uint8 cannot store' % exc.count)
@@ -769,13 +815,14 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
                 sdt = _storage_dtype(X, dtype)
                 eng = _engine_with_problem(X, W_mat, k, sdt, device, sparse_pattern, schedule, True)    # CSR again
         X_init = X
+        if corpus or device_spec is not None:
+            on_device = True                 # this X exists only on the device
+            X_init = _ResidentX(eng)
         if device_spec is not None:
             if reused:
                 idf = resident.idf
             rtv['idf'] = idf
             device_spec = {'tfidf': idf if idf is not None else False, 'normalize': device_spec['normalize']}
-            on_device = True                 # the preprocessed X exists only on the device
-            X_init = _ResidentX(eng)
             if counts and host_callbacks:
                 # what the callbacks are shown: the matrix the handle factorises, rebuilt from its scales in the handle's own order
                 rscale, cscale = eng.X_scales()

@@ -347,6 +347,8 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
 def _all_nonnegative(X):
     """np.all(X >= 0) (sklearn_interface.py:251) without the boolean copy of X, and for a large dense array on several threads
     (numpy's reductions release the GIL): 0.2 s of a 1.8 s fit at 100000 x 10000 went into the plain form.  NaN fails, as there."""
+    if isinstance(X, DeviceCorpus):     # counted on the device when the corpus was made
+        return X.negatives == 0
     if sp.issparse(X):          # the stored values (scipy refuses `>= 0` on a sparse matrix)
         return bool(np.all(X.tocsr().data >= 0))
     if not isinstance(X, np.ndarray) or X.ndim != 2 or X.size < (1 << 24):
@@ -416,7 +418,7 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
         """keep_resident on a scipy sparse X: nmf() keeps a handle when the preprocessing asked for runs on the device
         (nmf.preprocess_route); where it runs on the host -- a CSR handle and an empty row to normalise, without
         nmf_kwargs' uniform_rows=True -- there is no holder, as for every sparse X before the CSR handle preprocessed on the device"""
-        if not sp.issparse(X):
+        if not sp.issparse(X):      # (a DeviceCorpus too: whatever is asked for runs on the device)
             return True
         spec = _nmf_module._preprocess_spec(kw.get('preprocess'))
         if spec is None:
@@ -504,6 +506,8 @@ class NMF_TM_Estimator(_FactorPair, sklearn.base.BaseEstimator, sklearn.base.Tra
     def score(self, X, y=None):
         """R^2 of the reconstruction of new documents (sklearn_interface.py:339-345); the residual sum of squares
         is taken on the device (rri_objective) instead of through an n x d product on the host"""
+        if isinstance(X, DeviceCorpus):
+            raise TypeError('score() centres X on the host: it takes an array, not a DeviceCorpus (corpus.to_scipy().toarray())')
         sst = ((X - np.mean(X, axis=0)) ** 2).sum()
         W = self.transform(X)
         calc = _nmf_module.TrueObjComputer(np.asarray(X), W, self.T, 0, 0, 0, 0, None, None)
