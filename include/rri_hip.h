@@ -474,7 +474,9 @@ rri_status rri_csr_scale_X(rri_ctx* ctx, const double* col_scale, int32_t normal
  *                             (float64, as matrixops.py:146 writes it).  *uniform_rows_out = |U| (may be NULL).  Without
  *                             normalize_rows there are no totals and no uniform rows.
  * On a handle that HAS uniform rows rri_csr_scale_X, rri_csr_scale_X_uniform and rri_csr_column_positive_counts answer
- * RRI_ERR_INVALID and leave X alone: a second preprocessing of such an X is not built. */
+ * RRI_ERR_INVALID and leave X alone: a second preprocessing of such an X is not built.  While frozen statistics are set (below)
+ * rri_set_uniform_rows with count > 0, and rri_csr_scale_X_uniform where rows would be collected, answer RRI_ERR_UNSUPPORTED
+ * and change nothing: a handle never has both. */
 rri_status rri_set_uniform_rows(rri_ctx* ctx, const int32_t* rows, int64_t count, double value);
 rri_status rri_get_uniform_rows(rri_ctx* ctx, int32_t* rows_out, int64_t capacity, int64_t* count_out, double* value_out);
 rri_status rri_csr_scale_X_uniform(rri_ctx* ctx, const double* col_scale, int32_t normalize_rows, int64_t* uniform_rows_out);
@@ -559,7 +561,8 @@ rri_status rri_objective_parts(rri_ctx* ctx, double out[3]);
  * of topic t (rri_apply_reset_max_resid, rri_apply_reset_vectors) zeroes row t of B, row and column t of A and s[t]: W[:,t] = 0
  * of nmf.py:775 on the frozen rows; only the handle's own rows are reset candidates.
  * Handles: RRI_UNWEIGHTED with RRI_F32 or RRI_F64 storage, and RRI_UNWEIGHTED_SPARSE without uniform rows.
- * RRI_ERR_UNSUPPORTED, with nothing changed: weighted handles, RRI_UNWEIGHTED_RESIDUAL, RRI_F16 and RRI_U8, uniform rows, an
+ * RRI_ERR_UNSUPPORTED, with nothing changed: weighted handles, RRI_UNWEIGHTED_RESIDUAL, RRI_F16 and RRI_U8, uniform rows (and,
+ * while statistics are set, rri_set_uniform_rows with count > 0 and an rri_csr_scale_X_uniform that would collect rows), an
  * attached communicator (and rri_attach_comm while statistics are set); rri_sweep, rri_update_T_row, rri_topic_reduce_local
  * and rri_topic_finish with fix_W while statistics are set (the W[:,t] *= nt1 of nmf.py:450-452 would have to reach the frozen
  * rows).  Arguments are checked before any HIP call. */

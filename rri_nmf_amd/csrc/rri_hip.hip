@@ -4724,6 +4724,9 @@ rri_status rri_csr_scale_X(rri_ctx* c, const double* col_scale, int32_t normaliz
             *zero_rows_out = (int64_t)zero_rows;
             return RRI_OK;
         }
+        // frozen statistics and uniform rows do not go together (frozen_refusal, the other order): nothing has been written
+        if (zero_rows > 0 && c->fzB)
+            return fail(c, RRI_ERR_UNSUPPORTED, "frozen statistics are set and %llu rows would become uniform rows: clear the statistics first", zero_rows);
         if (zero_rows > 0) {              // their list, in row order (k_spu_collect), before anything is written
             const size_t list_bytes = ((size_t)c->n * sizeof(int) + 7) & ~(size_t)7;      // the count sits behind the list, aligned
             HIPCHK(c, list.alloc(list_bytes + sizeof(i64)));
@@ -4779,6 +4782,8 @@ rri_status rri_set_uniform_rows(rri_ctx* c, const int32_t* rows, int64_t count, 
         if (u[(size_t)q] < 0 || (i64)u[(size_t)q] >= c->n) return fail(c, RRI_ERR_INVALID, "uniform row %d is out of range (n = %lld)", (int)u[(size_t)q], (long long)c->n);
         if (q > 0 && u[(size_t)q] == u[(size_t)q - 1]) return fail(c, RRI_ERR_INVALID, "uniform row %d is listed twice", (int)u[(size_t)q]);
     }
+    // frozen statistics and uniform rows do not go together (frozen_refusal, the other order): nothing is changed
+    if (count > 0 && c->fzB) return fail(c, RRI_ERR_UNSUPPORTED, "frozen statistics are set: clear them before rows are declared uniform");
     HIPCHK(c, hipSetDevice(c->device));
     if (count == 0 && c->uni_n == 0) return RRI_OK;      // nothing to clear: nothing changes, nothing is dropped
     DevTmp t;

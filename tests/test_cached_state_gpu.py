@@ -15,6 +15,29 @@ handle's own W and T before every operation, so a failure names the operation an
 Tolerances and what the operations are: the docstring of tests/cs_cases.py.  That a stale value cannot hide under them is
 tests/test_cached_state_cases_cpu.py's to show.
 
+Frozen statistics, uniform rows and an X built from a DeviceCorpus came after that table; rri_frozen_set / _absorb call no
+changed() on purpose, rri_set_uniform_rows and rri_csr_scale_X_uniform reach one through rri_csr_scale_X, rri_upload_X_corpus
+through upload_X_csr_kept.  The model holds all three, four flavours draw them into sequences ('gram-frozen' under RRI_ONCHIP=1,
+'gram-frozen-fp32', 'csr-frozen', 'csr-uniform'), and the directed cases below put each between the operations that fill and use
+the carry, the pending column verdict, the cross terms, the tracked objective, Qt and ||X||^2.  That these cases can fail was
+checked with four mutations of rri_hip.hip, one at a time, the whole file run against each (every failure a wrong number or a
+wrong verdict, none a fault):
+  1. `!c->fzB` dropped from the tracked-objective condition of rri_objective: both cases of
+     test_tracked_objective_and_persistent_launches_follow_the_statistics fail (objective() right behind set_frozen answers
+     without the frozen rows' share, off by 18 % and more), and test_random_sequence[gram-frozen-4] and [gram-frozen-fp32-17];
+  2. `!c->fzB` dropped from the k_trow_small condition of enqueue_T_half: 16 of the 20 cases of
+     test_statistics_change_between_producer_and_consumer (all but xy-set and fixed_T, which run no free T-row step under
+     statistics), test_column_verdict_with_and_without_statistics, test_carry_after_a_borrower[absorb-sweep] and its CSR twin,
+     test_uniform_rows_behind_statistics_are_refused (the sweep behind the refusal), the [clear] case of the tracked-objective
+     test (its sweep under statistics) and 52 random sequences of the three flavours with statistics (W off by 4e-3 .. 3e-2);
+  3. changed(c, CH_X) taken out of the end of rri_csr_scale_X: all 15 set_uniform_rows cases of
+     test_a_change_of_X_beside_the_pattern_drops_what_came_from_X (value, list and clear, each for x_sq, xy, q and both carries),
+     its preprocess_csr_uniform-x_sq and -q cases, 9 random sequences of 'csr-uniform' and 2 of 'csr-frozen' (preprocess_csr);
+  4. wcheck_now without the addend s[t] (k_frozen_add_tail not launched): both cases of
+     test_column_verdict_with_and_without_statistics end the sweep under statistics in the error the oracle has only after
+     clear_frozen.
+No case failed on the unmodified library.
+
 Reference of the two earlier sequences: the CPU oracle, chained call by call with W_in / T_in, eps_stop=-1, in float64.  Tolerance: relfro < 1e-9 on W and
 on T of a float64 handle (summation order only, as tests/test_residual_gpu.py between two float64 runs).  A stale Qt cannot
 hide under it: given the T of the first fixed call in place of the current one, the oracle's last call ends with a W that is
@@ -109,15 +132,16 @@ def run_case(monkeypatch, flavour, ops, raises=None):
     for key, val in cs.FLAVOURS[flavour]['env'].items():
         monkeypatch.setenv(key, val)                       # read at rri_create
     lines = []
+    onchip = cs.FLAVOURS[flavour]['env'].get('RRI_ONCHIP') == '1'      # 'gram-onchip' and 'gram-frozen'
     e = cs.make_engine(flavour)
     try:
-        if flavour == 'gram-onchip':
+        if onchip:
             assert e.onchip_info()[0], '700 x 333 float64 is not eligible for the register-resident sweep'
         try:
             answers = cs.run_sequence(e, flavour, ops, log=lines.append, raises=raises)
         finally:
             print('\n'.join(lines))
-        if flavour == 'gram-onchip':
+        if onchip:
             launches, want = e.onchip_info()[1], cs.persistent_sweeps(ops)
             print('persistent launches: %d of %d free sweeps' % (launches, want))
             assert launches >= (want if e.onchip_fallbacks() == 0 else min(want, 1)), (launches, want, e.onchip_fallbacks())
@@ -195,14 +219,35 @@ def test_explicit_residual_across_the_form_switch(monkeypatch):
 
 
 @pytest.mark.parametrize('then', ['sweep', 'update_T_row'])
-@pytest.mark.parametrize('borrower', ['Xt_times', 'column_positive_counts', 'range_finder', 'X_times'])
+@pytest.mark.parametrize('borrower', ['Xt_times', 'column_positive_counts', 'range_finder', 'X_times'] + cs.BORROWERS + ['absorb'])
 def test_carry_after_a_borrower(monkeypatch, borrower, then):
     """carry_valid / carry_topic: after a free sweep Zpart / Gpart hold topic 0's partial sums; a borrower runs, then sweep(1) or
     update_T_row(0).  Only column_positive_counts tells: it sums into Zpart and reduces into red, and with CH_SCRATCH taken out
     of changed() its two cases fail (T off by 4e+1).  rri_Xt_times and rri_range_finder say CH_SCRATCH but keep their partial
     sums in a buffer of their own (DevTmp zm), and rri_X_times on a dense handle calls no changed() at all: their cases show
-    that the carry survives them, which is all they can show"""
+    that the carry survives them, which is all they can show.  The evaluation calls (topn_rows, rank_entries, entries_loglik,
+    cooccurrence_counts, masked_rmse, argmax_rows) and absorb promise to write nothing a later sweep reads: their answers are
+    checked against the handle's current W and T with each feature's own reference and bound (cs_cases.check_borrowed), W and T
+    must be bit for bit what they were, and the step that follows must be the model's"""
     directed(monkeypatch, 'carry-%s-%s' % (borrower, then))
+
+
+@pytest.mark.parametrize('then', ['sweep', 'update_T_row'])
+@pytest.mark.parametrize('borrower', cs.CORPUS_BORROWERS + ['absorb'])
+def test_carry_after_a_borrower_on_csr(monkeypatch, borrower, then):
+    """the same on a CSR handle, for the two calls that score a live DeviceCorpus (rri_corpus_entries_loglik,
+    rri_corpus_cooccurrence_counts; the corpus is closed after the call) and for absorb, which takes W^T X through the blocked
+    product behind rri_Xt_times"""
+    directed(monkeypatch, 'carry-%s-csr-%s' % (borrower, then))
+
+
+@pytest.mark.parametrize('stored_by', ['sweep', 'objective'])
+@pytest.mark.parametrize('flavour', ['weighted', 'pattern', 'residual'])
+@pytest.mark.parametrize('borrower', cs.BORROWERS)
+def test_maintained_residual_after_an_evaluation_call(monkeypatch, borrower, flavour, stored_by):
+    """resid_valid: sweep(1) [, objective()], an evaluation call, sweep(1) on the handles that keep a residual between calls: the
+    calls work on every flavour and must leave it alone"""
+    directed(monkeypatch, 'resid-%s-%s%s' % (borrower, flavour, '-after_objective' if stored_by == 'objective' else ''))
 
 
 def test_sweep_after_a_call_that_ended_in_an_error(monkeypatch):
@@ -236,6 +281,82 @@ def test_a_new_X_puts_the_scales_back_to_ones(monkeypatch, route):
 def test_fixed_T_products_after_scaling_a_bound_X(monkeypatch):
     """q_valid on bound memory: only a uint8 handle rescales a bound X (it writes the column scales, no matrix)"""
     directed(monkeypatch, 'q-scale_X-bound')
+
+
+# ---- frozen statistics, uniform rows, an X built from a DeviceCorpus -----------------------------------------------------------------
+@pytest.mark.parametrize('case', ['carry-set-sweep', 'carry-set-update_T_row', 'carry-clear-sweep', 'carry-other-sweep', 'xy-set', 'xy-clear',
+                                  'reset', 'rollback', 'online', 'fixed_T'])
+@pytest.mark.parametrize('store', ['plain', 'csr'])
+def test_statistics_change_between_producer_and_consumer(monkeypatch, store, case):
+    """rri_frozen_set / rri_frozen_absorb call no changed(): the statistics are read where a step uses them.  What one set of
+    statistics produced -- the carried sums of topic 0 and the pending column verdict of a free sweep, the cross terms of the
+    objective -- is consumed after they were set, cleared or replaced; a reset with no run paused zeroes topic t; a rollback
+    restores W and T only; a new X behind an absorb (the online loop) brings its own ||X||^2 and leaves c; sweeps with T fixed
+    ignore them.  The statistics are read back after every operation: bit for bit, after an absorb within the bound of
+    test_absorb_takes_the_sums_of_the_handles_rows"""
+    directed(monkeypatch, 'frozen-%s-%s' % (store, case))
+
+
+@pytest.mark.parametrize('store', ['plain', 'csr'])
+def test_column_verdict_with_and_without_statistics(monkeypatch, store):
+    """wcheck_now: under 'pen_a' column K - 1 of W, zero on the handle's rows, stays zero through its W half; with statistics whose
+    s[K - 1] > 0 the sweep ends without an error, after clear_frozen the next one ends in the oracle's"""
+    case = cs.CASES['frozen-%s-verdict' % store]
+    run_case(monkeypatch, case.flavour, case.ops, raises=case.raises)
+
+
+@pytest.mark.parametrize('case', ['set', 'clear'])
+def test_tracked_objective_and_persistent_launches_follow_the_statistics(monkeypatch, case):
+    """RRI_ONCHIP=1: sweep(2) persistent, objective(), set_frozen, objective() must carry the frozen rows' share; then sweep(1), no
+    persistent launch and onchip_info()[0] False, clear_frozen, sweep(1) persistent again, objective() (cs_cases.run_sequence
+    counts the launches of every sweep)"""
+    directed(monkeypatch, 'frozen-obj_track-' + case)
+
+
+@pytest.mark.parametrize('use', ['x_sq', 'xy', 'q', 'carry-sweep', 'carry-update_T_row'])
+@pytest.mark.parametrize('change', ['set_uniform_rows-value', 'set_uniform_rows-list', 'set_uniform_rows-clear', 'preprocess_csr_uniform',
+                                    'upload_X_corpus'])
+def test_a_change_of_X_beside_the_pattern_drops_what_came_from_X(monkeypatch, change, use):
+    """rri_set_uniform_rows (another value only, another list, a clear) and rri_csr_scale_X_uniform reach changed(c, CH_X) through
+    rri_csr_scale_X and write the list and the value after it; rri_upload_X_corpus goes through upload_X_csr_kept, and the
+    corpus is closed before the next operation.  Each between the operations that fill and use ||X||^2, the cross terms, Qt of a
+    fixed-T sweep and the carried sums of topic 0"""
+    name = '%s-%s' % (use, change) if not use.startswith('carry-') else 'carry-%s-%s' % (change, use[len('carry-'):])
+    directed(monkeypatch, name)
+
+
+def test_a_corpus_empties_the_list(monkeypatch):
+    directed(monkeypatch, 'uniform-emptied-by-upload_X_corpus')
+
+
+def test_the_store_built_from_a_corpus_is_that_of_upload_X_csr(monkeypatch):
+    """after rri_upload_X_corpus both blocked stores equal, byte for byte, those of a second handle given the canonical matrix
+    through rri_upload_X_csr"""
+    import scipy.sparse as sp
+    a = cs.make_engine('csr-frozen')
+    b = cs.make_engine('csr-frozen')
+    try:
+        m = cs.Model('csr-frozen')
+        op = cs.Op('upload_X_corpus', 3)
+        m.apply(op)
+        cs.apply_engine(a, m, op)
+        b.upload_X_csr(sp.csr_matrix(cs.corpus_raw(m.d, 3)[1]))
+        for which in (0, 1):
+            sa, sb = a.sparse_store(which), b.sparse_store(which)
+            for key in sa:
+                if key != 'build_us':
+                    assert np.array_equal(sa[key], sb[key]) and np.asarray(sa[key]).tobytes() == np.asarray(sb[key]).tobytes(), (which, key)
+    finally:
+        a.close(), b.close()
+
+
+@pytest.mark.parametrize('second', ['set_uniform_rows', 'preprocess_csr_uniform'])
+def test_uniform_rows_behind_statistics_are_refused(monkeypatch, second):
+    """statistics first, uniform rows second: RRI_ERR_UNSUPPORTED (NotImplementedError) as frozen_refusal() answers the other
+    order, and X (both blocked stores), the list, the statistics, W and T are bit for bit what they were (cs_cases.fingerprint);
+    the sweep(1) that follows is the model's"""
+    case = cs.CASES['mixed-' + second]
+    run_case(monkeypatch, case.flavour, case.ops, raises=case.raises)
 
 
 @pytest.mark.parametrize('seed', range(cs.n_seeds()))
