@@ -154,6 +154,14 @@ PROTOTYPES = {
     'rri_bench_stream_copy': (_I32, [_P, _I32, C.POINTER(_D)]),
 }
 
+# ... and every symbol include/rri_corpus_ops.h declares: corpora derived from a resident corpus.  A table of its own: these calls
+# keep and touch none of a handle's cached state
+CORPUS_OPS_PROTOTYPES = {
+    'rri_corpus_select': (_I32, [_P, _P, C.POINTER(_I64), _I64, C.POINTER(_I32), _I64, C.POINTER(_P)]),
+    'rri_corpus_column_counts': (_I32, [_P, _P, C.POINTER(_I64)]),
+    'rri_corpus_split': (_I32, [_P, _P, C.c_uint32, C.c_uint64, C.POINTER(_P), C.POINTER(_P)]),
+}
+
 _lib = None
 
 
@@ -214,7 +222,7 @@ def load_library(path=None):
         lib = C.CDLL(p)
     except OSError as e:  # e.g. libamdhip64 missing
         raise RRIHipUnavailable('cannot load %s: %s' % (p, e))
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in list(PROTOTYPES.items()) + list(CORPUS_OPS_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

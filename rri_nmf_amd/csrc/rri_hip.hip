@@ -48,6 +48,8 @@
 #include "rri_frozen_kernels.hpp"
 #include "rri_corpus_kernels.hpp"
 #include "rri_spbuild_kernels.hpp"
+#include "rri_corpus_ops.h"
+#include "rri_derive_kernels.hpp"
 
 using namespace rri;
 
@@ -3994,6 +3996,226 @@ rri_status rri_corpus_entries_loglik(rri_ctx* c, const rri_corpus* k, const int6
     for (i64 q = 0; rows && q < count; ++q)
         if (rows[q] < 0 || rows[q] >= c->n) return fail(c, RRI_ERR_INVALID, "rows[%lld] = %lld is out of range", (long long)q, (long long)rows[q]);
     return loglik_entries(c, rows, count, k->h_indptr.data(), nullptr, nullptr, k->indices, k->values, floor, ll_out, mass_out, floored_out);
+}
+
+// ---- corpora derived from a resident corpus (rri_derive.hpp has the semantics, rri_derive_kernels.hpp the kernels) ----------------
+namespace {
+// grid of a kernel that gives a wave to a piece, four pieces per workgroup, wave-stride beyond
+unsigned derive_grid(i64 pieces) { return (unsigned)std::max<i64>(1, std::min<i64>(16384, (pieces + 3) / 4)); }
+hipError_t derive_upload_bytes(DevTmp& t, const void* data, size_t bytes, hipStream_t s) {
+    const hipError_t e = t.alloc(at_least(bytes));
+    if (e != hipSuccess || !bytes) return e;
+    return hipMemcpyAsync(t.p, data, bytes, hipMemcpyHostToDevice, s);
+}
+// a host vector into a temporary of its own size (at least 8 bytes); the vector outlives the call's next synchronisation
+#define derive_upload(t, v, s) derive_upload_bytes((t), (v).data(), (v).size() * sizeof((v)[0]), (s))
+// the three arrays become a corpus that owns them; no HIP call, nothing fails in here
+rri_corpus* corpus_adopt(int device, i64 n_rows, i64 n_cols, i64 nnz, i64 neg, DevTmp& ptr, DevTmp& idx, DevTmp& val,
+                         std::vector<int64_t>&& h_ptr, double ms) {
+    rri_corpus* k = new rri_corpus();
+    k->device = device;
+    k->n_rows = n_rows; k->n_cols = n_cols; k->stored = nnz; k->nnz = nnz; k->neg = neg;
+    k->indptr = (i64*)ptr.p; k->indices = (int*)idx.p; k->values = (double*)val.p;
+    k->bytes = ptr.bytes + idx.bytes + val.bytes;
+    ptr.p = idx.p = val.p = nullptr;
+    k->h_indptr = std::move(h_ptr);
+    k->ingest_ms = ms;
+    g_corpora += 1;
+    g_corpus_bytes += (long long)k->bytes;
+    std::lock_guard<std::mutex> hold(g_corpus_lock);
+    g_corpus_alive.insert(k);
+    return k;
+}
+// the output offset of every piece and the indptr of the output from the pieces' counts: the pieces stand in output order
+void derive_offsets(const DerivePieces& pieces, const std::vector<int>& cnt, i64 rows_out, std::vector<int64_t>* piece_out,
+                    std::vector<int64_t>* indptr) {
+    piece_out->assign(pieces.row.size(), 0);
+    indptr->assign((size_t)rows_out + 1, 0);
+    i64 total = 0;
+    for (size_t p = 0; p < pieces.row.size(); ++p) {
+        (*piece_out)[p] = total;
+        total += cnt[p];
+        (*indptr)[(size_t)pieces.row[p] + 1] += cnt[p];
+    }
+    for (i64 r = 0; r < rows_out; ++r) (*indptr)[(size_t)r + 1] += (*indptr)[(size_t)r];
+}
+}  // namespace
+
+#define CHECK_DERIVE_CORPUS(c, k)                                                                                      \
+    do {                                                                                                               \
+        const bool alive_ = corpus_alive(k);                                                                           \
+        char why_[200] = "";                                                                                           \
+        if (derive_check_corpus(alive_, alive_ ? (k)->device : 0, (c)->device, why_, sizeof why_) != TOPN_REQ_OK)      \
+            return fail((c), RRI_ERR_INVALID, "%s", why_);                                                             \
+    } while (0)
+
+rri_status rri_corpus_select(rri_ctx* c, const rri_corpus* k, const int64_t* rows, int64_t m, const int32_t* keep, int64_t dk,
+                             rri_corpus** out) {
+    CHECK_CTX(c);
+    if (!out) return fail(c, RRI_ERR_INVALID, "the output pointer is NULL");
+    *out = nullptr;
+    CHECK_DERIVE_CORPUS(c, k);
+    char why[200] = "";
+    if (derive_check_select(k->n_rows, k->n_cols, rows, m, keep, dk, why, sizeof why) != TOPN_REQ_OK) return fail(c, RRI_ERR_INVALID, "%s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const i64 rows_out = rows ? m : k->n_rows, cols_out = keep ? dk : k->n_cols;
+    const DerivePieces pieces = derive_cut_pieces(k->h_indptr.data(), k->n_rows, rows, m);
+    const i64 np = (i64)pieces.row.size();
+    DevTmp tsrc, tlen, tmap, tcnt, tout, tstat, optr, oidx, oval;
+    EventPair ev[2];
+    for (EventPair& p : ev) HIPCHK(c, p.create());
+    HIPCHK(c, derive_upload(tsrc, pieces.src, c->stream));
+    HIPCHK(c, derive_upload(tlen, pieces.len, c->stream));
+    HIPCHK(c, tstat.alloc(DERIVE_STAT_WORDS * sizeof(u64)));
+    HIPCHK(c, hipMemsetAsync(tstat.p, 0, DERIVE_STAT_WORDS * sizeof(u64), c->stream));
+    std::vector<int> cnt(pieces.len);              // without keep a piece keeps all it has
+    std::vector<int> map;
+    HIPCHK(c, hipEventRecord(ev[0].a, c->stream));
+    if (keep) {
+        map.assign((size_t)k->n_cols, -1);
+        for (i64 j = 0; j < dk; ++j) map[(size_t)keep[j]] = (int)j;
+        HIPCHK(c, derive_upload(tmap, map, c->stream));
+        HIPCHK(c, tcnt.alloc(at_least((size_t)np * sizeof(int))));
+        if (np > 0) {
+            hipLaunchKernelGGL(k_derive_count, dim3(derive_grid(np)), dim3(256), 0, c->stream, (const i64*)tsrc.p, (const int*)tlen.p, np,
+                               (const int*)k->indices, (const int*)tmap.p, (int*)tcnt.p);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(cnt.data(), tcnt.p, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIPCHK(c, hipEventRecord(ev[0].b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<int64_t> piece_out, h_ptr;
+    derive_offsets(pieces, cnt, rows_out, &piece_out, &h_ptr);
+    const i64 nnz_o = h_ptr[(size_t)rows_out];
+    HIPCHK(c, derive_upload(tout, piece_out, c->stream));
+    HIPCHK(c, derive_upload(optr, h_ptr, c->stream));
+    HIPCHK(c, oidx.alloc(at_least((size_t)nnz_o * sizeof(int))));
+    HIPCHK(c, oval.alloc(at_least((size_t)nnz_o * sizeof(double))));
+    HIPCHK(c, hipEventRecord(ev[1].a, c->stream));
+    if (np > 0) {
+        hipLaunchKernelGGL(k_derive_write, dim3(derive_grid(np)), dim3(256), 0, c->stream, (const i64*)tsrc.p, (const int*)tlen.p,
+                           (const i64*)tout.p, np, (const int*)k->indices, (const double*)k->values, keep ? (const int*)tmap.p : (const int*)nullptr,
+                           (int*)oidx.p, (double*)oval.p, (u64*)tstat.p + DERIVE_STAT_NEG);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(ev[1].b, c->stream));
+    u64 h_stat[DERIVE_STAT_WORDS];
+    HIPCHK(c, hipMemcpyAsync(h_stat, tstat.p, sizeof h_stat, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double ms = 0.0;
+    for (EventPair& p : ev) {
+        float t = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&t, p.a, p.b));
+        ms += t;
+    }
+    *out = corpus_adopt(c->device, rows_out, cols_out, nnz_o, (i64)h_stat[DERIVE_STAT_NEG], optr, oidx, oval, std::move(h_ptr), ms);
+    return RRI_OK;
+}
+
+rri_status rri_corpus_column_counts(rri_ctx* c, const rri_corpus* k, int64_t* df_out) {
+    CHECK_CTX(c);
+    CHECK_DERIVE_CORPUS(c, k);
+    if (!df_out && k->n_cols > 0) return fail(c, RRI_ERR_INVALID, "the output pointer is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (k->n_cols == 0) return RRI_OK;
+    DevTmp tdf;
+    HIPCHK(c, tdf.alloc((size_t)k->n_cols * sizeof(u64)));
+    HIPCHK(c, hipMemsetAsync(tdf.p, 0, (size_t)k->n_cols * sizeof(u64), c->stream));
+    if (k->nnz > 0) {
+        hipLaunchKernelGGL(k_derive_column_counts, dim3(corpus_grid(k->nnz)), dim3(256), 0, c->stream, (const int*)k->indices, k->nnz, (u64*)tdf.p);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipMemcpyAsync(df_out, tdf.p, (size_t)k->n_cols * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RRI_OK;
+}
+
+rri_status rri_corpus_split(rri_ctx* c, const rri_corpus* k, uint32_t thr, uint64_t seed, rri_corpus** observed, rri_corpus** held) {
+    CHECK_CTX(c);
+    if (observed) *observed = nullptr;
+    if (held) *held = nullptr;
+    char why[200] = "";
+    if (!observed || !held) return derive_check_split(thr, observed != nullptr, held != nullptr, why, sizeof why), fail(c, RRI_ERR_INVALID, "%s", why);
+    CHECK_DERIVE_CORPUS(c, k);
+    if (derive_check_split(thr, true, true, why, sizeof why) != TOPN_REQ_OK) return fail(c, RRI_ERR_INVALID, "%s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const i64 nnz = k->nnz;
+    DevTmp tstat;
+    EventPair ev[3];
+    for (EventPair& p : ev) HIPCHK(c, p.create());
+    HIPCHK(c, tstat.alloc(DERIVE_STAT_WORDS * sizeof(u64)));
+    HIPCHK(c, hipMemsetAsync(tstat.p, 0xff, DERIVE_STAT_WORDS * sizeof(u64), c->stream));
+    // 1. the values are counts; nothing of the outputs exists before this verdict
+    HIPCHK(c, hipEventRecord(ev[0].a, c->stream));
+    if (nnz > 0) {
+        hipLaunchKernelGGL(k_split_check, dim3(corpus_grid(nnz)), dim3(256), 0, c->stream, (const double*)k->values, nnz, (u64*)tstat.p);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(ev[0].b, c->stream));
+    u64 h_stat[DERIVE_STAT_WORDS];
+    HIPCHK(c, hipMemcpyAsync(h_stat, tstat.p, sizeof h_stat, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int rule = 0; rule < SPLIT_RULES; ++rule)
+        if (h_stat[rule] != ~0ull) {
+            const i64 pos = (i64)h_stat[rule];
+            double v = 0.0;
+            HIPCHK(c, hipMemcpy(&v, k->values + pos, sizeof v, hipMemcpyDeviceToHost));
+            split_rule_text(rule, pos, v, why, sizeof why);
+            return fail(c, split_rule_code(rule) == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+        }
+    // 2. pass A: the held part of every entry, and what every piece leaves on either side
+    const DerivePieces pieces = derive_cut_pieces(k->h_indptr.data(), k->n_rows, nullptr, 0);
+    const i64 np = (i64)pieces.row.size();
+    DevTmp trow, tsrc, tlen, theld, tnh, tno, toh, too, hptr, hidx, hval, optr, oidx, oval;
+    HIPCHK(c, derive_upload(trow, pieces.row, c->stream));
+    HIPCHK(c, derive_upload(tsrc, pieces.src, c->stream));
+    HIPCHK(c, derive_upload(tlen, pieces.len, c->stream));
+    HIPCHK(c, theld.alloc(at_least((size_t)nnz * sizeof(int))));
+    HIPCHK(c, tnh.alloc(at_least((size_t)np * sizeof(int))));
+    HIPCHK(c, tno.alloc(at_least((size_t)np * sizeof(int))));
+    std::vector<int> nh((size_t)np), no((size_t)np);
+    HIPCHK(c, hipEventRecord(ev[1].a, c->stream));
+    if (np > 0) {
+        hipLaunchKernelGGL(k_split_held, dim3(derive_grid(np)), dim3(256), 0, c->stream, (const i64*)trow.p, (const i64*)tsrc.p, (const int*)tlen.p, np,
+                           (const int*)k->indices, (const double*)k->values, (unsigned)thr, (u64)seed, (int*)theld.p, (int*)tnh.p, (int*)tno.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(nh.data(), tnh.p, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(no.data(), tno.p, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipEventRecord(ev[1].b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // 3. the prefix sums on the host, then pass B writes both outputs once
+    std::vector<int64_t> piece_oh, piece_oo, h_hptr, h_optr;
+    derive_offsets(pieces, nh, k->n_rows, &piece_oh, &h_hptr);
+    derive_offsets(pieces, no, k->n_rows, &piece_oo, &h_optr);
+    const i64 nnz_h = h_hptr[(size_t)k->n_rows], nnz_o = h_optr[(size_t)k->n_rows];
+    HIPCHK(c, derive_upload(toh, piece_oh, c->stream));
+    HIPCHK(c, derive_upload(too, piece_oo, c->stream));
+    HIPCHK(c, derive_upload(hptr, h_hptr, c->stream));
+    HIPCHK(c, derive_upload(optr, h_optr, c->stream));
+    HIPCHK(c, hidx.alloc(at_least((size_t)nnz_h * sizeof(int))));
+    HIPCHK(c, hval.alloc(at_least((size_t)nnz_h * sizeof(double))));
+    HIPCHK(c, oidx.alloc(at_least((size_t)nnz_o * sizeof(int))));
+    HIPCHK(c, oval.alloc(at_least((size_t)nnz_o * sizeof(double))));
+    HIPCHK(c, hipEventRecord(ev[2].a, c->stream));
+    if (np > 0) {
+        hipLaunchKernelGGL(k_split_write, dim3(derive_grid(np)), dim3(256), 0, c->stream, (const i64*)tsrc.p, (const int*)tlen.p, (const i64*)toh.p,
+                           (const i64*)too.p, np, (const int*)k->indices, (const double*)k->values, (const int*)theld.p, (int*)hidx.p,
+                           (double*)hval.p, (int*)oidx.p, (double*)oval.p);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(ev[2].b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double ms = 0.0;
+    for (EventPair& p : ev) {
+        float t = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&t, p.a, p.b));
+        ms += t;
+    }
+    *observed = corpus_adopt(c->device, k->n_rows, k->n_cols, nnz_o, 0, optr, oidx, oval, std::move(h_optr), ms);
+    *held = corpus_adopt(c->device, k->n_rows, k->n_cols, nnz_h, 0, hptr, hidx, hval, std::move(h_hptr), ms);
+    return RRI_OK;
 }
 
 // ---- the blocked store of a CSR-X handle from a corpus (rri_spbuild.hpp has the steps, rri_spbuild_kernels.hpp the kernels) --------

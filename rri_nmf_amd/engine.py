@@ -159,7 +159,11 @@ class DeviceCorpus(object):
     shape; nnz (canonical entries); stored (entries as given); rows_rewritten, duplicates_merged, zeros_dropped (stored = nnz +
     duplicates_merged + zeros_dropped); negatives (canonical values below 0: entries_loglik refuses such a corpus); device_bytes;
     long_rows; ingest_ms (the HIP-event time of the ingest's kernels); device.  The corpus belongs to no handle: it serves every
-    RRIEngine on its device until close() (also: a context manager), and corpus_memory() counts it, device_memory() does not."""
+    RRIEngine on its device until close() (also: a context manager), and corpus_memory() counts it, device_memory() does not.
+
+    New corpora are derived from it on the device, the source staying as it is: take_rows(rows) and corpus[a:b] / corpus[mask] /
+    corpus[index_array] (row subsets, any order, repeats), select_words(keep), document_frequency(), prune_words(min_df, max_df,
+    max_words) and split_counts(held_out, random_state) (include/rri_corpus_ops.h)."""
 
     def __init__(self, X, device=0):
         import scipy.sparse as sp
@@ -243,11 +247,164 @@ class DeviceCorpus(object):
                                                    C.c_void_p(indptr), pdt, C.c_void_p(indices or None), idt,
                                                    C.c_void_p(values or None), vdt, on_device))
         del keep_alive
+        self._read_info()
+
+    def _read_info(self):
         info, ms = (C.c_int64 * _capi.RRI_CORPUS_INFO_FIELDS)(), C.c_double(0.0)
         self._lib.rri_corpus_info(self._c, info, _capi.RRI_CORPUS_INFO_FIELDS, C.byref(ms))
-        (_, _, self.stored, self.nnz, self.rows_rewritten, self.duplicates_merged, self.zeros_dropped, self.negatives,
+        (n_rows, n_cols, self.stored, self.nnz, self.rows_rewritten, self.duplicates_merged, self.zeros_dropped, self.negatives,
          self.device_bytes, self.long_rows) = (int(v) for v in info)
+        self.shape = (n_rows, n_cols)
         self.ingest_ms = float(ms.value)
+
+    @classmethod
+    def _adopt(cls, c, device, lib):
+        """the DeviceCorpus of a corpus the library has just made (rri_corpus_select, rri_corpus_split)"""
+        self = cls.__new__(cls)
+        self._c, self._lib, self.device = c, lib, int(device)
+        self._read_info()
+        return self
+
+    # ---- corpora derived on the device (include/rri_corpus_ops.h): the source is never modified, nothing of its size visits the host
+    @staticmethod
+    def _rows_of_index(index, n):
+        """what corpus[index] asks of take_rows: a slice (a step too), an int, a boolean mask of length n or an array of ints,
+        negative ones counting from the end as in numpy: the int64 row numbers"""
+        if isinstance(index, slice):
+            return np.arange(*index.indices(n), dtype=np.int64)
+        idx = np.asarray(index)
+        if idx.ndim > 1:
+            raise IndexError('a corpus is indexed by rows: a slice, an int, a mask or a one-dimensional array of ints')
+        if idx.dtype == np.bool_:
+            if idx.shape != (n,):
+                raise IndexError('a boolean mask of rows must have length %d, not %r' % (n, idx.shape))
+            return np.flatnonzero(idx).astype(np.int64)
+        if idx.size and idx.dtype.kind not in 'iu':
+            raise IndexError('row numbers must be integers, not %s' % idx.dtype)
+        idx = idx.reshape(-1).astype(np.int64)
+        if idx.size and (idx.min() < -n or idx.max() >= n):
+            raise IndexError('row %d is out of range for %d rows' % (idx[(idx < -n) | (idx >= n)][0], n))
+        return np.where(idx < 0, idx + n, idx)
+
+    @staticmethod
+    def _keep_of(keep, d):
+        """what select_words takes: ascending columns, or a boolean mask of length d: the int32 columns"""
+        keep = np.asarray(keep)
+        if keep.dtype == np.bool_:
+            if keep.shape != (d,):
+                raise ValueError('a boolean mask of words must have length %d, not %r' % (d, keep.shape))
+            return np.flatnonzero(keep).astype(np.int32)
+        if keep.size and keep.dtype.kind not in 'iu':
+            raise ValueError('columns must be integers, not %s' % keep.dtype)
+        keep = keep.reshape(-1).astype(np.int64)
+        if keep.size and (keep.min() < 0 or keep.max() >= d):
+            raise ValueError('column %d is out of range for %d columns' % (keep[(keep < 0) | (keep >= d)][0], d))
+        return keep.astype(np.int32)
+
+    @staticmethod
+    def _prune_selection(df, n_rows, min_df=1, max_df=1.0, max_words=None):
+        """the columns prune_words keeps, ascending (int32), from the document frequencies: lo <= df <= hi, an int bound being a
+        number of documents and a float in [0, 1] a share of the rows; where more than max_words remain, those of the largest df,
+        a tie going to the lower column"""
+        def bound(b, what):
+            if isinstance(b, (float, np.floating)):
+                if not 0.0 <= b <= 1.0:
+                    raise ValueError('%s = %r: a float bound is a share of the rows in [0, 1]' % (what, b))
+                return b * n_rows
+            if int(b) < 0:
+                raise ValueError('%s = %r is negative' % (what, b))
+            return int(b)
+        df = np.asarray(df, dtype=np.int64)
+        lo, hi = bound(min_df, 'min_df'), bound(max_df, 'max_df')
+        kept = np.flatnonzero((df >= lo) & (df <= hi))
+        if max_words is not None:
+            if int(max_words) < 0:
+                raise ValueError('max_words = %r is negative' % (max_words,))
+            if kept.size > int(max_words):        # stable on ascending columns: equal df keeps the lower column first
+                kept = np.sort(kept[np.argsort(-df[kept], kind='stable')[:int(max_words)]])
+        return kept.astype(np.int32)
+
+    @staticmethod
+    def _split_threshold(held_out):
+        """floor(held_out 2^32): the share of the tokens that is held out is this over 2^32"""
+        if not 0.0 < held_out < 1.0:
+            raise ValueError('held_out must lie inside (0, 1), not %r' % (held_out,))
+        thr = int(np.floor(float(held_out) * 4294967296.0))
+        if thr < 1:
+            raise ValueError('held_out = %r is below 2^-32: nothing would be held out' % (held_out,))
+        return thr
+
+    @staticmethod
+    def _split_seed(random_state):
+        """the 64-bit seed: an int in [0, 2^64), or two 32-bit words of a RandomState (low word first)"""
+        if isinstance(random_state, np.random.RandomState):
+            lo, hi = (int(v) for v in random_state.randint(0, 1 << 32, size=2, dtype=np.uint64))
+            return lo | (hi << 32)
+        if isinstance(random_state, (bool, np.bool_)) or not isinstance(random_state, (int, np.integer)):
+            raise TypeError('random_state must be an int in [0, 2^64) or a numpy RandomState, not %r' % (random_state,))
+        if not 0 <= int(random_state) < (1 << 64):
+            raise ValueError('random_state %r is outside [0, 2^64)' % (random_state,))
+        return int(random_state)
+
+    def _select(self, rows, keep):
+        """rri_corpus_select: rows None (all) or int64 row numbers, keep None (all) or ascending int32 columns"""
+        def arg(a, dtype, ctype):
+            if a is None:
+                return None, None, 0
+            a = np.ascontiguousarray(a, dtype=dtype)
+            hold = a if a.size else np.zeros(1, dtype=dtype)        # an empty list is a list: not NULL
+            return hold, hold.ctypes.data_as(C.POINTER(ctype)), int(a.size)
+        hold_r, rp, m = arg(rows, np.int64, C.c_int64)
+        hold_k, kp, dk = arg(keep, np.int32, C.c_int32)
+        out = C.c_void_p()
+        with self._handle() as eng:
+            eng._check(self._lib.rri_corpus_select(eng._h, self._ptr(), rp, m, kp, dk, C.byref(out)))
+        del hold_r, hold_k
+        return DeviceCorpus._adopt(out, self.device, self._lib)
+
+    def take_rows(self, rows):
+        """A new corpus of the rows `rows` (row numbers in [0, n), any order, repeats allowed) in that order, on the same device
+        (rri_corpus_select): the canonical form of A[rows], without a download or an upload of the entries."""
+        rows = np.asarray(rows)
+        if rows.size and rows.dtype.kind not in 'iu':
+            raise ValueError('row numbers must be integers, not %s' % rows.dtype)
+        return self._select(rows.reshape(-1).astype(np.int64), None)
+
+    def __getitem__(self, index):
+        """corpus[a:b], corpus[a:b:s], corpus[i], corpus[mask], corpus[index_array]: take_rows of those rows"""
+        return self._select(self._rows_of_index(index, self.shape[0]), None)
+
+    def select_words(self, keep):
+        """A new corpus of the columns `keep` -- ascending columns, or a boolean mask of length d --, renumbered to their places
+        in keep, on the same device: the canonical form of A[:, keep]."""
+        return self._select(None, self._keep_of(keep, self.shape[1]))
+
+    def document_frequency(self):
+        """(d,) int64: the rows with an entry in each column, counted on the device (rri_corpus_column_counts)"""
+        df = np.zeros(self.shape[1], dtype=np.int64)
+        with self._handle() as eng:
+            eng._check(self._lib.rri_corpus_column_counts(eng._h, self._ptr(), df.ctypes.data_as(C.POINTER(C.c_int64))))
+        return df
+
+    def prune_words(self, min_df=1, max_df=1.0, max_words=None):
+        """(corpus, kept): the corpus of the words whose document frequency lies in [min_df, max_df] -- an int is a number of
+        documents, a float in [0, 1] a share of the rows -- and, where more than max_words remain, of those with the largest
+        document frequency (a tie goes to the lower column); kept: their source columns, ascending.  The decision over the
+        d-sized frequency vector is made on the host; the entries stay on the device."""
+        kept = self._prune_selection(self.document_frequency(), self.shape[0], min_df, max_df, max_words)
+        return self.select_words(kept), kept
+
+    def split_counts(self, held_out=0.5, random_state=0):
+        """(observed, held), two corpora on the same device with observed + held == this corpus of counts: every token goes to
+        `held` with probability floor(held_out 2^32) / 2^32, independently, by a counter-based generator (Philox4x32-10) keyed
+        by random_state -- an int in [0, 2^64), or a RandomState that supplies two 32-bit words -- and counted by (column, row),
+        so the split depends on (row, column, count, seed) alone (rri_corpus_split).  ValueError for a held_out outside (0, 1)
+        or below 2^-32 and for values that are negative or not whole; NotImplementedError for a count above 2^20."""
+        thr, seed = self._split_threshold(held_out), self._split_seed(random_state)
+        observed, held = C.c_void_p(), C.c_void_p()
+        with self._handle() as eng:
+            eng._check(self._lib.rri_corpus_split(eng._h, self._ptr(), thr, seed, C.byref(observed), C.byref(held)))
+        return DeviceCorpus._adopt(observed, self.device, self._lib), DeviceCorpus._adopt(held, self.device, self._lib)
 
     def _handle(self):
         """a handle for the device, the stream and the error text: it holds nothing of the corpus's size"""

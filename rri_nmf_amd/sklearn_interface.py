@@ -655,7 +655,14 @@ def split_counts(X, held_out=0.5, random_state=0):
     observed + held == X: every token of a stored count goes to `held` with probability held_out, independently, so
     held = binomial(x, held_out) entry by entry (vectorised over the stored values, on the host).  For document completion:
     NMF_TM_Estimator.perplexity(held, observed=observed).  Explicit zeros are dropped from both parts.  ValueError for values
-    that are negative or not whole numbers, or for a held_out outside (0, 1)."""
+    that are negative or not whole numbers, or for a held_out outside (0, 1).
+
+    A DeviceCorpus is split where it lives: X.split_counts(held_out, random_state) returns two corpora on its device and nothing
+    of the corpus's size visits the host.  The two routes use different generators -- numpy's binomial here, a counter-based
+    Philox4x32-10 there --, so the same seed gives a different split on the two routes; both are the same binomial thinning and
+    equally valid, and each is reproducible from its seed."""
+    if isinstance(X, DeviceCorpus):
+        return X.split_counts(held_out=held_out, random_state=random_state)
     if not 0.0 < held_out < 1.0:
         raise ValueError('held_out must lie inside (0, 1), not %r' % (held_out,))
     A = sp.csr_matrix(X, copy=True)
