@@ -618,8 +618,12 @@ rri_status rri_onchip_info(rri_ctx* ctx, int32_t* eligible, int64_t* launches);
  *          of a blocked copy's work items)
  *   19     the read-only pass streams the packed 28-bit copy of an fp32 X (RRI_X_PACK; decided by the first sweep after X was set);
  *          20  the first top byte of its window;   21  tiles (8 rows x 1024 columns) with an element outside the window, read as
- *          fp32 (with more than 1/8 of them flagged there is no copy: 19 is 0, 21 and 22 say why);   22  tiles in all */
-#define RRI_LAYOUT_FIELDS 23
+ *          fp32 (with more than 1/8 of them flagged there is no copy: 19 is 0, 21 and 22 say why);   22  tiles in all
+ *   23     bits per element of the copy the pass streams: 28, 26 (the book-coded copy, rri_xnarrow.hpp; RRI_X_PACK=2, or unset and
+ *          few exceptions) or 0;   24  the book of the 26-bit copy, its seven exponent bytes in bytes 0..6, else 0;   25  elements
+ *          of X inside the window and outside the book (the exception entries of a 26-bit copy) as the last build counted them,
+ *          -1 where none was counted */
+#define RRI_LAYOUT_FIELDS 26
 rri_status rri_layout_info(rri_ctx* ctx, int64_t* out, int32_t n);
 /* The exchanges of that launch poll a bounded number of times.  When its workgroups cannot all run at once (a device shared
  * with another process, CUs masked away) the launch gives up, and the call does what the reference's sweep does under any

@@ -164,6 +164,14 @@ struct rri_ctx {
     // the packed copy of an fp32 X that the read-only pass streams instead of X (rri_xpack.hpp; xpack_ensure): 3.5 bytes per element
     unsigned char *xp = nullptr, *xp_flags = nullptr;   // the records; one flag byte per 8-row chunk and column group (tile)
     unsigned* xp_hmax = nullptr;                        // device: the largest top byte of X inside [1, 0x7e]
+    // ... or its 26-bit copy (rri_xnarrow.hpp; xnarrow_build): the fixed parts of the records, the directory of their exception
+    // entries, the entries.  xn_valid (with xp_valid): the passes read this one; flags, window and base are the 28-bit format's
+    unsigned char* xn = nullptr;
+    unsigned* xn_dir = nullptr;
+    unsigned short* xn_exc = nullptr;
+    bool xn_valid = false;
+    xnarrow::Books xn_books = {};
+    i64 xn_exceptions = -1;     // elements of X inside the window and outside the 7-entry book, as the histogram counts them; -1: not counted
     // RRI_U8: the X every kernel sees is (C[i][j] * cscale[j]) * rscale[i]; rscale[n], cscale[LD] (pad columns: 1), ones until set
     double *rscale = nullptr, *cscale = nullptr;
     bool xp_valid = false;      // the passes read xp: it was built from the X the handle holds and few enough tiles are flagged
@@ -369,7 +377,7 @@ static void changed(rri_ctx* c, unsigned what) {
     if ((what & (CH_T_ROW | CH_W_COL)) && !(what & CH_E_FOLLOWS)) c->resid_valid = false;
     if (what & (CH_T_ROW | CH_W_COL | CH_PENALTY)) c->obj_track_valid = false;
     if (what & (CH_X | CH_T | CH_T_ROW)) { c->q_valid = false; c->gfull_valid = false; }
-    if (what & CH_X) { c->x_sq_valid = false; c->xp_valid = false; c->xp_done = false; }
+    if (what & CH_X) { c->x_sq_valid = false; c->xp_valid = false; c->xn_valid = false; c->xp_done = false; }
     if (what & CH_ENDED) c->pending_wcheck = false;
 }
 // E has just been rebuilt from the current W and T: nothing is pending on it
@@ -668,7 +676,7 @@ struct LaunchX {
     static int stream_whole(const rri_ctx* c) {
         return (double)c->n * (double)c->LD * (double)c->es > 192.0e6 ? 0 : -1;
     }
-    template <bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS, bool PK>
+    template <bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS, int PK>
     static void pass_k(rri_ctx* c, void* Xp, i64 ldp, const double* trow, const double* wc, const Upd& u, const TgramJob& job,
                        int keep) {
         const int ncols = (int)std::min<i64>(ldp, c->LD);
@@ -682,16 +690,18 @@ struct LaunchX {
                            // -- reads and writes of a window stay in the DRAM pages that are open
                            ((ro_pass_interleaved(c) || UPD > 0) ? c->nrb : 0) |
                                ((c->sw.pass_rot >= 0 ? c->sw.pass_rot : (UPD > 0 ? c->rot_r : c->rot_x)) << 27),
-                           keep, PK ? (const unsigned char*)c->xp : nullptr, PK ? (const unsigned char*)c->xp_flags : nullptr,
-                           PK ? c->xp_base : 0, (const double*)c->rscale, (const double*)c->cscale);
+                           keep, PK == 2 ? (const unsigned char*)c->xn : PK ? (const unsigned char*)c->xp : nullptr, PK ? (const unsigned char*)c->xp_flags : nullptr,
+                           PK ? c->xp_base : 0, (const double*)c->rscale, (const double*)c->cscale,
+                           PK == 2 ? (const unsigned*)c->xn_dir : nullptr, PK == 2 ? (const unsigned short*)c->xn_exc : nullptr,
+                           PK == 2 ? c->xn_books : xnarrow::Books{});
     }
     // The read-only pass: 8 rows in flight per wave, the row dots (DO_Y) through LDS row sums.  The read-modify-write variants:
     // 16 rows in flight per wave, row dots by DPP wave sums -- 0.665 against 0.639 of 8 TB/s for the 8-row LDS row-sum variant
     // at C3 (profiles/r02_residual_schedule_geometry.log).  (The LDS-DMA ring k_pass_dma measured between +3 % and -9 % against
     // this pass, profiles/r04_pass_dma_ab.log, and was removed.)
     // keep: -1 = default-policy loads (and stores) throughout; >= 0: non-temporal, but for `keep` row blocks of a read-only pass
-    // PK: the read-only pass of an fp32 handle over the packed copy of X (c->xp; flagged tiles from Xp itself)
-    template <bool DO_Y, bool DO_Z, int UPD, bool PK = false>
+    // PK: the read-only pass of an fp32 handle over the packed copy of X (1: c->xp, 2: the 26-bit c->xn; flagged tiles from Xp itself)
+    template <bool DO_Y, bool DO_Z, int UPD, int PK = 0>
     static void pass_cfg(rri_ctx* c, void* Xp, i64 ldp, const double* trow, const double* wc, int keep, const Upd& u = Upd{},
                          const TgramJob& job = TgramJob{}) {
         constexpr int U = UPD > 0 ? 16 : 8;
@@ -710,7 +720,7 @@ struct LaunchX {
         }
         // the packed copy of X exists for an fp32 handle only: no PK pass is built for another storage type
         constexpr bool F32 = std::is_same<SX, float>::value;
-        pick_bool(F32 && c->xp_valid, [&](auto PK) {
+        pick_int<2, 1, 0>(F32 && c->xp_valid ? (c->xn_valid ? 2 : 1) : 0, [&](auto PK) {
             if constexpr (F32 || !PK) pass_cfg<DO_Y, DO_Z, 0, PK>(c, c->X, c->ldx, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw, c->keep_q, Upd{}, job);
         });
     }
@@ -2005,12 +2015,83 @@ bool enqueue_wsweep(rri_ctx* c, int sweep, int t0) {
 // as it did before.  An allocation that fails means no copy, and no error.
 // how the read-only pass loads X (rri_ctx::keep_q): the rule and its reasons are pass_keep of rri_layout.hpp
 int pass_keep(const rri_ctx* c) { return rri::pass_keep(c->plan, c->k, c->ldw, c->es, c->xp_valid, c->sw.pass_cache_mb); }
+void xnarrow_release(rri_ctx* c) {
+    dev_release(c, c->xn); dev_release(c, c->xn_dir); dev_release(c, c->xn_exc);
+    c->xn_valid = false;
+}
 void xpack_release(rri_ctx* c) {
+    xnarrow_release(c);
     dev_release(c, c->xp); dev_release(c, c->xp_flags); dev_release(c, c->xp_hmax);
     c->xp_valid = false;
     c->xp_flagged = c->xp_tiles = 0;
     c->xp_base = 0;
     c->keep_q = pass_keep(c);
+}
+// The 26-bit copy (rri_xnarrow.hpp): RRI_X_PACK=2 wherever the 28-bit copy would be built under =1; with the switch unset where
+// the 28-bit copy would be built and the elements of the window outside the 7-entry book are at most 1/16 of X (each costs 16
+// bits, so at 1/16 the entries eat half of the two bits saved).  Three kernels, each a read of X: the histogram of the exponent
+// byte with the window's top byte; the tile flags with the entry count of every record; the encoder.  The host picks the books
+// (256 counts), applies the 1/8 rule of the flags and sums the counts into the directory.
+// Returns 1: built (xp_valid, xn_valid);  0: not built, the caller builds the 28-bit copy (not wanted for this X, no memory, too
+// many entries for 32-bit offsets);  -1: too many flagged tiles, no copy of either kind (everything released, the counts recorded).
+int xnarrow_build(rri_ctx* c, i64 nitems, int ncols, unsigned grid) {
+    const i64 nrec = nitems * 4;
+    xnarrow_release(c);
+    dev_release(c, c->xp);
+    c->xn_exceptions = -1;
+    DevTmp hist, cls, counts;
+    if (dev_ensure(c, c->xp_flags, (size_t)nitems) != hipSuccess || dev_ensure(c, c->xp_hmax, sizeof(unsigned)) != hipSuccess ||
+        hist.alloc(256 * sizeof(unsigned long long)) != hipSuccess || cls.alloc(256) != hipSuccess ||
+        counts.alloc((size_t)nrec * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    unsigned hmax = 0;
+    uint64_t h[256];
+    (void)hipMemsetAsync(c->xp_hmax, 0, sizeof(unsigned), c->stream);
+    (void)hipMemsetAsync(c->xp_flags, 0, (size_t)nitems, c->stream);
+    (void)hipMemsetAsync(hist.p, 0, sizeof(h), c->stream);
+    hipLaunchKernelGGL(k_xnarrow_hist, dim3(grid), dim3(256), 0, c->stream, (const float*)c->X, c->ldx, (int)c->n, ncols, c->npanels, nitems,
+                       c->xp_hmax, (unsigned long long*)hist.p);
+    if (hipMemcpyAsync(h, hist.p, sizeof(h), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipMemcpyAsync(&hmax, c->xp_hmax, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    const unsigned base = xpack::base_of(hmax);
+    xnarrow::Books books;
+    uint8_t klass[256];
+    int nrare = 0;
+    const uint64_t exceptions = xnarrow::choose_books(h, base, books, klass, nrare);
+    c->xn_exceptions = (i64)exceptions;
+    if (c->sw.x_pack < 0 && (double)exceptions * 16.0 > (double)c->n * (double)ncols) return 0;
+    std::vector<unsigned char> flags((size_t)nitems);
+    std::vector<unsigned> cnt((size_t)nrec), dir((size_t)nrec + 1);
+    if (hipMemcpyAsync(cls.p, klass, 256, hipMemcpyHostToDevice, c->stream) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    hipLaunchKernelGGL(k_xnarrow_encode<false>, dim3(grid), dim3(256), 0, c->stream, (const float*)c->X, c->ldx, (int)c->n, ncols, c->npanels,
+                       nitems, base, (const unsigned char*)cls.p, (unsigned char*)nullptr, c->xp_flags, (unsigned*)counts.p,
+                       (const unsigned*)nullptr, (unsigned short*)nullptr);
+    if (hipMemcpyAsync(flags.data(), c->xp_flags, (size_t)nitems, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipMemcpyAsync(cnt.data(), counts.p, (size_t)nrec * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    i64 flagged = 0;
+    for (unsigned char f : flags) flagged += f != 0;
+    if (xpack_too_many_flagged(flagged, nitems)) { xpack_release(c); c->xp_flagged = flagged; c->xp_tiles = nitems; return -1; }
+    if (!xnarrow::build_directory(cnt.data(), (uint64_t)nrec, dir.data())) return 0;
+    const size_t nexc = dir[(size_t)nrec];
+    if (dev_alloc(c, c->xn, (size_t)nrec * xnarrow::RECORD_BYTES) != hipSuccess ||
+        dev_alloc(c, c->xn_dir, ((size_t)nrec + 1) * sizeof(unsigned)) != hipSuccess ||
+        dev_alloc(c, c->xn_exc, std::max<size_t>(nexc, 1) * sizeof(unsigned short)) != hipSuccess) { xnarrow_release(c); return 0; }
+    if (hipMemcpyAsync(c->xn_dir, dir.data(), ((size_t)nrec + 1) * sizeof(unsigned), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+        (void)hipGetLastError(); xnarrow_release(c); return 0;
+    }
+    hipLaunchKernelGGL(k_xnarrow_encode<true>, dim3(grid), dim3(256), 0, c->stream, (const float*)c->X, c->ldx, (int)c->n, ncols, c->npanels,
+                       nitems, base, (const unsigned char*)cls.p, c->xn, c->xp_flags, (unsigned*)nullptr, (const unsigned*)c->xn_dir, c->xn_exc);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); xnarrow_release(c); return 0; }   // dir, cls: host and temporary
+    c->xn_books = books;
+    c->xp_base = (int)base;
+    c->xp_flagged = flagged;
+    c->xp_tiles = nitems;
+    c->xp_valid = c->xn_valid = true;
+    // priced as the 28-bit copy (3.5 bytes per element; tests/test_layout_cpu.py restates that rule for a handle with a copy): a
+    // few percent fewer kept row blocks than would fit, the same loads under every value of RRI_X_PACK that builds a copy
+    c->keep_q = pass_keep(c);
+    return 1;
 }
 void xpack_ensure(rri_ctx* c) {
     if (c->xp_done) return;
@@ -2023,6 +2104,11 @@ void xpack_ensure(rri_ctx* c) {
     const bool reads_x = c->dtype == RRI_F32 && !c->weighted && !c->explicit_resid && !c->sparse && c->have_X;
     if (!reads_x || c->sw.x_pack == 0 || (c->sw.x_pack < 0 && c->keep_q < 0)) { xpack_release(c); return; }
     const i64 nitems = xpack_tiles(c->n, c->npanels, xpack::ROWS);
+    c->xn_valid = false;
+    if (c->sw.x_pack != 1) {
+        const int built = xnarrow_build(c, nitems, (int)std::min<i64>(c->ldx, c->LD), (unsigned)std::min<i64>(nitems, 8192));
+        if (built != 0) return;
+    } else xnarrow_release(c);
     if (dev_ensure(c, c->xp, (size_t)nitems * 4 * xpack::RECORD_BYTES) != hipSuccess || dev_ensure(c, c->xp_flags, (size_t)nitems) != hipSuccess ||
         dev_ensure(c, c->xp_hmax, sizeof(unsigned)) != hipSuccess) { xpack_release(c); return; }
     const int ncols = (int)std::min<i64>(c->ldx, c->LD);     // what the fp32 row loop reads (pass_k)
@@ -2359,7 +2445,7 @@ rri_switches read_switches() {
     sw.rot_debug = getenv("RRI_ROT_DEBUG") != nullptr;
     if (const char* e = getenv("RRI_MASK_BITS")) sw.mask_bits = atoi(e) != 0;
     if (const char* e = getenv("RRI_PASS_CACHE_MB")) sw.pass_cache_mb = std::max(0.0, atof(e));
-    if (const char* e = getenv("RRI_X_PACK")) sw.x_pack = atoi(e) != 0;
+    if (const char* e = getenv("RRI_X_PACK")) sw.x_pack = atoi(e) == 2 ? 2 : atoi(e) != 0;
     if (const char* e = getenv("RRI_PASS_PK_GEOM")) {
         char* end = nullptr;
         sw.pk_rows = (int)std::min<long>(std::max<long>(0, strtol(e, &end, 10)), 1 << 20);
@@ -5348,7 +5434,9 @@ rri_status rri_layout_info(rri_ctx* c, int64_t* out, int32_t n) {
         dense_w && c->nw_mask ? 1 : 0,
         !c->sparse && ro_pass_interleaved(c) ? 1 : 0,
         c->wcorr_nrb, c->n_cu,
-        c->xp_valid ? 1 : 0, c->xp_valid ? c->xp_base : 0, c->xp_flagged, c->xp_tiles};
+        c->xp_valid ? 1 : 0, c->xp_valid ? c->xp_base : 0, c->xp_flagged, c->xp_tiles,
+        c->xp_valid ? (c->xn_valid ? 26 : 28) : 0, c->xn_valid ? (int64_t)((uint64_t)c->xn_books.hi << 32 | c->xn_books.lo) : 0,
+        c->xn_exceptions};
     for (int i = 0; i < n && i < RRI_LAYOUT_FIELDS; ++i) out[i] = v[i];
     return RRI_OK;
 }

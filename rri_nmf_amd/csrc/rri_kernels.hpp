@@ -32,6 +32,7 @@
 #include "rri_halt.hpp"
 #include "rri_hip.h"
 #include "rri_layout.hpp"
+#include "rri_xnarrow.hpp"
 #include "rri_xpack.hpp"
 
 namespace rri {
@@ -51,6 +52,8 @@ namespace rri {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned __attribute__((may_alias)) u32_any;      // a dword of LDS that other code holds as doubles
 
 template <typename SX> struct XVec;
 template <> struct XVec<float> {
@@ -276,6 +279,85 @@ __device__ __forceinline__ void tgram_block(const double* __restrict__ T, i64 ld
         RRI_PASS_CHUNK_SUMS                                                                                       \
     }
 
+// The row loop over the 26-bit copy of an fp32 X (rri_xnarrow.hpp; PK == 2): the chunk of 8 rows is one 6.5 KiB record per wave,
+// six 16-byte loads and one 8-byte load per lane, and the record's exception entries -- 16 bits each, lanes take entries lane,
+// lane + 64, ... of the list the directory names.  An entry's exponent byte goes to a byte map in LDS, row u of it 64 dwords at
+// the start of row u of the wave's row-sum tile; every lane reads back the dword of its row before it decodes the row, which puts
+// the exponent in place before xe[] feeds the sums: the same xe[] in the same order as the fp32 loop.
+// The overlay is safe because all of it is the wave's own LDS traffic, which the LDS serves in program order, and the compiler
+// keeps that order (the map is written as bytes and read as u32_any, which alias the tile's doubles): the map rows are cleared
+// after the previous chunk's wave_rowsum8_finish has read the tile, the entries are scattered after the clear, the s_waitcnt and
+// wave barrier stand between the scatter and the first read, and wave_rowsum8_park of row u writes only row u of the tile, after
+// the map dword of row u was read and before that of row u + 1 is.  The directory words of the next chunk are loaded a chunk
+// ahead, and the first 64 entries before the record, so that no load of a chunk waits for another.
+// Padding (rows past n, lanes past ncols) decodes to a finite positive number: it meets wv = 0, tv = 0 or a row nobody stores.
+#define RRI_PASS_ROWS_PN(LNT) \
+    {                                                                                                             \
+        unsigned char* const mapb = reinterpret_cast<unsigned char*>(tile);                                       \
+        u32_any* const mapw = reinterpret_cast<u32_any*>(tile);                                                   \
+        constexpr unsigned MAP_ROW = 72 * sizeof(double);                                                         \
+        const unsigned wpanel = (unsigned)(pg * 4 + wave), wpanels = (unsigned)npg * 4u;                          \
+        unsigned e0 = 0u, e1 = 0u;                                                                                \
+        if (grow(0) < n) {                                                                                        \
+            const unsigned long long ri0 = xnarrow::record_index((unsigned)grow(0) >> 3, wpanel, wpanels);        \
+            e0 = xdir[ri0]; e1 = xdir[ri0 + 1];                                                                   \
+        }                                                                                                         \
+        for (int l0 = 0; l0 < rpb; l0 += U) {                                                                     \
+            const int r = grow(l0);                                                                               \
+            if (r >= n) break;                                                                                    \
+            const unsigned long long ri = xnarrow::record_index((unsigned)r >> 3, wpanel, wpanels);               \
+            const unsigned char* recb = XP + ri * xnarrow::RECORD_BYTES;                                          \
+            unsigned en = 0u;                                                                                     \
+            if (e0 + (unsigned)lane < e1) en = xexc[e0 + (unsigned)lane];                                         \
+            unsigned n0 = 0u, n1 = 0u;                                                                            \
+            if (l0 + U < rpb && grow(l0 + U) < n) {                                                               \
+                const unsigned long long rin = xnarrow::record_index((unsigned)grow(l0 + U) >> 3, wpanel, wpanels); \
+                n0 = xdir[rin]; n1 = xdir[rin + 1];                                                               \
+            }                                                                                                     \
+            unsigned xw[xnarrow::LANE_DWORDS];                                                                    \
+        _Pragma("unroll")                                                                                         \
+            for (int i = 0; i < (int)xnarrow::WIDE_SLOTS; ++i) {                                                  \
+                u32x4 v = u32x4{0u, 0u, 0u, 0u};                                                                  \
+                if (ok) v = stream_load<LNT>(reinterpret_cast<const u32x4*>(recb) + i * (int)xnarrow::LANES + lane); \
+                xw[4 * i] = v[0]; xw[4 * i + 1] = v[1]; xw[4 * i + 2] = v[2]; xw[4 * i + 3] = v[3];               \
+            }                                                                                                     \
+            {                                                                                                     \
+                u32x2 v = u32x2{0u, 0u};                                                                          \
+                if (ok) v = stream_load<LNT>(reinterpret_cast<const u32x2*>(recb + xnarrow::dword_offset(24u, 0u)) + lane); \
+                xw[24] = v[0]; xw[25] = v[1];                                                                     \
+            }                                                                                                     \
+        _Pragma("unroll")                                                                                         \
+            for (int u = 0; u < U; ++u) mapw[u * (int)(MAP_ROW / 4u) + lane] = 0u;                                \
+            if (e0 + (unsigned)lane < e1)                                                                         \
+                mapb[xnarrow::map_offset(en & 2047u, MAP_ROW)] = (unsigned char)xnarrow::rare_entry(xbooks, en >> xnarrow::POS_BITS); \
+            for (unsigned b = e0 + 64u; b < e1; b += 64u) {      /* wave-uniform: a record with more than 64 entries */ \
+                const unsigned j = b + (unsigned)lane;                                                            \
+                if (j < e1) {                                                                                     \
+                    const unsigned en2 = xexc[j];                                                                 \
+                    mapb[xnarrow::map_offset(en2 & 2047u, MAP_ROW)] = (unsigned char)xnarrow::rare_entry(xbooks, en2 >> xnarrow::POS_BITS); \
+                }                                                                                                 \
+            }                                                                                                     \
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                    \
+            __builtin_amdgcn_wave_barrier();                                                                      \
+        _Pragma("unroll")                                                                                         \
+            for (int u = 0; u < U; ++u) {                                                                         \
+                const int rr = r + u;                                                                             \
+                double wv = 0.0;                                                                                  \
+                if (DO_Z && rr < n) wv = wsh[l0 + u];                                                             \
+                const unsigned mapped = mapw[u * (int)(MAP_ROW / 4u) + lane];                                     \
+                unsigned xb[4];                                                                                   \
+                xnarrow::decode_row(xw, u, mapped, xbooks.lo, xbooks.hi, xb);                                     \
+                double xe[VN];                                                                                    \
+        _Pragma("unroll")                                                                                         \
+                for (int e = 0; e < VN; ++e) xe[e] = (double)__uint_as_float(xb[e]);                              \
+                RRI_PASS_ROW_SUMS                                                                                 \
+            }                                                                                                     \
+            RRI_PASS_CHUNK_SUMS                                                                                   \
+            if constexpr (!(DO_Y && RS)) __builtin_amdgcn_wave_barrier();                                         \
+            e0 = n0; e1 = n1;                                                                                     \
+        }                                                                                                         \
+    }
+
 // Block = 4 waves = 4 ADJACENT column panels (one per wave, 64 lanes * 16 B each) x one row block.
 // Every wave walks all rows of the block, U rows in flight; the 4 row-dot partials of a row meet in
 // LDS slots [wave][row] and are added in a fixed order at the end (Ypart has one slice per 4 panels);
@@ -286,7 +368,7 @@ __device__ __forceinline__ void tgram_block(const double* __restrict__ T, i64 ld
 // PK: the workgroup reads its rows from the packed copy XP (fp32, UPD = 0) unless one of its tiles is flagged (xflags: one byte
 // per 8-row chunk and column group, set where an element is outside the window of xbase .. xbase + 14): then it runs today's
 // loop on X.  ONE policy per workgroup for the whole row loop, taken in the prologue.
-template <typename SX, bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS, bool PK = false>
+template <typename SX, bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS, int PK = 0>
 __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0), SX, const SX>::type* __restrict__ X,
                                               i64 ldx, int n, int ncols,
                                               const double* __restrict__ trow, const double* __restrict__ wcol,
@@ -298,7 +380,10 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
                                               int keep_q, const unsigned char* __restrict__ XP = nullptr,
                                               const unsigned char* __restrict__ xflags = nullptr, int xbase = 0,
                                               const double* __restrict__ rscale = nullptr,
-                                              const double* __restrict__ cscale = nullptr) {
+                                              const double* __restrict__ cscale = nullptr,
+                                              const unsigned* __restrict__ xdir = nullptr,
+                                              const unsigned short* __restrict__ xexc = nullptr,
+                                              const xnarrow::Books xbooks = xnarrow::Books{}) {
     static_assert(!XSCALED<SX> || UPD == 0, "counts with scales are only read");
     static_assert(!PK || (std::is_same<SX, float>::value && UPD == 0 && U == 8), "the packed copy is of a read-only fp32 X");
     typedef XVec<SX> XV;
@@ -375,9 +460,18 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
             // three expansions, not four: a flagged workgroup streams its fp32 rows whether its row block is a kept one or not
             const unsigned nrb = ((unsigned)gridDim.x - (unsigned)job.nblocks) / (unsigned)npg;
             const bool kept = ((unsigned)(rb + 1) * (unsigned)keep_q) / nrb != ((unsigned)rb * (unsigned)keep_q) / nrb;
-            if (xflag) { RRI_PASS_ROWS(true) }
-            else if (kept) { RRI_PASS_ROWS_PK(false) }
-            else { RRI_PASS_ROWS_PK(true) }
+            if constexpr (PK == 2) {
+                if (xflag) { RRI_PASS_ROWS(true) }
+                else if (kept) { RRI_PASS_ROWS_PN(false) }
+                else { RRI_PASS_ROWS_PN(true) }
+            } else {
+                if (xflag) { RRI_PASS_ROWS(true) }
+                else if (kept) { RRI_PASS_ROWS_PK(false) }
+                else { RRI_PASS_ROWS_PK(true) }
+            }
+        } else if constexpr (PK == 2) {
+            if (xflag) { RRI_PASS_ROWS(false) }
+            else { RRI_PASS_ROWS_PN(false) }
         } else if constexpr (PK) {
             if (xflag) { RRI_PASS_ROWS(false) }
             else { RRI_PASS_ROWS_PK(false) }
@@ -414,6 +508,7 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
 
 #undef RRI_PASS_ROWS
 #undef RRI_PASS_ROWS_PK
+#undef RRI_PASS_ROWS_PN
 #undef RRI_PASS_ROW_SUMS
 #undef RRI_PASS_CHUNK_SUMS
 
@@ -467,6 +562,82 @@ __global__ __launch_bounds__(256) void k_xpack_encode(const float* __restrict__ 
         for (int i = 0; i < (int)xpack::SLOTS; ++i)
             rec[i * (int)xpack::LANES] = u32x4{out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]};
         if (bad) xflags[it] = 1;
+    }
+}
+
+// The one-time kernels behind the 26-bit copy (rri_xnarrow.hpp), in the same geometry, three reads of X in all.
+// k_xnarrow_hist: k_xpack_max's pass, which also counts the exponent byte of every element of X of sign 0 (hist[256], zeroed
+// before the launch; padding is not counted): the host picks the books from it.
+// k_xnarrow_encode<false>: the tile flags of the 28-bit format, computed as k_xpack_encode computes them (an element in neither
+// book flags its tile too; the books hold the whole window, so there is none), and the number of exception entries of every record.
+// k_xnarrow_encode<true>: writes the fixed parts, and every record's entries where the directory (the host's prefix sum of the
+// counts) puts them, lane after lane.
+__global__ __launch_bounds__(256) void k_xnarrow_hist(const float* __restrict__ X, i64 ldx, int n, int ncols, int npg, i64 nitems,
+                                                      unsigned* __restrict__ hmax, unsigned long long* __restrict__ hist) {
+    __shared__ unsigned long long h[256];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    h[threadIdx.x] = 0ull;
+    __syncthreads();
+    unsigned m = 0u;
+    for (i64 it = blockIdx.x; it < nitems; it += gridDim.x) {
+        const int q = (int)(it / npg), pg = (int)(it % npg);
+        const int col = (pg * 4 + wave) * 256 + lane * 4;
+        unsigned bits[xpack::ROWS][xpack::COLS];
+        xpack_load_lane(X, ldx, n, ncols, q, col, bits);
+#pragma unroll
+        for (int u = 0; u < (int)xpack::ROWS; ++u)
+#pragma unroll
+            for (int e = 0; e < (int)xpack::COLS; ++e) {
+                m = max(m, xpack::window_candidate(bits[u][e]));
+                if (q * (int)xpack::ROWS + u < n && col < ncols && !(bits[u][e] >> 31)) atomicAdd(&h[bits[u][e] >> 23], 1ull);
+            }
+    }
+    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
+    if (lane == 0 && m != 0u) atomicMax(hmax, m);
+    __syncthreads();
+    if (h[threadIdx.x] != 0ull) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
+}
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_xnarrow_encode(const float* __restrict__ X, i64 ldx, int n, int ncols, int npg, i64 nitems,
+                                                        unsigned base, const unsigned char* __restrict__ cls,
+                                                        unsigned char* __restrict__ XN, unsigned char* __restrict__ xflags,
+                                                        unsigned* __restrict__ counts, const unsigned* __restrict__ dir,
+                                                        unsigned short* __restrict__ exc) {
+    __shared__ unsigned char scls[256];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    scls[threadIdx.x] = cls[threadIdx.x];
+    __syncthreads();
+    for (i64 it = blockIdx.x; it < nitems; it += gridDim.x) {
+        const int q = (int)(it / npg), pg = (int)(it % npg);
+        const int col = (pg * 4 + wave) * 256 + lane * 4;
+        unsigned bits[xpack::ROWS][xpack::COLS], out[xnarrow::LANE_DWORDS];
+        xpack_load_lane(X, ldx, n, ncols, q, col, bits);
+        const unsigned rows_valid = col < ncols ? (unsigned)min(n - q * (int)xpack::ROWS, (int)xpack::ROWS) : 0u;
+        const unsigned long long ri = xnarrow::record_index((unsigned)q, (unsigned)(pg * 4 + wave), (unsigned)npg * 4u);
+        unsigned nexc;
+        bool neither;
+        xnarrow::encode_lane(bits, rows_valid, scls, (unsigned)lane, out, nullptr, nexc, neither);
+        unsigned upto = nexc;           // the entries of lanes 0 .. lane
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned o = (unsigned)__shfl_up((int)upto, off);
+            if (lane >= off) upto += o;
+        }
+        if constexpr (!WRITE) {
+            bool bad = neither;
+#pragma unroll
+            for (int u = 0; u < (int)xpack::ROWS; ++u)
+#pragma unroll
+                for (int e = 0; e < (int)xpack::COLS; ++e) bad = bad || !xpack::in_window(bits[u][e], base);
+            if (bad) xflags[it] = 1;
+            if (lane == 63) counts[ri] = upto;
+        } else {
+            xnarrow::encode_lane(bits, rows_valid, scls, (unsigned)lane, out, exc + ((size_t)dir[ri] + (upto - nexc)), nexc, neither);
+            unsigned char* rec = XN + ri * xnarrow::RECORD_BYTES;
+#pragma unroll
+            for (int i = 0; i < (int)xnarrow::WIDE_SLOTS; ++i)
+                reinterpret_cast<u32x4*>(rec)[i * (int)xnarrow::LANES + lane] = u32x4{out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]};
+            reinterpret_cast<u32x2*>(rec + xnarrow::dword_offset(24u, 0u))[lane] = u32x2{out[24], out[25]};
+        }
     }
 }
 

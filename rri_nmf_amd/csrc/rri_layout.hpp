@@ -60,8 +60,9 @@ struct rri_switches {
     double pass_cache_mb = PASS_CACHE_MB;   // RRI_PASS_CACHE_MB: what of the Infinity Cache a topic step may fill (pass_keep); 0: all of X streams
     int pk_rows = 0;           // RRI_PASS_PK_GEOM=<rows>[i|c] (diagnostics): rows per workgroup of the read-only pass (rounded up to 16, at most the
     int pk_il = -1;            // LDS cap) and interleaved (i) or contiguous (c) chunks, for dense fp32 handles of the Gram form (dense_plan)
-    int x_pack = -1;           // RRI_X_PACK: the packed 28-bit copy of an fp32 X for the read-only pass (xpack_ensure): 0 never, 1 wherever the
-                               // pass can read it, unset: where X does not fit the budget of pass_keep
+    int x_pack = -1;           // RRI_X_PACK: the packed copy of an fp32 X for the read-only pass (xpack_ensure): 0 never, 1 the 28-bit copy
+                               // wherever the pass can read it, 2 the 26-bit copy there (rri_xnarrow.hpp), unset: where X does not fit
+                               // the budget of pass_keep, the 26-bit copy if few elements are exceptions (xnarrow_build), else the 28-bit
 };
 
 // ---- the blocked store of a CSR pattern: dimensions ----------------------------------------------------------------------
