@@ -622,8 +622,10 @@ rri_status rri_onchip_info(rri_ctx* ctx, int32_t* eligible, int64_t* launches);
  *   23     bits per element of the copy the pass streams: 28, 26 (the book-coded copy, rri_xnarrow.hpp; RRI_X_PACK=2, or unset and
  *          few exceptions) or 0;   24  the book of the 26-bit copy, its seven exponent bytes in bytes 0..6, else 0;   25  elements
  *          of X inside the window and outside the book (the exception entries of a 26-bit copy) as the last build counted them,
- *          -1 where none was counted */
-#define RRI_LAYOUT_FIELDS 26
+ *          -1 where none was counted
+ *   26     the handle, with the parameters it has now, takes the early-sums schedule (RRI_EARLY_SUMS: the W-sized sums of a topic
+ *          step ride in the grid of its pass) wherever a step's early partials are valid;   27  W-column steps that took it so far */
+#define RRI_LAYOUT_FIELDS 28
 rri_status rri_layout_info(rri_ctx* ctx, int64_t* out, int32_t n);
 /* The exchanges of that launch poll a bounded number of times.  When its workgroups cannot all run at once (a device shared
  * with another process, CUs masked away) the launch gives up, and the call does what the reference's sweep does under any

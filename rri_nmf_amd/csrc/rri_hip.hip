@@ -261,6 +261,15 @@ struct rri_ctx {
 
     bool carry_valid = false;
     int carry_topic = -1;
+    // The early-sums schedule (RRI_EARLY_SUMS; early_ok): Tearly holds the partials of T T[t,:]^T of topic early_topic, left by
+    // k_trow_early, while early_valid -- the one thing the early job in the pass of that topic's W half needs before the pass is
+    // launched.  carry_wfin qualifies carry_valid: the carry was left by k_wfin (after step wfin_topic), so red is reduced
+    // already, its Gram entries wfin_topic and k + 1 are per-tile partials in wfp, and only k_trow_early can take it up.
+    // edot: the early job's row dots; Gearly: its Gram partials; ent: ||T[t,:]||^2; wfp: k_wfin's two vectors of tile partials.
+    double *Tearly = nullptr, *edot = nullptr, *Gearly = nullptr, *ent = nullptr, *wfp = nullptr;
+    bool early_valid = false, carry_wfin = false;
+    int early_topic = -1, wfin_topic = -1;
+    long early_steps = 0;      // W halves that took k_wfin (rri_layout_info)
     // <w_t, X t_t> of every topic's W half (per k_wcol block): with ||X||^2 and the two Gram matrices it gives the
     // objective without another pass over X.  xy_run = topics 0 .. xy_run-1 of the current sweep have run their
     // W half in order since the last change from outside; xy_valid: all k have, and no T row changed since.
@@ -331,7 +340,7 @@ static inline bool ro_pass_interleaved(const rri_ctx* c) { return rri::ro_pass_i
 // ---- what a handle keeps between steps and calls, and what each piece was computed from ------------------------------------
 //                                              X   M   W   T   scratch  penalties
 //   carry_valid / carry_topic                  x   x   x   x      x                 one topic's partial sums in Zpart / Gpart (Z2part)
-//   resid_valid                                x   x   x   x                        E (pattern-only: sp_e and its copies) = [M .*] (X - W T)
+//   resid_valid                               x   x   x   x                        E (pattern-only: sp_e and its copies) = [M .*] (X - W T)
 //   xy_run / xy_valid                          x       x   x                        XYpart: <w_t, X t_t> of the topics of one sweep, in order
 //   obj_track_valid                            x       x   x                x       DevState.obj_track of the last persistent launch
 //   q_valid                                    x           x                        Qt = X T^T
@@ -340,6 +349,9 @@ static inline bool ro_pass_interleaved(const rri_ctx* c) { return rri::ro_pass_i
 // (X of an RRI_U8 handle: the counts AND its two scale vectors -- a changed scale is CH_X.)
 // (X of an RRI_UNWEIGHTED_SPARSE handle: the stored CSR AND its uniform rows -- a changed list or value is CH_X; the list itself
 // is no cache: only rri_set_uniform_rows, rri_csr_scale_X_uniform and a new X, rri_upload_X_csr, which empties it, write it.)
+// (The early-sums schedule adds no row: carry_wfin qualifies carry_valid -- the carry is k_wfin's: red reduced already, two Gram
+// entries as tile sums in wfp -- and goes wherever carry_valid goes; early_valid, the partials of T T[t,:]^T in Tearly, lives from
+// the T half that leaves them to the W half of the same topic and is dropped by ANY change, that W half's own included.)
 // (scratch: Zpart / Gpart / red, which other entry points borrow.)  resid_fresh, dt_pending and dw_pending qualify E and are
 // read only while resid_valid holds; every rebuild resets them (resid_rebuilt).  pending_wcheck is no cache but a verdict still
 // owed on the column sums in Gpart: it is taken before Gpart is overwritten (flush_wcheck) and dropped only with the run it
@@ -365,6 +377,10 @@ enum : unsigned {
     CH_E_FOLLOWS = 1u << 9  // with the two above: the step keeps E in step through dt_pending / dw_pending
 };
 static void changed(rri_ctx* c, unsigned what) {
+    // the early partials of T T[t,:]^T live from the T half that leaves them to the W half of the same topic and no longer: that T
+    // half sets the bit after its own CH_T_ROW, and every change -- the W half's own CH_W_COL included -- drops it
+    if (what) c->early_valid = false;
+    if (what & (CH_X | CH_M | CH_W | CH_T | CH_SCRATCH | CH_ENDED | CH_T_ROW)) c->carry_wfin = false;   // wherever carry_valid goes
     if (what & (CH_X | CH_M | CH_W | CH_T | CH_SCRATCH | CH_ENDED)) {
         c->carry_valid = false;
         c->carry_topic = -1;
@@ -676,12 +692,12 @@ struct LaunchX {
     static int stream_whole(const rri_ctx* c) {
         return (double)c->n * (double)c->LD * (double)c->es > 192.0e6 ? 0 : -1;
     }
-    template <bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS, int PK>
+    template <bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS, int PK, bool EJ>
     static void pass_k(rri_ctx* c, void* Xp, i64 ldp, const double* trow, const double* wc, const Upd& u, const TgramJob& job,
-                       int keep) {
+                       int keep, const EarlyJob& ej) {
         const int ncols = (int)std::min<i64>(ldp, c->LD);
         typedef typename std::conditional<(UPD > 0), SX, const SX>::type XT;
-        hipLaunchKernelGGL((k_pass<SX, DO_Y, DO_Z, UPD, U, NT, RS, PK>), dim3(c->npanels * c->nrb + job.nblocks), dim3(256),
+        hipLaunchKernelGGL((k_pass<SX, DO_Y, DO_Z, UPD, U, NT, RS, PK, EJ>), dim3(c->npanels * c->nrb + job.nblocks + (EJ ? ej.nblocks : 0)), dim3(256),
                            pass_shmem(c, UPD), c->stream, (XT*)Xp, ldp, (int)c->n, ncols, trow, wc, c->Ypart,
                            c->Zpart, c->LD, c->rpb, c->npanels, u.a, u.b, u.a2, u.b2, u.b2sub, (const DevState*)c->st, job,
                            // interleaved row chunks: the workgroups running at one time walk ONE window of the matrix, as a
@@ -693,7 +709,7 @@ struct LaunchX {
                            keep, PK == 2 ? (const unsigned char*)c->xn : PK ? (const unsigned char*)c->xp : nullptr, PK ? (const unsigned char*)c->xp_flags : nullptr,
                            PK ? c->xp_base : 0, (const double*)c->rscale, (const double*)c->cscale,
                            PK == 2 ? (const unsigned*)c->xn_dir : nullptr, PK == 2 ? (const unsigned short*)c->xn_exc : nullptr,
-                           PK == 2 ? c->xn_books : xnarrow::Books{});
+                           PK == 2 ? c->xn_books : xnarrow::Books{}, ej);
     }
     // The read-only pass: 8 rows in flight per wave, the row dots (DO_Y) through LDS row sums.  The read-modify-write variants:
     // 16 rows in flight per wave, row dots by DPP wave sums -- 0.665 against 0.639 of 8 TB/s for the 8-row LDS row-sum variant
@@ -703,14 +719,21 @@ struct LaunchX {
     // PK: the read-only pass of an fp32 handle over the packed copy of X (1: c->xp, 2: the 26-bit c->xn; flagged tiles from Xp itself)
     template <bool DO_Y, bool DO_Z, int UPD, int PK = 0>
     static void pass_cfg(rri_ctx* c, void* Xp, i64 ldp, const double* trow, const double* wc, int keep, const Upd& u = Upd{},
-                         const TgramJob& job = TgramJob{}) {
+                         const TgramJob& job = TgramJob{}, const EarlyJob& ej = EarlyJob{}) {
         constexpr int U = UPD > 0 ? 16 : 8;
         constexpr bool RS = UPD == 0 && DO_Y;
-        pick_bool(keep >= 0, [&](auto nt) { pass_k<DO_Y, DO_Z, UPD, U, nt, RS, PK>(c, Xp, ldp, trow, wc, u, job, nt ? keep : 0); });
+        // the build with the early-sums job only where a job rides (the fused read-only pass of an early W half)
+        constexpr bool CAN_EJ = DO_Y && DO_Z && UPD == 0;
+        pick_bool(keep >= 0, [&](auto nt) {
+            pick_bool(CAN_EJ && ej.nblocks > 0, [&](auto with_job) {
+                if constexpr (CAN_EJ || !with_job) pass_k<DO_Y, DO_Z, UPD, U, nt, RS, PK, with_job>(c, Xp, ldp, trow, wc, u, job, nt ? keep : 0, ej);
+            });
+        });
     }
-    // row dots against T[t,:] (DO_Y) and column sums against W[:,tz] (DO_Z); `job`: the Gram row of T[t,:] rides along
+    // row dots against T[t,:] (DO_Y) and column sums against W[:,tz] (DO_Z); `job`: the Gram row of T[t,:] rides along; `ej`: and
+    // the W-sized sums of the step (the early-sums schedule; the fused pass of a dense X only)
     template <bool DO_Y, bool DO_Z>
-    static void pass(rri_ctx* c, int t, int tz, const TgramJob& job = TgramJob{}) {
+    static void pass(rri_ctx* c, int t, int tz, const TgramJob& job = TgramJob{}, const EarlyJob& ej = EarlyJob{}) {
         TimedScope ts(c, 0);
         if constexpr (!RO) {
             if (c->sparse_x) {    // X on CSR: the read-only pass over its two blocked copies (no side job: the caller runs k_tgram)
@@ -721,7 +744,7 @@ struct LaunchX {
         // the packed copy of X exists for an fp32 handle only: no PK pass is built for another storage type
         constexpr bool F32 = std::is_same<SX, float>::value;
         pick_int<2, 1, 0>(F32 && c->xp_valid ? (c->xn_valid ? 2 : 1) : 0, [&](auto PK) {
-            if constexpr (F32 || !PK) pass_cfg<DO_Y, DO_Z, 0, PK>(c, c->X, c->ldx, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw, c->keep_q, Upd{}, job);
+            if constexpr (F32 || !PK) pass_cfg<DO_Y, DO_Z, 0, PK>(c, c->X, c->ldx, c->T + (i64)t * c->LD, c->W + (i64)tz * c->ldw, c->keep_q, Upd{}, job, ej);
         });
     }
     // explicit-residual schedule: the same products over the stored residual R (c->E, stride LD)
@@ -1199,6 +1222,39 @@ struct LK {  // float64-only kernels
     }
     // no simplex projection configured: k_trow_numer stores the row itself and k_tgram finishes the checks
     static bool light(const rri_ctx* c) { return !(c->prm.project_T_each_iter && c->prm.has_t_row_sum); }
+    // ---- the early-sums schedule (RRI_EARLY_SUMS): the W-sized sums of a topic step ride in the grid of its pass ----
+    // The handles it is for: a dense unweighted X of the Gram form, every storage type; both factors moving, one device, no
+    // projection, and not the launch-bound sizes that take k_trow_small.  Everything else keeps k_wcol.  (Frozen rows ride
+    // along -- they add their share into red between k_wfin and k_trow_early, as between k_reduce and k_trow_numer -- so that a
+    // handle with all-zero statistics keeps the bits of one without any.)
+    static bool early_ok(const rri_ctx* c) {
+        return c->sw.early_sums && c->Tearly && !c->weighted && !c->explicit_resid && !c->sparse && c->k > 1 && !c->prm.fix_T &&
+               !c->prm.fix_W && !c->comm && light(c) && !(small(c) && !c->fzB && c->sw.trow_fused) && WCOL_TILES == 1 &&
+               early_job_lds_doubles(c->k) <= 5 * (size_t)c->rpb + 4 * 8 * 72;     // the pass's own LDS (pass_shmem) holds the job
+    }
+    static EarlyJob early_job(const rri_ctx* c, int t, int tn) {
+        return EarlyJob{(const double*)c->W, c->ldw, (int)c->n, c->k, t, tn, (const double*)c->Tearly, c->plan.nte, c->edot,
+                        c->Gearly, c->ent, early_job_first(c->npanels * c->nrb, c->n_cu), c->plan.e_blocks, c->plan.e_tpb};
+    }
+    // the launch after the pass: the column update from the early job's sums, k_reduce's blocks in the same grid
+    static void wfin(rri_ctx* c, int t, int tn, int sweep) {
+        TimedScope ts(c, 1);
+        const int nredb = (int)((c->LD + 31) / 32) + GRAM_SLICES;
+        hipLaunchKernelGGL(k_wfin, dim3(nredb + c->plan.nwfin), dim3(1024), 0, c->stream, c->W, c->ldw, (int)c->n, c->k, t, tn,
+                           (const double*)c->Ypart, c->npanels, (const double*)c->edot, (const double*)c->ent, c->Gpart,
+                           c->wfp, c->nwb, c->XYpart + (i64)t * c->xy_stride, (const double*)c->Zpart, c->LD, c->nrb, (const double*)c->Gearly,
+                           c->plan.e_blocks, c->red, nredb, sweep, kparams(c), c->st);
+        c->gpart_n = c->nwb;
+        c->early_steps += 1;
+        note_xy(c, t, c->nwb * WCOL_TILES);
+    }
+    // the T-row update that leaves T T[t,:]^T for the early job of the pass that follows
+    static void trow_early(rri_ctx* c, int t, int check_prev, int tprev, int sweep) {
+        hipLaunchKernelGGL(k_trow_early, dim3(c->plan.nte), dim3(1024), 0, c->stream, c->T, c->LD, (int)c->d, c->k, t,
+                           (const double*)c->red, c->LD, c->carry_wfin ? (const double*)c->wfp : (const double*)nullptr, c->nwb,
+                           c->wfin_topic, c->xraw, c->tpart, c->Tearly, check_prev, tprev, sweep, kparams(c), c->st);
+        c->tpart_n = c->ntb;
+    }
     static void trow(rri_ctx* c, int t, int check_prev, int tprev, int sweep, bool force_final) {
         hipLaunchKernelGGL(k_trow_numer, dim3(c->ntb), dim3(128), 0, c->stream, c->T, c->LD, (int)c->d, c->k, t,
                            (const double*)c->red, c->LD, c->xraw, c->tpart, c->tpart_idx, check_prev, tprev, sweep,
@@ -1565,15 +1621,26 @@ void enqueue_prologue(rri_ctx* c, int t, int sweep) {
     LK::wcol<false, true>(c, t, t, sweep);                             // Gram row of w_t
     DISPATCH_RO(c, (L::template pass<false, true>(c, t, t)));         // w_t^T X
     c->carry_valid = true;
+    c->carry_wfin = false;
     c->carry_topic = t;
 }
 
 void enqueue_T_half(rri_ctx* c, int sweep, int t, bool standalone) {
+    // early-sums schedule: the row update that leaves T T[t,:]^T for the pass of this topic's W half.  (The k_trow_final of a lone
+    // half step only takes the row checks here: without a projection it leaves the row as stored.)  What k_wfin left only
+    // k_trow_early can take up: any other route starts from the prologue (the column check it owes is taken there first, from Gpart).
+    const bool early = LK::early_ok(c);
+    if (c->carry_wfin && !early) c->carry_valid = false;
     if (!c->carry_valid || c->carry_topic != t) enqueue_prologue(c, t, sweep);
     {
         TimedScope ts(c, 2);
         const int chk = c->pending_wcheck ? 1 : 0;
-        if (LK::small(c) && !c->comm && !c->fzB && c->sw.trow_fused) {
+        if (early) {
+            if (!c->carry_wfin) LK::reduce(c);      // the carry is k_wcol's or the prologue's
+            LK::frozen_add(c, t, chk ? c->pending_wcheck_topic : -1);
+            LK::trow_early(c, t, chk, c->pending_wcheck_topic, sweep);
+            LK::trow_final_if_needed(c, t, sweep, standalone);
+        } else if (LK::small(c) && !c->comm && !c->fzB && c->sw.trow_fused) {
             LK::trow_small(c, t, chk, c->pending_wcheck_topic, sweep, standalone);
         } else {
             // the one cross-row reduction of a topic step: [w_t^T X | slices of (w_t^T W, ||w_t||^2, sum W[:,t-1])];
@@ -1588,6 +1655,7 @@ void enqueue_T_half(rri_ctx* c, int sweep, int t, bool standalone) {
         if (c->prm.fix_W && no_regs(c)) LK::scale_wcol(c, t);
     }
     changed(c, CH_T_ROW);
+    if (early) { c->early_valid = true; c->early_topic = t; }
 }
 
 void enqueue_W_half(rri_ctx* c, int sweep, int t) {
@@ -1607,9 +1675,14 @@ void enqueue_W_half(rri_ctx* c, int sweep, int t) {
                        c->nsplit, finish, sweep, kparams(c), c->st, c->k * c->nsplit};
         c->ttpart_n = c->nsplit;
     }
+    // early-sums schedule: the T half of this topic has just left T T[t,:]^T (nothing touched the handle since), so the W-sized
+    // sums of k_wcol ride in the pass's grid and one launch, k_wfin, finishes the column and reduces the carry.  Any step whose
+    // early partials are not there -- a lone half step, the first after rri_set_*, a reset, a resume -- runs k_wcol.
+    const bool early = carry_next && LK::early_ok(c) && c->early_valid && c->early_topic == t;
     if (carry_next) {
-        DISPATCH_RO(c, (L::template pass<true, true>(c, t, tn, job)));
-        LK::wcol<true, true>(c, t, tn, sweep);
+        DISPATCH_RO(c, (L::template pass<true, true>(c, t, tn, job, early ? LK::early_job(c, t, tn) : EarlyJob{})));
+        if (early) LK::wfin(c, t, tn, sweep);
+        else LK::wcol<true, true>(c, t, tn, sweep);
         c->carry_valid = true;
         c->carry_topic = tn;
         c->pending_wcheck = true;
@@ -1631,6 +1704,8 @@ void enqueue_W_half(rri_ctx* c, int sweep, int t) {
         c->carry_valid = false;
     }
     changed(c, CH_W_COL);
+    c->carry_wfin = early;
+    c->wfin_topic = t;
 }
 
 // ---- explicit-residual schedule (RRI_UNWEIGHTED_RESIDUAL; SURVEY 8a "explicit-residual variant") --------------
@@ -2446,6 +2521,7 @@ rri_switches read_switches() {
     if (const char* e = getenv("RRI_MASK_BITS")) sw.mask_bits = atoi(e) != 0;
     if (const char* e = getenv("RRI_PASS_CACHE_MB")) sw.pass_cache_mb = std::max(0.0, atof(e));
     if (const char* e = getenv("RRI_X_PACK")) sw.x_pack = atoi(e) == 2 ? 2 : atoi(e) != 0;
+    if (const char* e = getenv("RRI_EARLY_SUMS")) sw.early_sums = atoi(e) != 0;
     if (const char* e = getenv("RRI_PASS_PK_GEOM")) {
         char* end = nullptr;
         sw.pk_rows = (int)std::min<long>(std::max<long>(0, strtol(e, &end, 10)), 1 << 20);
@@ -2606,6 +2682,13 @@ rri_status rri_create(rri_ctx** out, int64_t n, int64_t d, int32_t k, int32_t dt
     CR(dev_alloc(c, c->objbuf, (size_t)(2 * k * k + k) * f8));
     CR(dev_alloc(c, c->dtmp, 16 * f8));
     CR(dev_alloc(c, c->itmp, 16 * sizeof(i64)));
+    if (c->sw.early_sums && !weighted && !explicit_resid && !p.sparse && k > 1) {      // the early-sums schedule (LK::early_ok)
+        CR(dev_alloc(c, c->Tearly, (size_t)p.nte * k * f8, true));
+        CR(dev_alloc(c, c->edot, (size_t)n * f8, true));
+        CR(dev_alloc(c, c->Gearly, (size_t)p.e_blocks * (k + 2) * f8, true));
+        CR(dev_alloc(c, c->ent, 8 * f8, true));
+        CR(dev_alloc(c, c->wfp, (size_t)2 * c->nwb * f8, true));
+    }
     // The flavours' own buffers, each in the order its flavour has always asked for them (calibrate_rot: the speed of a
     // read-modify-write pass belongs to the buffer's placement).  The stored residual first: k_resid writes the d real columns only
     // and the passes stream all LD, so the pad columns must hold zeros (recycled memory there once held NaN patterns, which
@@ -5166,6 +5249,7 @@ rri_status rri_topic_reduce_local(rri_ctx* c, int32_t t) {
             HIPCHK(c, hipMemsetAsync(c->red + 2 * c->LD, 0, 2 * sizeof(double), c->stream));
         return RRI_OK;
     }
+    if (c->carry_wfin) c->carry_valid = false;      // k_wfin's carry is not k_reduce's input (a run has taken its column check)
     if (!c->carry_valid || c->carry_topic != t) {
         // a local column check would see only this rank's rows: keep it pending for the reduced buffer
         const bool pend = c->pending_wcheck;
@@ -5436,7 +5520,8 @@ rri_status rri_layout_info(rri_ctx* c, int64_t* out, int32_t n) {
         c->wcorr_nrb, c->n_cu,
         c->xp_valid ? 1 : 0, c->xp_valid ? c->xp_base : 0, c->xp_flagged, c->xp_tiles,
         c->xp_valid ? (c->xn_valid ? 26 : 28) : 0, c->xn_valid ? (int64_t)((uint64_t)c->xn_books.hi << 32 | c->xn_books.lo) : 0,
-        c->xn_exceptions};
+        c->xn_exceptions,
+        LK::early_ok(c) ? 1 : 0, c->early_steps};
     for (int i = 0; i < n && i < RRI_LAYOUT_FIELDS; ++i) out[i] = v[i];
     return RRI_OK;
 }

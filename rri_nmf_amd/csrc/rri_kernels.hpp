@@ -184,6 +184,73 @@ __device__ __forceinline__ void tgram_block(const double* __restrict__ T, i64 ld
     }
 }
 
+// The early-sums schedule (RRI_EARLY_SUMS): a second job in the grid of the fused pass of topic step t.  Of what
+// k_wcol<true, true> computes after the pass, everything but the row dots y = X t_t comes from W and T T[t,:]^T alone, which are
+// final before the pass is launched (k_trow_early leaves the partials of T T[t,:]^T): per row the dot sum_{l != t} W[i,l] (T T[t,:]^T)[l],
+// and for the next topic tn the Gram entries w_tn^T w_l (l != t) and ||w_tn||^2.  `nblocks` workgroups, placed at `first` among
+// the pass's own (after its first round: early_job_first in rri_layout.hpp), walk `tpb` 64-row tiles each with k_wcol's loop --
+// the same tiles, the same four-wave split of the columns, the same order of every sum -- and write dot[n], Gpart[b][0..k+2)
+// (entries t and k + 1 zero: k_wfin leaves those two per tile) and nt[0] = ||T[t,:]||^2.  No block of the grid reads them.
+struct EarlyJob {
+    const double* Wt; i64 ldw; int n, k, t, tn;
+    const double* Tearly; int nte;             // nte partial vectors T T[t,:]^T (entry t: the share of ||T[t,:]||^2)
+    double *dot, *Gpart, *nt;
+    int first, nblocks, tpb;                   // nblocks == 0: no job
+};
+// CH: columns per batch of loads per wave (k_wcol: 16).  The job must fit the registers of the pass it rides in, whatever they
+// are (the float64 pass: 74): the batch is as small as that takes; the order of every sum is the same for every CH.
+template <int CH>
+__device__ __forceinline__ void early_block(const EarlyJob& e, int b, double* sm) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, k = e.k, t = e.t;
+    double* tts = sm;                // [k]
+    double* gsh = tts + k;           // [k+2]
+    double* dsh = gsh + k + 2;       // [4][64]
+    for (int l = tid; l < k + 2; l += 256) gsh[l] = 0.0;
+    for (int l = tid; l < k; l += 256) tts[l] = ordered_sum<8>(e.Tearly + l, k, 0, e.nte, 1);
+    __syncthreads();
+    if (b == 0 && tid == 0) e.nt[0] = tts[t];
+    __syncthreads();
+    if (tid == 0) tts[t] = 0.0;      // Tt[t] = 0 (nmf.py:732)
+    __syncthreads();
+    const int ntiles = (e.n + 63) / 64;
+    const int tile1 = min(ntiles, (b + 1) * e.tpb);
+    for (int tile = b * e.tpb; tile < tile1; ++tile) {
+        const i64 i = (i64)tile * 64 + lane;
+        const bool valid = i < e.n;
+        const double wn = valid ? e.Wt[(i64)e.tn * e.ldw + i] : 0.0;
+        double dotv = 0.0;
+        for (int l0 = wave; l0 < k; l0 += 4 * CH) {
+            double wl[CH];
+#pragma unroll
+            for (int q = 0; q < CH; ++q) {
+                const int l = l0 + 4 * q;
+                wl[q] = (l < k && valid && l != t) ? e.Wt[(i64)l * e.ldw + i] : 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < CH; ++q) {
+                const int l = l0 + 4 * q;
+                if (l < k) {   // wave-uniform
+                    dotv = fma(wl[q], tts[l], dotv);
+                    if (l != t) {
+                        const double g = wave_sum<double>(wn * wl[q]);
+                        if (lane == 0) gsh[l] += g;   // column l belongs to this wave alone
+                    }
+                }
+            }
+        }
+        dsh[wave * 64 + lane] = dotv;
+        __syncthreads();
+        if (wave == 0) {
+            if (valid) e.dot[i] = (dsh[lane] + dsh[64 + lane]) + (dsh[128 + lane] + dsh[192 + lane]);
+            const double nwp = wave_sum<double>(wn * wn);
+            if (lane == 0) gsh[k] += nwp;
+        }
+        __syncthreads();   // dsh is reused by the next tile
+    }
+    double* gp = e.Gpart + (i64)b * (k + 2);
+    for (int l = tid; l < k + 2; l += 256) gp[l] = gsh[l];
+}
+
 // What a row does with its unpacked elements xe[] (the row dots against tv, the column sums against wv), and what ends a chunk
 // of U rows: shared by the fp32 / float64 / float16 row loop and the packed one, which differ in how xe[] is filled.
 #define RRI_PASS_ROW_SUMS \
@@ -368,7 +435,9 @@ __device__ __forceinline__ void tgram_block(const double* __restrict__ T, i64 ld
 // PK: the workgroup reads its rows from the packed copy XP (fp32, UPD = 0) unless one of its tiles is flagged (xflags: one byte
 // per 8-row chunk and column group, set where an element is outside the window of xbase .. xbase + 14): then it runs today's
 // loop on X.  ONE policy per workgroup for the whole row loop, taken in the prologue.
-template <typename SX, bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS, int PK = 0>
+// EJ: the build of the fused read-only pass that carries the early-sums job (EarlyJob); every other launch runs the build without
+// it, whose workgroups read no field of `ejob` and start as they always did.
+template <typename SX, bool DO_Y, bool DO_Z, int UPD, int U, bool NT, bool RS, int PK = 0, bool EJ = false>
 __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0), SX, const SX>::type* __restrict__ X,
                                               i64 ldx, int n, int ncols,
                                               const double* __restrict__ trow, const double* __restrict__ wcol,
@@ -383,9 +452,11 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
                                               const double* __restrict__ cscale = nullptr,
                                               const unsigned* __restrict__ xdir = nullptr,
                                               const unsigned short* __restrict__ xexc = nullptr,
-                                              const xnarrow::Books xbooks = xnarrow::Books{}) {
+                                              const xnarrow::Books xbooks = xnarrow::Books{},
+                                              const EarlyJob ejob = EarlyJob{}) {
     static_assert(!XSCALED<SX> || UPD == 0, "counts with scales are only read");
     static_assert(!PK || (std::is_same<SX, float>::value && UPD == 0 && U == 8), "the packed copy is of a read-only fp32 X");
+    static_assert(!EJ || (DO_Y && DO_Z && UPD == 0), "the early-sums job rides in the fused read-only pass");
     typedef XVec<SX> XV;
     typedef typename XV::type V;
     constexpr int VN = XV::N;
@@ -402,9 +473,19 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
     // every tile, nothing else changed.
     const int nrb_il = nrb_il_rot & 0x07ffffff;
     const int rot = (int)((unsigned)nrb_il_rot >> 27);
-    int bid = (int)blockIdx.x - job.nblocks;
-    if (rot != 0 && (bid | 7) < (int)gridDim.x - job.nblocks) bid = (bid & ~7) | ((bid + rot) & 7);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    int bid = (int)blockIdx.x - job.nblocks;
+    int njobs = job.nblocks;       // workgroups of the grid that are not the pass's own
+    if constexpr (EJ) {
+        // the early-sums job of the fused pass: ejob.nblocks workgroups from position ejob.first on, the pass's own around them
+        if (bid >= ejob.first && bid < ejob.first + ejob.nblocks) {
+            early_block<(sizeof(SX) == 8 ? 4 : 8)>(ejob, bid - ejob.first, reinterpret_cast<double*>(smem));
+            return;
+        }
+        if (bid >= ejob.first) bid -= ejob.nblocks;
+        njobs += ejob.nblocks;
+    }
+    if (rot != 0 && (bid | 7) < (int)gridDim.x - njobs) bid = (bid & ~7) | ((bid + rot) & 7);
     double* ysh = reinterpret_cast<double*>(smem);            // [4 waves][rpb]
     double* wsh = ysh + 4 * rpb;                              // [rpb]
     double* ash = wsh + rpb;                                  // [rpb], only with UPD
@@ -458,7 +539,7 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
         // the Infinity Cache from pass to pass; the others stream past it (host: pass_keep in rri_hip.hip)
         if constexpr (PK && NT) {
             // three expansions, not four: a flagged workgroup streams its fp32 rows whether its row block is a kept one or not
-            const unsigned nrb = ((unsigned)gridDim.x - (unsigned)job.nblocks) / (unsigned)npg;
+            const unsigned nrb = ((unsigned)gridDim.x - (unsigned)njobs) / (unsigned)npg;
             const bool kept = ((unsigned)(rb + 1) * (unsigned)keep_q) / nrb != ((unsigned)rb * (unsigned)keep_q) / nrb;
             if constexpr (PK == 2) {
                 if (xflag) { RRI_PASS_ROWS(true) }
@@ -476,7 +557,7 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
             if (xflag) { RRI_PASS_ROWS(false) }
             else { RRI_PASS_ROWS_PK(false) }
         } else if constexpr (NT && UPD == 0) {
-            const unsigned nrb = ((unsigned)gridDim.x - (unsigned)job.nblocks) / (unsigned)npg;
+            const unsigned nrb = ((unsigned)gridDim.x - (unsigned)njobs) / (unsigned)npg;
             const bool kept = ((unsigned)(rb + 1) * (unsigned)keep_q) / nrb != ((unsigned)rb * (unsigned)keep_q) / nrb;
             if (kept) { RRI_PASS_ROWS(false) }
             else { RRI_PASS_ROWS(true) }
@@ -1106,18 +1187,17 @@ __global__ __launch_bounds__(256) void k_wcol_resid(double* __restrict__ Wt, i64
 // (in the row-sharded multi-GPU run this buffer is what the ranks all-reduce).
 // 1024 threads: column blocks take 32 columns x 32 row-block groups, the last block the Gram row.
 // =========================================================================================
-__global__ __launch_bounds__(1024) void k_reduce(const double* __restrict__ Zpart, i64 ldz, int nrb,
-                                                 const double* __restrict__ Gpart, int nwb, int k,
-                                                 double* __restrict__ red, const DevState* __restrict__ st) {
-    if (st->halt) return;
-    __shared__ double sh[32 * 33];
+// one workgroup (1024 threads) of the reduction: block bx of nb; the last GRAM_SLICES take the Gram row (none when Gpart == NULL)
+__device__ __forceinline__ void reduce_block(int bx, int nb, const double* __restrict__ Zpart, i64 ldz, int nrb,
+                                             const double* __restrict__ Gpart, int nwb, int k, double* __restrict__ red,
+                                             double* sh) {
     const int tid = threadIdx.x;
     // Gpart == NULL: column blocks only (the grid then has no Gram blocks)
     const int ngram = Gpart ? GRAM_SLICES : 0;
-    const int nzb = gridDim.x - ngram;
-    if ((int)blockIdx.x < nzb) {
+    const int nzb = nb - ngram;
+    if (bx < nzb) {
         const int c = tid & 31, g = tid >> 5;
-        const i64 j = (i64)blockIdx.x * 32 + c;
+        const i64 j = (i64)bx * 32 + c;
         double a = 0.0;
         if (j < ldz) a = ordered_sum<8>(Zpart + j, ldz, g, nrb, 32);
         sh[g * 33 + c] = a;
@@ -1129,7 +1209,7 @@ __global__ __launch_bounds__(1024) void k_reduce(const double* __restrict__ Zpar
         }
     } else {
         // Gram slice gs: rows [b0, b1) of Gpart, 16 waves striding over them, lanes over the k+2 entries
-        const int gs = blockIdx.x - nzb;
+        const int gs = bx - nzb;
         const int per = (nwb + GRAM_SLICES - 1) / GRAM_SLICES;
         const int b0 = gs * per, b1 = min(nwb, b0 + per);
         const int lane = tid & 63, wave = tid >> 6;  // 16 waves
@@ -1146,6 +1226,69 @@ __global__ __launch_bounds__(1024) void k_reduce(const double* __restrict__ Zpar
                 red[ldz + (i64)gs * (k + 2) + l] = s;
             }
         }
+    }
+}
+__global__ __launch_bounds__(1024) void k_reduce(const double* __restrict__ Zpart, i64 ldz, int nrb,
+                                                 const double* __restrict__ Gpart, int nwb, int k,
+                                                 double* __restrict__ red, const DevState* __restrict__ st) {
+    if (st->halt) return;
+    __shared__ double sh[32 * 33];
+    reduce_block((int)blockIdx.x, (int)gridDim.x, Zpart, ldz, nrb, Gpart, nwb, k, red, sh);
+}
+
+// =========================================================================================
+// k_wfin: the one launch between the fused pass of step t and the T-row update of topic tn on the early-sums schedule.
+// Everything it reads the pass's grid left behind.  1024 threads; the first `nredb` workgroups are k_reduce's (the column sums
+// of Zpart in its order; the Gram slices over the early job's Gpart rows), the others take 16 tiles of 64 rows each, one per
+// wave: y from Ypart in k_wcol's order, numer = (y - dot) - reg with k_wcol's branches of qf_min and its halt, W[:,t], and per
+// tile <w_tn, w_t'> and sum w_t' (wfp[0][tile], wfp[1][tile]: two dense vectors, which k_trow_early reads coalesced; the column
+// sum also as entry k + 1 of row `tile` of Gtile, where k_check_wcol looks for it) and <w_t', y> (xyp, one per 64 rows as k_wcol
+// leaves them).
+// =========================================================================================
+__global__ __launch_bounds__(1024) void k_wfin(double* __restrict__ Wt, i64 ldw, int n, int k, int t, int tn,
+                                               const double* __restrict__ Ypart, int npanels,
+                                               const double* __restrict__ dot, const double* __restrict__ nt,
+                                               double* __restrict__ Gtile, double* __restrict__ wfp, int ntiles,
+                                               double* __restrict__ xyp, const double* __restrict__ Zpart, i64 ldz, int nrb,
+                                               const double* __restrict__ Gearly, int ne, double* __restrict__ red,
+                                               int nredb, int sweep, KParams p, DevState* st) {
+    static_assert(WFIN_TILES == 16 && WCOL_TILES == 1, "a wave per tile, a row of Gtile and an entry of xyp per tile");
+    if (st->halt) return;
+    __shared__ double sh[32 * 33];
+    if ((int)blockIdx.x < nredb) {
+        reduce_block((int)blockIdx.x, nredb, Zpart, ldz, nrb, Gearly, ne, k, red, sh);
+        return;
+    }
+    const int b = (int)blockIdx.x - nredb;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double cden = nt[0] + p.reg_w_l2;             // denom = nt + reg_w_l2 (nmf.py:465)
+    const int mode = wcol_denominator_mode(cden, p);
+    if (mode < 0) {
+        if (b == 0 && threadIdx.x == 0) halt_set(st, mode, t, sweep, t);
+        return;
+    }
+    const i64 tile = (i64)b * 16 + wave;
+    if (tile * 64 >= n) return;                         // wave-uniform; no barrier follows
+    const i64 i = tile * 64 + lane;
+    const bool valid = i < n;
+    double wn = 0.0, y = 0.0, wnew = 0.0;
+    if (valid) {
+        wn = Wt[(i64)tn * ldw + i];
+        const double dt = dot[i];
+        y = ordered_sum<8>(Ypart + i, n, 0, npanels, 1);
+        const double numer = (y - dt) - p.reg_w_l1;
+        if (mode == 0) wnew = fmax(numer, 0.0) / (cden + p.eps);
+        else wnew = (-numer + cden < 0.0) ? p.w_row_sum : 0.0;
+        Wt[(i64)t * ldw + i] = wnew;
+    }
+    const double swp = wave_sum<double>(wnew);
+    const double xy = wave_sum<double>(wnew * y);
+    const double gt = wave_sum<double>(wn * wnew);      // Gram entry against the NEW column t
+    if (lane == 0) {
+        wfp[tile] = gt;
+        wfp[ntiles + tile] = swp;
+        Gtile[tile * (k + 2) + k + 1] = swp;
+        xyp[tile] = xy;
     }
 }
 
@@ -1235,6 +1378,133 @@ __global__ __launch_bounds__(128) void k_trow_numer(double* __restrict__ T, i64 
             tpart_idx[blockIdx.x] = wi[0];
         }
     }
+    if (blockIdx.x == 0 && tid == 0) st->tmode = mode;
+}
+
+// =========================================================================================
+// k_trow_early: k_trow_numer for the early-sums schedule -- no projection configured, the Gram form: the row is stored here
+// and T T[t,:]^T, which the next pass's early job needs before that pass is launched, is left as one partial vector per
+// workgroup.  1024 threads = 256 columns: wave w takes the topics l = q, q + 4, ... (q = w & 3) of the 64 columns cw = w >> 2,
+// so the four accumulators a0..a3 of k_trow_numer belong to four waves, each with its terms in ascending l, and
+// numer = (a0 + a1) + (a2 + a3) keeps its bits; a wave's first 16 T values come in one batch of loads and are still in
+// registers when x_j is known: times x_j and wave-summed they are the wave's share of (T T[t,:]^T)[l] (l == t: sum x_j^2).
+// tpart keeps its grouping of 128 columns (two column waves, added as block_sum adds them).
+// wfp != NULL: the W half before this step was k_wfin's (of topic twfin), and the two sums that need the new column -- <w_t, w_twfin>
+// and sum W[:,twfin] -- are its two vectors of `ntiles` tile partials; every workgroup adds them in one fixed order.
+// =========================================================================================
+__global__ __launch_bounds__(1024) void k_trow_early(double* __restrict__ T, i64 ldt, int d, int k, int t,
+                                                     const double* __restrict__ red, i64 ldz,
+                                                     const double* __restrict__ wfp, int ntiles, int twfin,
+                                                     double* __restrict__ xraw, double* __restrict__ tpart,
+                                                     double* __restrict__ Tearly, int check_prev, int tprev,
+                                                     int sweep, KParams p, DevState* st) {
+    static_assert(TROW_EARLY_COLS == 256, "16 waves: 4 topic residues x 4 column waves");
+    if (st->halt) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = wave & 3, cw = wave >> 2;
+    __shared__ double scratch[40];
+    __shared__ double gsh[RRI_MAX_K];
+    __shared__ double ash[4][256];
+    __shared__ double xsh[256];
+    __shared__ double wsum[4];
+    __shared__ double psh[4][RRI_MAX_K];
+    static_assert(RRI_MAX_K <= 1024, "a thread per topic");
+    const int cl = cw * 64 + lane;
+    const i64 j = (i64)blockIdx.x * 256 + cl;
+    const bool in = j < d;
+    constexpr int CH = 16;
+    // every load that waits for nothing first, so that they share one round trip: the wave's first batch of T (row t among them:
+    // gsh[t] == 0, so it may be read like the others), the reduced column sum, the Gram row, the per-tile partials
+    double tv0[CH];
+#pragma unroll
+    for (int i = 0; i < CH; ++i) tv0[i] = (q + 4 * i < k && in) ? T[(i64)(q + 4 * i) * ldt + j] : 0.0;
+    const double zj = (q == 0 && in) ? red[j] : 0.0;
+    const double gl = tid < k ? red_gram(red, ldz, k, tid) : 0.0;
+    const double nw = red_gram(red, ldz, k, k);
+    double gprev = 0.0, colsum = 0.0;
+    if (wfp) {
+        const double ga = ordered_sum<2>(wfp, 1, tid, ntiles, 1024);
+        const double gb = ordered_sum<2>(wfp + ntiles, 1, tid, ntiles, 1024);
+        // the two workgroup sums side by side: wave sums, then the 16 wave totals in wave order (block_sum's order)
+        const double wa = wave_sum<double>(ga), wb = wave_sum<double>(gb);
+        if (lane == 0) { scratch[wave] = wa; scratch[16 + wave] = wb; }
+        __syncthreads();
+        for (int i = 0; i < 16; ++i) { gprev += scratch[i]; colsum += scratch[16 + i]; }
+        // what k_wfin's Gram slices hold in these two places is zero; frozen rows have added their share there (k_frozen_add)
+        colsum += red_gram(red, ldz, k, k + 1);
+    } else if (check_prev) colsum = red_gram(red, ldz, k, k + 1);
+    if (check_prev) {
+        const int code = wcol_code(colsum, p);
+        if (code != 0) {
+            if (blockIdx.x == 0 && tid == 0) halt_set(st, code, tprev, sweep, t);
+            return;
+        }
+    }
+    const double c = nw + p.reg_t_l2;  // denom = nw + reg_t_l2 (nmf.py:438)
+    const int mode = trow_denominator_mode(c, p);   // optimization.py:60-73; no projection here: 0, 1 or an error
+    if (mode < 0) {
+        if (blockIdx.x == 0 && tid == 0) halt_set(st, mode, t, sweep, t);
+        return;
+    }
+    if (tid < k) gsh[tid] = (tid == t) ? 0.0 : ((wfp && tid == twfin) ? gprev + gl : gl);
+    __syncthreads();
+    double a = 0.0;
+#pragma unroll
+    for (int i = 0; i < CH; ++i)
+        if (q + 4 * i < k) a = fma(gsh[q + 4 * i], tv0[i], a);
+    for (int l0 = q + 4 * CH; l0 < k; l0 += 4 * CH) {
+        double tv[CH];
+#pragma unroll
+        for (int i = 0; i < CH; ++i) tv[i] = (l0 + 4 * i < k && in) ? T[(i64)(l0 + 4 * i) * ldt + j] : 0.0;
+#pragma unroll
+        for (int i = 0; i < CH; ++i)
+            if (l0 + 4 * i < k) a = fma(gsh[l0 + 4 * i], tv[i], a);
+    }
+    ash[q][cl] = a;
+    __syncthreads();
+    if (q == 0) {
+        double x = 0.0;
+        if (in) {
+            const double acc = (ash[0][cl] + ash[1][cl]) + (ash[2][cl] + ash[3][cl]);
+            const double numer = (zj - acc) - p.reg_t_l1;
+            if (mode == 0) x = fmax(numer, 0.0) / (c + p.eps);
+            else x = (-numer + c < 0.0) ? p.t_row_sum : 0.0;
+            xraw[j] = x;
+            T[(i64)t * ldt + j] = x;
+        }
+        xsh[cl] = x;
+        const double ws = wave_sum<double>(x);
+        if (lane == 0) wsum[cw] = ws;
+    }
+    __syncthreads();
+    const double x = xsh[cl];
+    if (tid < 2 && ((i64)blockIdx.x * 2 + tid) * 128 < d) tpart[blockIdx.x * 2 + tid] = (0.0 + wsum[2 * tid]) + wsum[2 * tid + 1];
+    // T T[t,:]^T of the row as stored: this workgroup's 256 columns (rows l != t are final; row t is x)
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+        const int l = q + 4 * i;
+        if (l < k) {   // wave-uniform
+            const double s = wave_sum<double>((l == t ? x : tv0[i]) * x);
+            if (lane == 0) psh[cw][l] = s;
+        }
+    }
+    for (int l0 = q + 4 * CH; l0 < k; l0 += 4 * CH) {
+        double tv[CH];
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+            const int l = l0 + 4 * i;
+            tv[i] = (l < k && in && l != t) ? T[(i64)l * ldt + j] : 0.0;
+        }
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+            const int l = l0 + 4 * i;
+            if (l < k) {
+                const double s = wave_sum<double>((l == t ? x : tv[i]) * x);
+                if (lane == 0) psh[cw][l] = s;
+            }
+        }
+    }
+    __syncthreads();
+    for (int l = tid; l < k; l += 1024) Tearly[(i64)blockIdx.x * k + l] = (psh[0][l] + psh[1][l]) + (psh[2][l] + psh[3][l]);
     if (blockIdx.x == 0 && tid == 0) st->tmode = mode;
 }
 

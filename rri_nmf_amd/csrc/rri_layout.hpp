@@ -63,6 +63,8 @@ struct rri_switches {
     int x_pack = -1;           // RRI_X_PACK: the packed copy of an fp32 X for the read-only pass (xpack_ensure): 0 never, 1 the 28-bit copy
                                // wherever the pass can read it, 2 the 26-bit copy there (rri_xnarrow.hpp), unset: where X does not fit
                                // the budget of pass_keep, the 26-bit copy if few elements are exceptions (xnarrow_build), else the 28-bit
+    bool early_sums = true;    // RRI_EARLY_SUMS=0: the W-sized sums of a topic step stay in k_wcol after the pass (never the early job
+                               // in the pass's grid, k_wfin and k_trow_early)
 };
 
 // ---- the blocked store of a CSR pattern: dimensions ----------------------------------------------------------------------
@@ -104,7 +106,23 @@ struct DensePlan {
     i64 gpart_rows = 1, ttpart_rows = 1, tpart_rows = 1;      // rows allocated in Gpart, Ttpart, tpart
     int xy_stride = 1;
     SpDims sp[2];          // the blocked copies (sparse flavours)
+    // the early-sums schedule (early_* below): workgroups of k_trow_early (= partial vectors T T[t,:]^T), workgroups of the early
+    // job in the pass's grid (= rows of its Gpart) and the 64-row tiles each walks, tile workgroups of k_wfin
+    int nte = 1, e_blocks = 1, e_tpb = 1, nwfin = 1;
 };
+
+// ---- the early-sums schedule (k_trow_early, the early job of k_pass, k_wfin) ------------------------------------------------
+constexpr int TROW_EARLY_COLS = 256;   // columns per workgroup of k_trow_early: 16 waves = 4 topic residues x 4 column waves
+constexpr int WFIN_TILES = 16;         // 64-row tiles per workgroup of k_wfin (one per wave)
+// workgroups of the early job: a quarter of a CU count's worth, so that they fit the slots the last round of the pass leaves
+// empty at the flagship shape (88 of 1024) and each walks its tiles in a fraction of a pass; never more than there are tiles
+inline int early_job_blocks(i64 n, int n_cu) { return (int)std::max<i64>(1, std::min<i64>((n + 63) / 64, std::max(n_cu, 4) / 4)); }
+// where they sit among the pass's own workgroups: after the first round (4 workgroups of the pass per CU), so that they neither
+// delay the start of the stream nor, where the pass fills whole rounds, wait for its tail; a pass of one round has them last,
+// beside it
+inline int early_job_first(int pass_blocks, int n_cu) { return std::min(pass_blocks, 4 * std::max(n_cu, 1)); }
+// LDS of the early job (doubles): T T[t,:]^T, the block's Gram partial, the four partial dots of a tile
+inline size_t early_job_lds_doubles(int k) { return (size_t)(2 * k + 2 + 256); }
 
 // flavour: as passed to rri_create (RRI_UNWEIGHTED .. RRI_UNWEIGHTED_SPARSE)
 inline DensePlan dense_plan(i64 n, i64 d, int k, int dtype, int flavour, const rri_switches& sw, int n_cu) {
@@ -185,6 +203,10 @@ inline DensePlan dense_plan(i64 n, i64 d, int k, int dtype, int flavour, const r
     p.ttpart_rows = std::max(p.nsplit, p.ntb32);   // k_tgram: nsplit column slices; k_trow_small: one per 32 columns
     p.tpart_rows = std::max(p.ntb, p.ntb32);
     if (weighted && !p.sparse) p.cpart_rows = (int)std::max<i64>(256, (n + 2047) / 2048);
+    p.nte = (int)((d + TROW_EARLY_COLS - 1) / TROW_EARLY_COLS);
+    p.e_blocks = early_job_blocks(n, n_cu);
+    p.e_tpb = (int)(((n + 63) / 64 + p.e_blocks - 1) / p.e_blocks);
+    p.nwfin = (int)((n + 64 * WFIN_TILES - 1) / (64 * WFIN_TILES));
     return p;
 }
 

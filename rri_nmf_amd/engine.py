@@ -1372,7 +1372,7 @@ class RRIEngine(object):
     LAYOUT_COPY_FIELDS = ('nblk', 'bw', 'lps', 'nwork')
     LAYOUT_FIELDS = ('rpb', 'nrb', 'npanels', 'mask_bits', 'mask_cols', 'mask_density', 'wtrow_small', 'nw_from_mask',
                      'interleaved', 'wcorr_nrb', 'n_cu', 'x_pack', 'x_pack_base', 'x_pack_flagged', 'x_pack_tiles', 'x_pack_bits',
-                     'x_pack_book', 'x_pack_exceptions')
+                     'x_pack_book', 'x_pack_exceptions', 'early_sums', 'early_steps')
     assert 2 * len(LAYOUT_COPY_FIELDS) + len(LAYOUT_FIELDS) == _capi.RRI_LAYOUT_FIELDS
 
     def layout_info(self):
@@ -1380,14 +1380,15 @@ class RRIEngine(object):
         nblk, bw, lps, nwork -- the pass geometry rpb / nrb / npanels, and which routes of the dense weighted step are taken
         (mask_density is None until the first topic step has measured it; nw_from_mask is what the last T-row step did), and the
         packed copy of an fp32 X: x_pack (the read-only pass streams it), x_pack_base, x_pack_flagged of x_pack_tiles tiles, x_pack_bits
-        per element (28, 26 or 0), x_pack_book (the seven exponent bytes of a 26-bit copy) and x_pack_exceptions (elements outside it)"""
+        per element (28, 26 or 0), x_pack_book (the seven exponent bytes of a 26-bit copy) and x_pack_exceptions (elements outside it);
+        early_sums (the handle takes the early-sums schedule with its current parameters) and early_steps (W-column steps that did)"""
         nc = len(self.LAYOUT_COPY_FIELDS)
         out = (C.c_int64 * _capi.RRI_LAYOUT_FIELDS)()
         self._check(self._lib.rri_layout_info(self._h, out, _capi.RRI_LAYOUT_FIELDS))
         v = [int(x) for x in out]
         info = {name: (v[i], v[nc + i]) for i, name in enumerate(self.LAYOUT_COPY_FIELDS)}
         info.update(zip(self.LAYOUT_FIELDS, v[2 * nc:]))
-        for name in ('mask_bits', 'mask_cols', 'wtrow_small', 'nw_from_mask', 'interleaved', 'x_pack'):
+        for name in ('mask_bits', 'mask_cols', 'wtrow_small', 'nw_from_mask', 'interleaved', 'x_pack', 'early_sums'):
             info[name] = bool(info[name])
         info['mask_density'] = None if info['mask_density'] < 0 else info['mask_density'] * 1e-9
         info['x_pack_book'] = [info['x_pack_book'] >> (8 * i) & 0xff for i in range(7)] if info['x_pack_bits'] == 26 else []
