@@ -57,6 +57,22 @@ int main() {
                         p.cpart_rows, p.gpart_rows, p.ttpart_rows, p.tpart_rows, p.xy_stride,
                         (int)ro_pass_interleaved(p.ro_il, p.npanels, p.nrb), (int)wtrow_small(false, p.nrb), load_bytes(dtype),
                         (int)dtype_size(dtype), (int)p.sparse, p.sp[0].nblk, p.sp[0].bw, p.sp[1].nblk, p.sp[1].bw);
+        } else if (what == "early") {
+            // the early-sums schedule of the plan: where the job sits among the pass's P own workgroups, how many of its workgroups
+            // walk no tile, the grids of k_trow_early and k_wfin, and the job's LDS against the pass's own (LK::early_ok)
+            int k, dtype;
+            rri_switches sw;
+            const DensePlan p = read_plan(&k, &dtype, &sw);
+            int n_cu;
+            std::cin >> n_cu;
+            const int P = p.npanels * p.nrb;
+            const long long tiles = (p.n + 63) / 64;
+            const long long busy = (tiles + p.e_tpb - 1) / p.e_tpb;
+            std::printf("early npanels=%d rpb=%d nrb=%d P=%d first=%d e_blocks=%d e_tpb=%d idle=%lld tiles=%lld nte=%d nwfin=%d nsplit=%d ntb=%d "
+                        "job_lds=%lld pass_lds=%lld interleaved=%d\n",
+                        p.npanels, p.rpb, p.nrb, P, early_job_first(P, n_cu), p.e_blocks, p.e_tpb, (long long)p.e_blocks - busy, tiles, p.nte,
+                        p.nwfin, p.nsplit, p.ntb, (long long)early_job_lds_doubles(k), 5LL * p.rpb + 4 * 8 * 72,
+                        (int)ro_pass_interleaved(p.ro_il, p.npanels, p.nrb));
         } else if (what == "keep") {
             int k, dtype, xp_valid;
             rri_switches sw;

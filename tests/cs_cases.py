@@ -67,6 +67,11 @@ it between the operations that fill and use every row of the table:
     two that score a live DeviceCorpus) are LOOKs of the new flavours and borrowers of the directed carry and residual cases;
     check_borrowed holds each answer to the handle's current W and T with the feature's own reference and bound.
 No case on the MI355X needed a looser bound than these.
+
+The early-sums schedule keeps four more fields on the handle -- early_valid / early_topic, carry_wfin / wfin_topic --
+and at this shape only RRI_TROW_SMALL=0 reaches it: the flavours 'gram-early', 'gram-early-fp32' and 'gram-early-u8' are 'gram-phases',
+'gram-fp32' and 'gram-u8' under that switch, with the evaluation calls among their LOOKs, and the directed cases 'early-*' put every
+change between the steps that fill and use those fields.  The model is the same: it has no schedule.
 """
 import os
 
@@ -118,8 +123,16 @@ FLAVOURS = {
     'gram-frozen-fp32': dict(kind='plain', dtype=np.float32, d=D_F32, env={}, frozen=True),
     'csr-frozen': dict(kind='csr', dtype=np.float64, d=D, env={}, frozen=True, corpus=True),
     'csr-uniform': dict(kind='csr', dtype=np.float64, d=D, env={}, uniform=True, corpus=True),
+    # the early-sums schedule (RRI_EARLY_SUMS, on by default): at this shape every flavour above takes k_trow_small or runs on chip
+    # and never reaches it, but for those with statistics.  RRI_TROW_SMALL=0 puts the three plain stores on it -- the early job in
+    # the pass's grid, k_wfin, k_trow_early -- with early_valid / early_topic / carry_wfin / wfin_topic to keep right between
+    # calls.  Appended last, for the same reason as the four above them
+    'gram-early': dict(kind='plain', dtype=np.float64, d=D, env={'RRI_ONCHIP': '0', 'RRI_TROW_SMALL': '0'}),
+    'gram-early-fp32': dict(kind='plain', dtype=np.float32, d=D_F32, env={'RRI_ONCHIP': '0', 'RRI_TROW_SMALL': '0'}),
+    'gram-early-u8': dict(kind='plain', dtype=np.uint8, d=D_F32, env={'RRI_ONCHIP': '0', 'RRI_TROW_SMALL': '0'}),
 }
 NEW_FLAVOURS = ['gram-frozen', 'gram-frozen-fp32', 'csr-frozen', 'csr-uniform']
+EARLY_FLAVOURS = ['gram-early', 'gram-early-fp32', 'gram-early-u8']
 RANDOM_FLAVOURS = [f for f in FLAVOURS if not f.endswith('-bind')]
 DIRECTED_ONLY = ['bind_mask']        # operations that no random alphabet has: bind_mask_device refuses the odd d of the weighted flavours
 WEIGHTED_KINDS = ('weighted', 'pattern')
@@ -161,7 +174,25 @@ def alphabet(flavour):
         # the two bandwidth probes are refused on this store (they write an X-sized buffer of the storage type); scale_X and
         # preprocess write the scale vectors only, so nothing is rounded twice and they stay, also on a bound X
         ops = [o for o in ops if o not in ('bench_rank1', 'bench_copy')] + ['bind_X', 'set_X_scales']
-    return ops + new_ops(flavour) + (BORROWERS + (CORPUS_BORROWERS if f['kind'] == 'csr' else []) if flavour in NEW_FLAVOURS else [])
+    return ops + new_ops(flavour) + (BORROWERS + (CORPUS_BORROWERS if f['kind'] == 'csr' else []) if flavour in NEW_FLAVOURS + EARLY_FLAVOURS else [])
+
+
+def early_schedule(pname):
+    """does a handle of an EARLY_FLAVOURS flavour take the early-sums schedule under these parameters (LK::early_ok: both factors
+    free, no projection of T)?"""
+    p = PARAMS[pname]
+    return not (p.get('fix_T') or p.get('fix_W') or p.get('project_T_each_iter'))
+
+
+def early_sweeps(ops, raises=None):
+    """how many sweep() calls of ops run on the early-sums schedule: each takes k_wfin at least once (every W half whose T half ran
+    in the same call), so layout_info()['early_steps'] must be positive after a sequence that holds one"""
+    ls, count = LegalState('plain'), 0
+    for i, op in enumerate(ops):
+        if op.name == 'sweep' and early_schedule(ls.pname) and i != raises:
+            count += 1
+        ls.follow(op)
+    return count
 
 
 def new_ops(flavour):
@@ -1280,7 +1311,8 @@ REDRAWS = {('gram-onchip', 2): 1, ('gram-onchip', 3): 1, ('gram-onchip', 7): 1, 
            ('gram-onchip', 19): 1, ('gram-phases', 14): 1, ('residual', 10): 1, ('residual', 13): 1, ('csr', 3): 1, ('csr', 6): 1,
            ('csr', 10): 1, ('csr', 12): 1, ('csr', 22): 1, ('gram-fp32', 9): 1,
            ('gram-u8', 21): 1,
-           ('gram-frozen', 6): 1, ('csr-uniform', 12): 1, ('csr-uniform', 17): 1}
+           ('gram-frozen', 6): 1, ('csr-uniform', 12): 1, ('csr-uniform', 17): 1,
+           ('gram-early', 1): 1, ('gram-early', 10): 1, ('gram-early', 18): 1, ('gram-early', 20): 1, ('gram-early-u8', 2): 1}
 
 
 def random_sequence(flavour, seed):
@@ -1400,6 +1432,7 @@ class Case(object):
       ('scales', j)      the last two operations (sweep(1), objective) on the current counts under the scales before operation j
       ('frozen', j)      the last operation under the frozen statistics as they were before operation j
       ('uniform', j)     the last operation on the current stored part of X under the list and value of before operation j
+      ('W_col', j, tt)   the last operation (update_W_col) with the early-sums partials T T[tt,:]^T of the T before operation j
     """
 
     def __init__(self, name, row, flavour, ops, stale=None, waived=None, raises=None):
@@ -1558,6 +1591,50 @@ for _b in CORPUS_BORROWERS + ['absorb']:
     for _nname, _next in (('sweep', S1), ('update_T_row', ('update_T_row', 0))):
         CASES.append(_case('carry-%s-csr-%s' % (_b, _nname), 'carry_valid / carry_topic', 'csr', [S1, _op, _next],
                            waived='an overwritten scratch buffer is no value the oracle can state'))
+# ---- the early-sums schedule ('gram-early': RRI_TROW_SMALL=0).  What it keeps between steps and calls: early_valid / early_topic, the
+#      partials of T T[t,:]^T that k_trow_early leaves for the early job of topic t's pass, and carry_wfin / wfin_topic, which say
+#      that the carry is k_wfin's (red reduced already, two Gram entries as tile sums in wfp).  Every case is "sweep, change,
+#      sweep or half step"; after the first sweep the carry of topic 0 is k_wfin's and wfp is live -----------------------------------
+_E = 'gram-early'
+_EROW = 'early_valid / early_topic'
+_CROW = 'carry_valid / carry_wfin / wfin_topic'
+# the rows of the table above changed() that a plain Gram-form handle has (resid_valid belongs to the weighted and the explicit-
+# residual handles, obj_track_valid to the persistent sweep: neither exists under this flavour's environment)
+for _name, _chg in (('upload_X', ('upload_X', 2)), ('scale_X', ('scale_X', 3))):
+    CASES.append(_case('early-x_sq-%s' % _name, 'x_sq_valid', _E, [S1, OBJ, _chg, S1, OBJ], stale=('x_sq', 2)))
+for _name, _chg in (('project_W_rows', ('project_W', 1.0)), ('rollback', ('rollback',)), ('apply_reset_vectors', ('reset', 4)), ('set_T', ('set_T', 5))):
+    _steps = ([('snapshot',)] if _name == 'rollback' else []) + [S1, OBJ, _chg, OBJ]
+    CASES.append(_case('early-xy-%s' % _name, 'xy_run / xy_valid', _E, _steps, stale=('xy', len(_steps) - 2)))
+for _name, _chg, _fields in (('set_T', ('set_T', 6), ('T',)), ('upload_X', ('upload_X', 4), ('X',))):
+    # a free sweep first: the fixed-T sweeps run behind the schedule, whose last T half left early_valid and whose last W half the carry
+    CASES.append(_case('early-q-%s' % _name, 'q_valid / gfull_valid', _E, [S1, ('set_params', 'fix_T'), S1, _chg, S1], stale=('factors', 3, _fields)))
+# the carry of topic 0 as k_wfin leaves it, taken from the old X
+for _name, _chg in (('upload_X', ('upload_X', 2)), ('scale_X', ('scale_X', 3))):
+    CASES.append(_case('early-carry-%s-sweep' % _name, _CROW, _E, [S1, _chg, S1], stale=('factors', 1, ('X',))))
+    CASES.append(_case('early-carry-%s-update_T_row' % _name, _CROW, _E, [S1, _chg, ('update_T_row', 0)], stale=('T_row', 1)))
+# early_valid: a change between the T half and the W half of ONE topic -- the W half must not take T T[t,:]^T from Tearly.  reset(7)
+# rewrites topic 2 itself, reset(13) topic 3 (entry 3 of T T[2,:]^T); the rollback takes T back to the snapshot
+for _name, _chg in (('reset-own-topic', ('reset', 7)), ('reset-other-topic', ('reset', 13)), ('rollback', ('rollback',)), ('set_T', ('set_T', 5))):
+    _steps = ([('snapshot',)] if _name == 'rollback' else []) + [S1, ('update_T_row', 2), _chg, ('update_W_col', 2)]
+    CASES.append(_case('early-halves-%s' % _name, _EROW, _E, _steps, stale=('W_col', len(_steps) - 2, 2)))
+# ... and a sweep ends with early_topic = K - 1: a lone W half of that topic after T was written from outside
+CASES.append(_case('early-lone_W_half-after-set_T', _EROW, _E, [S1, ('set_T', 5), ('update_W_col', K - 1)], stale=('W_col', 1, K - 1)))
+# early_topic: the partials are those of topic 2, the W half is topic 3's
+CASES.append(_case('early-topic-other_W_half', _EROW, _E, [S1, ('update_T_row', 2), ('update_W_col', 3)], stale=('W_col', 2, 2)))
+# the borrowers between k_wfin and the T half that takes up its carry
+for _b in BORROWERS:
+    _op = (_b,) if _b == 'argmax_rows' else (_b, _BSALT)
+    for _nname, _next in (('sweep', S1), ('update_T_row', ('update_T_row', 0))):
+        CASES.append(_case('early-carry-%s-%s' % (_b, _nname), _CROW, _E, [S1, _op, _next],
+                           waived='an overwritten scratch buffer is no value the oracle can state'))
+# set_params to a set without the schedule and back (no penalty changes: rri_set_params calls no changed()): the T half under fix_W
+# finds k_wfin's carry, which only k_trow_early can take up (the `carry_wfin && !early` line of enqueue_T_half)
+for _nname, _next in (('sweep', S1), ('update_T_row', ('update_T_row', 0))):
+    CASES.append(_case('early-off_and_on-%s' % _nname, _CROW, _E, [S1, ('set_params', 'fix_W'), _next, ('set_params', 'free'), S1],
+                       waived='k_wfin leaves the Gram row of its carry in another buffer than k_reduce reads: no value the oracle can state'))
+# a call that ends in an error in the middle of the schedule, then a sweep
+CASES.append(_case('early-ended-zero_column', 'carry_valid / pending_wcheck (CH_ENDED)', _E, [S1, ('zero_W_column', 2), S1, ('set_W', 3), S1], raises=2,
+                   waived='an error is a verdict, not a value'))
 CASES = {c.name: c for c in CASES}
 
 
@@ -1596,6 +1673,17 @@ def stale_reference(case):
         T = m.T.copy()
         T[t, :] = ms.half_T(t)
         return (m.W, m.T), (m.W, T)
+    if kind == 'W_col':
+        # the early job's sums from stale partials: T T[tt,:]^T of the T before operation j in place of T T[t,:]^T of the current
+        # one, its entry t for ||T[t,:]||^2; the row dots X T[t,:]^T are the pass's, from the current T
+        t, tt = case.ops[-1].arg, case.stale[2]
+        tts = old['T'].dot(old['T'][tt])
+        nt, tts[t] = float(tts[t]), 0.0
+        regs = {r: PARAMS[cur['pname']].get(r, 0.0) for r in REGS}
+        numer = cur['X'].dot(cur['T'][t]) - cur['W'].dot(tts)
+        W = cur['W'].copy()
+        W[:, t] = o.qf_min(-(numer - regs['reg_w_l1']), nt + regs['reg_w_l2'], s=None, ub=None)[0]
+        return (m.W, m.T), (W, m.T)
     if kind in ('frozen', 'uniform'):
         ms = Model(case.flavour)
         ms.ls.pname, ms.X, ms.M, ms.W, ms.T, ms.F, ms.U, ms.v = (cur[key] for key in ('pname', 'X', 'M', 'W', 'T', 'F', 'U', 'v'))

@@ -7,6 +7,7 @@ request, plus the arrays of a blocked copy or of a row sort.  Request lines (all
 
     plan  n d k dtype flavour n_cu pk_rows pk_il x_pack cache_mb        the dense plan of rri_create (dense_plan)
     keep  <the fields of plan> ldw xp_valid                             pass_keep and its terms
+    early <the fields of plan> n_cu                                     the early-sums schedule of that plan (RRI_PASS_PK_GEOM: pk_rows, pk_il)
     onchip n LD k is_f32 proj n_cu                                      the persistent sweep's geometry
     copy  which sparse_x es n_cu n d nnz indptr... indices...           one blocked copy of a CSR pattern (build_sp_copy)
     csr   rules n d nnz dtype has_data len indptr... len indices...     csr_check (len -1: a null pointer)
@@ -48,6 +49,10 @@ def plan_line(n, d, k, dtype, flavour=UNWEIGHTED, n_cu=256, pk_rows=0, pk_il=-1,
 
 def keep_line(n, d, k, dtype, ldw=None, xp_valid=False, **kw):
     return 'keep' + plan_line(n, d, k, dtype, **kw)[4:] + ' %d %d' % (n if ldw is None else ldw, int(xp_valid))
+
+
+def early_line(n, d, k, dtype, n_cu=256, **kw):
+    return 'early' + plan_line(n, d, k, dtype, n_cu=n_cu, **kw)[4:] + ' %d' % n_cu
 
 
 def copy_line(A, which, csrx, es, n_cu):

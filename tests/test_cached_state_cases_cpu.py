@@ -182,8 +182,13 @@ def test_the_alphabets_of_the_new_flavours():
     assert cs.alphabet('csr-frozen') == csr + cs.FROZEN_OPS + ['upload_X_corpus'] + borrowers + cs.CORPUS_BORROWERS
     assert cs.alphabet('csr-uniform') == csr + cs.UNIFORM_OPS + ['upload_X_corpus'] + borrowers + cs.CORPUS_BORROWERS
     for flavour in cs.RANDOM_FLAVOURS:
-        if flavour not in cs.NEW_FLAVOURS:          # the borrowers went into the LOOK alphabets of the four new flavours only
+        if flavour not in cs.NEW_FLAVOURS + cs.EARLY_FLAVOURS:      # the borrowers went into the LOOK alphabets of the flavours that came after 'gram-u8' only
             assert not set(cs.alphabet(flavour)) & set(borrowers + cs.CORPUS_BORROWERS + cs.FROZEN_OPS + cs.UNIFORM_OPS + ['upload_X_corpus'])
+    # the three flavours on the early-sums schedule: the alphabets of their twins and the borrowers, no state of their own
+    for flavour, twin in zip(cs.EARLY_FLAVOURS, ('gram-phases', 'gram-fp32', 'gram-u8')):
+        assert cs.alphabet(flavour) == cs.alphabet(twin) + borrowers and cs.new_ops(flavour) == [], flavour
+        assert {key: cs.FLAVOURS[flavour][key] for key in ('kind', 'dtype', 'd')} == {key: cs.FLAVOURS[twin][key] for key in ('kind', 'dtype', 'd')}
+        assert cs.FLAVOURS[flavour]['env'] == {'RRI_ONCHIP': '0', 'RRI_TROW_SMALL': '0'}, flavour
     assert cs.FLAVOURS['gram-frozen']['env'] == {'RRI_ONCHIP': '1'} and cs.FLAVOURS['gram-frozen-fp32']['d'] == cs.D_F32
     assert cs.factor_tol('gram-frozen-fp32') == 1e-7 and cs.Model('csr-uniform').U.size > 0
 
@@ -253,8 +258,10 @@ def test_the_sequences_of_the_earlier_flavours_are_what_they_were():
     import hashlib
     earlier = {'gram-onchip': '45bbf291725351b2', 'gram-phases': '19883f57ff211b84', 'residual': 'c7214b4a5f8f5a9b', 'weighted': 'b33bae3231fea92d',
                'pattern': 'd61e7ca1a6c2ccf5', 'csr': '7d5639a21a7150a8', 'gram-fp32': 'ac38742c61bd4f9f', 'gram-u8': 'd9b8aea59e7e0128'}
-    assert cs.RANDOM_FLAVOURS == list(earlier) + cs.NEW_FLAVOURS and list(cs.FLAVOURS)[-4:] == cs.NEW_FLAVOURS
+    # the earlier lists as they were, as a prefix; the three flavours of the early-sums schedule behind them, in this order
+    assert cs.RANDOM_FLAVOURS[:12] == list(earlier) + cs.NEW_FLAVOURS and list(cs.FLAVOURS)[-7:-3] == cs.NEW_FLAVOURS
     assert cs.NEW_FLAVOURS == ['gram-frozen', 'gram-frozen-fp32', 'csr-frozen', 'csr-uniform']
+    assert cs.RANDOM_FLAVOURS[12:] == cs.EARLY_FLAVOURS == list(cs.FLAVOURS)[-3:] == ['gram-early', 'gram-early-fp32', 'gram-early-u8']
     for flavour, digest in earlier.items():
         h = hashlib.sha256()
         for seed in range(24):
@@ -268,7 +275,26 @@ def test_the_sequences_of_the_earlier_flavours_are_what_they_were():
     before = {('gram-onchip', 2): 1, ('gram-onchip', 3): 1, ('gram-onchip', 7): 1, ('gram-onchip', 9): 1, ('gram-onchip', 13): 1,
               ('gram-onchip', 19): 1, ('gram-phases', 14): 1, ('residual', 10): 1, ('residual', 13): 1, ('csr', 3): 1, ('csr', 6): 1,
               ('csr', 10): 1, ('csr', 12): 1, ('csr', 22): 1, ('gram-fp32', 9): 1, ('gram-u8', 21): 1}
-    assert {key: val for key, val in cs.REDRAWS.items() if key[0] not in cs.NEW_FLAVOURS} == before
+    assert {key: val for key, val in cs.REDRAWS.items() if key[0] not in cs.NEW_FLAVOURS + cs.EARLY_FLAVOURS} == before
+    assert {key: val for key, val in cs.REDRAWS.items() if key[0] in cs.NEW_FLAVOURS} == {('gram-frozen', 6): 1, ('csr-uniform', 12): 1, ('csr-uniform', 17): 1}
+
+
+def test_early_sweeps_counts_the_sweeps_on_the_schedule():
+    """cs.early_sweeps: free, clipped and penalised sweeps run on the early-sums schedule, sweeps with a factor fixed or T projected
+    do not, and the sweep that a case expects to raise is not counted; every default sequence of the three flavours ends in one"""
+    ops = [cs.Op(*x) for x in (('sweep', 2), ('set_params', 'fix_T'), ('sweep', 1), ('set_params', 'pen_a'), ('sweep', 1), ('set_params', 'simplex'),
+                               ('sweep', 1), ('set_params', 'clip'), ('update_T_row', 1), ('sweep', 1), ('set_params', 'fix_W'), ('sweep', 1))]
+    assert cs.early_sweeps(ops) == 3 and cs.early_sweeps(ops, raises=0) == 2
+    assert [cs.early_schedule(p) for p in sorted(cs.PARAMS)] == [True, False, False, True, True, True, False], sorted(cs.PARAMS)
+    for flavour in cs.EARLY_FLAVOURS:
+        for seed in range(cs.DEFAULT_SEEDS):
+            ops = cs.random_sequence(flavour, seed)
+            ls = cs.LegalState('plain')
+            for op in ops[:-2]:
+                ls.follow(op)
+            assert cs.early_sweeps(ops) >= 1 or not cs.early_schedule(ls.pname), (flavour, seed)     # (the last two: sweep(1), objective)
+    case = cs.CASES['early-ended-zero_column']
+    assert cs.early_sweeps(case.ops, raises=case.raises) == 2
 
 
 def test_the_uint8_model_keeps_counts_and_scales_consistent_with_its_X():

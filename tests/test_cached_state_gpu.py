@@ -38,6 +38,27 @@ wrong verdict, none a fault):
      clear_frozen.
 No case failed on the unmodified library.
 
+The early-sums schedule keeps four more fields -- early_valid / early_topic (the partials of T T[t,:]^T in Tearly) and
+carry_wfin / wfin_topic (the carry is k_wfin's) -- and at 700 x 333 only RRI_TROW_SMALL=0 reaches it: the flavours 'gram-early',
+'gram-early-fp32' and 'gram-early-u8' draw the alphabets of their twins and the evaluation calls into sequences on it (a sequence
+with a sweep that admits the schedule must end with early_steps > 0: run_case), and the directed cases 'early-*' are "sweep, change,
+sweep or half step" for every row of the table a plain handle has, for a change between the T half and the W half of one topic, for
+every evaluation call between k_wfin and the T half that takes up its carry, for parameters that switch the schedule off and back
+without a changed(), and for a call that ends in an error.  That they can fail: three more mutations, host-side flags only (every
+index stays in bounds, the numbers go stale), one line at a time, the whole file against each:
+  5. `if (what) c->early_valid = false;` taken out of changed(): the four cases of test_a_change_between_the_two_halves_of_a_topic
+     (update_W_col(2) behind reset-own-topic off by 1.1e+0 in W, reset-other-topic 2.2e-2, rollback 9.5e-1, set_T 7.6e-1) and
+     test_a_lone_W_half_of_the_last_topic_after_set_T (7.5e+0); no random sequence of the 24 default seeds puts a write from outside
+     between the two halves of one topic, which is why the directed cases are there;
+  6. `&& c->early_topic == t` taken out of enqueue_W_half: test_a_W_half_of_another_topic_than_the_T_half_before_it (W off by 5.4e-1),
+     test_random_sequence[gram-early-20] (update_T_row(2), update_W_col(1): 9.4e-1) and [gram-frozen-21] (update_T_row(2),
+     update_W_col(3) under statistics: 3.0e+0);
+  7. `if (c->carry_wfin && !early) c->carry_valid = false;` taken out of enqueue_T_half: both cases of
+     test_parameters_without_the_schedule_and_back (the sweep under fix_W off by 1.6e+0 in T and 1.8e+0 in W, update_T_row(0) by
+     1.6e+0) and test_statistics_change_between_producer_and_consumer[plain-carry-clear-sweep] (the sweep behind clear_frozen, where
+     a handle of this size goes back to k_trow_small: T off by 1.7e+0).
+Again no case failed on the unmodified library.
+
 Reference of the two earlier sequences: the CPU oracle, chained call by call with W_in / T_in, eps_stop=-1, in float64.  Tolerance: relfro < 1e-9 on W and
 on T of a float64 handle (summation order only, as tests/test_residual_gpu.py between two float64 runs).  A stale Qt cannot
 hide under it: given the T of the first fixed call in place of the current one, the oracle's last call ends with a W that is
@@ -145,9 +166,23 @@ def run_case(monkeypatch, flavour, ops, raises=None):
             launches, want = e.onchip_info()[1], cs.persistent_sweeps(ops)
             print('persistent launches: %d of %d free sweeps' % (launches, want))
             assert launches >= (want if e.onchip_fallbacks() == 0 else min(want, 1)), (launches, want, e.onchip_fallbacks())
+        if flavour in cs.EARLY_FLAVOURS:
+            # the flavour is there for the early-sums schedule: a sequence with a sweep under parameters that admit it has taken k_wfin
+            info, want = e.layout_info(), cs.early_sweeps(ops, raises)
+            print('early-sums schedule: %d W halves through k_wfin, %d sweeps that must have taken it' % (info['early_steps'], want))
+            assert want == 0 or info['early_steps'] > 0, (info, want)
+            assert info['early_sums'] == cs.early_schedule(final_pname(ops)), info
         return answers
     finally:
         e.close()
+
+
+def final_pname(ops):
+    """the parameter set (cs.PARAMS) a handle holds after ops"""
+    ls = cs.LegalState('plain')
+    for op in ops:
+        ls.follow(op)
+    return ls.pname
 
 
 def directed(monkeypatch, name):
@@ -356,6 +391,57 @@ def test_uniform_rows_behind_statistics_are_refused(monkeypatch, second):
     order, and X (both blocked stores), the list, the statistics, W and T are bit for bit what they were (cs_cases.fingerprint);
     the sweep(1) that follows is the model's"""
     case = cs.CASES['mixed-' + second]
+    run_case(monkeypatch, case.flavour, case.ops, raises=case.raises)
+
+
+# ---- the early-sums schedule: early_valid / early_topic, carry_wfin / wfin_topic ('gram-early': RRI_TROW_SMALL=0) -----------------------
+EARLY_TABLE = ['x_sq-upload_X', 'x_sq-scale_X', 'xy-project_W_rows', 'xy-rollback', 'xy-apply_reset_vectors', 'xy-set_T', 'q-set_T', 'q-upload_X',
+               'carry-upload_X-sweep', 'carry-upload_X-update_T_row', 'carry-scale_X-sweep', 'carry-scale_X-update_T_row']
+
+
+@pytest.mark.parametrize('case', EARLY_TABLE)
+def test_rows_of_the_table_on_the_early_sums_schedule(monkeypatch, case):
+    """every row of the table above changed() that a plain Gram-form handle has (resid_valid belongs to the weighted and explicit-
+    residual handles, obj_track_valid to the persistent sweep), as "sweep, change, sweep or half step" with the first sweep on the
+    schedule: the carry that the change finds is k_wfin's"""
+    directed(monkeypatch, 'early-' + case)
+
+
+@pytest.mark.parametrize('change', ['reset-own-topic', 'reset-other-topic', 'rollback', 'set_T'])
+def test_a_change_between_the_two_halves_of_a_topic(monkeypatch, change):
+    """early_valid: sweep(1), update_T_row(2) leaves T T[2,:]^T in Tearly, T is written from outside, update_W_col(2) must take
+    k_wcol and the current T"""
+    directed(monkeypatch, 'early-halves-' + change)
+
+
+def test_a_lone_W_half_of_the_last_topic_after_set_T(monkeypatch):
+    """early_valid: a sweep ends with early_topic = K - 1; set_T; update_W_col(K - 1)"""
+    directed(monkeypatch, 'early-lone_W_half-after-set_T')
+
+
+def test_a_W_half_of_another_topic_than_the_T_half_before_it(monkeypatch):
+    """early_topic: sweep(1), update_T_row(2), update_W_col(3): the partials in Tearly are topic 2's"""
+    directed(monkeypatch, 'early-topic-other_W_half')
+
+
+@pytest.mark.parametrize('then', ['sweep', 'update_T_row'])
+@pytest.mark.parametrize('borrower', cs.BORROWERS)
+def test_k_wfin_carry_after_a_borrower(monkeypatch, borrower, then):
+    """carry_wfin / wfin_topic: after a sweep on the schedule the carry of topic 0 is k_wfin's -- red reduced, two Gram entries as
+    tile sums in wfp; an evaluation call runs between it and the T half that takes it up (test_carry_after_a_borrower has the rules)"""
+    directed(monkeypatch, 'early-carry-%s-%s' % (borrower, then))
+
+
+@pytest.mark.parametrize('then', ['sweep', 'update_T_row'])
+def test_parameters_without_the_schedule_and_back(monkeypatch, then):
+    """carry_wfin under early_ok false: sweep(1), set_params(fix_W) (no penalty changes: no changed()), a T half that finds k_wfin's
+    carry and must start from the prologue, set_params(free), sweep(1)"""
+    directed(monkeypatch, 'early-off_and_on-' + then)
+
+
+def test_sweep_on_the_schedule_after_a_call_that_ended_in_an_error(monkeypatch):
+    """CH_ENDED: sweep(1), W with a zero column, sweep(1) raises as the oracle does in the middle of the schedule, set_W(good), sweep(1)"""
+    case = cs.CASES['early-ended-zero_column']
     run_case(monkeypatch, case.flavour, case.ops, raises=case.raises)
 
 

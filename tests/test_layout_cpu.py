@@ -12,7 +12,8 @@ module (tests/layout_cases.py).  Checked:
   2. every blocked copy is a permutation of the stored entries with pads of (-1, bw), quad-aligned ascending segment pointers and
      work items that cover every (block, segment) exactly once;
   3. the rules no suite restates, at values worked out by hand from rri_create as it stood before the header existed (the
-     arithmetic is in the comments of each case);
+     arithmetic is in the comments of each case); 3b: the early-sums schedule at the shapes of tests/test_early_sums_routes_gpu.py
+     and 256 CUs -- the pass's own workgroups against early_job_first, tiles per job workgroup, the grids behind the pass;
   4. every refusal text of the CSR checks for the input that triggers it, and the row sort."""
 import numpy as np
 import pytest
@@ -21,6 +22,7 @@ import scipy.sparse as sp
 import layout_cases as lc
 import ld_cases
 import onchip_cases as oc
+import test_early_sums_routes_gpu as er
 import test_onchip_cases_cpu
 import test_pass_keep_gpu as pk
 import test_xpack_gpu as xg
@@ -136,9 +138,45 @@ for _code in ALL_TYPES:
     HAND_PLANS['tiny-panel+1-%d' % _code] = ((33, _pw + 1, 2, _code), dict(LD=_pw + VN[_code], npanels=2, rpb=32, nrb=2))
 
 
+# ---- 3b. the early-sums schedule at the shapes of tests/test_early_sums_routes_gpu.py, 256 CUs: F = early_job_first's 4 n_cu = 1024 -------
+# fields: npanels, rpb, nrb, P = npanels nrb, first = min(P, F), e_blocks = min(tiles, 64), e_tpb = ceil(tiles / e_blocks), idle =
+# e_blocks - ceil(tiles / e_tpb) job workgroups without a tile, nte = ceil(d / 256), nwfin = ceil(n / 1024), nsplit = min(8, d / 2048)
+EARLY_A1 = {
+    # RRI_PASS_PK_GEOM=16c / 16i, fp32, d = 130 (one panel): P = ceil(n / 16)
+    'F-1': dict(npanels=1, rpb=16, nrb=1023, P=1023, first=1023, e_blocks=64, tiles=256, e_tpb=4, idle=0, nte=1, nwfin=16, nsplit=1),
+    'F': dict(npanels=1, rpb=16, nrb=1024, P=1024, first=1024, e_blocks=64, tiles=256, e_tpb=4, idle=0, nte=1, nwfin=16, nsplit=1),
+    # 16385 rows: 257 tiles -> 5 per job workgroup, 52 of the 64 walk tiles
+    'F+1': dict(npanels=1, rpb=16, nrb=1025, P=1025, first=1024, e_blocks=64, tiles=257, e_tpb=5, idle=12, nte=1, nwfin=17, nsplit=1),
+    'F+11': dict(npanels=1, rpb=16, nrb=1035, P=1035, first=1024, e_blocks=64, tiles=259, e_tpb=5, idle=12, nte=1, nwfin=17, nsplit=1),
+    '2F': dict(npanels=1, rpb=16, nrb=2048, P=2048, first=1024, e_blocks=64, tiles=512, e_tpb=8, idle=0, nte=1, nwfin=32, nsplit=1),
+    # 5473 x 2503: LD 2504, 3 panels x 343 row blocks; 86 tiles -> 2 per job workgroup, 43 walk tiles; 10 workgroups of k_trow_early
+    'three-panels': dict(npanels=3, rpb=16, nrb=343, P=1029, first=1024, e_blocks=64, tiles=86, e_tpb=2, idle=21, nte=10, nwfin=6, nsplit=1),
+    # 3300 x 4100: 5 panels x 207 row blocks; 52 tiles, a job workgroup each; the Gram-row job in two column slices
+    'five-panels-nsplit2': dict(npanels=5, rpb=16, nrb=207, P=1035, first=1024, e_blocks=52, tiles=52, e_tpb=1, idle=0, nte=17, nwfin=4, nsplit=2),
+}
+EARLY_ROWS = {      # d = 130, k = 5, no switch: a pass of one round, the job last
+    1024: dict(tiles=16, e_blocks=16, e_tpb=1, idle=0, nwfin=1), 1025: dict(tiles=17, e_blocks=17, e_tpb=1, idle=0, nwfin=2),
+    4096: dict(tiles=64, e_blocks=64, e_tpb=1, idle=0, nwfin=4),
+    # 65 tiles on 64 job workgroups: two each, 33 walk tiles, 31 store a row of zeros
+    4097: dict(tiles=65, e_blocks=64, e_tpb=2, idle=31, nwfin=5), 4160: dict(tiles=65, e_blocks=64, e_tpb=2, idle=31, nwfin=5),
+}
+EARLY_COLS = {128: (1, 1), 129: (1, 2), 255: (1, 2), 256: (1, 2), 257: (2, 3), 384: (2, 3), 385: (2, 4)}      # n = 200: d -> (nte, ntb = ceil(d / 128))
+
+
 @pytest.fixture(scope='module')
 def asked(tmp_path_factory):
     a = Asked()
+    for name in er.A1_SHAPES:
+        n, d, k, _, _ = er.a1_shape(name, 256)
+        for il in (0, 1):
+            a.ask('early-%s-%d' % (name, il), lc.early_line(n, d, k, RRI_F32, pk_rows=16, pk_il=il))
+    for code in (RRI_F32, RRI_F64):
+        for n in EARLY_ROWS:
+            a.ask('early-n%d-%d' % (n, code), lc.early_line(n, 130, 5, code))
+        for d in EARLY_COLS:
+            a.ask('early-d%d-%d' % (d, code), lc.early_line(200, d, 5, code))
+    a.ask('early-lds-16rows', lc.early_line(16368, 130, 1024, RRI_F32, pk_rows=16, pk_il=0))
+    a.ask('early-lds-32rows', lc.early_line(1000, 300, 1024, RRI_F64))
     for name, (args, _) in HAND_PLANS.items():
         a.ask(name, lc.plan_line(*args[:4], **(args[4] if len(args) > 4 else {})))
     # pass_keep at 30011 x 2503, k = 4 (fp32: LD 2504, 3 panels; 170 blocks -> 177 rows -> 192 rows, 157 blocks; 469 blocks of 64 rows)
@@ -260,6 +298,42 @@ def test_plan_values_worked_out_by_hand(asked, name):
     got = asked[name]
     for f, v in HAND_PLANS[name][1].items():
         assert got[f] == v, (name, f, got[f], v)
+
+
+@pytest.mark.parametrize('name', er.A1_SHAPES)
+def test_early_job_sits_where_the_gpu_cases_say(asked, name):
+    """the shapes of test_early_sums_routes_gpu.test_job_inside_the_grid at 256 CUs: the job's first workgroup against the pass's own
+    count P on the side of F = 1024 that the case names, in both chunk orders"""
+    n, d, k, P, side = er.a1_shape(name, 256)
+    for il in (0, 1):
+        got = asked['early-%s-%d' % (name, il)]
+        for f, v in EARLY_A1[name].items():
+            assert got[f] == v, (name, il, f, got[f], v)
+        assert got['P'] == P and got['interleaved'] == il
+        assert {'below': P < 1024 and got['first'] == P, 'at': P == 1024 and got['first'] == P,
+                'above': P > 1024 and got['first'] == 1024}[side], (name, got)
+        assert got['job_lds'] <= got['pass_lds']
+    assert [nm for nm in er.A1_SHAPES if er.a1_shape(nm, 256)[4] == 'above'] == list(er.A1_INSIDE)
+    assert er.a1_shape('F+11', 256)[3] % 8 == 3 and er.a1_shape('five-panels-nsplit2', 256)[1] >= 4096
+
+
+def test_early_job_tiles_and_the_grids_behind_it(asked):
+    """the row and column edges of test_early_sums_routes_gpu.py: tiles per job workgroup and job workgroups without a tile, the tile
+    workgroups of k_wfin, the workgroups of k_trow_early and the entries of tpart; the job's LDS inside the pass's at k = 1024"""
+    for code in (RRI_F32, RRI_F64):
+        for n, want in EARLY_ROWS.items():
+            got = asked['early-n%d-%d' % (n, code)]
+            for f, v in dict(want, nte=1, npanels=1, first=got['P']).items():
+                assert got[f] == v, (n, code, f, got[f], v)
+            assert got['P'] <= 1024
+        for d, (nte, ntb) in EARLY_COLS.items():
+            got = asked['early-d%d-%d' % (d, code)]
+            assert (got['nte'], got['ntb'], got['tiles'], got['e_blocks'], got['e_tpb'], got['idle'], got['nwfin']) == (nte, ntb, 4, 4, 1, 0, 1), (d, code, got)
+            # k_trow_early's guard `(blockIdx.x * 2 + tid) * 128 < d` writes exactly the ntb entries of tpart that k_tgram adds
+            assert sum((2 * b + tid) * 128 < d for b in range(nte) for tid in (0, 1)) == ntb, d
+    # early_job_lds_doubles(1024) = 2 * 1024 + 2 + 256 = 2306 doubles against the pass's 5 rpb + 4 * 8 * 72: 2384 at 16 rows, 2464 at 32
+    small, floor = asked['early-lds-16rows'], asked['early-lds-32rows']
+    assert (small['rpb'], small['job_lds'], small['pass_lds']) == (16, 2306, 2384) and (floor['rpb'], floor['job_lds'], floor['pass_lds']) == (32, 2306, 2464)
 
 
 def test_pass_keep_by_hand(asked):
