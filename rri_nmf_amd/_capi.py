@@ -162,6 +162,13 @@ CORPUS_OPS_PROTOTYPES = {
     'rri_corpus_split': (_I32, [_P, _P, C.c_uint32, C.c_uint64, C.POINTER(_P), C.POINTER(_P)]),
 }
 
+# ... and every symbol include/rri_corpus_build.h declares: a corpus from (row, column, value) pairs and a split by whole entries.
+# A table of its own again: these calls, too, keep and touch none of a handle's cached state
+CORPUS_BUILD_PROTOTYPES = {
+    'rri_corpus_from_pairs': (_I32, [_P, C.POINTER(_P), _I64, _I64, _I64, _P, _P, _I32, _I64, _P, _I32, _I32]),
+    'rri_corpus_split_entries': (_I32, [_P, _P, C.c_uint32, C.c_uint64, C.POINTER(_P), C.POINTER(_P)]),
+}
+
 _lib = None
 
 
@@ -222,7 +229,7 @@ def load_library(path=None):
         lib = C.CDLL(p)
     except OSError as e:  # e.g. libamdhip64 missing
         raise RRIHipUnavailable('cannot load %s: %s' % (p, e))
-    for name, (res, args) in list(PROTOTYPES.items()) + list(CORPUS_OPS_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(CORPUS_OPS_PROTOTYPES.items()) + list(CORPUS_BUILD_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -50,6 +50,8 @@
 #include "rri_spbuild_kernels.hpp"
 #include "rri_corpus_ops.h"
 #include "rri_derive_kernels.hpp"
+#include "rri_corpus_build.h"
+#include "rri_corpus_build_kernels.hpp"
 
 using namespace rri;
 
@@ -4384,6 +4386,279 @@ rri_status rri_corpus_split(rri_ctx* c, const rri_corpus* k, uint32_t thr, uint6
     }
     *observed = corpus_adopt(c->device, k->n_rows, k->n_cols, nnz_o, 0, optr, oidx, oval, std::move(h_optr), ms);
     *held = corpus_adopt(c->device, k->n_rows, k->n_cols, nnz_h, 0, hptr, hidx, hval, std::move(h_hptr), ms);
+    return RRI_OK;
+}
+
+// ---- a corpus from pairs, a split by entry (rri_corpus_build.hpp has the semantics, rri_corpus_build_kernels.hpp the kernels) ------
+rri_status rri_corpus_from_pairs(rri_ctx* c, rri_corpus** out, int64_t n_rows, int64_t n_cols, int64_t n_pairs, const void* rows,
+                                 const void* cols, int32_t index_dtype, int64_t index_stride, const void* values,
+                                 int32_t values_dtype, int32_t on_device) {
+    CHECK_CTX(c);
+    if (!out) return fail(c, RRI_ERR_INVALID, "the output pointer is NULL");
+    *out = nullptr;
+    const CorpusPairs req{n_rows, n_cols, n_pairs, rows, cols, index_dtype, index_stride, values, values_dtype};
+    char why[200] = "";
+    const int bad = pairs_check_args(req, why, sizeof why);
+    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t isz = corpus_dtype_size(index_dtype), vsz = corpus_dtype_size(values_dtype);
+    const i64 stride = index_stride;
+    // the arrays on the device: the caller's own, or an upload as they lie -- an interleaved pair of index arrays travels once
+    DevTmp ra, rb, rv;
+    const void *dr = rows, *dc = cols, *dv = values;
+    if (!on_device && n_pairs > 0) {
+        const size_t span = ((size_t)(n_pairs - 1) * (size_t)stride + 1) * isz;
+        const uintptr_t r0 = (uintptr_t)rows, c0 = (uintptr_t)cols, lo = std::min(r0, c0), hi = std::max(r0, c0) + span;
+        if (std::max(r0, c0) - lo < span) {            // the two spans overlap: one upload covers both
+            HIPCHK(c, ra.alloc(hi - lo));
+            HIPCHK(c, hipMemcpyAsync(ra.p, (const void*)lo, hi - lo, hipMemcpyHostToDevice, c->stream));
+            dr = (const char*)ra.p + (r0 - lo);
+            dc = (const char*)ra.p + (c0 - lo);
+        } else {
+            HIPCHK(c, ra.alloc(span));
+            HIPCHK(c, rb.alloc(span));
+            HIPCHK(c, hipMemcpyAsync(ra.p, rows, span, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(rb.p, cols, span, hipMemcpyHostToDevice, c->stream));
+            dr = ra.p;
+            dc = rb.p;
+        }
+        if (values) {
+            HIPCHK(c, rv.alloc((size_t)n_pairs * vsz));
+            HIPCHK(c, hipMemcpyAsync(rv.p, values, (size_t)n_pairs * vsz, hipMemcpyHostToDevice, c->stream));
+            dv = rv.p;
+        }
+    }
+    DevTmp tstat, tcnt, tfill, tptr, tslots, tclen, sidx, sval;
+    HIPCHK(c, tstat.alloc(CORPUS_STAT_WORDS * sizeof(u64)));
+    HIPCHK(c, tcnt.alloc(at_least((size_t)n_rows * sizeof(unsigned))));
+    u64* stats = (u64*)tstat.p;
+    HIPCHK(c, hipMemsetAsync(stats, 0xff, 8 * sizeof(u64), c->stream));
+    HIPCHK(c, hipMemsetAsync(stats + 8, 0, 8 * sizeof(u64), c->stream));
+    HIPCHK(c, hipMemsetAsync(tcnt.p, 0, at_least((size_t)n_rows * sizeof(unsigned)), c->stream));
+    EventPair ev[4];          // the phases between two reads of the host: check, count, claim and sorts, compaction
+    int phases = 0;
+    for (EventPair& p : ev) HIPCHK(c, p.create());
+    u64 h_stat[CORPUS_STAT_WORDS];
+    const dim3 pgrid(pairs_grid(n_pairs));
+
+    // 1. the check, by position only; nothing else runs before its verdict is read
+    HIPCHK(c, hipEventRecord(ev[phases].a, c->stream));
+    if (n_pairs > 0) {
+        hipLaunchKernelGGL(k_pairs_check, pgrid, dim3(256), 0, c->stream, dr, dc, (int)index_dtype, stride, dv, (int)values_dtype,
+                           (i64)n_rows, (i64)n_cols, (i64)n_pairs, stats);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(ev[phases++].b, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_stat, stats, sizeof h_stat, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int rule = 0; rule < CB_RULES; ++rule)
+        if (h_stat[rule] != ~0ull) {           // the first broken rule at its smallest position; the offending number is one element
+            const i64 pos = (i64)h_stat[rule];
+            int64_t ival = 0;
+            double dval = 0.0;
+            unsigned char el[8] = {0};
+            if (rule < 2) {
+                HIPCHK(c, hipMemcpy(el, (const char*)(rule == 0 ? dr : dc) + (size_t)pos * (size_t)stride * isz, isz, hipMemcpyDeviceToHost));
+                ival = corpus_idx(el, index_dtype, 0);
+            } else {
+                HIPCHK(c, hipMemcpy(el, (const char*)dv + (size_t)pos * vsz, vsz, hipMemcpyDeviceToHost));
+                dval = corpus_val(el, values_dtype, 0);
+            }
+            pairs_rule_text(rule, pos, ival, dval, why, sizeof why);
+            return fail(c, RRI_ERR_INVALID, "%s", why);
+        }
+
+    // 2. the pairs of every row, one integer atomic per run of equal rows inside a wave; the host takes the exclusive scan
+    HIPCHK(c, hipEventRecord(ev[phases].a, c->stream));
+    if (n_pairs > 0) {
+        hipLaunchKernelGGL(k_pairs_count, pgrid, dim3(256), 0, c->stream, dr, (int)index_dtype, stride, (i64)n_pairs, (unsigned*)tcnt.p);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(ev[phases++].b, c->stream));
+    std::vector<unsigned> h_cnt((size_t)n_rows);
+    if (n_rows > 0) HIPCHK(c, hipMemcpyAsync(h_cnt.data(), tcnt.p, (size_t)n_rows * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<int64_t> h_ptr((size_t)n_rows + 1, 0);
+    // every row with a pair is sorted, by class, ascending: [short | medium by padded length | long], and the long rows' places in the key buffer
+    std::vector<int64_t> list_short, list_long, keyoff;
+    std::vector<std::vector<int64_t>> list_medium;          // [log2 of the padded length]
+    i64 key_total = 0;
+    for (i64 r = 0; r < n_rows; ++r) {
+        const i64 len = h_cnt[(size_t)r];
+        h_ptr[(size_t)r + 1] = h_ptr[(size_t)r] + len;
+        if (len == 0) continue;
+        if (len > CORPUS_ROW_MAX) return fail(c, RRI_ERR_UNSUPPORTED, "row %lld has %lld pairs: more than %lld are not sorted", (long long)r, (long long)len, (long long)CORPUS_ROW_MAX);
+        const int cls = corpus_row_class(true, len);
+        if (cls == CORPUS_ROW_SHORT) list_short.push_back(r);
+        else if (cls == CORPUS_ROW_MEDIUM) {
+            int lg = 0;
+            while ((1ll << lg) < corpus_pad(len)) ++lg;
+            if (list_medium.size() <= (size_t)lg) list_medium.resize((size_t)lg + 1);
+            list_medium[(size_t)lg].push_back(r);
+        } else {
+            list_long.push_back(r);
+            keyoff.push_back(key_total);
+            key_total += corpus_pad(len);
+        }
+    }
+    if (h_ptr[(size_t)n_rows] != n_pairs) return fail(c, RRI_ERR_HIP, "the rows' counts add up to %lld, not to the %lld pairs", (long long)h_ptr[(size_t)n_rows], (long long)n_pairs);
+
+    // 3. every pair claims a slot of its row; every row is sorted by (column, pair position) and merged into the staging at its raw offset
+    DevTmp tlist, tkoff, tkeys, fptr, fidx, fval;
+    HIPCHK(c, derive_upload(tptr, h_ptr, c->stream));
+    HIPCHK(c, tfill.alloc(at_least((size_t)n_rows * sizeof(unsigned))));
+    HIPCHK(c, tslots.alloc(at_least((size_t)n_pairs * sizeof(unsigned))));
+    HIPCHK(c, tclen.alloc(at_least((size_t)n_rows * sizeof(i64))));
+    HIPCHK(c, sidx.alloc(at_least((size_t)n_pairs * sizeof(int))));
+    HIPCHK(c, sval.alloc(at_least((size_t)n_pairs * sizeof(double))));
+    HIPCHK(c, hipMemsetAsync(tfill.p, 0, at_least((size_t)n_rows * sizeof(unsigned)), c->stream));
+    HIPCHK(c, hipMemsetAsync(tclen.p, 0, at_least((size_t)n_rows * sizeof(i64)), c->stream));
+    std::vector<int64_t> all(list_short);
+    for (const auto& l : list_medium) all.insert(all.end(), l.begin(), l.end());
+    all.insert(all.end(), list_long.begin(), list_long.end());
+    HIPCHK(c, derive_upload(tlist, all, c->stream));
+    HIPCHK(c, hipEventRecord(ev[phases].a, c->stream));
+    if (n_pairs > 0) {
+        hipLaunchKernelGGL(k_pairs_claim, pgrid, dim3(256), 0, c->stream, dr, (int)index_dtype, stride, (i64)n_pairs, (const i64*)tptr.p,
+                           (unsigned*)tfill.p, (unsigned*)tslots.p);
+        HIPCHK(c, hipGetLastError());
+        const i64* dl = (const i64*)tlist.p;
+        if (!list_short.empty()) {
+            hipLaunchKernelGGL(k_pairs_sort_wave, dim3((unsigned)((list_short.size() + 3) / 4)), dim3(256), 0, c->stream, dl,
+                               (i64)list_short.size(), (const i64*)tptr.p, (const unsigned*)tslots.p, dc, (int)index_dtype, stride, dv,
+                               (int)values_dtype, (int*)sidx.p, (double*)sval.p, (i64*)tclen.p, stats);
+            HIPCHK(c, hipGetLastError());
+        }
+        dl += list_short.size();
+        HIPCHK(c, allow_lds<k_pairs_sort_block<true>>(c, CORPUS_LDS_MAX * (int)sizeof(u64)));
+        for (size_t lg = 0; lg < list_medium.size(); ++lg) {
+            const size_t cnt = list_medium[lg].size();
+            if (!cnt) continue;
+            const i64 P = 1ll << lg;
+            hipLaunchKernelGGL(k_pairs_sort_block<true>, dim3((unsigned)cnt), dim3(P <= 1024 ? 256 : 1024), (size_t)P * sizeof(u64), c->stream,
+                               dl, (const i64*)nullptr, (u64*)nullptr, P, (const i64*)tptr.p, (const unsigned*)tslots.p, dc, (int)index_dtype,
+                               stride, dv, (int)values_dtype, (int*)sidx.p, (double*)sval.p, (i64*)tclen.p, stats);
+            HIPCHK(c, hipGetLastError());
+            dl += cnt;
+        }
+        if (!list_long.empty()) {
+            HIPCHK(c, derive_upload(tkoff, keyoff, c->stream));
+            HIPCHK(c, tkeys.alloc((size_t)key_total * sizeof(u64)));
+            hipLaunchKernelGGL(k_pairs_sort_block<false>, dim3((unsigned)list_long.size()), dim3(1024), 0, c->stream, dl, (const i64*)tkoff.p,
+                               (u64*)tkeys.p, (i64)0, (const i64*)tptr.p, (const unsigned*)tslots.p, dc, (int)index_dtype, stride, dv,
+                               (int)values_dtype, (int*)sidx.p, (double*)sval.p, (i64*)tclen.p, stats);
+            HIPCHK(c, hipGetLastError());
+        }
+    }
+    HIPCHK(c, hipEventRecord(ev[phases++].b, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_stat, stats, sizeof h_stat, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));       // (the lists, host memory of this call, have been read by now too)
+    const bool shorter = h_stat[CORPUS_STAT_DUP] + h_stat[CORPUS_STAT_ZERO] > 0;
+    std::vector<int64_t> h_cptr;
+    i64 nnz_c = n_pairs;
+    if (shorter) {
+        // 4. a row became shorter: the canonical lengths go to the host, which takes the prefix sum; the final arrays are written once
+        std::vector<int64_t> h_len((size_t)n_rows);
+        HIPCHK(c, hipMemcpy(h_len.data(), tclen.p, (size_t)n_rows * sizeof(i64), hipMemcpyDeviceToHost));
+        h_cptr.assign((size_t)n_rows + 1, 0);
+        for (i64 r = 0; r < n_rows; ++r) h_cptr[(size_t)r + 1] = h_cptr[(size_t)r] + h_len[(size_t)r];
+        nnz_c = h_cptr[(size_t)n_rows];
+        HIPCHK(c, derive_upload(fptr, h_cptr, c->stream));
+        HIPCHK(c, fidx.alloc(at_least((size_t)nnz_c * sizeof(int))));
+        HIPCHK(c, fval.alloc(at_least((size_t)nnz_c * sizeof(double))));
+        HIPCHK(c, hipEventRecord(ev[phases].a, c->stream));
+        if (nnz_c > 0) {
+            hipLaunchKernelGGL(k_corpus_compact, dim3(corpus_grid(nnz_c)), dim3(256), 0, c->stream, (const i64*)fptr.p, (const i64*)tptr.p,
+                               (i64)n_rows, nnz_c, (const int*)sidx.p, (const double*)sval.p, (int*)fidx.p, (double*)fval.p,
+                               stats + PAIRS_STAT_SCRATCH);          // the negatives were counted where the sums were formed
+            HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, hipEventRecord(ev[phases++].b, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else {
+        h_cptr = h_ptr;
+    }
+    double ms = 0.0;
+    for (int i = 0; i < phases; ++i) {
+        float t = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&t, ev[i].a, ev[i].b));
+        ms += t;
+    }
+    rri_corpus* k = corpus_adopt(c->device, n_rows, n_cols, nnz_c, (i64)h_stat[CORPUS_STAT_NEG], shorter ? fptr : tptr, shorter ? fidx : sidx,
+                                 shorter ? fval : sval, std::move(h_cptr), ms);
+    k->stored = n_pairs;
+    k->rewritten = (i64)h_stat[PAIRS_STAT_REWRITTEN];
+    k->dup = (i64)h_stat[CORPUS_STAT_DUP];
+    k->zeros = (i64)h_stat[CORPUS_STAT_ZERO];
+    k->long_rows = (i64)h_stat[PAIRS_STAT_LONG];
+    *out = k;
+    return RRI_OK;
+}
+
+rri_status rri_corpus_split_entries(rri_ctx* c, const rri_corpus* k, uint32_t thr, uint64_t seed, rri_corpus** observed, rri_corpus** held) {
+    CHECK_CTX(c);
+    if (observed) *observed = nullptr;
+    if (held) *held = nullptr;
+    char why[200] = "";
+    if (!observed || !held) return derive_check_split(thr, observed != nullptr, held != nullptr, why, sizeof why), fail(c, RRI_ERR_INVALID, "%s", why);
+    CHECK_DERIVE_CORPUS(c, k);
+    if (derive_check_split(thr, true, true, why, sizeof why) != TOPN_REQ_OK) return fail(c, RRI_ERR_INVALID, "%s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    // 1. pass A: what every piece holds out
+    const DerivePieces pieces = derive_cut_pieces(k->h_indptr.data(), k->n_rows, nullptr, 0);
+    const i64 np = (i64)pieces.row.size();
+    DevTmp tstat, trow, tsrc, tlen, tnh, toh, too, hptr, hidx, hval, optr, oidx, oval;
+    EventPair ev[2];
+    for (EventPair& p : ev) HIPCHK(c, p.create());
+    HIPCHK(c, tstat.alloc(DERIVE_STAT_WORDS * sizeof(u64)));
+    HIPCHK(c, hipMemsetAsync(tstat.p, 0, DERIVE_STAT_WORDS * sizeof(u64), c->stream));
+    HIPCHK(c, derive_upload(trow, pieces.row, c->stream));
+    HIPCHK(c, derive_upload(tsrc, pieces.src, c->stream));
+    HIPCHK(c, derive_upload(tlen, pieces.len, c->stream));
+    HIPCHK(c, tnh.alloc(at_least((size_t)np * sizeof(int))));
+    std::vector<int> nh((size_t)np), no((size_t)np);
+    HIPCHK(c, hipEventRecord(ev[0].a, c->stream));
+    if (np > 0) {
+        hipLaunchKernelGGL(k_entries_count, dim3(derive_grid(np)), dim3(256), 0, c->stream, (const i64*)trow.p, (const i64*)tsrc.p,
+                           (const int*)tlen.p, np, (const int*)k->indices, (unsigned)thr, (u64)seed, (int*)tnh.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(nh.data(), tnh.p, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipEventRecord(ev[0].b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (i64 p = 0; p < np; ++p) no[(size_t)p] = pieces.len[(size_t)p] - nh[(size_t)p];
+    // 2. the prefix sums on the host, then pass B writes both outputs once
+    std::vector<int64_t> piece_oh, piece_oo, h_hptr, h_optr;
+    derive_offsets(pieces, nh, k->n_rows, &piece_oh, &h_hptr);
+    derive_offsets(pieces, no, k->n_rows, &piece_oo, &h_optr);
+    const i64 nnz_h = h_hptr[(size_t)k->n_rows], nnz_o = h_optr[(size_t)k->n_rows];
+    HIPCHK(c, derive_upload(toh, piece_oh, c->stream));
+    HIPCHK(c, derive_upload(too, piece_oo, c->stream));
+    HIPCHK(c, derive_upload(hptr, h_hptr, c->stream));
+    HIPCHK(c, derive_upload(optr, h_optr, c->stream));
+    HIPCHK(c, hidx.alloc(at_least((size_t)nnz_h * sizeof(int))));
+    HIPCHK(c, hval.alloc(at_least((size_t)nnz_h * sizeof(double))));
+    HIPCHK(c, oidx.alloc(at_least((size_t)nnz_o * sizeof(int))));
+    HIPCHK(c, oval.alloc(at_least((size_t)nnz_o * sizeof(double))));
+    HIPCHK(c, hipEventRecord(ev[1].a, c->stream));
+    if (np > 0) {
+        hipLaunchKernelGGL(k_entries_write, dim3(derive_grid(np)), dim3(256), 0, c->stream, (const i64*)trow.p, (const i64*)tsrc.p,
+                           (const int*)tlen.p, (const i64*)toh.p, (const i64*)too.p, np, (const int*)k->indices, (const double*)k->values,
+                           (unsigned)thr, (u64)seed, (int*)hidx.p, (double*)hval.p, (int*)oidx.p, (double*)oval.p, (u64*)tstat.p);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(ev[1].b, c->stream));
+    u64 h_stat[DERIVE_STAT_WORDS];
+    HIPCHK(c, hipMemcpyAsync(h_stat, tstat.p, sizeof h_stat, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double ms = 0.0;
+    for (EventPair& p : ev) {
+        float t = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&t, p.a, p.b));
+        ms += t;
+    }
+    *observed = corpus_adopt(c->device, k->n_rows, k->n_cols, nnz_o, (i64)h_stat[ENTRIES_STAT_NEG_OBS], optr, oidx, oval, std::move(h_optr), ms);
+    *held = corpus_adopt(c->device, k->n_rows, k->n_cols, nnz_h, (i64)h_stat[ENTRIES_STAT_NEG_HELD], hptr, hidx, hval, std::move(h_hptr), ms);
     return RRI_OK;
 }
 

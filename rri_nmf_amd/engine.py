@@ -163,7 +163,10 @@ class DeviceCorpus(object):
 
     New corpora are derived from it on the device, the source staying as it is: take_rows(rows) and corpus[a:b] / corpus[mask] /
     corpus[index_array] (row subsets, any order, repeats), select_words(keep), document_frequency(), prune_words(min_df, max_df,
-    max_words) and split_counts(held_out, random_state) (include/rri_corpus_ops.h)."""
+    max_words) and split_counts(held_out, random_state) (include/rri_corpus_ops.h).  The two ends of that chain are on the device as
+    well (include/rri_corpus_build.h): from_pairs(pairs, values) makes a corpus of (row, column, value) triples -- tokens, or a
+    ratings log -- without a CSR matrix on the host, and split_entries(held_out, random_state) sends every entry, whole, to a
+    training or a held-out corpus."""
 
     def __init__(self, X, device=0):
         import scipy.sparse as sp
@@ -248,6 +251,120 @@ class DeviceCorpus(object):
                                                    C.c_void_p(values or None), vdt, on_device))
         del keep_alive
         self._read_info()
+
+    @classmethod
+    def from_pairs(cls, pairs, values=None, shape=None, cols=None, device=0):
+        """The corpus of a list of (row, column, value) pairs, built on the device (rri_corpus_from_pairs, include/
+        rri_corpus_build.h): `pairs` is an (m, 2) integer array -- an estimator's index_pairs, read where it lies when it is
+        C-contiguous int32 or int64 -- or a one-dimensional array of rows with `cols=` for the columns; `values` one number per
+        pair (float32 / float64; others become float64) or None: every pair counts 1, so (document, word) tokens become term
+        counts.  The inputs are numpy arrays, or GPU tensors in the sense of from_device (data_ptr(), dtype, device, numel();
+        torch's device is synchronised first), which are read where they are: the corpus then lives on the tensors' device.  It is
+        the corpus DeviceCorpus makes of the CSR matrix whose row i holds the pairs of row i in the order given: the values of
+        one (i, j) are added in float64 in that order, a sum that is exactly 0 is dropped.  shape=None is allowed for host arrays
+        only: (max row + 1, max column + 1), and (0, 0) for an empty list.  ValueError names the first pair that is out of range or
+        not finite; NotImplementedError 2^31 columns or more."""
+        self = cls.__new__(cls)
+        self._c = C.c_void_p()
+        idt, n_pairs, rp, cp, vp, vdt, stride, on_device, dev, keep_alive = cls._pairs_arguments(pairs, values, cols, device)
+        if shape is None:
+            if on_device:
+                raise ValueError('device tensors need shape=(n_rows, n_cols): the largest index is not looked for on the device')
+            r, c_ = keep_alive[0], keep_alive[1]
+            shape = (int(r.max()) + 1, int(c_.max()) + 1) if r.size else (0, 0)
+        if len(shape) != 2:
+            raise ValueError('shape must be (n_rows, n_cols)')
+        self._lib = _capi.load_library()
+        self.device = int(dev)
+        self.shape = (int(shape[0]), int(shape[1]))
+        with self._handle() as eng:
+            eng._check(self._lib.rri_corpus_from_pairs(eng._h, C.byref(self._c), self.shape[0], self.shape[1], n_pairs, C.c_void_p(rp or None),
+                                                       C.c_void_p(cp or None), idt, stride, C.c_void_p(vp or None), vdt, on_device))
+        del keep_alive
+        self._read_info()
+        return self
+
+    @staticmethod
+    def _pairs_arguments(pairs, values, cols, device):
+        """what rri_corpus_from_pairs is handed: (index dtype code, n_pairs, rows pointer, cols pointer, values pointer, values dtype
+        code, index stride, on_device, device, what must stay alive during the call -- the row and column views first)"""
+        def code(t, table, what):
+            name = str(t.dtype).split('.')[-1]
+            if name not in table:
+                raise TypeError('%s must be %s, not %s' % (what, ' or '.join(sorted(table)), t.dtype))
+            return table[name]
+        on_device = hasattr(pairs, 'data_ptr')
+        if on_device:
+            tensors = [t for t in (pairs, cols, values) if t is not None]
+            if not all(hasattr(t, 'data_ptr') for t in tensors):
+                raise ValueError('pairs, cols and values must all be GPU tensors, or all host arrays')
+            tensors = [t.contiguous() if hasattr(t, 'contiguous') else t for t in tensors]
+            index = {getattr(t.device, 'index', None) for t in tensors}
+            if any(getattr(t.device, 'type', 'cuda') != 'cuda' for t in tensors) or len(index) != 1:
+                raise ValueError('pairs, cols and values must be GPU tensors on one device')
+            dev = index.pop()
+            dev = 0 if dev is None else int(dev)
+            p = tensors[0]
+            idt, isz = code(p, _INDEX_CODES, 'pairs'), 4 if str(p.dtype).split('.')[-1] == 'int32' else 8
+            dims = tuple(getattr(p, 'shape', (int(p.numel()),)))
+            if cols is None:
+                if len(dims) != 2 or int(dims[1]) != 2:
+                    raise ValueError('pairs must be an (m, 2) array of (row, column) indices, or rows with cols=')
+                n_pairs, stride, rp, cp = int(dims[0]), 2, p.data_ptr(), p.data_ptr() + isz
+            else:
+                q = tensors[1]
+                if len(dims) != 1 or code(q, _INDEX_CODES, 'cols') != idt or int(q.numel()) != int(p.numel()):
+                    raise ValueError('rows and cols must be one-dimensional, of one dtype and one length')
+                n_pairs, stride, rp, cp = int(p.numel()), 1, p.data_ptr(), q.data_ptr()
+            v = tensors[-1] if values is not None else None
+            if v is not None and int(v.numel()) != n_pairs:
+                raise ValueError('values must have one entry per pair (%d)' % n_pairs)
+            if type(p).__module__.split('.')[0] == 'torch':
+                import torch
+                torch.cuda.synchronize(dev)
+            return (idt, n_pairs, rp if n_pairs else None, cp if n_pairs else None, v.data_ptr() if v is not None and n_pairs else None,
+                    code(v, _VALUE_CODES, 'values') if v is not None else _capi.RRI_F64, stride, 1, dev, tensors)
+        p = np.asarray(pairs)
+        if p.size and p.dtype.kind not in 'iu':
+            raise ValueError('pairs must be integers, not %s' % p.dtype)
+        if p.dtype.name not in _INDEX_CODES:
+            p = p.astype(np.int64)
+        if cols is None:
+            if p.ndim != 2 or p.shape[1] != 2:
+                raise ValueError('pairs must be an (m, 2) array of (row, column) indices, or rows with cols=')
+            p = np.ascontiguousarray(p)                 # no copy of a C-contiguous int32 / int64 array: read with a stride of 2
+            r, q, stride = p[:, 0], p[:, 1], 2
+        else:
+            q = np.asarray(cols)
+            if q.size and q.dtype.kind not in 'iu':
+                raise ValueError('cols must be integers, not %s' % q.dtype)
+            if p.ndim != 1 or q.ndim != 1 or p.size != q.size:
+                raise ValueError('rows and cols must be one-dimensional and of one length')
+            if q.dtype != p.dtype:                      # one dtype for both: the wider
+                p, q = p.astype(np.int64), q.astype(np.int64)
+            r, q, stride = np.ascontiguousarray(p), np.ascontiguousarray(q), 1
+        n_pairs = int(r.shape[0])
+        v = None
+        if values is not None:
+            v = np.asarray(values).reshape(-1)
+            v = np.ascontiguousarray(v if v.dtype.name in _VALUE_CODES else v.astype(np.float64))
+            if v.size != n_pairs:
+                raise ValueError('values must have one entry per pair (%d)' % n_pairs)
+        return (_INDEX_CODES[r.dtype.name], n_pairs, r.ctypes.data if n_pairs else None, q.ctypes.data if n_pairs else None,
+                v.ctypes.data if v is not None and n_pairs else None, _VALUE_CODES[v.dtype.name] if v is not None else _capi.RRI_F64,
+                stride, 0, int(device), (r, q, v, p))
+
+    def split_entries(self, held_out=0.05, random_state=0):
+        """(observed, held), two corpora on the same device: every entry goes, whole and bit for bit, to `held` with probability
+        floor(held_out 2^32) / 2^32 and to `observed` otherwise (rri_corpus_split_entries) -- the split of observed ratings into a
+        training and a held-out part.  The values may be negative or fractional; the two patterns are disjoint and their union is
+        this corpus's.  The generator is split_counts's (Philox4x32-10 keyed by random_state, counted by (column, row)), so the
+        split depends on (row, column, seed) alone and an entry whose count is 1 goes the same way in both."""
+        thr, seed = self._split_threshold(held_out), self._split_seed(random_state)
+        observed, held = C.c_void_p(), C.c_void_p()
+        with self._handle() as eng:
+            eng._check(self._lib.rri_corpus_split_entries(eng._h, self._ptr(), thr, seed, C.byref(observed), C.byref(held)))
+        return DeviceCorpus._adopt(observed, self.device, self._lib), DeviceCorpus._adopt(held, self.device, self._lib)
 
     def _read_info(self):
         info, ms = (C.c_int64 * _capi.RRI_CORPUS_INFO_FIELDS)(), C.c_double(0.0)

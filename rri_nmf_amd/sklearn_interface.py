@@ -131,7 +131,10 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
         return self
 
     def fit_from_Xtr(self, Xtr):
-        """builds the (index pairs, values) lists from a ratings matrix and fits"""
+        """builds the (index pairs, values) lists from a ratings matrix and fits.  A DeviceCorpus is taken through one
+        to_scipy() download: the weighted fit from a resident corpus is not built."""
+        if isinstance(Xtr, DeviceCorpus):
+            Xtr = Xtr.to_scipy()
         Xtr = Xtr.tocsr() if sp.issparse(Xtr) else sp.csr_matrix(Xtr)
         rows, cols = Xtr.nonzero()
         return self.fit(np.column_stack((rows, cols)), Xtr.data)
@@ -233,7 +236,10 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
         the user has to choose from.  exclude_seen leaves out the pairs given to fit (seen_, the hold-out included); a pair that
         is itself in seen_ is not eligible and gets rank -1 -- it is not taken out of the exclusion silently --, as does a pair
         whose prediction is NaN.  No n x d product is formed, and there is no host route: without a GPU the call raises
-        RRIHipUnavailable."""
+        RRIHipUnavailable.  A DeviceCorpus is taken as its matrix through one to_scipy() download: the weighted fit from a
+        resident corpus is not built, and neither is a ranking that reads one."""
+        if isinstance(X, DeviceCorpus):
+            X = X.to_scipy()
         if np.ndim(self.W) != 2 or np.ndim(self.T) != 2:
             raise ValueError('the estimator is not fitted: it has no W and T')
         if exclude_seen and getattr(self, 'seen_', None) is None:
@@ -277,7 +283,10 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
           mean_percentile_rank   mean over eligible targets with L_u > 1 of r / (L_u - 1)
         and n_items, users (how many were averaged), targets, targets_not_eligible (rank -1: in seen_ under exclude_seen, or a
         NaN prediction).  Without an eligible target the metrics are NaN and the counts say why.  Computed on the host in
-        float64; each rank of a row-sharded fit scores its own rows."""
+        float64; each rank of a row-sharded fit scores its own rows.  A DeviceCorpus is taken as its matrix through one
+        to_scipy() download: the weighted fit from a resident corpus is not built."""
+        if isinstance(X, DeviceCorpus):
+            X = X.to_scipy()
         n_items = int(n_items)
         if n_items < 1:
             raise ValueError('n_items must be a positive integer, not %d' % n_items)
@@ -329,7 +338,10 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
         return self._predict_entries(idx[:, 0], idx[:, 1])
 
     def score(self, X, y=np.array([])):
-        """RMSE of the clipped reconstruction on the given entries (sklearn_interface.py:172-182)"""
+        """RMSE of the clipped reconstruction on the given entries (sklearn_interface.py:172-182).  A DeviceCorpus is taken as its
+        matrix through one to_scipy() download: the weighted fit from a resident corpus is not built."""
+        if isinstance(X, DeviceCorpus):
+            X = X.to_scipy()
         if y.size > 0:
             if sp.issparse(X):
                 X = X.toarray()
@@ -677,3 +689,31 @@ def split_counts(X, held_out=0.5, random_state=0):
     held.eliminate_zeros()
     observed.eliminate_zeros()
     return observed, held
+
+
+def split_entries(X, held_out=0.05, random_state=0):
+    """Split the stored entries of X (n x d, scipy sparse or dense) into (observed, held), two CSR matrices: every entry goes,
+    whole and with its value as it is, to `held` with probability held_out and to `observed` otherwise -- the split of observed
+    ratings into a training and a held-out part.  Values may be negative or fractional; duplicates are summed and explicit zeros
+    dropped first, the patterns of the two parts are disjoint and their union is X's.  ValueError for a held_out outside (0, 1).
+
+    A DeviceCorpus is split where it lives: X.split_entries(held_out, random_state) returns two corpora on its device.  The two
+    routes use different generators -- one uniform draw per stored entry from numpy's RandomState here, a counter-based
+    Philox4x32-10 keyed by (row, column) there --, so the same seed gives a different split on the two routes; both send every
+    entry to `held` independently with the same probability and are equally valid, and each is reproducible from its seed."""
+    if isinstance(X, DeviceCorpus):
+        return X.split_entries(held_out=held_out, random_state=random_state)
+    if not 0.0 < held_out < 1.0:
+        raise ValueError('held_out must lie inside (0, 1), not %r' % (held_out,))
+    A = sp.csr_matrix(X, copy=True)
+    A.sum_duplicates()
+    A.eliminate_zeros()
+    A.sort_indices()
+    rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+    to_held = rs.random_sample(A.nnz) < held_out
+    rows = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
+    parts = []
+    for take in (~to_held, to_held):
+        indptr = np.concatenate(([0], np.cumsum(np.bincount(rows[take], minlength=A.shape[0])))).astype(A.indptr.dtype)
+        parts.append(sp.csr_matrix((A.data[take], A.indices[take], indptr), shape=A.shape))
+    return parts[0], parts[1]
