@@ -169,6 +169,15 @@ CORPUS_BUILD_PROTOTYPES = {
     'rri_corpus_split_entries': (_I32, [_P, _P, C.c_uint32, C.c_uint64, C.POINTER(_P), C.POINTER(_P)]),
 }
 
+# ... and every symbol include/rri_corpus_fit.h declares: the recommender side of the corpus chain.  The upload replaces the store of
+# a pattern-only handle through rri_upload_observed_csr; the other two read and keep nothing of a handle's cached state
+CORPUS_FIT_PROTOTYPES = {
+    'rri_upload_observed_corpus': (_I32, [_P, _P]),
+    'rri_corpus_entries_error': (_I32, [_P, _P, C.POINTER(_I64), _D, _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), C.POINTER(_D),
+                                        C.POINTER(_D)]),
+    'rri_corpus_value_range': (_I32, [_P, _P, C.POINTER(_D)]),
+}
+
 _lib = None
 
 
@@ -229,7 +238,8 @@ def load_library(path=None):
         lib = C.CDLL(p)
     except OSError as e:  # e.g. libamdhip64 missing
         raise RRIHipUnavailable('cannot load %s: %s' % (p, e))
-    for name, (res, args) in list(PROTOTYPES.items()) + list(CORPUS_OPS_PROTOTYPES.items()) + list(CORPUS_BUILD_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(CORPUS_OPS_PROTOTYPES.items()) + list(CORPUS_BUILD_PROTOTYPES.items()) + \
+            list(CORPUS_FIT_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

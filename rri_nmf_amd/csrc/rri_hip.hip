@@ -52,6 +52,8 @@
 #include "rri_derive_kernels.hpp"
 #include "rri_corpus_build.h"
 #include "rri_corpus_build_kernels.hpp"
+#include "rri_corpus_fit.h"
+#include "rri_fiterr_kernels.hpp"
 
 using namespace rri;
 
@@ -222,6 +224,16 @@ struct rri_ctx {
     int uni_req = UNI_REQ_NONE;
     const int* uni_req_rows = nullptr;   // UNI_REQ_ZERO: the rows that take zeros (device, the caller's), and how many
     i64 uni_req_n = 0;
+    // what the next rri_upload_observed_csr takes in place of host arrays (consumed there, the one place that replaces this store):
+    // the canonical arrays of a corpus on this device (rri_upload_observed_corpus, which has checked them and clears the request
+    // on every return path)
+    struct ObsReq {
+        const i64* indptr;
+        const int* indices;
+        const double* values;
+        i64 nnz;
+    };
+    const ObsReq* obs_req = nullptr;
     // dense weighted, one read-modify-write pass per topic step: the column sums a pass leaves for the next T row lack the
     // rank-one term of the W update that follows it; k_wmcorr takes that term from the mask alone (Cpart: its partials)
     double* Cpart = nullptr;
@@ -2981,14 +2993,29 @@ rri_status build_sp_store(rri_ctx* c, const int64_t* indptr, const int32_t* indi
 rri_status rri_upload_observed_csr(rri_ctx* c, const int64_t* indptr, const int32_t* indices, const void* values,
                                    int64_t nnz, int32_t data_dtype) {
     CHECK_CTX(c);
+    // a request of rri_upload_observed_corpus: the canonical arrays of a checked corpus stand in for the host arrays, are copied on
+    // the device and the blocked copies are built there (build_sp_store_device) -- the same bytes either way
+    const rri_ctx::ObsReq* resident = c->obs_req;
+    c->obs_req = nullptr;
+    if (resident) nnz = resident->nnz;
     REFUSE_RO(c, "an observation pattern");
     if (!c->sparse || c->sparse_x) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=RRI_WEIGHTED_SPARSE");
     if (nnz >= 2147483647LL) return fail(c, RRI_ERR_UNSUPPORTED, "more than 2^31-1 observed entries");
     HIPCHK(c, hipSetDevice(c->device));
     CsrDev dv;   // validates the arrays; its device copies of indptr / indices become the CSR copy
-    rri_status s = csr_to_device(c, indptr, indices, values, nnz, data_dtype, dv, CSR_INCREASING);
-    if (s != RRI_OK) return s;
-    s = build_sp_store(c, indptr, indices, nnz, data_dtype, dv, sp_target_items(c->n_cu, false));
+    rri_status s = RRI_OK;
+    if (resident) {
+        // the handle's own copies of the index arrays: the corpus is not kept and may go right after the call
+        HIPCHK(c, dv.indptr.alloc((size_t)(c->n + 1) * sizeof(i64)));
+        HIPCHK(c, dv.indices.alloc((size_t)std::max<i64>(nnz, 1) * sizeof(int)));
+        HIPCHK(c, hipMemcpyAsync(dv.indptr.p, resident->indptr, (size_t)(c->n + 1) * sizeof(i64), hipMemcpyDeviceToDevice, c->stream));
+        if (nnz > 0) HIPCHK(c, hipMemcpyAsync(dv.indices.p, resident->indices, (size_t)nnz * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+        s = build_sp_store_device(c, dv, resident->values, nnz, sp_target_items(c->n_cu, false));
+    } else {
+        s = csr_to_device(c, indptr, indices, values, nnz, data_dtype, dv, CSR_INCREASING);
+        if (s != RRI_OK) return s;
+        s = build_sp_store(c, indptr, indices, nnz, data_dtype, dv, sp_target_items(c->n_cu, false));
+    }
     if (s != RRI_OK) return s;
     HIPCHK(c, dev_alloc(c, c->sp_e, (size_t)std::max<i64>(nnz, 1) * c->es));
     c->have_X = true;
@@ -4805,6 +4832,158 @@ rri_status rri_upload_X_corpus(rri_ctx* c, const rri_corpus* k) {
     // the rest is the CSR upload's own: copies on the device, the store built there, the uniform rows cleared, the cached state reset
     const CorpusArrays resident{k->indptr, k->indices, k->values};
     return upload_X_csr_kept(c, nullptr, nullptr, nullptr, k->nnz, RRI_F64, &resident);
+}
+
+// ---- the recommender side of the corpus chain (include/rri_corpus_fit.h; rri_fiterr.hpp has the semantics, rri_fiterr_kernels.hpp
+// the kernels) -----------------------------------------------------------------------------------------------------------------
+// The pattern and ratings of a pattern-only handle from a corpus.  Everything is checked here, before the handle is touched; the
+// store itself is replaced where it always is: the request left on the handle is served by rri_upload_observed_csr, which also
+// drops what the handle has cached of X and of the pattern.
+rri_status rri_upload_observed_corpus(rri_ctx* c, const rri_corpus* k) {
+    CHECK_CTX(c);
+    REFUSE_RO(c, "an observation pattern from a corpus");
+    if (!c->sparse || c->sparse_x) return fail(c, RRI_ERR_INVALID, "handle was not created with weighted=RRI_WEIGHTED_SPARSE");
+    const bool alive = corpus_alive(k);
+    char why[200] = "";
+    const int bad = spbuild_check_corpus(alive, alive ? k->n_rows : 0, alive ? k->n_cols : 0, alive ? k->nnz : 0, alive ? k->device : 0, c->n,
+                                         c->d, c->device, why, sizeof why);
+    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+    const rri_ctx::ObsReq req{k->indptr, k->indices, k->values, k->nnz};
+    c->obs_req = &req;
+    const rri_status s = rri_upload_observed_csr(c, nullptr, nullptr, nullptr, k->nnz, RRI_F64);
+    c->obs_req = nullptr;       // (served and cleared there already: no return path leaves a pointer to this frame)
+    return s;
+}
+
+namespace {
+// the two launches of a chunk: the partials of its pieces (and the predictions, when asked for), and their sums per request
+hipError_t fiterr_chunk(rri_ctx* c, const double* Tt, const i64* rows, i64 q0, i64 nreq, const LoglikPiece* pieces, i64 npieces,
+                        const i64* first, const int* indices, const double* values, double lo, double hi, double* pred, double* psq,
+                        double* pabs, double* sq, double* ab) {
+    const size_t lds = 4 * (size_t)loglik_kp(c->k) * sizeof(double);
+    const dim3 grid((unsigned)((npieces + 3) / 4));
+    auto entries = [&](auto lanes) {
+        hipLaunchKernelGGL(k_fiterr_entries<decltype(lanes)::value>, grid, dim3(256), lds, c->stream, (const double*)c->W, c->ldw, Tt,
+                           c->k, rows, q0, pieces, npieces, indices, values, lo, hi, pred, psq, pabs);
+    };
+    switch (loglik_lanes(c->k)) {
+        case 4: entries(std::integral_constant<int, 4>()); break;
+        case 16: entries(std::integral_constant<int, 16>()); break;
+        default: entries(std::integral_constant<int, 64>()); break;      // a measurement build (-DRRI_LOGLIK_LANES=64) only
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_fiterr_sum, dim3((unsigned)((nreq + 255) / 256)), dim3(256), 0, c->stream, first, nreq, (const double*)psq,
+                       (const double*)pabs, sq, ab);
+    return hipGetLastError();
+}
+}  // namespace
+
+// Reads the handle's W and T; the transposed copy of T, the row list, a chunk's pieces, their partials, its predictions and its
+// sums live in temporaries of the call, so no sum a later sweep reads is touched and rri_device_memory reports what it reported
+// before.  The corpus's indices and values are read where they lie.  The request is checked before any HIP call.
+rri_status rri_corpus_entries_error(rri_ctx* c, const rri_corpus* k, const int64_t* rows, double clip_lo, double clip_hi,
+                                    double* sq_out, double* abs_out, double* pred_out, double totals[3], double* kernel_ms) {
+    CHECK_CORPUS(c, k);
+    char why[200] = "";
+    const int bad = fiterr_check_request(c->n, c->d, k->n_rows, k->n_cols, rows, clip_lo, clip_hi, why, sizeof why);
+    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+    const i64 count = k->n_rows;
+    const int64_t* indptr = k->h_indptr.data();
+    if (sq_out) std::fill(sq_out, sq_out + count, 0.0);
+    if (abs_out) std::fill(abs_out, abs_out + count, 0.0);
+    if (totals) totals[0] = totals[1] = totals[2] = 0.0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (count == 0 || k->nnz == 0) return RRI_OK;
+    if (!c->have_W || !c->have_T) return fail(c, RRI_ERR_INVALID, "W and T must be set first");
+    std::vector<LoglikChunk> chunks;
+    loglik_cut_chunks(indptr, count, LL_UPLOAD_BUDGET, &chunks);
+    i64 req_max = 0, ent_max = 0, pc_max = 0;
+    for (const LoglikChunk& ch : chunks) {
+        req_max = std::max<i64>(req_max, ch.q1 - ch.q0);
+        ent_max = std::max<i64>(ent_max, indptr[ch.q1] - indptr[ch.q0]);
+        pc_max = std::max<i64>(pc_max, loglik_cut_pieces(indptr, ch.q0, ch.q1, nullptr, nullptr));
+    }
+    if (req_max > 0x7fffffffLL) return fail(c, RRI_ERR_INVALID, "%lld requests are too many for one call", (long long)count);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int kp = loglik_kp(c->k);
+    DevTmp tTt, trows, tpc, tfirst, tpred, tps, tpa, tsq, tab;
+    HIPCHK(c, tTt.alloc((size_t)c->d * kp * sizeof(double)));
+    if (rows) HIPCHK(c, trows.alloc((size_t)req_max * sizeof(i64)));
+    HIPCHK(c, tpc.alloc((size_t)pc_max * sizeof(LoglikPiece)));
+    HIPCHK(c, tfirst.alloc((size_t)(req_max + 1) * sizeof(i64)));
+    if (pred_out) HIPCHK(c, tpred.alloc((size_t)ent_max * sizeof(double)));
+    HIPCHK(c, tps.alloc((size_t)pc_max * sizeof(double)));
+    HIPCHK(c, tpa.alloc((size_t)pc_max * sizeof(double)));
+    HIPCHK(c, tsq.alloc((size_t)req_max * sizeof(double)));
+    HIPCHK(c, tab.alloc((size_t)req_max * sizeof(double)));
+    EventPair ev;
+    HIPCHK(c, ev.create());
+    std::vector<double> h_sq((size_t)count, 0.0), h_ab((size_t)count, 0.0);
+    double ms = 0.0;
+    auto timed = [&]() {      // after a synchronise: the kernels between the two records
+        float t = 0.0f;
+        if (hipEventElapsedTime(&t, ev.a, ev.b) == hipSuccess) ms += t;
+    };
+    hipError_t e = hipEventRecord(ev.a, c->stream);
+    if (e == hipSuccess) e = LK::loglik_transpose(c, (double*)tTt.p);
+    if (e == hipSuccess) e = hipEventRecord(ev.b, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) timed();
+    std::vector<LoglikPiece> pieces((size_t)pc_max);
+    std::vector<int64_t> first((size_t)req_max + 1);
+    for (size_t i = 0; i < chunks.size() && e == hipSuccess; ++i) {
+        const i64 q0 = chunks[i].q0, nreq = chunks[i].q1 - q0, e0 = indptr[q0], nent = indptr[chunks[i].q1] - e0;
+        if (nent == 0) continue;                                // only requests without entries: their outputs are 0 already
+        const i64 npieces = loglik_cut_pieces(indptr, q0, chunks[i].q1, pieces.data(), first.data());
+        if (rows) e = hipMemcpyAsync(trows.p, rows + q0, (size_t)nreq * sizeof(i64), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(tpc.p, pieces.data(), (size_t)npieces * sizeof(LoglikPiece), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(tfirst.p, first.data(), (size_t)(nreq + 1) * sizeof(i64), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipEventRecord(ev.a, c->stream);
+        if (e == hipSuccess)
+            e = fiterr_chunk(c, (const double*)tTt.p, (const i64*)trows.p, q0, nreq, (const LoglikPiece*)tpc.p, npieces, (const i64*)tfirst.p,
+                             k->indices + e0, k->values + e0, clip_lo, clip_hi, (double*)tpred.p, (double*)tps.p, (double*)tpa.p,
+                             (double*)tsq.p, (double*)tab.p);
+        if (e == hipSuccess) e = hipEventRecord(ev.b, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_sq.data() + q0, tsq.p, (size_t)nreq * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_ab.data() + q0, tab.p, (size_t)nreq * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && pred_out) e = hipMemcpyAsync(pred_out + e0, tpred.p, (size_t)nent * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        // the pieces (host memory that the next chunk rewrites) have been read, and the temporaries are free for the next chunk
+        const hipError_t es = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = es;
+        if (e == hipSuccess) timed();
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "entries error failed: %s", hipGetErrorString(e));
+    double tot_sq = 0.0, tot_ab = 0.0;
+    for (i64 q = 0; q < count; ++q) {
+        tot_sq += h_sq[(size_t)q];
+        tot_ab += h_ab[(size_t)q];
+    }
+    if (sq_out) std::copy(h_sq.begin(), h_sq.end(), sq_out);
+    if (abs_out) std::copy(h_ab.begin(), h_ab.end(), abs_out);
+    if (totals) { totals[0] = tot_sq; totals[1] = tot_ab; totals[2] = (double)k->nnz; }
+    if (kernel_ms) *kernel_ms = ms;
+    return RRI_OK;
+}
+
+rri_status rri_corpus_value_range(rri_ctx* c, const rri_corpus* k, double out[2]) {
+    CHECK_CORPUS(c, k);
+    if (!out) return fail(c, RRI_ERR_INVALID, "out is NULL");
+    if (k->nnz == 0) return fail(c, RRI_ERR_INVALID, "the corpus is empty: it has no value range");
+    HIPCHK(c, hipSetDevice(c->device));
+    const unsigned nb = (unsigned)std::min<i64>(1024, (k->nnz + 255) / 256);
+    DevTmp part;
+    HIPCHK(c, part.alloc((size_t)(nb + 1) * 2 * sizeof(double)));
+    double* p = (double*)part.p;
+    hipLaunchKernelGGL(k_value_range, dim3(nb), dim3(256), 0, c->stream, (const double*)k->values, (const double*)k->values, (i64)1, k->nnz, p);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_value_range, dim3(1), dim3(256), 0, c->stream, (const double*)p, (const double*)(p + 1), (i64)2, (i64)nb, p + 2 * (size_t)nb);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, p + 2 * (size_t)nb, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RRI_OK;
 }
 
 rri_status rri_sparse_store_get(rri_ctx* c, int32_t which, int64_t* info, int32_t n_info, int64_t* segptr, uint16_t* idx, int32_t* perm,

@@ -166,7 +166,9 @@ class DeviceCorpus(object):
     max_words) and split_counts(held_out, random_state) (include/rri_corpus_ops.h).  The two ends of that chain are on the device as
     well (include/rri_corpus_build.h): from_pairs(pairs, values) makes a corpus of (row, column, value) triples -- tokens, or a
     ratings log -- without a CSR matrix on the host, and split_entries(held_out, random_state) sends every entry, whole, to a
-    training or a held-out corpus."""
+    training or a held-out corpus.  value_range() is the (min, max) of the values, and the recommender fit takes a corpus where
+    it lies (include/rri_corpus_fit.h; corpus_fit.upload_observed_corpus, corpus_fit.entries_error, nmf(corpus, k,
+    observed_only=True), NMF_RS_Estimator.fit_corpus)."""
 
     def __init__(self, X, device=0):
         import scipy.sparse as sp
@@ -542,6 +544,14 @@ class DeviceCorpus(object):
             eng._check(self._lib.rri_corpus_get(eng._h, self._ptr(), indptr.ctypes.data_as(C.POINTER(C.c_int64)),
                                                 indices.ctypes.data_as(C.POINTER(C.c_int32)), values.ctypes.data_as(C.POINTER(C.c_double))))
         return sp.csr_matrix((values, indices, indptr), shape=self.shape)
+
+    def value_range(self):
+        """(min, max) of the canonical values, reduced on the device (rri_corpus_value_range, include/rri_corpus_fit.h): the rating
+        range of a ratings corpus, without a download.  ValueError for an empty corpus."""
+        out = (C.c_double * 2)()
+        with self._handle() as eng:
+            eng._check(self._lib.rri_corpus_value_range(eng._h, self._ptr(), out))
+        return float(out[0]), float(out[1])
 
     def close(self):
         if getattr(self, '_c', None) is not None and self._c:

@@ -44,6 +44,15 @@ additions select the device side:
             ResidentProblem is kept.  The call must end on a CSR handle (sparse_X=True, or the automatic CSR route); no W_mat,
             w_row, group=, schedule='residual', float16 / uint8 storage or host callbacks.  None / False (default): such a
             matrix is preprocessed on the host, as before.
+    observed_only  True, with a DeviceCorpus X: the weighted flavour whose W_mat is the pattern of the corpus -- its stored
+            entries are the observed ratings.  The pattern-only handle is filled from the corpus on the device
+            (corpus_fit.upload_observed_corpus), no host copy of X exists, the default start runs through the handle's products
+            and rtv['obj_calculator'] re-evaluates on the corpus (while it is open).  No W_mat, preprocess, uniform_rows, frozen,
+            resident, w_row, group=, schedule='residual', float16 / uint8 storage, diagnostics, store_gradients, Gaussian
+            mechanism or host early_stop function.
+    An early_stop callable may carry `device_corpus = (held_corpus, lo, hi)`, a resident held-out DeviceCorpus of X's shape: it
+    is then scored between sweeps on the device where it lies (corpus_fit.entries_error: the clipped RMSE), like one that
+    carries `device_entries` but without its upload per sweep; on any X, not with group=.
 
 What runs where
     host (numpy, once):   argument checks, warnings and sentinel returns (nmf.py:280-315), the
@@ -58,6 +67,7 @@ import time
 import numpy as np
 import scipy.sparse
 
+from .corpus_fit import entries_error, upload_observed_corpus
 from .engine import DeviceCorpus, FrozenRows, RRIEngine, ZeroTotalRows
 from .initialization import _KNOWN as _KNOWN_INITS, initialize_nmf
 from .matrixops import normalize, proj_mat_to_simplex
@@ -78,7 +88,7 @@ class TrueObjComputer(object):
     objective value; true_objective() re-evaluates it on the device."""
 
     def __init__(self, X, W, T, reg_w_l2, reg_t_l2, reg_w_l1, reg_t_l1, Wm, wr, dtype=None, device=0,
-                 sparse_pattern=None, preprocess=None, group=None, sparse_X=None):
+                 sparse_pattern=None, preprocess=None, group=None, sparse_X=None, observed_only=False):
         self.X, self.W, self.T = X, W, T
         self.reg_w_l2, self.reg_t_l2 = reg_w_l2, reg_t_l2
         self.reg_w_l1, self.reg_t_l1 = reg_w_l1, reg_t_l1
@@ -88,6 +98,7 @@ class TrueObjComputer(object):
         self._preprocess = preprocess      # device-side tf-idf / normalisation that nmf() applied to X (idf resolved)
         self._group = group                # row-sharded: true_objective() is then a collective call
         self._sparse_X = sparse_X          # X kept as CSR on the device (nmf's sparse_X)
+        self._observed_only = observed_only    # X a DeviceCorpus whose pattern is W_mat (nmf's observed_only)
 
     def true_objective(self):
         X = self.X   # row weights, when used, are already folded into X by nmf() (nmf.py:335-338)
@@ -95,7 +106,7 @@ class TrueObjComputer(object):
         k = self.W.shape[1]
         sdt = _storage_dtype(X, self._dtype) if self._preprocess is None else np.dtype(self._dtype or np.float64)
         with _engine_with_problem(X, self.Wm, k, sdt, self._device, self._sparse_pattern,
-                                  sparse_X=self._sparse_X) as eng:
+                                  sparse_X=self._sparse_X, observed_only=self._observed_only) as eng:
             if self._preprocess is not None:
                 eng.preprocess(**self._preprocess)
             if self._group is not None:
@@ -208,12 +219,21 @@ def _route_of_call(X, spec, sparse_X=None, dtype=None, device=0, W_mat=None, w_r
     return route, csr
 
 
-def _engine_with_problem(X, W_mat, k, sdt, device, sparse_pattern=None, schedule='gram', sparse_X=None):
+def _engine_with_problem(X, W_mat, k, sdt, device, sparse_pattern=None, schedule='gram', sparse_X=None, observed_only=False):
     """Engine with X and the weights on the device.  scipy sparse X / 0-1 sparse W_mat go up as CSR: onto a
     pattern-only handle (no dense n x d array at all) when X lives on the pattern and the pattern is sparse enough
     -- `sparse_pattern` True / False forces the choice --, else densified / bit-packed on the device (SURVEY.md 8f
     rank 3); dense inputs as they are.  Without weights, sparse_x_route decides whether X stays CSR on the device."""
     n, d = X.shape
+    if isinstance(X, DeviceCorpus) and observed_only:
+        # the corpus's stored entries are the observed ones: a pattern-only handle, its store copied and built on the device
+        eng = RRIEngine(n, d, k, dtype=sdt, weighted='sparse', device=device)
+        try:
+            upload_observed_corpus(eng, X)
+        except Exception:
+            eng.close()
+            raise
+        return eng
     if isinstance(X, DeviceCorpus):
         # the canonical arrays are on the device: the handle copies them there and builds its blocked store there
         eng = RRIEngine(n, d, k, dtype=sdt, device=device, sparse_x=True)
@@ -502,13 +522,75 @@ def _compute_update_T(X, W, T, t, store_gradients=False, ind_rows_to_store=None,
     return wR, nw, wR_store, nw_store
 
 
+def _host_stop(early_stop):
+    """an early_stop callable that wants W, T on the host: it carries neither `device_entries` (host lists, scored by
+    rri_masked_rmse) nor `device_corpus` (a resident held-out corpus, scored by rri_corpus_entries_error)"""
+    return callable(early_stop) and getattr(early_stop, 'device_entries', None) is None \
+        and getattr(early_stop, 'device_corpus', None) is None
+
+
+def _check_device_corpus_stop(early_stop, shape, device, group):
+    """an early_stop callable that carries device_corpus = (held_corpus, lo, hi): the held-out corpus must be an open, non-empty
+    DeviceCorpus of the problem's shape on the call's device; checked before any device call.  The score is not collective"""
+    spec = getattr(early_stop, 'device_corpus', None) if callable(early_stop) else None
+    if spec is None:
+        return None
+    if group is not None:
+        raise NotImplementedError('an early_stop function with device_corpus is scored by a call that is not collective: with '
+                                  'group= pass device_entries, which rri_masked_rmse scores over all ranks')
+    try:
+        held, lo, hi = spec
+    except (TypeError, ValueError):
+        raise ValueError('early_stop.device_corpus must be (held_corpus, lo, hi)')
+    if not isinstance(held, DeviceCorpus):
+        raise ValueError('early_stop.device_corpus must be (held_corpus, lo, hi) with a DeviceCorpus, not %s' % type(held).__name__)
+    if tuple(held.shape) != tuple(shape):
+        raise ValueError('the held-out corpus is %d x %d, the problem %s' % (held.shape[0], held.shape[1], ' x '.join(str(s) for s in shape)))
+    if int(held.device) != int(device):
+        raise ValueError('the held-out corpus lives on device %d, the call asks for device %d' % (held.device, device))
+    held._ptr()     # a closed corpus: ValueError
+    if held.nnz == 0:
+        raise ValueError('the held-out corpus is empty: there is nothing to score')
+    return held, lo, hi
+
+
+def _check_observed_only_call(X, sparse_X, sparse_pattern, W_mat, preprocess, uniform_rows, frozen, resident, w_row, group, schedule,
+                              dtype, diagnostics, store_gradients, early_stop, gaussian, init, needs_init, device):
+    """nmf(corpus, k, observed_only=True): the weighted flavour whose W_mat is the pattern of a DeviceCorpus, on a pattern-only
+    handle filled from the corpus.  Nothing of X ever visits the host, so whatever needs it there, or another store, is refused
+    before any device call"""
+    if not isinstance(X, DeviceCorpus):
+        raise ValueError('observed_only=True takes a DeviceCorpus X: its stored entries are the observed ones (for host matrices '
+                         'pass W_mat, the pattern, with sparse_pattern=True)')
+    refused = [name for name, on in (('W_mat', W_mat is not None), ('preprocess', preprocess is not None),
+                                     ('uniform_rows=True', bool(uniform_rows)), ('frozen=', frozen is not None),
+                                     ('resident=', resident is not None), ('w_row', w_row is not None), ('group=', group is not None),
+                                     ("schedule='residual'", schedule == 'residual'),
+                                     ('dtype=float16', dtype is not None and np.dtype(dtype) == np.float16),
+                                     ('dtype=uint8', dtype is not None and np.dtype(dtype) == np.uint8),
+                                     ('sparse_X', sparse_X is not None), ('sparse_pattern=False', sparse_pattern is False),
+                                     ('diagnostics', bool(diagnostics)), ('store_gradients', bool(store_gradients)),
+                                     ('an early_stop function without device_entries', _host_stop(early_stop)),
+                                     ('the Gaussian mechanism', bool(gaussian)))
+               if on]
+    if refused:
+        raise ValueError('observed_only=True keeps the ratings of a DeviceCorpus on a pattern-only handle on one device and never '
+                         'brings them to the host; it does not combine with %s' % ', '.join(refused))
+    if needs_init and init not in _KNOWN_INITS:
+        raise NotImplementedError('init=%r needs X on the host: a DeviceCorpus X is initialised through the device products '
+                                  '(one of %r), or pass W_in and T_in' % (init, _KNOWN_INITS[1:]))
+    if int(X.device) != int(device):
+        raise ValueError('the corpus lives on device %d, the call asks for device %d' % (X.device, device))
+    X._ptr()        # a closed corpus: ValueError
+
+
 def _check_corpus_call(X, sparse_X, W_mat, w_row, group, schedule, dtype, diagnostics, store_gradients, early_stop, gaussian,
                        init, needs_init, device):
     """nmf() with a DeviceCorpus as X: the corpus is kept as CSR on its device and nothing of it ever visits the host, so
     whatever needs X there, or another store, is refused before any device call"""
     if sparse_X is not None and not sparse_X:
         raise ValueError('a DeviceCorpus X stays CSR on the device (sparse_X=True is implied): sparse_X=False would densify it')
-    host_stop = callable(early_stop) and getattr(early_stop, 'device_entries', None) is None
+    host_stop = _host_stop(early_stop)
     refused = [name for name, on in (('W_mat', W_mat is not None), ('w_row', w_row is not None), ('group=', group is not None),
                                      ("schedule='residual'", schedule == 'residual'),
                                      ('dtype=float16', dtype is not None and np.dtype(dtype) == np.float16),
@@ -544,7 +626,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         diagnostics=[], store_gradients=False,
         ind_rows_to_store=None, eps_gauss_t=None, delta_gauss_t=None,
         *, dtype=None, device=0, device_init=None, sparse_pattern=None, preprocess=None, schedule='gram', group=None,
-        resident=None, frozen=None, sparse_X=None, uniform_rows=None):
+        resident=None, frozen=None, sparse_X=None, uniform_rows=None, observed_only=False):
     """Non-negative factorisation X ~ W T by rank-one residue iteration; see the module docstring and
     the reference's docstring (nmf.py:109-269) for the parameters.  Returns a dict with 'W', 'T',
     'iter_cputime' (wall seconds since the start, per sweep), 'random_state' and, when the objective
@@ -568,10 +650,15 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     batch is absorbed all the same (the first batch of an online fit).  Unweighted calls in the Gram form with float32 /
     float64 or CSR storage on one device; no fix_W, w_row, early_stop, store_gradients or Gaussian mechanism."""
     corpus = isinstance(X, DeviceCorpus)
-    if corpus:
+    if observed_only:
+        _check_observed_only_call(X, sparse_X, sparse_pattern, W_mat, preprocess, uniform_rows, frozen, resident, w_row, group,
+                                  schedule, dtype, diagnostics, store_gradients, early_stop, eps_gauss_t and delta_gauss_t, init,
+                                  _is_empty(W_in) or _is_empty(T_in), device)
+    elif corpus:
         _check_corpus_call(X, sparse_X, W_mat, w_row, group, schedule, dtype, diagnostics, store_gradients, early_stop,
                            eps_gauss_t and delta_gauss_t, init, _is_empty(W_in) or _is_empty(T_in), device)
         sparse_X = True
+    stop_corpus = _check_device_corpus_stop(early_stop, X.shape if corpus else np.shape(X), device, group)
     if frozen is not None:
         if frozen is not True and not isinstance(frozen, FrozenRows):
             raise ValueError('frozen must be a FrozenRows, True (absorb this batch, nothing frozen yet) or None')
@@ -595,8 +682,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         raise ValueError('uniform_rows must be True, False or None')
     if uniform_rows:
         # uniform rows live on the handle that keeps X as CSR, and nothing on the host ever sees the preprocessed X
-        host_side = bool(diagnostics) or bool(store_gradients) or \
-            (callable(early_stop) and getattr(early_stop, 'device_entries', None) is None)
+        host_side = bool(diagnostics) or bool(store_gradients) or _host_stop(early_stop)
         refused = [name for name, on in (('W_mat', W_mat is not None), ('w_row', w_row is not None),
                                          ('group=', group is not None), ("schedule='residual'", schedule == 'residual'),
                                          ('dtype=float16', dtype is not None and np.dtype(dtype) == np.float16),
@@ -652,7 +738,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         # an early_stop callback that carries `device_entries` (what NMF_RS_Estimator.fit installs: the clipped RMSE on its
         # held-out entries, sklearn_interface.py:71-93) is scored by the library over ALL ranks' entries, so every rank takes
         # the same decision (nmf.py:381-407); a callback that wants W, T on the host would see one rank's rows
-        host_stop = callable(early_stop) and getattr(early_stop, 'device_entries', None) is None
+        host_stop = _host_stop(early_stop)
         # (round 4: per-row weights -- row-local, their refit a fold-in under the same group -- and the device-side tf-idf /
         # normalisation -- document frequencies all-reduced -- run sharded)
         if store_gradients or (eps_gauss_t and delta_gauss_t) or host_stop:
@@ -685,8 +771,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     spec = _preprocess_spec(preprocess)
     device_spec, csr_route = None, None
     if spec is not None:
-        host_callbacks = bool(diagnostics) or bool(store_gradients) or \
-            (callable(early_stop) and getattr(early_stop, 'device_entries', None) is None)
+        host_callbacks = bool(diagnostics) or bool(store_gradients) or _host_stop(early_stop)
         # (float16 storage: tf-idf and normalisation in float64 on the host, so that X is rounded once, at upload -- the device
         # route would round the raw X and then rewrite it)
         # (a corpus: always the device; a row that normalisation would make dense shows there, and is refused below)
@@ -788,7 +873,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             resident.close()
         # (with device preprocessing the question whether X stays CSR was answered for the route: the same answer here)
         eng = _engine_with_problem(X, W_mat, k, sdt, device, sparse_pattern, schedule,
-                                   sparse_X if device_spec is None or csr_route is None else csr_route)
+                                   sparse_X if device_spec is None or csr_route is None else csr_route, observed_only=observed_only)
     keep_handle = False
     try:
         if group is not None:
@@ -914,7 +999,9 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
             if early_stop:                       # nmf.py:381-407
                 if callable(early_stop):
                     entries = getattr(early_stop, 'device_entries', None)
-                    if entries is not None:   # clipped RMSE on listed entries: evaluated on the device
+                    if stop_corpus is not None:     # clipped RMSE on a resident held-out corpus: nothing is uploaded
+                        this_score = entries_error(eng, stop_corpus[0], clip=stop_corpus[1:])['rmse']
+                    elif entries is not None:   # clipped RMSE on listed entries: evaluated on the device
                         this_score = eng.masked_rmse(*entries)
                     else:
                         Wh, Th = current()
@@ -1014,7 +1101,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         rtv['obj_history'] = obj_history
         calc = TrueObjComputer(X, W, T, reg_w_l2, reg_t_l2, reg_w_l1, reg_t_l1, W_mat, w_row,
                                dtype=dtype, device=device, sparse_pattern=sparse_pattern, preprocess=device_spec, group=group,
-                               sparse_X=sparse_X)
+                               sparse_X=sparse_X, observed_only=observed_only)
         calc.obj = obj_history[-1] if obj_history else np.inf
         rtv['obj_calculator'] = calc
     rtv['iter_cputime'] = iter_cputime

@@ -139,6 +139,79 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
         rows, cols = Xtr.nonzero()
         return self.fit(np.column_stack((rows, cols)), Xtr.data)
 
+    def fit_corpus(self, train, held=None, keep_seen=True):
+        """The fit of `fit` from ratings that are resident: `train` is a DeviceCorpus (DeviceCorpus.from_pairs(index_pairs,
+        ratings), or the observed half of its split_entries), and nothing of its size visits the host -- no train_test_split, no
+        CSR matrix built on the host, no upload.  The solver runs nmf(train, k, observed_only=True, ...) with the options of `fit`:
+        the weighted flavour on a pattern-only handle whose store is built on the device from the corpus.  `held` is a DeviceCorpus
+        of held-out ratings for the early stop (scored between sweeps by rri_corpus_entries_error where it lies); with
+        use_validation_early_stopping and no `held`, train.split_entries(held_out=0.05, random_state=0) is made, used and closed
+        here (the hold-out is then another 5 % than train_test_split's: the same estimator, another draw).  The rating range that
+        clips predictions is that of train and held together (DeviceCorpus.value_range).  keep_seen=True downloads the pattern of
+        train and held once, after the fit, into seen_ (indptr and indices only) for recommend / rank; keep_seen=False leaves seen_
+        None, and recommend(exclude_seen=True) raises.  The default start runs through the handle's products whatever the size
+        (fit takes scikit-learn's SVD below 2e7 entries unless nmf_kwargs has device_init=True)."""
+        from .corpus_fit import pattern_of
+        if not isinstance(train, DeviceCorpus) or (held is not None and not isinstance(held, DeviceCorpus)):
+            raise TypeError('fit_corpus takes DeviceCorpus objects: for matrices and pairs there are fit_from_Xtr and fit')
+        if tuple(train.shape) != (self.n, self.d) or (held is not None and tuple(held.shape) != (self.n, self.d)):
+            raise ValueError('the corpora must be %d x %d' % (self.n, self.d))
+        ranges = [c.value_range() for c in (train, held) if c is not None and c.nnz > 0]
+        if not ranges:
+            raise ValueError('there are no ratings to fit')
+        self.min_rating, self.max_rating = min(r[0] for r in ranges), max(r[1] for r in ranges)
+        own = ()
+        fit_on, stop_on = train, held
+        try:
+            if self.use_validation_early_stopping and held is None:
+                own = train.split_entries(held_out=0.05, random_state=0)
+                fit_on, stop_on = own
+            if self.use_validation_early_stopping:
+                def RMSE_val(X_ignored, W, T):
+                    raise NotImplementedError('this early stop is scored on the device (device_corpus)')
+
+                RMSE_val.device_corpus = (stop_on, self.min_rating, self.max_rating)
+                self.early_stop = RMSE_val
+            else:
+                self.early_stop = False
+            W_in, T_in = self._warm_start()
+            soln = _nmf(fit_on, self.k, max_iter=self.max_iter, max_time=7200, compute_obj_each_iter=True,
+                        reset_topic_method=None, early_stop=self.early_stop, project_T_each_iter=False,
+                        t_row_sum=1.0, project_W_each_iter=False, w_row_sum=None,
+                        observed_only=True, W_in=W_in, T_in=T_in, reg_w_l1=self.wr1,
+                        reg_t_l1=self.tr1, random_state=self.random_state, **self.nmf_kwargs)
+        finally:
+            for c in own:
+                c.close()
+        self._keep(soln)     # (nmf_outputs['obj_calculator'] re-evaluates on the corpus it was given, while that one is open)
+        self.seen_ = None
+        if keep_seen:
+            seen = pattern_of(train)
+            if held is not None and held.nnz > 0:
+                seen = (seen + pattern_of(held)).tocsr()
+                seen.sum_duplicates()
+                seen.sort_indices()
+                seen.data[:] = 1.0
+            self.seen_ = seen
+        return self
+
+    def score_corpus(self, corpus):
+        """RMSE of the clipped reconstruction on the stored entries of a DeviceCorpus, scored on the device where the corpus lies
+        (rri_corpus_entries_error on a factors-only handle): what score(corpus.to_scipy()) returns, to rounding, without the
+        download."""
+        from .corpus_fit import entries_error
+        if np.ndim(self.W) != 2 or np.ndim(self.T) != 2:
+            raise ValueError('the estimator is not fitted: it has no W and T')
+        W = self.W.toarray() if sp.issparse(self.W) else np.asarray(self.W)
+        T = self.T.toarray() if sp.issparse(self.T) else np.asarray(self.T)
+        eng = RRIEngine(W.shape[0], T.shape[1], W.shape[1], dtype=np.float64, weighted=False, device=self.nmf_kwargs.get('device', 0))
+        try:        # factors only: such a handle holds nothing of size n x d
+            eng.set_W(W)
+            eng.set_T(T)
+            return entries_error(eng, corpus, clip=(self.min_rating, self.max_rating))['rmse']
+        finally:
+            eng.close()
+
     def transform(self, Xnew):
         """fold new rows in against the fitted T"""
         soln = _nmf(Xnew, self.k, max_iter=4, max_time=7200, project_W_each_iter=False,
@@ -236,8 +309,8 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
         the user has to choose from.  exclude_seen leaves out the pairs given to fit (seen_, the hold-out included); a pair that
         is itself in seen_ is not eligible and gets rank -1 -- it is not taken out of the exclusion silently --, as does a pair
         whose prediction is NaN.  No n x d product is formed, and there is no host route: without a GPU the call raises
-        RRIHipUnavailable.  A DeviceCorpus is taken as its matrix through one to_scipy() download: the weighted fit from a
-        resident corpus is not built, and neither is a ranking that reads one."""
+        RRIHipUnavailable.  A DeviceCorpus is taken as its matrix through one to_scipy() download: a ranking that reads a
+        resident corpus is not built (the fit and the score are: fit_corpus, score_corpus)."""
         if isinstance(X, DeviceCorpus):
             X = X.to_scipy()
         if np.ndim(self.W) != 2 or np.ndim(self.T) != 2:
@@ -284,7 +357,7 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
         and n_items, users (how many were averaged), targets, targets_not_eligible (rank -1: in seen_ under exclude_seen, or a
         NaN prediction).  Without an eligible target the metrics are NaN and the counts say why.  Computed on the host in
         float64; each rank of a row-sharded fit scores its own rows.  A DeviceCorpus is taken as its matrix through one
-        to_scipy() download: the weighted fit from a resident corpus is not built."""
+        to_scipy() download: a ranking that reads a resident corpus is not built."""
         if isinstance(X, DeviceCorpus):
             X = X.to_scipy()
         n_items = int(n_items)
