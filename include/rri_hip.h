@@ -624,8 +624,11 @@ rri_status rri_onchip_info(rri_ctx* ctx, int32_t* eligible, int64_t* launches);
  *          of X inside the window and outside the book (the exception entries of a 26-bit copy) as the last build counted them,
  *          -1 where none was counted
  *   26     the handle, with the parameters it has now, takes the early-sums schedule (RRI_EARLY_SUMS: the W-sized sums of a topic
- *          step ride in the grid of its pass) wherever a step's early partials are valid;   27  W-column steps that took it so far */
-#define RRI_LAYOUT_FIELDS 28
+ *          step ride in the grid of its pass) wherever a step's early partials are valid;   27  W-column steps that took it so far
+ *   28     the workgroups of that job are dealt through the pass's grid behind its first round (RRI_EARLY_DEAL=1), not placed
+ *          there in one run (unset or 0);   29  the pass's own workgroups between two of the job (0: one run -- the switch is off,
+ *          or the pass has fewer workgroups behind its first round than the job) */
+#define RRI_LAYOUT_FIELDS 30
 rri_status rri_layout_info(rri_ctx* ctx, int64_t* out, int32_t n);
 /* The exchanges of that launch poll a bounded number of times.  When its workgroups cannot all run at once (a device shared
  * with another process, CUs masked away) the launch gives up, and the call does what the reference's sweep does under any

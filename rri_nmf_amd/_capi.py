@@ -11,7 +11,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RRI_HIP_LIB', os.path.join(_PKG, 'lib', 'librri_hip.so'))
 
 RRI_GRAM_SLICES = 8     # include/rri_hip.h
-RRI_LAYOUT_FIELDS = 28  # include/rri_hip.h
+RRI_LAYOUT_FIELDS = 30  # include/rri_hip.h
 RRI_MAX_K = 1024        # include/rri_hip.h: rri_create refuses a larger k (RRI_ERR_UNSUPPORTED)
 RRI_MAX_TOPN = 64       # include/rri_hip.h: the longest list rri_topn_rows returns per row
 RRI_MAX_COOC_WORDS = 32     # include/rri_hip.h: the most words per group rri_cooccurrence_counts takes

@@ -68,6 +68,16 @@ __device__ __forceinline__ double ordered_sum_acc(double a0, const double* __res
     return a;
 }
 
+// A load that is issued where it is written.  The compiler sinks a plain load under a later branch when its value is first used
+// there (through a `const __restrict__` argument also past a fence of its own), and the load then waits behind that branch's own
+// round trip.  A relaxed atomic load of wavefront scope is the same instruction -- no cache bits, no wait of its own -- which
+// the compiler neither moves across a branch nor drops: for a batch of loads that is to share ONE round trip with the loads
+// the branches in front of its uses wait for.
+template <typename S>
+__device__ __forceinline__ S load_here(const S* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+
 // the same sum left in lane 63 only (no readlane: nothing goes through scalar registers -- k_pass keeps 16 row dots per chunk,
 // which as wave-uniform values cost 32 SGPRs and spilled 102 of them in the read-modify-write instantiations)
 template <typename S>

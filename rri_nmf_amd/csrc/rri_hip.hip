@@ -1248,7 +1248,8 @@ struct LK {  // float64-only kernels
     }
     static EarlyJob early_job(const rri_ctx* c, int t, int tn) {
         return EarlyJob{(const double*)c->W, c->ldw, (int)c->n, c->k, t, tn, (const double*)c->Tearly, c->plan.nte, c->edot,
-                        c->Gearly, c->ent, early_job_first(c->npanels * c->nrb, c->n_cu), c->plan.e_blocks, c->plan.e_tpb};
+                        c->Gearly, c->ent, early_job_first(c->npanels * c->nrb, c->n_cu), c->plan.e_blocks, c->plan.e_tpb,
+                        c->plan.e_stride};
     }
     // the launch after the pass: the column update from the early job's sums, k_reduce's blocks in the same grid
     static void wfin(rri_ctx* c, int t, int tn, int sweep) {
@@ -2536,6 +2537,7 @@ rri_switches read_switches() {
     if (const char* e = getenv("RRI_PASS_CACHE_MB")) sw.pass_cache_mb = std::max(0.0, atof(e));
     if (const char* e = getenv("RRI_X_PACK")) sw.x_pack = atoi(e) == 2 ? 2 : atoi(e) != 0;
     if (const char* e = getenv("RRI_EARLY_SUMS")) sw.early_sums = atoi(e) != 0;
+    if (const char* e = getenv("RRI_EARLY_DEAL")) sw.early_deal = atoi(e) != 0;
     if (const char* e = getenv("RRI_PASS_PK_GEOM")) {
         char* end = nullptr;
         sw.pk_rows = (int)std::min<long>(std::max<long>(0, strtol(e, &end, 10)), 1 << 20);
@@ -5975,7 +5977,8 @@ rri_status rri_layout_info(rri_ctx* c, int64_t* out, int32_t n) {
         c->xp_valid ? 1 : 0, c->xp_valid ? c->xp_base : 0, c->xp_flagged, c->xp_tiles,
         c->xp_valid ? (c->xn_valid ? 26 : 28) : 0, c->xn_valid ? (int64_t)((uint64_t)c->xn_books.hi << 32 | c->xn_books.lo) : 0,
         c->xn_exceptions,
-        LK::early_ok(c) ? 1 : 0, c->early_steps};
+        LK::early_ok(c) ? 1 : 0, c->early_steps,
+        c->sw.early_deal ? 1 : 0, c->plan.e_stride};
     for (int i = 0; i < n && i < RRI_LAYOUT_FIELDS; ++i) out[i] = v[i];
     return RRI_OK;
 }

@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "rri_device.hpp"
+#include "rri_early_deal.hpp"
 #include "rri_halt.hpp"
 #include "rri_hip.h"
 #include "rri_layout.hpp"
@@ -187,8 +188,9 @@ __device__ __forceinline__ void tgram_block(const double* __restrict__ T, i64 ld
 // The early-sums schedule (RRI_EARLY_SUMS): a second job in the grid of the fused pass of topic step t.  Of what
 // k_wcol<true, true> computes after the pass, everything but the row dots y = X t_t comes from W and T T[t,:]^T alone, which are
 // final before the pass is launched (k_trow_early leaves the partials of T T[t,:]^T): per row the dot sum_{l != t} W[i,l] (T T[t,:]^T)[l],
-// and for the next topic tn the Gram entries w_tn^T w_l (l != t) and ||w_tn||^2.  `nblocks` workgroups, placed at `first` among
-// the pass's own (after its first round: early_job_first in rri_layout.hpp), walk `tpb` 64-row tiles each with k_wcol's loop --
+// and for the next topic tn the Gram entries w_tn^T w_l (l != t) and ||w_tn||^2.  `nblocks` workgroups, placed from `first` on among
+// the pass's own (after its first round: early_job_first in rri_layout.hpp), `stride` of the pass's own behind each of them
+// (early_slot in rri_early_deal.hpp; 0: one contiguous run), walk `tpb` 64-row tiles each with k_wcol's loop --
 // the same tiles, the same four-wave split of the columns, the same order of every sum -- and write dot[n], Gpart[b][0..k+2)
 // (entries t and k + 1 zero: k_wfin leaves those two per tile) and nt[0] = ||T[t,:]||^2.  No block of the grid reads them.
 struct EarlyJob {
@@ -196,6 +198,7 @@ struct EarlyJob {
     const double* Tearly; int nte;             // nte partial vectors T T[t,:]^T (entry t: the share of ||T[t,:]||^2)
     double *dot, *Gpart, *nt;
     int first, nblocks, tpb;                   // nblocks == 0: no job
+    int stride;
 };
 // CH: columns per batch of loads per wave (k_wcol: 16).  The job must fit the registers of the pass it rides in, whatever they
 // are (the float64 pass: 74): the batch is as small as that takes; the order of every sum is the same for every CH.
@@ -478,11 +481,12 @@ __global__ __launch_bounds__(256) void k_pass(typename std::conditional<(UPD > 0
     int njobs = job.nblocks;       // workgroups of the grid that are not the pass's own
     if constexpr (EJ) {
         // the early-sums job of the fused pass: ejob.nblocks workgroups from position ejob.first on, the pass's own around them
-        if (bid >= ejob.first && bid < ejob.first + ejob.nblocks) {
-            early_block<(sizeof(SX) == 8 ? 4 : 8)>(ejob, bid - ejob.first, reinterpret_cast<double*>(smem));
+        const EarlySlot slot = early_slot(bid, ejob.first, ejob.nblocks, ejob.stride);
+        if (slot.job) {
+            early_block<(sizeof(SX) == 8 ? 4 : 8)>(ejob, slot.index, reinterpret_cast<double*>(smem));
             return;
         }
-        if (bid >= ejob.first) bid -= ejob.nblocks;
+        bid = slot.index;
         njobs += ejob.nblocks;
     }
     if (rot != 0 && (bid | 7) < (int)gridDim.x - njobs) bid = (bid & ~7) | ((bid + rot) & 7);
@@ -1253,29 +1257,47 @@ __global__ __launch_bounds__(1024) void k_wfin(double* __restrict__ Wt, i64 ldw,
                                                const double* __restrict__ Gearly, int ne, double* __restrict__ red,
                                                int nredb, int sweep, KParams p, DevState* st) {
     static_assert(WFIN_TILES == 16 && WCOL_TILES == 1, "a wave per tile, a row of Gtile and an entry of xyp per tile");
-    if (st->halt) return;
     __shared__ double sh[32 * 33];
     if ((int)blockIdx.x < nredb) {
+        if (st->halt) return;
         reduce_block((int)blockIdx.x, nredb, Zpart, ldz, nrb, Gearly, ne, k, red, sh);
         return;
     }
     const int b = (int)blockIdx.x - nredb;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double cden = nt[0] + p.reg_w_l2;             // denom = nt + reg_w_l2 (nmf.py:465)
+    const i64 tile = (i64)b * 16 + wave;
+    const i64 i = tile * 64 + lane;
+    const bool valid = i < n;
+    // Every load of a tile wave in ONE round trip: none of the addresses depends on a loaded value, so the halt word, nt[0], the
+    // row's wn and dot and its first WFIN_YB partials of y are issued before the first wait and the branches come behind them (a
+    // wave that returns has asked for values it never uses; load_here, because the compiler sinks plain loads under the branches,
+    // four round trips in a row).  Rows past n read row n - 1, partials past npanels the last one, and neither enters a sum:
+    // the terms of y are added in ordered_sum<8>'s order, zeros where it adds zeros.
+    constexpr int WFIN_YB = 16;
+    const i64 ic = valid ? i : (i64)n - 1;
+    const int halted = load_here(&st->halt);
+    const double nt0 = load_here(nt);
+    const double wnl = load_here(Wt + (i64)tn * ldw + ic);
+    const double dtl = load_here(dot + ic);
+    double yv[WFIN_YB];
+#pragma unroll
+    for (int q = 0; q < WFIN_YB; ++q) yv[q] = load_here(Ypart + (i64)min(q, npanels - 1) * n + ic);
+    __builtin_amdgcn_sched_barrier(0);                  // the first use (and its wait) behind the last load, not among them
+    if (__builtin_amdgcn_readfirstlane(halted)) return;
+    const double cden = nt0 + p.reg_w_l2;               // denom = nt + reg_w_l2 (nmf.py:465)
     const int mode = wcol_denominator_mode(cden, p);
     if (mode < 0) {
         if (b == 0 && threadIdx.x == 0) halt_set(st, mode, t, sweep, t);
         return;
     }
-    const i64 tile = (i64)b * 16 + wave;
     if (tile * 64 >= n) return;                         // wave-uniform; no barrier follows
-    const i64 i = tile * 64 + lane;
-    const bool valid = i < n;
     double wn = 0.0, y = 0.0, wnew = 0.0;
     if (valid) {
-        wn = Wt[(i64)tn * ldw + i];
-        const double dt = dot[i];
-        y = ordered_sum<8>(Ypart + i, n, 0, npanels, 1);
+        wn = wnl;
+        const double dt = dtl;
+#pragma unroll
+        for (int q = 0; q < WFIN_YB; ++q) y += q < npanels ? yv[q] : 0.0;
+        if (npanels > WFIN_YB) y = ordered_sum_acc<8>(y, Ypart + i, n, WFIN_YB, npanels, 1);
         const double numer = (y - dt) - p.reg_w_l1;
         if (mode == 0) wnew = fmax(numer, 0.0) / (cden + p.eps);
         else wnew = (-numer + cden < 0.0) ? p.w_row_sum : 0.0;

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "rri_early_deal.hpp"
 #include "rri_hip.h"
 
 namespace rri {
@@ -65,6 +66,9 @@ struct rri_switches {
                                // the budget of pass_keep, the 26-bit copy if few elements are exceptions (xnarrow_build), else the 28-bit
     bool early_sums = true;    // RRI_EARLY_SUMS=0: the W-sized sums of a topic step stay in k_wcol after the pass (never the early job
                                // in the pass's grid, k_wfin and k_trow_early)
+    bool early_deal = false;   // RRI_EARLY_DEAL=1: the early job's workgroups are dealt through the pass's grid behind its first round
+                               // (rri_early_deal.hpp), not placed there in one contiguous run; no sum depends on it, and at the
+                               // flagship shape the pass takes the same time either way
 };
 
 // ---- the blocked store of a CSR pattern: dimensions ----------------------------------------------------------------------
@@ -109,6 +113,7 @@ struct DensePlan {
     // the early-sums schedule (early_* below): workgroups of k_trow_early (= partial vectors T T[t,:]^T), workgroups of the early
     // job in the pass's grid (= rows of its Gpart) and the 64-row tiles each walks, tile workgroups of k_wfin
     int nte = 1, e_blocks = 1, e_tpb = 1, nwfin = 1;
+    int e_stride = 0;      // own workgroups of the pass between two of the job (early_deal_stride; 0: the job's are contiguous)
 };
 
 // ---- the early-sums schedule (k_trow_early, the early job of k_pass, k_wfin) ------------------------------------------------
@@ -119,7 +124,8 @@ constexpr int WFIN_TILES = 16;         // 64-row tiles per workgroup of k_wfin (
 inline int early_job_blocks(i64 n, int n_cu) { return (int)std::max<i64>(1, std::min<i64>((n + 63) / 64, std::max(n_cu, 4) / 4)); }
 // where they sit among the pass's own workgroups: after the first round (4 workgroups of the pass per CU), so that they neither
 // delay the start of the stream nor, where the pass fills whole rounds, wait for its tail; a pass of one round has them last,
-// beside it
+// beside it.  This is where the FIRST of them sits: the others follow it in a contiguous run or dealt through what is left of
+// the pass's grid (DensePlan::e_stride; the map is early_slot in rri_early_deal.hpp)
 inline int early_job_first(int pass_blocks, int n_cu) { return std::min(pass_blocks, 4 * std::max(n_cu, 1)); }
 // LDS of the early job (doubles): T T[t,:]^T, the block's Gram partial, the four partial dots of a tile
 inline size_t early_job_lds_doubles(int k) { return (size_t)(2 * k + 2 + 256); }
@@ -207,6 +213,7 @@ inline DensePlan dense_plan(i64 n, i64 d, int k, int dtype, int flavour, const r
     p.e_blocks = early_job_blocks(n, n_cu);
     p.e_tpb = (int)(((n + 63) / 64 + p.e_blocks - 1) / p.e_blocks);
     p.nwfin = (int)((n + 64 * WFIN_TILES - 1) / (64 * WFIN_TILES));
+    if (sw.early_deal && !p.sparse) p.e_stride = early_deal_stride(p.npanels * p.nrb, early_job_first(p.npanels * p.nrb, n_cu), p.e_blocks);
     return p;
 }
 

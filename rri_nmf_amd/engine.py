@@ -1499,7 +1499,7 @@ class RRIEngine(object):
     LAYOUT_COPY_FIELDS = ('nblk', 'bw', 'lps', 'nwork')
     LAYOUT_FIELDS = ('rpb', 'nrb', 'npanels', 'mask_bits', 'mask_cols', 'mask_density', 'wtrow_small', 'nw_from_mask',
                      'interleaved', 'wcorr_nrb', 'n_cu', 'x_pack', 'x_pack_base', 'x_pack_flagged', 'x_pack_tiles', 'x_pack_bits',
-                     'x_pack_book', 'x_pack_exceptions', 'early_sums', 'early_steps')
+                     'x_pack_book', 'x_pack_exceptions', 'early_sums', 'early_steps', 'early_deal', 'early_stride')
     assert 2 * len(LAYOUT_COPY_FIELDS) + len(LAYOUT_FIELDS) == _capi.RRI_LAYOUT_FIELDS
 
     def layout_info(self):
@@ -1508,14 +1508,16 @@ class RRIEngine(object):
         (mask_density is None until the first topic step has measured it; nw_from_mask is what the last T-row step did), and the
         packed copy of an fp32 X: x_pack (the read-only pass streams it), x_pack_base, x_pack_flagged of x_pack_tiles tiles, x_pack_bits
         per element (28, 26 or 0), x_pack_book (the seven exponent bytes of a 26-bit copy) and x_pack_exceptions (elements outside it);
-        early_sums (the handle takes the early-sums schedule with its current parameters) and early_steps (W-column steps that did)"""
+        early_sums (the handle takes the early-sums schedule with its current parameters) and early_steps (W-column steps that did);
+        early_deal (RRI_EARLY_DEAL: the job's workgroups are dealt through the pass's grid) and early_stride (the pass's own workgroups
+        between two of the job; 0: one contiguous run)"""
         nc = len(self.LAYOUT_COPY_FIELDS)
         out = (C.c_int64 * _capi.RRI_LAYOUT_FIELDS)()
         self._check(self._lib.rri_layout_info(self._h, out, _capi.RRI_LAYOUT_FIELDS))
         v = [int(x) for x in out]
         info = {name: (v[i], v[nc + i]) for i, name in enumerate(self.LAYOUT_COPY_FIELDS)}
         info.update(zip(self.LAYOUT_FIELDS, v[2 * nc:]))
-        for name in ('mask_bits', 'mask_cols', 'wtrow_small', 'nw_from_mask', 'interleaved', 'x_pack', 'early_sums'):
+        for name in ('mask_bits', 'mask_cols', 'wtrow_small', 'nw_from_mask', 'interleaved', 'x_pack', 'early_sums', 'early_deal'):
             info[name] = bool(info[name])
         info['mask_density'] = None if info['mask_density'] < 0 else info['mask_density'] * 1e-9
         info['x_pack_book'] = [info['x_pack_book'] >> (8 * i) & 0xff for i in range(7)] if info['x_pack_bits'] == 26 else []
