@@ -178,6 +178,15 @@ CORPUS_FIT_PROTOTYPES = {
     'rri_corpus_value_range': (_I32, [_P, _P, C.POINTER(_D)]),
 }
 
+# ... and every symbol include/rri_corpus_rank.h declares: top-N lists, ranks and ranking metrics against resident corpora.  All
+# three read a handle's W and T and keep nothing
+CORPUS_RANK_PROTOTYPES = {
+    'rri_corpus_topn_rows': (_I32, [_P, C.POINTER(_I64), _I64, _I32, _P, _D, _D, C.POINTER(_I32), C.POINTER(_D), C.POINTER(_D)]),
+    'rri_corpus_rank_entries': (_I32, [_P, _P, C.POINTER(_I64), _P, _D, _D, C.POINTER(_I32), C.POINTER(_D), C.POINTER(_I32),
+                                       C.POINTER(_D)]),
+    'rri_corpus_ranking_metrics': (_I32, [_P, _P, C.POINTER(_I64), _P, _I64, _D, C.POINTER(_D), C.POINTER(_D)]),
+}
+
 _lib = None
 
 
@@ -239,7 +248,7 @@ def load_library(path=None):
     except OSError as e:  # e.g. libamdhip64 missing
         raise RRIHipUnavailable('cannot load %s: %s' % (p, e))
     for name, (res, args) in list(PROTOTYPES.items()) + list(CORPUS_OPS_PROTOTYPES.items()) + list(CORPUS_BUILD_PROTOTYPES.items()) + \
-            list(CORPUS_FIT_PROTOTYPES.items()):
+            list(CORPUS_FIT_PROTOTYPES.items()) + list(CORPUS_RANK_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

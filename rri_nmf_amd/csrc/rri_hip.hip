@@ -54,6 +54,8 @@
 #include "rri_corpus_build_kernels.hpp"
 #include "rri_corpus_fit.h"
 #include "rri_fiterr_kernels.hpp"
+#include "rri_corpus_rank.h"
+#include "rri_corpus_rank_kernels.hpp"
 
 using namespace rri;
 
@@ -1336,26 +1338,26 @@ struct LK {  // float64-only kernels
                            (const double*)c->T, c->LD, c->k, ij, vals, count, lo, hi, c->normpart);
     }
     // the N best columns of W T for `count` requested rows (rri_topn_kernels.hpp); reads W and T, writes the two outputs only
-    static hipError_t topn_rows(rri_ctx* c, const i64* rows, i64 count, int N, const i64* eptr, const int* eidx, double lo,
-                                double hi, int* idx_out, double* val_out) {
+    static hipError_t topn_rows(rri_ctx* c, const i64* rows, i64 count, int N, const i64* eptr, const int* eidx, const i64* erow,
+                                double lo, double hi, int* idx_out, double* val_out) {
         const hipError_t e = allow_lds<k_topn_rows>(c, 64 * 1024);
         if (e != hipSuccess) return e;
         TimedScope ts(c, 4);
         hipLaunchKernelGGL(k_topn_rows, dim3((unsigned)((count + TOPN_ROWS - 1) / TOPN_ROWS)), dim3(256), topn_lds_bytes(N),
                            c->stream, (const double*)c->W, c->ldw, (const double*)c->T, c->LD, (int)c->d, c->k, rows, count, N,
-                           eptr, eidx, lo, hi, idx_out, val_out);
+                           eptr, eidx, erow, lo, hi, idx_out, val_out);
         return hipGetLastError();
     }
     // the ranks of listed columns of W T, piece by piece (rri_rank_kernels.hpp); reads W and T, writes the three outputs only
     static hipError_t rank_entries(rri_ctx* c, const i64* rows, const RankPiece* pieces, i64 npieces, const int* tidx,
-                                   const i64* eptr, const int* eidx, double lo, double hi, int* rank_out, double* val_out,
-                                   int* elig_out) {
+                                   const i64* eptr, const int* eidx, const i64* erow, double lo, double hi, int* rank_out,
+                                   double* val_out, int* elig_out) {
         const hipError_t e = allow_lds<k_rank_entries>(c, (int)rank_lds_bytes());
         if (e != hipSuccess) return e;
         TimedScope ts(c, 5);
         hipLaunchKernelGGL(k_rank_entries, dim3((unsigned)((npieces + RANK_PIECES - 1) / RANK_PIECES)), dim3(256), rank_lds_bytes(),
                            c->stream, (const double*)c->W, c->ldw, (const double*)c->T, c->LD, (int)c->d, c->k, rows, pieces, npieces,
-                           tidx, eptr, eidx, lo, hi, rank_out, val_out, elig_out);
+                           tidx, eptr, eidx, erow, lo, hi, rank_out, val_out, elig_out);
         return hipGetLastError();
     }
     // the masks of the rows [ch.r0, ch.r1) of a CSR pattern and the pair counts of those masks, added to codf
@@ -3678,8 +3680,8 @@ rri_status rri_topn_rows(rri_ctx* c, const int64_t* rows, int64_t count, int32_t
         HIPCHK(c, hipMemcpyAsync(tptr.p, excl_indptr, (size_t)(count + 1) * sizeof(i64), hipMemcpyHostToDevice, c->stream));
         if (nex > 0) HIPCHK(c, hipMemcpyAsync(tidx.p, excl_indices, (size_t)nex * sizeof(int), hipMemcpyHostToDevice, c->stream));
     }
-    hipError_t e = LK::topn_rows(c, (const i64*)trows.p, count, topn, (const i64*)tptr.p, (const int*)tidx.p, clip_lo, clip_hi,
-                                 (int*)tj.p, (double*)tv.p);
+    hipError_t e = LK::topn_rows(c, (const i64*)trows.p, count, topn, (const i64*)tptr.p, (const int*)tidx.p, nullptr, clip_lo,
+                                 clip_hi, (int*)tj.p, (double*)tv.p);
     if (e == hipSuccess) e = hipMemcpyAsync(idx_out, tj.p, (size_t)count * topn * sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(val_out, tv.p, (size_t)count * topn * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     const hipError_t es = hipStreamSynchronize(c->stream);
@@ -3726,7 +3728,7 @@ rri_status rri_rank_entries(rri_ctx* c, const int64_t* rows, int64_t count, cons
         if (nex > 0) HIPCHK(c, hipMemcpyAsync(tidx.p, excl_indices, (size_t)nex * sizeof(int), hipMemcpyHostToDevice, c->stream));
     }
     hipError_t e = LK::rank_entries(c, (const i64*)trows.p, (const RankPiece*)tpc.p, npieces, (const int*)ttg.p, (const i64*)tptr.p,
-                                    (const int*)tidx.p, clip_lo, clip_hi, (int*)tr.p, (double*)tv.p, (int*)te.p);
+                                    (const int*)tidx.p, nullptr, clip_lo, clip_hi, (int*)tr.p, (double*)tv.p, (int*)te.p);
     if (e == hipSuccess) e = hipMemcpyAsync(rank_out, tr.p, (size_t)ntg * sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(val_out, tv.p, (size_t)ntg * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && eligible_out) e = hipMemcpyAsync(eligible_out, te.p, (size_t)count * sizeof(int), hipMemcpyDeviceToHost, c->stream);
@@ -4985,6 +4987,190 @@ rri_status rri_corpus_value_range(rri_ctx* c, const rri_corpus* k, double out[2]
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, p + 2 * (size_t)nb, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RRI_OK;
+}
+
+// ---- top-N lists, ranks and ranking metrics against resident corpora (include/rri_corpus_rank.h; rri_corpus_rank.hpp has the
+// semantics, rri_corpus_rank_kernels.hpp the kernels) --------------------------------------------------------------------------------
+namespace {
+CrankCorpus crank_view(const rri_corpus* k) {
+    const bool alive = corpus_alive(k);
+    return CrankCorpus{k != nullptr, alive, alive ? k->n_rows : 0, alive ? k->n_cols : 0, alive ? k->device : 0};
+}
+// the HIP-event time of the kernels enqueued between begin() and end(); end() synchronises the stream
+struct CrankTimer {
+    rri_ctx* c;
+    EventPair ev;
+    double ms = 0.0;
+    hipError_t begin() { return hipEventRecord(ev.a, c->stream); }
+    hipError_t end() {
+        hipError_t e = hipEventRecord(ev.b, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        float t = 0.0f;
+        if (e == hipSuccess && hipEventElapsedTime(&t, ev.a, ev.b) == hipSuccess) ms += t;
+        return e;
+    }
+};
+// the ranks, values and eligible counts of every stored entry of `tg`, left on the device: the pieces are counted, scanned and cut
+// there, their number is the one value read back, and k_rank_entries reads targets and exclusion where they lie.  rows: the
+// device row list (NULL: request q scores row q).  The caller has checked the request and that there is something to score.
+hipError_t crank_rank_device(rri_ctx* c, const rri_corpus* tg, const i64* rows, const rri_corpus* ex, double lo, double hi, DevTmp& rank,
+                             DevTmp& val, DevTmp& elig, CrankTimer& tm) {
+    const i64 m = tg->n_rows, len = m + 1, tiles = (len + CRANK_SCAN_TILE - 1) / CRANK_SCAN_TILE;
+    DevTmp first, part, pieces;
+    hipError_t e = first.alloc((size_t)len * sizeof(i64));
+    if (e == hipSuccess) e = part.alloc((size_t)tiles * sizeof(i64));
+    if (e == hipSuccess) e = rank.alloc((size_t)tg->nnz * sizeof(int));
+    if (e == hipSuccess) e = val.alloc((size_t)tg->nnz * sizeof(double));
+    if (e == hipSuccess) e = elig.alloc((size_t)m * sizeof(int));
+    if (e == hipSuccess) e = hipMemsetAsync(elig.p, 0xff, (size_t)m * sizeof(int), c->stream);      // -1: a row without entries
+    if (e == hipSuccess) e = tm.begin();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_crank_count, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, (const i64*)tg->indptr, m, (i64*)first.p);
+    hipLaunchKernelGGL(k_crank_scan_part, dim3((unsigned)tiles), dim3(256), 0, c->stream, (const i64*)first.p, len, (i64*)part.p);
+    hipLaunchKernelGGL(k_crank_scan_top, dim3(1), dim3(256), 0, c->stream, (i64*)part.p, tiles);
+    hipLaunchKernelGGL(k_crank_scan_apply, dim3((unsigned)tiles), dim3(256), 0, c->stream, (i64*)first.p, len, (const i64*)part.p);
+    e = hipGetLastError();
+    i64 npieces = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&npieces, (const i64*)first.p + m, sizeof(i64), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = tm.end();
+    if (e != hipSuccess) return e;
+    if (npieces < 1 || npieces > tg->nnz || (npieces + RANK_PIECES - 1) / RANK_PIECES > 0x7fffffffLL) return hipErrorInvalidValue;
+    e = pieces.alloc((size_t)npieces * sizeof(RankPiece));
+    if (e == hipSuccess) e = tm.begin();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_crank_cut, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, (const i64*)tg->indptr, m, (const i64*)first.p,
+                       (RankPiece*)pieces.p);
+    e = hipGetLastError();
+    if (e == hipSuccess)
+        e = LK::rank_entries(c, rows, (const RankPiece*)pieces.p, npieces, (const int*)tg->indices, ex ? (const i64*)ex->indptr : nullptr,
+                             ex ? (const int*)ex->indices : nullptr, rows, lo, hi, (int*)rank.p, (double*)val.p, (int*)elig.p);
+    const hipError_t es = tm.end();      // the pieces are released behind the kernel that reads them
+    return e == hipSuccess ? es : e;
+}
+}  // namespace
+
+rri_status rri_corpus_topn_rows(rri_ctx* c, const int64_t* rows, int64_t count, int32_t topn, const rri_corpus* exclude, double clip_lo,
+                                double clip_hi, int32_t* idx_out, double* val_out, double* kernel_ms) {
+    CHECK_CTX(c);
+    char why[200] = "";
+    const int bad = crank_check_request(CRANK_CALL_TOPN, c->n, c->d, c->device, CrankCorpus{false, false, 0, 0, 0}, crank_view(exclude), rows,
+                                        count, topn, RRI_MAX_TOPN, 1, clip_lo, clip_hi, why, sizeof why);
+    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+    if (count > 0) {
+        if (!idx_out || !val_out) return fail(c, RRI_ERR_INVALID, "an output array is NULL");
+        if (!c->have_W || !c->have_T) return fail(c, RRI_ERR_INVALID, "W and T must be set first");
+        if ((count + TOPN_ROWS - 1) / TOPN_ROWS > 0x7fffffffLL) return fail(c, RRI_ERR_INVALID, "count %lld is too large for one call", (long long)count);
+    }
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (count == 0) return RRI_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevTmp trows, tj, tv;
+    CrankTimer tm{c};
+    HIPCHK(c, tm.ev.create());
+    if (rows) HIPCHK(c, trows.alloc((size_t)count * sizeof(i64)));
+    HIPCHK(c, tj.alloc((size_t)count * topn * sizeof(int)));
+    HIPCHK(c, tv.alloc((size_t)count * topn * sizeof(double)));
+    if (rows) HIPCHK(c, hipMemcpyAsync(trows.p, rows, (size_t)count * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+    hipError_t e = tm.begin();
+    if (e == hipSuccess)
+        e = LK::topn_rows(c, (const i64*)trows.p, count, topn, exclude ? (const i64*)exclude->indptr : nullptr,
+                          exclude ? (const int*)exclude->indices : nullptr, (const i64*)trows.p, clip_lo, clip_hi, (int*)tj.p, (double*)tv.p);
+    const hipError_t et = tm.end();
+    if (e == hipSuccess) e = et;
+    if (e == hipSuccess) e = hipMemcpyAsync(idx_out, tj.p, (size_t)count * topn * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(val_out, tv.p, (size_t)count * topn * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "top-N rows against a corpus failed: %s", hipGetErrorString(e));
+    if (kernel_ms) *kernel_ms = tm.ms;
+    return RRI_OK;
+}
+
+rri_status rri_corpus_rank_entries(rri_ctx* c, const rri_corpus* targets, const int64_t* rows, const rri_corpus* exclude, double clip_lo,
+                                   double clip_hi, int32_t* rank_out, double* val_out, int32_t* eligible_out, double* kernel_ms) {
+    CHECK_CTX(c);
+    char why[200] = "";
+    const int bad = crank_check_request(CRANK_CALL_RANK, c->n, c->d, c->device, crank_view(targets), crank_view(exclude), rows, 0, 1,
+                                        RRI_MAX_TOPN, 1, clip_lo, clip_hi, why, sizeof why);
+    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+    const i64 m = targets->n_rows, nnz = targets->nnz;
+    if (nnz > 0 && (!c->have_W || !c->have_T)) return fail(c, RRI_ERR_INVALID, "W and T must be set first");
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (eligible_out) std::fill(eligible_out, eligible_out + m, -1);
+    if (m == 0 || nnz == 0) return RRI_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevTmp trows, tr, tv, te;
+    CrankTimer tm{c};
+    HIPCHK(c, tm.ev.create());
+    if (rows) {
+        HIPCHK(c, trows.alloc((size_t)m * sizeof(i64)));
+        HIPCHK(c, hipMemcpyAsync(trows.p, rows, (size_t)m * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+    }
+    hipError_t e = crank_rank_device(c, targets, (const i64*)trows.p, exclude, clip_lo, clip_hi, tr, tv, te, tm);
+    if (e == hipSuccess && rank_out) e = hipMemcpyAsync(rank_out, tr.p, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && val_out) e = hipMemcpyAsync(val_out, tv.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && eligible_out) e = hipMemcpyAsync(eligible_out, te.p, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, RRI_ERR_HIP, "rank entries of a corpus failed: %s", hipGetErrorString(e));
+    if (kernel_ms) *kernel_ms = tm.ms;
+    return RRI_OK;
+}
+
+rri_status rri_corpus_ranking_metrics(rri_ctx* c, const rri_corpus* targets, const int64_t* rows, const rri_corpus* exclude,
+                                      int64_t n_items, double relevant_from, double out[16], double* kernel_ms) {
+    CHECK_CTX(c);
+    char why[200] = "";
+    const int bad = crank_check_request(CRANK_CALL_METRICS, c->n, c->d, c->device, crank_view(targets), crank_view(exclude), rows, 0, 1,
+                                        RRI_MAX_TOPN, n_items, 0.0, 0.0, why, sizeof why);
+    if (bad != TOPN_REQ_OK) return fail(c, bad == TOPN_REQ_UNSUPPORTED ? RRI_ERR_UNSUPPORTED : RRI_ERR_INVALID, "%s", why);
+    if (!out) return fail(c, RRI_ERR_INVALID, "out is NULL");
+    const i64 m = targets->n_rows, nnz = targets->nnz;
+    if (nnz > 0 && (!c->have_W || !c->have_T)) return fail(c, RRI_ERR_INVALID, "W and T must be set first");
+    std::fill(out, out + CRANK_OUT, 0.0);
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (m == 0 || nnz == 0) return RRI_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<double> table, ideal;
+    const i64 tl = crank_table_len(n_items, c->d);
+    crank_table(tl, &table, &ideal);
+    const i64 nb = (m + CRANK_SUM_ROWS - 1) / CRANK_SUM_ROWS;
+    DevTmp trows, tr, tv, te, ttab, tideal, tterms, tpart;
+    CrankTimer tm{c};
+    HIPCHK(c, tm.ev.create());
+    if (rows) {
+        HIPCHK(c, trows.alloc((size_t)m * sizeof(i64)));
+        HIPCHK(c, hipMemcpyAsync(trows.p, rows, (size_t)m * sizeof(i64), hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, ttab.alloc((size_t)tl * sizeof(double)));
+    HIPCHK(c, tideal.alloc((size_t)(tl + 1) * sizeof(double)));
+    HIPCHK(c, tterms.alloc((size_t)m * CRANK_TERMS * sizeof(double)));
+    HIPCHK(c, tpart.alloc((size_t)(nb + 1) * CRANK_TERMS * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(ttab.p, table.data(), (size_t)tl * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tideal.p, ideal.data(), (size_t)(tl + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const double inf = (double)INFINITY;
+    hipError_t e = crank_rank_device(c, targets, (const i64*)trows.p, exclude, -inf, inf, tr, tv, te, tm);
+    if (e == hipSuccess) e = tm.begin();
+    if (e == hipSuccess) {
+        double* part = (double*)tpart.p;
+        hipLaunchKernelGGL(k_crank_rows, dim3((unsigned)std::min<i64>(65536, (m + 3) / 4)), dim3(256), 0, c->stream, (const i64*)targets->indptr,
+                           (const double*)targets->values, m, (const int*)tr.p, (const int*)te.p, (i64)n_items, relevant_from,
+                           (const double*)ttab.p, (const double*)tideal.p, (double*)tterms.p);
+        hipLaunchKernelGGL(k_crank_sum, dim3((unsigned)nb), dim3(256), 0, c->stream, (const double*)tterms.p, m, (i64)CRANK_SUM_ROWS, part);
+        hipLaunchKernelGGL(k_crank_sum, dim3(1), dim3(256), 0, c->stream, (const double*)part, nb, nb, part + (size_t)nb * CRANK_TERMS);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(out, part + (size_t)nb * CRANK_TERMS, CRANK_TERMS * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        const hipError_t et = tm.end();
+        if (e == hipSuccess) e = et;
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);      // the table (host memory of this call) has been read by now too
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        std::fill(out, out + CRANK_OUT, 0.0);
+        return fail(c, RRI_ERR_HIP, "ranking metrics of a corpus failed: %s", hipGetErrorString(e));
+    }
+    if (kernel_ms) *kernel_ms = tm.ms;
     return RRI_OK;
 }
 

@@ -21,7 +21,8 @@
 // walk 1, reused) and move the cursor on by their number: work per piece is its segment's length plus the number of chunks, and
 // a score's eligibility is one LDS read and v == v.  NaN scores outside the exclusion are counted per piece:
 // eligible = d - |segment| - that count, reported by a request's first piece.  Whether a TARGET is excluded is asked once per
-// target at the end (topn_excluded).
+// target at the end (topn_excluded).  The segment of a request is row req of the exclusion CSR, or -- erow given -- row erow[req] of
+// any CSR pattern: a resident corpus of the handle's shape, read where it lies (rri_corpus_rank.hpp).
 //
 // Who may touch what in LDS: the rows of a piece (scores, columns, slots / flags, cursor) belong to the piece's wave alone.  A
 // row is cleared at the top of a chunk's step, marked between the two barriers of the chunk's first panel and read after the
@@ -47,8 +48,9 @@ inline size_t rank_lds_bytes() {
 __global__ __launch_bounds__(256, 2) void k_rank_entries(const double* __restrict__ Wt, i64 ldw, const double* __restrict__ T, i64 ldt,
                                                       int d, int k, const i64* __restrict__ rows, const RankPiece* __restrict__ pieces,
                                                       i64 npieces, const int* __restrict__ tidx, const i64* __restrict__ eptr,
-                                                      const int* __restrict__ eidx, double lo, double hi, int* __restrict__ rank_out,
-                                                      double* __restrict__ val_out, int* __restrict__ elig_out) {
+                                                      const int* __restrict__ eidx, const i64* __restrict__ erow, double lo, double hi,
+                                                      int* __restrict__ rank_out, double* __restrict__ val_out,
+                                                      int* __restrict__ elig_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* tsh = reinterpret_cast<double*>(smem);                             // [TOPN_KP][TOPN_COLS]
     double* tsc = tsh + TOPN_KP * TOPN_COLS;                                   // [RANK_PIECES][RANK_SEG] scores of the targets
@@ -75,8 +77,9 @@ __global__ __launch_bounds__(256, 2) void k_rank_entries(const double* __restric
         tsc[pl * RANK_SEG + lane] = nan;
         if (lane == 0) {
             const bool seg = eptr && p0 + r < npieces;
-            ecur[pl] = seg ? eptr[req] : 0;
-            eend[pl] = seg ? eptr[req + 1] : 0;
+            const i64 er = (seg && erow) ? erow[req] : req;                  // the exclusion's row that serves the request
+            ecur[pl] = seg ? eptr[er] : 0;
+            eend[pl] = seg ? eptr[er + 1] : 0;
         }
     }
     // a cleared slot row holds 0xff (no target at the column), a cleared flag row 0 (not excluded); thread -> its own 16 bytes,
@@ -243,7 +246,8 @@ __global__ __launch_bounds__(256, 2) void k_rank_entries(const double* __restric
         if (p0 + r < npieces) {                                              // uniform: every lane of the wave is here
             const RankPiece pc = pieces[p0 + r];
             const int pl = wave * 16 + r;
-            const i64 e0 = eptr ? eptr[pc.req] : 0, e1 = eptr ? eptr[pc.req + 1] : 0;
+            const i64 er = (eptr && erow) ? erow[pc.req] : pc.req;
+            const i64 e0 = eptr ? eptr[er] : 0, e1 = eptr ? eptr[er + 1] : 0;
             const int nanr = __shfl(nanl[r >> 2], (r & 3) * 16);
             if (lane < pc.cnt) {
                 const double ts = tsc[pl * RANK_SEG + lane];

@@ -18,6 +18,8 @@
 // until at most 64 entries are left, which the lanes compare at once --, and the insertion is one step: every lane asks
 // whether its slot stays ahead of the candidate, the count of those that do is the candidate's place, the slots behind take
 // their left neighbour's content by a lane shift.  About N ln(d / N) insertions per row, so serial per wave is cheap.
+// The exclusion is a CSR pattern with one row per request, or -- erow given -- any CSR pattern of which request q reads row
+// erow[q]: a resident corpus of the handle's shape, read where it lies through the row list (rri_corpus_rank.hpp).
 #pragma once
 
 #include "rri_topn.hpp"
@@ -33,8 +35,9 @@ inline size_t topn_lds_bytes(int N) { return (size_t)TOPN_KP * TOPN_COLS * 8 + (
 
 __global__ __launch_bounds__(256) void k_topn_rows(const double* __restrict__ Wt, i64 ldw, const double* __restrict__ T, i64 ldt,
                                                    int d, int k, const i64* __restrict__ rows, i64 count, int N,
-                                                   const i64* __restrict__ eptr, const int* __restrict__ eidx, double lo,
-                                                   double hi, int* __restrict__ idx_out, double* __restrict__ val_out) {
+                                                   const i64* __restrict__ eptr, const int* __restrict__ eidx,
+                                                   const i64* __restrict__ erow, double lo, double hi, int* __restrict__ idx_out,
+                                                   double* __restrict__ val_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* tsh = reinterpret_cast<double*>(smem);                         // [TOPN_KP][TOPN_COLS]
     double* lv = tsh + TOPN_KP * TOPN_COLS;                                // [TOPN_ROWS][N]
@@ -112,7 +115,8 @@ __global__ __launch_bounds__(256) void k_topn_rows(const double* __restrict__ Wt
                     const int row = (b >> 4) + 4 * r;                     // of the wave's 16
                     if (!topn_enters(cv, cj, __shfl(thv[r], b), __shfl(thj[r], b))) continue;
                     if (eptr) {
-                        i64 e0 = eptr[q0 + row], e1 = eptr[q0 + row + 1];
+                        const i64 er = erow ? erow[q0 + row] : q0 + row;   // the exclusion's row that serves the request
+                        i64 e0 = eptr[er], e1 = eptr[er + 1];
                         while (e1 - e0 > 64) {                            // halve; the half kept can still hold cj
                             const i64 mid = e0 + (e1 - e0) / 2;
                             if (eidx[mid] < cj) e0 = mid + 1;

@@ -212,6 +212,80 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
         finally:
             eng.close()
 
+    def _factors_engine(self, corpora):
+        """a factors-only handle holding the fitted W and T (nothing of size n x d), after the corpora have been checked"""
+        if np.ndim(self.W) != 2 or np.ndim(self.T) != 2:
+            raise ValueError('the estimator is not fitted: it has no W and T')
+        for what, c in corpora:
+            if c is not None and not isinstance(c, DeviceCorpus):
+                raise TypeError('%s must be a DeviceCorpus, not %s' % (what, type(c).__name__))
+        W = self.W.toarray() if sp.issparse(self.W) else np.asarray(self.W)       # sparsify() was called: dense copies
+        T = self.T.toarray() if sp.issparse(self.T) else np.asarray(self.T)
+        eng = RRIEngine(W.shape[0], T.shape[1], W.shape[1], dtype=np.float64, weighted=False, device=self.nmf_kwargs.get('device', 0))
+        try:
+            eng.set_W(W)
+            eng.set_T(T)
+        except Exception:
+            eng.close()
+            raise
+        return eng
+
+    def recommend_corpus(self, users=None, n_items=10, exclude=None):
+        """`recommend` against a resident exclusion: the n_items best items for each of `users` (row indices, any order, duplicates
+        allowed; None: every user), leaving out for user i the stored entries of row i of `exclude` -- a DeviceCorpus of the
+        estimator's shape, typically the corpus split_entries was called on (train and held-out together), or None --, read where
+        it lies (rri_corpus_topn_rows): no seen_, no copy of the excluded pairs on the host.  (items int32 (m, n_items), scores
+        float64 (m, n_items)), the items and scores `recommend` returns when seen_ is that corpus's pattern."""
+        from .corpus_rank import topn_rows
+        eng = self._factors_engine((('exclude', exclude),))
+        try:
+            n = eng.n
+            users = np.arange(n, dtype=np.int64) if users is None else np.asarray(users, dtype=np.int64).reshape(-1)
+            if users.size and (users.min() < 0 or users.max() >= n):
+                raise ValueError('users must be row indices in [0, %d)' % n)
+            n_items = int(n_items)
+            items = np.empty((users.size, max(n_items, 0)), dtype=np.int32)
+            scores = np.empty((users.size, max(n_items, 0)), dtype=np.float64)
+            for lo in range(0, users.size, _RECOMMEND_CHUNK):       # the exclusion is indexed by the user: passed whole to every chunk
+                u = users[lo:lo + _RECOMMEND_CHUNK]
+                items[lo:lo + u.size], scores[lo:lo + u.size] = topn_rows(eng, u, n_items, exclude=exclude,
+                                                                          clip=(self.min_rating, self.max_rating))[:2]
+        finally:
+            eng.close()
+        return items, scores
+
+    def rank_corpus(self, targets, exclude=None):
+        """`rank` for pairs that are resident: the place of every stored entry (user i, item j) of the DeviceCorpus `targets` (the
+        estimator's shape) among user i's items, counted on the device where the corpus lies (rri_corpus_rank_entries): (rank int32
+        per canonical entry in corpus order, eligible int32 per row; -1 for a user without entries, who is not scored).  `exclude`
+        as in recommend_corpus; an entry that is itself excluded, or whose prediction is NaN, gets rank -1."""
+        from .corpus_rank import rank_entries
+        eng = self._factors_engine((('targets', targets), ('exclude', exclude)))
+        try:
+            if targets is None or tuple(targets.shape) != (eng.n, eng.d):
+                raise ValueError('targets must be a DeviceCorpus of shape %d x %d' % (eng.n, eng.d))
+            res = rank_entries(eng, targets, exclude=exclude, clip=(self.min_rating, self.max_rating), values=False)
+        finally:
+            eng.close()
+        return res['rank'], res['eligible']
+
+    def ranking_score_corpus(self, targets, n_items=10, exclude=None, relevant_from=None):
+        """`ranking_score` for pairs that are resident: the same dict, formula for formula, over the stored entries of the
+        DeviceCorpus `targets` whose value is at least relevant_from (None: all), ranked and summed on the device
+        (rri_corpus_ranking_metrics): a dozen doubles come back, not one rank per pair, and neither the corpus nor seen_ is
+        downloaded.  `exclude` as in recommend_corpus.  The metrics agree with ranking_score's to the order of the sums."""
+        from .corpus_rank import ranking_metrics
+        n_items = int(n_items)
+        if n_items < 1:
+            raise ValueError('n_items must be a positive integer, not %d' % n_items)
+        eng = self._factors_engine((('targets', targets), ('exclude', exclude)))
+        try:
+            if targets is None or tuple(targets.shape) != (eng.n, eng.d):
+                raise ValueError('targets must be a DeviceCorpus of shape %d x %d' % (eng.n, eng.d))
+            return ranking_metrics(eng, targets, n_items, exclude=exclude, relevant_from=relevant_from)
+        finally:
+            eng.close()
+
     def transform(self, Xnew):
         """fold new rows in against the fitted T"""
         soln = _nmf(Xnew, self.k, max_iter=4, max_time=7200, project_W_each_iter=False,
@@ -244,7 +318,8 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
         the unclipped prediction W[i, :] T[:, j], larger first, equal predictions by the smaller item; the scores returned are
         clipped to the rating range, the numbers `predict` gives for those pairs.  exclude_seen leaves out the pairs given to fit
         (seen_, the hold-out included); a user with fewer than n_items items left gets item -1 and score NaN in the last slots.
-        No n x d product is formed anywhere, and there is no host route: without a GPU the call raises RRIHipUnavailable."""
+        No n x d product is formed anywhere, and there is no host route: without a GPU the call raises RRIHipUnavailable.
+        recommend_corpus excludes the entries of a resident corpus instead of seen_, without a copy of them on the host."""
         if np.ndim(self.W) != 2 or np.ndim(self.T) != 2:
             raise ValueError('the estimator is not fitted: it has no W and T')
         if exclude_seen and getattr(self, 'seen_', None) is None:
@@ -309,8 +384,9 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
         the user has to choose from.  exclude_seen leaves out the pairs given to fit (seen_, the hold-out included); a pair that
         is itself in seen_ is not eligible and gets rank -1 -- it is not taken out of the exclusion silently --, as does a pair
         whose prediction is NaN.  No n x d product is formed, and there is no host route: without a GPU the call raises
-        RRIHipUnavailable.  A DeviceCorpus is taken as its matrix through one to_scipy() download: a ranking that reads a
-        resident corpus is not built (the fit and the score are: fit_corpus, score_corpus)."""
+        RRIHipUnavailable.  A DeviceCorpus is taken as its matrix through one to_scipy() download: into this method a route that
+        reads a resident corpus is not built, because its answer is aligned with pairs on the host; rank_corpus ranks the corpus
+        where it lies."""
         if isinstance(X, DeviceCorpus):
             X = X.to_scipy()
         if np.ndim(self.W) != 2 or np.ndim(self.T) != 2:
@@ -357,7 +433,8 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
         and n_items, users (how many were averaged), targets, targets_not_eligible (rank -1: in seen_ under exclude_seen, or a
         NaN prediction).  Without an eligible target the metrics are NaN and the counts say why.  Computed on the host in
         float64; each rank of a row-sharded fit scores its own rows.  A DeviceCorpus is taken as its matrix through one
-        to_scipy() download: a ranking that reads a resident corpus is not built."""
+        to_scipy() download: into this method a route that reads a resident corpus is not built; ranking_score_corpus ranks the
+        corpus where it lies and sums the metrics on the device."""
         if isinstance(X, DeviceCorpus):
             X = X.to_scipy()
         n_items = int(n_items)
