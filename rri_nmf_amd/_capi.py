@@ -187,6 +187,13 @@ CORPUS_RANK_PROTOTYPES = {
     'rri_corpus_ranking_metrics': (_I32, [_P, _P, C.POINTER(_I64), _P, _I64, _D, C.POINTER(_D), C.POINTER(_D)]),
 }
 
+# ... and every symbol include/rri_fold.h declares: the one-launch fold sweep of a pattern-only handle, asked for per handle.  Neither
+# call touches a handle's cached state
+FOLD_PROTOTYPES = {
+    'rri_set_fold_schedule': (_I32, [_P, C.c_int]),
+    'rri_fold_info': (_I32, [_P, C.POINTER(_I64)]),
+}
+
 _lib = None
 
 
@@ -248,7 +255,7 @@ def load_library(path=None):
     except OSError as e:  # e.g. libamdhip64 missing
         raise RRIHipUnavailable('cannot load %s: %s' % (p, e))
     for name, (res, args) in list(PROTOTYPES.items()) + list(CORPUS_OPS_PROTOTYPES.items()) + list(CORPUS_BUILD_PROTOTYPES.items()) + \
-            list(CORPUS_FIT_PROTOTYPES.items()) + list(CORPUS_RANK_PROTOTYPES.items()):
+            list(CORPUS_FIT_PROTOTYPES.items()) + list(CORPUS_RANK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -39,7 +39,7 @@ struct DevState {
     int tmode;       // qf_min branch of the current T row: 0 c>0, 1 c<=0 bounds, 2 c<=0 one-hot
     int proj_iters;  // Michelot iterations of the last projection (diagnostic)
     int pad0;        // k_wsweep_verdict: first column k_wsweep_repair restores after a reset event (0: none); cleared with halt
-    int pad1;
+    int pad1;        // k_wfold_verdict: 1 when the halt was found inside a one-launch fold sweep (rri_fold_info counts them); cleared with halt
     double nt1;      // 1-norm of the unprojected T-row solution (qf_min's nx, nmf.py:447)
     double nt;       // ||T[t,:]||^2
     double sumT;

@@ -56,6 +56,8 @@
 #include "rri_fiterr_kernels.hpp"
 #include "rri_corpus_rank.h"
 #include "rri_corpus_rank_kernels.hpp"
+#include "rri_fold.h"
+#include "rri_fold_kernels.hpp"
 
 using namespace rri;
 
@@ -186,6 +188,12 @@ struct rri_ctx {
     i64 xp_flagged = 0, xp_tiles = 0;
     bool gfull_valid = false;   // Gfull = T T^T of the current T (k_wsweep_rows)
     double *Gfull = nullptr, *Wsweep0 = nullptr, *wsum_part = nullptr, *wsums = nullptr;   // whole-sweep W half with T fixed: lazily allocated
+    // ... and its form for a pattern-only handle (rri_fold.h; k_wfold_rows): asked for with rri_set_fold_schedule, for the handle's
+    // life.  fold_part: per topic and workgroup the column sum, then the count of negative denominators (2 k fold_nwg doubles,
+    // allocated by the first such sweep, like Wsweep0).  tt_valid: sp_Tt holds the transpose of the handle's current T
+    bool fold_asked = false, tt_valid = false;
+    double* fold_part = nullptr;
+    long fold_launches = 0, fold_stepped = 0, fold_halts = 0;   // sweeps as one launch; sweeps launch by launch while asked; halts in a launch
     double *Y2part = nullptr, *Z2part = nullptr, *dtv = nullptr, *dwv = nullptr, *wold = nullptr, *zeros = nullptr;  // weighted
     i64 ldw = 0;     // row stride of the k-major W (>= n)
     int nsplit = 4;  // column slices of k_tgram
@@ -377,6 +385,8 @@ static inline bool ro_pass_interleaved(const rri_ctx* c) { return rri::ro_pass_i
 // builds the copy anew.  keep_q is NOT recomputed at that moment (it is set where the copy is decided, xpack_ensure): single topic
 // steps between a new X and the next sweep read the fp32 X with the kept row-block count of the 3.5-byte blocks, about 14 % more
 // kept bytes than the budget of pass_keep -- a cache policy, no bit of any result -- until that sweep recomputes it.
+// (tt_valid -- sp_Tt holds the transpose of the current T, for the one-launch fold sweep of a pattern-only handle -- was computed
+// from T alone and goes wherever gfull_valid goes; the borrowers of sp_Tt that write another matrix into it drop it themselves.)
 // Coarser than the table on purpose: any change from outside the schedule drops the first four rows together, and a new X drops
 // Gfull as well.  A narrower rule would move where an fp32 residual is rebuilt, and with it the low bits of a run.
 enum : unsigned {
@@ -408,7 +418,7 @@ static void changed(rri_ctx* c, unsigned what) {
     if (what & CH_T_ROW) { c->carry_valid = false; c->xy_valid = false; }
     if ((what & (CH_T_ROW | CH_W_COL)) && !(what & CH_E_FOLLOWS)) c->resid_valid = false;
     if (what & (CH_T_ROW | CH_W_COL | CH_PENALTY)) c->obj_track_valid = false;
-    if (what & (CH_X | CH_T | CH_T_ROW)) { c->q_valid = false; c->gfull_valid = false; }
+    if (what & (CH_X | CH_T | CH_T_ROW)) { c->q_valid = false; c->gfull_valid = false; c->tt_valid = false; }
     if (what & CH_X) { c->x_sq_valid = false; c->xp_valid = false; c->xn_valid = false; c->xp_done = false; }
     if (what & CH_ENDED) c->pending_wcheck = false;
 }
@@ -958,6 +968,7 @@ struct LaunchX {
     }
     static void spx_xtt(rri_ctx* c, const double* Tm, int m, double* out) {   // out (m x n) = (X Tm^T)^T on the CSR
         const i64 total = (i64)m * c->d;
+        c->tt_valid = false;      // sp_Tt is borrowed for the transpose of Tm
         hipLaunchKernelGGL((k_convert2d<double, double, true>), dim3((unsigned)std::min<i64>(4096, (total + 255) / 256)),
                            dim3(256), 0, c->stream, Tm, c->LD, c->sp_Tt, (i64)c->kp, (i64)m, c->d);
         hipLaunchKernelGGL((k_spx_xtt<SX>), dim3((unsigned)((c->n + 3) / 4)), dim3(256), 0, c->stream,
@@ -1020,6 +1031,19 @@ struct LaunchX {
             for (int w = 0; w < 2; ++w)
                 hipLaunchKernelGGL((k_sp_permute<SX>), dim3(2048), dim3(256), 0, c->stream, (const SX*)c->sp_e,
                                    (const int*)c->sp[w].perm, c->sp[w].count, (SX*)c->sp[w].val);
+    }
+    // k_wfold_rows over the canonical CSR: topics [t0, k) of every row, nwg = ceil(n / FOLD_ROWS) workgroups; false: the opt-in to
+    // its dynamic LDS was refused
+    static bool wfold(rri_ctx* c, int t0, int nwg) {
+        return pick_int<1, 2, 3, 4>(fold_kt(c->k), [&](auto kt) {
+            constexpr int KT = kt;
+            if (allow_lds<k_wfold_rows<SX, KT>>(c, (int)FOLD_LDS_LIMIT) != hipSuccess) return false;
+            hipLaunchKernelGGL((k_wfold_rows<SX, KT>), dim3((unsigned)nwg), dim3(64 * FOLD_WAVES), wfold_lds_bytes(c->k, FOLD_ROWS), c->stream,
+                               c->W, c->Wsweep0, c->ldw, (int)c->n, c->k, t0, (const i64*)c->sp_rowptr, (const int*)c->sp_col,
+                               (const SX*)c->sp_x, (const double*)c->sp_Tt, c->kp, c->fold_part, c->fold_part + (size_t)c->k * nwg, nwg,
+                               kparams(c), (const DevState*)c->st);
+            return true;
+        });
     }
     // 0/1 masks are bit-packed (32 columns per word): the mask then costs 1/32 of its fp32 bytes per pass
     static rri_status pack_mask_if_binary(rri_ctx* c) {
@@ -2048,9 +2072,41 @@ void calibrate_rot(rri_ctx* c) {
 // ---- T fixed: the W half of all topics of a sweep as one launch (k_wsweep_rows) ---------------------------------------
 // k <= 256: k_wsweep_verdict keeps one column sum per topic in ssum[256].  The LDS bound is the tighter one today (k <= 109);
 // the explicit term keeps the verdict's array safe if that bound ever moves.
+// ... or, on a pattern-only handle that asked for it (rri_set_fold_schedule), k_wfold_rows: q and G per row from the row's own
+// observed entries (wfold_ok of rri_fold.hpp)
+bool wfold_sched(const rri_ctx* c) {
+    return wfold_ok(c->fold_asked, c->weighted != 0, c->sparse, c->sparse_x, c->prm.fix_T != 0, c->prm.fix_W != 0, c->comm != nullptr, c->k);
+}
 bool wsweep_ok(const rri_ctx* c) {
+    if (wfold_sched(c)) return true;
     return c->sw.wsweep && c->prm.fix_T && !c->prm.fix_W && !c->weighted && (!c->sparse || c->sparse_x) && c->k >= 1 &&
            c->k <= 256 && wsweep_lds_bytes(c->k) <= 150 * 1024;
+}
+// The launches of the fold sweep: sp_Tt once per T, k_wfold_rows, the verdicts in topic order, the repair.  What the launch
+// leaves behind is announced by its caller, enqueue_wsweep.  false: a buffer or the LDS opt-in could not be had
+bool launch_wfold(rri_ctx* c, int sweep, int t0) {
+    const int k = c->k;
+    const size_t f8 = sizeof(double);
+    const int nwg = (int)((c->n + FOLD_ROWS - 1) / FOLD_ROWS);
+    if (dev_ensure(c, c->Wsweep0, (size_t)k * c->ldw * f8) != hipSuccess || dev_ensure(c, c->fold_part, (size_t)2 * k * nwg * f8) != hipSuccess)
+        return false;
+    flush_wcheck(c, sweep, t0);     // (a column check left by steps before T was fixed)
+    if (!c->tt_valid) {          // T transposed: once per T, reused by every sweep
+        const i64 total = (i64)k * c->d;
+        hipLaunchKernelGGL((k_convert2d<double, double, true>), dim3((unsigned)std::min<i64>(4096, (total + 255) / 256)), dim3(256), 0, c->stream,
+                           (const double*)c->T, c->LD, c->sp_Tt, (i64)c->kp, (i64)k, c->d);
+        c->tt_valid = true;
+    }
+    TimedScope ts(c, 1);
+    bool ok = false;
+    DISPATCH(c, ok = L::wfold(c, t0, nwg));
+    if (!ok) return false;
+    hipLaunchKernelGGL(k_wfold_verdict, dim3(1), dim3(1024), 0, c->stream, (const double*)c->fold_part,
+                       (const double*)(c->fold_part + (size_t)k * nwg), nwg, k, t0, sweep, kparams(c), c->st);
+    hipLaunchKernelGGL(k_wsweep_repair, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream, c->W, (const double*)c->Wsweep0,
+                       c->ldw, (int)c->n, k, (const DevState*)c->st);
+    c->fold_launches += 1;
+    return true;
 }
 // k_wsweep_rows leaves one column-sum partial and one cross-term partial per 64 rows (c->nwb of them), the count that
 // note_xy(c, t, nwb * WCOL_TILES) and k_wsweep_verdict read back: that holds only with one 64-row tile per k_wcol block
@@ -2059,6 +2115,15 @@ static_assert(WCOL_TILES == 1, "enqueue_wsweep assumes one 64-row tile per k_wco
 bool enqueue_wsweep(rri_ctx* c, int sweep, int t0) {
     const int k = c->k;
     const size_t f8 = sizeof(double);
+    if (wfold_sched(c)) {
+        // a pattern-only handle: W changed and neither copy of the stored residual followed it, so the next objective or free
+        // sweep rebuilds E (w_refresh); no carry, no column verdict owed
+        if (!launch_wfold(c, sweep, t0)) return false;
+        c->skip_row_finish = false;
+        c->carry_valid = false;
+        changed(c, CH_W_COL);
+        return true;
+    }
     if (dev_ensure(c, c->Gfull, (size_t)k * k * f8) != hipSuccess || dev_ensure(c, c->Wsweep0, (size_t)k * c->ldw * f8) != hipSuccess ||
         dev_ensure(c, c->wsum_part, (size_t)k * c->nwb * f8) != hipSuccess || dev_ensure(c, c->wsums, (size_t)k * f8) != hipSuccess)
         return false;
@@ -2233,6 +2298,8 @@ void enqueue_range(rri_ctx* c, Cursor cur, int s_end) {
         for (int s = cur.sweep; s < s_end; ++s) {
             const int t0 = (s == cur.sweep) ? cur.topic : 0;
             const int sa = s;
+            if (wsweep_ok(c) && enqueue_wsweep(c, sa, t0)) continue;      // pattern-only, T fixed, asked for: the W half of every topic in one launch
+            if (c->fold_asked) c->fold_stepped += 1;
             for (int t = t0; t < k; ++t) {
                 const int ph = (s == cur.sweep && t == cur.topic) ? cur.phase : 0;
                 // once per sweep (and after resets), unless rri_objective has just rebuilt it from the same W, T
@@ -3174,6 +3241,11 @@ static rri_status run_and_collect(rri_ctx* c, Cursor from, int32_t* sweeps_done)
     }
     c->obj_track_pending = false;
     c->onchip_in_flight = false;
+    if (s.halt != 0 && s.pad1 == 1) {     // k_wfold_verdict halted the queue: the fold launches enqueued behind that sweep returned at once
+        const int at = s.halt_pos == 0 ? s.halt_sweep - 1 : s.halt_sweep;
+        c->fold_halts += 1;
+        c->fold_launches -= std::max(0, c->run_total - 1 - at);
+    }
     return status_from_halt(c, s, sweeps_done);
 }
 
@@ -6142,6 +6214,30 @@ rri_status rri_onchip_info(rri_ctx* c, int32_t* eligible, int64_t* launches) {
     CHECK_CTX(c);
     if (eligible) *eligible = (c->have_X && c->have_params && onchip_ok(c)) ? 1 : 0;
     if (launches) *launches = c->onchip_launches;
+    return RRI_OK;
+}
+
+// ---- include/rri_fold.h: the one-launch fold sweep of a pattern-only handle, per handle and opt-in ------------------------------
+// Remembered for the handle's life; nothing the handle keeps between calls was computed from it, so no cached state is touched:
+// the next sweep simply takes the schedule wsweep_ok finds.
+rri_status rri_set_fold_schedule(rri_ctx* c, int on) {
+    const char* why = nullptr;
+    if (fold_check_args(c != nullptr, c && c->weighted && c->sparse && !c->sparse_x, true, &why) != 0) return fail(c, RRI_ERR_INVALID, "rri_set_fold_schedule: %s", why);
+    c->fold_asked = on != 0;
+    return RRI_OK;
+}
+
+rri_status rri_fold_info(const rri_ctx* c, int64_t out[6]) {
+    const char* why = nullptr;
+    if (fold_check_args(c != nullptr, c && c->weighted && c->sparse && !c->sparse_x, out != nullptr, &why) != 0) {
+        return fail(const_cast<rri_ctx*>(c), RRI_ERR_INVALID, "rri_fold_info: %s", why);     // (the error text is no state of the run)
+    }
+    out[0] = c->fold_asked ? 1 : 0;
+    out[1] = (c->have_params && wfold_sched(c)) ? 1 : 0;
+    out[2] = c->fold_launches;
+    out[3] = c->fold_stepped;
+    out[4] = c->fold_halts;
+    out[5] = FOLD_ROWS;
     return RRI_OK;
 }
 

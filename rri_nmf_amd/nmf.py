@@ -69,6 +69,7 @@ import scipy.sparse
 
 from .corpus_fit import entries_error, upload_observed_corpus
 from .engine import DeviceCorpus, FrozenRows, RRIEngine, ZeroTotalRows
+from .fold import fold_info, set_fold_schedule
 from .initialization import _KNOWN as _KNOWN_INITS, initialize_nmf
 from .matrixops import normalize, proj_mat_to_simplex
 from .optimization import universal_stopping_condition
@@ -610,6 +611,20 @@ def _check_corpus_call(X, sparse_X, W_mat, w_row, group, schedule, dtype, diagno
     X._ptr()        # a closed corpus: ValueError
 
 
+def _check_fold_in_call(fix_T, observed_only, sparse_pattern, group, resident):
+    """nmf(..., fold_in=True): the one-launch fold sweep belongs to runs with T fixed on a pattern-only handle on one device; whatever
+    would end on another handle is refused before any device call"""
+    if not fix_T:
+        raise ValueError('fold_in=True folds rows in against a fixed T: pass fix_T=True and T_in')
+    if not observed_only and sparse_pattern is not True:
+        raise ValueError('fold_in=True runs on a pattern-only handle: pass a DeviceCorpus with observed_only=True, or scipy sparse X '
+                         'and W_mat with sparse_pattern=True')
+    if group is not None:
+        raise ValueError('fold_in=True runs on one device: it does not combine with group=')
+    if resident is not None:
+        raise ValueError('fold_in=True asks the handle for its life: it does not combine with resident=, whose handle later calls reuse')
+
+
 def _sentinel(W, T):
     return {'W': W, 'T': T, 'obj_history': [-np.inf], 'iter_cputime': [0]}
 
@@ -626,7 +641,7 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
         diagnostics=[], store_gradients=False,
         ind_rows_to_store=None, eps_gauss_t=None, delta_gauss_t=None,
         *, dtype=None, device=0, device_init=None, sparse_pattern=None, preprocess=None, schedule='gram', group=None,
-        resident=None, frozen=None, sparse_X=None, uniform_rows=None, observed_only=False):
+        resident=None, frozen=None, sparse_X=None, uniform_rows=None, observed_only=False, fold_in=False):
     """Non-negative factorisation X ~ W T by rank-one residue iteration; see the module docstring and
     the reference's docstring (nmf.py:109-269) for the parameters.  Returns a dict with 'W', 'T',
     'iter_cputime' (wall seconds since the start, per sweep), 'random_state' and, when the objective
@@ -648,8 +663,13 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
     the final projection of W, this batch's rows are absorbed with the W they have then, and the sum comes back as
     rtv['frozen'].  True: no rows are frozen yet -- nothing is set, the sweeps are those of a call without the option, the
     batch is absorbed all the same (the first batch of an online fit).  Unweighted calls in the Gram form with float32 /
-    float64 or CSR storage on one device; no fix_W, w_row, early_stop, store_gradients or Gaussian mechanism."""
+    float64 or CSR storage on one device; no fix_W, w_row, early_stop, store_gradients or Gaussian mechanism.
+    fold_in (keyword only): True asks the call's pattern-only handle for the one-launch W half of sweeps with T fixed (fold.py,
+    include/rri_fold.h): fix_T must be set and the call must end on such a handle -- observed_only=True with a DeviceCorpus, or a
+    host CSR with sparse_pattern=True.  A rank above 64 is not refused: it runs launch by launch."""
     corpus = isinstance(X, DeviceCorpus)
+    if fold_in:
+        _check_fold_in_call(fix_T, observed_only, sparse_pattern, group, resident)
     if observed_only:
         _check_observed_only_call(X, sparse_X, sparse_pattern, W_mat, preprocess, uniform_rows, frozen, resident, w_row, group,
                                   schedule, dtype, diagnostics, store_gradients, early_stop, eps_gauss_t and delta_gauss_t, init,
@@ -876,6 +896,8 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
                                    sparse_X if device_spec is None or csr_route is None else csr_route, observed_only=observed_only)
     keep_handle = False
     try:
+        if fold_in:
+            set_fold_schedule(eng)      # (another flavour of handle: ValueError, the library's text)
         if group is not None:
             eng.attach_group(group)
         on_device = device_init if device_init is not None else (float(n) * d >= DEVICE_INIT_MIN_ELEMS)
@@ -1068,6 +1090,8 @@ def nmf(X, k, w_row=None, W_mat=None, fix_W=False, fix_T=False,
 
         W, T = current()
         n_resets_used = eng.n_resets_used
+        if fold_in:
+            rtv['fold_info'] = fold_info(eng)       # how the sweeps were taken: as one launch each, or launch by launch (k > 64)
         if half or counts:
             rtv['x_storage_relerr'] = eng.storage_relerr
         keep_handle = resident is not None and resident.engine is eng

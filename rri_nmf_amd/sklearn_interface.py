@@ -195,15 +195,19 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
             self.seen_ = seen
         return self
 
-    def score_corpus(self, corpus):
+    def score_corpus(self, corpus, W=None):
         """RMSE of the clipped reconstruction on the stored entries of a DeviceCorpus, scored on the device where the corpus lies
         (rri_corpus_entries_error on a factors-only handle): what score(corpus.to_scipy()) returns, to rounding, without the
-        download."""
+        download.  W: the rows of folded users (transform_corpus), m x k, scored with the fitted T against a corpus of m x d; None:
+        the fitted W."""
         from .corpus_fit import entries_error
-        if np.ndim(self.W) != 2 or np.ndim(self.T) != 2:
+        if np.ndim(self.T) != 2 or (W is None and np.ndim(self.W) != 2):
             raise ValueError('the estimator is not fitted: it has no W and T')
-        W = self.W.toarray() if sp.issparse(self.W) else np.asarray(self.W)
         T = self.T.toarray() if sp.issparse(self.T) else np.asarray(self.T)
+        if W is None:
+            W = self.W.toarray() if sp.issparse(self.W) else np.asarray(self.W)
+        else:
+            W = self._folded_rows(W, T, (('corpus', corpus),))
         eng = RRIEngine(W.shape[0], T.shape[1], W.shape[1], dtype=np.float64, weighted=False, device=self.nmf_kwargs.get('device', 0))
         try:        # factors only: such a handle holds nothing of size n x d
             eng.set_W(W)
@@ -212,15 +216,30 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
         finally:
             eng.close()
 
-    def _factors_engine(self, corpora):
-        """a factors-only handle holding the fitted W and T (nothing of size n x d), after the corpora have been checked"""
-        if np.ndim(self.W) != 2 or np.ndim(self.T) != 2:
+    @staticmethod
+    def _folded_rows(W, T, corpora):
+        """the W of folded users as a float64 (m, k) array beside the fitted T; the corpora given with it must be m x d"""
+        W = np.asarray(W.toarray() if sp.issparse(W) else W, dtype=np.float64)
+        if W.ndim != 2 or W.shape[1] != T.shape[0]:
+            raise ValueError('W must be an (m, %d) array of folded rows, not of shape %s' % (T.shape[0], W.shape))
+        for what, c in corpora:
+            if isinstance(c, DeviceCorpus) and tuple(c.shape) != (W.shape[0], T.shape[1]):
+                raise ValueError('with W of %d rows, %s must be a DeviceCorpus of shape %d x %d' % (W.shape[0], what, W.shape[0], T.shape[1]))
+        return W
+
+    def _factors_engine(self, corpora, W=None):
+        """a factors-only handle holding the fitted W -- or the (m, k) rows of folded users given as W -- and the fitted T (nothing of
+        size n x d), after the corpora have been checked"""
+        if np.ndim(self.T) != 2 or (W is None and np.ndim(self.W) != 2):
             raise ValueError('the estimator is not fitted: it has no W and T')
         for what, c in corpora:
             if c is not None and not isinstance(c, DeviceCorpus):
                 raise TypeError('%s must be a DeviceCorpus, not %s' % (what, type(c).__name__))
-        W = self.W.toarray() if sp.issparse(self.W) else np.asarray(self.W)       # sparsify() was called: dense copies
         T = self.T.toarray() if sp.issparse(self.T) else np.asarray(self.T)
+        if W is None:
+            W = self.W.toarray() if sp.issparse(self.W) else np.asarray(self.W)       # sparsify() was called: dense copies
+        else:
+            W = self._folded_rows(W, T, corpora)
         eng = RRIEngine(W.shape[0], T.shape[1], W.shape[1], dtype=np.float64, weighted=False, device=self.nmf_kwargs.get('device', 0))
         try:
             eng.set_W(W)
@@ -230,14 +249,15 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
             raise
         return eng
 
-    def recommend_corpus(self, users=None, n_items=10, exclude=None):
+    def recommend_corpus(self, users=None, n_items=10, exclude=None, W=None):
         """`recommend` against a resident exclusion: the n_items best items for each of `users` (row indices, any order, duplicates
         allowed; None: every user), leaving out for user i the stored entries of row i of `exclude` -- a DeviceCorpus of the
         estimator's shape, typically the corpus split_entries was called on (train and held-out together), or None --, read where
         it lies (rri_corpus_topn_rows): no seen_, no copy of the excluded pairs on the host.  (items int32 (m, n_items), scores
-        float64 (m, n_items)), the items and scores `recommend` returns when seen_ is that corpus's pattern."""
+        float64 (m, n_items)), the items and scores `recommend` returns when seen_ is that corpus's pattern.  W: the (m, k) rows of
+        folded users (transform_corpus) instead of the fitted W: `users` index those rows and `exclude` is then m x d."""
         from .corpus_rank import topn_rows
-        eng = self._factors_engine((('exclude', exclude),))
+        eng = self._factors_engine((('exclude', exclude),), W)
         try:
             n = eng.n
             users = np.arange(n, dtype=np.int64) if users is None else np.asarray(users, dtype=np.int64).reshape(-1)
@@ -254,13 +274,14 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
             eng.close()
         return items, scores
 
-    def rank_corpus(self, targets, exclude=None):
+    def rank_corpus(self, targets, exclude=None, W=None):
         """`rank` for pairs that are resident: the place of every stored entry (user i, item j) of the DeviceCorpus `targets` (the
         estimator's shape) among user i's items, counted on the device where the corpus lies (rri_corpus_rank_entries): (rank int32
         per canonical entry in corpus order, eligible int32 per row; -1 for a user without entries, who is not scored).  `exclude`
-        as in recommend_corpus; an entry that is itself excluded, or whose prediction is NaN, gets rank -1."""
+        as in recommend_corpus; an entry that is itself excluded, or whose prediction is NaN, gets rank -1.  W as in recommend_corpus:
+        the corpora are then m x d."""
         from .corpus_rank import rank_entries
-        eng = self._factors_engine((('targets', targets), ('exclude', exclude)))
+        eng = self._factors_engine((('targets', targets), ('exclude', exclude)), W)
         try:
             if targets is None or tuple(targets.shape) != (eng.n, eng.d):
                 raise ValueError('targets must be a DeviceCorpus of shape %d x %d' % (eng.n, eng.d))
@@ -269,16 +290,16 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
             eng.close()
         return res['rank'], res['eligible']
 
-    def ranking_score_corpus(self, targets, n_items=10, exclude=None, relevant_from=None):
+    def ranking_score_corpus(self, targets, n_items=10, exclude=None, relevant_from=None, W=None):
         """`ranking_score` for pairs that are resident: the same dict, formula for formula, over the stored entries of the
         DeviceCorpus `targets` whose value is at least relevant_from (None: all), ranked and summed on the device
         (rri_corpus_ranking_metrics): a dozen doubles come back, not one rank per pair, and neither the corpus nor seen_ is
-        downloaded.  `exclude` as in recommend_corpus.  The metrics agree with ranking_score's to the order of the sums."""
+        downloaded.  `exclude` and W as in recommend_corpus.  The metrics agree with ranking_score's to the order of the sums."""
         from .corpus_rank import ranking_metrics
         n_items = int(n_items)
         if n_items < 1:
             raise ValueError('n_items must be a positive integer, not %d' % n_items)
-        eng = self._factors_engine((('targets', targets), ('exclude', exclude)))
+        eng = self._factors_engine((('targets', targets), ('exclude', exclude)), W)
         try:
             if targets is None or tuple(targets.shape) != (eng.n, eng.d):
                 raise ValueError('targets must be a DeviceCorpus of shape %d x %d' % (eng.n, eng.d))
@@ -286,8 +307,27 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
         finally:
             eng.close()
 
+    def transform_corpus(self, new):
+        """`transform` for ratings that are resident: `new` is a DeviceCorpus of m x d (any m) whose stored entries are the new
+        users' ratings, and nothing of its size visits the host.  The solver runs nmf(new, k, observed_only=True, fold_in=True, ...)
+        with the options of `transform`: four sweeps with T fixed on a pattern-only handle whose store is built on the device, each
+        sweep's W half one launch (include/rri_fold.h; k <= 64, a larger rank runs launch by launch).  Returns W_new (m x k), which
+        recommend_corpus, rank_corpus, ranking_score_corpus and score_corpus take as W=."""
+        if not isinstance(new, DeviceCorpus):
+            raise TypeError('transform_corpus takes a DeviceCorpus, not %s: for matrices there is transform' % type(new).__name__)
+        if np.ndim(self.T) != 2:
+            raise ValueError('the estimator is not fitted: it has no T')
+        if new.shape[1] != self.d:
+            raise ValueError('the corpus has %d columns, the estimator %d' % (new.shape[1], self.d))
+        T = self.T.toarray() if sp.issparse(self.T) else self.T
+        soln = _nmf(new, self.k, max_iter=4, max_time=7200, project_W_each_iter=False,
+                    project_T_each_iter=False, observed_only=True, fold_in=True, T_in=T, fix_T=True,
+                    reg_w_l1=self.wr1, reg_t_l1=self.tr1, t_row_sum=1.0, w_row_sum=None,
+                    reset_topic_method='random', random_state=self.random_state, **self.nmf_kwargs)
+        return soln['W']
+
     def transform(self, Xnew):
-        """fold new rows in against the fitted T"""
+        """fold new rows in against the fitted T (transform_corpus: the same from a DeviceCorpus, one launch per sweep)"""
         soln = _nmf(Xnew, self.k, max_iter=4, max_time=7200, project_W_each_iter=False,
                     project_T_each_iter=False, W_mat=_observed_mask(Xnew), T_in=self.T, fix_T=True,
                     reg_w_l1=self.wr1, reg_t_l1=self.tr1, t_row_sum=1.0, w_row_sum=None,
