@@ -194,6 +194,12 @@ FOLD_PROTOTYPES = {
     'rri_fold_info': (_I32, [_P, C.POINTER(_I64)]),
 }
 
+# ... and the symbol include/rri_corpus_rowsplit.h declares: the split of a corpus that holds out an exact number of entries of every
+# row.  Like the split by entry it keeps and touches none of a handle's cached state
+CORPUS_ROWSPLIT_PROTOTYPES = {
+    'rri_corpus_split_rows': (_I32, [_P, _P, _I64, _D, _I64, C.c_uint64, C.POINTER(_P), C.POINTER(_P)]),
+}
+
 _lib = None
 
 
@@ -255,7 +261,8 @@ def load_library(path=None):
     except OSError as e:  # e.g. libamdhip64 missing
         raise RRIHipUnavailable('cannot load %s: %s' % (p, e))
     for name, (res, args) in list(PROTOTYPES.items()) + list(CORPUS_OPS_PROTOTYPES.items()) + list(CORPUS_BUILD_PROTOTYPES.items()) + \
-            list(CORPUS_FIT_PROTOTYPES.items()) + list(CORPUS_RANK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()):
+            list(CORPUS_FIT_PROTOTYPES.items()) + list(CORPUS_RANK_PROTOTYPES.items()) + list(FOLD_PROTOTYPES.items()) + \
+            list(CORPUS_ROWSPLIT_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

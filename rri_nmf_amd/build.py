@@ -16,7 +16,8 @@ SRC = os.path.join(PKG, 'csrc', 'rri_hip.hip')
 DEPS = [SRC] + sorted(os.path.join(PKG, 'csrc', f) for f in os.listdir(os.path.join(PKG, 'csrc')) if f.endswith('.hpp')) + \
     [os.path.join(ROOT, 'include', 'rri_hip.h'), os.path.join(ROOT, 'include', 'rri_corpus_ops.h'),
      os.path.join(ROOT, 'include', 'rri_corpus_build.h'), os.path.join(ROOT, 'include', 'rri_corpus_fit.h'),
-     os.path.join(ROOT, 'include', 'rri_corpus_rank.h'), os.path.join(ROOT, 'include', 'rri_fold.h')]
+     os.path.join(ROOT, 'include', 'rri_corpus_rank.h'), os.path.join(ROOT, 'include', 'rri_fold.h'),
+     os.path.join(ROOT, 'include', 'rri_corpus_rowsplit.h')]
 LIB = os.path.join(PKG, 'lib', 'librri_hip.so')
 
 

@@ -58,6 +58,8 @@
 #include "rri_corpus_rank_kernels.hpp"
 #include "rri_fold.h"
 #include "rri_fold_kernels.hpp"
+#include "rri_corpus_rowsplit.h"
+#include "rri_rowsplit_kernels.hpp"
 
 using namespace rri;
 
@@ -4748,6 +4750,112 @@ rri_status rri_corpus_split_entries(rri_ctx* c, const rri_corpus* k, uint32_t th
         hipLaunchKernelGGL(k_entries_write, dim3(derive_grid(np)), dim3(256), 0, c->stream, (const i64*)trow.p, (const i64*)tsrc.p,
                            (const int*)tlen.p, (const i64*)toh.p, (const i64*)too.p, np, (const int*)k->indices, (const double*)k->values,
                            (unsigned)thr, (u64)seed, (int*)hidx.p, (double*)hval.p, (int*)oidx.p, (double*)oval.p, (u64*)tstat.p);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(ev[1].b, c->stream));
+    u64 h_stat[DERIVE_STAT_WORDS];
+    HIPCHK(c, hipMemcpyAsync(h_stat, tstat.p, sizeof h_stat, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double ms = 0.0;
+    for (EventPair& p : ev) {
+        float t = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&t, p.a, p.b));
+        ms += t;
+    }
+    *observed = corpus_adopt(c->device, k->n_rows, k->n_cols, nnz_o, (i64)h_stat[ENTRIES_STAT_NEG_OBS], optr, oidx, oval, std::move(h_optr), ms);
+    *held = corpus_adopt(c->device, k->n_rows, k->n_cols, nnz_h, (i64)h_stat[ENTRIES_STAT_NEG_HELD], hptr, hidx, hval, std::move(h_hptr), ms);
+    return RRI_OK;
+}
+
+// the split by row (rri_rowsplit.hpp has the semantics, rri_rowsplit_kernels.hpp the kernels): the quotas and the bounds of the rows
+// that give up nothing or everything on the host, the other bounds by class, then the count and write of the split by entry
+rri_status rri_corpus_split_rows(rri_ctx* c, const rri_corpus* k, int64_t n_held, double fraction, int64_t min_observed, uint64_t seed,
+                                 rri_corpus** observed, rri_corpus** held) {
+    CHECK_CTX(c);
+    if (observed) *observed = nullptr;
+    if (held) *held = nullptr;
+    char why[200] = "";
+    if (!observed || !held) return rowsplit_check_request(n_held, fraction, min_observed, observed != nullptr, held != nullptr, why, sizeof why), fail(c, RRI_ERR_INVALID, "%s", why);
+    CHECK_DERIVE_CORPUS(c, k);
+    if (rowsplit_check_request(n_held, fraction, min_observed, true, true, why, sizeof why) != TOPN_REQ_OK) return fail(c, RRI_ERR_INVALID, "%s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    // 1. the quotas; the rows whose bound must be looked for, by class
+    std::vector<uint64_t> h_bound((size_t)k->n_rows, ROWSPLIT_BOUND_NONE);
+    std::vector<int64_t> list, quota, list_block, quota_block;
+    for (i64 r = 0; r < k->n_rows; ++r) {
+        const i64 L = k->h_indptr[(size_t)r + 1] - k->h_indptr[(size_t)r], h = rowsplit_quota(L, n_held, fraction, min_observed);
+        const int cls = rowsplit_class(L, h);
+        if (cls == ROWSPLIT_CLASS_NONE) {
+            if (h > 0) h_bound[(size_t)r] = ROWSPLIT_BOUND_ALL;           // h == L > 0
+        } else {
+            (cls == ROWSPLIT_CLASS_WAVE ? list : list_block).push_back(r);
+            (cls == ROWSPLIT_CLASS_WAVE ? quota : quota_block).push_back(h);
+        }
+    }
+    const i64 n_wave = (i64)list.size(), n_block = (i64)list_block.size();
+    list.insert(list.end(), list_block.begin(), list_block.end());
+    quota.insert(quota.end(), quota_block.begin(), quota_block.end());
+    const DerivePieces pieces = derive_cut_pieces(k->h_indptr.data(), k->n_rows, nullptr, 0);
+    const i64 np = (i64)pieces.row.size();
+    DevTmp tstat, tbound, tlist, tquota, trow, tsrc, tlen, tnh, toh, too, hptr, hidx, hval, optr, oidx, oval;
+    EventPair ev[2];
+    for (EventPair& p : ev) HIPCHK(c, p.create());
+    HIPCHK(c, tstat.alloc(DERIVE_STAT_WORDS * sizeof(u64)));
+    HIPCHK(c, hipMemsetAsync(tstat.p, 0, DERIVE_STAT_WORDS * sizeof(u64), c->stream));
+    HIPCHK(c, derive_upload(tbound, h_bound, c->stream));
+    HIPCHK(c, derive_upload(tlist, list, c->stream));
+    HIPCHK(c, derive_upload(tquota, quota, c->stream));
+    HIPCHK(c, derive_upload(trow, pieces.row, c->stream));
+    HIPCHK(c, derive_upload(tsrc, pieces.src, c->stream));
+    HIPCHK(c, derive_upload(tlen, pieces.len, c->stream));
+    HIPCHK(c, tnh.alloc(at_least((size_t)np * sizeof(int))));
+    std::vector<int> nh((size_t)np), no((size_t)np);
+    // 2. the bounds, then pass A: what every piece holds out
+    HIPCHK(c, hipEventRecord(ev[0].a, c->stream));
+    if (n_wave > 0) {
+        hipLaunchKernelGGL(k_rowsplit_select_wave, dim3(derive_grid(n_wave)), dim3(256), 0, c->stream, (const i64*)tlist.p, (const i64*)tquota.p,
+                           n_wave, (const i64*)k->indptr, (const int*)k->indices, (u64)seed, (u64*)tbound.p);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (n_block > 0) {
+        hipLaunchKernelGGL(k_rowsplit_select_block, dim3((unsigned)std::min<i64>(n_block, 1 << 20)), dim3(ROWSPLIT_BLOCK_THREADS), 0, c->stream,
+                           (const i64*)tlist.p + n_wave, (const i64*)tquota.p + n_wave, n_block, (const i64*)k->indptr, (const int*)k->indices,
+                           (u64)seed, (u64*)tbound.p);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (np > 0) {
+        hipLaunchKernelGGL(k_rowsplit_count, dim3(derive_grid(np)), dim3(256), 0, c->stream, (const i64*)trow.p, (const i64*)tsrc.p,
+                           (const int*)tlen.p, np, (const int*)k->indices, (const u64*)tbound.p, (u64)seed, (int*)tnh.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(nh.data(), tnh.p, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipEventRecord(ev[0].b, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (i64 p = 0; p < np; ++p) no[(size_t)p] = pieces.len[(size_t)p] - nh[(size_t)p];
+    // 3. the prefix sums on the host, then pass B writes both outputs once
+    std::vector<int64_t> piece_oh, piece_oo, h_hptr, h_optr;
+    derive_offsets(pieces, nh, k->n_rows, &piece_oh, &h_hptr);
+    derive_offsets(pieces, no, k->n_rows, &piece_oo, &h_optr);
+    const i64 nnz_h = h_hptr[(size_t)k->n_rows], nnz_o = h_optr[(size_t)k->n_rows];
+    for (i64 r = 0; r < k->n_rows; ++r) {       // every row gave up its quota, or a selection went wrong: nothing is written then
+        const i64 L = k->h_indptr[(size_t)r + 1] - k->h_indptr[(size_t)r], got = h_hptr[(size_t)r + 1] - h_hptr[(size_t)r];
+        if (got != rowsplit_quota(L, n_held, fraction, min_observed))
+            return fail(c, RRI_ERR_HIP, "row %lld holds %lld entries out, not its quota of %lld", (long long)r, (long long)got,
+                        (long long)rowsplit_quota(L, n_held, fraction, min_observed));
+    }
+    HIPCHK(c, derive_upload(toh, piece_oh, c->stream));
+    HIPCHK(c, derive_upload(too, piece_oo, c->stream));
+    HIPCHK(c, derive_upload(hptr, h_hptr, c->stream));
+    HIPCHK(c, derive_upload(optr, h_optr, c->stream));
+    HIPCHK(c, hidx.alloc(at_least((size_t)nnz_h * sizeof(int))));
+    HIPCHK(c, hval.alloc(at_least((size_t)nnz_h * sizeof(double))));
+    HIPCHK(c, oidx.alloc(at_least((size_t)nnz_o * sizeof(int))));
+    HIPCHK(c, oval.alloc(at_least((size_t)nnz_o * sizeof(double))));
+    HIPCHK(c, hipEventRecord(ev[1].a, c->stream));
+    if (np > 0) {
+        hipLaunchKernelGGL(k_rowsplit_write, dim3(derive_grid(np)), dim3(256), 0, c->stream, (const i64*)trow.p, (const i64*)tsrc.p,
+                           (const int*)tlen.p, (const i64*)toh.p, (const i64*)too.p, np, (const int*)k->indices, (const double*)k->values,
+                           (const u64*)tbound.p, (u64)seed, (int*)hidx.p, (double*)hval.p, (int*)oidx.p, (double*)oval.p, (u64*)tstat.p);
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipEventRecord(ev[1].b, c->stream));

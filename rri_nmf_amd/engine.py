@@ -166,7 +166,8 @@ class DeviceCorpus(object):
     max_words) and split_counts(held_out, random_state) (include/rri_corpus_ops.h).  The two ends of that chain are on the device as
     well (include/rri_corpus_build.h): from_pairs(pairs, values) makes a corpus of (row, column, value) triples -- tokens, or a
     ratings log -- without a CSR matrix on the host, and split_entries(held_out, random_state) sends every entry, whole, to a
-    training or a held-out corpus.  value_range() is the (min, max) of the values, and the recommender fit takes a corpus where
+    training or a held-out corpus; split_rows(n_held | held_out, min_observed, random_state) holds out an exact number of entries
+    of every row instead (include/rri_corpus_rowsplit.h).  value_range() is the (min, max) of the values, and the recommender fit takes a corpus where
     it lies (include/rri_corpus_fit.h; corpus_fit.upload_observed_corpus, corpus_fit.entries_error, nmf(corpus, k,
     observed_only=True), NMF_RS_Estimator.fit_corpus)."""
 
@@ -366,6 +367,54 @@ class DeviceCorpus(object):
         observed, held = C.c_void_p(), C.c_void_p()
         with self._handle() as eng:
             eng._check(self._lib.rri_corpus_split_entries(eng._h, self._ptr(), thr, seed, C.byref(observed), C.byref(held)))
+        return DeviceCorpus._adopt(observed, self.device, self._lib), DeviceCorpus._adopt(held, self.device, self._lib)
+
+    @staticmethod
+    def _split_rows_request(n_held, held_out, min_observed):
+        """what rri_corpus_split_rows is handed for the two modes of split_rows: (n_held or -1, fraction or 0.0, min_observed);
+        ValueError / TypeError before any device call"""
+        def whole(v, what):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError('%s must be an int, not %r' % (what, v))
+            return int(v)
+        if (n_held is None) == (held_out is None):
+            raise ValueError('split_rows takes exactly one of n_held (a count per row) and held_out (a share of every row), not %s'
+                             % ('both' if n_held is not None else 'neither'))
+        min_observed = whole(min_observed, 'min_observed')
+        if not 0 <= min_observed < (1 << 63):
+            raise ValueError('min_observed must be at least 0, not %r' % (min_observed,))
+        if n_held is not None:
+            n_held = whole(n_held, 'n_held')
+            if not 1 <= n_held < (1 << 63):
+                raise ValueError('n_held must be at least 1, not %r' % (n_held,))
+            return n_held, 0.0, min_observed
+        if isinstance(held_out, (bool, np.bool_)) or not isinstance(held_out, (int, float, np.integer, np.floating)):
+            raise TypeError('held_out must be a number in (0, 1], not %r' % (held_out,))
+        if not 0.0 < float(held_out) <= 1.0:
+            raise ValueError('held_out must lie inside (0, 1], not %r' % (held_out,))
+        return -1, float(held_out), min_observed
+
+    @staticmethod
+    def _split_rows_quota(lengths, n_held, fraction, min_observed):
+        """rowsplit_quota for an array of row lengths and a checked request (n_held or -1, fraction): what every row gives up"""
+        L = np.asarray(lengths, dtype=np.int64)
+        want = np.full(L.shape, n_held, dtype=np.int64) if n_held >= 1 else np.floor(fraction * L.astype(np.float64) + 0.5).astype(np.int64)
+        return np.minimum(want, np.maximum(L - min_observed, 0))
+
+    def split_rows(self, n_held=None, held_out=None, min_observed=1, random_state=0):
+        """(observed, held), two corpora on the same device: every row gives up an exact number of its entries, whole and bit for bit
+        (rri_corpus_split_rows, include/rri_corpus_rowsplit.h).  Exactly one of n_held (every row gives up n_held entries: leave-k-out)
+        and held_out (a row of L entries gives up floor(held_out L + 0.5)) is given; either way a row keeps at least min_observed
+        entries, giving up fewer -- or none -- where it is short: h = min(want, max(L - min_observed, 0)).  The entries given up are
+        those with the smallest keys (Philox word << 32 | column), the Philox word being split_entries's for (row, column,
+        random_state): for one seed the held set for h is inside that for h + 1, and where split_entries holds m entries of a row,
+        a quota of m holds the same ones.  The two patterns are disjoint and their union is this corpus's."""
+        n_held, fraction, min_observed = self._split_rows_request(n_held, held_out, min_observed)
+        seed = self._split_seed(random_state)
+        observed, held = C.c_void_p(), C.c_void_p()
+        with self._handle() as eng:
+            eng._check(self._lib.rri_corpus_split_rows(eng._h, self._ptr(), n_held, fraction, min_observed, seed, C.byref(observed),
+                                                       C.byref(held)))
         return DeviceCorpus._adopt(observed, self.device, self._lib), DeviceCorpus._adopt(held, self.device, self._lib)
 
     def _read_info(self):

@@ -326,6 +326,35 @@ class NMF_RS_Estimator(_FactorPair, sklearn.base.BaseEstimator):
                     reset_topic_method='random', random_state=self.random_state, **self.nmf_kwargs)
         return soln['W']
 
+    def ranking_score_new_users(self, new, n_items=10, n_held=None, held_out=None, min_observed=1, relevant_from=None, random_state=None):
+        """The ranking metrics of users the fit never saw (strong generalisation), end to end on the device: `new` is a DeviceCorpus
+        of m x d holding their ratings.  Every user gives up part of the ratings (new.split_rows: n_held per user, or the share
+        held_out; neither given: held_out=0.2; every user keeps at least min_observed), is folded in from the ratings kept
+        (transform_corpus), and the ratings given up are ranked among the items the user has not kept (ranking_score_corpus with
+        exclude=observed and W=the folded rows).  It is exactly that composition; random_state=None is the estimator's own.  Returns
+        the dict of ranking_score_corpus with two integer keys added: observed_entries and held_entries."""
+        if not isinstance(new, DeviceCorpus):
+            raise TypeError('ranking_score_new_users takes a DeviceCorpus, not %s' % type(new).__name__)
+        if n_held is None and held_out is None:
+            held_out = 0.2
+        DeviceCorpus._split_rows_request(n_held, held_out, min_observed)
+        if int(n_items) < 1:
+            raise ValueError('n_items must be a positive integer, not %d' % int(n_items))
+        if np.ndim(self.T) != 2:
+            raise ValueError('the estimator is not fitted: it has no T')
+        if new.shape[1] != self.d:
+            raise ValueError('the corpus has %d columns, the estimator %d' % (new.shape[1], self.d))
+        observed, held = new.split_rows(n_held=n_held, held_out=held_out, min_observed=min_observed,
+                                        random_state=self.random_state if random_state is None else random_state)
+        try:
+            W_new = self.transform_corpus(observed)
+            out = dict(self.ranking_score_corpus(held, n_items, exclude=observed, relevant_from=relevant_from, W=W_new))
+            out['observed_entries'], out['held_entries'] = int(observed.nnz), int(held.nnz)
+            return out
+        finally:
+            observed.close()
+            held.close()
+
     def transform(self, Xnew):
         """fold new rows in against the fitted T (transform_corpus: the same from a DeviceCorpus, one launch per sweep)"""
         soln = _nmf(Xnew, self.k, max_iter=4, max_time=7200, project_W_each_iter=False,
@@ -902,6 +931,42 @@ def split_entries(X, held_out=0.05, random_state=0):
     rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
     to_held = rs.random_sample(A.nnz) < held_out
     rows = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
+    parts = []
+    for take in (~to_held, to_held):
+        indptr = np.concatenate(([0], np.cumsum(np.bincount(rows[take], minlength=A.shape[0])))).astype(A.indptr.dtype)
+        parts.append(sp.csr_matrix((A.data[take], A.indices[take], indptr), shape=A.shape))
+    return parts[0], parts[1]
+
+
+def split_rows(X, n_held=None, held_out=None, min_observed=1, random_state=0):
+    """Split the stored entries of X (n x d, scipy sparse or dense) into (observed, held), two CSR matrices, row by row: every row
+    gives up an exact number of its entries, whole and with their values as they are -- leave-k-out with n_held=k, or a share of
+    every row with held_out (exactly one of the two is given).  A row of L entries gives up h = min(want, max(L - min_observed, 0))
+    of them, want being n_held or floor(held_out L + 0.5): a row keeps at least min_observed entries and gives up fewer, or none,
+    where it is short.  Duplicates are summed and explicit zeros dropped first, the patterns of the two parts are disjoint and their
+    union is X's.  ValueError for both modes or neither, n_held below 1, a held_out outside (0, 1] and a negative min_observed.
+
+    A DeviceCorpus is split where it lives: X.split_rows(n_held, held_out, min_observed, random_state) returns two corpora on its
+    device.  The quota of a row is the same function on both routes; which entries a row gives up is not: the two routes use
+    different generators -- numpy's RandomState.choice without replacement here, row after row; the h smallest keys of a
+    counter-based Philox4x32-10 keyed by (row, column) there --, so the same seed gives a different split on the two routes;
+    both choose the h entries of a row uniformly among its subsets of that size and are equally valid, and each is reproducible from
+    its seed."""
+    if isinstance(X, DeviceCorpus):
+        return X.split_rows(n_held=n_held, held_out=held_out, min_observed=min_observed, random_state=random_state)
+    n_held, fraction, min_observed = DeviceCorpus._split_rows_request(n_held, held_out, min_observed)
+    A = sp.csr_matrix(X, copy=True)
+    A.sum_duplicates()
+    A.eliminate_zeros()
+    A.sort_indices()
+    rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+    lengths = np.diff(A.indptr).astype(np.int64)
+    quota = DeviceCorpus._split_rows_quota(lengths, n_held, fraction, min_observed)
+    rows = np.repeat(np.arange(A.shape[0]), lengths)
+    to_held = np.zeros(A.nnz, dtype=bool)
+    for r in np.flatnonzero(quota > 0):          # a choice per row: linear in the entries, where a sort of all draws is not
+        lo, L, h = int(A.indptr[r]), int(lengths[r]), int(quota[r])
+        to_held[lo + rs.choice(L, size=h, replace=False) if h < L else slice(lo, lo + L)] = True
     parts = []
     for take in (~to_held, to_held):
         indptr = np.concatenate(([0], np.cumsum(np.bincount(rows[take], minlength=A.shape[0])))).astype(A.indptr.dtype)
